@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the Buddhabrot hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json `metric`): 4096x4096 canvas on [-2,2]^2, max_iter = 20000, min_iter = 20
 (config C3), synthetic seeded sample stream (rocRAND-compatible XORWOW, seed 1337).  A STEP is one
@@ -13,9 +13,18 @@ north_star prescribes ("one RCCL reduce at checkpoint/-s time").
 
 Prints ONE JSON line on rank 0.  `value` is whole-job drawn samples per second (millions) with all
 inputs (generator states, histogram) resident in HBM.  `roofline` prices the dominant (only) kernel
-against the fp64 vector-ALU peak -- there is no contraction in this path, hence no MFMA -- and
-`roofline_scatter` prices its histogram atomics against HBM; `cpu_baseline` is the oracle's OpenMP
-loop on this host's cores over a bounded sample of the same workload.
+against the fp64 vector-ALU peak -- there is no contraction in this path, hence no MFMA.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds, as before the
+clock, the legs that take launches of their own: `other_configs` (the other BASELINE.json configs),
+the draw launch and the scatter kernels alone (`roofline.alone_ms`, `roofline_scatter`) and
+`roofline_full_iterate`; after it, `reference_gpu` (the reference's own HIP build) and `cpu_baseline`
+(the oracle's OpenMP loop on this host's cores over a bounded sample of the same workload).  Each of
+them can still be switched off with its --no-* option.
+
+--dump-outputs DIR writes what the timed steps computed, as a caller of the path receives it, as
+float64 .npy files (see dump_outputs).  The inputs depend only on the arguments (seed 1337, --warmup,
+--steps, --config, --gpus): two builds run with the same arguments can be compared file for file.
 """
 
 import argparse
@@ -239,7 +248,8 @@ class Job:
         self.counters = torch.zeros(17, dtype=torch.int64, device=dev)
         self.draw_stream_t = torch.cuda.current_stream()
         self.stream = self.draw_stream_t.cuda_stream
-        cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, first, threads, self.states.data_ptr(), self.stream)
+        self.first = first
+        self.seed_generators()
         # scratch for the deferred tile-binned scatter (pixel stream + its sorted copy), ~12 GiB of 288 at C3
         self.ws_bytes = 0 if direct_atomics else cb.scatter_workspace_bytes(self.dims, threads, samples_per_thread,
                                                                             self.planes)
@@ -253,6 +263,10 @@ class Job:
         # orbits still in flight at the end of a launch are carried to the next one instead of being drained at a
         # fraction of the lanes; a launch without samples (inside the timed region) completes them
         self.carry = torch.zeros(cb.carry_bytes(threads), dtype=torch.uint8, device=dev)
+
+    def seed_generators(self):
+        """Generator subsequences [first, first + threads) of seed 1337, from their start."""
+        self.cb.initialize_rng(self.cb.CB_DEFAULT_RNG_SEED, self.first, self.threads, self.states.data_ptr(), self.stream)
 
     def draw(self, samples, k, variant=None, stream=None, carry=None):
         cb = self.cb
@@ -420,11 +434,42 @@ def baseline_metric():
         return "Msamples/sec (escaping points) + HBM GB/s, 4096x4096 max_iter=20000, 1/2/4/8 GPU"
 
 
+# --dump-outputs: the counters with the reference's meaning (cudabrot.cu:312,398-412); the step, cycle and clock
+# counters depend on how the kernels iterate, not on what they compute, and are not dumped
+DUMP_COUNTERS = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "increments")
+DUMP_SAMPLE_PIXELS = 1 << 22      # 32 MiB as float64: every config's dump stays under 64 MB
+DUMP_SAMPLE_SEED = 1337
+
+
+def dump_outputs(directory, hist, cnt, torch, np):
+    """Write what the timed steps computed (the histogram after the drain launch, and the counters), as float64 --
+    exact: every value is an integer below 2^53:
+      histogram_sample.npy    the u64 counters of DUMP_SAMPLE_PIXELS pixels of the flat [planes, h, w] histogram,
+                              drawn once without replacement by numpy's default_rng(DUMP_SAMPLE_SEED), in index order
+                              (the whole histogram when it is smaller)
+      histogram_row_sums.npy  the sum of each row of each plane: every pixel counts in one of them
+      counters.npy            DUMP_COUNTERS, in that order"""
+    os.makedirs(directory, exist_ok=True)
+    n = hist.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(n, DUMP_SAMPLE_PIXELS), replace=False))
+    sample = hist[torch.from_numpy(idx).to(hist.device)].cpu().numpy().view(np.uint64)
+    rows = hist.view(-1, W).sum(dim=1).cpu().numpy().view(np.uint64)
+    np.save(os.path.join(directory, "histogram_sample.npy"), sample.astype(np.float64))
+    np.save(os.path.join(directory, "histogram_row_sums.npy"), rows.astype(np.float64))
+    np.save(os.path.join(directory, "counters.npy"), np.array([cnt[k] for k in DUMP_COUNTERS], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)   # 0.6 s of launches: the one drain launch at the end (15 ms) is 2 % of it
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the histogram they accumulated and the sample counters to DIR "
+                         "as float64 .npy files")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: other configs, the kernels alone, the "
+                         "full-iterate roofline, the reference's HIP build and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference", action="store_true")
     ap.add_argument("--no-full-iterate", action="store_true",
@@ -443,6 +488,8 @@ def main():
                     help="workload: C3 (default, the config BASELINE.json's metric is quoted on), C4 (20000x20000), C2, "
                          "C5 (the colour recipe's three windows fused, 20000x15000)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global W, H, MAX_ITER, MIN_ITER
     W, H, MAX_ITER, MIN_ITER = CONFIGS[args.config]
 
@@ -482,13 +529,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- diagnostic legs, BEFORE the clock (not counted in `value`) ----------------------------------------
+    # ---- diagnostic legs (--full), BEFORE the clock (not counted in `value`) --------------------------------
     # They used to follow the timed region; run first they also bring the device to its working clocks: the
     # first launches on an idle GPU take 10 %, 4 %, 2 % ... longer, and the driver's run has five warm-up steps.
     #
     # (0) the other BASELINE.json configs, each with buffers of its own, freed before the headline workload's
     other_configs = None
-    if world == 1 and not args.no_other_configs and not args.direct_atomics:
+    if args.full and world == 1 and not args.no_other_configs and not args.direct_atomics:
         other_configs = {}
         for name in ("C4", "C2", "C5", "C3"):
             if name == args.config:
@@ -507,12 +554,16 @@ def main():
     # (1) The draw launch and the scatter kernels ALONE, for alone_ms and roofline_scatter.  Four sequential
     # launches on one stream, the last two timed.
     seq_flush_ms, seq_incr, seq_draw_ms = [], [], []
-    if ws_bytes:
+    if args.full and ws_bytes:
         seq_draw_ms, seq_flush_ms, seq_incr = job.sequential_leg(np)
     # (2) the iterate loop against its roofline (one GPU only): see full_iterate_leg
     full_iterate = None
-    if world == 1 and not args.no_full_iterate:
+    if args.full and world == 1 and not args.no_full_iterate:
         full_iterate = full_iterate_leg(job, torch, np, dev)
+    if args.full:
+        # the legs drew from the generators: start them again, so that the timed steps draw the samples a plain run
+        # draws (both legs end with a drain, so no orbit is in flight)
+        job.seed_generators()
 
     for _ in range(args.warmup):
         job.step()
@@ -587,12 +638,12 @@ def main():
         traffic = recorded_traffic(threads * samples_per_thread) if args.config == "C3" else None
         busy = recorded_valu_busy(threads * samples_per_thread) if args.config == "C3" else None
         tflops = iters_per_launch * FLOPS_PER_ITERATION / (avg_ms * 1e-3) / 1e12
-        if ws_bytes:   # the scatter kernels alone (sequential leg before the clock)
+        scatter_ms = None
+        if seq_flush_ms:   # the scatter kernels alone (sequential leg before the clock, --full)
             scatter_ms = sum(seq_flush_ms) / len(seq_flush_ms)
             scatter_incr = sum(seq_incr) / len(seq_incr)
-        else:          # direct atomics happen inside the draw kernel
+        elif not ws_bytes:   # direct atomics happen inside the draw kernel
             scatter_ms, scatter_incr = avg_ms, incr_per_launch
-        scatter_gbps = scatter_incr * BYTES_PER_INCREMENT / (scatter_ms * 1e-3) / 1e9
         if args.config == "C5":
             workload = "C5: %dx%d canvas on [%g,%g]x[%g,%g], fused windows (max, min) %s" % ((W, H) + C5_BOX + (C5_WINDOWS,))
         else:
@@ -672,7 +723,10 @@ def main():
                         "of every CU to the scatter, DESIGN.md 4.1b) -- alone_ms / frac_alone: the same launch with nothing "
                         "beside it, before the clock; step_frac: the same flops over the whole step",
             },
-            "roofline_scatter": {
+        }
+        if scatter_ms is not None:
+            scatter_gbps = scatter_incr * BYTES_PER_INCREMENT / (scatter_ms * 1e-3) / 1e9
+            line["roofline_scatter"] = {
                 "bound": "hbm",
                 "kernel": "bin_region_sort + bin_gather_accumulate (+ region / slice tables)" if ws_bytes
                           else "atomics inside the draw kernel",
@@ -696,19 +750,20 @@ def main():
                         "(fabric bytes per launch, PMC passes of traffic_source) is what HBM sees; achieved_counter_gbps / "
                         "frac_counter price those bytes over the same time: the LDS tiles absorb repeats, so they are fewer "
                         "than the algorithmic ones",
-            },
-        }
+            }
         if busy:
             line["roofline"].update(busy)
         if full_iterate is not None:
             line["roofline_full_iterate"] = full_iterate
         if other_configs is not None:
             line["other_configs"] = other_configs
-        if world == 1 and not args.no_reference:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hist, cnt, torch, np)
+        if args.full and world == 1 and not args.no_reference:
             ref = reference_gpu()
             if ref:
                 line["reference_gpu"] = ref
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
 

@@ -2,9 +2,11 @@
 """Regenerates the golden vectors from the reference's OWN lines (oracle/_ref/, built by
 `make -C oracle ref` where /root/reference is present): the histogram rows of appendix_b.json are
 re-derived and compared with the committed file, and burning_ship.json (the reference compiled with
--DRENDER_BURNING_SHIP, cudabrot.cu:15-17) is written.
+-DRENDER_BURNING_SHIP, cudabrot.cu:15-17) and reference_lines.json (what tests/test_oracle_vs_ref.py compares
+with where oracle/_ref is absent) are written.
 
-usage: python tests/golden/make_goldens.py            # verify appendix_b.json, (re)write burning_ship.json
+usage: python tests/golden/make_goldens.py            # verify appendix_b.json, (re)write burning_ship.json and
+                                                      # reference_lines.json
        python tests/golden/make_goldens.py --full     # also (re)write full_size.json: BASELINE.json's C4 and C5
                                                       # at full size (minutes; ~20 GB of host memory)
 """
@@ -120,6 +122,45 @@ def write_full_size():
     print("full_size.json: %d rows written" % len(rows))
 
 
+def write_reference_lines(fma, ship):
+    """The reference's side of every case of tests/test_oracle_vs_ref.py, computed with the test's own helpers."""
+    import tempfile
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_vs_ref as t
+
+    out = {"_comment": "the reference's side of tests/test_oracle_vs_ref.py: cudabrot.cu:43-67,284-414,416-468,548-577 "
+                       "compiled for the host (oracle/Makefile ref: libref_fma.so, libref_ship_fma.so); histograms as "
+                       "digests; written by tests/golden/make_goldens.py",
+           "histograms": {str(i): t.hist_digest(oracle, t.ref_render(fma, *c)) for i, c in enumerate(t.CONFIGS)},
+           "burning_ship_histograms": {t.ship_id(c): t.hist_digest(oracle, t.ref_render(ship, *c)) for c in t.SHIP_CONFIGS},
+           "rng": t.ref_rng_rows(fma),
+           "point_functions": t.ref_point_functions(fma, t.sample_points()),
+           "tonemap": {}}
+    hist = t.tonemap_hist(oracle)
+    with tempfile.TemporaryDirectory() as tmp:
+        for gamma in t.GAMMAS:
+            # the "Max value" line goes to file descriptor 1 (the driver flushes it): read it from a file there
+            log = os.path.join(tmp, "stdout")
+            sys.stdout.flush()
+            saved = os.dup(1)
+            with open(log, "wb") as f:
+                os.dup2(f.fileno(), 1)
+                try:
+                    rgray, pgm = t.ref_tonemap(fma, hist, gamma, os.path.join(tmp, "ref.pgm"))
+                finally:
+                    os.dup2(saved, 1)
+                    os.close(saved)
+            with open(log) as f:
+                printed = f.read()
+            out["tonemap"][repr(gamma)] = {"stdout": printed, "gray_sha256": t.sha256(np.ascontiguousarray(rgray, dtype="<u2").tobytes()),
+                                           "pgm_sha256": t.sha256(pgm)}
+    with open(os.path.join(HERE, "reference_lines.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("reference_lines.json written")
+
+
 def main():
     fma, ship = oracle.ref_library("fma"), oracle.ref_library("ship_fma")
     if fma is None or ship is None:
@@ -145,6 +186,7 @@ def main():
         json.dump(out, f, indent=1)
         f.write("\n")
     print("burning_ship.json: %d rows written" % len(ship_rows))
+    write_reference_lines(fma, ship)
     if "--full" in sys.argv[1:]:
         write_full_size()
 

@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys, the roofline and the CPU
-baseline objects), on a short run."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys; with --full also the roofline legs,
+the other configs and the CPU baseline object; --dump-outputs), on a short run."""
 
 import json
 import os
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_prints_one_json_line_with_the_contract_keys(repo_root):
     r = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-reference", "--no-full-iterate", "--no-other-configs"],
+                        "--full", "--no-reference", "--no-full-iterate", "--no-other-configs"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=repo_root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
@@ -36,11 +36,49 @@ def test_bench_prints_one_json_line_with_the_contract_keys(repo_root):
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["sample"]
 
 
+
+def test_plain_run_times_the_steps_alone_and_dumps_what_they_computed(repo_root, tmp_path):
+    """Without --full the line carries the headline and nothing that takes launches of its own; --dump-outputs writes
+    float64 arrays, under 64 MB, that agree with the line.  A --full run with the same arguments dumps the same
+    arrays: its legs before the clock leave the samples of the timed steps as they are."""
+    import numpy as np
+
+    dumps = []
+    for extra in ([], ["--full", "--no-reference", "--no-full-iterate", "--no-other-configs", "--no-cpu-baseline"]):
+        out = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--gpus", "1", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(out)] + extra,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=repo_root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [x for x in r.stdout.splitlines() if x.strip()]
+        assert len(lines) == 1
+        b = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in b, k
+        assert b["steps"] == 3 and b["warmup"] == 1 and b["dtype"] == "f64" and b["value"] > 0
+        for k in ("other_configs", "roofline_full_iterate", "reference_gpu", "cpu_baseline"):
+            assert k not in b, k
+        assert ("roofline_scatter" in b) == bool(extra) and (b["roofline"]["alone_ms"] is not None) == bool(extra)
+        names = sorted(os.listdir(out))
+        assert names == ["counters.npy", "histogram_row_sums.npy", "histogram_sample.npy"]
+        assert sum(os.path.getsize(out / f) for f in names) < 64e6
+        d = {f: np.load(out / f) for f in names}
+        assert all(a.dtype == np.float64 for a in d.values())
+        samples, rejected, never_escaped, too_fast, recorded, increments = d["counters.npy"]
+        assert samples == 3 * b["config"]["samples_per_step_per_gpu"]
+        assert samples == rejected + never_escaped + too_fast + recorded and recorded > 0
+        assert d["histogram_row_sums.npy"].shape == (4096,) and d["histogram_row_sums.npy"].sum() == increments
+        sample = d["histogram_sample.npy"]
+        assert sample.shape == (1 << 22,) and 0 < sample.sum() < increments
+        dumps.append(d)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
 def test_bench_line_carries_the_other_configs(repo_root):
     """`other_configs`: short before-the-clock legs of BASELINE.json's C4, C2 and C5 (fused recipe windows) in the
     one JSON line, each checked inside bench.py against its own increment counter."""
     r = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-reference", "--no-full-iterate", "--no-cpu-baseline"],
+                        "--full", "--no-reference", "--no-full-iterate", "--no-cpu-baseline"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=repo_root)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([x for x in r.stdout.splitlines() if x.strip()][-1])
@@ -57,7 +95,7 @@ def test_every_other_config_carries_its_two_rooflines(repo_root):
     """a driver-visible roofline for every BASELINE config, not C3 alone -- frac, executed iterations,
     and (from the committed counter summary of that config under profiles/) valu_busy and traffic."""
     r = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-reference", "--no-full-iterate", "--no-cpu-baseline"],
+                        "--full", "--no-reference", "--no-full-iterate", "--no-cpu-baseline"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=repo_root)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([x for x in r.stdout.splitlines() if x.strip()][-1])

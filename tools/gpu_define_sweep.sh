@@ -3,7 +3,7 @@
 # line.   usage: [CONFIG=C4] [STEPS=20] tools/gpu_define_sweep.sh "" "-DCB_GATHER_NARROW_TWO_LEVEL=1" "-DCB_SORT_PRIO_RANK=1 ..." ...
 set -u
 mkdir -p gpurun_out
-B="--config ${CONFIG:-C3} --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
+B="--config ${CONFIG:-C3} --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
 for setting in "$@"; do
   rm -f cudabrot_amd/csrc/build/draw_wide*.o cudabrot_amd/csrc/build/draw_wave*.o cudabrot_amd/csrc/build/scatter.o
   make -s -C cudabrot_amd/csrc all EXTRA="$setting" > gpurun_out/sweep_build.log 2>&1 || { echo "build failed: $setting"; tail -5 gpurun_out/sweep_build.log; continue; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The embedded interior map against another one (tools/_ab/map_depth9.bin: the map before round 4's depth-10 cells) on one
 # box, alternating: what the added cells are worth in time.   usage: tools/gpu_map_depth_ab.sh [rounds]
-B="--config C3 --steps 20 --warmup 5 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
+B="--config C3 --steps 20 --warmup 5 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
 for k in $(seq ${1:-3}); do
   for which in other embedded; do
     if [ $which = other ]; then export CUDABROT_AMD_DEBUG=1 CUDABROT_AMD_INTERIOR_MAP=tools/_ab/map_depth9.bin; else unset CUDABROT_AMD_DEBUG CUDABROT_AMD_INTERIOR_MAP; fi

@@ -3,7 +3,7 @@
 # usage: tools/gpu_map_levels.sh 13 14 15
 set -u
 mkdir -p gpurun_out
-B="--steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
+B="--steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
 make -s -C cudabrot_amd/csrc build/interior_map > /dev/null 2>&1
 for level in "$@"; do
   if [ "$level" = 0 ]; then

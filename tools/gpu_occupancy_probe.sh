@@ -4,7 +4,7 @@
 # time is the unpadded beside-the-draw time, it is.   usage: [CONFIG=C4] tools/gpu_occupancy_probe.sh
 set -u
 mkdir -p gpurun_out
-B="--config ${CONFIG:-C3} --steps 10 --warmup 3 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
+B="--config ${CONFIG:-C3} --steps 10 --warmup 3 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
 for setting in "" "-DCB_SORT_LDS_PAD=16384" "-DCB_GATHER_LDS_PAD=24576" "-DCB_SORT_LDS_PAD=16384 -DCB_GATHER_LDS_PAD=24576"; do
   rm -f cudabrot_amd/csrc/build/scatter.o
   make -s -C cudabrot_amd/csrc all EXTRA="$setting" > gpurun_out/occ_build.log 2>&1 || { echo "build failed: $setting"; continue; }

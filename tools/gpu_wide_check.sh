@@ -13,7 +13,7 @@ run() {  # run <seconds> <logfile> <cmd...>
 }
 run 120 gpurun_out/smoke.log python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 run 600 gpurun_out/pytest_parity.log python -m pytest tests/test_gpu_parity.py -x -q || { grep -E "^E " gpurun_out/pytest_parity.log | head -30; exit 1; }
-B="--steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
+B="--steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs"
 TAILN=1 run 200 gpurun_out/bench_wide.json python3 bench.py $B
 export CUDABROT_AMD_DEBUG=1
 TAILN=1 run 200 gpurun_out/bench_nowide.json env CUDABROT_AMD_NO_WIDE=1 python3 bench.py $B

@@ -3,7 +3,7 @@
 # (make EXTRA=...); prints the bench's short line per setting.   usage: tools/gpu_wide_sweep.sh "" "-DCB_WREPLAY_MIN=48" ...
 set -u
 mkdir -p gpurun_out
-B="--steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs ${BENCH_EXTRA:-}"
+B="--steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --no-reference --no-full-iterate --no-other-configs ${BENCH_EXTRA:-}"
 n=0
 for setting in "$@"; do
   n=$((n+1))
