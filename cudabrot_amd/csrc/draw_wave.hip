@@ -2054,8 +2054,12 @@ draw_wave_kernel(DrawArgs a) {
     if (lane_id() == 0) a.bin.wave_count[wave_id] = next_chunk;
   }
   if (carry) {  // leave queues and orbit slots for the next launch (empty after a drain)
+    // a wave that holds nothing leaves tag 0, the tag of a fresh buffer: the next launch may be draw_wide_kernel's,
+    // and an empty record is not work it would drop
+    const bool holds_work = samples_left != 0u || ((q0_count | q1_count | q2_count) != 0) ||
+                            __ballot(l_rem[0] > 0 || l_rem[1] > 0 || p_act) != 0ull;
     if (lane_id() == 0) {
-      carry[0] = 1ull;
+      carry[0] = holds_work ? 1ull : 0ull;
       carry[1] = (unsigned long long) (uint32_t) q0_head | ((unsigned long long) (uint32_t) q0_count << 32);
       carry[2] = (unsigned long long) (uint32_t) q1_head | ((unsigned long long) (uint32_t) q1_count << 32);
       carry[3] = (unsigned long long) (uint32_t) q2_head | ((unsigned long long) (uint32_t) q2_count << 32);

@@ -95,7 +95,8 @@ constexpr uint32_t kWideLanePlanes = kSlots * 6 + 2 + 4 + 1;
 // The record lies over the two records of the waves this one replaces (draw_wave.hip's: kCarryWordsPerWave words each,
 // tag 1 in word 0).  Both headers carry THIS kernel's tag, 2 -- the second record's header words are skipped by the lane
 // planes -- so that either kernel, handed a carry buffer the other one wrote, sees a foreign tag in every record it
-// reads and reports it (CB_STATUS_CARRY_FOREIGN) instead of taking the orbits in it for none.
+// reads and reports it (CB_STATUS_CARRY_FOREIGN) instead of taking the orbits in it for none.  A wave that ends with
+// nothing in flight (after a drain) writes tag 0 in both instead: an empty record is any kernel's to start from.
 constexpr uint32_t kWidePlanesFront = (kCarryWordsPerWave - kCarryHeaderWords - kWideQueueWords) / 64;
 __host__ __device__ constexpr uint32_t wide_plane(uint32_t p) {  // word offset of lane plane p in the record
   return p < kWidePlanesFront ? kCarryHeaderWords + kWideQueueWords + 64u * p
@@ -1484,7 +1485,11 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
   };
   const uint32_t keep_rest = __builtin_amdgcn_readfirstlane(a.drain ? 1u : 0u);  // 0: leave in-flight work to the next launch
   post_progress_and_set_priority(halves_left);
-  if (carry[0] != 0ull && carry[0] != 2ull) status |= CB_STATUS_CARRY_FOREIGN;  // draw_wave_kernel's: not ours to resume
+  // draw_wave_kernel's records (tag 1; 0: empty or never written) are not ours to resume: either of the two waves this
+  // one replaces may hold work
+  if ((carry[0] != 0ull && carry[0] != 2ull) || (carry[kCarryWordsPerWave] != 0ull && carry[kCarryWordsPerWave] != 2ull)) {
+    status |= CB_STATUS_CARRY_FOREIGN;
+  }
   if (carry[0] == 2ull) {  // wave-uniform: the header is one address (2: a record of this kernel)
     q0_head = (int) __builtin_amdgcn_readfirstlane((uint32_t) carry[1]);
     q0_count = (int) __builtin_amdgcn_readfirstlane((uint32_t) (carry[1] >> 32));
@@ -1810,9 +1815,14 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
   {  // leave queues and orbit slots for the next launch (empty after a drain)
     unsigned long long *carry = ea->carry + (size_t) wave_id * (2u * kCarryWordsPerWave);
     asm volatile("" : "+s"(carry));
+    // a wave that holds nothing leaves tag 0, the tag of a fresh buffer: the next launch may be draw_wave_kernel's
+    // (a caller who changes the launch's shape after a drain), and an empty record is not work it would drop
+    const bool holds_work = ((halves_left | pending) != 0u) || ((q0_count | q1_count | q2_count) != 0) || pact != 0ull ||
+                            __ballot(l_rem[0] > 0 || l_rem[1] > 0 || l_rem[2] > 0 || l_rem[3] > 0) != 0ull;
+    const unsigned long long tag = holds_work ? 2ull : 0ull;
     if (lane_id() == 0) {
-      carry[0] = 2ull;
-      carry[kCarryWordsPerWave] = 2ull;  // (where draw_wave_kernel's odd waves look for their tag)
+      carry[0] = tag;
+      carry[kCarryWordsPerWave] = tag;  // (where draw_wave_kernel's odd waves look for their tag)
       carry[1] = (unsigned long long) (uint32_t) q0_head | ((unsigned long long) (uint32_t) q0_count << 32);
       carry[2] = (unsigned long long) (uint32_t) q1_head | ((unsigned long long) (uint32_t) q1_count << 32);
       carry[3] = (unsigned long long) (uint32_t) q2_head | ((unsigned long long) (uint32_t) q2_count << 32);
