@@ -26,6 +26,7 @@ CB_KERNEL_FLAG_BURNING_SHIP = 0x100
 CB_KERNEL_FLAG_DRAIN = 0x200
 # cb_counters.status bits (include/cudabrot_amd.h)
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
+CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -69,6 +70,23 @@ class IterationControl(C.Structure):
     """cb_iteration_control == IterationControl (cudabrot.cu:62-67)."""
 
     _fields_ = [("max_escape_iterations", C.c_int), ("min_escape_iterations", C.c_int)]
+
+
+class ColorParams(C.Structure):
+    """cb_color_params: the composition and the levels' percentages of the colour stage."""
+
+    _fields_ = [("compose", C.c_int), ("black_percent", C.c_double), ("white_percent", C.c_double),
+                ("hue_shift", C.c_double)]
+
+    @classmethod
+    def make(cls, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
+        if isinstance(compose, str):
+            modes = {"rgb": CB_COMPOSE_RGB, "hsl": CB_COMPOSE_HSL}
+            if compose not in modes:
+                raise ValueError("compose must be 'rgb' or 'hsl', not %r" % compose)
+            compose = modes[compose]
+        black, white = stretch
+        return cls(int(compose), float(black), float(white), float(hue_shift))
 
 
 class Counters(C.Structure):
@@ -139,6 +157,7 @@ def _load():
     lib_ = C.CDLL(path)
     vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
     dims_p, it_p, cnt_p = C.POINTER(FractalDimensions), C.POINTER(IterationControl), C.POINTER(Counters)
+    col_p = C.POINTER(ColorParams)
     sigs = {
         "cb_abi_version": (i32, []),
         "cb_error_string": (C.c_char_p, [i32]),
@@ -176,6 +195,10 @@ def _load():
         "cb_tone_value": (C.c_uint16, [u64, u64, C.c_double]),
         "cb_tone_map_device": (i32, [vp, i32, i32, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double), vp]),
         "cb_renderer_grayscale_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_compose_color": (i32, [C.POINTER(vp), i32, i32, col_p, vp, vp]),
+        "cb_compose_color_device": (i32, [C.POINTER(vp), i32, i32, C.c_double, i32, col_p, vp, vp, vp]),
+        "cb_renderer_color_image": (i32, [vp, C.POINTER(i32), C.c_double, i32, col_p, vp, vp]),
+        "cb_save_ppm_be": (i32, [C.c_char_p, vp, i32, i32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -194,7 +217,7 @@ EXPORTED_SYMBOLS = (
     "cb_renderer_destroy cb_set_grayscale_pixels cb_save_image cb_save_image_be cb_tone_value "
     "cb_tone_map_device cb_renderer_grayscale_image cb_renderer_read_rng_states cb_renderer_write_rng_states "
     "cb_draw_buddhabrot_channels cb_flush_scatter_channels cb_renderer_create_channels cb_renderer_grayscale_plane cb_renderers_reduce "
-    "cb_renderer_prepare"
+    "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be"
 ).split()
 
 
@@ -323,6 +346,20 @@ class Renderer:
         )
         return gray, int(mx.value), float(scale.value)
 
+    def color_image(self, planes=(0, 1, 2), gamma=1.0, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
+        """Colour stage on the device (cb_renderer_color_image): planes[0..2] -> (big-endian u16 image [h,w,3] = the
+        PPM body, levels [(black, white)] * 3)."""
+        rgb = np.empty((self.dims.h, self.dims.w, 3), dtype=">u2")
+        levels = np.zeros(6, dtype=np.uint16)
+        idx = (C.c_int * 3)(*[int(j) for j in planes])
+        params = ColorParams.make(compose, stretch, hue_shift)
+        _check(
+            lib.cb_renderer_color_image(self._h, idx, float(gamma), int(mode), C.byref(params), rgb.ctypes.data,
+                                        levels.ctypes.data),
+            "cb_renderer_color_image",
+        )
+        return rgb, _level_pairs(levels)
+
     def write_histogram(self, hist):
         a = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
         if a.size != (self.n_channels or 1) * self.dims.w * self.dims.h:
@@ -411,3 +448,44 @@ def save_image(path, gray):
     g = np.array(gray, dtype=np.uint16, order="C")
     h, w = g.shape
     return int(lib.cb_save_image(os.fsencode(path), g.ctypes.data, w, h))
+
+
+def _level_pairs(levels):
+    return [(int(levels[2 * j]), int(levels[2 * j + 1])) for j in range(3)]
+
+
+def compose_color(grays, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
+    """Colour stage on the host (cb_compose_color): three u16 images [h,w] (the values of the PGMs) ->
+    (big-endian u16 image [h,w,3] = the PPM body, levels [(black, white)] * 3)."""
+    planes = [np.ascontiguousarray(g, dtype=np.uint16) for g in grays]
+    if len(planes) != 3 or any(g.ndim != 2 or g.shape != planes[0].shape for g in planes):
+        raise ValueError("compose_color wants three images of one shape")
+    h, w = planes[0].shape
+    rgb = np.empty((h, w, 3), dtype=">u2")
+    levels = np.zeros(6, dtype=np.uint16)
+    ptrs = (C.c_void_p * 3)(*[g.ctypes.data for g in planes])
+    params = ColorParams.make(compose, stretch, hue_shift)
+    _check(lib.cb_compose_color(ptrs, w, h, C.byref(params), rgb.ctypes.data, levels.ctypes.data), "cb_compose_color")
+    return rgb, _level_pairs(levels)
+
+
+def compose_color_device(d_hists, w, h, gamma, d_rgb_be, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0,
+                         stream=0):
+    """cb_compose_color_device on caller-owned device memory (integer pointers: three histograms of w*h u64, the
+    3*w*h u16 of the output) -> levels [(black, white)] * 3."""
+    levels = np.zeros(6, dtype=np.uint16)
+    ptrs = (C.c_void_p * 3)(*[int(p) for p in d_hists])
+    params = ColorParams.make(compose, stretch, hue_shift)
+    _check(
+        lib.cb_compose_color_device(ptrs, w, h, float(gamma), int(mode), C.byref(params), d_rgb_be, levels.ctypes.data,
+                                    stream),
+        "cb_compose_color_device",
+    )
+    return _level_pairs(levels)
+
+
+def save_ppm(path, rgb):
+    """Binary 16-bit PPM of an image [h,w,3] (cb_save_ppm_be) -> 0, or 1/2/3 as save_image."""
+    a = np.ascontiguousarray(rgb, dtype=">u2")
+    h, w, _ = a.shape
+    return int(lib.cb_save_ppm_be(os.fsencode(path), a.ctypes.data, w, h))

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "color_math.h"
 #include "kernels.h"
 
 namespace {
@@ -798,6 +799,30 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
   if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
   if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
   (void) hipFree(d_gray);
+  return rc;
+}
+
+int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
+                            const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
+  if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
+  const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
+  const cb_pixel *src[3];
+  for (int j = 0; j < 3; ++j) {
+    if (planes[j] < 0 || planes[j] >= (r->n_channels ? r->n_channels : 1)) return (int) hipErrorInvalidValue;
+    src[j] = r->d_hist + (size_t) planes[j] * n;
+  }
+  CB_TRY(hipSetDevice(r->device));
+  {
+    int rc = finish(r);
+    if (rc) return rc;
+  }
+  const size_t bytes = 3 * n * sizeof(uint16_t);
+  uint16_t *d_rgb = nullptr;
+  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_rgb), bytes));
+  int rc = cb_compose_color_device(src, r->dims.w, r->dims.h, gamma, tone_mode, p, d_rgb, levels, r->stream);
+  if (rc == 0) rc = (int) hipMemcpyAsync(host_rgb_be, d_rgb, bytes, hipMemcpyDeviceToHost, r->stream);
+  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
+  (void) hipFree(d_rgb);
   return rc;
 }
 

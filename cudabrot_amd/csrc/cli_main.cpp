@@ -14,8 +14,11 @@
 //    Ctrl+C act at launch granularity; the printed pass count still counts reference-sized passes;
 //  * extension flags, which the reference answers with its usage text: --passes N, --kernel NAME,
 //    --stats, --tonemap FORM, --seed N, --rng-state FILE, --burning-ship, --channel MAX:MIN:FILE, --gpus N,
-//    --state-format native|raw (raw: the -s file as the reference's bare buffer, uint32 when every count fits).
+//    --state-format native|raw (raw: the -s file as the reference's bare buffer, uint32 when every count fits),
+//    --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W (the three --channel planes composed into
+//    one 16-bit PPM: include/cudabrot_amd.h, "Colour image").
 #include <errno.h>
+#include <math.h>
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -62,6 +65,11 @@ struct Settings {
   bool bad_state_format = false;
   int tone_mode = CB_TONE_AUTO;                     // --tonemap (extension): device table / thresholds
   bool host_tonemap = false;                        //   ... or the reference's host loop
+  // --color FILE (extension): the three --channel planes composed into one RGB image; --compose, --hue-shift,
+  // --color-stretch B:W set its cb_color_params (defaults: rgb, 0, ImageMagick's -normalize 2:1)
+  const char *color_file = nullptr;
+  cb_color_params color = {CB_COMPOSE_RGB, 2.0, 1.0, 0.0};
+  const char *bad_color_flag = nullptr;             // the message of a bad --compose / --hue-shift / --color-stretch
 };
 
 // The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
@@ -196,6 +204,45 @@ const std::vector<Flag> &flag_table() {
          s.raw_state = strcmp(t, "raw") == 0;
          s.bad_state_format = !s.raw_state && strcmp(t, "native") != 0;
        }},
+      {"--color", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) { s.color_file = t; }},
+      {"--compose", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         if (strcmp(t, "rgb") == 0) {
+           s.color.compose = CB_COMPOSE_RGB;
+         } else if (strcmp(t, "hsl") == 0) {
+           s.color.compose = CB_COMPOSE_HSL;
+         } else {
+           s.bad_color_flag = "Invalid compose mode (want rgb or hsl)";
+         }
+       }},
+      {"--hue-shift", Value::kDouble, nullptr, false,
+       [](Settings &s, long, double d, const char *) {
+         if (isfinite(d)) {
+           s.color.hue_shift = d;
+         } else {
+           s.bad_color_flag = "Invalid hue shift (want a finite number)";
+         }
+       }},
+      {"--color-stretch", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         // B:W, two numbers: B % of the pixels go black, W % white (finite, B >= 0, W >= 0, B + W < 100)
+         char *end = nullptr;
+         const double b = strtod(t, &end);
+         bool ok = end != t && *end == ':';
+         double w = 0.0;
+         if (ok) {
+           const char *rest = end + 1;
+           w = strtod(rest, &end);
+           ok = end != rest && *end == 0;
+         }
+         if (ok && isfinite(b) && isfinite(w) && b >= 0.0 && w >= 0.0 && b + w < 100.0) {
+           s.color.black_percent = b;
+           s.color.white_percent = w;
+         } else {
+           s.bad_color_flag = "Invalid color stretch (want B:W, percentages with B + W < 100)";
+         }
+       }},
       {"--tonemap", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
          s.host_tonemap = strcmp(t, "host") == 0;
@@ -273,7 +320,15 @@ Settings parse_arguments(int argc, char **argv) {
       printf("Invalid state format (want native or raw): %s\n", text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_color_flag) {
+      printf("%s: %s\n", s.bad_color_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  if (s.color_file && s.n_channels != 3) {  // after parsing: --color and the --channel flags come in any order
+    printf("--color needs exactly 3 --channel images, got %d.\n", s.n_channels);
+    usage_and_exit(argv[0]);
   }
   return s;
 }
@@ -312,6 +367,7 @@ class Run {
     save_rng_state();
     if (cfg_.n_channels > 0) {
       save_channels();
+      if (cfg_.color_file) save_color();
     } else {
       printf("Saving image.\n");
       save_image(cfg_.output_image);
@@ -330,6 +386,7 @@ class Run {
   cb_pixel *counts_ = nullptr;   // host mirror of the histogram (only with -s or --tonemap host)
   uint16_t *gray_ = nullptr;
   bool gray_is_big_endian_ = false;
+  std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
@@ -650,10 +707,36 @@ class Run {
       printf("Channel %d: %d max iterations, %d min iterations.\n", j,
              cfg_.channel_window[j].max_escape_iterations, cfg_.channel_window[j].min_escape_iterations);
       tone_map(j);
+      if (cfg_.color_file && cfg_.host_tonemap) {  // before save_image swaps gray_ in place
+        color_grays_.resize(3 * pixel_count());
+        memcpy(color_grays_.data() + (uint64_t) j * pixel_count(), gray_, pixel_count() * sizeof(uint16_t));
+      }
       printf("Saving image.\n");
       save_image(cfg_.channel_file[j].c_str());
       printf("Done! Output image saved: %s\n", cfg_.channel_file[j].c_str());
     }
+  }
+
+  // --color: the three planes composed into one RGB image, on the device (only the image crosses to the host) or, with
+  // --tonemap host, by the host restatement from the planes' values; the bytes are the same.  With --gpus N this
+  // is rank 0's histogram, after the reduce.
+  void save_color() {
+    std::vector<uint16_t> rgb_be(3 * pixel_count());
+    uint16_t levels[6] = {0, 0, 0, 0, 0, 0};
+    if (cfg_.host_tonemap) {
+      const uint16_t *planes[3] = {color_grays_.data(), color_grays_.data() + pixel_count(),
+                                   color_grays_.data() + 2 * pixel_count()};
+      CB_CHECK(cb_compose_color(planes, cfg_.canvas.w, cfg_.canvas.h, &cfg_.color, rgb_be.data(), levels));
+    } else {
+      const int planes[3] = {0, 1, 2};
+      CB_CHECK(cb_renderer_color_image(renderer_, planes, cfg_.gamma_correction, cfg_.tone_mode, &cfg_.color,
+                                       rgb_be.data(), levels));
+    }
+    printf("Color levels: black %u %u %u, white %u %u %u\n", levels[0], levels[2], levels[4], levels[1], levels[3],
+           levels[5]);
+    printf("Saving color image.\n");
+    report_save(cb_save_ppm_be(cfg_.color_file, rgb_be.data(), cfg_.canvas.w, cfg_.canvas.h));
+    printf("Done! Color image saved: %s\n", cfg_.color_file);
   }
 
   void print_stats() {
@@ -696,10 +779,13 @@ class Run {
   }
 
   void save_image(const char *path) {  // cudabrot.cu:548-577: failures are reported and the run still ends with 0
-    static const char *const kWhy[] = {nullptr, "Failed opening output image.",
-                                       "Failed writing pgm header.", "Failed writing pixel data."};
-    const int rc = gray_is_big_endian_ ? cb_save_image_be(path, gray_, cfg_.canvas.w, cfg_.canvas.h)
-                                       : cb_save_image(path, gray_, cfg_.canvas.w, cfg_.canvas.h);
+    report_save(gray_is_big_endian_ ? cb_save_image_be(path, gray_, cfg_.canvas.w, cfg_.canvas.h)
+                                    : cb_save_image(path, gray_, cfg_.canvas.w, cfg_.canvas.h));
+  }
+
+  static void report_save(int rc) {
+    static const char *const kWhy[] = {nullptr, "Failed opening output image.", "Failed writing pgm header.",
+                                       "Failed writing pixel data."};
     if (rc >= 1 && rc <= 3) printf("%s\n", kWhy[rc]);
   }
 #undef CB_CHECK

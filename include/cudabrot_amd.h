@@ -282,6 +282,57 @@ int cb_renderer_grayscale_image(cb_renderer *r, double gamma, int mode, uint16_t
 int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mode, uint16_t *host_gray_be,
                                 uint64_t *max_out, double *scale_out);
 
+/* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
+ *
+ * The reference's colour recipe (generate_hires_color_image.sh) renders three windows, stretches each PGM with
+ * ImageMagick's `convert -normalize` and merges them with an external HSL combiner.  This stage does the stretch and
+ * the merge on the tone-mapped planes.  It is the project's own definition: it is not the external combiner bit for
+ * bit (that program is not part of this project).  Normative; host, device and the tests' numpy restatement agree
+ * byte for byte (only IEEE + - * floor and compares on the device, no division, no contraction):
+ *
+ *   input of plane j: v, the 16-bit tone value of each pixel (what the plane's PGM holds; cb_tone_value with the
+ *   run's gamma); N = w*h.
+ *   1. levels, per plane, with percentages B = black_percent and W = white_percent (ImageMagick's -normalize: 2, 1):
+ *        nb = (uint64_t)((double)N * (B / 100.0)),  nw = (uint64_t)((double)N * (W / 100.0));
+ *        black = the smallest k with #{v <= k} > nb,  white = the largest k with #{v >= k} > nw.
+ *      Valid only for finite B, W with 0 <= B, 0 <= W, B + W < 100.
+ *   2. stretch (fp64): s = 0 if v <= black; else s = 1 if v >= white; else s = (double)(v - black) * inv with
+ *      inv = 1.0 / (double)(white - black) evaluated by the host (this also covers white <= black).
+ *   3. CB_COMPOSE_RGB: out_j = (uint16_t)floor(s_j * 65535.0 + 0.5)  (plane 0 -> R, 1 -> G, 2 -> B).
+ *   4. CB_COMPOSE_HSL (fp64, in this order): h = s0 + hue_shift; h = h - floor(h); S = s1; L = s2;
+ *        q = L < 0.5 ? L * (1.0 + S) : (L + S) - L * S;  p = 2.0 * L - q;
+ *        f(t): t = t - floor(t); t < 1.0/6.0 -> p + ((q - p) * 6.0) * t; t < 0.5 -> q;
+ *              t < 2.0/3.0 -> p + ((q - p) * 6.0) * (2.0/3.0 - t); else p;
+ *        R = f(h + 1.0/3.0), G = f(h), B = f(h - 1.0/3.0); each clamped to [0, 1], then floor(c * 65535.0 + 0.5).
+ *   5. file: binary PPM, header "P6\n%d %d\n65535\n", then w*h pixels of big-endian R, G, B u16, row 0 = the PGMs'. */
+#define CB_COMPOSE_RGB 0
+#define CB_COMPOSE_HSL 1
+typedef struct {
+  int compose;           /* CB_COMPOSE_RGB or CB_COMPOSE_HSL */
+  double black_percent;  /* B of step 1 */
+  double white_percent;  /* W of step 1 */
+  double hue_shift;      /* added to the hue (CB_COMPOSE_HSL only); finite */
+} cb_color_params;
+
+/* The whole definition on the host: gray[j] are host-endian w*h planes (what cb_set_grayscale_pixels makes);
+ * rgb_be receives 3*w*h big-endian u16 (the PPM body); levels (may be NULL) receives black0, white0, black1, ...
+ * hipErrorInvalidValue for bad params (compose, percentages, hue shift, sizes) or a NULL pointer. */
+int cb_compose_color(const uint16_t *const gray[3], int w, int h, const cb_color_params *p, uint16_t *rgb_be,
+                     uint16_t levels[6]);
+/* The same from three DEVICE histograms (any cb_pixel planes of w*h): each is tone-mapped with cb_tone_map_device
+ * (gamma, tone_mode), the levels are found on the device (two 256-bin radix passes) and one kernel writes the
+ * big-endian RGB body to d_rgb_be (3*w*h u16).  Synchronises `stream`; the bytes equal cb_compose_color's on the
+ * grays of cb_set_grayscale_pixels. */
+int cb_compose_color_device(const cb_pixel *const d_hist[3], int w, int h, double gamma, int tone_mode,
+                            const cb_color_params *p, uint16_t *d_rgb_be, uint16_t levels[6], void *stream);
+/* For a renderer: finishes carried work, composes planes[0..2] (indices of its channel planes; 0 for a renderer
+ * without channels) and copies the 3*w*h big-endian u16 of the RGB body to host_rgb_be. */
+int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
+                            const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]);
+/* Writes the binary PPM of step 5 from a big-endian body; 0, or 1/2/3 = open / header / pixel-data failure (as
+ * cb_save_image). */
+int cb_save_ppm_be(const char *path, const uint16_t *rgb_be, int w, int h);
+
 const char *cb_error_string(int code);
 int cb_abi_version(void);
 
