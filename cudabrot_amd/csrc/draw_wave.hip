@@ -18,7 +18,7 @@
 //           this is where the many orbits that leave after a few dozen iterations leave.  mid_steps
 //           is chosen so that min_iter - (head_steps + mid_steps) is a multiple of kChunk.
 //           Survivors (~2 % of the samples) go to Q1 as (c, z).
-//   LONG    each lane holds TWO deep orbits and iterates them side by side in chunks of kChunk (30)
+//   LONG    each lane holds TWO deep orbits and iterates them side by side in chunks of kChunk (60)
 //           steps of hand-written asm; finished slots refill from Q1 at chunk boundaries, so the lanes
 //           stay on deep orbits.  An orbit is retired when it escapes, reaches max_iter, or is found
 //           to be exactly periodic (then it can never escape).  Escaped orbits whose chunk lies at or
@@ -49,12 +49,8 @@
 // |.| operand modifiers on one instruction of the step, free of charge -- and the cardioid / bulb
 // shortcut is skipped (:397-399).  The second build exports launch_draw_wave_ship.
 #ifdef CB_BURNING_SHIP
-#define CB_AL "|"
-#define CB_AR "|"
 #define CB_LAUNCH_NAME launch_draw_wave_ship
 #else
-#define CB_AL ""
-#define CB_AR ""
 #define CB_LAUNCH_NAME launch_draw_wave
 #endif
 
@@ -67,56 +63,16 @@ constexpr int kOrbitsPerLane = 2;      // deep orbits a lane iterates side by si
 constexpr int kQ0Cap = 128;            // HEAD survivors: c            (2 KiB per wave)
 constexpr int kQ1Cap = 96;             // MID survivors: (c, z)        (3 KiB per wave)
 constexpr int kQ2Cap = 192;            // accepted starting points: c  (3 KiB per wave)
-// Iterations of the HEAD stage (every lane, one sample each), 2..4.  After the shortcut test and k iterations
-// 30.5 / 17.3 / 11.9 / 8.9 % of the samples are still iterating (k = 1..4): HEAD's later steps run with most
-// lanes switched off, MID's re-derive them for the survivors only.
-#ifndef CB_HEAD_STEPS
-#define CB_HEAD_STEPS 4
-#endif
-#if CB_HEAD_STEPS == 4
-#define CB_HEAD_MORE_STEPS CB_STEP_LIT CB_STEP_LIT CB_STEP_LIT
-#define CB_MID_REDERIVE_MORE CB_STEP_NOTEST CB_STEP_NOTEST CB_STEP_NOTEST
-#elif CB_HEAD_STEPS == 3
-#define CB_HEAD_MORE_STEPS CB_STEP_LIT CB_STEP_LIT
-#define CB_MID_REDERIVE_MORE CB_STEP_NOTEST CB_STEP_NOTEST
-#elif CB_HEAD_STEPS == 2
-#define CB_HEAD_MORE_STEPS CB_STEP_LIT
-#define CB_MID_REDERIVE_MORE CB_STEP_NOTEST
-#else
-#error "CB_HEAD_STEPS: 2, 3 or 4"
-#endif
-constexpr int kHeadSteps = CB_HEAD_STEPS;
-// -DCB_DBG_REPLAY: the timed kernel's wave dump counts REPLAY burst steps and the lanes active in them
-// (tools/wave_dump_stats.py prints them as "chunks" and "slots") instead of LONG chunks and orbit slots.
-#ifdef CB_DBG_REPLAY
-constexpr bool kDbgReplay = true;
-#else
-constexpr bool kDbgReplay = false;
-#endif
-#ifndef CB_Q1_LOW
-#define CB_Q1_LOW 32
-#endif
-#ifndef CB_Q1_EXIT
-#define CB_Q1_EXIT 8
-#endif
-#ifndef CB_REPLAY_MIN
-#define CB_REPLAY_MIN 56
-#endif
-#ifndef CB_REPLAY_BURST
-#define CB_REPLAY_BURST 32
-#endif
-#ifndef CB_PRIO_CHUNKS
-#define CB_PRIO_CHUNKS 32
-#endif
-constexpr int kQ1Low = CB_Q1_LOW;      // run MID while fewer deep orbits than this are queued
-constexpr int kQ1Exit = CB_Q1_EXIT;    // LONG hands over to HEAD / MID below this many
-constexpr int kReplayMin = CB_REPLAY_MIN;  // suspend REPLAY below this many busy lanes (unless draining)
-constexpr uint32_t kReplayBurst = CB_REPLAY_BURST;  // replay steps per asm burst
-#ifndef CB_BRENT_BITS
-#define CB_BRENT_BITS 2
-#endif
-constexpr uint32_t kBrentBits = CB_BRENT_BITS;     // periodicity check: re-save when the chunk count has no bits below its top 2
-constexpr uint32_t kPrioChunks = CB_PRIO_CHUNKS;  // LONG chunks per priority level in the rotation (power of two)
+// Iterations of the HEAD stage (every lane, one sample each; CB_HEAD_TEST and mid_pass spell them out).  After the
+// shortcut test and k iterations 30.5 / 17.3 / 11.9 / 8.9 % of the samples are still iterating (k = 1..4): HEAD's
+// later steps run with most lanes switched off, MID's re-derive them for the survivors only.
+constexpr int kHeadSteps = 4;
+constexpr int kQ1Low = 32;             // run MID while fewer deep orbits than this are queued
+constexpr int kQ1Exit = 8;             // LONG hands over to HEAD / MID below this many
+constexpr int kReplayMin = 56;         // suspend REPLAY below this many busy lanes (unless draining)
+constexpr uint32_t kReplayBurst = 32;  // replay steps per asm burst
+constexpr uint32_t kBrentBits = 2;     // periodicity check: re-save when the chunk count has no bits below its top 2
+constexpr uint32_t kPrioChunks = 32;   // LONG chunks per priority level in the rotation (power of two)
 
 // The ring capacities are exact worst cases, not estimates: a stage runs only while its output ring can take
 // everything the stage may push (CB_STATUS_QUEUE_OVERFLOW guards the reasoning, these guard the constants).
@@ -137,73 +93,8 @@ struct WaveQueues {
   uint32_t q2_lrem[kQ2Cap];
 };
 
-struct Orbit {
-  double cr, ci, r, i;
-};
-
-// This lane's bit of a wave-uniform mask, as a predicate: the mask itself becomes the condition
-// register (s_and_saveexec), no vector instruction.
-__device__ __forceinline__ bool lane_in(unsigned long long mask) {
-  return __builtin_amdgcn_inverse_ballot_w64(mask);
-}
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t) v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t) (v >> 32));
-  return ((unsigned long long) hi << 32) | lo;
-}
-
-// ---- one orbit per lane under EXEC (HEAD, MID, the last short chunk of LONG) -----------------------
+// ---- one orbit per lane under EXEC (CB_STEP, iterate_steps: draw_common.h) ------------------------
 //
-// One z <- z^2 + c step on the lanes in EXEC, on DOUBLED coordinates, in the order of
-// device_math.h's mandel_step2:
-//   a = i*i; a = fma(r,r,-a); i = fma(r,i,ci); r = fma(a,0.5,cr); a = r*r; a = fma(i,i,a)
-// then EXEC &= !(16.0 < a) (v_cmpx: a lane leaves at its escape, cudabrot.cu:336), after adding the
-// number of lanes that execute the step to the scalar counter.  k16 is 16.0 in a scalar pair.
-#define CB_STEP                                       \
-  "s_bcnt1_i32_b64 %[tmp], exec\n\t"                  \
-  "v_mul_f64 %[a], %[i], %[i]\n\t"                    \
-  "s_add_u32 %[cnt], %[cnt], %[tmp]\n\t"              \
-  "v_fma_f64 %[a], %[r], %[r], -%[a]\n\t"             \
-  "v_fma_f64 %[i], " CB_AL "%[r]" CB_AR ", " CB_AL "%[i]" CB_AR ", %[ci]\n\t"             \
-  "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"              \
-  "v_mul_f64 %[a], %[r], %[r]\n\t"                    \
-  "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"              \
-  "v_cmpx_nlt_f64_e32 vcc, %[k16], %[a]\n\t"
-
-// n steps (wave-uniform run-time count) on the lanes of `mask`, leaving early once every lane has
-// escaped.  Returns the lanes that escaped; r, i of the others advance by n iterations; lane_steps
-// receives the executed lane-steps (a lane that escapes at its j-th step counts j).
-__device__ __forceinline__ unsigned long long iterate_steps(unsigned long long mask, uint32_t n,
-                                                            Orbit &o, uint32_t &lane_steps) {
-  unsigned long long save, escaped;
-  uint32_t cnt, tmp, ctr;
-  double a;
-  const double k16 = 16.0;
-  asm volatile(
-      "s_mov_b64 %[save], exec\n\t"
-      "s_mov_b32 %[cnt], 0\n\t"
-      "s_mov_b64 exec, %[mask]\n\t"
-      "s_mov_b32 %[ctr], %[n]\n\t"
-      "s_cmp_eq_u32 %[n], 0\n\t"
-      "s_cbranch_scc1 2f\n\t"
-      "1:\n\t"
-      CB_STEP
-      "s_cbranch_execz 2f\n\t"
-      "s_sub_u32 %[ctr], %[ctr], 1\n\t"
-      "s_cmp_lg_u32 %[ctr], 0\n\t"
-      "s_cbranch_scc1 1b\n\t"
-      "2:\n\t"
-      "s_andn2_b64 %[esc], %[mask], exec\n\t"
-      "s_mov_b64 exec, %[save]\n\t"
-      "s_nop 4\n\t"
-      : [r] "+v"(o.r), [i] "+v"(o.i), [a] "=&v"(a), [save] "=&s"(save),
-        [esc] "=&s"(escaped), [cnt] "=&s"(cnt), [tmp] "=&s"(tmp), [ctr] "=&s"(ctr)
-      : [mask] "s"(mask), [n] "s"(n), [cr] "v"(o.cr), [ci] "v"(o.ci), [k16] "s"(k16)
-      : "vcc", "scc");
-  lane_steps = cnt;
-  return escaped;
-}
-
 // Runs iterations [k0, k0 + n) of the orbits in `alive` (IterateMandelbrot, cudabrot.cu:326-337) and
 // sorts the escapes by the accept filter of cudabrot.cu:407-408: an escape at index k < min_iter is
 // too fast, one at k >= min_iter is accepted (k < max_iter holds by construction).  Removes the
@@ -244,16 +135,6 @@ __device__ __forceinline__ unsigned long long iterate_window(unsigned long long 
 //               keeps the current rotation in a scalar: logical word j lives in field (j + rot) % 5.
 //   the test    cardioid / bulb test (in_main_cardioid2, in_order2_bulb2) and the first kHeadSteps
 //               iterations under EXEC; the rounded I*I of the tests is the first product of step 1.
-template <int K>
-__device__ __forceinline__ uint32_t &xorwow_word(Xorwow &s) {
-  static_assert(K >= 0 && K < 5, "five words");
-  if constexpr (K == 0) return s.x0;
-  if constexpr (K == 1) return s.x1;
-  if constexpr (K == 2) return s.x2;
-  if constexpr (K == 3) return s.x3;
-  return s.x4;
-}
-
 // One output: xk is the oldest word (x0 of rocrand's step), xp the newest (x4); the new word
 // replaces xk (which also serves as a temporary once t is formed); out = d + k * 362437 + new word
 // (the multiple of the Weyl increment goes through one scratch scalar).
@@ -330,19 +211,6 @@ static_assert(362437u == 0x587c5u && 2u * 362437u == 0xb0f8au && 3u * 362437u ==
   "s_cmp_ge_u32 %[sc], 5\n\t"                                      \
   "s_cselect_b32 %[rot], %[rot], %[sc]\n\t"
 
-// The generator words in logical order again (rot back to 0), for store_rng and the generic HEAD.
-template <int ROT>
-__device__ __forceinline__ Xorwow xorwow_unrotated(Xorwow &s) {
-  Xorwow r;
-  r.x0 = xorwow_word<(0 + ROT) % 5>(s);
-  r.x1 = xorwow_word<(1 + ROT) % 5>(s);
-  r.x2 = xorwow_word<(2 + ROT) % 5>(s);
-  r.x3 = xorwow_word<(3 + ROT) % 5>(s);
-  r.x4 = xorwow_word<(4 + ROT) % 5>(s);
-  r.d = s.d;
-  return r;
-}
-
 // The test of one pass: cardioid / bulb test and HEAD's iterations of the lanes in `valid`, then the
 // survivors' c goes to Q0 (slot (tail + rank) & 127 of the ring at LDS byte address q0_lds: q0_cr there,
 // q0_ci 1024 bytes on).  alive0: lanes outside both regions (cudabrot.cu:398); alive4: lanes that have
@@ -388,7 +256,7 @@ __device__ __forceinline__ Xorwow xorwow_unrotated(Xorwow &s) {
   "v_mul_f64 %[a], %[r], %[r]\n\t"                                             \
   "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"                                       \
   "v_cmpx_nlt_f64_e32 vcc, 0x40300000, %[a]\n\t"                               \
-  CB_HEAD_MORE_STEPS                                                            \
+  CB_STEP_LIT CB_STEP_LIT CB_STEP_LIT                                           \
   "s_mov_b64 %[alive4], exec\n\t"                                              \
   /* survivors (EXEC) -> Q0 */                                                  \
   "v_mbcnt_lo_u32_b32 %[slot], exec_lo, 0\n\t"                                 \
@@ -407,7 +275,7 @@ __device__ __forceinline__ Xorwow xorwow_unrotated(Xorwow &s) {
 __device__ __forceinline__ void head_loop(Xorwow &g, uint32_t &samples_left, uint32_t &rot, unsigned long long valid,
                                           uint32_t q0_tail, uint32_t &q0_count, uint32_t q0_lds,
                                           uint32_t &n_rejected, uint32_t &n_too_fast, uint32_t &n_steps) {
-  static_assert(kQ0Cap == 128, "ring mask and the 1024-byte distance of q0_ci in CB_HEAD_TEST");
+  static_assert(kQ0Cap == 128 && kHeadSteps == 4, "ring mask, the 1024-byte distance of q0_ci and the steps of CB_HEAD_TEST");
   unsigned long long save, alive0, alive4, gone;
   uint32_t cnt, tmp, sc, slot, t, u, o1, o2;
   double a, r, i, x, q, f, cr, ci;
@@ -463,11 +331,6 @@ __device__ __forceinline__ void head_loop(Xorwow &g, uint32_t &samples_left, uin
 // compare), run n_steps more iterations under EXEC and push the survivors' (c, z) to Q1 (ring slot
 // (q1_tail + rank) mod 96 at q1_lds; q1_ci, q1_r, q1_i follow at 768-byte distances).  lane_steps:
 // the executed iterations of the n_steps window; alive: the survivors.
-#define CB_STEP_NOTEST                                \
-  "v_mul_f64 %[a], %[i], %[i]\n\t"                    \
-  "v_fma_f64 %[a], %[r], %[r], -%[a]\n\t"             \
-  "v_fma_f64 %[i], " CB_AL "%[r]" CB_AR ", " CB_AL "%[i]" CB_AR ", %[ci]\n\t"             \
-  "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"
 // map / shift / cols / rows: the interior map (DrawArgs::interior_map, 0: none; draw_wide.hip's mid_pass has the same
 // lines): the cell of every popped c is looked up while the stage iterates, and a lane whose cell is marked -- proven
 // never-escaping -- is not pushed (`hit`, among the lanes of `take`).
@@ -476,7 +339,7 @@ __device__ __forceinline__ void mid_pass(unsigned long long take, uint32_t lane_
                                          uint32_t q1_lds, unsigned long long &alive,
                                          uint32_t &lane_steps, unsigned long long map, uint32_t shift,
                                          uint32_t cols, uint32_t rows, unsigned long long &hit) {
-  static_assert(kQ0Cap == 128 && kQ1Cap == 96, "ring mask, ring length and plane distances below");
+  static_assert(kQ0Cap == 128 && kQ1Cap == 96 && kHeadSteps == 4, "ring mask, ring length and plane distances below");
   unsigned long long save, t64;
   uint32_t cnt, tmp, ctr, slot, wr, mbit, hitb;
   double cr, ci, r, i, a;
@@ -520,7 +383,7 @@ __device__ __forceinline__ void mid_pass(unsigned long long take, uint32_t lane_
       "v_fma_f64 %[a], %[cr], %[cr], -%[a]\n\t"
       "v_fma_f64 %[i], " CB_AL "%[cr]" CB_AR ", " CB_AL "%[ci]" CB_AR ", %[ci]\n\t"
       "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"
-      CB_MID_REDERIVE_MORE
+      CB_STEP_NOTEST CB_STEP_NOTEST CB_STEP_NOTEST
       "s_cmp_eq_u32 %[n], 0\n\t"
       "s_cbranch_scc1 2f\n\t"
       "1:\n\t"
@@ -600,26 +463,7 @@ __device__ __forceinline__ void mid_pass(unsigned long long take, uint32_t lane_
   "v_cmp_nlt_f64_e64 %[c1], %[k16], %[a1]\n\t"
 #define CB_STEP2X4 CB_STEP2 CB_STEP2 CB_STEP2 CB_STEP2
 #define CB_STEP2X24 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4
-#if CB_CHUNK == 24
-#define CB_STEP2_CHUNK CB_STEP2X24
-#elif CB_CHUNK == 30
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X4 CB_STEP2 CB_STEP2
-#elif CB_CHUNK == 32
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X4 CB_STEP2X4
-#elif CB_CHUNK == 36
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4
-#elif CB_CHUNK == 60
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X24 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4
-#elif CB_CHUNK == 90
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X24 CB_STEP2X24 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4 CB_STEP2 CB_STEP2
-#elif CB_CHUNK == 120
-#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X24 CB_STEP2X24 CB_STEP2X24 CB_STEP2X24
-#else
-#error "unroll CB_STEP2 for this chunk length"
-#endif
-#define CB_STR2(x) #x
-#define CB_STR(x) CB_STR2(x)
-#define CB_CHUNK_S CB_STR(CB_CHUNK)  // the chunk length as a constant of the asm blocks below (VOP2 / VOPC e32: may be a literal)
+#define CB_STEP2_CHUNK CB_STEP2X24 CB_STEP2X24 CB_STEP2X4 CB_STEP2X4 CB_STEP2X4  // kChunk = 60 steps
 
 // kChunk steps on orbit A of the lanes in mask_a and on orbit B of the lanes in mask_b (both
 // wave-uniform; called with EXEC = all 64 lanes).  esc_a / esc_b receive the lanes whose orbit
@@ -628,6 +472,7 @@ __device__ __forceinline__ void mid_pass(unsigned long long take, uint32_t lane_
 __device__ __forceinline__ void iterate_chunk2(unsigned long long mask_a, unsigned long long mask_b,
                                                Orbit &oa, Orbit &ob, unsigned long long &esc_a,
                                                unsigned long long &esc_b, uint32_t &lane_steps) {
+  static_assert(kChunk == 60, "CB_STEP2_CHUNK is unrolled for 60 steps");
   unsigned long long la = mask_a, lb = mask_b, c0, c1;
   uint32_t cnt, t0, t1;
   double a0, a1;
@@ -649,27 +494,27 @@ __device__ __forceinline__ void iterate_chunk2(unsigned long long mask_a, unsign
   lane_steps = cnt;
 }
 
-// ---- the same chunk with the escape test on every tenth step only -----------------------------------------
+// ---- the same chunk with the escape test behind its last step only ---------------------------------------
 //
 // Three of the seven instructions of a step exist for the escape test (|z|^2 and the compare).  The LONG
 // stage does not need the step at which an orbit escapes, only WHETHER it escaped inside the chunk (the
 // accept filter goes by chunk, cudabrot.cu:407-408; the REPLAY stage finds the exact index again), and escape
 // is absorbing: with |c| <= 2, |z| > 2 implies |z^2 + c| >= |z|^2 - |c| > |z|.  In fp64 that holds up to
-// rounding: if the reference's test fires at some step (4 |z|^2 = M > 16 on the doubled coordinates), then
-// writing |Z_k| >= 4 - e_k for the steps after it, e' <= 4 e + 2^-39 (|C| <= 4 + 2^-40 for every sample that
-// survives HEAD -- a larger |c| escapes at iteration 0 with margin; rounding of one step <= 2^-44 while |Z| <=
-// 8, beyond that |Z'| >= 28), so nine steps later e <= 2^-21 and M >= 16 - 2^-17, or M is infinite / NaN.
-// The chunk therefore computes |Z|^2 on every tenth step only and compares it with kSparseThreshold =
-// 16 - 2^-10 (64 times the bound; `le` is false for NaN): a lane above it stops counting as alive.  At the
-// end of the chunk such a lane has escaped for certain if its FINAL M is above 16 (or NaN): escaped at that
-// very step if not before.  What is left -- a lane that was above the threshold at a test step and is at or
-// below 16 at the end: an orbit grazing |z| = 2 without leaving, one test step in 3 x 10^8 -- is decided
-// exactly by recomputing the orbit from z0 = c with the per-step test (verify_chunk_escape below).
-// 8 instructions per step for the two orbits + 6 per test step: 258 per 30 steps instead of 420, and no scalar
-// bookkeeping inside the chunk: the executed iterations are counted per chunk (kChunk per orbit that ran it)
-// and the over-count of an orbit's last chunk is taken back when REPLAY knows its escape index
-// (long_overcount).  Only used when every escape inside a full LONG chunk is accepted (min_iter <= the start
-// of the LONG stage): an escape that is too fast is never replayed, so its index would stay unknown.
+// rounding, and the bound is weak only where |C| may exceed 4 by a rounding (doubled coordinates): there an orbit
+// just beyond |Z| = 4 need not move away from it.  For a sample with |C|^2 < kSparseThreshold = 16 - 2^-10
+// (|C| < 4 - 2^-13) it must: |Z| > 4 implies |Z'| >= |Z|^2 / 2 - |C| > 4 + 2^-13, against a rounding of 2^-44 per
+// step -- once the reference's test has fired, every later |Z|^2 is above 16 (or infinite, or NaN: `nle` is true
+// for NaN).  So for such a sample ONE test, behind the chunk's last step, is the exact answer to "did it escape
+// inside the chunk": !(M_last <= 16), M_last being the very expression the reference tests.  The other samples --
+// |c| within 2^-14 of 2, and of those only what has survived HEAD and MID: about one in 10^8 -- are decided by
+// verify_chunk_escape at every chunk they run.  The class of a sample is recomputed with the chunk (3 instructions
+// per orbit set: cheaper than a flag that lives across chunks).
+// 8 instructions per step for the two orbits + 12 per chunk: 492 per 60 steps instead of 840 with a test on every
+// step (and 516 with one on every tenth), and no scalar bookkeeping inside the chunk: the executed iterations are
+// counted per chunk (kChunk per orbit that ran it) and the over-count of an orbit's last chunk is taken back when
+// REPLAY knows its escape index (long_overcount).  Only used when every escape inside a full LONG chunk is
+// accepted (min_iter <= the start of the LONG stage): an escape that is too fast is never replayed, so its index
+// would stay unknown.
 [[maybe_unused]] constexpr double kSparseThreshold = 16.0 - 0x1p-10;  // (the value capi.hip puts into DrawArgs::sparse_threshold)
 #define CB_STEP2_NT                                       \
   "v_mul_f64 %[a0], %[ia], %[ia]\n\t"                     \
@@ -680,42 +525,6 @@ __device__ __forceinline__ void iterate_chunk2(unsigned long long mask_a, unsign
   "v_fma_f64 %[ib], " CB_AL "%[rb]" CB_AR ", " CB_AL "%[ib]" CB_AR ", %[cib]\n\t"             \
   "v_fma_f64 %[ra], %[a0], 0.5, %[cra]\n\t"               \
   "v_fma_f64 %[rb], %[a1], 0.5, %[crb]\n\t"
-// the first step after a test step: the masks of that test are applied behind its first instructions
-#define CB_STEP2_NT_AND                                   \
-  "v_mul_f64 %[a0], %[ia], %[ia]\n\t"                     \
-  "v_mul_f64 %[a1], %[ib], %[ib]\n\t"                     \
-  "s_and_b64 %[la], %[la], %[c0]\n\t"                     \
-  "v_fma_f64 %[a0], %[ra], %[ra], -%[a0]\n\t"             \
-  "s_and_b64 %[lb], %[lb], %[c1]\n\t"                     \
-  "v_fma_f64 %[a1], %[rb], %[rb], -%[a1]\n\t"             \
-  "v_fma_f64 %[ia], " CB_AL "%[ra]" CB_AR ", " CB_AL "%[ia]" CB_AR ", %[cia]\n\t"             \
-  "v_fma_f64 %[ib], " CB_AL "%[rb]" CB_AR ", " CB_AL "%[ib]" CB_AR ", %[cib]\n\t"             \
-  "v_fma_f64 %[ra], %[a0], 0.5, %[cra]\n\t"               \
-  "v_fma_f64 %[rb], %[a1], 0.5, %[crb]\n\t"
-// |Z|^2 of both orbits and the test against the threshold
-#define CB_STEP2_TEST                                     \
-  "v_mul_f64 %[a0], %[ra], %[ra]\n\t"                     \
-  "v_mul_f64 %[a1], %[rb], %[rb]\n\t"                     \
-  "v_fma_f64 %[a0], %[ia], %[ia], %[a0]\n\t"              \
-  "v_fma_f64 %[a1], %[ib], %[ib], %[a1]\n\t"              \
-  "v_cmp_le_f64_e64 %[c0], %[a0], %[kt]\n\t"              \
-  "v_cmp_le_f64_e64 %[c1], %[a1], %[kt]\n\t"
-#define CB_STEP2_NTX8 CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT
-// ---- ... and on the LAST step only --------------------------------------------------------------------
-//
-// (-DCB_SPARSE_STRIDE=10 keeps the form above.)  The tenth-step tests exist because the bound above is weak where
-// |C| may exceed 4 by a rounding: there an orbit just beyond |Z| = 4 need not move away from it.  For a sample
-// with |C|^2 < 16 - 2^-10 (|C| < 4 - 2^-13) it must: |Z| > 4 implies |Z'| >= |Z|^2 / 2 - |C| > 4 + 2^-13,
-// against a rounding of 2^-44 per step -- once the reference's test has fired, every later |Z|^2 is above 16
-// (or infinite, or NaN: `nle` is true for NaN).  So for such a sample ONE test, behind the chunk's last step, is
-// the exact answer to "did it escape inside the chunk": !(M_last <= 16), M_last being the very expression the
-// reference tests.  The other samples -- |c| within 2^-14 of 2, and of those only what has survived HEAD and
-// MID: about one in 10^8 -- are decided by verify_chunk_escape at every chunk they run.  The class of a sample
-// is recomputed with the chunk (3 instructions per orbit set: cheaper than a flag that lives across chunks).
-// 8 instructions per step for the two orbits + 12 per chunk: 492 per 60 steps instead of 516.
-#ifndef CB_SPARSE_STRIDE
-#define CB_SPARSE_STRIDE 0
-#endif
 #define CB_STEP2_LAST_TEST                                \
   "v_mul_f64 %[a0], %[ra], %[ra]\n\t"                     \
   "v_mul_f64 %[a1], %[rb], %[rb]\n\t"                     \
@@ -729,110 +538,34 @@ __device__ __forceinline__ void iterate_chunk2(unsigned long long mask_a, unsign
   "v_fma_f64 %[a1], %[cib], %[cib], %[a1]\n\t"            \
   "v_cmp_nlt_f64_e64 %[c0], %[a0], %[kt]\n\t"             \
   "v_cmp_nlt_f64_e64 %[c1], %[a1], %[kt]\n\t"
-#define CB_STEP2_NTX10 CB_STEP2_NTX8 CB_STEP2_NT CB_STEP2_NT
+#define CB_STEP2_NTX10 CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT CB_STEP2_NT
 #define CB_STEP2_NTX30 CB_STEP2_NTX10 CB_STEP2_NTX10 CB_STEP2_NTX10
-constexpr int kSparseStride = 10;  // steps between tests; the bound above is for at most ten
-#define CB_SPARSE_GROUP_FIRST CB_STEP2_NT CB_STEP2_NTX8 CB_STEP2_NT CB_STEP2_TEST
-#define CB_SPARSE_GROUP_NEXT CB_STEP2_NT_AND CB_STEP2_NTX8 CB_STEP2_NT CB_STEP2_TEST
-#if CB_CHUNK == 30
-#define CB_SPARSE_CHUNK CB_SPARSE_GROUP_FIRST CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT
-#elif CB_CHUNK == 60
-#define CB_SPARSE_CHUNK CB_SPARSE_GROUP_FIRST CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT
-#elif CB_CHUNK == 40
-#define CB_SPARSE_CHUNK CB_SPARSE_GROUP_FIRST CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT
-#elif CB_CHUNK == 90
-#define CB_SPARSE_GROUP_NEXT3 CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT
-#define CB_SPARSE_CHUNK CB_SPARSE_GROUP_FIRST CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT3 CB_SPARSE_GROUP_NEXT3
-#elif CB_CHUNK == 120
-#define CB_SPARSE_GROUP_NEXT3 CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT
-#define CB_SPARSE_CHUNK CB_SPARSE_GROUP_FIRST CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT CB_SPARSE_GROUP_NEXT3 CB_SPARSE_GROUP_NEXT3 CB_SPARSE_GROUP_NEXT3
-#else
-#define CB_SPARSE_CHUNK
-#endif
-static_assert(kChunk % kSparseStride == 0 || true, "sparse chunks are groups of ten steps");
 
-// The chunk of iterate_chunk2 with sparse tests.  esc_*: lanes of the masks that stopped counting as alive;
-// sure_*: lanes whose final |Z|^2 is above 16 or NaN (for a lane of esc_*: it escaped inside the chunk for
-// certain).  The caller decides esc & ~sure exactly (verify_chunk_escape).
+// The chunk of iterate_chunk2 with the one test.  esc_*: lanes of the masks that escaped or whose sample is not of
+// the sure class; sure_*: lanes whose sample is of the sure class (for a lane of esc_*: it escaped inside the chunk
+// for certain).  The caller decides esc & ~sure exactly (verify_chunk_escape).
 __device__ __forceinline__ void iterate_chunk2_sparse(unsigned long long mask_a, unsigned long long mask_b,
                                                       Orbit &oa, Orbit &ob, unsigned long long &esc_a,
                                                       unsigned long long &esc_b, unsigned long long &sure_a,
                                                       unsigned long long &sure_b, double threshold) {
-  unsigned long long la = mask_a, lb = mask_b, c0, c1, d0, d1;
+  static_assert(kChunk == 60, "unrolled: two times thirty steps");
+  unsigned long long c0, c1, d0, d1;
   double a0, a1;
   const double k16 = 16.0, kt = threshold;  // kSparseThreshold, or a test's lower one (DrawArgs::sparse_threshold)
-#if CB_SPARSE_STRIDE == 0
-  // one test behind the last step: esc = escaped (exact for the lanes of sure); sure = |C|^2 below the threshold
-  static_assert(kChunk == 30 || kChunk == 60 || kChunk == 90 || kChunk == 120, "unrolled in thirties");
   asm volatile(
       CB_STEP2_NTX30
-#if CB_CHUNK >= 60
       CB_STEP2_NTX30
-#endif
-#if CB_CHUNK >= 90
-      CB_STEP2_NTX30
-#endif
-#if CB_CHUNK >= 120
-      CB_STEP2_NTX30
-#endif
       CB_STEP2_LAST_TEST
       "s_nop 2\n\t"
       : [ra] "+v"(oa.r), [ia] "+v"(oa.i), [rb] "+v"(ob.r), [ib] "+v"(ob.i), [a0] "=&v"(a0), [a1] "=&v"(a1),
         [c0] "=&s"(c0), [c1] "=&s"(c1), [d0] "=&s"(d0), [d1] "=&s"(d1)
       : [cra] "v"(oa.cr), [cia] "v"(oa.ci), [crb] "v"(ob.cr), [cib] "v"(ob.ci), [k16] "s"(k16), [kt] "s"(kt)
       : "scc");
-  (void) la;
-  (void) lb;
   // the caller decides esc & ~sure exactly: make that "every lane that is not sure" (escaped or not at the end)
   esc_a = mask_a & (d0 | c0);
   esc_b = mask_b & (d1 | c1);
   sure_a = ~c0;
   sure_b = ~c1;
-#else
-  asm volatile(
-      CB_SPARSE_CHUNK
-      "v_cmp_nle_f64_e64 %[d0], %[a0], %[k16]\n\t"
-      "v_cmp_nle_f64_e64 %[d1], %[a1], %[k16]\n\t"
-      "s_and_b64 %[la], %[la], %[c0]\n\t"
-      "s_and_b64 %[lb], %[lb], %[c1]\n\t"
-      "s_nop 2\n\t"
-      : [ra] "+v"(oa.r), [ia] "+v"(oa.i), [rb] "+v"(ob.r), [ib] "+v"(ob.i), [la] "+s"(la),
-        [lb] "+s"(lb), [a0] "=&v"(a0), [a1] "=&v"(a1),
-        [c0] "=&s"(c0), [c1] "=&s"(c1), [d0] "=&s"(d0), [d1] "=&s"(d1)
-      : [cra] "v"(oa.cr), [cia] "v"(oa.ci), [crb] "v"(ob.cr), [cib] "v"(ob.ci), [k16] "s"(k16), [kt] "s"(kt)
-      : "scc");
-  esc_a = mask_a & ~la;
-  esc_b = mask_b & ~lb;
-  sure_a = d0;
-  sure_b = d1;
-#endif
-}
-
-// The exact decision for the lanes of `doubt`: did the orbit with starting point (cr, ci) escape during the
-// kChunk iterations after its first `done` ones (lane-wise)?  Recomputed from z0 = c with the reference's
-// test after every step (cudabrot.cu:326-337); the steps before the chunk passed that test when they were
-// made.  Rare (see above), so plain C++ under EXEC: same arithmetic as the asm (device_math.h).
-__device__ __forceinline__ unsigned long long verify_chunk_escape(unsigned long long doubt, const Orbit &o,
-                                                                  int done) {
-  bool escaped = false;
-  if (lane_in(doubt)) {
-    double r = o.cr, i = o.ci;
-    for (int k = 0; k < done; ++k) {
-#ifdef CB_BURNING_SHIP
-      (void) mandel_step2_ship(o.cr, o.ci, r, i);
-#else
-      (void) mandel_step2(o.cr, o.ci, r, i);
-#endif
-    }
-    for (int k = 0; k < kChunk && !escaped; ++k) {
-#ifdef CB_BURNING_SHIP
-      escaped = mandel_step2_ship(o.cr, o.ci, r, i) > 16.0;
-#else
-      escaped = mandel_step2(o.cr, o.ci, r, i) > 16.0;
-#endif
-    }
-  }
-  return __ballot(escaped);
 }
 
 // Iterations the sparse chunks counted beyond the escape of an orbit that took `steps` iterations in all
@@ -1186,22 +919,12 @@ __device__ __forceinline__ void long_retire(const Orbit &o, double &seen_r, doub
 // Up to n_steps (>= 1) replay steps on the lanes of `act`; the stream region must have room for
 // 64 * n_steps more entries.  On return `act` holds the lanes still replaying, `fill` the new fill,
 // lane_steps / hits the executed lane-steps and the entries appended.  p holds DOUBLED coordinates.
-// The kernel's arguments, read afresh: a scalar load from the argument segment at the point of use
-// instead of a value held in (and spilled from) scalar registers since the kernel began.
-typedef const DrawArgs __attribute__((address_space(4))) *KernelArgs;
-__device__ __forceinline__ KernelArgs fresh_args() {
-  KernelArgs p = (KernelArgs) __builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-
 template <bool kPow2>
 __device__ __forceinline__ void replay_burst(unsigned long long &act, uint32_t n_steps, Orbit &p,
                                              int &p_steps, const Canvas &cv, uint32_t *region,
                                              uint32_t &fill, uint32_t &lane_steps, uint32_t &hits,
                                              uint32_t row_shift, uint32_t tag,
-                                             unsigned long long emit, bool tagged,
-                                             uint32_t *burst_steps = nullptr) {
+                                             unsigned long long emit, bool tagged) {
   unsigned long long save, alive, hx, hy, scp;
   uint32_t cs, ch, ctr, t;
   double a, fx, fy, d0, d1, d2, d3;
@@ -1280,8 +1003,6 @@ __device__ __forceinline__ void replay_burst(unsigned long long &act, uint32_t n
   }
   lane_steps = cs;
   hits = ch;
-  // (diagnostics) steps of this burst: the loop leaves before its counter steps when the last lane ends
-  if (burst_steps) *burst_steps = n_steps - ctr + (act == 0ull ? 1u : 0u);
 }
 
 
@@ -1296,7 +1017,7 @@ __device__ __forceinline__ void replay_burst_chunked(unsigned long long &act, ui
                                                      uint32_t &lane_steps, uint32_t &hits, uint32_t row_shift,
                                                      uint32_t tag, unsigned long long emit, bool tagged,
                                                      uint32_t *cursors, uint32_t cursors_lds, uint32_t &next_chunk,
-                                                     uint32_t *desc, uint32_t *burst_steps = nullptr) {
+                                                     uint32_t *desc) {
   unsigned long long save, alive, hx, hy, scp, over;
   uint32_t cs, ch, ctr, t;
   double a, fx, fy, d0, d1, d2, d3;
@@ -1327,7 +1048,6 @@ __device__ __forceinline__ void replay_burst_chunked(unsigned long long &act, ui
       [one] "v"(1u)
   const double rx = kPow2 ? 0.0 : ka->rcp_delta_real, ry = kPow2 ? 0.0 : ka->rcp_delta_imag;
   const double kg = 0.5 - 0x1p-24;
-  const uint32_t all_steps = n_steps;
   lane_steps = 0;
   hits = 0;
   for (;;) {  // the burst, resumed behind every step that had to open chunks
@@ -1356,10 +1076,7 @@ __device__ __forceinline__ void replay_burst_chunked(unsigned long long &act, ui
   }
   lane_steps += cs;
   hits += ch;
-  if (over == 0ull) {  // the burst ran to its end: ctr steps were left when the last lane stopped (0: none did)
-    if (burst_steps) *burst_steps = all_steps - (ctr != 0u ? ctr - 1u : 0u);
-    break;
-  }
+  if (over == 0ull) break;  // the burst ran to its end
   // The lanes of `over` found their group's chunk full (or the group has none yet): their word is in e, the
   // place they took in pos -- lim, lim + 1, ... in some order, one run per group.  Group by group: open the next
   // free chunk, put the words at its start and the group's cursor behind them.  (Once per kChunkWords words of a
@@ -1381,10 +1098,7 @@ __device__ __forceinline__ void replay_burst_chunked(unsigned long long &act, ui
     next_chunk++;
     over &= ~same;
   }
-  if (n_steps == 0u || act == 0ull) {
-    if (burst_steps) *burst_steps = all_steps - n_steps;
-    break;
-  }
+  if (n_steps == 0u || act == 0ull) break;
   }  // resumed
 #undef CB_CHUNKED_OUTPUTS
 #undef CB_CHUNKED_INPUTS
@@ -1660,28 +1374,22 @@ draw_wave_kernel(DrawArgs a) {
           unsigned long long act_mask = __ballot(p_act);
           const unsigned long long was_act = act_mask;
           const unsigned long long emit = multi ? __ballot(p_real) : ~0ull;
-          uint32_t steps = 0, hits = 0, burst = 0;
+          uint32_t steps = 0, hits = 0;
           if (kChunked) {
             uint32_t *const desc = a.bin.chunk_desc + (size_t) wave_id * a.bin.chunks_per_wave;
             if (cv.pow2_real && cv.pow2_imag) {
               replay_burst_chunked<true>(act_mask, kReplayBurst, po, p_steps, region, region_fill, steps, hits,
-                                         a.bin.e_row_shift, p_tag, emit, multi, my_cursors, cursors_lds, next_chunk, desc,
-                                         kDbgReplay ? &burst : nullptr);
+                                         a.bin.e_row_shift, p_tag, emit, multi, my_cursors, cursors_lds, next_chunk, desc);
             } else {
               replay_burst_chunked<false>(act_mask, kReplayBurst, po, p_steps, region, region_fill, steps, hits,
-                                          a.bin.e_row_shift, p_tag, emit, multi, my_cursors, cursors_lds, next_chunk, desc,
-                                          kDbgReplay ? &burst : nullptr);
+                                          a.bin.e_row_shift, p_tag, emit, multi, my_cursors, cursors_lds, next_chunk, desc);
             }
           } else if (cv.pow2_real && cv.pow2_imag) {
             replay_burst<true>(act_mask, kReplayBurst, po, p_steps, cv, region, region_fill, steps, hits,
-                               a.bin.e_row_shift, p_tag, emit, multi, kDbgReplay ? &burst : nullptr);
+                               a.bin.e_row_shift, p_tag, emit, multi);
           } else {
             replay_burst<false>(act_mask, kReplayBurst, po, p_steps, cv, region, region_fill, steps, hits,
-                                a.bin.e_row_shift, p_tag, emit, multi, kDbgReplay ? &burst : nullptr);
-          }
-          if (kTimed && kDbgReplay) {  // the wave dump then describes REPLAY bursts instead of LONG chunks
-            dbg_chunks += burst;
-            dbg_slots += steps;
+                                a.bin.e_row_shift, p_tag, emit, multi);
           }
           n_replay += steps;
           n_incr += hits;
@@ -1974,7 +1682,7 @@ draw_wave_kernel(DrawArgs a) {
       }
       if ((full_mask[0] | full_mask[1]) != 0ull) {
         unsigned long long esc[kOrbitsPerLane];
-        if (la->sparse_long) {  // the escape test on every tenth step (iterate_chunk2_sparse)
+        if (la->sparse_long) {  // the escape test behind the chunk's last step (iterate_chunk2_sparse)
           unsigned long long sure[kOrbitsPerLane];
           iterate_chunk2_sparse(full_mask[0], full_mask[1], lo[0], lo[1], esc[0], esc[1], sure[0], sure[1],
                                 la->sparse_threshold);
@@ -1993,11 +1701,11 @@ draw_wave_kernel(DrawArgs a) {
           iterate_chunk2(full_mask[0], full_mask[1], lo[0], lo[1], esc[0], esc[1], steps);
           n_iterate += steps;
         }
-        if (kTimed && !kDbgReplay) {
+        if (kTimed) {
           dbg_chunks++;
           dbg_slots += (unsigned long long) (__popcll(full_mask[0]) + __popcll(full_mask[1]));
         }
-        // Bookkeeping (asm: long_retire).  An orbit's chunk covered escape indices [k_lo, k_lo + 32)
+        // Bookkeeping (asm: long_retire).  An orbit's chunk covered escape indices [k_lo, k_lo + kChunk)
         // with k_lo = max_iter - l_rem; min_iter - long_start is a multiple of kChunk, so the whole chunk
         // is on one side of min_iter (cudabrot.cu:407-408): escapes with l_rem <= max_iter - min_iter are
         // accepted.  Exact-periodicity early-out: if z is bit for bit a value this
@@ -2006,7 +1714,7 @@ draw_wave_kernel(DrawArgs a) {
         // IterateMandelbrot would return max_iterations -- the same outcome, without executing the
         // remaining iterations.  Brent's scheme at chunk granularity: compare with one saved point,
         // re-save on a geometric schedule of chunk counts (long_retire); a cycle of period p is found
-        // p / gcd(p, kChunk) chunks after a save that lies on it (hence kChunk = 30, kernels.h).
+        // p / gcd(p, kChunk) chunks after a save that lies on it (hence the choice of kChunk, kernels.h).
 #pragma unroll
         for (int o = 0; o < kOrbitsPerLane; ++o) {
           unsigned long long push = 0ull, ended = 0ull, periodic = 0ull;

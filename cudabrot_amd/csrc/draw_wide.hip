@@ -31,12 +31,8 @@
 
 // Compiled twice like draw_wave.hip: as is, and with -DCB_BURNING_SHIP (cudabrot.cu:15-17).
 #ifdef CB_BURNING_SHIP
-#define CB_AL "|"
-#define CB_AR "|"
 #define CB_LAUNCH_NAME launch_draw_wide_ship
 #else
-#define CB_AL ""
-#define CB_AR ""
 #define CB_LAUNCH_NAME launch_draw_wide
 #endif
 
@@ -50,27 +46,11 @@ constexpr int kQ0Cap = 128;            // HEAD survivors: c            (2 KiB pe
 constexpr int kQ1Cap = 96;             // MID survivors: (c, z)        (3 KiB per wave)
 constexpr int kQ2Cap = 320;            // accepted starting points: c  (5 KiB per wave)
 constexpr int kHeadSteps = 4;
-#ifndef CB_WQ1_LOW
-#define CB_WQ1_LOW 32
-#endif
-#ifndef CB_WQ1_EXIT
-#define CB_WQ1_EXIT 8
-#endif
-#ifndef CB_WREPLAY_MIN
-#define CB_WREPLAY_MIN 56
-#endif
-#ifndef CB_WREPLAY_BURST
-#define CB_WREPLAY_BURST 32
-#endif
-constexpr int kQ1Low = CB_WQ1_LOW;      // run MID while fewer deep orbits than this are queued
-constexpr int kReplayMin = CB_WREPLAY_MIN;  // suspend REPLAY below this many busy lanes (unless draining)
-constexpr uint32_t kReplayBurst = CB_WREPLAY_BURST;  // replay steps per asm burst
-#ifndef CB_WIDE_PRIO_BEHIND
-#define CB_WIDE_PRIO_BEHIND 2  // s_setprio of the wave of a SIMD that has more left to draw ...
-#endif
-#ifndef CB_WIDE_PRIO_AHEAD
-#define CB_WIDE_PRIO_AHEAD 1   // ... and of the other
-#endif
+constexpr int kQ1Low = 32;              // run MID while fewer deep orbits than this are queued
+constexpr int kReplayMin = 56;          // suspend REPLAY below this many busy lanes (unless draining)
+constexpr uint32_t kReplayBurst = 32;   // replay steps per asm burst
+constexpr int kPrioBehind = 2;          // s_setprio of the wave of a SIMD that has more left to draw ...
+constexpr int kPrioAhead = 1;           // ... and of the other
 constexpr uint32_t kBrentBits = 2;      // periodicity check: re-save when the chunk count has no bits below its top 2
 constexpr uint32_t kPrioChunks = 64;    // LONG chunks between two looks at the progress board (power of two)
 constexpr uint32_t kPrioHalves = 256;   // HEAD half-passes between two looks (power of two; a look costs a round trip to L2)
@@ -106,72 +86,10 @@ static_assert(kCarryHeaderWords + kWideQueueWords <= kCarryWordsPerWave, "the qu
 static_assert(wide_plane(kWideLanePlanes - 1) + 64u <= 2 * kCarryWordsPerWave,
               "a wide wave uses the carry records of the two waves it replaces");
 
-struct Orbit {
-  double cr, ci, r, i;
-};
-
-__device__ __forceinline__ bool lane_in(unsigned long long mask) {
-  return __builtin_amdgcn_inverse_ballot_w64(mask);
-}
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t) v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t) (v >> 32));
-  return ((unsigned long long) hi << 32) | lo;
-}
-
-typedef const DrawArgs __attribute__((address_space(4))) *KernelArgs;
-__device__ __forceinline__ KernelArgs fresh_args() {
-  KernelArgs p = (KernelArgs) __builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-// the same without the barrier: loads the compiler may hoist and keep in scalar registers (the stages of this kernel
-// run at two waves per SIMD, where a wait for a scalar load at every stage entry is not hidden by other waves)
+// fresh_args (draw_common.h) without the barrier: loads the compiler may hoist and keep in scalar registers (the
+// stages of this kernel run at two waves per SIMD, where a wait for a scalar load at every stage entry is not hidden
+// by other waves)
 __device__ __forceinline__ KernelArgs kernel_args() { return (KernelArgs) __builtin_amdgcn_kernarg_segment_ptr(); }
-
-// ---- one orbit per lane under EXEC (MID, the last short chunk of LONG, the first and last HEAD sample) --------
-// (draw_wave.hip, CB_STEP: the six instructions of mandel_step2, the lane-step count, EXEC &= !(16 < |Z|^2))
-#define CB_STEP                                       \
-  "s_bcnt1_i32_b64 %[tmp], exec\n\t"                  \
-  "v_mul_f64 %[a], %[i], %[i]\n\t"                    \
-  "s_add_u32 %[cnt], %[cnt], %[tmp]\n\t"              \
-  "v_fma_f64 %[a], %[r], %[r], -%[a]\n\t"             \
-  "v_fma_f64 %[i], " CB_AL "%[r]" CB_AR ", " CB_AL "%[i]" CB_AR ", %[ci]\n\t"             \
-  "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"              \
-  "v_mul_f64 %[a], %[r], %[r]\n\t"                    \
-  "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"              \
-  "v_cmpx_nlt_f64_e32 vcc, %[k16], %[a]\n\t"
-
-__device__ __forceinline__ unsigned long long iterate_steps(unsigned long long mask, uint32_t n,
-                                                            Orbit &o, uint32_t &lane_steps) {
-  unsigned long long save, escaped;
-  uint32_t cnt, tmp, ctr;
-  double a;
-  const double k16 = 16.0;
-  asm volatile(
-      "s_mov_b64 %[save], exec\n\t"
-      "s_mov_b32 %[cnt], 0\n\t"
-      "s_mov_b64 exec, %[mask]\n\t"
-      "s_mov_b32 %[ctr], %[n]\n\t"
-      "s_cmp_eq_u32 %[n], 0\n\t"
-      "s_cbranch_scc1 2f\n\t"
-      "1:\n\t"
-      CB_STEP
-      "s_cbranch_execz 2f\n\t"
-      "s_sub_u32 %[ctr], %[ctr], 1\n\t"
-      "s_cmp_lg_u32 %[ctr], 0\n\t"
-      "s_cbranch_scc1 1b\n\t"
-      "2:\n\t"
-      "s_andn2_b64 %[esc], %[mask], exec\n\t"
-      "s_mov_b64 exec, %[save]\n\t"
-      "s_nop 4\n\t"
-      : [r] "+v"(o.r), [i] "+v"(o.i), [a] "=&v"(a), [save] "=&s"(save),
-        [esc] "=&s"(escaped), [cnt] "=&s"(cnt), [tmp] "=&s"(tmp), [ctr] "=&s"(ctr)
-      : [mask] "s"(mask), [n] "s"(n), [cr] "v"(o.cr), [ci] "v"(o.ci), [k16] "s"(k16)
-      : "vcc", "scc");
-  lane_steps = cnt;
-  return escaped;
-}
 
 // ---- HEAD, software-pipelined -----------------------------------------------------------------------------------
 //
@@ -450,27 +368,7 @@ __device__ __forceinline__ void head_bodies(uint32_t enable, Xorwow2 &g, uint32_
   n_too_fast += acc0 - survivors;
 }
 
-// logical word j of a generator whose words are rotated by ROT (field (j + ROT) % 5), and back
-template <int K>
-__device__ __forceinline__ uint32_t &xorwow_word(Xorwow &s) {
-  static_assert(K >= 0 && K < 5, "five words");
-  if constexpr (K == 0) return s.x0;
-  if constexpr (K == 1) return s.x1;
-  if constexpr (K == 2) return s.x2;
-  if constexpr (K == 3) return s.x3;
-  return s.x4;
-}
-template <int ROT>
-__device__ __forceinline__ Xorwow xorwow_unrotated(Xorwow &s) {  // rotated fields -> logical order
-  Xorwow r;
-  r.x0 = xorwow_word<(0 + ROT) % 5>(s);
-  r.x1 = xorwow_word<(1 + ROT) % 5>(s);
-  r.x2 = xorwow_word<(2 + ROT) % 5>(s);
-  r.x3 = xorwow_word<(3 + ROT) % 5>(s);
-  r.x4 = xorwow_word<(4 + ROT) % 5>(s);
-  r.d = s.d;
-  return r;
-}
+// rotated fields -> logical order (xorwow_unrotated: draw_common.h)
 __device__ __forceinline__ Xorwow xorwow_unrotate(Xorwow s, uint32_t rot) {
   switch (rot) {
     case 1: return xorwow_unrotated<1>(s);
@@ -506,11 +404,6 @@ __device__ __forceinline__ Xorwow xorwow_rotated4(const Xorwow &s) {
   "v_mul_f64 %[a], %[r], %[r]\n\t"                    \
   "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"              \
   "v_cmpx_nlt_f64_e32 vcc, 0x40300000, %[a]\n\t"
-#define CB_STEP_NOTEST                                \
-  "v_mul_f64 %[a], %[i], %[i]\n\t"                    \
-  "v_fma_f64 %[a], %[r], %[r], -%[a]\n\t"             \
-  "v_fma_f64 %[i], " CB_AL "%[r]" CB_AR ", " CB_AL "%[i]" CB_AR ", %[ci]\n\t"             \
-  "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"
 // map / shift / cols / rows: the interior map (DrawArgs::interior_map; map = 0: none).  The cell of every popped c is
 // looked up while the stage iterates -- column floor((Cr + 4) 2^shift), row floor(|Ci| 2^shift) on doubled coordinates,
 // one byte load per lane behind the LDS reads, waited for in front of the push -- and a lane whose cell is marked is not
@@ -708,35 +601,6 @@ __device__ __forceinline__ void iterate_chunk4(uint32_t enable, const unsigned l
   esc[3] = mask[3] & (d3 | c3);
   doubt = (mask[0] & c0) | (mask[1] & c1) | (mask[2] & c2) | (mask[3] & c3);
 }
-
-// The exact decision for the lanes of `doubt` (draw_wave.hip, verify_chunk_escape): did the orbit with starting
-// point (cr, ci) escape during the kChunk iterations after its first `done` ones?
-__device__ __forceinline__ unsigned long long verify_chunk_escape(unsigned long long doubt, const Orbit &o,
-                                                                  int done) {
-  bool escaped = false;
-  if (lane_in(doubt)) {
-    double r = o.cr, i = o.ci;
-    for (int k = 0; k < done; ++k) {
-#ifdef CB_BURNING_SHIP
-      (void) mandel_step2_ship(o.cr, o.ci, r, i);
-#else
-      (void) mandel_step2(o.cr, o.ci, r, i);
-#endif
-    }
-    for (int k = 0; k < kChunk && !escaped; ++k) {
-#ifdef CB_BURNING_SHIP
-      escaped = mandel_step2_ship(o.cr, o.ci, r, i) > 16.0;
-#else
-      escaped = mandel_step2(o.cr, o.ci, r, i) > 16.0;
-#endif
-    }
-  }
-  return __ballot(escaped);
-}
-
-#define CB_STR2(x) #x
-#define CB_STR(x) CB_STR2(x)
-#define CB_CHUNK_S CB_STR(CB_CHUNK)
 
 // long_refill4 (draw_wave.hip, long_refill, for the four slots in one statement): the idle lanes (l_rem == 0) of
 // every slot in turn take (c, z) from Q1 -- ring slot (q1_head + rank) mod 96 at LDS byte address q1_lds, planes 768
@@ -1038,52 +902,20 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
   "v_cvt_i32_f64 %[col], %[fx]\n\t"                       \
   "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"                  \
   "v_cvt_i32_f64 %[row], %[fy]\n\t"
-// Cache policy of the stream's stores (gfx942+ bits: sc0, sc1, nt), as text behind the instruction.  The stream is
-// written once and read once, a launch later.
-#ifndef CB_STREAM_STORE_POLICY_ID  // (a number, so that a sweep can pass it through make: tools/gpu_define_sweep.sh)
-#define CB_STREAM_STORE_POLICY_ID 0
-#endif
-#if CB_STREAM_STORE_POLICY_ID == 0
-#define CB_STREAM_STORE_POLICY ""
-#elif CB_STREAM_STORE_POLICY_ID == 1
-#define CB_STREAM_STORE_POLICY " nt"
-#elif CB_STREAM_STORE_POLICY_ID == 2
-#define CB_STREAM_STORE_POLICY " sc1"
-#elif CB_STREAM_STORE_POLICY_ID == 3
-#define CB_STREAM_STORE_POLICY " sc0 sc1"
-#elif CB_STREAM_STORE_POLICY_ID == 4
-#define CB_STREAM_STORE_POLICY " sc0 sc1 nt"
-#elif CB_STREAM_STORE_POLICY_ID == 5
-#define CB_STREAM_STORE_POLICY " sc0"
-#elif CB_STREAM_STORE_POLICY_ID == 6
-#define CB_STREAM_STORE_POLICY " sc1 nt"
-#endif
-#ifdef CB_EXPERIMENT_PACKED24  /* timing only: 3-byte entries, two stores per step (the sort does not read them) */
-#define CBW_REPLAY_WORD "v_lshl_or_b32 %[e], %[row], 12, %[col]\n\t"
-#define CBW_REPLAY_PLACE "v_add_u32 %[pidx], %[pidx], %[fill]\n\t" "v_mul_u32_u24 %[pidx], 3, %[pidx]\n\t"
-#define CBW_REPLAY_STORE "global_store_short %[pidx], %[e], %[base]\n\t" "global_store_byte_d16_hi %[pidx], %[e], %[base] offset:2\n\t"
-#elif defined(CB_EXPERIMENT_NO_STREAM_STORE)  /* timing only: the replay without its store (one-level streams) */
-#define CBW_REPLAY_WORD "v_lshl_or_b32 %[e], %[row], 16, %[col]\n\t"
-#define CBW_REPLAY_PLACE "v_add_lshl_u32 %[pidx], %[pidx], %[fill], 2\n\t"
-#define CBW_REPLAY_STORE ""
-#else
-#define CBW_REPLAY_WORD "v_lshl_or_b32 %[e], %[row], 16, %[col]\n\t"
-#define CBW_REPLAY_PLACE "v_add_lshl_u32 %[pidx], %[pidx], %[fill], 2\n\t"
-#define CBW_REPLAY_STORE "global_store_dword %[pidx], %[e], %[base]" CB_STREAM_STORE_POLICY "\n\t"
-#endif
+// The stream's stores keep the default cache policy: the stream is written once and read once, a launch later.
 #define CBW_REPLAY_LOOP                                   \
   CBW_REPLAY_STEP_COMMON                                  \
   "s_and_b64 vcc, vcc, %[hx]\n\t"                         \
   "v_mul_f64 %[a], %[r], %[r]\n\t"                        \
-  CBW_REPLAY_WORD                                         \
+  "v_lshl_or_b32 %[e], %[row], 16, %[col]\n\t"            \
   "v_mbcnt_lo_u32_b32 %[pidx], vcc_lo, 0\n\t"             \
   "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"                  \
   "v_mbcnt_hi_u32_b32 %[pidx], vcc_hi, %[pidx]\n\t"       \
   "s_bcnt1_i32_b64 %[t], vcc\n\t"                         \
-  CBW_REPLAY_PLACE                                        \
+  "v_add_lshl_u32 %[pidx], %[pidx], %[fill], 2\n\t"       \
   "s_and_b64 %[act], %[act], %[alive]\n\t"                \
   "s_mov_b64 exec, vcc\n\t"                               \
-  CBW_REPLAY_STORE                                        \
+  "global_store_dword %[pidx], %[e], %[base]\n\t"         \
   "s_add_u32 %[fill], %[fill], %[t]\n\t"                  \
   "s_mov_b64 exec, %[act]\n\t"                            \
   "s_cbranch_execz 8f\n\t"              /* (not taken but once) */ \
@@ -1139,7 +971,7 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
   "s_andn2_b64 %[over], exec, vcc\n\t"                    \
   "s_mov_b64 exec, vcc\n\t"                               \
   "v_lshlrev_b32 %[pos], 2, %[pos]\n\t"                   \
-  "global_store_dword %[pos], %[e], %[base]" CB_STREAM_STORE_POLICY "\n\t" \
+  "global_store_dword %[pos], %[e], %[base]\n\t"           \
   "s_cmp_lg_u64 %[over], 0\n\t"                           \
   "s_cbranch_scc1 8f\n\t"               /* (the step is complete: it counts) */ \
   "s_mov_b64 exec, %[act]\n\t"                            \
@@ -1425,10 +1257,6 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
   const uint32_t wave_slot = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (3 << 11));  // HW_REG_HW_ID bits 3:0
   uint32_t long_chunks = 0;
   unsigned long long t_head = 0, t_mid = 0, t_long = 0, t_replay = 0;
-#ifdef CB_WIDE_PROBE  // (tools/wide_stage_probe.py: units of work per stage beside the stage clocks)
-  unsigned long long probe_chunks = 0, probe_lane_chunks = 0, probe_replay_steps = 0, probe_bursts = 0;
-  unsigned long long probe_lanes_at_start = 0, probe_lanes_at_end = 0;
-#endif
   const unsigned long long t_start = kTimed ? __builtin_amdgcn_s_memtime() : 0ull;
   const unsigned long long rt_start = kTimed ? __builtin_amdgcn_s_memrealtime() : 0ull;
   const uint32_t q0_lds = __builtin_amdgcn_readfirstlane(
@@ -1478,9 +1306,9 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
     const int rank = __popcll(__ballot(before_me));
     // (the scatter's waves beside these: scatter.hip, CB_SCATTER_PRIO)
     if (rank == 0) {
-      __builtin_amdgcn_s_setprio(CB_WIDE_PRIO_BEHIND);
+      __builtin_amdgcn_s_setprio(kPrioBehind);
     } else {
-      __builtin_amdgcn_s_setprio(CB_WIDE_PRIO_AHEAD);
+      __builtin_amdgcn_s_setprio(kPrioAhead);
     }
   };
   const uint32_t keep_rest = __builtin_amdgcn_readfirstlane(a.drain ? 1u : 0u);  // 0: leave in-flight work to the next launch
@@ -1583,9 +1411,6 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
                    : ((region_fill + 64u * kReplayBurst <= region_cap) ? 0u : 1u);
       ChunkOverflow ovf;
       uint32_t steps = 0, hits = 0, popped;
-#ifdef CB_WIDE_PROBE
-      const uint32_t clock_before = replay_clock;
-#endif
       popped = replay_stage<kPow2, kChunked>(do_replay ? 1u : 0u, pact, (uint32_t) q2_head, (uint32_t) q2_count, q2_lds,
                                              draining ? 1u : (uint32_t) kReplayMin, kReplayBurst, direct, po, p_start,
                                              region, region_fill, replay_clock, steps, hits, cursors_lds, ovf);
@@ -1599,14 +1424,6 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
       n_recorded += popped;
       n_replay += steps;
       n_incr += hits;
-#ifdef CB_WIDE_PROBE
-      if (replay_clock != clock_before) {
-        probe_replay_steps += replay_clock - clock_before;
-        ++probe_bursts;
-        probe_lanes_at_start += (uint32_t) n_replaying + popped;
-        probe_lanes_at_end += (uint32_t) __popcll(pact);
-      }
-#endif
       if (do_replay && __ballot(lane_in(pact) && (replay_clock - p_start) > (uint32_t) max_iter) != 0ull) {
         // cannot happen: the orbit escaped within max_iter steps in an earlier stage
         status |= CB_STATUS_REPLAY_RUNAWAY;
@@ -1732,11 +1549,6 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
       iterate_chunk4(any_full != 0ull ? 1u : 0u, full_mask, lo, esc, doubt, la->sparse_threshold);
       n_iterate += (unsigned long long) kChunk * (unsigned long long) (__popcll(full_mask[0]) + __popcll(full_mask[1]) +
                                                                        __popcll(full_mask[2]) + __popcll(full_mask[3]));
-#ifdef CB_WIDE_PROBE
-      probe_chunks += any_full != 0ull ? 1u : 0u;
-      probe_lane_chunks += (unsigned long long) (__popcll(full_mask[0]) + __popcll(full_mask[1]) + __popcll(full_mask[2]) +
-                                                 __popcll(full_mask[3]));
-#endif
       if (doubt != 0ull) {  // a sample with |c| next to 2 somewhere in the wave: decided exactly, slot by slot
         const double kt = la->sparse_threshold;
 #pragma unroll
@@ -1871,21 +1683,11 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
       __hip_atomic_fetch_add(c + 11, t_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(c + 12, t_replay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(c + 13, t_all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef CB_WIDE_PROBE
-      (void) rt_start;
-      __hip_atomic_fetch_add(c + 14, probe_chunks | (probe_lane_chunks << 28), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(c + 15, probe_replay_steps | (probe_bursts << 36), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
       const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
       __hip_atomic_fetch_max(c + 14, ~rt_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_max(c + 15, rt_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       // (the MID stage's share of cycles_head, in the slot draw_wave_kernel uses for the waves' lifetimes)
-#ifdef CB_WIDE_PROBE
-      __hip_atomic_fetch_add(c + 16, probe_lanes_at_start | (probe_lanes_at_end << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
       __hip_atomic_fetch_add(c + 16, t_mid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     }
   }
 }

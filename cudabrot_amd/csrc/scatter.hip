@@ -41,41 +41,23 @@
 
 #include "kernels.h"
 
-// priority of the sort / gather waves (0..3; tools/gpu_wide_prio.sh sweeps it against draw_wide.hip's CB_WIDE_PRIO_*)
-#ifndef CB_SCATTER_PRIO
-#define CB_SCATTER_PRIO 0
-#endif
-// ... of the region sort while it reads its region / writes its image (few instructions, long waits: worth issuing
-// early), while it ranks (most of its vector and LDS instructions), and of the gather
-#ifndef CB_GATHER_MASKED_ADDS  // (0: never, 1: on canvases of more than 1024 tiles, 2: always -- bin_gather_accumulate_kernel)
-#define CB_GATHER_MASKED_ADDS 1
-#endif
-#ifndef CB_GATHER_SKIP_BLOCKS
-#define CB_GATHER_SKIP_BLOCKS 1
-#endif
-#ifndef CB_LEAN_BATCH
-#define CB_LEAN_BATCH 4  // 16-byte loads a thread of the lean region sort keeps in flight
-#endif
-#ifndef CB_SORT_PRIO_IO
-#define CB_SORT_PRIO_IO 3   // (swept beside the wide draw kernel's 2 / 1, tools/gpu_wide_prio.sh: -5..7 % per step against 0)
-#endif
-#ifndef CB_SORT_PRIO_RANK
-#define CB_SORT_PRIO_RANK CB_SCATTER_PRIO
-#endif
-#ifndef CB_GATHER_PRIO
-#define CB_GATHER_PRIO CB_SCATTER_PRIO
-#endif
-
 namespace cb {
 
 namespace {
 
+// Issue priorities (0..3) of the region sort while it reads its region / writes its image (few instructions, long
+// waits: worth issuing early), while it ranks (most of its vector and LDS instructions), and of the gather.  Swept
+// beside the wide draw kernel's 2 / 1 (draw_wide.hip, kPrioBehind / kPrioAhead): -5..7 % per step against 0.
+constexpr int kSortPrioIo = 3;
+constexpr int kSortPrioRank = 0;
+constexpr int kGatherPrio = 0;
+constexpr uint32_t kLeanBatch = 4;  // 16-byte loads a thread of the lean region sort keeps in flight
+
 constexpr uint32_t kScatterThreads = 512;          // level A
 constexpr uint32_t kChunkEntries = 8192;           // level A: 16 per thread
 constexpr uint32_t kPerThread = kChunkEntries / kScatterThreads;
-// threads of an accumulate workgroup: 1024 where a workgroup has thousands of runs to walk (one level: 0.1 ms of
-// 1.5 at C3), 512 where a tile has few regions (two levels: 2.2 ms instead of 2.3 at 20000^2)
-constexpr uint32_t kAccThreadsWide = 1024, kAccThreadsNarrow = 512;
+// threads of an accumulate workgroup (launch_binned_scatter)
+constexpr uint32_t kAccThreadsWide = 1024;
 constexpr uint32_t kGroupShift = 10;
 static_assert((1u << kGroupShift) == kGroupTiles, "group = tile >> kGroupShift");
 constexpr uint32_t kReplicas = kGroupReplicas;     // level-A keys per group (2..8 measured equal at 20000^2; 16: 5 % slower, 64: 15 %)
@@ -264,17 +246,11 @@ __global__ void __launch_bounds__(256) bin_fill_regions_kernel(BinLayout b) {
 // How many regions one accumulate workgroup gathers from.  A workgroup zeroes and flushes a 64 KiB tile, so it
 // wants many regions; the GPU wants thousands of workgroups, and a canvas of few tiles (the reference's 1000 x
 // 1000 default has 64) would otherwise give a few hundred.  pairs = (tile, region) pairs of the launch.
-#ifndef CB_SLICE_TARGET
-#define CB_SLICE_TARGET 12288
-#endif
-#ifndef CB_SLICE_TARGET_TWO_LEVEL
-#define CB_SLICE_TARGET_TWO_LEVEL 6144
-#endif
-constexpr uint32_t kSliceTargetGroups = CB_SLICE_TARGET;
+constexpr uint32_t kSliceTargetGroups = 12288;
 // ... on a canvas of more than 1024 tiles the tiles alone are thousands of workgroups, a tile sees few entries per
 // slice, and what a further slice of a tile costs is a 64 KiB tile zeroed, scanned and flushed once more (C4: 24649
 // tiles; 9.95 -> 9.45 ms per step with half the slices beyond one per tile, and no different with fewer still)
-constexpr uint32_t kSliceTargetGroupsTwoLevel = CB_SLICE_TARGET_TWO_LEVEL;
+constexpr uint32_t kSliceTargetGroupsTwoLevel = 6144;
 static_assert(kSliceTargetGroupsTwoLevel <= kSliceTargetGroups, "the grid of the gather is sized by the larger one");
 constexpr uint32_t kSliceRegionsMin = 512;  // one run per lane: fewer leave waves of the workgroup without work
 constexpr uint32_t kSliceEntriesMin = 32768;  // ... and a workgroup should find a few entries per pixel of its tile
@@ -337,40 +313,17 @@ constexpr uint32_t kDummyPlace = kRegionEntries + 8u;
 // (the reference's default 1000 x 1000 has 64) -- eight replicas of 256.
 template <bool kFewTiles>
 struct SortLds {
-#ifndef CB_CNT_REPLICAS
-#define CB_CNT_REPLICAS 2
-#endif
-  static constexpr uint32_t kReplicas = kFewTiles ? 8u : CB_CNT_REPLICAS;
+  static constexpr uint32_t kReplicas = kFewTiles ? 8u : 2u;
   static constexpr uint32_t kStride = (kFewTiles ? 256u : kGroupTiles) + 16u;  // counters of a replica + the dummy
   static constexpr size_t kBytes =  // counters | wave_totals[16] | chunks of the region[32] {first word, words} | image
       (kReplicas * kStride + 16 + 2 * kRegionChunks + 4) * sizeof(uint32_t) + (kRegionEntries + 16) * sizeof(uint16_t);
 };
 constexpr uint32_t kFewTilesMax = 256;
-#ifndef CB_SORT_GRID
-#define CB_SORT_GRID 32768
-#endif
-constexpr uint32_t kSortGrid = CB_SORT_GRID;  // workgroups of the region sort (each takes every kSortGrid-th region)
+constexpr uint32_t kSortGrid = 32768;  // workgroups of the region sort (each takes every kSortGrid-th region)
 // The lean instance takes kRunBatch CONSECUTIVE regions at a time and publishes a tile's run starts in them as ONE
 // 16-byte store: run_start is [tile][region], a region's 1024 run starts lie a row apart, and as 2-byte stores each
 // costs the fabric a sector of its own (C3: 44 MB of table, 1.2 GB written; C4: 87 MB, 2.3 GB).
-#ifndef CB_RUN_BATCH
-#define CB_RUN_BATCH 8
-#endif
-constexpr uint32_t kRunBatch = CB_RUN_BATCH;  // 8 (16-byte stores), or 1: a store of 2 bytes per tile and region
-
-// 16 bytes of the stream, which the sort reads once (CB_SORT_NT_LOADS: as a non-temporal load)
-#ifndef CB_SORT_NT_LOADS
-#define CB_SORT_NT_LOADS 0
-#endif
-__device__ __forceinline__ uint4 stream_load16(const uint4 *p) {
-#if CB_SORT_NT_LOADS
-  typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
-  const U32x4 v = __builtin_nontemporal_load(reinterpret_cast<const U32x4 *>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
+constexpr uint32_t kRunBatch = 8;  // eight 2-byte run starts: one 16-byte store
 
 // kPlain: one plane and the plain word row << 16 | col (every render that is not a fused multi-channel one):
 // tile and offset with constant shifts instead of the layout's run-time fields.
@@ -394,7 +347,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
   constexpr uint32_t kDummyKey = kCntStride - 16u;  // the counter behind a replica's real ones
   // Beside the two-waves-per-SIMD draw kernel (draw_wide.hip) these waves share their SIMDs with draw waves that
   // never wait for memory: the scatter issues little and waits a lot, so it goes first when it can issue.
-  __builtin_amdgcn_s_setprio(CB_SORT_PRIO_IO);
+  __builtin_amdgcn_s_setprio(kSortPrioIo);
   extern __shared__ uint32_t lds[];
   uint32_t *cnt = lds + (threadIdx.x % kCntReplicas) * kCntStride;  // this lane's replica
   uint32_t *wave_totals = lds + kCntReplicas * kCntStride;
@@ -465,7 +418,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     const uint32_t image_at = (uint32_t) reinterpret_cast<uintptr_t>(static_cast<void *>(image));
     const uint4 *src4 = reinterpret_cast<const uint4 *>(src);
     const uint32_t tiles_x = b.tiles_x;
-    constexpr uint32_t kBatch = kChunked ? 2u : CB_LEAN_BATCH;  // 16-byte loads in flight per thread (chunked: 64-bit addresses)
+    constexpr uint32_t kBatch = kChunked ? 2u : kLeanBatch;  // 16-byte loads in flight per thread (chunked: 64-bit addresses)
     // kMasked: a region that is not full (a wave's last): loads clamped to the region, the slots beyond it count into the
     // replica's dummy counter and are not placed -- two or three more instructions per entry, on a tenth of them
     const auto sort_region = [&](auto masked) {
@@ -493,9 +446,9 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
         if (kChunked) {  // (a chunk the region does not have: {0, 0} -- the start of the stream, no words)
           const uint2 cd = chunks[4u * (part * kBatch + j) + my_chunk];
           words_g[j] = cd.y;
-          v[j] = stream_load16(&src4[(size_t) (cd.x >> 2) + in_chunk]);
+          v[j] = src4[(size_t) (cd.x >> 2) + in_chunk];
         } else {
-          v[j] = stream_load16(&src4[kMasked ? (i4 < last4 ? i4 : last4) : i4]);
+          v[j] = src4[kMasked ? (i4 < last4 ? i4 : last4) : i4];
         }
       }
 #pragma unroll
@@ -536,11 +489,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
       }
       uint32_t first = sort_exclusive_scan(sum, wave_totals);
       __syncthreads();
-      if (kRunBatch == 8u) {
-        push_run(first >> 1);  // (a thread beyond the group's tiles: the region's entries, which nobody reads)
-      } else if (threadIdx.x < nk) {
-        b.run_start[(size_t) threadIdx.x * b.max_regions + r] = (uint16_t) (first >> 1);
-      }
+      push_run(first >> 1);  // (a thread beyond the group's tiles: the region's entries, which nobody reads)
 #pragma unroll
       for (uint32_t k = 0; k < kCntReplicas; ++k) {
         if (has_key) lds[k * kCntStride + threadIdx.x] = image_at + first;
@@ -548,7 +497,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
       }
     }
     __syncthreads();
-    __builtin_amdgcn_s_setprio(CB_SORT_PRIO_RANK);
+    __builtin_amdgcn_s_setprio(kSortPrioRank);
 #pragma unroll
     for (uint32_t g = 0; g < kSortPerThread / 8u; ++g) {  // 3. rank and place, eight entries' atomics in flight
       if (beyond(2u * g)) break;  // (groups 2 g and 2 g + 1: beyond the region)
@@ -571,7 +520,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
       asm volatile("" ::: "memory");
     }
     __syncthreads();
-    __builtin_amdgcn_s_setprio(CB_SORT_PRIO_IO);
+    __builtin_amdgcn_s_setprio(kSortPrioIo);
     {  // 4. the image leaves as one linear block
       const uint4 *s4 = reinterpret_cast<const uint4 *>(image);
       uint4 *d4 = reinterpret_cast<uint4 *>(b.sorted + start);
@@ -663,7 +612,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     }
   }
   __syncthreads();
-  __builtin_amdgcn_s_setprio(CB_SORT_PRIO_RANK);
+  __builtin_amdgcn_s_setprio(kSortPrioRank);
   // 2. where each tile's run starts: exclusive scan of the counts; published as run_start[tile][region]
   {
     const bool has_key = threadIdx.x < kDummyKey;  // (with few tiles most threads only take part in the scan)
@@ -694,7 +643,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     image[real ? shift + pos : kDummyPlace] = (uint16_t) e[k];
   }
   __syncthreads();
-  __builtin_amdgcn_s_setprio(CB_SORT_PRIO_IO);
+  __builtin_amdgcn_s_setprio(kSortPrioIo);
   // 4. the image leaves as one linear block: image[shift + i] -> sorted[start + i]
   uint16_t *dst = b.sorted + (start - shift);  // 16-byte aligned; index = position in the image
   const uint32_t lo = shift, hi = shift + n;
@@ -711,7 +660,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
   if (kChunked && threadIdx.x == 0) b.region_count[r] = n;  // from chunks to entries (every region is sorted once)
   }  // (not the lean instance)
   }  // regions of the batch
-  if (kLean && kRunBatch == 8u && threadIdx.x < (b.n_tiles < kGroupTiles ? b.n_tiles : kGroupTiles)) {
+  if (kLean && threadIdx.x < (b.n_tiles < kGroupTiles ? b.n_tiles : kGroupTiles)) {
     *reinterpret_cast<uint4 *>(b.run_start + (size_t) threadIdx.x * b.max_regions + r_batch) =
         make_uint4(runs[0], runs[1], runs[2], runs[3]);
   }
@@ -727,7 +676,7 @@ __global__ void __launch_bounds__(kAccThreads) bin_gather_accumulate_kernel(BinL
                                                                             unsigned long long *hist,
                                                                             int w, int h) {
   __shared__ uint32_t tile[kTilePixels];  // 64 KiB
-  __builtin_amdgcn_s_setprio(CB_GATHER_PRIO);  // (see bin_region_sort_kernel)
+  __builtin_amdgcn_s_setprio(kGatherPrio);  // (see bin_region_sort_kernel)
   // which (tile, slice) is this workgroup?  slice_base is an exclusive prefix: binary search
   const uint32_t s = blockIdx.x;
   if (s >= b.slice_base[b.n_tiles]) return;  // the grid is an upper bound
@@ -801,10 +750,10 @@ __global__ void __launch_bounds__(kAccThreads) bin_gather_accumulate_kernel(BinL
           // so most rounds end after one or two of their four blocks -- beside the draw kernel the gather's vector
           // instructions are what it costs)
           const uint32_t i0 = at + 8u * j;
-          if (CB_GATHER_SKIP_BLOCKS && __ballot(i0 < len) == 0ull) break;
+          if (__ballot(i0 < len) == 0ull) break;
           const uint32_t words[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
           // a block that lies inside the run in every lane (the runs of a hot tile are long, and alike): no tests
-          if (CB_GATHER_SKIP_BLOCKS && __ballot(i0 < lead || i0 + 8u > len) == 0ull) {
+          if (__ballot(i0 < lead || i0 + 8u > len) == 0ull) {
 #pragma unroll
             for (uint32_t q = 0; q < 8; ++q) lds_inc(&tile[(words[q >> 1] >> ((q & 1u) * 16u)) & 0xffffu]);
             continue;
@@ -1243,9 +1192,7 @@ BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t 
 // registers each, two per SIMD -- land behind them, and what they leave free on a SIMD is no longer one block of 256
 // registers: the region sort's workgroup (four waves of 64 on every SIMD of a CU) then fits nowhere until draw waves
 // exit, i.e. the sort runs AFTER the draw instead of beside it (C4: a step of 12.1 ms instead of 9.4, every other step).
-#ifndef CB_CHAIN_DELAY_US
-#define CB_CHAIN_DELAY_US 40
-#endif
+constexpr uint32_t kChainDelayUs = 40;
 __global__ void __launch_bounds__(64) chain_delay_kernel(uint32_t ticks) {
   const unsigned long long t0 = wall_clock64();  // 100 MHz
   for (uint32_t turn = 0; turn < 4096u && wall_clock64() - t0 < ticks; ++turn) __builtin_amdgcn_s_sleep(32);
@@ -1254,7 +1201,7 @@ __global__ void __launch_bounds__(64) chain_delay_kernel(uint32_t ticks) {
 hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, int w, int h,
                                  hipStream_t stream) {
   if (!b.enabled) return hipSuccess;
-  if (CB_CHAIN_DELAY_US) hipLaunchKernelGGL(chain_delay_kernel, dim3(1), dim3(64), 0, stream, CB_CHAIN_DELAY_US * 100u);
+  hipLaunchKernelGGL(chain_delay_kernel, dim3(1), dim3(64), 0, stream, kChainDelayUs * 100u);
   if (b.chunked) {
     hipLaunchKernelGGL(chunk_count_kernel, dim3(b.n_waves), dim3(64), 0, stream, b);
     hipLaunchKernelGGL(group_scan_rows_kernel, dim3(b.n_groups), dim3(256), 0, stream, b);
@@ -1280,14 +1227,7 @@ hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, i
                      b.e_chan_mask == 0u;
   const bool few = b.n_tiles <= kFewTilesMax;
   uint32_t skip_lean = 0u;
-#ifndef CB_SORT_LDS_PAD  // (a measuring switch: more LDS per sort workgroup than it needs -- 16384 leaves room for ONE per CU)
-#define CB_SORT_LDS_PAD 0
-#endif
-#ifndef CB_GATHER_LDS_PAD  // (likewise for the gather, whose 64 KiB tile is static)
-#define CB_GATHER_LDS_PAD 0
-#endif
   const auto launch_sort = [&](auto kernel, size_t lds_bytes, uint32_t batch = 1u) -> hipError_t {
-    lds_bytes += CB_SORT_LDS_PAD;
     // per call: the attribute belongs to the current device
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);  // ~74 KiB of the 160 per CU
@@ -1299,13 +1239,8 @@ hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, i
   };
   hipError_t se;
   if (b.chunked) {
-#ifndef CB_NO_LEAN_SORT
     se = plain ? launch_sort(bin_region_sort_kernel<true, false, true, true>, SortLds<false>::kBytes, kRunBatch)
-#else
-    se = plain ? launch_sort(bin_region_sort_kernel<true, false, true>, SortLds<false>::kBytes)
-#endif
                : launch_sort(bin_region_sort_kernel<false, false, true>, SortLds<false>::kBytes);
-#ifndef CB_NO_LEAN_SORT
   } else if (plain && !b.two_level && b.tiles_x <= 128u) {  // (columns below 16384: the lean instance's word)
     // the full regions first (lean instance: 10 vector instructions per entry), then the waves' last, partial ones
     se = few ? launch_sort(bin_region_sort_kernel<true, true, false, true>, SortLds<true>::kBytes, kRunBatch)
@@ -1317,7 +1252,6 @@ hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, i
       se = few ? launch_sort(bin_region_sort_kernel<true, true>, SortLds<true>::kBytes)
                : launch_sort(bin_region_sort_kernel<true, false>, SortLds<false>::kBytes);
     }
-#endif
   } else if (few) {
     se = plain ? launch_sort(bin_region_sort_kernel<true, true>, SortLds<true>::kBytes)
                : launch_sort(bin_region_sort_kernel<false, true>, SortLds<true>::kBytes);
@@ -1332,21 +1266,13 @@ hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, i
   const unsigned long long slices = b.n_tiles + (by_cap > kSliceTargetGroups ? by_cap : kSliceTargetGroups) + 1ull;
   // 1024 threads per workgroup on every canvas.  (Canvases of more than 1024 tiles had 512, for two workgroups per CU
   // with the GPU to themselves; beside the draw launch there is LDS for ONE 64 KiB tile per CU either way, and a
-  // workgroup of 1024 threads has twice the runs in flight: C4 +3 %, tools/gpu_define_sweep.sh.)
-#ifndef CB_GATHER_NARROW_TWO_LEVEL
-#define CB_GATHER_NARROW_TWO_LEVEL 0
-#endif
-  const bool masked = CB_GATHER_MASKED_ADDS == 2 || (CB_GATHER_MASKED_ADDS == 1 && b.two_level);
-  const auto launch_gather = [&](auto kernel, uint32_t threads) {
-    hipLaunchKernelGGL(kernel, dim3((uint32_t) slices), dim3(threads), CB_GATHER_LDS_PAD, stream, b, hist, w, h);
+  // workgroup of 1024 threads has twice the runs in flight: C4 +3 %, measured.)  Masked adds on canvases of more than
+  // 1024 tiles (bin_gather_accumulate_kernel).
+  const auto launch_gather = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t) slices), dim3(kAccThreadsWide), 0, stream, b, hist, w, h);
   };
-  if (b.two_level && CB_GATHER_NARROW_TWO_LEVEL) {
-    if (masked) launch_gather(bin_gather_accumulate_kernel<kAccThreadsNarrow, true>, kAccThreadsNarrow);
-    else launch_gather(bin_gather_accumulate_kernel<kAccThreadsNarrow, false>, kAccThreadsNarrow);
-  } else {
-    if (masked) launch_gather(bin_gather_accumulate_kernel<kAccThreadsWide, true>, kAccThreadsWide);
-    else launch_gather(bin_gather_accumulate_kernel<kAccThreadsWide, false>, kAccThreadsWide);
-  }
+  if (b.two_level) launch_gather(bin_gather_accumulate_kernel<kAccThreadsWide, true>);
+  else launch_gather(bin_gather_accumulate_kernel<kAccThreadsWide, false>);
   return hipGetLastError();
 }
 
