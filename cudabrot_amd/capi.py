@@ -24,6 +24,7 @@ CB_KERNEL_FULL_ITERATE = 3
 CB_TONE_AUTO, CB_TONE_LUT, CB_TONE_THRESHOLDS = 0, 1, 2
 CB_KERNEL_FLAG_BURNING_SHIP = 0x100
 CB_KERNEL_FLAG_DRAIN = 0x200
+CB_KERNEL_FLAG_ANTI = 0x400  # the anti-Buddhabrot (with CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE; no channels)
 # cb_counters.status bits (include/cudabrot_amd.h)
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1

@@ -24,6 +24,9 @@ namespace {
     if (cb_e_ != hipSuccess) return (int) cb_e_; \
   } while (0)
 
+// The flags a kernel variant may carry beside its base (CB_KERNEL_DEFAULT ... CB_KERNEL_FULL_ITERATE).
+constexpr int kVariantFlags = CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN | CB_KERNEL_FLAG_ANTI;
+
 // One copy of the jump matrices per device, created on first use and kept for the process lifetime.
 std::mutex g_matrix_mutex;
 const uint32_t *g_matrices[64] = {nullptr};
@@ -131,15 +134,18 @@ const DeviceMap *device_map(MapKind kind) {
 
 // The interior map for a launch of the wave-scheduled kernels (their MID stage in its one-piece form looks samples up;
 // the lock-step kernel and the other forms ignore it): where orbits may be retired early at all -- not the Burning
-// Ship, not the full-iterate variants (CUDABROT_AMD_NO_INTERIOR_MAP=1, a test knob: never).  0, or an error: a map that
-// should be there and is not is never passed over in silence.
-bool wants_interior_map(bool ship, int base_variant) {
-  return !(ship || base_variant == CB_KERNEL_FULL_ITERATE || base_variant == CB_KERNEL_SIMPLE ||
+// Ship, not the full-iterate variants, not the anti-Buddhabrot, which plots exactly the samples the map retires
+// (CUDABROT_AMD_NO_INTERIOR_MAP=1, a test knob: never).  0, or an error: a map that should be there and is not is never
+// passed over in silence.
+bool wants_interior_map(int kernel_variant) {
+  const int base_variant = kernel_variant & ~kVariantFlags;
+  return !((kernel_variant & (CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_ANTI)) != 0 ||
+           base_variant == CB_KERNEL_FULL_ITERATE || base_variant == CB_KERNEL_SIMPLE ||
            cb_debug_knob("CUDABROT_AMD_TIMED_FULL") != nullptr || cb_debug_knob("CUDABROT_AMD_NO_INTERIOR_MAP") != nullptr);
 }
-int attach_interior_map(cb::DrawArgs &a, bool ship, int base_variant) {
+int attach_interior_map(cb::DrawArgs &a, int kernel_variant) {
   g_interior_level.store(0, std::memory_order_relaxed);
-  if (!wants_interior_map(ship, base_variant)) return 0;
+  if (!wants_interior_map(kernel_variant)) return 0;
   const DeviceMap *m = device_map(kMapInterior);
   if (!m) return (int) hipErrorInvalidValue;
   a.interior_map = m->d_bytes;
@@ -292,7 +298,8 @@ namespace {
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
 int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
-  const bool wave = (kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN)) != CB_KERNEL_SIMPLE;
+  // the lock-step kernel and the anti kernels: direct atomics, no deferred scatter, no carry
+  const bool wave = (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE && (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0;
   const bool deferred = r->d_workspace[0] && wave;
   const int k = r->next_workspace;
   if (deferred && r->flush_pending[k]) {
@@ -314,9 +321,7 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   }
   if (rc) return rc;
   {
-    const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-    const int base = kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN);
-    const DeviceMap *m = wants_interior_map(ship, base) ? device_map(kMapInterior) : nullptr;
+    const DeviceMap *m = wants_interior_map(kernel_variant) ? device_map(kMapInterior) : nullptr;
     r->interior_level = m ? (int) m->level : 0;
   }
   if (wave && r->d_carry) {
@@ -509,14 +514,17 @@ int cb_draw_buddhabrot(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
   if (!dims || !iterations || !d_hist || !d_states) return (int) hipErrorInvalidValue;
   if (dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  const int base_variant = kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN);
-  if (base_variant == CB_KERNEL_SIMPLE) {  // the baseline kernel: atomics, every launch complete
+  const int base_variant = kernel_variant & ~kVariantFlags;
+  const bool anti = (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0;
+  if (anti && base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE) return (int) hipErrorInvalidValue;
+  if (base_variant == CB_KERNEL_SIMPLE || anti) {  // the baseline and the anti kernels: atomics, every launch complete
     d_workspace = nullptr;
     d_carry = nullptr;
   }
   cb::DrawArgs a = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread,
                              d_counters, d_workspace, workspace_bytes, d_carry);
   a.burning_ship = ship ? 1 : 0;
+  a.anti = anti ? 1 : 0;
   if ((kernel_variant & CB_KERNEL_FLAG_DRAIN) && a.carry) a.drain = 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {
@@ -525,8 +533,13 @@ int cb_draw_buddhabrot(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
   }
   const auto wave = ship ? cb::launch_draw_wave_ship : cb::launch_draw_wave;
   {
-    const int rc = attach_interior_map(a, ship, base_variant);
+    const int rc = attach_interior_map(a, kernel_variant);
     if (rc) return rc;
+  }
+  if (anti) {  // draw_anti.hip: the product kernel (4) or the lock-step one (5)
+    const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
+    g_last_draw_kernel.store(lockstep ? 5 : 4, std::memory_order_relaxed);
+    return (int) cb::launch_draw_anti(a, lockstep, s);
   }
   // the two-waves-per-SIMD kernel where it applies (CUDABROT_AMD_NO_WIDE=1, a test knob: never)
   const bool wide = cb::draw_wide_takes(a) && cb_debug_knob("CUDABROT_AMD_NO_WIDE") == nullptr;
@@ -568,9 +581,10 @@ int cb_draw_buddhabrot_channels(const cb_fractal_dimensions *dims, cb_pixel *d_h
     return (int) hipErrorInvalidValue;
   }
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  const int base_variant = kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN);
-  if (base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_FULL_ITERATE) {
-    return (int) hipErrorInvalidValue;  // the wave-scheduled kernel only
+  const int base_variant = kernel_variant & ~kVariantFlags;
+  if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_FULL_ITERATE) ||
+      (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0) {
+    return (int) hipErrorInvalidValue;  // the wave-scheduled kernel only; no anti channels
   }
   // the kernel iterates to the largest max; what escapes before the smallest min is in no window
   cb_iteration_control hull = windows[0];
@@ -598,7 +612,7 @@ int cb_draw_buddhabrot_channels(const cb_fractal_dimensions *dims, cb_pixel *d_h
     if (rc) return rc;
   }
   {
-    const int rc = attach_interior_map(a, ship, base_variant);
+    const int rc = attach_interior_map(a, kernel_variant);
     if (rc) return rc;
   }
   const auto wave = ship ? cb::launch_draw_wave_ship : cb::launch_draw_wave;
@@ -683,14 +697,15 @@ uint32_t max_passes_per_launch() {
 // What a renderer allocates on first use, because it depends on the kernel variant: the two scatter
 // workspaces (tens of GB on a large canvas -- hipMalloc of that size can take seconds).
 void prepare_for_variant(cb_renderer *r, int kernel_variant) {
-  if ((kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN)) == CB_KERNEL_TIMED && cb_debug_knob("CUDABROT_AMD_WAVE_DUMP") &&
+  if ((kernel_variant & ~kVariantFlags) == CB_KERNEL_TIMED && cb_debug_knob("CUDABROT_AMD_WAVE_DUMP") &&
       !g_wave_dump) {
     const size_t bytes = (size_t) cb::draw_wave_count(r->n_threads) * 8 * sizeof(unsigned long long);
     if (hipMalloc(&g_wave_dump, bytes) != hipSuccess || hipMemset(g_wave_dump, 0, bytes) != hipSuccess) {
       g_wave_dump = nullptr;
     }
   }
-  if (!r->workspace_tried && (kernel_variant & ~(CB_KERNEL_FLAG_BURNING_SHIP | CB_KERNEL_FLAG_DRAIN)) != CB_KERNEL_SIMPLE &&
+  if (!r->workspace_tried && (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE &&
+      (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0 &&  // the anti kernels add directly
       cb_debug_knob("CUDABROT_AMD_NO_WORKSPACE") == nullptr) {
     // scatter workspace for the largest launch render_passes makes; on any failure: direct atomics
     r->workspace_tried = 1;

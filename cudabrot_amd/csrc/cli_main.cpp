@@ -13,7 +13,8 @@
 //  * reference passes (512*512 threads x 50 samples) are fused into launches of about 0.2 s, so -t and
 //    Ctrl+C act at launch granularity; the printed pass count still counts reference-sized passes;
 //  * extension flags, which the reference answers with its usage text: --passes N, --kernel NAME,
-//    --stats, --tonemap FORM, --seed N, --rng-state FILE, --burning-ship, --channel MAX:MIN:FILE, --gpus N,
+//    --stats, --tonemap FORM, --seed N, --rng-state FILE, --burning-ship, --anti (the anti-Buddhabrot: the orbits
+//    that never escape, include/cudabrot_amd.h CB_KERNEL_FLAG_ANTI), --channel MAX:MIN:FILE, --gpus N,
 //    --state-format native|raw (raw: the -s file as the reference's bare buffer, uint32 when every count fits),
 //    --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W (the three --channel planes composed into
 //    one 16-bit PPM: include/cudabrot_amd.h, "Colour image").
@@ -53,6 +54,7 @@ struct Settings {
   int kernel_variant = CB_KERNEL_DEFAULT;           // --kernel (extension)
   bool print_stats = false;                         // --stats  (extension)
   bool burning_ship = false;                        // --burning-ship (extension; cudabrot.cu:15-17)
+  bool anti = false;                                // --anti (extension): the anti-Buddhabrot, CB_KERNEL_FLAG_ANTI
   int gpus = 1;                                     // --gpus N (extension): devices -d .. -d + N - 1
   // --channel MAX:MIN:FILE (extension, repeatable): fused multi-channel render, one image per window
   int n_channels = 0;
@@ -195,6 +197,8 @@ const std::vector<Flag> &flag_table() {
        [](Settings &s, long i, double, const char *) { s.gpus = (i < 1) ? 1 : (i > 64 ? 64 : (int) i); }},
       {"--burning-ship", Value::kNone, nullptr, false,
        [](Settings &s, long, double, const char *) { s.burning_ship = true; }},
+      {"--anti", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.anti = true; }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -325,6 +329,10 @@ Settings parse_arguments(int argc, char **argv) {
       usage_and_exit(argv[0]);
     }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  if (s.anti && (s.n_channels > 0 || s.color_file)) {  // no fused anti channels (include/cudabrot_amd.h)
+    printf("--anti does not combine with --channel.\n");
+    usage_and_exit(argv[0]);
   }
   if (s.color_file && s.n_channels != 3) {  // after parsing: --color and the --channel flags come in any order
     printf("--color needs exactly 3 --channel images, got %d.\n", s.n_channels);
@@ -521,7 +529,8 @@ class Run {
       }
     }
     fflush(stdout);
-    const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0);
+    const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0) |
+                        (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));
     for (cb_renderer *p : peers_) CB_CHECK(cb_renderer_prepare(p, variant));

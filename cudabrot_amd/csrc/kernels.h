@@ -158,6 +158,9 @@ struct DrawArgs {
   // the reference's RENDER_BURNING_SHIP variant (cudabrot.cu:15-17); read by draw_simple_kernel, the
   // wave kernel has a build of its own for it (launch_draw_wave_ship)
   int burning_ship;
+  // CB_KERNEL_FLAG_ANTI: the anti-Buddhabrot (the orbits that never escape, draw_anti.hip); read by the capi's
+  // dispatch only, the anti kernels are the only ones launched with it set
+  int anti;
   // Fused multi-channel render: n_channels > 0 windows [chan_min[j], chan_max[j]) of
   // the escape index; max_iter / min_iter above are then the largest max and the smallest min, and an
   // orbit is replayed once into every channel whose window holds its escape index.  hist is
@@ -200,6 +203,9 @@ hipError_t launch_draw_wave_ship(const DrawArgs &a, bool timed, hipStream_t stre
 bool draw_wide_takes(const DrawArgs &a);
 hipError_t launch_draw_wide(const DrawArgs &a, bool timed, hipStream_t stream);
 hipError_t launch_draw_wide_ship(const DrawArgs &a, bool timed, hipStream_t stream);
+// draw_anti.hip: the anti-Buddhabrot, lockstep = draw_anti_simple_kernel (the definition, lane per thread) or the
+// cycle-compressed draw_anti_kernel; a.burning_ship picks the step.  Direct atomics, no workspace, no carry.
+hipError_t launch_draw_anti(const DrawArgs &a, bool lockstep, hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

@@ -106,6 +106,26 @@ typedef struct {
  * render.  A launch with samples_per_thread = 0 does only that. */
 #define CB_KERNEL_FLAG_DRAIN 0x200
 
+/* OR-ed into CB_KERNEL_DEFAULT (the cycle-compressed product kernel) or CB_KERNEL_SIMPLE (the lock-step kernel), with or
+ * without CB_KERNEL_FLAG_BURNING_SHIP: the ANTI-Buddhabrot, the orbits of the samples that do NOT escape.
+ * Normative:
+ *   samples: the same stream as a normal render (same subsequences, 4 XORWOW draws per sample); the step is the
+ *   canonical fp64 step of the variant.  With z_0 = c, z_k = step(z_{k-1}) and M = max_escape_iterations, a sample
+ *   ESCAPES if |z_k|^2 > 4 for some 1 <= k <= M.  No cardioid / bulb rejection, no interior map.
+ *   recorded: a non-escaping sample adds z_1 .. z_M, M points, each binned as a normal replay bins its points; an
+ *   escaping sample adds nothing.  min_escape_iterations is ignored; M <= 0 records nothing.
+ *   counters: samples as usual; rejected 0; never_escaped = recorded = the non-escaping samples; too_fast = the
+ *   escaping samples; iterate_steps = sum of k over the escapers + M per non-escaping sample (what the definition
+ *   executes); replay_steps = M * recorded; increments = the weighted in-canvas increments (what the histogram gains);
+ *   skipped_steps = the part of iterate_steps + replay_steps not executed.  All but skipped_steps and the timing fields
+ *   are identical between the two kernels.
+ *   cycle compression (the product kernel): if z_1 .. z_n were tested not escaping and z_n == z_s bit for bit in both
+ *   components, 1 <= s < n <= M, p = n - s, the orbit never escapes and its M points are z_1 .. z_{s-1} with weight 1
+ *   and z_{s+j}, 0 <= j < p, with weight floor((M - s - j) / p) + 1: the same histogram, bit for bit.
+ * An anti launch ignores d_workspace and d_carry and is complete when it ends; cb_draw_buddhabrot_channels refuses it
+ * (hipErrorInvalidValue), as cb_draw_buddhabrot does with any other base variant. */
+#define CB_KERNEL_FLAG_ANTI 0x400
+
 /* RecomputePixelDeltas (cudabrot.cu:505-527).  Returns 1 and fills delta_* if the canvas is valid,
  * else 0 and, if msg is not NULL, *msg points at the reference's message for the failed check. */
 int cb_recompute_pixel_deltas(cb_fractal_dimensions *dims, const char **msg);
@@ -343,7 +363,8 @@ int cb_abi_version(void);
 const char *cb_debug_knob(const char *name);
 /* Which draw kernel the last cb_draw_buddhabrot* call of this process launched (the renderer's calls included):
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
- * scatter), 3 the lock-step baseline.  The kernels give identical results; tests use this to know what they covered. */
+ * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel.  The
+ * kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
  * c-plane whose samples provably never escape: the draw kernel retires them without iterating; made and proven by
