@@ -113,7 +113,8 @@ typedef struct {
  *   canonical fp64 step of the variant.  With z_0 = c, z_k = step(z_{k-1}) and M = max_escape_iterations, a sample
  *   ESCAPES if |z_k|^2 > 4 for some 1 <= k <= M.  No cardioid / bulb rejection, no interior map.
  *   recorded: a non-escaping sample adds z_1 .. z_M, M points, each binned as a normal replay bins its points; an
- *   escaping sample adds nothing.  min_escape_iterations is ignored; M <= 0 records nothing.
+ *   escaping sample adds nothing.  min_escape_iterations is ignored.  M <= 0 tests nothing and adds no point: every
+ *   sample counts as not escaping (never_escaped = recorded = samples) and the step counters stay 0.
  *   counters: samples as usual; rejected 0; never_escaped = recorded = the non-escaping samples; too_fast = the
  *   escaping samples; iterate_steps = sum of k over the escapers + M per non-escaping sample (what the definition
  *   executes); replay_steps = M * recorded; increments = the weighted in-canvas increments (what the histogram gains);

@@ -17,6 +17,14 @@ typedef struct {
       skipped_steps;
 } anti_counters;
 
+/* What mode 1 decided, per render (the census): how many samples had a cycle detected, how many of those at n == M (the
+ * last step allowed), how many with (M - s) % p == 0 / != 0 (the edge of the weight split), the smallest q = (M - s) / p
+ * and the largest p.  min_q and max_p are 0 while cycles == 0.  Tests use it to show that an M reaches the branch it is
+ * meant to reach. */
+typedef struct {
+  uint64_t cycles, at_m, rem_zero, rem_nonzero, min_q, max_p;
+} anti_census;
+
 #define ANTI_CHUNK 60
 
 static inline double step(double cr, double ci, double *r, double *i, int ship) {
@@ -51,9 +59,20 @@ static int brent_save(uint32_t chunks) {
 
 static int same_bits(double a, double b) { return memcmp(&a, &b, sizeof(double)) == 0; }
 
-/* One sample c. */
+static void census_add(anti_census *dst, const anti_census *src) {
+  if (src->cycles > 0) {
+    if (dst->cycles == 0 || src->min_q < dst->min_q) dst->min_q = src->min_q;
+    if (src->max_p > dst->max_p) dst->max_p = src->max_p;
+  }
+  dst->cycles += src->cycles;
+  dst->at_m += src->at_m;
+  dst->rem_zero += src->rem_zero;
+  dst->rem_nonzero += src->rem_nonzero;
+}
+
+/* One sample c; cs (may be NULL) gains what was decided about it. */
 static void anti_sample(const orc_dims *d, uint64_t *hist, int max_iter, int ship, int mode, double cr, double ci,
-                        int atomic, anti_counters *c) {
+                        int atomic, anti_counters *c, anti_census *cs) {
   const int M = max_iter > 0 ? max_iter : 0;
   double r = cr, i = ci, sr = 0.0, si = 0.0;
   int saved = 0, n = 0, s = M + 1, p = 0;
@@ -84,6 +103,10 @@ static void anti_sample(const orc_dims *d, uint64_t *hist, int max_iter, int shi
   c->replay_steps += (uint64_t) M;
   const int end = p > 0 ? s - 1 + p : M;
   c->skipped_steps += (uint64_t) (M - n) + (uint64_t) (M - end);
+  if (cs && p > 0) {
+    const anti_census one = {1u, n == M, (M - s) % p == 0, (M - s) % p != 0, (uint64_t) ((M - s) / p), (uint64_t) p};
+    census_add(cs, &one);
+  }
   r = cr;
   i = ci;
   for (int j = 1; j <= end; ++j) {
@@ -99,32 +122,41 @@ static void counters_add(anti_counters *dst, const anti_counters *src) {
   for (size_t k = 0; k < sizeof(anti_counters) / sizeof(uint64_t); ++k) a[k] += b[k];
 }
 
-/* samples_per_thread samples from each of states[0 .. n_threads), advancing them; n_omp > 0: OpenMP. */
+/* samples_per_thread samples from each of states[0 .. n_threads), advancing them; n_omp > 0: OpenMP.  census (may be
+ * NULL) gains the census of these samples. */
 void anti_draw(const orc_dims *d, uint64_t *hist, int max_iter, int ship, int mode, orc_xorwow *states,
-               uint64_t n_threads, int samples_per_thread, anti_counters *out, int n_omp) {
+               uint64_t n_threads, int samples_per_thread, anti_counters *out, int n_omp, anti_census *census) {
   anti_counters total;
+  anti_census total_cs;
   memset(&total, 0, sizeof(total));
+  memset(&total_cs, 0, sizeof(total_cs));
   const int workers = n_omp > 0 ? n_omp : 1;
 #pragma omp parallel num_threads(workers) if (n_omp > 0)
   {
     anti_counters c;
+    anti_census cs;
     memset(&c, 0, sizeof(c));
+    memset(&cs, 0, sizeof(cs));
 #pragma omp for schedule(dynamic, 16)
     for (int64_t t = 0; t < (int64_t) n_threads; t++) {
       for (int k = 0; k < samples_per_thread; ++k) {
         const double re = orc_uniform_double(&states[t]) * 4.0 - 2.0;
         const double im = orc_uniform_double(&states[t]) * 4.0 - 2.0;
-        anti_sample(d, hist, max_iter, ship, mode, re, im, n_omp > 0, &c);
+        anti_sample(d, hist, max_iter, ship, mode, re, im, n_omp > 0, &c, &cs);
       }
     }
 #pragma omp critical(anti_counters_sum)
-    counters_add(&total, &c);
+    {
+      counters_add(&total, &c);
+      census_add(&total_cs, &cs);
+    }
   }
   counters_add(out, &total);
+  if (census) census_add(census, &total_cs);
 }
 
 /* Given starting points (hand-picked c), one after another. */
 void anti_points(const orc_dims *d, uint64_t *hist, int max_iter, int ship, int mode, const double *re,
-                 const double *im, uint64_t n, anti_counters *out) {
-  for (uint64_t k = 0; k < n; ++k) anti_sample(d, hist, max_iter, ship, mode, re[k], im[k], 0, out);
+                 const double *im, uint64_t n, anti_counters *out, anti_census *census) {
+  for (uint64_t k = 0; k < n; ++k) anti_sample(d, hist, max_iter, ship, mode, re[k], im[k], 0, out, census);
 }

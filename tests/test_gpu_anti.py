@@ -33,20 +33,35 @@ def ref(tmp_path_factory):
     return anti.load(tmp_path_factory.mktemp("anti_ref"))
 
 
-def gpu_anti(cb, w, h, box, max_iter, threads, passes, base, ship=False):
-    """One launch of `passes` reference passes on fresh generators (seed 1337, subsequences [0, threads))."""
+def gpu_anti(cb, w, h, box, max_iter, threads, passes, base, ship=False, *, seed=None, first=0, launches=None,
+             min_iter=20, flags=0, hist0=None, counters0=None, no_counters=False, workspace=None, carry=None):
+    """One launch of `passes` reference passes on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist
+    [h, w], counters dict, cb_debug_last_draw_kernel, generator states as bytes).
+    seed, first: other generators; launches: samples per thread of each launch, one after another on the same states,
+    instead of one of passes x 50; flags: OR-ed into the variant; hist0 (u64 [h, w]) and counters0 (17 u64): what the
+    buffers hold before; no_counters: d_counters = NULL (the counters come back as zeros); workspace = (torch buffer,
+    bytes) and carry (torch buffer): passed to every launch."""
     import torch
 
     dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(w, h, *box)
-    hist = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
+    if hist0 is None:
+        hist = torch.zeros(w * h, dtype=torch.int64, device=dev)
+    else:
+        hist = torch.from_numpy(np.ascontiguousarray(hist0, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
+    if counters0 is None:
+        counters = torch.zeros(17, dtype=torch.int64, device=dev)
+    else:
+        counters = torch.from_numpy(np.ascontiguousarray(counters0, dtype=np.uint64).view(np.int64)).to(dev)
     states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    variant = base | cb.CB_KERNEL_FLAG_ANTI | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
-    cb.draw_buddhabrot(dims, hist.data_ptr(), cb.IterationControl(max_iter, 20), states.data_ptr(), threads,
-                       passes * cb.CB_SAMPLES_PER_THREAD, counters.data_ptr(), variant, stream)
+    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED if seed is None else seed, first, threads, states.data_ptr(), stream)
+    variant = base | cb.CB_KERNEL_FLAG_ANTI | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0) | flags
+    ws_ptr, ws_bytes = (workspace[0].data_ptr(), workspace[1]) if workspace else (0, 0)
+    for samples in ([passes * cb.CB_SAMPLES_PER_THREAD] if launches is None else launches):
+        cb.draw_buddhabrot(dims, hist.data_ptr(), cb.IterationControl(max_iter, min_iter), states.data_ptr(), threads,
+                           samples, 0 if no_counters else counters.data_ptr(), variant, stream, ws_ptr, ws_bytes,
+                           carry.data_ptr() if carry is not None else 0)
     kernel = cb.lib.cb_debug_last_draw_kernel()
     torch.cuda.synchronize()
     names = [f[0] for f in cb.Counters._fields_]

@@ -13,6 +13,9 @@ and demands identical histograms and counters.
     python tools/gpu_fuzz.py [SECONDS] [SEED]      exit 1 at the first mismatch (the trial is printed)
     HEAVY=1 python tools/gpu_fuzz.py ...           product-sized launches and canvases, deferred scatter
                                                    against direct atomics of the same kernel
+    ANTI=1 python tools/gpu_fuzz.py ...            the anti-Buddhabrot (CB_KERNEL_FLAG_ANTI): draw_anti_kernel against
+                                                   draw_anti_simple_kernel, generator states compared as well; M from
+                                                   the edges of its rounds (12 steps) and chunks (60 steps)
 """
 import os
 
@@ -33,8 +36,7 @@ COMPARED = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "ite
             "increments", "status")
 
 
-def trial(rng):
-    t = {}
+def canvas_and_box(rng, t):
     big = rng.random() < 0.15
     t["w"] = rng.choice([1, 2, 7, 64, 100, 128, 129, 255, 256, 333, 512, 640, 1000]) if not big else rng.choice([2048, 3000, 4096])
     t["h"] = rng.choice([1, 3, 8, 64, 100, 127, 128, 200, 256, 384, 512, 777, 1000]) if not big else rng.choice([1024, 2500, 4096])
@@ -49,6 +51,11 @@ def trial(rng):
         t["box"] = (cx - rx, cx + rx, cy - ry, cy + ry)
     else:              # far from the set: almost nothing lands
         t["box"] = (1.0, 3.0, 1.0, 2.5)
+
+
+def trial(rng):
+    t = {}
+    canvas_and_box(rng, t)
     t["max_iter"] = rng.choice([1, 2, 5, 19, 20, 21, 33, 64, 100, 257, 1000, 2000, 5000, 20000])
     t["min_iter"] = rng.choice([0, 1, 2, 19, 20, 21, 32, 40, 99, 1000, 30000])
     t["threads"] = rng.choice([1, 63, 64, 65, 200, 256, 1000, 1024, 4096, 5000, 16384])
@@ -136,6 +143,85 @@ def render(t, variant, window=None, fused=False, on_device=False):
     return hist.cpu().numpy().view(np.uint64), cnt
 
 
+def anti_trial(rng):
+    """An anti launch sequence: M at and around the product kernel's decisions (a round is 12 steps, a chunk 60, the
+    first cycle can be found at 120), ragged thread counts, several launches on the same generators."""
+    t = {}
+    canvas_and_box(rng, t)
+    t["ship"] = rng.random() < 0.3
+    t["max_iter"] = rng.choice([0, 1, 5, 12, 59, 60, 61, 119, 120, 121, 180, 181, 240, 257, 360, 1000, 2000, 5000, 20000])
+    t["threads"] = rng.choice([1, 63, 64, 65, 200, 256, 1000, 1024, 1337, 4096, 5000, 16384])
+    if t["max_iter"] >= 5000:   # keep the lock-step kernel's run time in hand
+        t["threads"] = min(t["threads"], 4096)
+    t["launch_samples"] = [rng.choice([1, 2, 7, 50, 64, 100, 150]) for _ in range(rng.randint(1, 4))]
+    t["seed"] = rng.choice([1337, 1337, 1, 0xdeadbeefcafe])
+    t["first"] = rng.choice([0, 0, 1, 262144, 2097151])
+    t["min_iter"] = rng.choice([0, 1, 20, 99, 1000, 30000])      # ignored by an anti launch
+    t["buffers"] = rng.random() < 0.5                             # workspace and carry given (and ignored) or NULL
+    return t
+
+
+def render_anti(t, variant):
+    """The launches of an anti trial -> (histogram, counters, generator states)."""
+    dev = torch.device("cuda", 0)
+    dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
+    it = cb.IterationControl(t["max_iter"], t["min_iter"])
+    n = t["threads"]
+    flags = cb.CB_KERNEL_FLAG_ANTI | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
+    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
+    hist = torch.zeros(t["w"] * t["h"], dtype=torch.int64, device=dev)
+    counters = torch.zeros(17, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
+    ws_bytes = max(cb.scatter_workspace_bytes(dims, n, max(t["launch_samples"])), 4096) if t["buffers"] else 0
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    carry = torch.zeros(cb.carry_bytes(n) if t["buffers"] else 1, dtype=torch.uint8, device=dev)
+    for s in t["launch_samples"]:
+        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), n, s, counters.data_ptr(), variant | flags,
+                           stream, ws.data_ptr() if t["buffers"] else 0, ws_bytes,
+                           carry.data_ptr() if t["buffers"] else 0)
+    torch.cuda.synchronize()
+    c = counters.cpu().numpy().view(np.uint64)
+    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
+    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
+
+
+def anti_main(seconds, seed):
+    rng = random.Random(seed)
+    t_end = time.time() + seconds
+    n = compressed = 0
+    last_print = time.time()
+    while time.time() < t_end:
+        t = anti_trial(rng)
+        try:
+            want, wc, want_states = render_anti(t, cb.CB_KERNEL_SIMPLE)
+            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 5
+            got, gc, got_states = render_anti(t, cb.CB_KERNEL_DEFAULT)
+            product_ran = cb.lib.cb_debug_last_draw_kernel() == 4
+        except cb.CudabrotError as e:
+            print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
+            return 1
+        bad = [k for k in COMPARED if wc[k] != gc[k]]
+        if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
+                lockstep_ran and product_ran) or wc["skipped_steps"] != 0:
+            print("MISMATCH at anti trial %d (seed %d): %r" % (n, seed, t))
+            print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
+            print("  counters that differ: %r; lock-step skipped_steps %d" % ([(k, wc[k], gc[k]) for k in bad],
+                                                                            wc["skipped_steps"]))
+            print("  generator states identical: %s" % np.array_equal(want_states, got_states))
+            print("  pixels that differ: %d of %d; sums %d vs %d" % (int((want != got).sum()), want.size,
+                                                                     int(want.sum()), int(got.sum())), flush=True)
+            return 1
+        n += 1
+        compressed += 1 if gc["skipped_steps"] > 0 else 0
+        if time.time() - last_print > 30:
+            print("%d anti trials identical so far (%d with skipped_steps > 0)" % (n, compressed), flush=True)
+            last_print = time.time()
+    print("gpu_fuzz: %d anti trials (%d with skipped_steps > 0), histograms, counters and generator states identical "
+          "(seed %d)" % (n, compressed, seed))
+    return 0
+
+
 def heavy_trial(rng):
     """Product-sized launches: the deferred scatter (one and two sort levels, carry) against the same
     kernel with direct atomics -- the lock-step kernel would take minutes at these sizes."""
@@ -205,6 +291,8 @@ def render_with_renderer(t):
 def main():
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    if os.environ.get("ANTI") == "1":
+        return anti_main(seconds, seed)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     n = 0
