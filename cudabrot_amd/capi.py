@@ -25,6 +25,8 @@ CB_TONE_AUTO, CB_TONE_LUT, CB_TONE_THRESHOLDS = 0, 1, 2
 CB_KERNEL_FLAG_BURNING_SHIP = 0x100
 CB_KERNEL_FLAG_DRAIN = 0x200
 CB_KERNEL_FLAG_ANTI = 0x400  # the anti-Buddhabrot (with CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE; no channels)
+CB_FOCUS_MIN_LEVEL, CB_FOCUS_MAX_LEVEL = 4, 10  # focused render: cells of side 2^-level
+CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
 # cb_counters.status bits (include/cudabrot_amd.h)
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
@@ -200,6 +202,12 @@ def _load():
         "cb_compose_color_device": (i32, [C.POINTER(vp), i32, i32, C.c_double, i32, col_p, vp, vp, vp]),
         "cb_renderer_color_image": (i32, [vp, C.POINTER(i32), C.c_double, i32, col_p, vp, vp]),
         "cb_save_ppm_be": (i32, [C.c_char_p, vp, i32, i32]),
+        "cb_focus_mask_bytes": (C.c_size_t, [i32]),
+        "cb_focus_probe": (i32, [dims_p, it_p, vp, u32, u32, i32, vp, vp, i32, vp]),
+        "cb_focus_cells": (i32, [i32, vp, i32, vp, C.POINTER(u32)]),
+        "cb_draw_buddhabrot_focus": (i32, [dims_p, vp, it_p, vp, u32, u32, vp, i32, i32, vp, u32, vp]),
+        "cb_renderer_set_focus": (i32, [vp, i32, u32, i32, i32]),
+        "cb_renderer_focus_cells": (i32, [vp, C.POINTER(u32), C.POINTER(u32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -218,7 +226,8 @@ EXPORTED_SYMBOLS = (
     "cb_renderer_destroy cb_set_grayscale_pixels cb_save_image cb_save_image_be cb_tone_value "
     "cb_tone_map_device cb_renderer_grayscale_image cb_renderer_read_rng_states cb_renderer_write_rng_states "
     "cb_draw_buddhabrot_channels cb_flush_scatter_channels cb_renderer_create_channels cb_renderer_grayscale_plane cb_renderers_reduce "
-    "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be"
+    "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be "
+    "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells"
 ).split()
 
 
@@ -278,6 +287,44 @@ def flush_scatter(dims, d_hist, n_threads, d_workspace, workspace_bytes, stream=
            "cb_flush_scatter")
 
 
+def focus_mask_bytes(level):
+    """Bytes of a focus mask of this level: (4 * 2^level)^2 bits (0 for a level out of range)."""
+    return int(lib.cb_focus_mask_bytes(int(level)))
+
+
+def focus_probe(dims, iterations, d_states, n_threads, samples_per_thread, level, d_mask, d_counters=0,
+                kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The probe of a focused render on caller-owned device memory (integer pointers); ORs into d_mask."""
+    _check(
+        lib.cb_focus_probe(C.byref(dims), C.byref(iterations), d_states, n_threads, samples_per_thread, int(level),
+                           d_mask, d_counters, kernel_variant, stream),
+        "cb_focus_probe",
+    )
+
+
+def focus_cells(level, mask, dilate=1):
+    """The cell list of a host mask (u32 words): the mask dilated by `dilate` cells, ascending indices (u32 array)."""
+    m = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+    if m.size * 4 != focus_mask_bytes(level):
+        raise ValueError("mask size does not match the level")
+    n = C.c_uint32()
+    _check(lib.cb_focus_cells(int(level), m.ctypes.data, int(dilate), None, C.byref(n)), "cb_focus_cells")
+    cells = np.empty(int(n.value), dtype=np.uint32)
+    _check(lib.cb_focus_cells(int(level), m.ctypes.data, int(dilate), cells.ctypes.data, C.byref(n)), "cb_focus_cells")
+    return cells
+
+
+def draw_buddhabrot_focus(dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters=0,
+                          kernel_variant=CB_KERNEL_DEFAULT, level=0, d_cells=0, n_cells=0, stream=0):
+    """The focused draw on caller-owned device memory: samples from d_cells[0 .. n_cells) of the level's grid (level 0,
+    no cells: the uniform source, a normal render through the focus kernel)."""
+    _check(
+        lib.cb_draw_buddhabrot_focus(C.byref(dims), d_hist, C.byref(iterations), d_states, n_threads,
+                                     samples_per_thread, d_counters, kernel_variant, int(level), d_cells, n_cells, stream),
+        "cb_draw_buddhabrot_focus",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -304,6 +351,19 @@ class Renderer:
                                                 first_subsequence, n_threads),
                 "cb_renderer_create_channels",
             )
+
+    def set_focus(self, level=8, probe_passes=64, dilate=1, kernel_variant=CB_KERNEL_DEFAULT):
+        """Make this a focused renderer (cb_renderer_set_focus), before the first pass -> (cells listed, cells of the
+        grid).  Raises CudabrotError with code CB_ERROR_FOCUS_EMPTY when the probe marks no cell."""
+        _check(lib.cb_renderer_set_focus(self._h, int(level), int(probe_passes), int(dilate), kernel_variant),
+               "cb_renderer_set_focus")
+        return self.focus_cells()
+
+    def focus_cells(self):
+        """(cells listed, cells of the grid) of a focused renderer; (0, 0) without focus."""
+        n, total = C.c_uint32(), C.c_uint32()
+        _check(lib.cb_renderer_focus_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_focus_cells")
+        return int(n.value), int(total.value)
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""

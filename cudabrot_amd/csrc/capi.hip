@@ -291,6 +291,14 @@ struct cb_renderer {
   // the level of the interior map this renderer's last launch used (0: none) -- its own record: the process-wide
   // cb_debug_interior_map_level is whichever rank's launch came last
   int interior_level;
+  // what the generators were made from (cb_renderer_set_focus probes on fresh ones) and whether a pass was rendered
+  uint64_t seed, first_subsequence;
+  bool rendered;
+  // focused render (cb_renderer_set_focus): the grid's level (0: none), the cell list and the probe's step
+  int focus_level;
+  uint32_t *d_focus_cells;
+  uint32_t focus_n_cells;
+  bool focus_ship;
 };
 
 namespace {
@@ -298,6 +306,14 @@ namespace {
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
 int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
+  if (r->focus_level) {  // draw_focus.hip: direct atomics, no deferred scatter, no carry, no interior map
+    r->interior_level = 0;
+    if (passes == 0) return 0;
+    if (((kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0) != r->focus_ship) return (int) hipErrorInvalidValue;
+    return cb_draw_buddhabrot_focus(&r->dims, r->d_hist, &r->iterations, r->d_states, r->n_threads,
+                                    passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->focus_level,
+                                    r->d_focus_cells, r->focus_n_cells, r->stream);
+  }
   // the lock-step kernel and the anti kernels: direct atomics, no deferred scatter, no carry
   const bool wave = (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE && (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0;
   const bool deferred = r->d_workspace[0] && wave;
@@ -472,6 +488,9 @@ const char *cb_error_string(int code) {
   if (code == CB_ERROR_KERNEL_INVARIANT) {
     return "the draw kernel reported a broken internal invariant (cb_counters.status): samples were lost";
   }
+  if (code == CB_ERROR_FOCUS_EMPTY) {
+    return "the focus probe marked no cell: no probed sample has an accepted orbit that enters the canvas";
+  }
   return hipGetErrorString((hipError_t) code);
 }
 
@@ -633,6 +652,117 @@ int cb_flush_scatter_channels(const cb_fractal_dimensions *dims, cb_pixel *d_his
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- focused render (draw_focus.hip; include/cudabrot_amd.h, "Focused render") --------------------------------------
+
+namespace {
+
+// CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning Ship's flag: everything a focus launch accepts.
+bool focus_variant_ok(int kernel_variant) {
+  const int base_variant = kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP;
+  return base_variant == CB_KERNEL_DEFAULT || base_variant == CB_KERNEL_SIMPLE;
+}
+
+int launch_focus(cb::FocusArgs &f, int kernel_variant, hipStream_t stream) {
+  f.d.burning_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0 ? 1 : 0;
+  if (f.level) {
+    f.cell_side = ldexp(1.0, -f.level);
+    f.cell_scale = ldexp(1.0, -(f.level + 2));
+    f.cells_per_unit = ldexp(1.0, f.level);
+  }
+  const bool lockstep = (kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
+  g_last_draw_kernel.store(lockstep ? 7 : 6, std::memory_order_relaxed);
+  g_interior_level.store(0, std::memory_order_relaxed);
+  return (int) cb::launch_draw_focus(f, lockstep, stream);
+}
+
+}  // namespace
+
+int cb_focus_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *iterations, void *d_states,
+                   uint32_t n_threads, uint32_t samples_per_thread, int level, uint32_t *d_mask,
+                   cb_counters *d_counters, int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_states || !d_mask || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !focus_variant_ok(kernel_variant)) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::FocusArgs f;
+  memset(&f, 0, sizeof(f));
+  f.d = make_args(dims, iterations, nullptr, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  f.level = level;
+  f.mask = d_mask;
+  return launch_focus(f, kernel_variant, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                             const cb_iteration_control *iterations, void *d_states, uint32_t n_threads,
+                             uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, int level,
+                             const uint32_t *d_cells, uint32_t n_cells, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!focus_variant_ok(kernel_variant)) return (int) hipErrorInvalidValue;
+  const bool uniform = d_cells == nullptr && n_cells == 0 && level == 0;  // the tests' normal render through this kernel
+  if (!uniform && (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !d_cells || n_cells == 0)) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::FocusArgs f;
+  memset(&f, 0, sizeof(f));
+  f.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  f.level = level;
+  f.cells = d_cells;
+  f.n_cells = n_cells;
+  return launch_focus(f, kernel_variant, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
+  if (!r || r->n_channels > 0 || r->rendered || r->focus_level != 0 || probe_passes == 0 || dilate < 0 ||
+      level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !focus_variant_ok(kernel_variant)) {
+    return (int) hipErrorInvalidValue;
+  }
+  CB_TRY(hipSetDevice(r->device));
+  const size_t mask_bytes = cb_focus_mask_bytes(level);
+  void *d_states = nullptr;
+  uint32_t *d_mask = nullptr, *d_cells = nullptr;
+  std::vector<uint32_t> mask(mask_bytes / sizeof(uint32_t)), cells;
+  uint32_t n_cells = 0;
+  int rc = (int) hipMalloc(&d_states, cb_rng_state_bytes(r->n_threads));
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_mask), mask_bytes);
+  if (!rc) rc = (int) hipMemsetAsync(d_mask, 0, mask_bytes, r->stream);
+  if (!rc) rc = cb_initialize_rng(r->seed, r->first_subsequence, r->n_threads, d_states, r->stream);
+  for (uint32_t left = probe_passes; !rc && left > 0;) {
+    const uint32_t now = left < kRendererPassesPerLaunch ? left : kRendererPassesPerLaunch;
+    rc = cb_focus_probe(&r->dims, &r->iterations, d_states, r->n_threads, now * CB_SAMPLES_PER_THREAD, level, d_mask,
+                        nullptr, kernel_variant, r->stream);
+    left -= now;
+  }
+  if (!rc) rc = (int) hipMemcpyAsync(mask.data(), d_mask, mask_bytes, hipMemcpyDeviceToHost, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
+  if (!rc) rc = cb_focus_cells(level, mask.data(), dilate, nullptr, &n_cells);
+  if (!rc && n_cells == 0) rc = CB_ERROR_FOCUS_EMPTY;
+  if (!rc) {
+    cells.resize(n_cells);
+    rc = cb_focus_cells(level, mask.data(), dilate, cells.data(), &n_cells);
+  }
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_cells), (size_t) n_cells * sizeof(uint32_t));
+  if (!rc) rc = (int) hipMemcpy(d_cells, cells.data(), (size_t) n_cells * sizeof(uint32_t), hipMemcpyHostToDevice);
+  (void) hipFree(d_states);
+  (void) hipFree(d_mask);
+  if (rc) {
+    (void) hipFree(d_cells);
+    return rc;
+  }
+  r->focus_level = level;
+  r->d_focus_cells = d_cells;
+  r->focus_n_cells = n_cells;
+  r->focus_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  return 0;
+}
+
+int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total) {
+  if (!r) return (int) hipErrorInvalidValue;
+  const uint32_t n = r->focus_level ? 4u << r->focus_level : 0u;
+  if (n_cells) *n_cells = r->focus_level ? r->focus_n_cells : 0u;
+  if (n_total) *n_total = n * n;
+  return 0;
+}
+
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
                        const cb_iteration_control *iterations, uint64_t seed,
                        uint64_t first_subsequence, uint32_t n_threads) {
@@ -657,6 +787,8 @@ int cb_renderer_create_channels(cb_renderer **out, int device, const cb_fractal_
   r->n_channels = n_channels;
   for (int j = 0; j < n_channels; ++j) r->windows[j] = iterations[j];
   r->n_threads = n_threads;
+  r->seed = seed;
+  r->first_subsequence = first_subsequence;
   const size_t hist_bytes = (size_t) dims->w * (size_t) dims->h * sizeof(cb_pixel) * (size_t) (n_channels ? n_channels : 1);
   hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->flush_stream, hipStreamNonBlocking);
@@ -704,7 +836,8 @@ void prepare_for_variant(cb_renderer *r, int kernel_variant) {
       g_wave_dump = nullptr;
     }
   }
-  if (!r->workspace_tried && (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE &&
+  if (!r->workspace_tried && r->focus_level == 0 &&  // the focus kernels add directly
+      (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE &&
       (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0 &&  // the anti kernels add directly
       cb_debug_knob("CUDABROT_AMD_NO_WORKSPACE") == nullptr) {
     // scatter workspace for the largest launch render_passes makes; on any failure: direct atomics
@@ -741,6 +874,7 @@ int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_varian
   CB_TRY(hipSetDevice(r->device));
   const uint32_t max_passes_per_launch = ::max_passes_per_launch();
   prepare_for_variant(r, kernel_variant);
+  if (passes > 0) r->rendered = true;
   if (r->carry_pending && r->carry_variant != kernel_variant) {
     int rc = finish(r);  // a different kernel variant cannot take over the carried work
     if (rc) return rc;
@@ -902,6 +1036,7 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_states);
   (void) hipFree(r->d_counters);
   (void) hipFree(r->d_carry);
+  (void) hipFree(r->d_focus_cells);
   (void) hipFree(r->d_workspace[0]);
   (void) hipFree(r->d_workspace[1]);
   for (int k = 0; k < 2; ++k) {

@@ -17,7 +17,9 @@
 //    that never escape, include/cudabrot_amd.h CB_KERNEL_FLAG_ANTI), --channel MAX:MIN:FILE, --gpus N,
 //    --state-format native|raw (raw: the -s file as the reference's bare buffer, uint32 when every count fits),
 //    --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W (the three --channel planes composed into
-//    one 16-bit PPM: include/cudabrot_amd.h, "Colour image").
+//    one 16-bit PPM: include/cudabrot_amd.h, "Colour image"), --focus, --focus-level L, --focus-probe PASSES,
+//    --focus-dilate D (a cropped canvas sampled only from the cells of the plane whose samples reach it:
+//    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on).
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -72,6 +74,12 @@ struct Settings {
   const char *color_file = nullptr;
   cb_color_params color = {CB_COMPOSE_RGB, 2.0, 1.0, 0.0};
   const char *bad_color_flag = nullptr;             // the message of a bad --compose / --hue-shift / --color-stretch
+  // --focus (extension): samples drawn only from the cells a probe found to reach the canvas (cb_renderer_set_focus)
+  bool focus = false;
+  int focus_level = 8;                              // --focus-level: cells of side 2^-L
+  long focus_probe = 64;                            // --focus-probe: reference passes of the probe
+  int focus_dilate = 1;                             // --focus-dilate: cells the probe's mask is widened by
+  const char *bad_focus_flag = nullptr;             // the message of a bad --focus-level / -probe / -dilate
 };
 
 // The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
@@ -199,6 +207,35 @@ const std::vector<Flag> &flag_table() {
        [](Settings &s, long, double, const char *) { s.burning_ship = true; }},
       {"--anti", Value::kNone, nullptr, false,
        [](Settings &s, long, double, const char *) { s.anti = true; }},
+      {"--focus", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.focus = true; }},
+      {"--focus-level", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i >= CB_FOCUS_MIN_LEVEL && i <= CB_FOCUS_MAX_LEVEL) {
+           s.focus_level = (int) i;
+         } else {
+           s.bad_focus_flag = "Invalid focus level (want 4 to 10)";
+         }
+       }},
+      {"--focus-probe", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i >= 1) {
+           s.focus_probe = i;
+         } else {
+           s.bad_focus_flag = "Invalid focus probe (want at least 1 pass)";
+         }
+       }},
+      {"--focus-dilate", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i >= 0) {
+           s.focus_dilate = (int) i;
+         } else {
+           s.bad_focus_flag = "Invalid focus dilation (want 0 or more cells)";
+         }
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -328,7 +365,24 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_color_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_focus_flag) {
+      printf("%s: %s\n", s.bad_focus_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  // a focused render is one plane of escaping orbits on one device (include/cudabrot_amd.h, cb_renderer_set_focus)
+  if (s.focus && (s.n_channels > 0 || s.color_file)) {
+    printf("--focus does not combine with --channel.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.focus && s.anti) {
+    printf("--focus does not combine with --anti.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.focus && s.gpus > 1) {  // every rank would probe a mask of its own
+    printf("--focus does not combine with --gpus above 1.\n");
+    usage_and_exit(argv[0]);
   }
   if (s.anti && (s.n_channels > 0 || s.color_file)) {  // no fused anti channels (include/cudabrot_amd.h)
     printf("--anti does not combine with --channel.\n");
@@ -531,6 +585,7 @@ class Run {
     fflush(stdout);
     const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0) |
                         (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0);
+    if (cfg_.focus) set_focus(variant);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));
     for (cb_renderer *p : peers_) CB_CHECK(cb_renderer_prepare(p, variant));
@@ -579,6 +634,23 @@ class Run {
     printf("%ld Buddhabrot passes took %f seconds.\n", done, wall_seconds() - t0);
     if (cfg_.print_stats) print_stats();
     if (cfg_.n_channels == 0) tone_map(0);
+  }
+
+  // --focus: the probe and the cell list, before the clock of the pass loop starts.  The probe runs on generators of its
+  // own, so a run resumed with -s and --rng-state finds the list of the run it continues.
+  void set_focus(int variant) {
+    const int rc = cb_renderer_set_focus(renderer_, cfg_.focus_level, (uint32_t) cfg_.focus_probe, cfg_.focus_dilate,
+                                         variant);
+    if (rc == CB_ERROR_FOCUS_EMPTY) {
+      printf("Focus: no sample of the %ld probe passes reaches the canvas; nothing to render.\n", cfg_.focus_probe);
+      die();
+    }
+    CB_CHECK(rc);
+    uint32_t n_cells = 0, n_total = 0;
+    CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
+    printf("Focus: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", n_cells, n_total,
+           cfg_.focus_level, cfg_.focus_probe, cfg_.focus_dilate);
+    fflush(stdout);
   }
 
   // The pass loop of --gpus N.  One persistent host thread per rank; the ranks do not meet at batch
@@ -769,6 +841,12 @@ class Run {
     std::string levels = std::to_string(cb_renderer_interior_map_level(renderer_));
     for (cb_renderer *p : peers_) levels += ", " + std::to_string(cb_renderer_interior_map_level(p));
     fprintf(stderr, "{\"interior_map_levels\": [%s], ", levels.c_str());
+    if (cfg_.focus) {  // the part of the plane the samples come from: the factor between focused and uniform sample counts
+      uint32_t n_cells = 0, n_total = 0;
+      CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
+      fprintf(stderr, "\"focus_cells\": %u, \"focus_total\": %u, \"focus_fraction\": %.9g, ", n_cells, n_total,
+              n_total ? (double) n_cells / (double) n_total : 0.0);
+    }
     fprintf(stderr,
             "\"samples\": %llu, \"rejected\": %llu, \"never_escaped\": %llu, \"too_fast\": %llu, "
             "\"recorded\": %llu, \"iterate_steps\": %llu, \"replay_steps\": %llu, "

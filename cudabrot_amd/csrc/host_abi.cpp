@@ -41,4 +41,63 @@ const char *cb_debug_knob(const char *name) {
 
 size_t cb_rng_state_bytes(uint32_t n_threads) { return (size_t) n_threads * 6u * sizeof(uint32_t); }
 
+// ---- focused render: the host side of the cell list (include/cudabrot_amd.h, "Focused render") ----------------------
+
+size_t cb_focus_mask_bytes(int level) {
+  if (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL) return 0;
+  const size_t n = (size_t) 4 << level;
+  return n * n / 8;  // n is a multiple of 64
+}
+
+// The mask dilated by `dilate` cells in the Chebyshev metric = a box of side 2 d + 1 = a horizontal pass (is any cell
+// of [col - d, col + d] set?) followed by a vertical one over its result.  Each is a sliding count, so the cost is
+// O(n^2) whatever d; the vertical pass keeps one count per column and walks whole rows.  Not hot: 16 Mi cells at the
+// largest level.
+int cb_focus_cells(int level, const uint32_t *mask_host, int dilate, uint32_t *cells_out, uint32_t *n_cells) {
+  const int kInvalidValue = 1;  // hipErrorInvalidValue
+  if (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !mask_host || !n_cells || dilate < 0) {
+    return kInvalidValue;
+  }
+  const long n = 4L << level;
+  const long d = dilate < n ? dilate : n;  // beyond the grid's side every larger d gives the same
+  unsigned char *wide = (unsigned char *) malloc((size_t) n * (size_t) n);  // after the horizontal pass
+  uint32_t *count = (uint32_t *) calloc((size_t) n, sizeof(uint32_t));      // set cells of a column inside the window
+  if (!wide || !count) {
+    free(wide);
+    free(count);
+    return 2;  // hipErrorOutOfMemory
+  }
+  for (long row = 0; row < n; ++row) {
+    const size_t base = (size_t) row * (size_t) n;
+    auto bit = [&](long col) { return (mask_host[(base + (size_t) col) >> 5] >> ((base + (size_t) col) & 31u)) & 1u; };
+    uint32_t inside = 0;  // set cells of [col - d, col + d], clipped
+    for (long col = 0; col < d && col < n; ++col) inside += bit(col);
+    for (long col = 0; col < n; ++col) {
+      if (col + d < n) inside += bit(col + d);
+      if (col - d - 1 >= 0) inside -= bit(col - d - 1);
+      wide[base + (size_t) col] = inside != 0;
+    }
+  }
+  uint32_t found = 0;
+  for (long row = 0; row < d && row < n; ++row) {
+    for (long col = 0; col < n; ++col) count[col] += wide[(size_t) row * (size_t) n + (size_t) col];
+  }
+  for (long row = 0; row < n; ++row) {
+    const unsigned char *enter = row + d < n ? wide + (size_t) (row + d) * (size_t) n : nullptr;
+    const unsigned char *leave = row - d - 1 >= 0 ? wide + (size_t) (row - d - 1) * (size_t) n : nullptr;
+    for (long col = 0; col < n; ++col) {
+      if (enter) count[col] += enter[col];
+      if (leave) count[col] -= leave[col];
+      if (count[col] != 0) {
+        if (cells_out) cells_out[found] = (uint32_t) (row * n + col);
+        found++;
+      }
+    }
+  }
+  free(wide);
+  free(count);
+  *n_cells = found;
+  return 0;
+}
+
 }  // extern "C"

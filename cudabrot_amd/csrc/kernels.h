@@ -207,6 +207,25 @@ hipError_t launch_draw_wide_ship(const DrawArgs &a, bool timed, hipStream_t stre
 // cycle-compressed draw_anti_kernel; a.burning_ship picks the step.  Direct atomics, no workspace, no carry.
 hipError_t launch_draw_anti(const DrawArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_focus.hip: the focused render (include/cudabrot_amd.h, "Focused render").  A launch is a SOURCE of samples and a
+// SINK of accepted orbits:
+//   cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample);
+//   mask == null:  the histogram sink (d.hist, every in-canvas point); else the probe's mask (one bit per cell of the
+//                  c-plane, set by a sample whose accepted orbit has an in-canvas point; the replay stops there).
+// d carries the canvas, the iteration control, the generators, the counters and burning_ship; its workspace, carry and
+// interior-map fields are not read.
+struct FocusArgs {
+  DrawArgs d;
+  int level;              // cells of side 2^-level (cells or mask given)
+  uint32_t n_cells;       // entries of `cells`
+  const uint32_t *cells;  // ascending cell indices row * n + col, n = 4 << level
+  uint32_t *mask;         // n * n bits
+  double cell_side;       // 2^-level
+  double cell_scale;      // 2^-(level + 2): (x + 2) * cell_scale lies in (0, 2^-level]
+  double cells_per_unit;  // 2^level
+};
+hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

@@ -127,6 +127,10 @@ typedef struct {
  * (hipErrorInvalidValue), as cb_draw_buddhabrot does with any other base variant. */
 #define CB_KERNEL_FLAG_ANTI 0x400
 
+/* Returned (instead of a hipError_t) by cb_renderer_set_focus when the probe marked no cell: no sample of the probe has
+ * an accepted orbit that enters the canvas, so a focused render would have nothing to sample from. */
+#define CB_ERROR_FOCUS_EMPTY 100002
+
 /* RecomputePixelDeltas (cudabrot.cu:505-527).  Returns 1 and fills delta_* if the canvas is valid,
  * else 0 and, if msg is not NULL, *msg points at the reference's message for the failed check. */
 int cb_recompute_pixel_deltas(cb_fractal_dimensions *dims, const char **msg);
@@ -217,6 +221,66 @@ int cb_flush_scatter_channels(const cb_fractal_dimensions *dims, cb_pixel *d_his
                               uint32_t n_threads, void *d_workspace, size_t workspace_bytes,
                               void *stream);
 
+/* ---- Focused render: a cropped canvas sampled only from the cells that reach it -- *
+ *
+ * A render of a small window wastes almost every sample: samples are drawn over [-2, 2]^2 and few of their orbits enter
+ * the window.  A focused render first PROBES which cells of the c-plane hold samples whose orbits reach the canvas, and
+ * then draws its samples from those cells only.  The project's own definition (the reference has none).  Normative:
+ *
+ *   Grid.  Level L, CB_FOCUS_MIN_LEVEL <= L <= CB_FOCUS_MAX_LEVEL.  Cells of side 2^-L over [-2, 2)^2, n = 4 * 2^L
+ *   cells per side; cell (row, col) has the corner lo_re = -2 + col * 2^-L, lo_im = -2 + row * 2^-L (exact) and the
+ *   index row * n + col.  A MASK is n * n bits in uint32_t words: bit (index & 31) of word (index >> 5).
+ *
+ *   Probe.  A normal launch on the normal sample stream (4 XORWOW draws per sample, the same cardioid / bulb rejection,
+ *   iterate, accept filter min <= k < max, replay and binning as cb_draw_buddhabrot), except that nothing is added to a
+ *   histogram: a sample whose accepted orbit has AT LEAST ONE in-canvas point sets the bit of the cell that holds its c,
+ *   col = (int)((re + 2) * 2^L), row = (int)((im + 2) * 2^L), both exact; re = 2 exactly, which the sample stream can
+ *   return, is clamped to n - 1.  The mask is a union of bits and so independent of the schedule.  The replay stops at
+ *   the first in-canvas point.  Counters as a normal launch, except: recorded = the samples that set a bit (newly or
+ *   not), replay_steps = the replay steps up to and including that first point (all of them for an orbit that never
+ *   enters), increments = 0.
+ *
+ *   Cell list.  The mask dilated by d cells in the Chebyshev metric (d >= 0, clipped at the grid's edge), then the set
+ *   cells in ascending index order: cells[0 .. n_cells).
+ *
+ *   Focused draw.  Thread t consumes its subsequence SIX draws per sample, in this order: a = next(), b = next();
+ *   j = (((uint64_t)a << 32 | b) * n_cells) >> 64 (the high half of the 128-bit product); cell = cells[j];
+ *   x = the next coordinate of the normal stream, y = the one after (two draws each, values in (-2, 2]);
+ *   re = lo_re(cell) + (x + 2.0) * 2^-(L+2), im = lo_im(cell) + (y + 2.0) * 2^-(L+2).  x + 2.0 and the scaling are
+ *   exact, so each coordinate is ONE rounded IEEE addition; the offset lies in (0, 2^-L], so a point may sit on its
+ *   cell's upper edge.  From c = (re, im) on everything is the reference's: cardioid / bulb rejection, IterateMandelbrot,
+ *   the accept filter, IterateAndRecord into the histogram, and every cb_counters field with its normal meaning.
+ *
+ * What the image means: the density of a normal render restricted to the samples of the listed cells -- the normal
+ * image minus what the unlisted cells would have contributed (the known bias of an importance map; a longer probe and a
+ * larger dilation shrink it).  n_cells / n^2 is the factor between focused and uniform sample counts.
+ *
+ * Two kernels (draw_focus.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence with the exact-periodicity
+ * early-out, and CB_KERNEL_SIMPLE, the definition in lock-step; optionally | CB_KERNEL_FLAG_BURNING_SHIP; any other
+ * variant is hipErrorInvalidValue.  Identical masks, histograms, generator states and counters (but skipped_steps).
+ * Direct atomics, no workspace, no carry: every launch is complete when it ends. */
+#define CB_FOCUS_MIN_LEVEL 4
+#define CB_FOCUS_MAX_LEVEL 10
+/* Bytes of a mask of this level (n * n / 8; 0 for a level out of range). */
+size_t cb_focus_mask_bytes(int level);
+/* The probe: ORs into d_mask (cb_focus_mask_bytes(level) of device memory, zeroed by the caller before the first
+ * launch), advances d_states like a normal launch, adds to d_counters (may be NULL). */
+int cb_focus_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *iterations, void *d_states,
+                   uint32_t n_threads, uint32_t samples_per_thread, int level, uint32_t *d_mask,
+                   cb_counters *d_counters, int kernel_variant, void *stream);
+/* Host side of the cell list, from a mask in HOST memory: *n_cells receives the number of cells of the dilated mask;
+ * cells_out (may be NULL: count only) receives them and must hold that many entries (n * n always suffices).
+ * hipErrorInvalidValue for a level out of range, dilate < 0 or a NULL mask or n_cells. */
+int cb_focus_cells(int level, const uint32_t *mask_host, int dilate, uint32_t *cells_out, uint32_t *n_cells);
+/* The focused draw: as cb_draw_buddhabrot without workspace and carry, with the samples drawn from d_cells[0 .. n_cells)
+ * (device memory, entries below n * n).  n_cells = 0 is hipErrorInvalidValue.  For tests, d_cells == NULL && n_cells == 0
+ * && level == 0 selects the UNIFORM source: a normal render through this kernel, equal to cb_draw_buddhabrot's bit for
+ * bit. */
+int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                             const cb_iteration_control *iterations, void *d_states, uint32_t n_threads,
+                             uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, int level,
+                             const uint32_t *d_cells, uint32_t n_cells, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -237,6 +301,19 @@ int cb_renderer_create_channels(cb_renderer **out, int device, const cb_fractal_
  * carried to the next call; cb_renderer_finish (called by the read/write functions below) completes
  * them and waits for everything. */
 int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_variant);
+/* Makes this renderer a FOCUSED one ("Focused render" above); before its first pass, once.  Probes probe_passes
+ * reference passes (50 samples per thread each) of FRESH generators rocrand_init(seed, first_subsequence + t, 0) in a
+ * temporary buffer -- the renderer's own generators are not touched, so the cell list is a pure function of (seed,
+ * threads, canvas, iteration control, step, level, probe_passes, dilate) and a resumed run rebuilds the identical list
+ * -- dilates the mask by `dilate` cells and keeps the list; every later cb_renderer_render_passes launches focused
+ * draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE only, no CB_KERNEL_FLAG_ANTI, the same CB_KERNEL_FLAG_BURNING_SHIP as
+ * here: anything else is hipErrorInvalidValue).  kernel_variant: the kernel and the step of the probe.  Returns
+ * CB_ERROR_FOCUS_EMPTY when the list is empty (the renderer is then unchanged), hipErrorInvalidValue for a channel
+ * renderer, a renderer that has rendered or is focused already, a level out of range, probe_passes = 0, dilate < 0. */
+int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant);
+/* The size of a focused renderer's cell list and of its grid (n * n): their quotient is the part of the plane the
+ * samples are drawn from.  0 and 0 for a renderer without focus.  Either pointer may be NULL. */
+int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -364,8 +441,9 @@ int cb_abi_version(void);
 const char *cb_debug_knob(const char *name);
 /* Which draw kernel the last cb_draw_buddhabrot* call of this process launched (the renderer's calls included):
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
- * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel.  The
- * kernels give identical results; tests use this to know what they covered. */
+ * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
+ * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel.
+ * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
  * c-plane whose samples provably never escape: the draw kernel retires them without iterating; made and proven by
