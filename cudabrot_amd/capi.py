@@ -208,6 +208,9 @@ def _load():
         "cb_draw_buddhabrot_focus": (i32, [dims_p, vp, it_p, vp, u32, u32, vp, i32, i32, vp, u32, vp]),
         "cb_renderer_set_focus": (i32, [vp, i32, u32, i32, i32]),
         "cb_renderer_focus_cells": (i32, [vp, C.POINTER(u32), C.POINTER(u32)]),
+        "cb_draw_buddhabrot_projected": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), vp, u32, u32, vp, i32, vp]),
+        "cb_renderer_set_projection": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_renderer_projection": (i32, [vp, C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -227,7 +230,8 @@ EXPORTED_SYMBOLS = (
     "cb_tone_map_device cb_renderer_grayscale_image cb_renderer_read_rng_states cb_renderer_write_rng_states "
     "cb_draw_buddhabrot_channels cb_flush_scatter_channels cb_renderer_create_channels cb_renderer_grayscale_plane cb_renderers_reduce "
     "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be "
-    "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells"
+    "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells "
+    "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection"
 ).split()
 
 
@@ -325,6 +329,28 @@ def draw_buddhabrot_focus(dims, d_hist, iterations, d_states, n_threads, samples
     )
 
 
+IDENTITY_PROJECTION = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+
+
+def _projection(projection):
+    """P[2][4] (rows u, v; columns z_re, z_im, c_re, c_im) as eight C doubles."""
+    p = np.asarray(projection, dtype=np.float64).reshape(-1)
+    if p.size != 8:
+        raise ValueError("a projection is eight numbers: P[2][4]")
+    return (C.c_double * 8)(*[float(x) for x in p])
+
+
+def draw_buddhabrot_projected(dims, d_hist, iterations, projection, d_states, n_threads, samples_per_thread,
+                              d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The projected draw on caller-owned device memory (cb_draw_buddhabrot_projected): the normal sample stream, every
+    recorded point plotted at P (z_re, z_im, c_re, c_im); the canvas is the (u, v) window."""
+    _check(
+        lib.cb_draw_buddhabrot_projected(C.byref(dims), d_hist, C.byref(iterations), _projection(projection), d_states,
+                                         n_threads, samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_projected",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -364,6 +390,17 @@ class Renderer:
         n, total = C.c_uint32(), C.c_uint32()
         _check(lib.cb_renderer_focus_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_focus_cells")
         return int(n.value), int(total.value)
+
+    def set_projection(self, projection):
+        """Make this a projected renderer (cb_renderer_set_projection), before the first pass."""
+        _check(lib.cb_renderer_set_projection(self._h, _projection(projection)), "cb_renderer_set_projection")
+
+    def projection(self):
+        """The matrix of a projected renderer as a [2, 4] array; None without one."""
+        out = (C.c_double * 8)()
+        if not lib.cb_renderer_projection(self._h, out):
+            return None
+        return np.array(list(out), dtype=np.float64).reshape(2, 4)
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""

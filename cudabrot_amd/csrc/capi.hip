@@ -299,6 +299,9 @@ struct cb_renderer {
   uint32_t *d_focus_cells;
   uint32_t focus_n_cells;
   bool focus_ship;
+  // projected render (cb_renderer_set_projection): the matrix P[2][4]
+  bool projected;
+  double projection[8];
 };
 
 namespace {
@@ -313,6 +316,14 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
     return cb_draw_buddhabrot_focus(&r->dims, r->d_hist, &r->iterations, r->d_states, r->n_threads,
                                     passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->focus_level,
                                     r->d_focus_cells, r->focus_n_cells, r->stream);
+  }
+  if (r->projected) {  // draw_project.hip: direct atomics, no deferred scatter, no carry
+    if (passes == 0) return 0;
+    const int rc = cb_draw_buddhabrot_projected(&r->dims, r->d_hist, &r->iterations, r->projection, r->d_states,
+                                                r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
+                                                kernel_variant, r->stream);
+    r->interior_level = rc ? 0 : cb_debug_interior_map_level();
+    return rc;
   }
   // the lock-step kernel and the anti kernels: direct atomics, no deferred scatter, no carry
   const bool wave = (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE && (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0;
@@ -712,7 +723,7 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
 }
 
 int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
-  if (!r || r->n_channels > 0 || r->rendered || r->focus_level != 0 || probe_passes == 0 || dilate < 0 ||
+  if (!r || r->n_channels > 0 || r->rendered || r->focus_level != 0 || r->projected || probe_passes == 0 || dilate < 0 ||
       level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !focus_variant_ok(kernel_variant)) {
     return (int) hipErrorInvalidValue;
   }
@@ -761,6 +772,59 @@ int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n
   if (n_cells) *n_cells = r->focus_level ? r->focus_n_cells : 0u;
   if (n_total) *n_total = n * n;
   return 0;
+}
+
+// ---- projected render (draw_project.hip; include/cudabrot_amd.h, "Projected render") -------------------------------
+
+namespace {
+
+bool projection_ok(const double *p) {
+  if (!p) return false;
+  for (int j = 0; j < 8; ++j) {
+    if (!isfinite(p[j])) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                                 const cb_iteration_control *iterations, const double projection[8], void *d_states,
+                                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                                 int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!focus_variant_ok(kernel_variant) || !projection_ok(projection)) return (int) hipErrorInvalidValue;
+  cb::ProjectArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  pa.d.burning_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0 ? 1 : 0;
+  memcpy(pa.p, projection, sizeof(pa.p));
+  const bool lockstep = (kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
+  // The interior map where the normal product path consults it: wants_interior_map's rule (not the lock-step kernel, not
+  // the Burning Ship, not with the knob), and only when max_iter leaves that path a LONG stage (max_iter > head + mid
+  // steps of plan_stages, 20 for min_iter <= 16) -- below that it retires nothing through the map either.
+  g_interior_level.store(0, std::memory_order_relaxed);
+  if (pa.d.long_steps > 0) {
+    const int rc = attach_interior_map(pa.d, kernel_variant);
+    if (rc) return rc;
+  }
+  g_last_draw_kernel.store(lockstep ? 9 : 8, std::memory_order_relaxed);
+  return (int) cb::launch_draw_project(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cb_renderer_set_projection(cb_renderer *r, const double projection[8]) {
+  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->projected || !projection_ok(projection)) {
+    return (int) hipErrorInvalidValue;
+  }
+  memcpy(r->projection, projection, sizeof(r->projection));
+  r->projected = true;
+  return 0;
+}
+
+int cb_renderer_projection(const cb_renderer *r, double out[8]) {
+  if (!r || !out || !r->projected) return 0;
+  memcpy(out, r->projection, sizeof(r->projection));
+  return 1;
 }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
@@ -836,7 +900,7 @@ void prepare_for_variant(cb_renderer *r, int kernel_variant) {
       g_wave_dump = nullptr;
     }
   }
-  if (!r->workspace_tried && r->focus_level == 0 &&  // the focus kernels add directly
+  if (!r->workspace_tried && r->focus_level == 0 && !r->projected &&  // the focus and projection kernels add directly
       (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE &&
       (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0 &&  // the anti kernels add directly
       cb_debug_knob("CUDABROT_AMD_NO_WORKSPACE") == nullptr) {

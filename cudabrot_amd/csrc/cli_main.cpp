@@ -19,7 +19,9 @@
 //    --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W (the three --channel planes composed into
 //    one 16-bit PPM: include/cudabrot_amd.h, "Colour image"), --focus, --focus-level L, --focus-probe PASSES,
 //    --focus-dilate D (a cropped canvas sampled only from the cells of the plane whose samples reach it:
-//    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on).
+//    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on), --project
+//    a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG (the plane of the 4-D set (z_re, z_im, c_re, c_im) the orbits are
+//    plotted on: include/cudabrot_amd.h, "Projected render").
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -80,7 +82,66 @@ struct Settings {
   long focus_probe = 64;                            // --focus-probe: reference passes of the probe
   int focus_dilate = 1;                             // --focus-dilate: cells the probe's mask is widened by
   const char *bad_focus_flag = nullptr;             // the message of a bad --focus-level / -probe / -dilate
+  // --project / --plane / --rotate (extensions): the plotted plane, P[2][4] over (zr, zi, cr, ci) (cb_renderer_set_projection)
+  bool project_given = false, plane_given = false, rotate_given = false;
+  double projection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+  const char *bad_project_flag = nullptr;           // the message of a bad --project / --plane / --rotate
+  bool projected() const { return project_given || plane_given || rotate_given; }
 };
+
+// One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
+int axis_of(const char *text, char after, const char **rest) {
+  static const char *const kNames[4] = {"zr", "zi", "cr", "ci"};
+  for (int j = 0; j < 4; ++j) {
+    if (strncmp(text, kNames[j], 2) == 0 && text[2] == after) {
+      *rest = text + (after ? 3 : 2);
+      return j;
+    }
+  }
+  return -1;
+}
+
+// --project a,b,c,d:e,f,g,h: eight finite numbers, strtod's syntax (hexfloats included).
+bool parse_projection(const char *text, double out[8]) {
+  const char *at = text;
+  for (int j = 0; j < 8; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    out[j] = strtod(at, &end);
+    if (end == at || !isfinite(out[j]) || *end != (j == 7 ? 0 : (j == 3 ? ':' : ','))) return false;
+    at = end + 1;
+  }
+  return true;
+}
+
+// --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane.  An integer multiple of 90
+// degrees uses exact 0 and +-1 (a permutation of the two columns with signs); otherwise the host's cos and sin.
+bool rotate_projection(const char *text, double p[8]) {
+  const char *rest = nullptr;
+  const int x = axis_of(text, ',', &rest);
+  const int y = x < 0 ? -1 : axis_of(rest, ':', &rest);
+  if (x < 0 || y < 0 || x == y || *rest == 0 || *rest == ' ' || *rest == '\t') return false;
+  char *end = nullptr;
+  const double degrees = strtod(rest, &end);
+  if (end == rest || *end != 0 || !isfinite(degrees)) return false;
+  double co, si;
+  const double quarters = degrees / 90.0;
+  if (quarters == floor(quarters)) {
+    const int q = (int) fmod(fmod(quarters, 4.0) + 4.0, 4.0);
+    co = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
+    si = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
+  } else {
+    const double radians = degrees * (M_PI / 180.0);
+    co = cos(radians);
+    si = sin(radians);
+  }
+  for (int row = 0; row < 2; ++row) {
+    const double a = p[4 * row + x], b = p[4 * row + y];
+    p[4 * row + x] = (a * co - b * si) + 0.0;  // (+ 0.0: an exact zero is +0)
+    p[4 * row + y] = (a * si + b * co) + 0.0;
+  }
+  return true;
+}
 
 // The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
 const char kUsageBody[] =
@@ -236,6 +297,39 @@ const std::vector<Flag> &flag_table() {
            s.bad_focus_flag = "Invalid focus dilation (want 0 or more cells)";
          }
        }},
+      {"--project", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.project_given = true;
+         if (!parse_projection(t, s.projection)) {
+           s.bad_project_flag = "Invalid projection (want a,b,c,d:e,f,g,h, eight finite numbers)";
+         }
+       }},
+      {"--plane", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         const char *rest = nullptr;
+         const int x = axis_of(t, ',', &rest);
+         const int y = x < 0 ? -1 : axis_of(rest, 0, &rest);
+         s.plane_given = true;
+         if (x < 0 || y < 0 || x == y) {
+           s.bad_project_flag = "Invalid plane (want X,Y, two different axes of zr, zi, cr, ci)";
+           return;
+         }
+         if (s.rotate_given) {  // the rotations start from the plane
+           s.bad_project_flag = "Invalid plane (--plane goes before the first --rotate)";
+           return;
+         }
+         for (int j = 0; j < 8; ++j) s.projection[j] = 0.0;
+         s.projection[x] = 1.0;
+         s.projection[4 + y] = 1.0;
+       }},
+      {"--rotate", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.rotate_given = true;
+         if (s.project_given) return;  // refused after parsing; the matrix given is not touched
+         if (!rotate_projection(t, s.projection)) {
+           s.bad_project_flag = "Invalid rotation (want X,Y:DEG, two different axes of zr, zi, cr, ci and a finite angle)";
+         }
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -369,7 +463,33 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_focus_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_project_flag) {
+      printf("%s: %s\n", s.bad_project_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  // a projected render is one plane of escaping orbits on one device, sampled uniformly (include/cudabrot_amd.h,
+  // cb_renderer_set_projection)
+  if (s.project_given && (s.plane_given || s.rotate_given)) {
+    printf("--project does not combine with --plane or --rotate.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.projected() && (s.n_channels > 0 || s.color_file)) {
+    printf("A projection does not combine with --channel.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.projected() && s.anti) {
+    printf("A projection does not combine with --anti.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.projected() && s.focus) {
+    printf("A projection does not combine with --focus.\n");
+    usage_and_exit(argv[0]);
+  }
+  if (s.projected() && s.gpus > 1) {
+    printf("A projection does not combine with --gpus above 1.\n");
+    usage_and_exit(argv[0]);
   }
   // a focused render is one plane of escaping orbits on one device (include/cudabrot_amd.h, cb_renderer_set_focus)
   if (s.focus && (s.n_channels > 0 || s.color_file)) {
@@ -421,6 +541,12 @@ class Run {
     printf("Creating %dx%d image, %d max iterations.\n", cfg_.canvas.w, cfg_.canvas.h,
            max_iterations);  // cudabrot.cu:779-780
     printf("Calculating image...\n");
+    if (cfg_.projected() && cfg_.print_stats) {  // the matrix defines the run: printed before any device is touched
+      const double *p = cfg_.projection;
+      fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
+              p[3], p[4], p[5], p[6], p[7]);
+      fflush(stderr);
+    }
     setup();
     load_inprogress();
     load_rng_state();
@@ -506,6 +632,7 @@ class Run {
         peers_.push_back(one);
       }
     }
+    if (cfg_.projected()) CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
     if (need_host_counts()) {
       counts_ = (cb_pixel *) calloc(1, buffer_bytes());
       if (!counts_) die();

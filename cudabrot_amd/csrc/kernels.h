@@ -226,6 +226,16 @@ struct FocusArgs {
 };
 hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_project.hip: the projected render (include/cudabrot_amd.h, "Projected render").  p is the matrix P[2][4], rows
+// (u, v), columns (z_re, z_im, c_re, c_im), finite.  d carries the canvas (the (u, v) window), the iteration control, the
+// generators, the counters, burning_ship and the interior map (null: none; read by the product kernel with the Mandelbrot
+// step only); its workspace and carry fields are not read.
+struct ProjectArgs {
+  DrawArgs d;
+  double p[8];
+};
+hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

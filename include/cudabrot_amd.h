@@ -281,6 +281,44 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, int level,
                              const uint32_t *d_cells, uint32_t n_cells, void *stream);
 
+/* ---- Projected render: any 2-D projection of the 4-D Buddhabrot ---------------- *
+ *
+ * Every recorded orbit point is a point (z_re, z_im, c_re, c_im) of a four-dimensional set; the normal render plots its
+ * (z_re, z_im) shadow.  A PROJECTION is eight doubles P[2][4], row-major: rows (u, v), columns in the order (z_re, z_im,
+ * c_re, c_im).  Entries must be finite; anything else is hipErrorInvalidValue.
+ *
+ *   Samples.  The normal stream, four XORWOW draws per sample; the same cardioid / bulb rejection (not for the Burning
+ *   Ship), the same IterateMandelbrot, the same accept filter min <= k < max.  The replay visits exactly the points
+ *   IterateAndRecord visits: z_1 ... z_{k+1}, the escaping point included.
+ *
+ *   Plot.  Each visited point z of a sample c is plotted at
+ *       K_u = fma(P[0][2], c_re, P[0][3] * c_im)                  (once per sample)
+ *       u   = fma(P[0][0], z_re, fma(P[0][1], z_im, K_u))
+ *   and v likewise from row 1.  Every operation is IEEE fp64, each fma one rounding, nothing else contracted.  (u, v) is
+ *   then binned exactly as the reference bins (re, im), with u in the place of re and v in the place of im: the same
+ *   `x < min` early-out, (int) ((x - min) / delta) and bounds tests.  The canvas (w, h, min_real ... max_imag) describes
+ *   the (u, v) window.
+ *
+ *   Counters keep their normal meaning; skipped_steps is the executed-work discount, as in every product kernel.
+ *
+ *   Identity.  P = {{1,0,0,0},{0,1,0,0}} is a normal render bit for bit: histogram, generator states and every counter
+ *   but skipped_steps.  Every visited z is finite -- the point before an escaping one has |z|^2 <= 4, so the escaping
+ *   point itself is bounded -- and c is finite, so each zero entry contributes a product that is exactly +0 or -0, never
+ *   NaN: K_u = +-0, fma(0, z_im, K_u) = +-0, and u = fma(1, z_re, +-0) = z_re, except that u may be +0 where z_re is -0
+ *   (or the reverse).  +0 and -0 compare equal in `x < min`, and x - min differs at most in the sign of a zero, which
+ *   (int) (x / delta) maps to pixel 0 either way: a +-0 difference cannot move a bin.
+ *
+ * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence, with the interior map
+ * (Mandelbrot step only) and the exact-periodicity early-out, and CB_KERNEL_SIMPLE, the definition in lock-step;
+ * optionally | CB_KERNEL_FLAG_BURNING_SHIP; any other variant, CB_KERNEL_FLAG_ANTI included, is hipErrorInvalidValue.
+ * Identical histograms, generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry:
+ * every launch is complete when it ends.  The -s buffer format is unchanged and does NOT record the plane: resuming a
+ * buffer with another projection adds two different images, and nothing can notice. */
+int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                                 const cb_iteration_control *iterations, const double projection[8], void *d_states,
+                                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                                 int kernel_variant, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -309,11 +347,22 @@ int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_varian
  * draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE only, no CB_KERNEL_FLAG_ANTI, the same CB_KERNEL_FLAG_BURNING_SHIP as
  * here: anything else is hipErrorInvalidValue).  kernel_variant: the kernel and the step of the probe.  Returns
  * CB_ERROR_FOCUS_EMPTY when the list is empty (the renderer is then unchanged), hipErrorInvalidValue for a channel
- * renderer, a renderer that has rendered or is focused already, a level out of range, probe_passes = 0, dilate < 0. */
+ * renderer, a projected renderer, a renderer that has rendered or is focused already, a level out of range,
+ * probe_passes = 0, dilate < 0. */
 int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant);
 /* The size of a focused renderer's cell list and of its grid (n * n): their quotient is the part of the plane the
  * samples are drawn from.  0 and 0 for a renderer without focus.  Either pointer may be NULL. */
 int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total);
+/* Makes this renderer a PROJECTED one ("Projected render" above); before its first pass, once.  Every later
+ * cb_renderer_render_passes launches projected draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning
+ * Ship's flag: anything else is hipErrorInvalidValue); render_passes, finish and the histogram, image and state reads
+ * work as for a focused renderer.  hipErrorInvalidValue for a channel renderer, a focused renderer, a renderer that has
+ * rendered or is projected already, or a non-finite entry; cb_renderer_set_focus on a projected renderer is refused
+ * likewise. */
+int cb_renderer_set_projection(cb_renderer *r, const double projection[8]);
+/* A projected renderer's matrix: returns 1 and fills out[8]; returns 0 and leaves `out` alone for a renderer without
+ * one (or a NULL argument). */
+int cb_renderer_projection(const cb_renderer *r, double out[8]);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -442,7 +491,8 @@ const char *cb_debug_knob(const char *name);
 /* Which draw kernel the last cb_draw_buddhabrot* call of this process launched (the renderer's calls included):
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
  * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
- * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel.
+ * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel,
+ * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
