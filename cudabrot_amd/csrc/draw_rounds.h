@@ -1,0 +1,187 @@
+// draw_rounds.h -- what the kernels with one reference thread per lane share (kernels.hip's draw_simple_kernel,
+// draw_anti.hip, draw_focus.hip, draw_project.hip): the per-lane counters, the reference's escape-index loop for the
+// lock-step kernels, and the round scheduler of the three product kernels.
+#pragma once
+
+#include "draw_common.h"
+
+namespace cb {
+
+// Per-lane statistics, summed over the wave at kernel end (one atomic per counter per wave); `reserved` is
+// cb_counters.skipped_steps.
+struct LaneStats {
+  unsigned long long samples = 0, rejected = 0, never_escaped = 0, too_fast = 0, recorded = 0,
+                     iterate_steps = 0, replay_steps = 0, increments = 0, reserved = 0,
+                     status = 0;
+};
+
+__device__ __forceinline__ void flush_stats(cb_counters *counters, const LaneStats &s) {
+  if (!counters) return;
+  const unsigned long long v[10] = {
+      wave_sum(s.samples),       wave_sum(s.rejected),     wave_sum(s.never_escaped),
+      wave_sum(s.too_fast),      wave_sum(s.recorded),     wave_sum(s.iterate_steps),
+      wave_sum(s.replay_steps),  wave_sum(s.increments),   wave_sum(s.reserved),
+      wave_sum(s.status)};
+  if (lane_id() == 0) {
+    unsigned long long *c = reinterpret_cast<unsigned long long *>(counters);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      if (v[i]) __hip_atomic_fetch_add(c + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (v[9]) __hip_atomic_fetch_or(c + 9, v[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// IterateMandelbrot (cudabrot.cu:319-340) for the lock-step kernels: the k of the first z_{k+1} with |z|^2 > 4, or
+// max_iter when none of z_1 .. z_max_iter escapes (at once for max_iter <= 0).
+__device__ __forceinline__ int escape_index(double real, double imag, int max_iter, bool ship) {
+  double r = real, i = imag;
+  for (int it = 0; it < max_iter; ++it) {
+    if ((ship ? mandel_step_ship(real, imag, r, i) : mandel_step(real, imag, r, i)) > 4.0) return it;
+  }
+  return max_iter;
+}
+
+template <bool kShip>
+__device__ __forceinline__ double orbit_step(double cr, double ci, double &r, double &i) {
+  return kShip ? mandel_step_ship(cr, ci, r, i) : mandel_step(cr, ci, r, i);
+}
+
+// Bit-for-bit equality of two points (not ==: -0.0 == 0.0, and a NaN equals nothing).
+__device__ __forceinline__ bool same_bits(double r, double i, double sr, double si) {
+  return __double_as_longlong(r) == __double_as_longlong(sr) && __double_as_longlong(i) == __double_as_longlong(si);
+}
+
+// Brent's schedule refined (draw_wave.hip long_retire): the saved point is replaced when the number of
+// chunks done has no set bit below its top two -- after 1, 2, 3, 4, 6, 8, 12, 16, 24 ... chunks.
+__device__ __forceinline__ bool brent_save(uint32_t chunks) {
+  const int top = 31 - __clz((int) chunks);
+  return top < 1 || (chunks & ((1u << (top - 1)) - 1u)) == 0u;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The round scheduler: lanes refilled from their own subsequence, exact-periodicity check at chunk boundaries
+// ------------------------------------------------------------------------------------------------
+//
+// Every lane owns one reference thread (its generator, its samples_per_thread samples) and works on one sample at a
+// time.  The wave advances in ROUNDS of kRound steps; in a round each lane makes up to kRound steps of its own phase,
+// and between rounds each lane, on its own, does its bookkeeping.  What a kernel adds is its MODE: a struct with the
+// step (kShip), whatever per-lane state it needs beyond RoundLane, and four inlined hooks, named where they are called:
+//   NEXT     the lane's next sample, or DONE when it has none left.  mode.next draws c and says what becomes of it: it
+//            is iterated, or retired as drawn -- rejected (cardioid, bulb), or proven interior and counted as the
+//            reference counts a sample that never escapes -- and the next one drawn.  (max_iter 0 needs no case of its
+//            own: ITERATE makes no step and is at k == max_iter at once.)
+//   ITERATE  z_k -> z_{k+kRound} (fewer at max_iter), testing |z|^2 > 4 after every step.  A lane that escapes at its
+//            n-th step (the reference's k = n - 1) notes n in `end` and idles to the round's end (ESCAPED); there
+//            mode.escaped counts the sample and decides: true, REPLAY z_1 .. z_n.
+//            At k a multiple of kChunk: z_k == the saved point z_saved bit for bit -> the orbit is the exact cycle
+//            z_saved .. z_{k-1} repeated, every point of which passed the test, so it never escapes;
+//            else Brent's save.  On such a cycle, or at k == max_iter, mode.never_escapes counts the sample (the steps
+//            not made go to skipped_steps) and decides: true, REPLAY up to the `end` it has set.
+//   REPLAY   z_1 .. z_end from z_0 = c, the same steps bit for bit; mode.point bins each, and may end the replay there
+//            by returning true.
+// A lane that completes a phase mid-round idles to the round's end: kRound steps are the grain of the refill.  Rounds
+// divide kChunk, so an iterating lane is at a chunk boundary exactly when k % kChunk == 0.
+constexpr int kRound = 12;
+static_assert(kChunk % kRound == 0, "an iterating lane meets every chunk boundary at a round's end");
+
+enum : int { kSampleIterate = 0, kSampleRejected = 1, kSampleInterior = 2 };  // what mode.next returns
+enum : int { kRoundNext = 0, kRoundIterate = 1, kRoundReplay = 2, kRoundEscaped = 3, kRoundDone = 4 };
+
+struct RoundLane {
+  int max_iter;                                   // wave-uniform: the launch's, negative taken as 0
+  double cr = 0.0, ci = 0.0, r = 0.0, i = 0.0;    // the sample and its orbit: z_k
+  double sr = 0.0, si = 0.0;                      // ITERATE: the saved point z_saved
+  int k = 0;                                      // index of z
+  int saved = 0;                                  // ITERATE: index of the saved point (0: none yet)
+  int end = 0;                                    // ESCAPED: the step that escaped; REPLAY: the last index replayed
+};
+
+template <class Mode>
+__device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = tid < a.n_threads;
+  LaneStats st;
+  Xorwow rng = {0u, 0u, 0u, 0u, 0u, 0u};
+  if (valid) rng = load_rng(a.states, a.n_threads, tid);
+  uint32_t left = valid ? a.samples_per_thread : 0u;
+  int phase = kRoundNext;
+  RoundLane l;
+  l.max_iter = a.max_iter > 0 ? a.max_iter : 0;
+  while (true) {
+    // ---- between rounds: each lane's bookkeeping --------------------------------------------------------------
+    if (phase == kRoundNext) {
+      while (left > 0u) {
+        left--;
+        st.samples++;
+        const int drawn = mode.next(rng, l);
+        if (drawn == kSampleRejected) {
+          st.rejected++;
+          continue;
+        }
+        if (drawn == kSampleInterior) {  // as the reference counts it, every step of it skipped
+          st.never_escaped++;
+          st.iterate_steps += (unsigned long long) l.max_iter;
+          st.reserved += (unsigned long long) l.max_iter;
+          continue;
+        }
+        l.r = l.cr;
+        l.i = l.ci;
+        l.k = 0;
+        l.saved = 0;
+        phase = kRoundIterate;
+        break;
+      }
+      if (phase == kRoundNext) phase = kRoundDone;
+    }
+    if (__ballot(phase != kRoundDone) == 0ull) break;
+    // ---- one round ----------------------------------------------------------------------------------------------
+    const int limit = phase == kRoundIterate ? l.max_iter : l.end;
+    const int stop = phase == kRoundDone ? l.k : (limit - l.k < kRound ? limit : l.k + kRound);
+#pragma unroll 2
+    for (int t = 0; t < kRound; ++t) {
+      if (l.k < stop) {
+        const double m = orbit_step<Mode::kShip>(l.cr, l.ci, l.r, l.i);
+        ++l.k;
+        if (phase == kRoundReplay) {
+          if (mode.point(l, st)) {
+            phase = kRoundNext;
+            l.k = stop;
+          }
+        } else if (m > 4.0) {  // escaped at z_k
+          l.end = l.k;
+          phase = kRoundEscaped;
+          l.k = stop;  // no more steps this round
+        }
+      }
+    }
+    bool replay = false;
+    if (phase == kRoundReplay) {
+      if (l.k == l.end) phase = kRoundNext;
+    } else if (phase == kRoundEscaped) {
+      replay = mode.escaped(l, st);
+      if (!replay) phase = kRoundNext;
+    } else if (phase == kRoundIterate) {
+      const bool boundary = (l.k % kChunk) == 0;
+      const bool cycle = boundary && l.saved > 0 && same_bits(l.r, l.i, l.sr, l.si);
+      if (cycle || l.k == l.max_iter) {
+        replay = mode.never_escapes(l, st, cycle);
+        if (!replay) phase = kRoundNext;
+      } else if (boundary && brent_save((uint32_t) (l.k / kChunk))) {
+        l.sr = l.r;
+        l.si = l.i;
+        l.saved = l.k;
+      }
+    }
+    if (replay) {
+      l.r = l.cr;
+      l.i = l.ci;
+      l.k = 0;
+      phase = kRoundReplay;
+    }
+  }
+  if (valid) store_rng(a.states, a.n_threads, tid, rng);
+  flush_stats(a.counters, st);
+}
+
+}  // namespace cb

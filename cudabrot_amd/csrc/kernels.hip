@@ -9,7 +9,7 @@
 //                      lock-step.  Validation baseline: ~2 % lane efficiency at deep max_iter
 //                      (SURVEY.md H2).
 //   (draw_wave_kernel, the product path, lives in draw_wave.hip.)
-#include "draw_common.h"
+#include "draw_rounds.h"
 
 namespace cb {
 
@@ -86,34 +86,6 @@ hipError_t launch_rng_init(uint64_t seed, uint64_t first_subsequence, uint32_t n
 }
 
 // ------------------------------------------------------------------------------------------------
-// Shared pieces of the draw kernels
-// ------------------------------------------------------------------------------------------------
-
-// Per-lane statistics, summed over the wave at kernel end (one atomic per counter per wave).
-struct LaneStats {
-  unsigned long long samples = 0, rejected = 0, never_escaped = 0, too_fast = 0, recorded = 0,
-                     iterate_steps = 0, replay_steps = 0, increments = 0, reserved = 0,
-                     status = 0;
-};
-
-__device__ __forceinline__ void flush_stats(cb_counters *counters, const LaneStats &s) {
-  if (!counters) return;
-  const unsigned long long v[10] = {
-      wave_sum(s.samples),       wave_sum(s.rejected),     wave_sum(s.never_escaped),
-      wave_sum(s.too_fast),      wave_sum(s.recorded),     wave_sum(s.iterate_steps),
-      wave_sum(s.replay_steps),  wave_sum(s.increments),   wave_sum(s.reserved),
-      wave_sum(s.status)};
-  if (lane_id() == 0) {
-    unsigned long long *c = reinterpret_cast<unsigned long long *>(counters);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      if (v[i]) __hip_atomic_fetch_add(c + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (v[9]) __hip_atomic_fetch_or(c + 9, v[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // draw_simple_kernel: the reference's loop structure, one lane per reference thread
 // ------------------------------------------------------------------------------------------------
 
@@ -132,15 +104,7 @@ __global__ void __launch_bounds__(256) draw_simple_kernel(DrawArgs a) {
         st.rejected++;
         continue;
       }
-      // IterateMandelbrot, cudabrot.cu:319-340
-      double r = real, i = imag;
-      int k = a.max_iter;
-      for (int it = 0; it < a.max_iter; ++it) {
-        if ((a.burning_ship ? mandel_step_ship(real, imag, r, i) : mandel_step(real, imag, r, i)) > 4.0) {
-          k = it;
-          break;
-        }
-      }
+      const int k = escape_index(real, imag, a.max_iter, a.burning_ship);  // IterateMandelbrot
       if (k >= a.max_iter) {  // cudabrot.cu:407
         st.never_escaped++;
         st.iterate_steps += (unsigned long long) (a.max_iter > 0 ? a.max_iter : 0);
@@ -153,8 +117,7 @@ __global__ void __launch_bounds__(256) draw_simple_kernel(DrawArgs a) {
       }
       st.recorded++;
       // IterateAndRecord, cudabrot.cu:347-365; bounded so that a wave always terminates
-      r = real;
-      i = imag;
+      double r = real, i = imag;
       for (int it = 0; it <= a.max_iter; ++it) {
         const double m = a.burning_ship ? mandel_step_ship(real, imag, r, i) : mandel_step(real, imag, r, i);
         st.replay_steps++;
