@@ -122,6 +122,31 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ScatterArray(C.Structure):
+    """cb_scatter_array: one array of the scatter workspace, as bytes from its start."""
+
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+SCATTER_ARRAYS = ("wave_count stream a_count a_base grouped region_start region_count region_group owner_first "
+                  "group_first group_regions n_regions chunk_desc chunk_list run_start slice_base sorted").split()
+
+
+class ScatterLayout(C.Structure):
+    """cb_scatter_layout: the carve of a scatter workspace (cb_debug_scatter_layout)."""
+
+    _fields_ = [
+        (n, C.c_uint32)
+        for n in ("enabled n_waves cap n_tiles tiles_x tiles_y n_planes two_level n_groups chunked chunks_per_wave "
+                  "max_regions e_row_shift e_col_mask e_row_mask e_chan_shift e_chan_mask reserved").split()
+    ] + [(n, ScatterArray) for n in SCATTER_ARRAYS]
+
+    def arrays(self):
+        """{name: (offset, bytes)} of the arrays the layout has."""
+        return {n: (int(getattr(self, n).offset), int(getattr(self, n).bytes))
+                for n in SCATTER_ARRAYS if getattr(self, n).bytes}
+
+
 def _share_torch_hip_runtime():
     """One HIP runtime per process.
 
@@ -179,6 +204,7 @@ def _load():
         "cb_flush_scatter_channels": (i32, [dims_p, vp, i32, u32, vp, C.c_size_t, vp]),
         "cb_renderer_finish": (i32, [vp]),
         "cb_flush_scatter": (i32, [dims_p, vp, u32, vp, C.c_size_t, vp]),
+        "cb_debug_scatter_layout": (i32, [dims_p, i32, u32, vp, C.c_size_t, C.POINTER(ScatterLayout)]),
         "cb_renderer_create": (i32, [C.POINTER(vp), i32, dims_p, it_p, u64, u64, u32]),
         "cb_renderer_create_channels": (i32, [C.POINTER(vp), i32, dims_p, it_p, i32, u64, u64, u32]),
         "cb_renderer_grayscale_plane": (i32, [vp, i32, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
@@ -231,7 +257,7 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_channels cb_flush_scatter_channels cb_renderer_create_channels cb_renderer_grayscale_plane cb_renderers_reduce "
     "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be "
     "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells "
-    "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection"
+    "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout"
 ).split()
 
 
@@ -289,6 +315,15 @@ def flush_scatter(dims, d_hist, n_threads, d_workspace, workspace_bytes, stream=
     """Adds the pixel stream a draw_buddhabrot call deferred into the workspace to the histogram."""
     _check(lib.cb_flush_scatter(C.byref(dims), d_hist, n_threads, d_workspace, workspace_bytes, stream),
            "cb_flush_scatter")
+
+
+def debug_scatter_layout(dims, n_threads, d_workspace, workspace_bytes, n_channels=0):
+    """Where flush_scatter (n_channels = 0) or flush_scatter_channels (1..4) finds its arrays in this workspace: a
+    ScatterLayout.  Host arithmetic on the arguments; d_workspace is any non-zero address and is not touched."""
+    out = ScatterLayout()
+    _check(lib.cb_debug_scatter_layout(C.byref(dims), n_channels, n_threads, d_workspace, workspace_bytes,
+                                       C.byref(out)), "cb_debug_scatter_layout")
+    return out
 
 
 def focus_mask_bytes(level):

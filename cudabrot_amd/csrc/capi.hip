@@ -663,6 +663,64 @@ int cb_flush_scatter_channels(const cb_fractal_dimensions *dims, cb_pixel *d_his
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, uint32_t n_threads,
+                            const void *d_workspace, size_t workspace_bytes, cb_scatter_layout *out) {
+  if (!dims || !out || dims->w <= 0 || dims->h <= 0 || n_channels < 0 || n_channels > CB_MAX_CHANNELS) {
+    return (int) hipErrorInvalidValue;
+  }
+  // the carve of the draw and flush entry points above, and nothing else: the workspace is not touched
+  cb::BinLayoutBytes carved;
+  const cb::BinLayout b = cb::make_bin_layout(const_cast<void *>(d_workspace), workspace_bytes, dims->w, dims->h,
+                                              cb::draw_wave_count(n_threads), n_channels, &carved);
+  memset(out, 0, sizeof(*out));
+  out->enabled = b.enabled;
+  out->n_waves = b.n_waves;
+  out->n_planes = b.n_planes;
+  out->e_row_shift = b.e_row_shift;
+  out->e_col_mask = b.e_col_mask;
+  out->e_row_mask = b.e_row_mask;
+  out->e_chan_shift = b.e_chan_shift;
+  out->e_chan_mask = b.e_chan_mask;
+  if (!b.enabled) return 0;
+  out->cap = b.cap;
+  out->n_tiles = b.n_tiles;
+  out->tiles_x = b.tiles_x;
+  out->tiles_y = b.tiles_y;
+  out->two_level = b.two_level;
+  out->n_groups = b.n_groups;
+  out->chunked = b.chunked;
+  out->chunks_per_wave = b.chunks_per_wave;
+  out->max_regions = b.max_regions;
+  const auto place = [&](const void *p, size_t bytes) {
+    cb_scatter_array a = {0, 0};
+    if (p) {
+      a.offset = (uint64_t) (reinterpret_cast<uintptr_t>(p) - reinterpret_cast<uintptr_t>(d_workspace));
+      a.bytes = (uint64_t) bytes;
+    }
+    return a;
+  };
+#define CB_PLACE(name) out->name = place(b.name, carved.name)
+  CB_PLACE(wave_count);
+  CB_PLACE(stream);
+  CB_PLACE(a_count);
+  CB_PLACE(a_base);
+  CB_PLACE(grouped);
+  CB_PLACE(region_start);
+  CB_PLACE(region_count);
+  CB_PLACE(region_group);
+  CB_PLACE(owner_first);
+  CB_PLACE(group_first);
+  CB_PLACE(group_regions);
+  CB_PLACE(n_regions);
+  CB_PLACE(chunk_desc);
+  CB_PLACE(chunk_list);
+  CB_PLACE(run_start);
+  CB_PLACE(slice_base);
+  CB_PLACE(sorted);
+#undef CB_PLACE
+  return 0;
+}
+
 // ---- focused render (draw_focus.hip; include/cudabrot_amd.h, "Focused render") --------------------------------------
 
 namespace {

@@ -94,9 +94,16 @@ struct BinLayout {
 // Bytes of a workspace for launches that write about entries_per_wave stream entries per wave (0 if
 // the canvas cannot use one: a side above 65536 or more than 262144 tiles over all planes).
 size_t bin_workspace_bytes(int w, int h, uint32_t n_waves, double entries_per_wave, int n_planes = 1);
+// Bytes of every array of a BinLayout as make_bin_layout carved it (0: the layout has no such array): what
+// cb_debug_scatter_layout reports.  The kernels never see it.
+struct BinLayoutBytes {
+  size_t wave_count, stream, a_count, a_base, grouped, region_start, region_count, region_group, owner_first,
+      group_first, group_regions, n_regions, chunk_desc, chunk_list, run_start, slice_base, sorted;
+};
 // Carves `bytes` at `workspace` into a BinLayout (enabled = 0 if it is too small or the canvas does
-// not qualify).
-BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t n_waves, int n_channels = 0);
+// not qualify).  Host arithmetic only: the workspace is not touched.  carved (may be null): the arrays' sizes.
+BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t n_waves, int n_channels = 0,
+                          BinLayoutBytes *carved = nullptr);
 // region sort -> gather + accumulate on `stream`, after the draw kernel that filled the stream.
 hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, int w, int h,
                                  hipStream_t stream);

@@ -1072,10 +1072,12 @@ size_t bytes_per_entry(const Shape &s) {
   return sizeof(uint32_t) + sizeof(uint16_t) + (s.two_level ? sizeof(uint32_t) : 0);
 }
 
+// (carved: where the array's size is noted for cb_debug_scatter_layout)
 template <typename T>
-T *carve(uintptr_t &p, size_t bytes) {
+T *carve(uintptr_t &p, size_t bytes, size_t &carved) {
   T *r = reinterpret_cast<T *>(p);
   p += round_up(bytes, 256);
+  carved = bytes;
   return r;
 }
 
@@ -1098,9 +1100,13 @@ size_t bin_workspace_bytes(int w, int h, uint32_t n_waves, double entries_per_wa
   return fixed_bytes(s, n_waves, max_regions_for(s, n_waves, entries)) + entries * bytes_per_entry(s) + 8192;
 }
 
-BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t n_waves, int n_channels) {
+BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t n_waves, int n_channels,
+                          BinLayoutBytes *carved) {
   BinLayout b;
   memset(&b, 0, sizeof(b));
+  BinLayoutBytes sizes;
+  memset(&sizes, 0, sizeof(sizes));
+  if (carved) *carved = sizes;
   b.e_row_shift = 16;
   b.e_col_mask = 0xffffu;
   b.e_row_mask = 0xffffu;
@@ -1135,54 +1141,67 @@ BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t 
   const uintptr_t p_end = p + bytes;
   p = (p + 255) & ~(uintptr_t) 255;
   if (p >= p_end) return b;
-  // The region table (and with it run_start) is sized by the entries, which are sized by what is left:
-  // shrink cap until everything fits.
+  // The region table (and with it run_start; chunked: an image of 64 KiB per region) is sized by the entries, which
+  // are sized by what is left: the largest cap with which everything fits.  (What the table takes falls with cap in
+  // steps, so the bytes a cap is over by do not say how far to cut: a search.  Cutting by them gave up on the suggested
+  // workspace of a chunked launch of few waves, where the images outweigh the segments, and elsewhere stopped up to
+  // a unit short of what the workspace was sized for.)
   const size_t per_entry = bytes_per_entry(s);
+  // segments start on 16-byte boundaries of the 16-bit sorted image too; chunked: a segment is a whole number of chunks
+  const unsigned long long unit = s.chunked ? kChunkWords : 8u;
+  static_assert(kMinRegionEntries % kChunkWords == 0 && kChunkWords % 8u == 0, "the search moves in units");
   unsigned long long cap = (p_end - p) / (per_entry * (size_t) n_waves);
   const unsigned long long cap_limit = 0xffffffffull / n_waves;  // all entries together < 2^32
   if (cap > cap_limit) cap = cap_limit;
-  for (;;) {
-    cap &= ~7ull;  // segments start on 16-byte boundaries of the 16-bit sorted image too
-    if (s.chunked) cap &= ~(unsigned long long) (kChunkWords - 1u);  // a segment is a whole number of chunks
-    if (cap < kMinRegionEntries) return b;
-    const uint32_t mr = max_regions_for(s, n_waves, cap * n_waves);
-    const size_t need = fixed_bytes(s, n_waves, mr) + (size_t) cap * n_waves * per_entry + 1024;
-    if (p + need <= p_end) break;
-    const size_t over = p + need - p_end;
-    const unsigned long long cut = over / (per_entry * (size_t) n_waves) + (s.chunked ? kChunkWords : 8u);
-    if (cut >= cap) return b;
-    cap -= cut;
+  cap = cap / unit * unit;
+  const auto fits = [&](unsigned long long c) {
+    const uint32_t mr = max_regions_for(s, n_waves, c * n_waves);
+    return p + fixed_bytes(s, n_waves, mr) + (size_t) c * n_waves * per_entry + 1024 <= p_end;
+  };
+  if (cap < kMinRegionEntries || !fits(kMinRegionEntries)) return b;
+  if (!fits(cap)) {
+    unsigned long long lo = kMinRegionEntries, hi = cap;  // multiples of unit: lo fits, hi does not
+    while (hi - lo > unit) {
+      const unsigned long long mid = (lo + (hi - lo) / 2) / unit * unit;
+      if (fits(mid)) {
+        lo = mid;
+      } else {
+        hi = mid;
+      }
+    }
+    cap = lo;
   }
   b.cap = (uint32_t) cap;
   b.max_regions = max_regions_for(s, n_waves, cap * n_waves);
   const size_t rows = b.n_tiles < kGroupTiles ? b.n_tiles : kGroupTiles;
-  b.wave_count = carve<uint32_t>(p, (size_t) n_waves * sizeof(uint32_t));
-  b.region_start = carve<unsigned long long>(p, (size_t) b.max_regions * sizeof(unsigned long long));
-  b.region_count = carve<uint32_t>(p, (size_t) b.max_regions * sizeof(uint32_t));
-  b.region_group = carve<uint32_t>(p, (size_t) b.max_regions * sizeof(uint32_t));
-  b.group_first = carve<uint32_t>(p, (size_t) kMaxGroups * sizeof(uint32_t));
-  b.group_regions = carve<uint32_t>(p, (size_t) kMaxGroups * sizeof(uint32_t));
-  b.owner_first = carve<uint32_t>(p, ((size_t) (n_waves > kMaxGroups ? n_waves : kMaxGroups) + 1) * sizeof(uint32_t));
-  b.n_regions = carve<uint32_t>(p, 256);
+  b.wave_count = carve<uint32_t>(p, (size_t) n_waves * sizeof(uint32_t), sizes.wave_count);
+  b.region_start = carve<unsigned long long>(p, (size_t) b.max_regions * sizeof(unsigned long long), sizes.region_start);
+  b.region_count = carve<uint32_t>(p, (size_t) b.max_regions * sizeof(uint32_t), sizes.region_count);
+  b.region_group = carve<uint32_t>(p, (size_t) b.max_regions * sizeof(uint32_t), sizes.region_group);
+  b.group_first = carve<uint32_t>(p, (size_t) kMaxGroups * sizeof(uint32_t), sizes.group_first);
+  b.group_regions = carve<uint32_t>(p, (size_t) kMaxGroups * sizeof(uint32_t), sizes.group_regions);
+  b.owner_first = carve<uint32_t>(p, ((size_t) (n_waves > kMaxGroups ? n_waves : kMaxGroups) + 1) * sizeof(uint32_t), sizes.owner_first);
+  b.n_regions = carve<uint32_t>(p, 256, sizes.n_regions);
   b.chunked = s.chunked;
   b.chunks_per_wave = s.chunked ? b.cap / kChunkWords : 0u;
-  b.run_start = carve<uint16_t>(p, rows * b.max_regions * sizeof(uint16_t));
-  b.slice_base = carve<uint32_t>(p, ((size_t) b.n_tiles + 1) * sizeof(uint32_t));
+  b.run_start = carve<uint16_t>(p, rows * b.max_regions * sizeof(uint16_t), sizes.run_start);
+  b.slice_base = carve<uint32_t>(p, ((size_t) b.n_tiles + 1) * sizeof(uint32_t), sizes.slice_base);
   if (b.two_level) {
     const size_t keys = (size_t) b.n_groups * kReplicas;
-    b.a_count = carve<uint32_t>(p, keys * n_waves * sizeof(uint32_t));
-    b.a_base = carve<unsigned long long>(p, (keys + 1) * sizeof(unsigned long long));
+    b.a_count = carve<uint32_t>(p, keys * n_waves * sizeof(uint32_t), sizes.a_count);
+    b.a_base = carve<unsigned long long>(p, (keys + 1) * sizeof(unsigned long long), sizes.a_base);
   }
-  b.stream = carve<uint32_t>(p, (size_t) n_waves * b.cap * sizeof(uint32_t));
+  b.stream = carve<uint32_t>(p, (size_t) n_waves * b.cap * sizeof(uint32_t), sizes.stream);
   if (b.chunked) {
-    b.chunk_desc = carve<uint32_t>(p, (size_t) n_waves * b.chunks_per_wave * sizeof(uint32_t));
-    b.chunk_list = carve<uint2>(p, (size_t) n_waves * b.chunks_per_wave * sizeof(uint2));
-    b.sorted = carve<uint16_t>(p, (size_t) b.max_regions * kRegionEntries * sizeof(uint16_t));
+    b.chunk_desc = carve<uint32_t>(p, (size_t) n_waves * b.chunks_per_wave * sizeof(uint32_t), sizes.chunk_desc);
+    b.chunk_list = carve<uint2>(p, (size_t) n_waves * b.chunks_per_wave * sizeof(uint2), sizes.chunk_list);
+    b.sorted = carve<uint16_t>(p, (size_t) b.max_regions * kRegionEntries * sizeof(uint16_t), sizes.sorted);
   } else {
-    if (b.two_level) b.grouped = carve<uint32_t>(p, (size_t) n_waves * b.cap * sizeof(uint32_t));
-    b.sorted = carve<uint16_t>(p, (size_t) n_waves * b.cap * sizeof(uint16_t));
+    if (b.two_level) b.grouped = carve<uint32_t>(p, (size_t) n_waves * b.cap * sizeof(uint32_t), sizes.grouped);
+    b.sorted = carve<uint16_t>(p, (size_t) n_waves * b.cap * sizeof(uint16_t), sizes.sorted);
   }
   b.enabled = 1;
+  if (carved) *carved = sizes;
   return b;
 }
 

@@ -488,6 +488,31 @@ int cb_abi_version(void);
  * gate: the value of `name`, or NULL unless CUDABROT_AMD_DEBUG=1 is set too -- a stray variable in a user's
  * environment cannot change the path the product takes.  (The reference has no such knobs.) */
 const char *cb_debug_knob(const char *name);
+/* Where the scatter keeps its arrays in a workspace ("Diagnostics and test knobs"): the carve that
+ * cb_draw_buddhabrot[_channels] and cb_flush_scatter[_channels] make of (d_workspace, workspace_bytes) for this canvas
+ * and n_threads -- a pure function of the arguments, so a test can write a stream of its own into a workspace and have
+ * the flush sort it.  n_channels = 0: the one-plane layout of cb_draw_buddhabrot / cb_flush_scatter (word = row << 16 |
+ * col); 1..CB_MAX_CHANNELS: the layout of the _channels entry points.  Host arithmetic only: no device memory is
+ * touched and nothing is launched, so it works without a GPU on any non-null d_workspace.  enabled = 0 (everything
+ * behind the word format 0): such a workspace is not used, the draw call adds with direct atomics.
+ * An array the layout does not have reports offset 0, bytes 0. */
+typedef struct cb_scatter_array {
+  uint64_t offset; /* bytes from d_workspace */
+  uint64_t bytes;  /* as carved (the next array starts on the next 256-byte boundary) */
+} cb_scatter_array;
+typedef struct cb_scatter_layout {
+  uint32_t enabled, n_waves, cap, n_tiles, tiles_x, tiles_y, n_planes, two_level, n_groups, chunked, chunks_per_wave,
+      max_regions;
+  /* a stream word: col = word & e_col_mask, row = (word >> e_row_shift) & e_row_mask,
+   * plane = (word >> e_chan_shift) & e_chan_mask */
+  uint32_t e_row_shift, e_col_mask, e_row_mask, e_chan_shift, e_chan_mask;
+  uint32_t reserved;
+  cb_scatter_array wave_count, stream, a_count, a_base, grouped, region_start, region_count, region_group, owner_first,
+      group_first, group_regions, n_regions, chunk_desc, chunk_list, run_start, slice_base, sorted;
+} cb_scatter_layout;
+/* 0, or hipErrorInvalidValue for a NULL dims / out, a canvas without pixels or n_channels outside 0..CB_MAX_CHANNELS. */
+int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, uint32_t n_threads,
+                            const void *d_workspace, size_t workspace_bytes, cb_scatter_layout *out);
 /* Which draw kernel the last cb_draw_buddhabrot* call of this process launched (the renderer's calls included):
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
  * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
