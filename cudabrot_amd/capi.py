@@ -25,6 +25,18 @@ CB_TONE_AUTO, CB_TONE_LUT, CB_TONE_THRESHOLDS = 0, 1, 2
 CB_KERNEL_FLAG_BURNING_SHIP = 0x100
 CB_KERNEL_FLAG_DRAIN = 0x200
 CB_KERNEL_FLAG_ANTI = 0x400  # the anti-Buddhabrot (with CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE; no channels)
+CB_POWER_MIN, CB_POWER_MAX = 3, 8  # the Multibrot step z^d + c (projected renders only)
+CB_KERNEL_POWER_MASK = 0xF000
+
+
+def CB_KERNEL_POWER(degree):
+    """The kernel-variant field of the Multibrot degree (OR-ed into CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE)."""
+    degree = int(degree)
+    if not CB_POWER_MIN <= degree <= CB_POWER_MAX:
+        raise ValueError("degree must be an integer from %d to %d" % (CB_POWER_MIN, CB_POWER_MAX))
+    return degree << 12
+
+
 CB_FOCUS_MIN_LEVEL, CB_FOCUS_MAX_LEVEL = 4, 10  # focused render: cells of side 2^-level
 CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
 # cb_counters.status bits (include/cudabrot_amd.h)

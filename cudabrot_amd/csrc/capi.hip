@@ -543,6 +543,7 @@ int cb_draw_buddhabrot(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
                        void *d_workspace, size_t workspace_bytes, void *d_carry, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states) return (int) hipErrorInvalidValue;
   if (dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0) return (int) hipErrorInvalidValue;  // projected renders only
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
   const int base_variant = kernel_variant & ~kVariantFlags;
   const bool anti = (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0;
@@ -611,7 +612,7 @@ int cb_draw_buddhabrot_channels(const cb_fractal_dimensions *dims, cb_pixel *d_h
     return (int) hipErrorInvalidValue;
   }
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  const int base_variant = kernel_variant & ~kVariantFlags;
+  const int base_variant = kernel_variant & ~kVariantFlags;  // a Multibrot degree stays in it and is refused below
   if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_FULL_ITERATE) ||
       (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0) {
     return (int) hipErrorInvalidValue;  // the wave-scheduled kernel only; no anti channels
@@ -725,7 +726,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
 
 namespace {
 
-// CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning Ship's flag: everything a focus launch accepts.
+// CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning Ship's flag: everything a focus launch accepts (a
+// Multibrot degree, CB_KERNEL_POWER_MASK, is one of the other bits).
 bool focus_variant_ok(int kernel_variant) {
   const int base_variant = kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP;
   return base_variant == CB_KERNEL_DEFAULT || base_variant == CB_KERNEL_SIMPLE;
@@ -851,7 +853,24 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
                                  uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                  int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!focus_variant_ok(kernel_variant) || !projection_ok(projection)) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection)) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0) {  // draw_power.hip: the Multibrot step, "Multibrot step"
+    const int degree = (kernel_variant & CB_KERNEL_POWER_MASK) >> 12;
+    const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;  // no Burning Ship, no anti
+    if (degree < CB_POWER_MIN || degree > CB_POWER_MAX || (base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE)) {
+      return (int) hipErrorInvalidValue;
+    }
+    cb::PowerArgs pw;
+    memset(&pw, 0, sizeof(pw));
+    pw.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+    memcpy(pw.p, projection, sizeof(pw.p));
+    pw.degree = degree;
+    const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
+    g_interior_level.store(0, std::memory_order_relaxed);  // the map is the Mandelbrot set's
+    g_last_draw_kernel.store(lockstep ? 11 : 10, std::memory_order_relaxed);
+    return (int) cb::launch_draw_power(pw, lockstep, reinterpret_cast<hipStream_t>(stream));
+  }
+  if (!focus_variant_ok(kernel_variant)) return (int) hipErrorInvalidValue;
   cb::ProjectArgs pa;
   memset(&pa, 0, sizeof(pa));
   pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
@@ -993,6 +1012,7 @@ int cb_renderer_prepare(cb_renderer *r, int kernel_variant) {
 
 int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_variant) {
   if (!r) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0 && !r->projected) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   const uint32_t max_passes_per_launch = ::max_passes_per_launch();
   prepare_for_variant(r, kernel_variant);

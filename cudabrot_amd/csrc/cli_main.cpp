@@ -21,7 +21,8 @@
 //    --focus-dilate D (a cropped canvas sampled only from the cells of the plane whose samples reach it:
 //    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on), --project
 //    a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG (the plane of the 4-D set (z_re, z_im, c_re, c_im) the orbits are
-//    plotted on: include/cudabrot_amd.h, "Projected render").
+//    plotted on: include/cudabrot_amd.h, "Projected render"), --power D (the Multibrot step z^D + c, D = 3 .. 8, on
+//    the projected path: include/cudabrot_amd.h, "Multibrot step").
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -86,7 +87,11 @@ struct Settings {
   bool project_given = false, plane_given = false, rotate_given = false;
   double projection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
   const char *bad_project_flag = nullptr;           // the message of a bad --project / --plane / --rotate
-  bool projected() const { return project_given || plane_given || rotate_given; }
+  // --power D (extension): the Multibrot step z^D + c, CB_KERNEL_POWER(D); makes the run a projected one (the identity
+  // unless a plane is given)
+  int power = 0;
+  const char *bad_power_flag = nullptr;             // the message of a bad --power
+  bool projected() const { return project_given || plane_given || rotate_given || power != 0; }
 };
 
 // One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
@@ -330,6 +335,16 @@ const std::vector<Flag> &flag_table() {
            s.bad_project_flag = "Invalid rotation (want X,Y:DEG, two different axes of zr, zi, cr, ci and a finite angle)";
          }
        }},
+      {"--power", Value::kText, nullptr, false,  // text: a value that is no integer gets the flag's own message
+       [](Settings &s, long, double, const char *t) {
+         char *end = nullptr;
+         const long d = strtol(t, &end, 10);
+         if (t[0] == 0 || *end != 0 || d < CB_POWER_MIN || d > CB_POWER_MAX) {
+           s.bad_power_flag = "Invalid power (want an integer from 3 to 8)";
+           return;
+         }
+         s.power = (int) d;
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -467,7 +482,25 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_project_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_power_flag) {
+      printf("%s: %s\n", s.bad_power_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  // a Multibrot render is a projected render with a step of its own (include/cudabrot_amd.h, "Multibrot step"): its
+  // refusals come before the projection's, which it would otherwise trip
+  if (s.power != 0) {
+    const char *with = s.burning_ship                         ? "--burning-ship"
+                       : s.anti                               ? "--anti"
+                       : s.focus                              ? "--focus"
+                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
+                       : s.gpus > 1                           ? "--gpus above 1"
+                                                              : nullptr;
+    if (with) {
+      printf("--power does not combine with %s.\n", with);
+      usage_and_exit(argv[0]);
+    }
   }
   // a projected render is one plane of escaping orbits on one device, sampled uniformly (include/cudabrot_amd.h,
   // cb_renderer_set_projection)
@@ -545,6 +578,7 @@ class Run {
       const double *p = cfg_.projection;
       fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
               p[3], p[4], p[5], p[6], p[7]);
+      if (cfg_.power != 0) fprintf(stderr, "{\"power\": %d}\n", cfg_.power);  // the step: it defines the run as well
       fflush(stderr);
     }
     setup();
@@ -711,7 +745,7 @@ class Run {
     }
     fflush(stdout);
     const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0) |
-                        (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0);
+                        (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0) | (cfg_.power ? CB_KERNEL_POWER(cfg_.power) : 0);
     if (cfg_.focus) set_focus(variant);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));

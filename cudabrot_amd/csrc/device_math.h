@@ -144,6 +144,52 @@ __device__ __forceinline__ double mandel_step2_ship(double CR, double CI, double
   return __builtin_fma(NI, NI, NR * NR);
 }
 
+// ---- the Multibrot step z <- z^d + c (include/cudabrot_amd.h, "Multibrot step") -----------------------
+//
+// The power is d - 1 multiplications by z, left to right: w <- w * z with
+//   t = wi*i; nr = fma(wr, r, -t); s = wi*r; ni = fma(wr, i, s)
+// then r' = cr + wr, i' = ci + wi, m = fma(i', i', r'*r').  4 (d - 1) multiplies and FMAs, 2 adds, 2 for m.
+// Written twice, so that the lock-step kernel and the product kernel of draw_power.hip are two writings of the
+// definition: power_step is the run-time loop, power_step_n<D> the same sequence unrolled by the template.
+__device__ __forceinline__ double power_step(int d, double cr, double ci, double &r, double &i) {
+  double wr = r, wi = i;
+  for (int n = 1; n < d; ++n) {
+    const double t = wi * i;
+    const double nr = __builtin_fma(wr, r, -t);
+    const double s = wi * r;
+    const double ni = __builtin_fma(wr, i, s);
+    wr = nr;
+    wi = ni;
+  }
+  const double nr = cr + wr;
+  const double ni = ci + wi;
+  r = nr;
+  i = ni;
+  return __builtin_fma(ni, ni, nr * nr);
+}
+
+// (wr, wi) <- (wr, wi) * (r, i), N times.
+template <int N>
+__device__ __forceinline__ void power_times_z(double r, double i, double &wr, double &wi) {
+  if constexpr (N > 0) {
+    const double re = __builtin_fma(wr, r, -(wi * i));
+    const double im = __builtin_fma(wr, i, wi * r);
+    wr = re;
+    wi = im;
+    power_times_z<N - 1>(r, i, wr, wi);
+  }
+}
+
+template <int D>
+__device__ __forceinline__ double power_step_n(double cr, double ci, double &r, double &i) {
+  static_assert(D >= 3 && D <= 8, "CB_POWER_MIN .. CB_POWER_MAX");
+  double wr = r, wi = i;
+  power_times_z<D - 1>(r, i, wr, wi);
+  r = cr + wr;
+  i = ci + wi;
+  return __builtin_fma(i, i, r * r);
+}
+
 // Canvas geometry as the kernels consume it: FractalDimensions (cudabrot.cu:46-58) plus the exact
 // reciprocal fast path of SURVEY.md H3.
 struct Canvas {

@@ -1,6 +1,6 @@
 // draw_rounds.h -- what the kernels with one reference thread per lane share (kernels.hip's draw_simple_kernel,
-// draw_anti.hip, draw_focus.hip, draw_project.hip): the per-lane counters, the reference's escape-index loop for the
-// lock-step kernels, and the round scheduler of the three product kernels.
+// draw_anti.hip, draw_focus.hip, draw_project.hip, draw_power.hip): the per-lane counters, the reference's escape-index
+// loop for the lock-step kernels, and the round scheduler of the product kernels.
 #pragma once
 
 #include "draw_common.h"
@@ -66,7 +66,8 @@ __device__ __forceinline__ bool brent_save(uint32_t chunks) {
 // Every lane owns one reference thread (its generator, its samples_per_thread samples) and works on one sample at a
 // time.  The wave advances in ROUNDS of kRound steps; in a round each lane makes up to kRound steps of its own phase,
 // and between rounds each lane, on its own, does its bookkeeping.  What a kernel adds is its MODE: a struct with the
-// step (kShip), whatever per-lane state it needs beyond RoundLane, and four inlined hooks, named where they are called:
+// step (kShip, or a step of its own: round_step below), whatever per-lane state it needs beyond RoundLane, and four
+// inlined hooks, named where they are called:
 //   NEXT     the lane's next sample, or DONE when it has none left.  mode.next draws c and says what becomes of it: it
 //            is iterated, or retired as drawn -- rejected (cardioid, bulb), or proven interior and counted as the
 //            reference counts a sample that never escapes -- and the next one drawn.  (max_iter 0 needs no case of its
@@ -96,6 +97,17 @@ struct RoundLane {
   int saved = 0;                                  // ITERATE: index of the saved point (0: none yet)
   int end = 0;                                    // ESCAPED: the step that escaped; REPLAY: the last index replayed
 };
+
+// The step of a round: the mode's own `double step(RoundLane &)` where it has one (it advances l.r, l.i and returns
+// |z|^2), else the reference's step, picked by Mode::kShip.  ITERATE and REPLAY make the same call.
+template <class Mode>
+__device__ __forceinline__ auto round_step(Mode &mode, RoundLane &l, int) -> decltype(mode.step(l)) {
+  return mode.step(l);
+}
+template <class Mode>
+__device__ __forceinline__ double round_step(Mode &, RoundLane &l, long) {
+  return orbit_step<Mode::kShip>(l.cr, l.ci, l.r, l.i);
+}
 
 template <class Mode>
 __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
@@ -141,7 +153,7 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
 #pragma unroll 2
     for (int t = 0; t < kRound; ++t) {
       if (l.k < stop) {
-        const double m = orbit_step<Mode::kShip>(l.cr, l.ci, l.r, l.i);
+        const double m = round_step(mode, l, 0);
         ++l.k;
         if (phase == kRoundReplay) {
           if (mode.point(l, st)) {

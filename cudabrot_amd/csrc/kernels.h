@@ -243,6 +243,17 @@ struct ProjectArgs {
 };
 hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_power.hip: the Multibrot Buddhabrot (include/cudabrot_amd.h, "Multibrot step"): the projected render with the step
+// z <- z^degree + c, CB_POWER_MIN <= degree <= CB_POWER_MAX (anything else: hipErrorInvalidValue, nothing launched).  p as
+// in ProjectArgs.  d carries the canvas, the iteration control, the generators and the counters; its burning_ship,
+// interior-map, workspace and carry fields are not read.
+struct PowerArgs {
+  DrawArgs d;
+  double p[8];
+  int degree;
+};
+hipError_t launch_draw_power(const PowerArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

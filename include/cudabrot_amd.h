@@ -127,6 +127,50 @@ typedef struct {
  * (hipErrorInvalidValue), as cb_draw_buddhabrot does with any other base variant. */
 #define CB_KERNEL_FLAG_ANTI 0x400
 
+/* ---- Multibrot step: z^d + c on the projected render ----------------------------- *
+ *
+ * CB_KERNEL_POWER(d), OR-ed into CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, replaces the step of a PROJECTED render
+ * ("Projected render" below) by z <- z^d + c.  Field 0 means the step as without it.  Normative:
+ *
+ *   Degree.  CB_POWER_MIN = 3 <= d <= CB_POWER_MAX = 8.
+ *
+ *   Step.  One step from z = (r, i) with sample c = (cr, ci) is IEEE fp64; each fma is one rounding and nothing else is
+ *   contracted:
+ *       wr = r; wi = i
+ *       repeat d-1 times, in this order:
+ *           t  = wi * i            nr = fma(wr, r, -t)
+ *           s  = wi * r            ni = fma(wr, i,  s)
+ *           wr = nr; wi = ni
+ *       r' = cr + wr;  i' = ci + wi
+ *       m  = fma(i', i', r' * r')          escape: m > 4.0
+ *   The power is d - 1 multiplications by z, left to right.  Addition chains such as (z^2)^2 are faster but round
+ *   differently, so they are not this definition.
+ *
+ *   Everything else is the projected render's: the normal sample stream (4 XORWOW draws per sample, z_0 = c),
+ *   IterateMandelbrot's loop shape (k = index of the first escaping z_{k+1}, or max), the accept filter min <= k < max,
+ *   the replay of z_1 ... z_{k+1}, the projection P[2][4] with its four fused operations per point, and the binning.  As
+ *   for the Burning Ship there is no cardioid or bulb rejection (rejected = 0) and no interior map.  Counters keep their
+ *   normal meaning; skipped_steps is the executed-work discount.
+ *
+ *   Every visited point is finite: the point before an escaping one has |z|^2 <= 4, so the escaping point has
+ *   |z| <= 2^8 + |c|.  The plain Multibrot image is therefore the identity projection P = {{1,0,0,0},{0,1,0,0}}, which
+ *   cannot move a bin ("Projected render", Identity).
+ *
+ * Accepted by cb_draw_buddhabrot_projected and by cb_renderer_render_passes / cb_renderer_prepare on a projected
+ * renderer.  hipErrorInvalidValue, with nothing launched or written: a field value of 1, 2 or 9 ... 15; a degree together
+ * with CB_KERNEL_FLAG_BURNING_SHIP, CB_KERNEL_FLAG_ANTI or a base variant other than the two above; a degree given to
+ * cb_draw_buddhabrot, cb_draw_buddhabrot_channels, cb_focus_probe, cb_draw_buddhabrot_focus, cb_renderer_set_focus, or to
+ * cb_renderer_render_passes on a renderer without a projection.
+ * Two kernels (draw_power.hip): CB_KERNEL_DEFAULT, one instance per degree with the step unrolled, lanes refilled from
+ * their own subsequence, with the exact-periodicity early-out; CB_KERNEL_SIMPLE, the definition in lock-step with the
+ * degree a run-time argument.  Identical histograms, generator states and counters (but skipped_steps).
+ * The -s buffer records the degree no more than it records the plane: resuming a buffer with another degree adds two
+ * different images, and nothing can notice. */
+#define CB_POWER_MIN 3
+#define CB_POWER_MAX 8
+#define CB_KERNEL_POWER(d) ((d) << 12)
+#define CB_KERNEL_POWER_MASK 0xF000
+
 /* Returned (instead of a hipError_t) by cb_renderer_set_focus when the probe marked no cell: no sample of the probe has
  * an accepted orbit that enters the canvas, so a focused render would have nothing to sample from. */
 #define CB_ERROR_FOCUS_EMPTY 100002
@@ -311,6 +355,7 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
  * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence, with the interior map
  * (Mandelbrot step only) and the exact-periodicity early-out, and CB_KERNEL_SIMPLE, the definition in lock-step;
  * optionally | CB_KERNEL_FLAG_BURNING_SHIP; any other variant, CB_KERNEL_FLAG_ANTI included, is hipErrorInvalidValue.
+ * (| CB_KERNEL_POWER(d) instead of the Burning Ship's flag: the Multibrot step and its two kernels, "Multibrot step".)
  * Identical histograms, generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry:
  * every launch is complete when it ends.  The -s buffer format is unchanged and does NOT record the plane: resuming a
  * buffer with another projection adds two different images, and nothing can notice. */
@@ -517,7 +562,9 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
  * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
  * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel,
- * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel.
+ * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
+ * 10 the Multibrot product kernel (draw_power_kernel: cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot
+ * lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

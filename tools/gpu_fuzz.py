@@ -16,6 +16,9 @@ and demands identical histograms and counters.
     ANTI=1 python tools/gpu_fuzz.py ...            the anti-Buddhabrot (CB_KERNEL_FLAG_ANTI): draw_anti_kernel against
                                                    draw_anti_simple_kernel, generator states compared as well; M from
                                                    the edges of its rounds (12 steps) and chunks (60 steps)
+    POWER=1 python tools/gpu_fuzz.py ...           the Multibrot render (CB_KERNEL_POWER): draw_power_kernel<D> against
+                                                   draw_power_simple_kernel -- random degree, shapes and matrices,
+                                                   generator states compared as well
 """
 import os
 
@@ -222,6 +225,87 @@ def anti_main(seconds, seed):
     return 0
 
 
+def power_trial(rng):
+    """A Multibrot launch sequence: any degree, max_iter at and around the scheduler's rounds (12 steps) and chunks (60),
+    ragged thread counts, several launches on the same generators, a plane out of unit rows or a random matrix."""
+    t = {}
+    canvas_and_box(rng, t)
+    t["degree"] = rng.randint(cb.CB_POWER_MIN, cb.CB_POWER_MAX)
+    t["max_iter"] = rng.choice([0, 1, 5, 11, 12, 13, 59, 60, 61, 119, 120, 121, 180, 257, 1000, 2000, 5000, 20000])
+    t["min_iter"] = rng.choice([0, 0, 1, 2, 20, 59, 60, 99, 1000, 30000])
+    t["threads"] = rng.choice([1, 63, 64, 65, 200, 256, 1000, 1024, 1337, 4096, 5000, 16384])
+    if t["max_iter"] >= 5000:   # keep the lock-step kernel's run time in hand
+        t["threads"] = min(t["threads"], 4096)
+    t["launch_samples"] = [rng.choice([1, 2, 7, 50, 64, 100, 150]) for _ in range(rng.randint(1, 4))]
+    t["seed"] = rng.choice([1337, 1337, 1, 0xdeadbeefcafe])
+    t["first"] = rng.choice([0, 0, 1, 262144, 2097151])
+    kind = rng.random()
+    if kind < 0.3:
+        t["matrix"] = list(cb.IDENTITY_PROJECTION)
+    elif kind < 0.6:   # two different axes of (zr, zi, cr, ci)
+        x, y = rng.sample(range(4), 2)
+        t["matrix"] = [1.0 if j == x else 0.0 for j in range(4)] + [1.0 if j == y else 0.0 for j in range(4)]
+    else:
+        t["matrix"] = [rng.uniform(-1.5, 1.5) for _ in range(8)]
+    return t
+
+
+def render_power(t, variant):
+    """The launches of a Multibrot trial -> (histogram, counters, generator states)."""
+    dev = torch.device("cuda", 0)
+    dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
+    it = cb.IterationControl(t["max_iter"], t["min_iter"])
+    n = t["threads"]
+    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
+    hist = torch.zeros(t["w"] * t["h"], dtype=torch.int64, device=dev)
+    counters = torch.zeros(17, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
+    for s in t["launch_samples"]:
+        cb.draw_buddhabrot_projected(dims, hist.data_ptr(), it, t["matrix"], states.data_ptr(), n, s, counters.data_ptr(),
+                                     variant | cb.CB_KERNEL_POWER(t["degree"]), stream)
+    torch.cuda.synchronize()
+    c = counters.cpu().numpy().view(np.uint64)
+    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
+    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
+
+
+def power_main(seconds, seed):
+    rng = random.Random(seed)
+    t_end = time.time() + seconds
+    n = early = 0
+    last_print = time.time()
+    while time.time() < t_end:
+        t = power_trial(rng)
+        try:
+            want, wc, want_states = render_power(t, cb.CB_KERNEL_SIMPLE)
+            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 11
+            got, gc, got_states = render_power(t, cb.CB_KERNEL_DEFAULT)
+            product_ran = cb.lib.cb_debug_last_draw_kernel() == 10
+        except cb.CudabrotError as e:
+            print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
+            return 1
+        bad = [k for k in COMPARED if wc[k] != gc[k]]
+        if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
+                lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or wc["rejected"] != 0:
+            print("MISMATCH at power trial %d (seed %d): %r" % (n, seed, t))
+            print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
+            print("  counters that differ: %r; lock-step skipped_steps %d, rejected %d" % (
+                [(k, wc[k], gc[k]) for k in bad], wc["skipped_steps"], wc["rejected"]))
+            print("  generator states identical: %s" % np.array_equal(want_states, got_states))
+            print("  pixels that differ: %d of %d; sums %d vs %d" % (int((want != got).sum()), want.size,
+                                                                     int(want.sum()), int(got.sum())), flush=True)
+            return 1
+        n += 1
+        early += 1 if gc["skipped_steps"] > 0 else 0
+        if time.time() - last_print > 30:
+            print("%d power trials identical so far (%d with skipped_steps > 0)" % (n, early), flush=True)
+            last_print = time.time()
+    print("gpu_fuzz: %d power trials (%d with skipped_steps > 0), histograms, counters and generator states identical "
+          "(seed %d)" % (n, early, seed))
+    return 0
+
+
 def heavy_trial(rng):
     """Product-sized launches: the deferred scatter (one and two sort levels, carry) against the same
     kernel with direct atomics -- the lock-step kernel would take minutes at these sizes."""
@@ -293,6 +377,8 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     if os.environ.get("ANTI") == "1":
         return anti_main(seconds, seed)
+    if os.environ.get("POWER") == "1":
+        return power_main(seconds, seed)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     n = 0
