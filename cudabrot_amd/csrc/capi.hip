@@ -854,38 +854,31 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
                                  int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection)) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0) {  // draw_power.hip: the Multibrot step, "Multibrot step"
-    const int degree = (kernel_variant & CB_KERNEL_POWER_MASK) >> 12;
-    const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;  // no Burning Ship, no anti
-    if (degree < CB_POWER_MIN || degree > CB_POWER_MAX || (base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE)) {
-      return (int) hipErrorInvalidValue;
-    }
-    cb::PowerArgs pw;
-    memset(&pw, 0, sizeof(pw));
-    pw.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-    memcpy(pw.p, projection, sizeof(pw.p));
-    pw.degree = degree;
-    const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
-    g_interior_level.store(0, std::memory_order_relaxed);  // the map is the Mandelbrot set's
-    g_last_draw_kernel.store(lockstep ? 11 : 10, std::memory_order_relaxed);
-    return (int) cb::launch_draw_power(pw, lockstep, reinterpret_cast<hipStream_t>(stream));
+  // The Multibrot step ("Multibrot step"): a degree CB_POWER_MIN .. CB_POWER_MAX, no Burning Ship, no anti
+  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
+  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
+  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
+  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
+    return (int) hipErrorInvalidValue;
   }
-  if (!focus_variant_ok(kernel_variant)) return (int) hipErrorInvalidValue;
   cb::ProjectArgs pa;
   memset(&pa, 0, sizeof(pa));
   pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  pa.d.burning_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0 ? 1 : 0;
+  pa.d.burning_ship = ship ? 1 : 0;
   memcpy(pa.p, projection, sizeof(pa.p));
-  const bool lockstep = (kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
-  // The interior map where the normal product path consults it: wants_interior_map's rule (not the lock-step kernel, not
-  // the Burning Ship, not with the knob), and only when max_iter leaves that path a LONG stage (max_iter > head + mid
-  // steps of plan_stages, 20 for min_iter <= 16) -- below that it retires nothing through the map either.
+  pa.degree = degree;
+  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
+  // The interior map (the Mandelbrot set's: degree 2 only) where the normal product path consults it: wants_interior_map's
+  // rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter leaves that path a
+  // LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it retires nothing
+  // through the map either.
   g_interior_level.store(0, std::memory_order_relaxed);
-  if (pa.d.long_steps > 0) {
+  if (!power && pa.d.long_steps > 0) {
     const int rc = attach_interior_map(pa.d, kernel_variant);
     if (rc) return rc;
   }
-  g_last_draw_kernel.store(lockstep ? 9 : 8, std::memory_order_relaxed);
+  g_last_draw_kernel.store((power ? 10 : 8) + (lockstep ? 1 : 0), std::memory_order_relaxed);
   return (int) cb::launch_draw_project(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -149,7 +149,7 @@ __device__ __forceinline__ double mandel_step2_ship(double CR, double CI, double
 // The power is d - 1 multiplications by z, left to right: w <- w * z with
 //   t = wi*i; nr = fma(wr, r, -t); s = wi*r; ni = fma(wr, i, s)
 // then r' = cr + wr, i' = ci + wi, m = fma(i', i', r'*r').  4 (d - 1) multiplies and FMAs, 2 adds, 2 for m.
-// Written twice, so that the lock-step kernel and the product kernel of draw_power.hip are two writings of the
+// Written twice, so that the Multibrot lock-step kernel and product kernel of draw_project.hip are two writings of the
 // definition: power_step is the run-time loop, power_step_n<D> the same sequence unrolled by the template.
 __device__ __forceinline__ double power_step(int d, double cr, double ci, double &r, double &i) {
   double wr = r, wi = i;

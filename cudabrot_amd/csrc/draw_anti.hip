@@ -76,8 +76,7 @@ struct AntiMode {
   unsigned long long q = 0ull;
 
   __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    l.cr = sample_coordinate(rng);
-    l.ci = sample_coordinate(rng);
+    uniform_sample(rng, l.cr, l.ci);
     return kSampleIterate;
   }
 

@@ -46,8 +46,7 @@ __device__ __forceinline__ void next_sample(const FocusArgs &a, Xorwow &rng, dou
     cr = lo_re + off_re;
     ci = lo_im + off_im;
   } else {
-    cr = sample_coordinate(rng);
-    ci = sample_coordinate(rng);
+    uniform_sample(rng, cr, ci);
   }
 }
 
@@ -149,23 +148,11 @@ struct FocusMode {
     return kSampleIterate;
   }
 
+  // the mask sink counts `recorded` at the point that ends its replay, and gives back the steps it does not make
   __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
-    st.iterate_steps += (unsigned long long) l.end;
-    if (l.end - 1 < fa.d.min_iter) {
-      st.too_fast++;
-      return false;
-    }
-    if (!kMask) st.recorded++;
-    st.replay_steps += (unsigned long long) l.end;  // the mask sink gives back the steps it does not make
-    return true;
+    return count_escaped(l, fa.d.min_iter, st, !kMask);
   }
-
-  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) {
-    st.never_escaped++;
-    st.iterate_steps += (unsigned long long) l.max_iter;
-    st.reserved += (unsigned long long) (l.max_iter - l.k);  // 0 at k == max_iter
-    return false;
-  }
+  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) { return count_never_escapes(l, st); }
 
   __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
     int row, col;

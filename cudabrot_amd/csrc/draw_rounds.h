@@ -1,6 +1,7 @@
 // draw_rounds.h -- what the kernels with one reference thread per lane share (kernels.hip's draw_simple_kernel,
-// draw_anti.hip, draw_focus.hip, draw_project.hip, draw_power.hip): the per-lane counters, the reference's escape-index
-// loop for the lock-step kernels, and the round scheduler of the product kernels.
+// draw_anti.hip, draw_focus.hip, draw_project.hip): the per-lane counters, the uniform sample, the reference's
+// escape-index loop for the lock-step kernels, and the round scheduler of the product kernels with the escape accounting
+// of its modes.
 #pragma once
 
 #include "draw_common.h"
@@ -30,6 +31,12 @@ __device__ __forceinline__ void flush_stats(cb_counters *counters, const LaneSta
     }
     if (v[9]) __hip_atomic_fetch_or(c + 9, v[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// The sample of the normal stream: c uniform over [-2, 2)^2, two draws per coordinate.
+__device__ __forceinline__ void uniform_sample(Xorwow &rng, double &real, double &imag) {
+  real = sample_coordinate(rng);
+  imag = sample_coordinate(rng);
 }
 
 // IterateMandelbrot (cudabrot.cu:319-340) for the lock-step kernels: the k of the first z_{k+1} with |z|^2 > 4, or
@@ -107,6 +114,27 @@ __device__ __forceinline__ auto round_step(Mode &mode, RoundLane &l, int) -> dec
 template <class Mode>
 __device__ __forceinline__ double round_step(Mode &, RoundLane &l, long) {
   return orbit_step<Mode::kShip>(l.cr, l.ci, l.r, l.i);
+}
+
+// The escape accounting of an escape render's mode (not the anti-Buddhabrot's, which records the other samples).
+// mode.escaped: the sample went l.end steps; through the accept filter min <= k < max, k = l.end - 1, to REPLAY (true).
+// recorded = false: the mode counts `recorded` itself (the mask sink, at the point that ends its replay).
+__device__ __forceinline__ bool count_escaped(const RoundLane &l, int min_iter, LaneStats &st, bool recorded = true) {
+  st.iterate_steps += (unsigned long long) l.end;
+  if (l.end - 1 < min_iter) {
+    st.too_fast++;
+    return false;
+  }
+  if (recorded) st.recorded++;
+  st.replay_steps += (unsigned long long) l.end;
+  return true;
+}
+// mode.never_escapes: counted as the reference counts it, the steps not made in skipped_steps; nothing to replay.
+__device__ __forceinline__ bool count_never_escapes(const RoundLane &l, LaneStats &st) {
+  st.never_escaped++;
+  st.iterate_steps += (unsigned long long) l.max_iter;
+  st.reserved += (unsigned long long) (l.max_iter - l.k);  // 0 at k == max_iter
+  return false;
 }
 
 template <class Mode>

@@ -234,25 +234,17 @@ struct FocusArgs {
 hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream);
 
 // draw_project.hip: the projected render (include/cudabrot_amd.h, "Projected render").  p is the matrix P[2][4], rows
-// (u, v), columns (z_re, z_im, c_re, c_im), finite.  d carries the canvas (the (u, v) window), the iteration control, the
-// generators, the counters, burning_ship and the interior map (null: none; read by the product kernel with the Mandelbrot
-// step only); its workspace and carry fields are not read.
+// (u, v), columns (z_re, z_im, c_re, c_im), finite.  degree picks the step: 2, the reference's (d.burning_ship: its Burning
+// Ship variant), or CB_POWER_MIN .. CB_POWER_MAX, the Multibrot step z <- z^degree + c ("Multibrot step"), which has no
+// Burning Ship variant; anything else: hipErrorInvalidValue, nothing launched.  d carries the canvas (the (u, v) window),
+// the iteration control, the generators, the counters, burning_ship and the interior map (null: none; read by the product
+// kernel with the Mandelbrot step only); its workspace and carry fields are not read.
 struct ProjectArgs {
-  DrawArgs d;
-  double p[8];
-};
-hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
-
-// draw_power.hip: the Multibrot Buddhabrot (include/cudabrot_amd.h, "Multibrot step"): the projected render with the step
-// z <- z^degree + c, CB_POWER_MIN <= degree <= CB_POWER_MAX (anything else: hipErrorInvalidValue, nothing launched).  p as
-// in ProjectArgs.  d carries the canvas, the iteration control, the generators and the counters; its burning_ship,
-// interior-map, workspace and carry fields are not read.
-struct PowerArgs {
   DrawArgs d;
   double p[8];
   int degree;
 };
-hipError_t launch_draw_power(const PowerArgs &a, bool lockstep, hipStream_t stream);
+hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

@@ -161,7 +161,7 @@ typedef struct {
  * with CB_KERNEL_FLAG_BURNING_SHIP, CB_KERNEL_FLAG_ANTI or a base variant other than the two above; a degree given to
  * cb_draw_buddhabrot, cb_draw_buddhabrot_channels, cb_focus_probe, cb_draw_buddhabrot_focus, cb_renderer_set_focus, or to
  * cb_renderer_render_passes on a renderer without a projection.
- * Two kernels (draw_power.hip): CB_KERNEL_DEFAULT, one instance per degree with the step unrolled, lanes refilled from
+ * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, one instance per degree with the step unrolled, lanes refilled from
  * their own subsequence, with the exact-periodicity early-out; CB_KERNEL_SIMPLE, the definition in lock-step with the
  * degree a run-time argument.  Identical histograms, generator states and counters (but skipped_steps).
  * The -s buffer records the degree no more than it records the plane: resuming a buffer with another degree adds two
@@ -563,8 +563,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
  * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel,
  * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
- * 10 the Multibrot product kernel (draw_power_kernel: cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot
- * lock-step kernel.
+ * 10 the Multibrot product kernel (draw_power_kernel, the projected render's with the power step:
+ * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

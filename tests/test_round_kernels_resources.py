@@ -1,7 +1,8 @@
 """What the compiler makes of the kernels with one reference thread per lane (draw_anti.hip, draw_focus.hip,
-draw_project.hip: three modes of draw_rounds.h's scheduler and their lock-step twins), checked where it is built: hipcc
+draw_project.hip: the modes of draw_rounds.h's scheduler and their lock-step twins), checked where it is built: hipcc
 cross-compiles for gfx950 without a GPU and reports every kernel's resources.  DESIGN.md sections 4.9 to 4.11 claim no
-spill, no scratch, no AGPRs and no LDS for every instance, and per file the registers and waves per SIMD below."""
+spill, no scratch, no AGPRs and no LDS for every instance, and per file the registers and waves per SIMD below.
+draw_project.hip also holds the Multibrot kernels: tests/test_power_kernels_resources.py."""
 
 import os
 import re
@@ -18,21 +19,9 @@ def at_most(vgprs, waves):
     return lambda k: int(k["VGPRs"]) <= vgprs and int(k["Occupancy [waves/SIMD]"]) >= waves
 
 
-# file -> (product kernel, its instances, its bar, lock-step kernel, its bar)
-FILES = {
-    # <ship> x 2; the lock-step kernel takes the ship as a run-time flag
-    "draw_anti": ("draw_anti_kernel", 2, at_most(72, 7), "draw_anti_simple_kernel",
-                  lambda k: int(k["VGPRs"]) <= 64 and int(k["Occupancy [waves/SIMD]"]) == 8),
-    # (cells, histogram), (uniform, mask), (uniform, histogram), each for both steps
-    "draw_focus": ("draw_focus_kernel", 6, at_most(128, 4), "draw_focus_simple_kernel", at_most(128, 4)),
-    "draw_project": ("draw_project_kernel", 2, at_most(128, 4), "draw_project_simple_kernel", at_most(128, 4)),
-}
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-@pytest.mark.parametrize("name", list(FILES))
-def test_round_kernels_fit_without_scratch(tmp_path, name):
-    product_name, instances, product_bar, lockstep_name, lockstep_bar = FILES[name]
+def compile_kernels(tmp_path, name):
+    """Every kernel of cudabrot_amd/csrc/<name>.hip as the compiler reports it: [{"name": mangled, remark: value}], and
+    the assembly it wrote."""
     flags = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-S",
              "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run([HIPCC, *flags, "-o", str(tmp_path / "kernels.s"), os.path.join(CSRC, name + ".hip")],
@@ -50,16 +39,36 @@ def test_round_kernels_fit_without_scratch(tmp_path, name):
         elif cur is not None and ":" in body:
             k, v = body.split(":", 1)
             cur[k.strip()] = v.strip()
+    with open(tmp_path / "kernels.s") as f:
+        return kernels, f.read()
+
+
+# file -> (product kernel, its instances, its bar, lock-step kernel, its bar, kernels in the file)
+FILES = {
+    # <ship> x 2; the lock-step kernel takes the ship as a run-time flag
+    "draw_anti": ("draw_anti_kernel", 2, at_most(72, 7), "draw_anti_simple_kernel",
+                  lambda k: int(k["VGPRs"]) <= 64 and int(k["Occupancy [waves/SIMD]"]) == 8, 3),
+    # (cells, histogram), (uniform, mask), (uniform, histogram), each for both steps
+    "draw_focus": ("draw_focus_kernel", 6, at_most(128, 4), "draw_focus_simple_kernel", at_most(128, 4), 7),
+    # and the seven Multibrot kernels (tests/test_power_kernels_resources.py)
+    "draw_project": ("draw_project_kernel", 2, at_most(128, 4), "draw_project_simple_kernel", at_most(128, 4), 10),
+}
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@pytest.mark.parametrize("name", list(FILES))
+def test_round_kernels_fit_without_scratch(tmp_path, name):
+    product_name, instances, product_bar, lockstep_name, lockstep_bar, total = FILES[name]
+    kernels, assembly = compile_kernels(tmp_path, name)
     product = [k for k in kernels if product_name in k["name"]]
     lockstep = [k for k in kernels if lockstep_name in k["name"]]
     # the product instances, one lock-step kernel, nothing else
-    assert len(product) == instances and len(lockstep) == 1 and len(kernels) == instances + 1, [k["name"] for k in kernels]
-    for k in product + lockstep:
+    assert len(product) == instances and len(lockstep) == 1 and len(kernels) == total, [k["name"] for k in kernels]
+    for k in kernels:
         assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
         assert int(k["AGPRs"]) == 0 and int(k["LDS Size [bytes/block]"]) == 0, k
     for k in product:
         assert product_bar(k), k
     for k in lockstep:
         assert lockstep_bar(k), k
-    with open(tmp_path / "kernels.s") as f:
-        assert "scratch_" not in f.read()
+    assert "scratch_" not in assembly
