@@ -249,6 +249,10 @@ def _load():
         "cb_draw_buddhabrot_projected": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), vp, u32, u32, vp, i32, vp]),
         "cb_renderer_set_projection": (i32, [vp, C.POINTER(C.c_double)]),
         "cb_renderer_projection": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_draw_buddhabrot_julia": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, u32,
+                                           vp, i32, vp]),
+        "cb_renderer_set_julia": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "cb_renderer_julia": (i32, [vp, C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -269,7 +273,8 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_channels cb_flush_scatter_channels cb_renderer_create_channels cb_renderer_grayscale_plane cb_renderers_reduce "
     "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be "
     "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells "
-    "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout"
+    "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout "
+    "cb_draw_buddhabrot_julia cb_renderer_set_julia cb_renderer_julia"
 ).split()
 
 
@@ -398,6 +403,26 @@ def draw_buddhabrot_projected(dims, d_hist, iterations, projection, d_states, n_
     )
 
 
+def _julia_c(c):
+    """The fixed c of a Julia render, (c_re, c_im), as two C doubles."""
+    v = np.asarray(c, dtype=np.float64).reshape(-1)
+    if v.size != 2:
+        raise ValueError("a Julia parameter is two numbers: (c_re, c_im)")
+    return (C.c_double * 2)(float(v[0]), float(v[1]))
+
+
+def draw_buddhabrot_julia(dims, d_hist, iterations, projection, julia_c, d_states, n_threads, samples_per_thread,
+                          d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The Julia draw on caller-owned device memory (cb_draw_buddhabrot_julia): the sample of the normal stream is z_0,
+    c = julia_c is fixed, every recorded point is plotted at P (z_re, z_im, c_re, c_im)."""
+    _check(
+        lib.cb_draw_buddhabrot_julia(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                     _julia_c(julia_c), d_states, n_threads, samples_per_thread, d_counters,
+                                     kernel_variant, stream),
+        "cb_draw_buddhabrot_julia",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -448,6 +473,18 @@ class Renderer:
         if not lib.cb_renderer_projection(self._h, out):
             return None
         return np.array(list(out), dtype=np.float64).reshape(2, 4)
+
+    def set_julia(self, julia_c, projection=None):
+        """Make this a Julia renderer (cb_renderer_set_julia), before the first pass; projection None: the identity."""
+        p = None if projection is None else _projection(projection)
+        _check(lib.cb_renderer_set_julia(self._h, p, _julia_c(julia_c)), "cb_renderer_set_julia")
+
+    def julia(self):
+        """The c of a Julia renderer as (c_re, c_im); None for any other renderer."""
+        out = (C.c_double * 2)()
+        if not lib.cb_renderer_julia(self._h, out):
+            return None
+        return float(out[0]), float(out[1])
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""

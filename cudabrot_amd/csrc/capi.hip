@@ -302,6 +302,9 @@ struct cb_renderer {
   // projected render (cb_renderer_set_projection): the matrix P[2][4]
   bool projected;
   double projection[8];
+  // Julia render (cb_renderer_set_julia): a projected renderer whose draws take this fixed c and the sample as z_0
+  bool julia;
+  double julia_c[2];
 };
 
 namespace {
@@ -319,6 +322,12 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   }
   if (r->projected) {  // draw_project.hip: direct atomics, no deferred scatter, no carry
     if (passes == 0) return 0;
+    if (r->julia) {  // draw_julia.hip: no interior map either
+      r->interior_level = 0;
+      return cb_draw_buddhabrot_julia(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia_c, r->d_states,
+                                      r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant,
+                                      r->stream);
+    }
     const int rc = cb_draw_buddhabrot_projected(&r->dims, r->d_hist, &r->iterations, r->projection, r->d_states,
                                                 r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
                                                 kernel_variant, r->stream);
@@ -894,6 +903,66 @@ int cb_renderer_set_projection(cb_renderer *r, const double projection[8]) {
 int cb_renderer_projection(const cb_renderer *r, double out[8]) {
   if (!r || !out || !r->projected) return 0;
   memcpy(out, r->projection, sizeof(r->projection));
+  return 1;
+}
+
+// ---- Julia render (draw_julia.hip; include/cudabrot_amd.h, "Julia render") ------------------------------------------
+
+namespace {
+
+const double kIdentityProjection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+
+bool julia_c_ok(const double *c) {  // both in [-2, 2]; a NaN fails the comparisons
+  return c && c[0] >= -2.0 && c[0] <= 2.0 && c[1] >= -2.0 && c[1] <= 2.0;
+}
+
+}  // namespace
+
+int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2], void *d_states, uint32_t n_threads,
+                             uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection) || !julia_c_ok(julia_c)) return (int) hipErrorInvalidValue;
+  // the variant rules of the projected draw: a base of two, the Burning Ship or a degree, not both, no anti
+  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
+  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
+  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
+  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::JuliaArgs ja;
+  memset(&ja, 0, sizeof(ja));
+  ja.pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  ja.pa.d.burning_ship = ship ? 1 : 0;
+  memcpy(ja.pa.p, projection, sizeof(ja.pa.p));
+  ja.pa.degree = degree;
+  ja.c[0] = julia_c[0];
+  ja.c[1] = julia_c[1];
+  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
+  g_interior_level.store(0, std::memory_order_relaxed);
+  g_last_draw_kernel.store(lockstep ? 13 : 12, std::memory_order_relaxed);
+  return (int) cb::launch_draw_julia(ja, lockstep, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cb_renderer_set_julia(cb_renderer *r, const double projection[8], const double julia_c[2]) {
+  const double *p = projection ? projection : kIdentityProjection;
+  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->projected || !projection_ok(p) ||
+      !julia_c_ok(julia_c)) {
+    return (int) hipErrorInvalidValue;
+  }
+  memcpy(r->projection, p, sizeof(r->projection));
+  r->julia_c[0] = julia_c[0];
+  r->julia_c[1] = julia_c[1];
+  r->projected = true;  // what cb_renderer_set_focus and cb_renderer_set_projection refuse
+  r->julia = true;
+  return 0;
+}
+
+int cb_renderer_julia(const cb_renderer *r, double out[2]) {
+  if (!r || !out || !r->julia) return 0;
+  out[0] = r->julia_c[0];
+  out[1] = r->julia_c[1];
   return 1;
 }
 

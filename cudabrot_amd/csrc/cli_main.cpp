@@ -22,7 +22,9 @@
 //    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on), --project
 //    a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG (the plane of the 4-D set (z_re, z_im, c_re, c_im) the orbits are
 //    plotted on: include/cudabrot_amd.h, "Projected render"), --power D (the Multibrot step z^D + c, D = 3 .. 8, on
-//    the projected path: include/cudabrot_amd.h, "Multibrot step").
+//    the projected path: include/cudabrot_amd.h, "Multibrot step"), --julia RE,IM (the Buddhabrot of the Julia set
+//    of c = RE + IM i: c fixed, the samples are the starting points; -2 <= RE, IM <= 2; with --power or
+//    --burning-ship, on any plane: include/cudabrot_amd.h, "Julia render").
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -91,7 +93,12 @@ struct Settings {
   // unless a plane is given)
   int power = 0;
   const char *bad_power_flag = nullptr;             // the message of a bad --power
-  bool projected() const { return project_given || plane_given || rotate_given || power != 0; }
+  // --julia RE,IM (extension): the Buddhabrot of the Julia set of c = RE + IM i (cb_renderer_set_julia); makes the run a
+  // projected one as --power does
+  bool julia = false;
+  double julia_c[2] = {0.0, 0.0};
+  const char *bad_julia_flag = nullptr;             // the message of a bad --julia
+  bool projected() const { return project_given || plane_given || rotate_given || power != 0 || julia; }
 };
 
 // One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
@@ -114,6 +121,19 @@ bool parse_projection(const char *text, double out[8]) {
     char *end = nullptr;
     out[j] = strtod(at, &end);
     if (end == at || !isfinite(out[j]) || *end != (j == 7 ? 0 : (j == 3 ? ':' : ','))) return false;
+    at = end + 1;
+  }
+  return true;
+}
+
+// --julia RE,IM: two finite numbers in [-2, 2], strtod's syntax (hexfloats included).
+bool parse_julia(const char *text, double out[2]) {
+  const char *at = text;
+  for (int j = 0; j < 2; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    out[j] = strtod(at, &end);
+    if (end == at || !(out[j] >= -2.0 && out[j] <= 2.0) || *end != (j == 1 ? 0 : ',')) return false;
     at = end + 1;
   }
   return true;
@@ -345,6 +365,13 @@ const std::vector<Flag> &flag_table() {
          }
          s.power = (int) d;
        }},
+      {"--julia", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.julia = true;
+         if (!parse_julia(t, s.julia_c)) {
+           s.bad_julia_flag = "Invalid julia parameter (want RE,IM, two numbers from -2 to 2)";
+         }
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -486,6 +513,10 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_power_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_julia_flag) {
+      printf("%s: %s\n", s.bad_julia_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
   }
   // a Multibrot render is a projected render with a step of its own (include/cudabrot_amd.h, "Multibrot step"): its
@@ -499,6 +530,19 @@ Settings parse_arguments(int argc, char **argv) {
                                                               : nullptr;
     if (with) {
       printf("--power does not combine with %s.\n", with);
+      usage_and_exit(argv[0]);
+    }
+  }
+  // a Julia render is a projected render as well (include/cudabrot_amd.h, "Julia render"), with either step but the
+  // Multibrot step's own refusals before its own
+  if (s.julia) {
+    const char *with = s.anti                                 ? "--anti"
+                       : s.focus                              ? "--focus"
+                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
+                       : s.gpus > 1                           ? "--gpus above 1"
+                                                              : nullptr;
+    if (with) {
+      printf("--julia does not combine with %s.\n", with);
       usage_and_exit(argv[0]);
     }
   }
@@ -579,6 +623,7 @@ class Run {
       fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
               p[3], p[4], p[5], p[6], p[7]);
       if (cfg_.power != 0) fprintf(stderr, "{\"power\": %d}\n", cfg_.power);  // the step: it defines the run as well
+      if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       fflush(stderr);
     }
     setup();
@@ -666,7 +711,11 @@ class Run {
         peers_.push_back(one);
       }
     }
-    if (cfg_.projected()) CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
+    if (cfg_.julia) {
+      CB_CHECK(cb_renderer_set_julia(renderer_, cfg_.projection, cfg_.julia_c));
+    } else if (cfg_.projected()) {
+      CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
+    }
     if (need_host_counts()) {
       counts_ = (cb_pixel *) calloc(1, buffer_bytes());
       if (!counts_) die();

@@ -24,20 +24,11 @@
 //                               the step a run-time loop (power_step).
 //   draw_power_kernel<D>        its product kernel (10), one instance per degree, the step the unrolled power_step_n<D>.
 // No workspace, no carry, no LDS: every launch is complete, and lane t advances generator t by exactly its samples.
-#include "draw_rounds.h"
+#include "draw_plot.h"
 
 namespace cb {
 
 namespace {
-
-// The sample's part of a plotted coordinate: the two columns of P that multiply c.
-__device__ __forceinline__ double project_constant(double pc_re, double pc_im, double cr, double ci) {
-  return __builtin_fma(pc_re, cr, pc_im * ci);
-}
-// One plotted coordinate of the point (r, i): the two columns of P that multiply z, and the sample's constant.
-__device__ __forceinline__ double project_point(double pz_re, double pz_im, double r, double i, double k) {
-  return __builtin_fma(pz_re, r, __builtin_fma(pz_im, i, k));
-}
 
 // The interior map (DrawArgs::interior_map), on undoubled coordinates: column floor((c_re + 2) 2^level), row
 // floor(|c_im| 2^level), level = interior_shift + 1; c_re + 2 is exact for every sample of the stream.  true: every
@@ -53,27 +44,6 @@ __device__ __forceinline__ bool interior_marked(const DrawArgs &a, double cr, do
   const uint32_t index = row * a.interior_cols + col;  // < 2.5 * 1.25 * 4^level
   return ((a.interior_map[index >> 3] >> (index & 7u)) & 1u) != 0u;
 }
-
-// What the product kernels share: the plot of a replayed point.  (ku, kv) is the sample's part of (u, v).
-struct Plot {
-  const ProjectArgs &pa;
-  const Canvas cv;
-  double ku = 0.0, kv = 0.0;
-
-  __device__ __forceinline__ void constant(double cr, double ci) {
-    ku = project_constant(pa.p[2], pa.p[3], cr, ci);
-    kv = project_constant(pa.p[6], pa.p[7], cr, ci);
-  }
-  __device__ __forceinline__ void point(double r, double i, LaneStats &st) const {
-    const double u = project_point(pa.p[0], pa.p[1], r, i, ku);
-    const double v = project_point(pa.p[4], pa.p[5], r, i, kv);
-    int row, col;
-    if (pixel_of(u, v, cv, row, col)) {
-      add_to_pixel(pa.d.hist, cv, row, col, 1ull);
-      st.increments++;
-    }
-  }
-};
 
 }  // namespace
 
@@ -201,21 +171,6 @@ __global__ void __launch_bounds__(256) draw_power_simple_kernel(ProjectArgs pa) 
 // that the step is a function of z, which z^d + c is too.
 
 namespace {
-
-template <bool kShip>
-struct ReferenceOrbit {
-  static constexpr bool kMandelbrot = !kShip;
-  static __device__ __forceinline__ double step(double cr, double ci, double &r, double &i) {
-    return orbit_step<kShip>(cr, ci, r, i);
-  }
-};
-template <int D>
-struct PowerOrbit {  // the degree wave-uniform and the loop gone
-  static constexpr bool kMandelbrot = false;
-  static __device__ __forceinline__ double step(double cr, double ci, double &r, double &i) {
-    return power_step_n<D>(cr, ci, r, i);
-  }
-};
 
 template <class Step>
 struct PlotMode {

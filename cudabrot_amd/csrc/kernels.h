@@ -246,6 +246,16 @@ struct ProjectArgs {
 };
 hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_julia.hip: the Julia render (include/cudabrot_amd.h, "Julia render").  pa is a projected render's arguments --
+// canvas, iteration control, generators, counters, burning_ship, the matrix and the degree, with the same rule for the
+// degree -- of which the interior map is not read; c is the fixed parameter (c_re, c_im), both in [-2, 2]: anything else,
+// a NaN included, is hipErrorInvalidValue, nothing launched.  The sample of the stream is z_0.
+struct JuliaArgs {
+  ProjectArgs pa;
+  double c[2];
+};
+hipError_t launch_draw_julia(const JuliaArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

@@ -364,6 +364,49 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
                                  uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                  int kernel_variant, void *stream);
 
+/* ---- Julia render: the Buddhabrot of a Julia set on the projected path ------------ *
+ *
+ * Every other render samples c and starts the orbit at z_0 = c.  A JULIA render fixes c and samples the starting point:
+ * it is a projected render ("Projected render" above) with one change to where the sample goes.  The project's own
+ * definition (the reference has none).  Normative:
+ *
+ *   Parameter.  julia_c[2] = (c_re, c_im), both finite and in [-2, 2]; anything else is hipErrorInvalidValue.
+ *
+ *   Samples.  The normal stream: four XORWOW draws per sample, two coordinates (s_re, s_im) in [-2, 2)^2.  The sample is
+ *   z_0.  Nothing is rejected: no cardioid or bulb test and no interior map, so rejected = 0.
+ *
+ *   Iteration.  z_{n+1} = step(c, z_n) with the fixed c.  The step is the reference's (mandel_step), its Burning Ship
+ *   variant under CB_KERNEL_FLAG_BURNING_SHIP, or the Multibrot step of degree d under CB_KERNEL_POWER(d) ("Multibrot
+ *   step", not together with the Burning Ship), each the same sequence of IEEE fp64 operations as in the other renders,
+ *   bit for bit.
+ *
+ *   Escape index.  k is the index of the first z_{k+1} with |z|^2 > 4 among z_1 ... z_max; if there is none, k = max and
+ *   the sample is never_escaped.  z_0 is neither tested nor plotted, just as the reference neither tests nor plots
+ *   z_0 = c.
+ *
+ *   Accept filter and replay.  min <= k < max; the replay visits z_1 ... z_{k+1}, the escaping point included.
+ *
+ *   Plot.  The visited point is (z_re, z_im, c_re, c_im) WITH THE FIXED c: K_u and K_v are computed from julia_c, not
+ *   from the sample; u, v and the binning are exactly the projected render's.  A plane that uses only c-axes is
+ *   degenerate (every point lands on one pixel); it is allowed.
+ *
+ *   Counters mean what they mean for a Multibrot render; skipped_steps is the executed-work discount of the product
+ *   kernel, and the lock-step kernel leaves it 0.
+ *
+ *   Every visited point is finite: |z_0|^2 <= 8, so |z_1| <= 8^(d/2) + |c| <= 4096 + 2 sqrt 2, and every later visited
+ *   point follows a point with |z|^2 <= 4.
+ *
+ * Two kernels (draw_julia.hip): CB_KERNEL_DEFAULT, one instance per step, lanes refilled from their own subsequence, with
+ * the exact-periodicity early-out -- all that retires a Julia interior: attracting cycles land on an exact fp64 cycle
+ * quickly -- and CB_KERNEL_SIMPLE, the definition in lock-step with step and degree run-time arguments; optionally
+ * | CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d); any other variant, CB_KERNEL_FLAG_ANTI included, is
+ * hipErrorInvalidValue, with nothing launched or written.  Identical histograms, generator states and counters (but
+ * skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete when it ends.  The -s buffer records
+ * c no more than it records the plane or the degree. */
+int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2], void *d_states, uint32_t n_threads,
+                             uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -408,6 +451,16 @@ int cb_renderer_set_projection(cb_renderer *r, const double projection[8]);
 /* A projected renderer's matrix: returns 1 and fills out[8]; returns 0 and leaves `out` alone for a renderer without
  * one (or a NULL argument). */
 int cb_renderer_projection(const cb_renderer *r, double out[8]);
+/* Makes this renderer a JULIA one ("Julia render" above); before its first pass, once.  projection: the matrix, NULL for
+ * the identity.  Every later cb_renderer_render_passes launches Julia draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE,
+ * optionally with the Burning Ship's flag or CB_KERNEL_POWER(d): anything else is hipErrorInvalidValue).
+ * hipErrorInvalidValue for a channel renderer, a focused or projected renderer, a renderer that has rendered or is a Julia
+ * one already, a non-finite matrix entry, or a c that is not two numbers in [-2, 2].  A Julia renderer is a projected
+ * one: cb_renderer_projection returns its matrix, cb_renderer_set_focus and cb_renderer_set_projection are refused. */
+int cb_renderer_set_julia(cb_renderer *r, const double projection[8], const double julia_c[2]);
+/* A Julia renderer's c: returns 1 and fills out[2]; returns 0 and leaves `out` alone for any other renderer (or a NULL
+ * argument). */
+int cb_renderer_julia(const cb_renderer *r, double out[2]);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -564,7 +617,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel,
  * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
  * 10 the Multibrot product kernel (draw_power_kernel, the projected render's with the power step:
- * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel.
+ * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel, 12 the Julia product kernel
+ * (draw_julia_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
