@@ -42,6 +42,7 @@ CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
 # cb_counters.status bits (include/cudabrot_amd.h)
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
+CB_PALETTE_MAX_ENTRIES, CB_PALETTE_MAX_STOPS = 1 << 24, 16  # palette render: the table's entries, the stops of one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -102,6 +103,12 @@ class ColorParams(C.Structure):
             compose = modes[compose]
         black, white = stretch
         return cls(int(compose), float(black), float(white), float(hue_shift))
+
+
+class PaletteStop(C.Structure):
+    """cb_palette_stop: one colour stop (k, r, g, b) of a palette."""
+
+    _fields_ = [("k", C.c_int), ("r", C.c_int), ("g", C.c_int), ("b", C.c_int)]
 
 
 class Counters(C.Structure):
@@ -253,6 +260,12 @@ def _load():
                                            vp, i32, vp]),
         "cb_renderer_set_julia": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "cb_renderer_julia": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_palette_from_stops": (i32, [C.POINTER(PaletteStop), i32, vp, u32]),
+        "cb_draw_buddhabrot_palette": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp,
+                                             u32, u32, vp, i32, vp]),
+        "cb_renderer_set_palette": (i32, [vp, vp, u32]),
+        "cb_renderer_palette": (i32, [vp, C.POINTER(u32)]),
+        "cb_renderer_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -274,7 +287,8 @@ EXPORTED_SYMBOLS = (
     "cb_renderer_prepare cb_compose_color cb_compose_color_device cb_renderer_color_image cb_save_ppm_be "
     "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells "
     "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout "
-    "cb_draw_buddhabrot_julia cb_renderer_set_julia cb_renderer_julia"
+    "cb_draw_buddhabrot_julia cb_renderer_set_julia cb_renderer_julia "
+    "cb_palette_from_stops cb_draw_buddhabrot_palette cb_renderer_set_palette cb_renderer_palette cb_renderer_palette_image"
 ).split()
 
 
@@ -423,6 +437,30 @@ def draw_buddhabrot_julia(dims, d_hist, iterations, projection, julia_c, d_state
     )
 
 
+def palette_from_stops(stops, n_entries):
+    """The table of a list of colour stops (cb_palette_from_stops): stops = [(k, r, g, b), ...], k ascending -> u32 array
+    of n_entries entries, entry k = r | g << 8 | b << 16 of an orbit with escape index k."""
+    stops = [tuple(int(v) for v in s) for s in stops]
+    if any(len(s) != 4 for s in stops):
+        raise ValueError("a colour stop is four numbers: (k, r, g, b)")
+    arr = (PaletteStop * max(len(stops), 1))(*[PaletteStop(*s) for s in stops])
+    lut = np.empty(max(int(n_entries), 0), dtype=np.uint32)
+    _check(lib.cb_palette_from_stops(arr, len(stops), lut.ctypes.data, int(n_entries) & 0xFFFFFFFF), "cb_palette_from_stops")
+    return lut
+
+
+def draw_buddhabrot_palette(dims, d_hist, iterations, projection, julia_c, d_lut, n_entries, d_states, n_threads,
+                            samples_per_thread, d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The palette draw on caller-owned device memory (cb_draw_buddhabrot_palette): d_hist is three planes, d_lut the table
+    of n_entries == max_iter entries on the device; julia_c None samples c (a projected render), else c is fixed."""
+    _check(
+        lib.cb_draw_buddhabrot_palette(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                       None if julia_c is None else _julia_c(julia_c), d_lut, n_entries, d_states,
+                                       n_threads, samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_palette",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -434,6 +472,7 @@ class Renderer:
         self.iterations = iterations
         self.n_threads = n_threads
         self._h = C.c_void_p()
+        self.palette_entries = 0
         if isinstance(iterations, IterationControl):
             self.n_channels = 0
             _check(
@@ -486,6 +525,33 @@ class Renderer:
             return None
         return float(out[0]), float(out[1])
 
+    def set_palette(self, lut):
+        """Make this a palette renderer (cb_renderer_set_palette), before the first pass and after set_projection or
+        set_julia (alone: the identity projection): lut is the table, max_iter u32 entries.  The histogram becomes three
+        planes."""
+        a = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+        _check(lib.cb_renderer_set_palette(self._h, a.ctypes.data, a.size), "cb_renderer_set_palette")
+        self.palette_entries = int(a.size)
+
+    def palette(self):
+        """The number of entries of a palette renderer's table; None for any other renderer."""
+        n = C.c_uint32()
+        if not lib.cb_renderer_palette(self._h, C.byref(n)):
+            return None
+        return int(n.value)
+
+    def palette_image(self, gamma=1.0, mode=0):
+        """The image of a palette renderer (cb_renderer_palette_image) -> (big-endian u16 image [h,w,3] = the PPM body,
+        the largest count of the three planes, scale)."""
+        rgb = np.empty((self.dims.h, self.dims.w, 3), dtype=">u2")
+        mx, scale = C.c_uint64(), C.c_double()
+        _check(lib.cb_renderer_palette_image(self._h, float(gamma), int(mode), rgb.ctypes.data, C.byref(mx),
+                                             C.byref(scale)), "cb_renderer_palette_image")
+        return rgb, int(mx.value), float(scale.value)
+
+    def _planes(self):
+        return 3 if self.palette_entries else (self.n_channels or 1)
+
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""
         _check(lib.cb_renderer_prepare(self._h, kernel_variant), "cb_renderer_prepare")
@@ -498,10 +564,10 @@ class Renderer:
         _check(lib.cb_renderer_finish(self._h), "cb_renderer_finish")
 
     def read_histogram(self):
-        planes = self.n_channels or 1
+        planes = self._planes()
         out = np.empty(planes * self.dims.w * self.dims.h, dtype=np.uint64)
         _check(lib.cb_renderer_read_histogram(self._h, out.ctypes.data), "cb_renderer_read_histogram")
-        if self.n_channels:
+        if self.n_channels or self.palette_entries:
             return out.reshape(planes, self.dims.h, self.dims.w)
         return out.reshape(self.dims.h, self.dims.w)
 
@@ -544,7 +610,7 @@ class Renderer:
 
     def write_histogram(self, hist):
         a = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
-        if a.size != (self.n_channels or 1) * self.dims.w * self.dims.h:
+        if a.size != self._planes() * self.dims.w * self.dims.h:
             raise ValueError("histogram size does not match the canvas")
         _check(lib.cb_renderer_write_histogram(self._h, a.ctypes.data), "cb_renderer_write_histogram")
 

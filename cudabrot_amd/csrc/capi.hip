@@ -305,9 +305,17 @@ struct cb_renderer {
   // Julia render (cb_renderer_set_julia): a projected renderer whose draws take this fixed c and the sample as z_0
   bool julia;
   double julia_c[2];
+  // palette render (cb_renderer_set_palette): a projected or Julia renderer whose draws weigh orbits by this table; d_hist
+  // is then three planes
+  bool palette;
+  uint32_t *d_palette;
+  uint32_t palette_entries;
 };
 
 namespace {
+
+// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette renderer, else one.
+size_t renderer_planes(const cb_renderer *r) { return r->palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u); }
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
@@ -322,6 +330,14 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   }
   if (r->projected) {  // draw_project.hip: direct atomics, no deferred scatter, no carry
     if (passes == 0) return 0;
+    if (r->palette) {  // draw_palette.hip: either of the two below with the table
+      const int rc = cb_draw_buddhabrot_palette(&r->dims, r->d_hist, &r->iterations, r->projection,
+                                                r->julia ? r->julia_c : nullptr, r->d_palette, r->palette_entries,
+                                                r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
+                                                kernel_variant, r->stream);
+      r->interior_level = rc ? 0 : cb_debug_interior_map_level();
+      return rc;
+    }
     if (r->julia) {  // draw_julia.hip: no interior map either
       r->interior_level = 0;
       return cb_draw_buddhabrot_julia(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia_c, r->d_states,
@@ -966,6 +982,108 @@ int cb_renderer_julia(const cb_renderer *r, double out[2]) {
   return 1;
 }
 
+// ---- palette render (draw_palette.hip; include/cudabrot_amd.h, "Palette render") ------------------------------------
+
+namespace {
+
+bool palette_entries_ok(uint32_t n_entries, const cb_iteration_control *iterations) {
+  return n_entries >= 1u && n_entries <= (uint32_t) CB_PALETTE_MAX_ENTRIES && iterations->max_escape_iterations >= 1 &&
+         (uint32_t) iterations->max_escape_iterations == n_entries;
+}
+
+// out[3 i + j] = planes[j n + i]: the three planes of big-endian values as the R, G, B of a PPM body.
+__global__ void __launch_bounds__(256) interleave_planes_kernel(const uint16_t *planes, size_t n, uint16_t *out) {
+  const size_t stride = (size_t) gridDim.x * blockDim.x;
+  for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    out[3 * i + 0] = planes[i];
+    out[3 * i + 1] = planes[n + i];
+    out[3 * i + 2] = planes[2 * n + i];
+  }
+}
+
+}  // namespace
+
+int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2], const uint32_t *d_lut,
+                               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
+                               cb_counters *d_counters, int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  if (!d_lut || !palette_entries_ok(n_entries, iterations)) return (int) hipErrorInvalidValue;
+  // the variant rules of the projected and Julia draws: a base of two, the Burning Ship or a degree, not both, no anti
+  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
+  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
+  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
+  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::PaletteArgs pl;
+  memset(&pl, 0, sizeof(pl));
+  cb::ProjectArgs &pa = pl.ja.pa;
+  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  pa.d.burning_ship = ship ? 1 : 0;
+  memcpy(pa.p, projection, sizeof(pa.p));
+  pa.degree = degree;
+  if (julia_c) {
+    pl.julia = 1;
+    pl.ja.c[0] = julia_c[0];
+    pl.ja.c[1] = julia_c[1];
+  }
+  pl.lut = d_lut;
+  pl.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
+  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
+  // the interior map: a sampled c with the Mandelbrot step, under cb_draw_buddhabrot_projected's rule
+  g_interior_level.store(0, std::memory_order_relaxed);
+  if (!julia_c && !power && pa.d.long_steps > 0) {
+    const int rc = attach_interior_map(pa.d, kernel_variant);
+    if (rc) return rc;
+  }
+  g_last_draw_kernel.store(lockstep ? 15 : 14, std::memory_order_relaxed);
+  return (int) cb::launch_draw_palette(pl, lockstep, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
+  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || !lut_host ||
+      !palette_entries_ok(n_entries, &r->iterations)) {
+    return (int) hipErrorInvalidValue;
+  }
+  for (uint32_t k = 0; k < n_entries; ++k) {
+    if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;
+  }
+  CB_TRY(hipSetDevice(r->device));
+  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
+  const size_t hist_bytes = 3 * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
+  cb_pixel *d_hist = nullptr;
+  uint32_t *d_lut = nullptr;
+  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_lut), (size_t) n_entries * sizeof(uint32_t));
+  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
+  if (!rc) rc = (int) hipMemcpyAsync(d_lut, lut_host, (size_t) n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);  // lut_host is the caller's
+  if (rc) {
+    (void) hipFree(d_hist);
+    (void) hipFree(d_lut);
+    return rc;
+  }
+  (void) hipFree(r->d_hist);
+  r->d_hist = d_hist;
+  r->d_palette = d_lut;
+  r->palette_entries = n_entries;
+  r->palette = true;
+  if (!r->projected) {  // alone: the identity projection
+    memcpy(r->projection, kIdentityProjection, sizeof(r->projection));
+    r->projected = true;  // what cb_renderer_set_focus, cb_renderer_set_projection and cb_renderer_set_julia refuse
+  }
+  return 0;
+}
+
+int cb_renderer_palette(const cb_renderer *r, uint32_t *n_entries) {
+  if (!r || !r->palette) return 0;
+  if (n_entries) *n_entries = r->palette_entries;
+  return 1;
+}
+
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
                        const cb_iteration_control *iterations, uint64_t seed,
                        uint64_t first_subsequence, uint32_t n_threads) {
@@ -1123,8 +1241,7 @@ int cb_renderer_read_histogram(cb_renderer *r, cb_pixel *host_out) {
     int rc = finish(r);
     if (rc) return rc;
   }
-  const size_t bytes = (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel) *
-                       (size_t) (r->n_channels ? r->n_channels : 1);
+  const size_t bytes = (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel) * renderer_planes(r);
   CB_TRY(hipMemcpyAsync(host_out, r->d_hist, bytes, hipMemcpyDeviceToHost, r->stream));
   return (int) hipStreamSynchronize(r->stream);
 }
@@ -1136,7 +1253,7 @@ int cb_renderer_grayscale_image(cb_renderer *r, double gamma, int mode, uint16_t
 
 int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mode, uint16_t *host_gray_be,
                                 uint64_t *max_out, double *scale_out) {
-  if (!r || !host_gray_be || plane < 0 || plane >= (r->n_channels ? r->n_channels : 1)) {
+  if (!r || !host_gray_be || plane < 0 || (size_t) plane >= renderer_planes(r)) {
     return (int) hipErrorInvalidValue;
   }
   CB_TRY(hipSetDevice(r->device));
@@ -1155,13 +1272,41 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
   return rc;
 }
 
+int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                              double *scale_out) {
+  if (!r || !r->palette || !host_rgb_be || r->dims.h > 0x7fffffff / 3) return (int) hipErrorInvalidValue;
+  CB_TRY(hipSetDevice(r->device));
+  {
+    int rc = finish(r);
+    if (rc) return rc;
+  }
+  const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
+  uint16_t *d_planes = nullptr, *d_rgb = nullptr;
+  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_planes), 3 * n * sizeof(uint16_t));
+  if (rc == 0) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_rgb), 3 * n * sizeof(uint16_t));
+  // the three planes as one w x 3h image: one maximum for all of them
+  if (rc == 0) rc = cb_tone_map_device(r->d_hist, r->dims.w, 3 * r->dims.h, gamma, tone_mode, d_planes, max_out, scale_out,
+                                       r->stream);
+  if (rc == 0) {
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(interleave_planes_kernel, dim3((uint32_t) (blocks < 4096 ? blocks : 4096)), dim3(256), 0, r->stream,
+                       d_planes, n, d_rgb);
+    rc = (int) hipGetLastError();
+  }
+  if (rc == 0) rc = (int) hipMemcpyAsync(host_rgb_be, d_rgb, 3 * n * sizeof(uint16_t), hipMemcpyDeviceToHost, r->stream);
+  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
+  (void) hipFree(d_planes);
+  (void) hipFree(d_rgb);
+  return rc;
+}
+
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
                             const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
   const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
   const cb_pixel *src[3];
   for (int j = 0; j < 3; ++j) {
-    if (planes[j] < 0 || planes[j] >= (r->n_channels ? r->n_channels : 1)) return (int) hipErrorInvalidValue;
+    if (planes[j] < 0 || (size_t) planes[j] >= renderer_planes(r)) return (int) hipErrorInvalidValue;
     src[j] = r->d_hist + (size_t) planes[j] * n;
   }
   CB_TRY(hipSetDevice(r->device));
@@ -1186,8 +1331,7 @@ int cb_renderer_write_histogram(cb_renderer *r, const cb_pixel *host_in) {
     int rc = finish(r);
     if (rc) return rc;
   }
-  const size_t bytes = (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel) *
-                       (size_t) (r->n_channels ? r->n_channels : 1);
+  const size_t bytes = (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel) * renderer_planes(r);
   CB_TRY(hipMemcpyAsync(r->d_hist, host_in, bytes, hipMemcpyHostToDevice, r->stream));
   return (int) hipStreamSynchronize(r->stream);
 }
@@ -1241,6 +1385,7 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_counters);
   (void) hipFree(r->d_carry);
   (void) hipFree(r->d_focus_cells);
+  (void) hipFree(r->d_palette);
   (void) hipFree(r->d_workspace[0]);
   (void) hipFree(r->d_workspace[1]);
   for (int k = 0; k < 2; ++k) {
@@ -1261,7 +1406,7 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
   for (int k = 0; k < n; ++k) {
     cb_renderer *r = renderers[k];
     if (!r || r->dims.w != renderers[0]->dims.w || r->dims.h != renderers[0]->dims.h ||
-        r->n_channels != renderers[0]->n_channels) {
+        r->n_channels != renderers[0]->n_channels || r->palette != renderers[0]->palette) {
       return (int) hipErrorInvalidValue;
     }
     CB_TRY(hipSetDevice(r->device));
@@ -1269,7 +1414,7 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
     if (rc) return rc;
   }
   cb_renderer *root = renderers[0];
-  const size_t count = (size_t) root->dims.w * (size_t) root->dims.h * (size_t) (root->n_channels ? root->n_channels : 1);
+  const size_t count = (size_t) root->dims.w * (size_t) root->dims.h * renderer_planes(root);
   if (n == 1) {
     // CUDABROT_AMD_FORCE_RCCL=1 (test knob): a reduce over one rank, to exercise the RCCL calls where
     // only one device exists

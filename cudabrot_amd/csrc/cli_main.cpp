@@ -24,7 +24,10 @@
 //    plotted on: include/cudabrot_amd.h, "Projected render"), --power D (the Multibrot step z^D + c, D = 3 .. 8, on
 //    the projected path: include/cudabrot_amd.h, "Multibrot step"), --julia RE,IM (the Buddhabrot of the Julia set
 //    of c = RE + IM i: c fixed, the samples are the starting points; -2 <= RE, IM <= 2; with --power or
-//    --burning-ship, on any plane: include/cudabrot_amd.h, "Julia render").
+//    --burning-ship, on any plane: include/cudabrot_amd.h, "Julia render"), --palette K:RRGGBB[,K:RRGGBB...] (orbits
+//    coloured by their escape index: colour stops interpolated into a table of -m entries, three planes of integer
+//    weights, -o receives a 16-bit PPM; on the projected path with any plane, --power, --julia or --burning-ship:
+//    include/cudabrot_amd.h, "Palette render").
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -98,7 +101,13 @@ struct Settings {
   bool julia = false;
   double julia_c[2] = {0.0, 0.0};
   const char *bad_julia_flag = nullptr;             // the message of a bad --julia
-  bool projected() const { return project_given || plane_given || rotate_given || power != 0 || julia; }
+  // --palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a palette render (cb_palette_from_stops,
+  // cb_renderer_set_palette); makes the run a projected one as --power does
+  int n_palette_stops = 0;
+  cb_palette_stop palette_stops[CB_PALETTE_MAX_STOPS] = {};
+  const char *bad_palette_flag = nullptr;           // the message of a bad --palette
+  bool palette() const { return n_palette_stops > 0; }
+  bool projected() const { return project_given || plane_given || rotate_given || power != 0 || julia || palette(); }
 };
 
 // One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
@@ -137,6 +146,32 @@ bool parse_julia(const char *text, double out[2]) {
     at = end + 1;
   }
   return true;
+}
+
+// --palette K:RRGGBB[,K:RRGGBB...]: 1 to CB_PALETTE_MAX_STOPS stops, K decimal digits and strictly ascending, the colour
+// six hex digits.  Returns the number of stops, 0 for anything else.
+int parse_palette(const char *text, cb_palette_stop out[CB_PALETTE_MAX_STOPS]) {
+  const char *at = text;
+  int n = 0;
+  for (;;) {
+    if (n == CB_PALETTE_MAX_STOPS || *at < '0' || *at > '9') return 0;
+    long k = 0;
+    for (; *at >= '0' && *at <= '9'; ++at) {
+      k = k * 10 + (*at - '0');
+      if (k > 0x7fffffffL) return 0;
+    }
+    if (*at++ != ':' || (n > 0 && k <= out[n - 1].k)) return 0;
+    int v[3] = {0, 0, 0};
+    for (int j = 0; j < 6; ++j, ++at) {
+      const char ch = *at;
+      const int digit = (ch >= '0' && ch <= '9') ? ch - '0' : (ch >= 'a' && ch <= 'f') ? ch - 'a' + 10 : (ch >= 'A' && ch <= 'F') ? ch - 'A' + 10 : -1;
+      if (digit < 0) return 0;
+      v[j / 2] = v[j / 2] * 16 + digit;
+    }
+    out[n++] = {(int) k, v[0], v[1], v[2]};
+    if (*at == 0) return n;
+    if (*at++ != ',') return 0;
+  }
 }
 
 // --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane.  An integer multiple of 90
@@ -372,6 +407,13 @@ const std::vector<Flag> &flag_table() {
            s.bad_julia_flag = "Invalid julia parameter (want RE,IM, two numbers from -2 to 2)";
          }
        }},
+      {"--palette", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.n_palette_stops = parse_palette(t, s.palette_stops);
+         if (s.n_palette_stops == 0) {
+           s.bad_palette_flag = "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops)";
+         }
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -517,7 +559,29 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_julia_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_palette_flag) {
+      printf("%s: %s\n", s.bad_palette_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  // a palette render is a projected render with three planes (include/cudabrot_amd.h, "Palette render"): its refusals come
+  // before those of the step, of c and of the projection, which it would otherwise trip
+  if (s.palette()) {
+    const char *with = s.anti                                 ? "--anti"
+                       : s.focus                              ? "--focus"
+                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
+                       : s.gpus > 1                           ? "--gpus above 1"
+                       : s.raw_state                          ? "--state-format raw"
+                                                              : nullptr;
+    if (with) {
+      printf("--palette does not combine with %s.\n", with);
+      usage_and_exit(argv[0]);
+    }
+    if (s.iterations.max_escape_iterations < 1 || s.iterations.max_escape_iterations > CB_PALETTE_MAX_ENTRIES) {
+      printf("--palette needs -m from 1 to %d.\n", CB_PALETTE_MAX_ENTRIES);  // the table has -m entries
+      usage_and_exit(argv[0]);
+    }
   }
   // a Multibrot render is a projected render with a step of its own (include/cudabrot_amd.h, "Multibrot step"): its
   // refusals come before the projection's, which it would otherwise trip
@@ -624,6 +688,14 @@ class Run {
               p[3], p[4], p[5], p[6], p[7]);
       if (cfg_.power != 0) fprintf(stderr, "{\"power\": %d}\n", cfg_.power);  // the step: it defines the run as well
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
+      if (cfg_.palette()) {  // and the colours
+        fprintf(stderr, "{\"palette\": [");
+        for (int j = 0; j < cfg_.n_palette_stops; ++j) {
+          const cb_palette_stop &stop = cfg_.palette_stops[j];
+          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
+        }
+        fprintf(stderr, "]}\n");
+      }
       fflush(stderr);
     }
     setup();
@@ -635,6 +707,10 @@ class Run {
     if (cfg_.n_channels > 0) {
       save_channels();
       if (cfg_.color_file) save_color();
+    } else if (cfg_.palette()) {
+      printf("Saving image.\n");
+      report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
+      printf("Done! Output image saved: %s\n", cfg_.output_image);
     } else {
       printf("Saving image.\n");
       save_image(cfg_.output_image);
@@ -654,11 +730,12 @@ class Run {
   uint16_t *gray_ = nullptr;
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
+  std::vector<uint16_t> palette_rgb_be_;  // --palette: the PPM body
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
   uint64_t pixel_count() const { return (uint64_t) cfg_.canvas.w * (uint64_t) cfg_.canvas.h; }
-  uint64_t planes() const { return cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u; }
+  uint64_t planes() const { return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u); }
   uint64_t buffer_bytes() const { return planes() * pixel_count() * sizeof(cb_pixel); }
 
   void release() {  // cudabrot.cu:112-119
@@ -715,6 +792,11 @@ class Run {
       CB_CHECK(cb_renderer_set_julia(renderer_, cfg_.projection, cfg_.julia_c));
     } else if (cfg_.projected()) {
       CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
+    }
+    if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
+      std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
+      CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
+      CB_CHECK(cb_renderer_set_palette(renderer_, lut.data(), (uint32_t) lut.size()));
     }
     if (need_host_counts()) {
       counts_ = (cb_pixel *) calloc(1, buffer_bytes());
@@ -843,7 +925,11 @@ class Run {
     }
     printf("%ld Buddhabrot passes took %f seconds.\n", done, wall_seconds() - t0);
     if (cfg_.print_stats) print_stats();
-    if (cfg_.n_channels == 0) tone_map(0);
+    if (cfg_.palette()) {
+      palette_image();
+    } else if (cfg_.n_channels == 0) {
+      tone_map(0);
+    }
   }
 
   // --focus: the probe and the cell list, before the clock of the pass loop starts.  The probe runs on generators of its
@@ -988,6 +1074,28 @@ class Run {
       CB_CHECK(cb_renderer_grayscale_plane(renderer_, plane, cfg_.gamma_correction, cfg_.tone_mode, gray_,
                                            &max, &scale));
       gray_is_big_endian_ = true;
+    }
+    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+  }
+
+  // --palette: the three planes tone-mapped against their common maximum, as one w x 3h image, and interleaved into the
+  // PPM body -- on the device, or with --tonemap host by the reference's host loop; the bytes are the same.
+  void palette_image() {
+    uint64_t max = 0;
+    double scale = 0.0;
+    palette_rgb_be_.resize(3 * pixel_count());
+    if (cfg_.host_tonemap) {
+      std::vector<uint16_t> planar(3 * pixel_count());
+      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, 3 * cfg_.canvas.h, cfg_.gamma_correction, planar.data(), &max, &scale);
+      for (uint64_t i = 0; i < pixel_count(); ++i) {
+        for (uint64_t j = 0; j < 3; ++j) {
+          const uint16_t v = planar[j * pixel_count() + i];
+          palette_rgb_be_[3 * i + j] = (uint16_t) ((v << 8) | (v >> 8));
+        }
+      }
+    } else {
+      CB_CHECK(cb_renderer_palette_image(renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max,
+                                         &scale));
     }
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }

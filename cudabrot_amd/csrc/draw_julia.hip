@@ -103,33 +103,6 @@ __global__ void __launch_bounds__(256) draw_julia_simple_kernel(JuliaArgs ja) {
 // the lane's pair, and the plot's constant is made from it once, before the first round.  The early-out's proof uses only
 // that the step is a function of z, which it is for a fixed c.
 
-namespace {
-
-template <class Step>
-struct JuliaMode {
-  Plot plot;
-  const double c_re, c_im;
-
-  __device__ __forceinline__ double step(RoundLane &l) { return Step::step(c_re, c_im, l.r, l.i); }
-
-  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    uniform_sample(rng, l.cr, l.ci);
-    return kSampleIterate;
-  }
-
-  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
-    return count_escaped(l, plot.pa.d.min_iter, st);
-  }
-  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) { return count_never_escapes(l, st); }
-
-  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
-    plot.point(l.r, l.i, st);
-    return false;
-  }
-};
-
-}  // namespace
-
 template <class Step>
 __global__ void __launch_bounds__(256) draw_julia_kernel(JuliaArgs ja) {
   JuliaMode<Step> mode{{ja.pa, make_canvas(ja.pa.d)}, ja.c[0], ja.c[1]};

@@ -1,6 +1,7 @@
-// draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_project.hip, draw_julia.hip;
-// include/cudabrot_amd.h, "Projected render"): the four fused operations of a plotted point, the plot of a replayed point
-// for the modes of draw_rounds.h's scheduler, and the steps those modes are instantiated with.
+// draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_project.hip, draw_julia.hip,
+// draw_palette.hip; include/cudabrot_amd.h, "Projected render"): the four fused operations of a plotted point, the plot of
+// a replayed point for the modes of draw_rounds.h's scheduler, the steps those modes are instantiated with, and the two
+// modes themselves -- a sampled c and a fixed one -- which the palette render's mode builds on.
 #pragma once
 
 #include "draw_rounds.h"
@@ -53,5 +54,82 @@ struct PowerOrbit {  // the degree wave-uniform and the loop gone
     return power_step_n<D>(cr, ci, r, i);
   }
 };
+
+// ---- the plot modes of draw_rounds.h's scheduler (draw_project.hip, draw_julia.hip, draw_palette.hip) -----------------
+
+namespace {
+
+// The interior map (DrawArgs::interior_map), on undoubled coordinates: column floor((c_re + 2) 2^level), row
+// floor(|c_im| 2^level), level = interior_shift + 1; c_re + 2 is exact for every sample of the stream.  true: every
+// sample of the cell that holds c provably never escapes.
+__device__ __forceinline__ bool interior_marked(const DrawArgs &a, double cr, double ci) {
+  const int level = (int) a.interior_shift + 1;
+  const double x = __builtin_ldexp(cr + 2.0, level);
+  const double y = __builtin_ldexp(__builtin_fabs(ci), level);
+  if (!(x >= 0.0)) return false;
+  const uint32_t col = (uint32_t) x;
+  const uint32_t row = (uint32_t) y;
+  if (col >= a.interior_cols || row >= a.interior_rows) return false;
+  const uint32_t index = row * a.interior_cols + col;  // < 2.5 * 1.25 * 4^level
+  return ((a.interior_map[index >> 3] >> (index & 7u)) & 1u) != 0u;
+}
+
+
+// The mode of a render that samples c (draw_project.hip has the commentary): z_0 = c, the plot's constant from the sample.
+template <class Step>
+struct PlotMode {
+  Plot plot;
+
+  __device__ __forceinline__ double step(RoundLane &l) { return Step::step(l.cr, l.ci, l.r, l.i); }
+
+  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
+    uniform_sample(rng, l.cr, l.ci);
+    if (!Step::kMandelbrot) return kSampleIterate;
+    if (in_main_cardioid(l.cr, l.ci) || in_order2_bulb(l.cr, l.ci)) return kSampleRejected;
+    const DrawArgs &a = plot.pa.d;
+    if (a.interior_map != nullptr && interior_marked(a, l.cr, l.ci)) return kSampleInterior;  // not iterated
+    return kSampleIterate;
+  }
+
+  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
+    if (!count_escaped(l, plot.pa.d.min_iter, st)) return false;
+    plot.constant(l.cr, l.ci);
+    return true;
+  }
+  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) { return count_never_escapes(l, st); }
+
+  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
+    plot.point(l.r, l.i, st);
+    return false;
+  }
+};
+
+
+// The mode of a Julia render (draw_julia.hip has the commentary): z_0 = the sample, c and the plot's constant fixed.
+template <class Step>
+struct JuliaMode {
+  Plot plot;
+  const double c_re, c_im;
+
+  __device__ __forceinline__ double step(RoundLane &l) { return Step::step(c_re, c_im, l.r, l.i); }
+
+  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
+    uniform_sample(rng, l.cr, l.ci);
+    return kSampleIterate;
+  }
+
+  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
+    return count_escaped(l, plot.pa.d.min_iter, st);
+  }
+  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) { return count_never_escapes(l, st); }
+
+  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
+    plot.point(l.r, l.i, st);
+    return false;
+  }
+};
+
+
+}  // namespace
 
 }  // namespace cb

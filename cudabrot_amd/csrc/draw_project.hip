@@ -28,25 +28,6 @@
 
 namespace cb {
 
-namespace {
-
-// The interior map (DrawArgs::interior_map), on undoubled coordinates: column floor((c_re + 2) 2^level), row
-// floor(|c_im| 2^level), level = interior_shift + 1; c_re + 2 is exact for every sample of the stream.  true: every
-// sample of the cell that holds c provably never escapes.
-__device__ __forceinline__ bool interior_marked(const DrawArgs &a, double cr, double ci) {
-  const int level = (int) a.interior_shift + 1;
-  const double x = __builtin_ldexp(cr + 2.0, level);
-  const double y = __builtin_ldexp(__builtin_fabs(ci), level);
-  if (!(x >= 0.0)) return false;
-  const uint32_t col = (uint32_t) x;
-  const uint32_t row = (uint32_t) y;
-  if (col >= a.interior_cols || row >= a.interior_rows) return false;
-  const uint32_t index = row * a.interior_cols + col;  // < 2.5 * 1.25 * 4^level
-  return ((a.interior_map[index >> 3] >> (index & 7u)) & 1u) != 0u;
-}
-
-}  // namespace
-
 // ------------------------------------------------------------------------------------------------
 // draw_project_simple_kernel, draw_power_simple_kernel: the definition, verbatim
 // ------------------------------------------------------------------------------------------------
@@ -169,38 +150,6 @@ __global__ void __launch_bounds__(256) draw_power_simple_kernel(ProjectArgs pa) 
 // accept filter to REPLAY of z_1 .. z_n, each point projected and binned (device-scope atomics); an exact cycle never
 // escapes and is counted as the reference counts it, the steps not made in skipped_steps.  The early-out's proof uses only
 // that the step is a function of z, which z^d + c is too.
-
-namespace {
-
-template <class Step>
-struct PlotMode {
-  Plot plot;
-
-  __device__ __forceinline__ double step(RoundLane &l) { return Step::step(l.cr, l.ci, l.r, l.i); }
-
-  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    uniform_sample(rng, l.cr, l.ci);
-    if (!Step::kMandelbrot) return kSampleIterate;
-    if (in_main_cardioid(l.cr, l.ci) || in_order2_bulb(l.cr, l.ci)) return kSampleRejected;
-    const DrawArgs &a = plot.pa.d;
-    if (a.interior_map != nullptr && interior_marked(a, l.cr, l.ci)) return kSampleInterior;  // not iterated
-    return kSampleIterate;
-  }
-
-  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
-    if (!count_escaped(l, plot.pa.d.min_iter, st)) return false;
-    plot.constant(l.cr, l.ci);
-    return true;
-  }
-  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool) { return count_never_escapes(l, st); }
-
-  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
-    plot.point(l.r, l.i, st);
-    return false;
-  }
-};
-
-}  // namespace
 
 template <bool kShip>
 __global__ void __launch_bounds__(256) draw_project_kernel(ProjectArgs pa) {

@@ -100,4 +100,38 @@ int cb_focus_cells(int level, const uint32_t *mask_host, int dilate, uint32_t *c
   return 0;
 }
 
+// ---- palette render: the table of a list of colour stops (include/cudabrot_amd.h, "Palette render") ----------------
+
+int cb_palette_from_stops(const cb_palette_stop *stops, int n_stops, uint32_t *lut_out, uint32_t n_entries) {
+  const int kInvalidValue = 1;  // hipErrorInvalidValue
+  if (!stops || !lut_out || n_stops < 1 || n_stops > CB_PALETTE_MAX_STOPS || n_entries < 1u ||
+      n_entries > (uint32_t) CB_PALETTE_MAX_ENTRIES) {
+    return kInvalidValue;
+  }
+  for (int j = 0; j < n_stops; ++j) {
+    const cb_palette_stop &s = stops[j];
+    if (s.k < 0 || (j > 0 && s.k <= stops[j - 1].k) || s.r < 0 || s.r > 255 || s.g < 0 || s.g > 255 || s.b < 0 || s.b > 255) {
+      return kInvalidValue;
+    }
+  }
+  int above = 0;  // the first stop with k_stop > k
+  for (uint32_t k = 0; k < n_entries; ++k) {
+    while (above < n_stops && (uint64_t) stops[above].k <= k) above++;
+    const cb_palette_stop &a = stops[above > 0 ? above - 1 : 0];
+    const cb_palette_stop &b = stops[above < n_stops ? above : n_stops - 1];
+    uint32_t rgb[3];
+    const int va[3] = {a.r, a.g, a.b}, vb[3] = {b.r, b.g, b.b};
+    for (int j = 0; j < 3; ++j) {
+      if (above == 0 || above == n_stops) {  // at or before the first stop, at or after the last
+        rgb[j] = (uint32_t) (above == 0 ? va[j] : vb[j]);
+      } else {
+        const uint64_t span = (uint64_t) (b.k - a.k);
+        rgb[j] = (uint32_t) (((uint64_t) va[j] * ((uint64_t) b.k - k) + (uint64_t) vb[j] * (k - (uint64_t) a.k) + span / 2) / span);
+      }
+    }
+    lut_out[k] = rgb[0] | (rgb[1] << 8) | (rgb[2] << 16);
+  }
+  return 0;
+}
+
 }  // extern "C"

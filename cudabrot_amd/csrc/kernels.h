@@ -256,6 +256,20 @@ struct JuliaArgs {
 };
 hipError_t launch_draw_julia(const JuliaArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_palette.hip: the palette render (include/cudabrot_amd.h, "Palette render").  ja is a Julia render's arguments, of
+// which c is read only when julia != 0; julia == 0 samples c as a projected render does, interior map included (read by
+// the product kernel with the Mandelbrot step only).  ja.pa.d.hist is three planes of plane_pixels counters each; lut is
+// the table on the device, ja.pa.d.max_iter entries -- which must be 1 .. CB_PALETTE_MAX_ENTRIES -- of which entry k
+// carries the weights of an orbit with escape index k.  A null table, a max_iter out of that range and whatever
+// launch_draw_project and launch_draw_julia refuse: hipErrorInvalidValue, nothing launched.
+struct PaletteArgs {
+  JuliaArgs ja;
+  int julia;
+  const uint32_t *lut;
+  unsigned long long plane_pixels;
+};
+hipError_t launch_draw_palette(const PaletteArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

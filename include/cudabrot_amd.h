@@ -407,6 +407,69 @@ int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              const double projection[8], const double julia_c[2], void *d_states, uint32_t n_threads,
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream);
 
+/* ---- Palette render: orbits coloured by their escape index -------------------------- *
+ *
+ * A Buddhabrot is usually shown coloured by how long its orbits took to escape.  A PALETTE render is a projected render
+ * ("Projected render" above; julia_c NULL) or a Julia render ("Julia render"; julia_c given), and those sections,
+ * together with "Multibrot step", apply unchanged: the sample stream, rejection, the interior map where the Mandelbrot
+ * step has one, the iteration, the escape index k, the accept filter min <= k < max, the replayed points z_1 ... z_{k+1},
+ * the projection's four fused operations and the binning.  What changes is where an in-canvas point goes and with what
+ * weight.  The project's own definition (the reference has none).  Normative:
+ *
+ *   Table.  lut has n_entries uint32_t entries and n_entries == max_escape_iterations, 1 <= n_entries <=
+ *   CB_PALETTE_MAX_ENTRIES (2^24).  Entry k carries the weights of an orbit with escape index k: R = bits 0-7, G = bits
+ *   8-15, B = bits 16-23.  Bits 24-31 are not read by the kernels.  Entries below min_escape_iterations are never looked
+ *   up.
+ *
+ *   Histogram.  Three planes of w*h cb_pixel, plane 0 = R, 1 = G, 2 = B, contiguous: the layout of a three-channel
+ *   histogram.  An in-canvas point of an accepted orbit adds weight_j to its pixel in plane j, for every j with
+ *   weight_j != 0.  Integer weights keep the histogram a pure function of the sample stream: hard windows are the table
+ *   whose entries are 0 or 1 per plane, the plain render is the constant table 0x010101.
+ *
+ *   Counters.  samples, rejected, never_escaped, too_fast, recorded, iterate_steps and replay_steps are exactly what the
+ *   same render without a palette counts: an accepted orbit whose entry is all zero still counts in recorded and
+ *   replay_steps.  increments is the sum of the weights added -- what the histogram gains, as the anti-Buddhabrot counts
+ *   it.  skipped_steps is the executed-work discount: the product kernel does not replay an orbit whose entry is zero
+ *   and adds its k + 1 replay steps to skipped_steps; the lock-step kernel replays everything and leaves it 0.
+ *
+ *   Stops -> table (cb_palette_from_stops, host only).  1 to CB_PALETTE_MAX_STOPS (16) stops (k, r, g, b), k >= 0
+ *   strictly ascending, components 0 .. 255.  For k <= k_first the entry is the first stop's colour, for k >= k_last the
+ *   last stop's.  For adjacent stops a, b with k_a <= k < k_b each component is
+ *       (v_a * (k_b - k) + v_b * (k - k_a) + (k_b - k_a) / 2) / (k_b - k_a)
+ *   in uint64_t, both divisions truncating.  The entry is r | g << 8 | b << 16.  Anything else is hipErrorInvalidValue.
+ *
+ *   Image.  Let M be the largest counter of all three planes together.  Each counter maps to cb_tone_value(count, M,
+ *   gamma): cb_set_grayscale_pixels applied to the three planes as one w x 3h image.  A common maximum, because the
+ *   ratio between a pixel's planes is its colour; no percentile stretch.  The file is the binary PPM of "Colour image"
+ *   step 5 below: P6, 65535, big-endian R, G, B per pixel, rows as in the PGM.
+ *
+ * Two kernels (draw_palette.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c (sampled, fixed), lanes
+ * refilled from their own subsequence with the exact-periodicity early-out and, for the Mandelbrot step on a sampled c,
+ * the interior map under cb_draw_buddhabrot_projected's rule; CB_KERNEL_SIMPLE, the definition in lock-step.  Variants
+ * are cb_draw_buddhabrot_julia's (| CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d)).  Identical histograms,
+ * generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete
+ * when it ends.  The -s buffer has three planes and records the table no more than it records the plane, the degree or
+ * c. */
+#define CB_PALETTE_MAX_ENTRIES (1 << 24)
+#define CB_PALETTE_MAX_STOPS 16
+typedef struct {
+  int k;       /* escape index of the stop, >= 0 */
+  int r, g, b; /* 0 .. 255 */
+} cb_palette_stop;
+/* The table of the stops (host arithmetic only): lut_out receives n_entries entries.  hipErrorInvalidValue, with lut_out
+ * untouched: a NULL pointer, n_stops outside 1 .. CB_PALETTE_MAX_STOPS, n_entries outside 1 .. CB_PALETTE_MAX_ENTRIES, a
+ * negative k, stops not strictly ascending in k, a component outside 0 .. 255. */
+int cb_palette_from_stops(const cb_palette_stop *stops, int n_stops, uint32_t *lut_out, uint32_t n_entries);
+/* The palette draw on caller-owned device memory: d_hist is THREE planes of w*h cb_pixel, d_lut the table on the device.
+ * julia_c NULL: c is sampled (a projected render); else the fixed c of a Julia render.  hipErrorInvalidValue, with
+ * nothing launched or written: a NULL table, n_entries != iterations->max_escape_iterations, n_entries outside 1 ..
+ * CB_PALETTE_MAX_ENTRIES, and everything cb_draw_buddhabrot_projected (julia_c NULL) or cb_draw_buddhabrot_julia
+ * refuses. */
+int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2], const uint32_t *d_lut,
+                               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
+                               cb_counters *d_counters, int kernel_variant, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -461,6 +524,20 @@ int cb_renderer_set_julia(cb_renderer *r, const double projection[8], const doub
 /* A Julia renderer's c: returns 1 and fills out[2]; returns 0 and leaves `out` alone for any other renderer (or a NULL
  * argument). */
 int cb_renderer_julia(const cb_renderer *r, double out[2]);
+/* Makes this renderer a PALETTE one ("Palette render" above); before its first pass, once, and after
+ * cb_renderer_set_projection or cb_renderer_set_julia where one of them is wanted: alone it means the identity
+ * projection.  lut_host is the table in HOST memory; it is copied to the device, and the histogram is reallocated and
+ * zeroed as three planes.  Every later cb_renderer_render_passes launches palette draws with the variants of the
+ * renderer it was (a projected or a Julia one); render_passes, finish, read / write_histogram (three planes),
+ * read_counters, the generator states and cb_renderer_grayscale_plane (planes 0 .. 2, each with its own maximum, as for
+ * channels) work on the three planes.  hipErrorInvalidValue for a channel or focused renderer, a renderer that has
+ * rendered or has a palette already, a NULL table, a table with any bit 24-31 set, n_entries !=
+ * max_escape_iterations or outside 1 .. CB_PALETTE_MAX_ENTRIES.  Afterwards cb_renderer_set_projection,
+ * cb_renderer_set_julia and cb_renderer_set_focus are refused. */
+int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries);
+/* A palette renderer's table: returns 1 and sets *n_entries (may be NULL); returns 0 and leaves it alone for any other
+ * renderer (or a NULL renderer). */
+int cb_renderer_palette(const cb_renderer *r, uint32_t *n_entries);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -526,6 +603,14 @@ int cb_renderer_grayscale_image(cb_renderer *r, double gamma, int mode, uint16_t
 /* ... for plane `plane` of a multi-channel renderer. */
 int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mode, uint16_t *host_gray_be,
                                 uint64_t *max_out, double *scale_out);
+
+/* The image of a palette renderer ("Palette render", Image; finishes carried work first): cb_tone_map_device over the
+ * three planes as one w x 3h image -- one maximum for all of them -- then one kernel interleaves the planar values.
+ * host_rgb_be receives the 3*w*h big-endian u16 of the PPM body (cb_save_ppm_be writes the file); *max_out and
+ * *scale_out (may be NULL) the two numbers of the "Max value" line.  hipErrorInvalidValue for a renderer without a
+ * palette. */
+int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                              double *scale_out);
 
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
@@ -618,7 +703,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
  * 10 the Multibrot product kernel (draw_power_kernel, the projected render's with the power step:
  * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel, 12 the Julia product kernel
- * (draw_julia_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel.
+ * (draw_julia_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
+ * (draw_palette_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
