@@ -37,6 +37,23 @@ def CB_KERNEL_POWER(degree):
     return degree << 12
 
 
+# the formula steps (include/cudabrot_amd.h, "Formula step"; projected, Julia and palette renders only)
+CB_FORMULA_TRICORN, CB_FORMULA_CELTIC, CB_FORMULA_BUFFALO, CB_FORMULA_PERPENDICULAR, CB_FORMULA_CELTIC_TRICORN = 1, 2, 3, 4, 5
+CB_FORMULA_MAX = 5
+CB_KERNEL_FORMULA_MASK = 0xF0000
+CB_FORMULA_NAMES = {"tricorn": 1, "celtic": 2, "buffalo": 3, "perpendicular": 4, "celtic-tricorn": 5}  # the CLI's names
+
+
+def CB_KERNEL_FORMULA(formula):
+    """The kernel-variant field of a formula step (OR-ed into CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE): a code
+    CB_FORMULA_TRICORN .. CB_FORMULA_MAX, or one of CB_FORMULA_NAMES."""
+    code = CB_FORMULA_NAMES.get(formula) if isinstance(formula, str) else int(formula)
+    if code is None or not CB_FORMULA_TRICORN <= code <= CB_FORMULA_MAX:
+        raise ValueError("formula must be a code from %d to %d or one of %s" % (CB_FORMULA_TRICORN, CB_FORMULA_MAX,
+                                                                                 ", ".join(CB_FORMULA_NAMES)))
+    return code << 16
+
+
 CB_FOCUS_MIN_LEVEL, CB_FOCUS_MAX_LEVEL = 4, 10  # focused render: cells of side 2^-level
 CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
 # cb_counters.status bits (include/cudabrot_amd.h)

@@ -568,7 +568,9 @@ int cb_draw_buddhabrot(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
                        void *d_workspace, size_t workspace_bytes, void *d_carry, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states) return (int) hipErrorInvalidValue;
   if (dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0) return (int) hipErrorInvalidValue;  // projected renders only
+  if ((kernel_variant & (CB_KERNEL_POWER_MASK | CB_KERNEL_FORMULA_MASK)) != 0) {
+    return (int) hipErrorInvalidValue;  // a degree, a formula: projected renders only
+  }
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
   const int base_variant = kernel_variant & ~kVariantFlags;
   const bool anti = (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0;
@@ -637,7 +639,7 @@ int cb_draw_buddhabrot_channels(const cb_fractal_dimensions *dims, cb_pixel *d_h
     return (int) hipErrorInvalidValue;
   }
   const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  const int base_variant = kernel_variant & ~kVariantFlags;  // a Multibrot degree stays in it and is refused below
+  const int base_variant = kernel_variant & ~kVariantFlags;  // a Multibrot degree or a formula stays in it and is refused below
   if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_FULL_ITERATE) ||
       (kernel_variant & CB_KERNEL_FLAG_ANTI) != 0) {
     return (int) hipErrorInvalidValue;  // the wave-scheduled kernel only; no anti channels
@@ -752,7 +754,7 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
 namespace {
 
 // CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning Ship's flag: everything a focus launch accepts (a
-// Multibrot degree, CB_KERNEL_POWER_MASK, is one of the other bits).
+// Multibrot degree, CB_KERNEL_POWER_MASK, or a formula, CB_KERNEL_FORMULA_MASK, is one of the other bits).
 bool focus_variant_ok(int kernel_variant) {
   const int base_variant = kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP;
   return base_variant == CB_KERNEL_DEFAULT || base_variant == CB_KERNEL_SIMPLE;
@@ -871,6 +873,41 @@ bool projection_ok(const double *p) {
   return true;
 }
 
+// The formula render (draw_formula.hip; include/cudabrot_amd.h, "Formula step"): what the three plotted draws below do with
+// a variant that carries CB_KERNEL_FORMULA(f), once their own arguments have passed.  julia_c null: c is sampled; d_lut
+// null: one plane, no table.
+int draw_formula(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                 const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states,
+                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
+  // a code CB_FORMULA_TRICORN .. CB_FORMULA_MAX on a base of two and nothing else: a formula is a step of its own (no
+  // Burning Ship, no degree), and the projected draws know neither anti nor drain
+  const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
+  const int base_variant = kernel_variant & ~CB_KERNEL_FORMULA_MASK;
+  if (formula < CB_FORMULA_TRICORN || formula > CB_FORMULA_MAX ||
+      (base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE)) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::FormulaArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  cb::ProjectArgs &pa = fa.pl.ja.pa;
+  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  memcpy(pa.p, projection, sizeof(pa.p));
+  pa.degree = 2;
+  if (julia_c) {
+    fa.pl.julia = 1;
+    fa.pl.ja.c[0] = julia_c[0];
+    fa.pl.ja.c[1] = julia_c[1];
+  }
+  fa.pl.lut = d_lut;
+  fa.pl.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
+  fa.formula = formula;
+  fa.palette = d_lut ? 1 : 0;
+  const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
+  g_interior_level.store(0, std::memory_order_relaxed);  // no interior map for these sets
+  g_last_draw_kernel.store(lockstep ? 17 : 16, std::memory_order_relaxed);
+  return (int) cb::launch_draw_formula(fa, lockstep, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
@@ -879,6 +916,10 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
                                  int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection)) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
+    return draw_formula(dims, d_hist, iterations, projection, nullptr, nullptr, d_states, n_threads, samples_per_thread,
+                        d_counters, kernel_variant, stream);
+  }
   // The Multibrot step ("Multibrot step"): a degree CB_POWER_MIN .. CB_POWER_MAX, no Burning Ship, no anti
   const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
   const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
@@ -939,6 +980,10 @@ int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection) || !julia_c_ok(julia_c)) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
+    return draw_formula(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads, samples_per_thread,
+                        d_counters, kernel_variant, stream);
+  }
   // the variant rules of the projected draw: a base of two, the Burning Ship or a degree, not both, no anti
   const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
   const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
@@ -1010,6 +1055,10 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
   if (!d_lut || !palette_entries_ok(n_entries, iterations)) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
+    return draw_formula(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
+                        d_counters, kernel_variant, stream);
+  }
   // the variant rules of the projected and Julia draws: a base of two, the Burning Ship or a degree, not both, no anti
   const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
   const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
@@ -1192,7 +1241,9 @@ int cb_renderer_prepare(cb_renderer *r, int kernel_variant) {
 
 int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_variant) {
   if (!r) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_POWER_MASK) != 0 && !r->projected) return (int) hipErrorInvalidValue;
+  if ((kernel_variant & (CB_KERNEL_POWER_MASK | CB_KERNEL_FORMULA_MASK)) != 0 && !r->projected) {
+    return (int) hipErrorInvalidValue;  // a degree, a formula: on a projected, Julia or palette renderer only
+  }
   CB_TRY(hipSetDevice(r->device));
   const uint32_t max_passes_per_launch = ::max_passes_per_launch();
   prepare_for_variant(r, kernel_variant);

@@ -27,7 +27,9 @@
 //    --burning-ship, on any plane: include/cudabrot_amd.h, "Julia render"), --palette K:RRGGBB[,K:RRGGBB...] (orbits
 //    coloured by their escape index: colour stops interpolated into a table of -m entries, three planes of integer
 //    weights, -o receives a 16-bit PPM; on the projected path with any plane, --power, --julia or --burning-ship:
-//    include/cudabrot_amd.h, "Palette render").
+//    include/cudabrot_amd.h, "Palette render"), --formula NAME (another step of the quadratic family: tricorn, celtic,
+//    buffalo, perpendicular or celtic-tricorn, on the projected path with any plane, --julia or --palette:
+//    include/cudabrot_amd.h, "Formula step").
 #include <errno.h>
 #include <math.h>
 #include <signal.h>
@@ -107,7 +109,13 @@ struct Settings {
   cb_palette_stop palette_stops[CB_PALETTE_MAX_STOPS] = {};
   const char *bad_palette_flag = nullptr;           // the message of a bad --palette
   bool palette() const { return n_palette_stops > 0; }
-  bool projected() const { return project_given || plane_given || rotate_given || power != 0 || julia || palette(); }
+  // --formula NAME (extension): a formula step, CB_KERNEL_FORMULA(code); makes the run a projected one as --power does
+  int formula = 0;
+  const char *formula_name = nullptr;
+  const char *bad_formula_flag = nullptr;           // the message of a bad --formula
+  bool projected() const {
+    return project_given || plane_given || rotate_given || power != 0 || julia || palette() || formula != 0;
+  }
 };
 
 // One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
@@ -414,6 +422,19 @@ const std::vector<Flag> &flag_table() {
            s.bad_palette_flag = "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops)";
          }
        }},
+      {"--formula", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         static const char *const kNames[CB_FORMULA_MAX] = {"tricorn", "celtic", "buffalo", "perpendicular",
+                                                            "celtic-tricorn"};  // codes 1 .. CB_FORMULA_MAX
+         for (int code = 1; code <= CB_FORMULA_MAX; ++code) {
+           if (strcmp(t, kNames[code - 1]) == 0) {
+             s.formula = code;
+             s.formula_name = kNames[code - 1];
+             return;
+           }
+         }
+         s.bad_formula_flag = "Invalid formula (want tricorn, celtic, buffalo, perpendicular or celtic-tricorn)";
+       }},
       {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
       {"--rng-state", Value::kText, nullptr, false,
@@ -563,7 +584,26 @@ Settings parse_arguments(int argc, char **argv) {
       printf("%s: %s\n", s.bad_palette_flag, text);
       usage_and_exit(argv[0]);
     }
+    if (s.bad_formula_flag) {
+      printf("%s: %s\n", s.bad_formula_flag, text);
+      usage_and_exit(argv[0]);
+    }
     if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  // a formula render is a projected render with a step of its own (include/cudabrot_amd.h, "Formula step"): its refusals
+  // come before those of the palette, the Multibrot step, c and the projection, which it would otherwise trip
+  if (s.formula != 0) {
+    const char *with = s.power != 0                           ? "--power"
+                       : s.burning_ship                       ? "--burning-ship"
+                       : s.anti                               ? "--anti"
+                       : s.focus                              ? "--focus"
+                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
+                       : s.gpus > 1                           ? "--gpus above 1"
+                                                              : nullptr;
+    if (with) {
+      printf("--formula does not combine with %s.\n", with);
+      usage_and_exit(argv[0]);
+    }
   }
   // a palette render is a projected render with three planes (include/cudabrot_amd.h, "Palette render"): its refusals come
   // before those of the step, of c and of the projection, which it would otherwise trip
@@ -687,6 +727,7 @@ class Run {
       fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
               p[3], p[4], p[5], p[6], p[7]);
       if (cfg_.power != 0) fprintf(stderr, "{\"power\": %d}\n", cfg_.power);  // the step: it defines the run as well
+      if (cfg_.formula != 0) fprintf(stderr, "{\"formula\": \"%s\"}\n", cfg_.formula_name);  // or this step
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       if (cfg_.palette()) {  // and the colours
         fprintf(stderr, "{\"palette\": [");
@@ -876,7 +917,8 @@ class Run {
     }
     fflush(stdout);
     const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0) |
-                        (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0) | (cfg_.power ? CB_KERNEL_POWER(cfg_.power) : 0);
+                        (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0) | (cfg_.power ? CB_KERNEL_POWER(cfg_.power) : 0) |
+                        (cfg_.formula ? CB_KERNEL_FORMULA(cfg_.formula) : 0);
     if (cfg_.focus) set_focus(variant);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));

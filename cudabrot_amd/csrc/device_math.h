@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/cudabrot_amd.h"  // CB_FORMULA_*: the codes of formula_step
+
 namespace cb {
 
 // XORWOW generator state (rocRAND 4.2 rocrand_xorwow.h:72-89, the live part): 160 xorshift bits and
@@ -188,6 +190,69 @@ __device__ __forceinline__ double power_step_n(double cr, double ci, double &r, 
   r = cr + wr;
   i = ci + wi;
   return __builtin_fma(i, i, r * r);
+}
+
+// ---- the formula step (include/cudabrot_amd.h, "Formula step") ----------------------------------------
+//
+// mandel_step with a sign or a magnitude changed in nr or ni, by the code F = CB_FORMULA_TRICORN .. CB_FORMULA_CELTIC_TRICORN:
+//   nr = cr + t                      tricorn, perpendicular          nr = cr + |t|     celtic, buffalo, celtic-tricorn
+//   ni = fma(-(r + r), i, ci)        tricorn, celtic-tricorn         ni = fma(r + r, i, ci)              celtic
+//   ni = fma(|r| + |r|, |i|, ci)     buffalo (the ship's)            ni = fma(-(|r| + |r|), i, ci)       perpendicular
+// Negation and fabs are exact (operand modifiers on gfx950), so each is mandel_step's seven instructions.  Written twice,
+// as power_step is: formula_step<F> with the code a template argument (the product kernels) and formula_step(f, ...) with
+// the code a run-time argument (the lock-step kernel), two writings of the definition; within either kernel ITERATE and
+// REPLAY make the same call, so a replayed orbit retraces the tested one bit for bit.
+template <int F>
+__device__ __forceinline__ double formula_step(double cr, double ci, double &r, double &i) {
+  static_assert(F >= CB_FORMULA_TRICORN && F <= CB_FORMULA_MAX, "CB_FORMULA_TRICORN .. CB_FORMULA_MAX");
+  constexpr bool kAbsT = F == CB_FORMULA_CELTIC || F == CB_FORMULA_BUFFALO || F == CB_FORMULA_CELTIC_TRICORN;
+  const double ii = i * i;
+  const double t = __builtin_fma(r, r, -ii);
+  const double nr = cr + (kAbsT ? __builtin_fabs(t) : t);
+  double ni;
+  if constexpr (F == CB_FORMULA_TRICORN || F == CB_FORMULA_CELTIC_TRICORN) {
+    ni = __builtin_fma(-(r + r), i, ci);
+  } else if constexpr (F == CB_FORMULA_CELTIC) {
+    ni = __builtin_fma(r + r, i, ci);
+  } else if constexpr (F == CB_FORMULA_BUFFALO) {
+    ni = __builtin_fma(__builtin_fabs(r) + __builtin_fabs(r), __builtin_fabs(i), ci);
+  } else {
+    ni = __builtin_fma(-(__builtin_fabs(r) + __builtin_fabs(r)), i, ci);
+  }
+  r = nr;
+  i = ni;
+  return __builtin_fma(ni, ni, nr * nr);
+}
+
+__device__ __forceinline__ double formula_step(int f, double cr, double ci, double &r, double &i) {
+  const double ii = i * i;
+  const double t = __builtin_fma(r, r, -ii);
+  double nr, ni;
+  switch (f) {
+    case CB_FORMULA_TRICORN:
+      nr = cr + t;
+      ni = __builtin_fma(-(r + r), i, ci);
+      break;
+    case CB_FORMULA_CELTIC:
+      nr = cr + __builtin_fabs(t);
+      ni = __builtin_fma(r + r, i, ci);
+      break;
+    case CB_FORMULA_BUFFALO:
+      nr = cr + __builtin_fabs(t);
+      ni = __builtin_fma(__builtin_fabs(r) + __builtin_fabs(r), __builtin_fabs(i), ci);
+      break;
+    case CB_FORMULA_PERPENDICULAR:
+      nr = cr + t;
+      ni = __builtin_fma(-(__builtin_fabs(r) + __builtin_fabs(r)), i, ci);
+      break;
+    default:  // CB_FORMULA_CELTIC_TRICORN: launch_draw_formula lets no other code through
+      nr = cr + __builtin_fabs(t);
+      ni = __builtin_fma(-(r + r), i, ci);
+      break;
+  }
+  r = nr;
+  i = ni;
+  return __builtin_fma(ni, ni, nr * nr);
 }
 
 // Canvas geometry as the kernels consume it: FractalDimensions (cudabrot.cu:46-58) plus the exact

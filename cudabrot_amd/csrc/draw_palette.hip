@@ -14,20 +14,11 @@
 //                                   zero adds nothing anywhere, so it is not replayed: its steps go to skipped_steps.
 //                                   Same histogram, generator states and counters (but skipped_steps).
 // No workspace, no carry, no LDS: every launch is complete, and lane t advances generator t by exactly its samples.
-#include <type_traits>
-
 #include "draw_plot.h"
 
 namespace cb {
 
 namespace {
-
-constexpr uint32_t kPaletteWeightBits = 0x00ffffffu;  // bits 24-31 of an entry are not read
-
-// weight_j of an entry: plane 0 = R, 1 = G, 2 = B.
-__device__ __forceinline__ unsigned long long palette_weight(uint32_t entry, int plane) {
-  return (unsigned long long) ((entry >> (8 * plane)) & 0xffu);
-}
 
 // One step with c = (c_re, c_im); degree 2 is the reference's step or its Burning Ship variant, else the Multibrot step.
 __device__ __forceinline__ double palette_step(int degree, bool ship, double c_re, double c_im, double &r, double &i) {
@@ -128,59 +119,11 @@ __global__ void __launch_bounds__(256) draw_palette_simple_kernel(PaletteArgs pl
 // draw_palette_kernel: lanes refilled from their own subsequence, exact-periodicity early-out
 // ------------------------------------------------------------------------------------------------
 //
-// The round scheduler of draw_rounds.h with this mode, which is PlotMode (a sampled c) or JuliaMode (a fixed one) of
-// draw_plot.h with another ESCAPED and another plot: step, NEXT and the never-escaping case are theirs.  ESCAPED counts
+// The round scheduler of draw_rounds.h with PaletteMode of draw_plot.h, which is PlotMode (a sampled c) or JuliaMode (a
+// fixed one) with another ESCAPED and another plot: step, NEXT and the never-escaping case are theirs.  ESCAPED counts
 // the orbit as they do and then loads its entry, once: the lane keeps it through the replay.  A zero entry ends the
 // sample there -- counted as recorded and in replay_steps like any accepted orbit, the replay not made in
 // skipped_steps.  A replayed point finds its pixel once and adds each non-zero weight to that pixel of its plane.
-
-namespace {
-
-template <class Step, bool kJulia>
-struct PaletteMode {
-  typename std::conditional<kJulia, JuliaMode<Step>, PlotMode<Step>>::type base;
-  const uint32_t *const lut;
-  const unsigned long long plane_pixels;
-  uint32_t entry = 0u;  // of the orbit in REPLAY
-
-  __device__ __forceinline__ double step(RoundLane &l) { return base.step(l); }
-  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) { return base.next(rng, l); }
-
-  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
-    // (for a sampled c, PlotMode also makes an accepted orbit's two projection constants here, before the entry is known:
-    // a zero-entry orbit pays for those two operations and never uses them)
-    const bool accepted = base.escaped(l, st);
-    // k = l.end - 1: min_iter <= k < max_iter == n_entries, and 0 <= k
-    entry = accepted ? lut[l.end - 1] & kPaletteWeightBits : 0u;
-    // (one add on every path: an add of its own in this branch, beside count_escaped's to too_fast in the other, makes the
-    // compiler index the counters through memory)
-    st.reserved += accepted && entry == 0u ? (unsigned long long) l.end : 0ull;
-    return entry != 0u;
-  }
-  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool cycle) {
-    return base.never_escapes(l, st, cycle);
-  }
-
-  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
-    const Plot &plot = base.plot;
-    const double u = project_point(plot.pa.p[0], plot.pa.p[1], l.r, l.i, plot.ku);
-    const double v = project_point(plot.pa.p[4], plot.pa.p[5], l.r, l.i, plot.kv);
-    int row, col;
-    if (pixel_of(u, v, plot.cv, row, col)) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const unsigned long long weight = palette_weight(entry, j);
-        if (weight != 0ull) {
-          add_to_pixel(plot.pa.d.hist + (unsigned long long) j * plane_pixels, plot.cv, row, col, weight);
-          st.increments += weight;
-        }
-      }
-    }
-    return false;
-  }
-};
-
-}  // namespace
 
 template <class Step, bool kJulia>
 __global__ void __launch_bounds__(256) draw_palette_kernel(PaletteArgs pl) {

@@ -1,8 +1,10 @@
 // draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_project.hip, draw_julia.hip,
-// draw_palette.hip; include/cudabrot_amd.h, "Projected render"): the four fused operations of a plotted point, the plot of
-// a replayed point for the modes of draw_rounds.h's scheduler, the steps those modes are instantiated with, and the two
-// modes themselves -- a sampled c and a fixed one -- which the palette render's mode builds on.
+// draw_palette.hip, draw_formula.hip; include/cudabrot_amd.h, "Projected render"): the four fused operations of a plotted
+// point, the plot of a replayed point for the modes of draw_rounds.h's scheduler, the steps those modes are instantiated
+// with, and the modes themselves -- a sampled c, a fixed one, and the palette render's mode, which builds on either.
 #pragma once
+
+#include <type_traits>
 
 #include "draw_rounds.h"
 
@@ -55,7 +57,24 @@ struct PowerOrbit {  // the degree wave-uniform and the loop gone
   }
 };
 
-// ---- the plot modes of draw_rounds.h's scheduler (draw_project.hip, draw_julia.hip, draw_palette.hip) -----------------
+template <int F>
+struct FormulaOrbit {  // include/cudabrot_amd.h, "Formula step": the code wave-uniform and the switch gone
+  static constexpr bool kMandelbrot = false;
+  static __device__ __forceinline__ double step(double cr, double ci, double &r, double &i) {
+    return formula_step<F>(cr, ci, r, i);
+  }
+};
+
+// ---- the palette's entry (include/cudabrot_amd.h, "Palette render") -----------------------------------------------------
+
+constexpr uint32_t kPaletteWeightBits = 0x00ffffffu;  // bits 24-31 of an entry are not read
+
+// weight_j of an entry: plane 0 = R, 1 = G, 2 = B.
+__device__ __forceinline__ unsigned long long palette_weight(uint32_t entry, int plane) {
+  return (unsigned long long) ((entry >> (8 * plane)) & 0xffu);
+}
+
+// ---- the plot modes of draw_rounds.h's scheduler (draw_project.hip, draw_julia.hip, draw_palette.hip, draw_formula.hip) --
 
 namespace {
 
@@ -125,6 +144,53 @@ struct JuliaMode {
 
   __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
     plot.point(l.r, l.i, st);
+    return false;
+  }
+};
+
+
+// The mode of a palette render (draw_palette.hip has the commentary): either mode above with another ESCAPED, which loads
+// the orbit's entry once, and another plot, which adds each non-zero weight to the pixel of its plane.
+template <class Step, bool kJulia>
+struct PaletteMode {
+  typename std::conditional<kJulia, JuliaMode<Step>, PlotMode<Step>>::type base;
+  const uint32_t *const lut;
+  const unsigned long long plane_pixels;
+  uint32_t entry = 0u;  // of the orbit in REPLAY
+
+  __device__ __forceinline__ double step(RoundLane &l) { return base.step(l); }
+  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) { return base.next(rng, l); }
+
+  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
+    // (for a sampled c, PlotMode also makes an accepted orbit's two projection constants here, before the entry is known:
+    // a zero-entry orbit pays for those two operations and never uses them)
+    const bool accepted = base.escaped(l, st);
+    // k = l.end - 1: min_iter <= k < max_iter == n_entries, and 0 <= k
+    entry = accepted ? lut[l.end - 1] & kPaletteWeightBits : 0u;
+    // (one add on every path: an add of its own in this branch, beside count_escaped's to too_fast in the other, makes the
+    // compiler index the counters through memory)
+    st.reserved += accepted && entry == 0u ? (unsigned long long) l.end : 0ull;
+    return entry != 0u;
+  }
+  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool cycle) {
+    return base.never_escapes(l, st, cycle);
+  }
+
+  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
+    const Plot &plot = base.plot;
+    const double u = project_point(plot.pa.p[0], plot.pa.p[1], l.r, l.i, plot.ku);
+    const double v = project_point(plot.pa.p[4], plot.pa.p[5], l.r, l.i, plot.kv);
+    int row, col;
+    if (pixel_of(u, v, plot.cv, row, col)) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const unsigned long long weight = palette_weight(entry, j);
+        if (weight != 0ull) {
+          add_to_pixel(plot.pa.d.hist + (unsigned long long) j * plane_pixels, plot.cv, row, col, weight);
+          st.increments += weight;
+        }
+      }
+    }
     return false;
   }
 };

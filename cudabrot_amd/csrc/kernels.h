@@ -270,6 +270,19 @@ struct PaletteArgs {
 };
 hipError_t launch_draw_palette(const PaletteArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_formula.hip: the formula step (include/cudabrot_amd.h, "Formula step") on a projected render, a Julia render or
+// a palette render of either.  pl is a palette render's arguments with degree 2 and no Burning Ship: of it, c is read
+// only when pl.julia != 0, and lut and plane_pixels only when palette != 0 -- else pl.ja.pa.d.hist is one plane.  The
+// interior map is never read.  formula is the code, CB_FORMULA_TRICORN .. CB_FORMULA_MAX.  hipErrorInvalidValue, nothing
+// launched: any other code, a degree other than 2 or the Burning Ship with it, and whatever launch_draw_julia (julia)
+// and launch_draw_palette (palette) refuse.
+struct FormulaArgs {
+  PaletteArgs pl;
+  int formula;
+  int palette;
+};
+hipError_t launch_draw_formula(const FormulaArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

@@ -171,6 +171,65 @@ typedef struct {
 #define CB_KERNEL_POWER(d) ((d) << 12)
 #define CB_KERNEL_POWER_MASK 0xF000
 
+/* ---- Formula step: tricorn, Celtic and kin on the projected render ----------------- *
+ *
+ * CB_KERNEL_FORMULA(f), OR-ed into CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, replaces the step of a PROJECTED render
+ * ("Projected render" below), of a JULIA render or of a PALETTE render by another member of the quadratic family whose
+ * members differ from the reference's step by a sign or an absolute value.  Field 0 means the step as without it.  This
+ * is the project's own definition: sign conventions differ between programs, and these are ours.  Normative:
+ *
+ *   Code.  CB_FORMULA_TRICORN = 1 <= f <= CB_FORMULA_MAX = 5.
+ *
+ *   Step.  One step from z = (r, i) with c = (cr, ci) is IEEE fp64; each fma is one rounding and nothing else is
+ *   contracted; negation and fabs are exact:
+ *       ii = i * i
+ *       t  = fma(r, r, -ii)
+ *       nr, ni by the code:
+ *         code  name              nr             ni
+ *         1     tricorn           cr + t         fma(-(r + r), i, ci)                         (the Mandelbar)
+ *         2     celtic            cr + fabs(t)   fma(r + r, i, ci)
+ *         3     buffalo           cr + fabs(t)   fma(fabs(r) + fabs(r), fabs(i), ci)          (the Burning Ship's cross term)
+ *         4     perpendicular     cr + t         fma(-(fabs(r) + fabs(r)), i, ci)
+ *         5     celtic-tricorn    cr + fabs(t)   fma(-(r + r), i, ci)                         (the Celtic Mandelbar)
+ *       r' = nr;  i' = ni
+ *       m  = fma(ni, ni, nr * nr)          escape: m > 4.0
+ *   With nr = cr + t and ni = fma(r + r, i, ci) this is the reference's step, which has no code.
+ *
+ *   Everything else is a Multibrot render's ("Multibrot step"): a projected render, on the identity matrix unless one is
+ *   given; the normal sample stream (4 XORWOW draws per sample, z_0 = c); IterateMandelbrot's loop shape (k = index of
+ *   the first escaping z_{k+1}, or max); the accept filter min <= k < max; the replay of z_1 ... z_{k+1}; the projection
+ *   P[2][4] with its four fused operations per point; the binning.  No cardioid or bulb rejection (rejected = 0) and no
+ *   interior map (cb_debug_interior_map_level() == 0).  Counters keep their normal meaning; skipped_steps is the
+ *   executed-work discount of the product kernel.
+ *
+ *   Every visited point is finite: a visited point follows a point with |z|^2 <= 4 (z_0 = c or a point that passed the
+ *   test), and |t| <= |z|^2, 2 |r| |i| <= |z|^2, so |nr| <= |cr| + 4 and |ni| <= |ci| + 4 up to rounding: |z'| <= 4 +
+ *   |c| <= 4 + 2 sqrt(2).  The identity projection cannot move a bin ("Projected render", Identity).
+ *
+ *   With a fixed c (cb_draw_buddhabrot_julia): the fixed c goes into the same step, and everything else is under "Julia
+ *   render"'s rules -- the sample is z_0, |z_0|^2 may exceed 4 and z_1 is then finite all the same (|z_0| <= 2 sqrt(2)).
+ *   With a table (cb_draw_buddhabrot_palette): under "Palette render"'s rules, for a sampled c or a fixed one.
+ *
+ * Accepted by cb_draw_buddhabrot_projected, cb_draw_buddhabrot_julia, cb_draw_buddhabrot_palette and by
+ * cb_renderer_render_passes on a projected, Julia or palette renderer.  hipErrorInvalidValue, with nothing launched or
+ * written: a field value of 6 ... 15; a code together with CB_KERNEL_FLAG_BURNING_SHIP, CB_KERNEL_FLAG_ANTI,
+ * CB_KERNEL_FLAG_DRAIN, CB_KERNEL_POWER(d) or a base variant other than the two above; a code given to
+ * cb_draw_buddhabrot, cb_draw_buddhabrot_channels, cb_focus_probe, cb_draw_buddhabrot_focus, cb_renderer_set_focus, or to
+ * cb_renderer_render_passes on a plain, channel or focused renderer.
+ * Two kernels (draw_formula.hip): CB_KERNEL_DEFAULT, one instance per code, per source of c (sampled, fixed) and per
+ * sink (one plane, the palette's three), lanes refilled from their own subsequence, with the exact-periodicity
+ * early-out; CB_KERNEL_SIMPLE, the definition in lock-step with code, source and sink run-time arguments.  Identical
+ * histograms, generator states and counters (but skipped_steps).
+ * The -s buffer records the formula no more than it records the plane. */
+#define CB_FORMULA_TRICORN 1
+#define CB_FORMULA_CELTIC 2
+#define CB_FORMULA_BUFFALO 3
+#define CB_FORMULA_PERPENDICULAR 4
+#define CB_FORMULA_CELTIC_TRICORN 5
+#define CB_FORMULA_MAX 5
+#define CB_KERNEL_FORMULA(f) ((f) << 16)
+#define CB_KERNEL_FORMULA_MASK 0xF0000
+
 /* Returned (instead of a hipError_t) by cb_renderer_set_focus when the probe marked no cell: no sample of the probe has
  * an accepted orbit that enters the canvas, so a focused render would have nothing to sample from. */
 #define CB_ERROR_FOCUS_EMPTY 100002
@@ -355,7 +414,8 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
  * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence, with the interior map
  * (Mandelbrot step only) and the exact-periodicity early-out, and CB_KERNEL_SIMPLE, the definition in lock-step;
  * optionally | CB_KERNEL_FLAG_BURNING_SHIP; any other variant, CB_KERNEL_FLAG_ANTI included, is hipErrorInvalidValue.
- * (| CB_KERNEL_POWER(d) instead of the Burning Ship's flag: the Multibrot step and its two kernels, "Multibrot step".)
+ * (| CB_KERNEL_POWER(d) instead of the Burning Ship's flag: the Multibrot step and its two kernels, "Multibrot step";
+ * | CB_KERNEL_FORMULA(f) instead of either: a formula step and its two kernels, "Formula step".)
  * Identical histograms, generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry:
  * every launch is complete when it ends.  The -s buffer format is unchanged and does NOT record the plane: resuming a
  * buffer with another projection adds two different images, and nothing can notice. */
@@ -399,7 +459,8 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
  * Two kernels (draw_julia.hip): CB_KERNEL_DEFAULT, one instance per step, lanes refilled from their own subsequence, with
  * the exact-periodicity early-out -- all that retires a Julia interior: attracting cycles land on an exact fp64 cycle
  * quickly -- and CB_KERNEL_SIMPLE, the definition in lock-step with step and degree run-time arguments; optionally
- * | CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d); any other variant, CB_KERNEL_FLAG_ANTI included, is
+ * | CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d), or | CB_KERNEL_FORMULA(f) instead of either ("Formula step",
+ * draw_formula.hip); any other variant, CB_KERNEL_FLAG_ANTI included, is
  * hipErrorInvalidValue, with nothing launched or written.  Identical histograms, generator states and counters (but
  * skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete when it ends.  The -s buffer records
  * c no more than it records the plane or the degree. */
@@ -446,7 +507,8 @@ int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist
  * Two kernels (draw_palette.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c (sampled, fixed), lanes
  * refilled from their own subsequence with the exact-periodicity early-out and, for the Mandelbrot step on a sampled c,
  * the interior map under cb_draw_buddhabrot_projected's rule; CB_KERNEL_SIMPLE, the definition in lock-step.  Variants
- * are cb_draw_buddhabrot_julia's (| CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d)).  Identical histograms,
+ * are cb_draw_buddhabrot_julia's (| CB_KERNEL_FLAG_BURNING_SHIP, | CB_KERNEL_POWER(d) or | CB_KERNEL_FORMULA(f), the last
+ * with the two kernels of draw_formula.hip).  Identical histograms,
  * generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete
  * when it ends.  The -s buffer has three planes and records the table no more than it records the plane, the degree or
  * c. */
@@ -506,7 +568,7 @@ int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int 
 int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total);
 /* Makes this renderer a PROJECTED one ("Projected render" above); before its first pass, once.  Every later
  * cb_renderer_render_passes launches projected draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with the Burning
- * Ship's flag: anything else is hipErrorInvalidValue); render_passes, finish and the histogram, image and state reads
+ * Ship's flag, CB_KERNEL_POWER(d) or CB_KERNEL_FORMULA(f): anything else is hipErrorInvalidValue); render_passes, finish and the histogram, image and state reads
  * work as for a focused renderer.  hipErrorInvalidValue for a channel renderer, a focused renderer, a renderer that has
  * rendered or is projected already, or a non-finite entry; cb_renderer_set_focus on a projected renderer is refused
  * likewise. */
@@ -516,7 +578,8 @@ int cb_renderer_set_projection(cb_renderer *r, const double projection[8]);
 int cb_renderer_projection(const cb_renderer *r, double out[8]);
 /* Makes this renderer a JULIA one ("Julia render" above); before its first pass, once.  projection: the matrix, NULL for
  * the identity.  Every later cb_renderer_render_passes launches Julia draws (CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE,
- * optionally with the Burning Ship's flag or CB_KERNEL_POWER(d): anything else is hipErrorInvalidValue).
+ * optionally with the Burning Ship's flag, CB_KERNEL_POWER(d) or CB_KERNEL_FORMULA(f): anything else is
+ * hipErrorInvalidValue).
  * hipErrorInvalidValue for a channel renderer, a focused or projected renderer, a renderer that has rendered or is a Julia
  * one already, a non-finite matrix entry, or a c that is not two numbers in [-2, 2].  A Julia renderer is a projected
  * one: cb_renderer_projection returns its matrix, cb_renderer_set_focus and cb_renderer_set_projection are refused. */
@@ -704,7 +767,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * 10 the Multibrot product kernel (draw_power_kernel, the projected render's with the power step:
  * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel, 12 the Julia product kernel
  * (draw_julia_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
- * (draw_palette_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel.
+ * (draw_palette_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel, 16 the formula product kernel
+ * (draw_formula_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
