@@ -317,6 +317,10 @@ namespace {
 // The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette renderer, else one.
 size_t renderer_planes(const cb_renderer *r) { return r->palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u); }
 
+int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
+              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
+
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
 int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
@@ -328,27 +332,11 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
                                     passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->focus_level,
                                     r->d_focus_cells, r->focus_n_cells, r->stream);
   }
-  if (r->projected) {  // draw_project.hip: direct atomics, no deferred scatter, no carry
+  if (r->projected) {  // draw_plot.hip: direct atomics, no deferred scatter, no carry; what the setters took is checked
     if (passes == 0) return 0;
-    if (r->palette) {  // draw_palette.hip: either of the two below with the table
-      const int rc = cb_draw_buddhabrot_palette(&r->dims, r->d_hist, &r->iterations, r->projection,
-                                                r->julia ? r->julia_c : nullptr, r->d_palette, r->palette_entries,
-                                                r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
-                                                kernel_variant, r->stream);
-      r->interior_level = rc ? 0 : cb_debug_interior_map_level();
-      return rc;
-    }
-    if (r->julia) {  // draw_julia.hip: no interior map either
-      r->interior_level = 0;
-      return cb_draw_buddhabrot_julia(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia_c, r->d_states,
-                                      r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant,
-                                      r->stream);
-    }
-    const int rc = cb_draw_buddhabrot_projected(&r->dims, r->d_hist, &r->iterations, r->projection, r->d_states,
-                                                r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
-                                                kernel_variant, r->stream);
-    r->interior_level = rc ? 0 : cb_debug_interior_map_level();
-    return rc;
+    return draw_plot(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
+                     r->palette ? r->d_palette : nullptr, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
+                     r->d_counters, kernel_variant, r->stream, &r->interior_level);
   }
   // the lock-step kernel and the anti kernels: direct atomics, no deferred scatter, no carry
   const bool wave = (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE && (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0;
@@ -861,7 +849,7 @@ int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n
   return 0;
 }
 
-// ---- projected render (draw_project.hip; include/cudabrot_amd.h, "Projected render") -------------------------------
+// ---- projected render (draw_plot.hip; include/cudabrot_amd.h, "Projected render") -------------------------------
 
 namespace {
 
@@ -873,39 +861,56 @@ bool projection_ok(const double *p) {
   return true;
 }
 
-// The formula render (draw_formula.hip; include/cudabrot_amd.h, "Formula step"): what the three plotted draws below do with
-// a variant that carries CB_KERNEL_FORMULA(f), once their own arguments have passed.  julia_c null: c is sampled; d_lut
-// null: one plane, no table.
-int draw_formula(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-                 const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states,
-                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
-  // a code CB_FORMULA_TRICORN .. CB_FORMULA_MAX on a base of two and nothing else: a formula is a step of its own (no
-  // Burning Ship, no degree), and the projected draws know neither anti nor drain
+// The plotted draws (draw_plot.hip): what the three entry points below do once their own arguments have passed.  julia_c
+// null: c is sampled; d_lut null: one plane, no table.  interior_level (may be null): the level of the interior map the
+// launch used, 0 for none or when nothing was launched.
+int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
+              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
+  if (interior_level) *interior_level = 0;
+  // A base of two and at most one of: a formula code CB_FORMULA_TRICORN .. CB_FORMULA_MAX ("Formula step"), a degree
+  // CB_POWER_MIN .. CB_POWER_MAX ("Multibrot step"), the Burning Ship.  The plotted draws know neither anti nor drain.
   const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
-  const int base_variant = kernel_variant & ~CB_KERNEL_FORMULA_MASK;
-  if (formula < CB_FORMULA_TRICORN || formula > CB_FORMULA_MAX ||
-      (base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE)) {
+  const int degree_bits = (kernel_variant & CB_KERNEL_POWER_MASK) >> 12;
+  const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  const int base_variant = kernel_variant & ~(CB_KERNEL_FORMULA_MASK | CB_KERNEL_POWER_MASK | CB_KERNEL_FLAG_BURNING_SHIP);
+  const bool power = degree_bits != 0;
+  if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE) || formula > CB_FORMULA_MAX ||
+      (power && (degree_bits < CB_POWER_MIN || degree_bits > CB_POWER_MAX)) ||
+      (formula != 0 ? 1 : 0) + (power ? 1 : 0) + (ship ? 1 : 0) > 1) {
     return (int) hipErrorInvalidValue;
   }
-  cb::FormulaArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  cb::ProjectArgs &pa = fa.pl.ja.pa;
+  cb::PlotArgs pa;
+  memset(&pa, 0, sizeof(pa));
   pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
+  pa.d.burning_ship = ship ? 1 : 0;
   memcpy(pa.p, projection, sizeof(pa.p));
-  pa.degree = 2;
+  pa.degree = power ? degree_bits : 2;
   if (julia_c) {
-    fa.pl.julia = 1;
-    fa.pl.ja.c[0] = julia_c[0];
-    fa.pl.ja.c[1] = julia_c[1];
+    pa.julia = 1;
+    pa.c[0] = julia_c[0];
+    pa.c[1] = julia_c[1];
   }
-  fa.pl.lut = d_lut;
-  fa.pl.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
-  fa.formula = formula;
-  fa.palette = d_lut ? 1 : 0;
+  pa.lut = d_lut;
+  pa.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
+  pa.formula = formula;
+  pa.palette = d_lut ? 1 : 0;
   const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
-  g_interior_level.store(0, std::memory_order_relaxed);  // no interior map for these sets
-  g_last_draw_kernel.store(lockstep ? 17 : 16, std::memory_order_relaxed);
-  return (int) cb::launch_draw_formula(fa, lockstep, reinterpret_cast<hipStream_t>(stream));
+  // The interior map (the Mandelbrot set's: a sampled c, degree 2, no formula) where the normal product path consults it:
+  // wants_interior_map's rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter
+  // leaves that path a LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it
+  // retires nothing through the map either.
+  g_interior_level.store(0, std::memory_order_relaxed);
+  if (!julia_c && !power && formula == 0 && pa.d.long_steps > 0) {
+    const int rc = attach_interior_map(pa.d, kernel_variant);
+    if (rc) return rc;
+  }
+  // cb_debug_last_draw_kernel names the entry point and the step: product / lock-step
+  const int id = formula != 0 ? 16 : d_lut ? 14 : julia_c ? 12 : power ? 10 : 8;
+  g_last_draw_kernel.store(id + (lockstep ? 1 : 0), std::memory_order_relaxed);
+  const int rc = (int) cb::launch_draw_plot(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
+  if (interior_level && !rc && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
+  return rc;
 }
 
 }  // namespace
@@ -916,36 +921,8 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
                                  int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection)) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
-    return draw_formula(dims, d_hist, iterations, projection, nullptr, nullptr, d_states, n_threads, samples_per_thread,
-                        d_counters, kernel_variant, stream);
-  }
-  // The Multibrot step ("Multibrot step"): a degree CB_POWER_MIN .. CB_POWER_MAX, no Burning Ship, no anti
-  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
-  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
-  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
-  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
-    return (int) hipErrorInvalidValue;
-  }
-  cb::ProjectArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  pa.d.burning_ship = ship ? 1 : 0;
-  memcpy(pa.p, projection, sizeof(pa.p));
-  pa.degree = degree;
-  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
-  // The interior map (the Mandelbrot set's: degree 2 only) where the normal product path consults it: wants_interior_map's
-  // rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter leaves that path a
-  // LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it retires nothing
-  // through the map either.
-  g_interior_level.store(0, std::memory_order_relaxed);
-  if (!power && pa.d.long_steps > 0) {
-    const int rc = attach_interior_map(pa.d, kernel_variant);
-    if (rc) return rc;
-  }
-  g_last_draw_kernel.store((power ? 10 : 8) + (lockstep ? 1 : 0), std::memory_order_relaxed);
-  return (int) cb::launch_draw_project(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
+  return draw_plot(dims, d_hist, iterations, projection, nullptr, nullptr, d_states, n_threads, samples_per_thread,
+                   d_counters, kernel_variant, stream, nullptr);
 }
 
 int cb_renderer_set_projection(cb_renderer *r, const double projection[8]) {
@@ -963,7 +940,7 @@ int cb_renderer_projection(const cb_renderer *r, double out[8]) {
   return 1;
 }
 
-// ---- Julia render (draw_julia.hip; include/cudabrot_amd.h, "Julia render") ------------------------------------------
+// ---- Julia render (draw_plot.hip; include/cudabrot_amd.h, "Julia render") -------------------------------------------
 
 namespace {
 
@@ -980,30 +957,8 @@ int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection) || !julia_c_ok(julia_c)) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
-    return draw_formula(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads, samples_per_thread,
-                        d_counters, kernel_variant, stream);
-  }
-  // the variant rules of the projected draw: a base of two, the Burning Ship or a degree, not both, no anti
-  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
-  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
-  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
-  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
-    return (int) hipErrorInvalidValue;
-  }
-  cb::JuliaArgs ja;
-  memset(&ja, 0, sizeof(ja));
-  ja.pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  ja.pa.d.burning_ship = ship ? 1 : 0;
-  memcpy(ja.pa.p, projection, sizeof(ja.pa.p));
-  ja.pa.degree = degree;
-  ja.c[0] = julia_c[0];
-  ja.c[1] = julia_c[1];
-  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
-  g_interior_level.store(0, std::memory_order_relaxed);
-  g_last_draw_kernel.store(lockstep ? 13 : 12, std::memory_order_relaxed);
-  return (int) cb::launch_draw_julia(ja, lockstep, reinterpret_cast<hipStream_t>(stream));
+  return draw_plot(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads, samples_per_thread,
+                   d_counters, kernel_variant, stream, nullptr);
 }
 
 int cb_renderer_set_julia(cb_renderer *r, const double projection[8], const double julia_c[2]) {
@@ -1027,7 +982,7 @@ int cb_renderer_julia(const cb_renderer *r, double out[2]) {
   return 1;
 }
 
-// ---- palette render (draw_palette.hip; include/cudabrot_amd.h, "Palette render") ------------------------------------
+// ---- palette render (draw_plot.hip; include/cudabrot_amd.h, "Palette render") ---------------------------------------
 
 namespace {
 
@@ -1055,41 +1010,8 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
   if (!d_lut || !palette_entries_ok(n_entries, iterations)) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & CB_KERNEL_FORMULA_MASK) != 0) {
-    return draw_formula(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
-                        d_counters, kernel_variant, stream);
-  }
-  // the variant rules of the projected and Julia draws: a base of two, the Burning Ship or a degree, not both, no anti
-  const bool power = (kernel_variant & CB_KERNEL_POWER_MASK) != 0;
-  const int degree = power ? (kernel_variant & CB_KERNEL_POWER_MASK) >> 12 : 2;
-  const int base_variant = kernel_variant & ~CB_KERNEL_POWER_MASK;
-  const bool ship = (base_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  if (!focus_variant_ok(base_variant) || (power && (degree < CB_POWER_MIN || degree > CB_POWER_MAX || ship))) {
-    return (int) hipErrorInvalidValue;
-  }
-  cb::PaletteArgs pl;
-  memset(&pl, 0, sizeof(pl));
-  cb::ProjectArgs &pa = pl.ja.pa;
-  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  pa.d.burning_ship = ship ? 1 : 0;
-  memcpy(pa.p, projection, sizeof(pa.p));
-  pa.degree = degree;
-  if (julia_c) {
-    pl.julia = 1;
-    pl.ja.c[0] = julia_c[0];
-    pl.ja.c[1] = julia_c[1];
-  }
-  pl.lut = d_lut;
-  pl.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
-  const bool lockstep = (base_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
-  // the interior map: a sampled c with the Mandelbrot step, under cb_draw_buddhabrot_projected's rule
-  g_interior_level.store(0, std::memory_order_relaxed);
-  if (!julia_c && !power && pa.d.long_steps > 0) {
-    const int rc = attach_interior_map(pa.d, kernel_variant);
-    if (rc) return rc;
-  }
-  g_last_draw_kernel.store(lockstep ? 15 : 14, std::memory_order_relaxed);
-  return (int) cb::launch_draw_palette(pl, lockstep, reinterpret_cast<hipStream_t>(stream));
+  return draw_plot(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
+                   d_counters, kernel_variant, stream, nullptr);
 }
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {

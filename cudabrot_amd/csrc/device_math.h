@@ -151,7 +151,7 @@ __device__ __forceinline__ double mandel_step2_ship(double CR, double CI, double
 // The power is d - 1 multiplications by z, left to right: w <- w * z with
 //   t = wi*i; nr = fma(wr, r, -t); s = wi*r; ni = fma(wr, i, s)
 // then r' = cr + wr, i' = ci + wi, m = fma(i', i', r'*r').  4 (d - 1) multiplies and FMAs, 2 adds, 2 for m.
-// Written twice, so that the Multibrot lock-step kernel and product kernel of draw_project.hip are two writings of the
+// Written twice, so that the Multibrot lock-step kernel and product kernel of draw_plot.hip are two writings of the
 // definition: power_step is the run-time loop, power_step_n<D> the same sequence unrolled by the template.
 __device__ __forceinline__ double power_step(int d, double cr, double ci, double &r, double &i) {
   double wr = r, wi = i;
@@ -245,7 +245,7 @@ __device__ __forceinline__ double formula_step(int f, double cr, double ci, doub
       nr = cr + t;
       ni = __builtin_fma(-(__builtin_fabs(r) + __builtin_fabs(r)), i, ci);
       break;
-    default:  // CB_FORMULA_CELTIC_TRICORN: launch_draw_formula lets no other code through
+    default:  // CB_FORMULA_CELTIC_TRICORN: launch_draw_plot lets no other code through
       nr = cr + __builtin_fabs(t);
       ni = __builtin_fma(-(r + r), i, ci);
       break;

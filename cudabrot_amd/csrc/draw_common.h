@@ -1,6 +1,6 @@
 // draw_common.h -- pieces shared by all draw kernels: the asm step and the chunk helpers of draw_wave.hip and
 // draw_wide.hip, the canvas, the generator's load and store.  What the kernels with one reference thread per lane share
-// beyond that (kernels.hip, draw_anti.hip, draw_focus.hip, draw_project.hip, draw_julia.hip) is in draw_rounds.h.
+// beyond that (kernels.hip, draw_anti.hip, draw_focus.hip, draw_plot.hip) is in draw_rounds.h.
 #pragma once
 
 #include "device_math.h"

@@ -1,7 +1,7 @@
-// draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_project.hip, draw_julia.hip,
-// draw_palette.hip, draw_formula.hip; include/cudabrot_amd.h, "Projected render"): the four fused operations of a plotted
-// point, the plot of a replayed point for the modes of draw_rounds.h's scheduler, the steps those modes are instantiated
-// with, and the modes themselves -- a sampled c, a fixed one, and the palette render's mode, which builds on either.
+// draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_plot.hip; include/cudabrot_amd.h,
+// "Projected render"): the four fused operations of a plotted point, the plot of a replayed point for the modes of
+// draw_rounds.h's scheduler, the steps those modes are instantiated with, and the modes themselves -- a sampled c, a fixed
+// one, and the palette render's mode, which builds on either.
 #pragma once
 
 #include <type_traits>
@@ -21,7 +21,7 @@ __device__ __forceinline__ double project_point(double pz_re, double pz_im, doub
 
 // What the product kernels share: the plot of a replayed point.  (ku, kv) is c's part of (u, v).
 struct Plot {
-  const ProjectArgs &pa;
+  const PlotArgs &pa;
   const Canvas cv;
   double ku = 0.0, kv = 0.0;
 
@@ -74,7 +74,7 @@ __device__ __forceinline__ unsigned long long palette_weight(uint32_t entry, int
   return (unsigned long long) ((entry >> (8 * plane)) & 0xffu);
 }
 
-// ---- the plot modes of draw_rounds.h's scheduler (draw_project.hip, draw_julia.hip, draw_palette.hip, draw_formula.hip) --
+// ---- the plot modes of draw_rounds.h's scheduler (draw_plot.hip) ---------------------------------------------------------
 
 namespace {
 
@@ -94,7 +94,7 @@ __device__ __forceinline__ bool interior_marked(const DrawArgs &a, double cr, do
 }
 
 
-// The mode of a render that samples c (draw_project.hip has the commentary): z_0 = c, the plot's constant from the sample.
+// The mode of a render that samples c (draw_plot.hip has the commentary): z_0 = c, the plot's constant from the sample.
 template <class Step>
 struct PlotMode {
   Plot plot;
@@ -124,7 +124,7 @@ struct PlotMode {
 };
 
 
-// The mode of a Julia render (draw_julia.hip has the commentary): z_0 = the sample, c and the plot's constant fixed.
+// The mode of a Julia render (draw_plot.hip has the commentary): z_0 = the sample, c and the plot's constant fixed.
 template <class Step>
 struct JuliaMode {
   Plot plot;
@@ -149,7 +149,7 @@ struct JuliaMode {
 };
 
 
-// The mode of a palette render (draw_palette.hip has the commentary): either mode above with another ESCAPED, which loads
+// The mode of a palette render (draw_plot.hip has the commentary): either mode above with another ESCAPED, which loads
 // the orbit's entry once, and another plot, which adds each non-zero weight to the pixel of its plane.
 template <class Step, bool kJulia>
 struct PaletteMode {

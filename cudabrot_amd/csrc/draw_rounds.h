@@ -1,5 +1,5 @@
 // draw_rounds.h -- what the kernels with one reference thread per lane share (kernels.hip's draw_simple_kernel,
-// draw_anti.hip, draw_focus.hip, draw_project.hip, draw_julia.hip, draw_palette.hip): the per-lane counters, the uniform
+// draw_anti.hip, draw_focus.hip, draw_plot.hip): the per-lane counters, the uniform
 // sample, the reference's escape-index loop for the lock-step kernels, and the round scheduler of the product kernels
 // with the escape accounting of its modes.
 #pragma once

@@ -233,55 +233,40 @@ struct FocusArgs {
 };
 hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream);
 
-// draw_project.hip: the projected render (include/cudabrot_amd.h, "Projected render").  p is the matrix P[2][4], rows
-// (u, v), columns (z_re, z_im, c_re, c_im), finite.  degree picks the step: 2, the reference's (d.burning_ship: its Burning
-// Ship variant), or CB_POWER_MIN .. CB_POWER_MAX, the Multibrot step z <- z^degree + c ("Multibrot step"), which has no
-// Burning Ship variant; anything else: hipErrorInvalidValue, nothing launched.  d carries the canvas (the (u, v) window),
-// the iteration control, the generators, the counters, burning_ship and the interior map (null: none; read by the product
-// kernel with the Mandelbrot step only); its workspace and carry fields are not read.
-struct ProjectArgs {
+// draw_plot.hip: the plotted renders -- projected ("Projected render" of include/cudabrot_amd.h), Multibrot ("Multibrot
+// step"), Julia ("Julia render"), palette ("Palette render") and formula ("Formula step") -- are one launch with a step, a
+// source of c and a sink.
+//   d        the canvas (the (u, v) window), the iteration control, the generators, the counters and burning_ship; its
+//            workspace and carry fields are not read.  d.interior_map (null: none) is read by the product kernel with
+//            the Mandelbrot step on a sampled c only: julia == 0, formula == 0, degree == 2, no Burning Ship.
+//   p        the matrix P[2][4], rows (u, v), columns (z_re, z_im, c_re, c_im), finite.  Always read.
+//   The step: formula != 0 is the code CB_FORMULA_TRICORN .. CB_FORMULA_MAX (0: not a formula), and then degree must be 2
+//            and d.burning_ship 0: a formula is a step of its own.  Else degree 2 is the reference's step (d.burning_ship:
+//            its Burning Ship variant) and CB_POWER_MIN .. CB_POWER_MAX the Multibrot step z <- z^degree + c, which has no
+//            Burning Ship variant.
+//   The source of c: julia == 0 samples c from the stream (z_0 = c); julia != 0 takes the fixed c = (c[0], c[1]), both in
+//            [-2, 2], and the sample of the stream is z_0.  c is read only when julia != 0.
+//   The sink: palette == 0 adds 1 per point to the one plane d.hist; palette != 0 makes d.hist three planes plane_pixels
+//            counters apart and lut the table on the device, d.max_iter entries -- which must be 1 ..
+//            CB_PALETTE_MAX_ENTRIES -- of which entry k carries the weights of an orbit with escape index k.  lut and
+//            plane_pixels are read only when palette != 0.
+// hipErrorInvalidValue, nothing launched: a degree outside {2, CB_POWER_MIN .. CB_POWER_MAX}; a degree other than 2 or
+// the Burning Ship beside a formula; the Burning Ship beside a degree other than 2; julia with a c outside [-2, 2], a NaN
+// included; palette with a null table or a max_iter outside 1 .. CB_PALETTE_MAX_ENTRIES; a formula code above
+// CB_FORMULA_MAX or below 0.  lockstep: the definition, one lane per reference thread -- the formula's kernel, else the
+// palette's, else the Julia render's, else the Multibrot step's, else the projected render's.
+struct PlotArgs {
   DrawArgs d;
   double p[8];
   int degree;
-};
-hipError_t launch_draw_project(const ProjectArgs &a, bool lockstep, hipStream_t stream);
-
-// draw_julia.hip: the Julia render (include/cudabrot_amd.h, "Julia render").  pa is a projected render's arguments --
-// canvas, iteration control, generators, counters, burning_ship, the matrix and the degree, with the same rule for the
-// degree -- of which the interior map is not read; c is the fixed parameter (c_re, c_im), both in [-2, 2]: anything else,
-// a NaN included, is hipErrorInvalidValue, nothing launched.  The sample of the stream is z_0.
-struct JuliaArgs {
-  ProjectArgs pa;
   double c[2];
-};
-hipError_t launch_draw_julia(const JuliaArgs &a, bool lockstep, hipStream_t stream);
-
-// draw_palette.hip: the palette render (include/cudabrot_amd.h, "Palette render").  ja is a Julia render's arguments, of
-// which c is read only when julia != 0; julia == 0 samples c as a projected render does, interior map included (read by
-// the product kernel with the Mandelbrot step only).  ja.pa.d.hist is three planes of plane_pixels counters each; lut is
-// the table on the device, ja.pa.d.max_iter entries -- which must be 1 .. CB_PALETTE_MAX_ENTRIES -- of which entry k
-// carries the weights of an orbit with escape index k.  A null table, a max_iter out of that range and whatever
-// launch_draw_project and launch_draw_julia refuse: hipErrorInvalidValue, nothing launched.
-struct PaletteArgs {
-  JuliaArgs ja;
   int julia;
   const uint32_t *lut;
   unsigned long long plane_pixels;
-};
-hipError_t launch_draw_palette(const PaletteArgs &a, bool lockstep, hipStream_t stream);
-
-// draw_formula.hip: the formula step (include/cudabrot_amd.h, "Formula step") on a projected render, a Julia render or
-// a palette render of either.  pl is a palette render's arguments with degree 2 and no Burning Ship: of it, c is read
-// only when pl.julia != 0, and lut and plane_pixels only when palette != 0 -- else pl.ja.pa.d.hist is one plane.  The
-// interior map is never read.  formula is the code, CB_FORMULA_TRICORN .. CB_FORMULA_MAX.  hipErrorInvalidValue, nothing
-// launched: any other code, a degree other than 2 or the Burning Ship with it, and whatever launch_draw_julia (julia)
-// and launch_draw_palette (palette) refuse.
-struct FormulaArgs {
-  PaletteArgs pl;
   int formula;
   int palette;
 };
-hipError_t launch_draw_formula(const FormulaArgs &a, bool lockstep, hipStream_t stream);
+hipError_t launch_draw_plot(const PlotArgs &a, bool lockstep, hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

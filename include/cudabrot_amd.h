@@ -161,7 +161,7 @@ typedef struct {
  * with CB_KERNEL_FLAG_BURNING_SHIP, CB_KERNEL_FLAG_ANTI or a base variant other than the two above; a degree given to
  * cb_draw_buddhabrot, cb_draw_buddhabrot_channels, cb_focus_probe, cb_draw_buddhabrot_focus, cb_renderer_set_focus, or to
  * cb_renderer_render_passes on a renderer without a projection.
- * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, one instance per degree with the step unrolled, lanes refilled from
+ * Two kernels (draw_plot.hip): CB_KERNEL_DEFAULT, one instance per degree with the step unrolled, lanes refilled from
  * their own subsequence, with the exact-periodicity early-out; CB_KERNEL_SIMPLE, the definition in lock-step with the
  * degree a run-time argument.  Identical histograms, generator states and counters (but skipped_steps).
  * The -s buffer records the degree no more than it records the plane: resuming a buffer with another degree adds two
@@ -216,7 +216,7 @@ typedef struct {
  * CB_KERNEL_FLAG_DRAIN, CB_KERNEL_POWER(d) or a base variant other than the two above; a code given to
  * cb_draw_buddhabrot, cb_draw_buddhabrot_channels, cb_focus_probe, cb_draw_buddhabrot_focus, cb_renderer_set_focus, or to
  * cb_renderer_render_passes on a plain, channel or focused renderer.
- * Two kernels (draw_formula.hip): CB_KERNEL_DEFAULT, one instance per code, per source of c (sampled, fixed) and per
+ * Two kernels (draw_plot.hip): CB_KERNEL_DEFAULT, one instance per code, per source of c (sampled, fixed) and per
  * sink (one plane, the palette's three), lanes refilled from their own subsequence, with the exact-periodicity
  * early-out; CB_KERNEL_SIMPLE, the definition in lock-step with code, source and sink run-time arguments.  Identical
  * histograms, generator states and counters (but skipped_steps).
@@ -411,7 +411,7 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
  *   (or the reverse).  +0 and -0 compare equal in `x < min`, and x - min differs at most in the sign of a zero, which
  *   (int) (x / delta) maps to pixel 0 either way: a +-0 difference cannot move a bin.
  *
- * Two kernels (draw_project.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence, with the interior map
+ * Two kernels (draw_plot.hip): CB_KERNEL_DEFAULT, lanes refilled from their own subsequence, with the interior map
  * (Mandelbrot step only) and the exact-periodicity early-out, and CB_KERNEL_SIMPLE, the definition in lock-step;
  * optionally | CB_KERNEL_FLAG_BURNING_SHIP; any other variant, CB_KERNEL_FLAG_ANTI included, is hipErrorInvalidValue.
  * (| CB_KERNEL_POWER(d) instead of the Burning Ship's flag: the Multibrot step and its two kernels, "Multibrot step";
@@ -456,11 +456,11 @@ int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_
  *   Every visited point is finite: |z_0|^2 <= 8, so |z_1| <= 8^(d/2) + |c| <= 4096 + 2 sqrt 2, and every later visited
  *   point follows a point with |z|^2 <= 4.
  *
- * Two kernels (draw_julia.hip): CB_KERNEL_DEFAULT, one instance per step, lanes refilled from their own subsequence, with
+ * Two kernels (draw_plot.hip): CB_KERNEL_DEFAULT, one instance per step, lanes refilled from their own subsequence, with
  * the exact-periodicity early-out -- all that retires a Julia interior: attracting cycles land on an exact fp64 cycle
  * quickly -- and CB_KERNEL_SIMPLE, the definition in lock-step with step and degree run-time arguments; optionally
- * | CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d), or | CB_KERNEL_FORMULA(f) instead of either ("Formula step",
- * draw_formula.hip); any other variant, CB_KERNEL_FLAG_ANTI included, is
+ * | CB_KERNEL_FLAG_BURNING_SHIP or | CB_KERNEL_POWER(d), or | CB_KERNEL_FORMULA(f) instead of either ("Formula step");
+ * any other variant, CB_KERNEL_FLAG_ANTI included, is
  * hipErrorInvalidValue, with nothing launched or written.  Identical histograms, generator states and counters (but
  * skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete when it ends.  The -s buffer records
  * c no more than it records the plane or the degree. */
@@ -504,11 +504,11 @@ int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist
  *   ratio between a pixel's planes is its colour; no percentile stretch.  The file is the binary PPM of "Colour image"
  *   step 5 below: P6, 65535, big-endian R, G, B per pixel, rows as in the PGM.
  *
- * Two kernels (draw_palette.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c (sampled, fixed), lanes
+ * Two kernels (draw_plot.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c (sampled, fixed), lanes
  * refilled from their own subsequence with the exact-periodicity early-out and, for the Mandelbrot step on a sampled c,
  * the interior map under cb_draw_buddhabrot_projected's rule; CB_KERNEL_SIMPLE, the definition in lock-step.  Variants
  * are cb_draw_buddhabrot_julia's (| CB_KERNEL_FLAG_BURNING_SHIP, | CB_KERNEL_POWER(d) or | CB_KERNEL_FORMULA(f), the last
- * with the two kernels of draw_formula.hip).  Identical histograms,
+ * with the two kernels of "Formula step").  Identical histograms,
  * generator states and counters (but skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete
  * when it ends.  The -s buffer has three planes and records the table no more than it records the plane, the degree or
  * c. */
@@ -763,12 +763,12 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * 0 none yet, 1 draw_wave_kernel (four waves per SIMD), 2 draw_wide_kernel (two waves per SIMD, runs beside the
  * scatter), 3 the lock-step baseline, 4 the anti product kernel (draw_anti_kernel), 5 the anti lock-step kernel, 6 the
  * focus product kernel (draw_focus_kernel: cb_focus_probe and cb_draw_buddhabrot_focus), 7 the focus lock-step kernel,
- * 8 the projection product kernel (draw_project_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
- * 10 the Multibrot product kernel (draw_power_kernel, the projected render's with the power step:
+ * 8 the projection product kernel (draw_plot_kernel: cb_draw_buddhabrot_projected), 9 the projection lock-step kernel,
+ * 10 the Multibrot product kernel (draw_plot_kernel, the projected render's with the power step:
  * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel, 12 the Julia product kernel
- * (draw_julia_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
- * (draw_palette_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel, 16 the formula product kernel
- * (draw_formula_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel.
+ * (draw_plot_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
+ * (draw_plot_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel, 16 the formula product kernel
+ * (draw_plot_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

@@ -1,4 +1,4 @@
-"""The kernels on the round scheduler (draw_rounds.h: draw_anti_kernel, draw_focus_kernel, draw_project_kernel) against
+"""The kernels on the round scheduler (draw_rounds.h: draw_anti_kernel, draw_focus_kernel, draw_plot_kernel) against
 a recording of themselves, `skipped_steps` included.
 
 Every other comparison of these kernels leaves `skipped_steps` out, because product and lock-step kernels legitimately

@@ -1,8 +1,8 @@
-"""What the compiler makes of the kernels with one reference thread per lane (draw_anti.hip, draw_focus.hip,
-draw_project.hip: the modes of draw_rounds.h's scheduler and their lock-step twins), checked where it is built: hipcc
-cross-compiles for gfx950 without a GPU and reports every kernel's resources.  DESIGN.md sections 4.9 to 4.11 claim no
-spill, no scratch, no AGPRs and no LDS for every instance, and per file the registers and waves per SIMD below.
-draw_project.hip also holds the Multibrot kernels: tests/test_power_kernels_resources.py."""
+"""What the compiler makes of the kernels with one reference thread per lane (draw_anti.hip, draw_focus.hip: the modes
+of draw_rounds.h's scheduler and their lock-step twins), checked where it is built: hipcc cross-compiles for gfx950
+without a GPU and reports every kernel's resources.  DESIGN.md sections 4.9 and 4.10 claim no spill, no scratch, no
+AGPRs and no LDS for every instance, and per file the registers and waves per SIMD below.  The plotted renders' kernels
+(draw_plot.hip): tests/test_plot_kernels_resources.py."""
 
 import os
 import re
@@ -50,8 +50,6 @@ FILES = {
                   lambda k: int(k["VGPRs"]) <= 64 and int(k["Occupancy [waves/SIMD]"]) == 8, 3),
     # (cells, histogram), (uniform, mask), (uniform, histogram), each for both steps
     "draw_focus": ("draw_focus_kernel", 6, at_most(128, 4), "draw_focus_simple_kernel", at_most(128, 4), 7),
-    # and the seven Multibrot kernels (tests/test_power_kernels_resources.py)
-    "draw_project": ("draw_project_kernel", 2, at_most(128, 4), "draw_project_simple_kernel", at_most(128, 4), 10),
 }
 
 

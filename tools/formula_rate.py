@@ -1,8 +1,8 @@
 """Formula-render throughput through cb_renderer: samples per second and executed steps per sample on a
 4096^2 canvas over [-2, 2]^2 with the identity matrix, 262144 threads, -m 2000, -c 20 (the method of
-tools/julia_rate.py), of each of the five product instances of draw_formula_kernel with a sampled c and one plane
-(draw_formula.hip), of the lock-step kernel (with the tricorn), and beside them, as the yardstick, of the Burning Ship
-instance of draw_project_kernel on the same shape: the closest existing kernel -- the same scheduler, no rejection, no
+tools/julia_rate.py), of each of the five product instances of draw_plot_kernel over FormulaOrbit<F> with a sampled c and one plane
+(draw_plot.hip), of the lock-step kernel (with the tricorn), and beside them, as the yardstick, of the Burning Ship
+instance of draw_plot_kernel on the same shape: the closest existing kernel -- the same scheduler, no rejection, no
 interior map -- whose assembly the formula render leaves alone.  Every row is a process of its own under its own time
 limit (a child of this script); it makes one warm-up pass and then three timed repetitions, finish() included, and prints
 one JSON line with the three rates and their median.  The first child that fails or runs out of time ends the script:

@@ -16,8 +16,8 @@ and demands identical histograms and counters.
     ANTI=1 python tools/gpu_fuzz.py ...            the anti-Buddhabrot (CB_KERNEL_FLAG_ANTI): draw_anti_kernel against
                                                    draw_anti_simple_kernel, generator states compared as well; M from
                                                    the edges of its rounds (12 steps) and chunks (60 steps)
-    POWER=1 python tools/gpu_fuzz.py ...           the Multibrot render (CB_KERNEL_POWER): draw_power_kernel<D> against
-                                                   draw_power_simple_kernel (draw_project.hip) -- random degree,
+    POWER=1 python tools/gpu_fuzz.py ...           the Multibrot render (CB_KERNEL_POWER): draw_plot_kernel (PowerOrbit<D>) against
+                                                   draw_power_simple_kernel (draw_plot.hip) -- random degree,
                                                    shapes and matrices, generator states compared as well
 """
 import os

@@ -1,6 +1,6 @@
 """Julia-render throughput through cb_renderer: samples per second and executed steps per sample on a
 4096^2 canvas over [-2, 2]^2 with the identity matrix, 262144 threads, -c 20, -m 20000, of the product kernel
-(draw_julia_kernel, draw_julia.hip) and its lock-step twin at c = (-1, 0) and c = (-0.8, 0.156), and of the projected
+(draw_plot_kernel with a fixed c, draw_plot.hip) and its lock-step twin at c = (-1, 0) and c = (-0.8, 0.156), and of the projected
 render's product kernel on the plane (zr, zi) (c = "none": the nearest workload that samples c).  Every measurement is a
 process of its own under its own time limit (a child of this script); it makes one warm-up pass and then three timed
 repetitions, finish() included, and prints one JSON line with the three rates and their median.  The first child that

@@ -1,5 +1,5 @@
 """Palette-render throughput through cb_renderer: samples per second of the palette product kernel
-(draw_palette_kernel, draw_palette.hip) with one, two and three non-zero planes, beside cb_draw_buddhabrot_projected's
+(draw_plot_kernel with a table, draw_plot.hip) with one, two and three non-zero planes, beside cb_draw_buddhabrot_projected's
 product kernel on the same shape -- which this render leaves alone: the yardstick.  4096^2 canvas over [-2, 2]^2, the
 identity matrix, 262144 threads, -c 20, -m 2000 by default; tables R = 1 / R = G = 1 / R = G = B = 1 for every k, so
 each in-canvas point costs one, two or three atomics and the work is otherwise the projected render's.  Every measurement

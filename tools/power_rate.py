@@ -1,6 +1,6 @@
 """Multibrot-render throughput through cb_renderer: samples per second and executed steps per sample on a
-4096^2 canvas over [-2, 2]^2 with the identity matrix, 262144 threads, -c 20, of the product kernel (draw_power_kernel<D>,
-draw_project.hip) and its lock-step twin, at d = 3 and d = 8 and -m 500 and -m 20000.  Every measurement is a process of
+4096^2 canvas over [-2, 2]^2 with the identity matrix, 262144 threads, -c 20, of the product kernel (draw_plot_kernel over
+PowerOrbit<D>, draw_plot.hip) and its lock-step twin, at d = 3 and d = 8 and -m 500 and -m 20000.  Every measurement is a process of
 its own under its own time limit (a child of this script); it makes one warm-up pass and then three timed repetitions,
 finish() included, and prints one JSON line with the three rates and their median.  The first child that fails or runs
 out of time ends the script: nothing more is started on the device after it.
