@@ -4,23 +4,12 @@ read from the `"projection"` and `"formula"` lines that --stats prints before an
 
 import json
 import os
-import subprocess
 
 import pytest
 
+from plot_harness import exe, run  # noqa: F401
+
 NAMES = ["tricorn", "celtic", "buffalo", "perpendicular", "celtic-tricorn"]
-
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, **kw)
 
 
 BAD = "Invalid formula (want tricorn, celtic, buffalo, perpendicular or celtic-tricorn): "

@@ -1,6 +1,7 @@
 """The formula step (include/cudabrot_amd.h, "Formula step") without a GPU: the restatement's five steps
-(tests/formula_reference.c) against its plain and Burning Ship steps through the identities that define the family, bit
-for bit; the header's text and constants; the Python constants."""
+(tests/plot_reference.c) against its plain and Burning Ship steps through the identities that define the family, bit
+for bit -- two settings of the one step function, a formula code against PLAIN (code 0) or SHIP (code 0 with the ship
+flag); the header's text and constants; the Python constants."""
 
 import os
 import re
@@ -9,15 +10,15 @@ import struct
 import numpy as np
 import pytest
 
-import formula_reference as formula
+import plot_reference as plot
+from plot_harness import ref  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T, C, B, P, CT = (formula.NAMES[n] for n in ("tricorn", "celtic", "buffalo", "perpendicular", "celtic-tricorn"))
+T, C, B, P, CT = (plot.NAMES[n] for n in ("tricorn", "celtic", "buffalo", "perpendicular", "celtic-tricorn"))
 
 
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return formula.load(tmp_path_factory.mktemp("formula_ref"))
+def step(ref, f, cr, ci, r, i):
+    return plot.step(ref, cr, ci, r, i, formula=f)
 
 
 def bits(x):
@@ -57,23 +58,23 @@ def test_enough_inputs_on_both_sides_of_t():
 
 def test_tricorn_is_the_plain_step_of_the_conjugate(ref):
     for cr, ci, r, i in INPUTS:
-        assert same(formula.step(ref, T, cr, ci, r, i), formula.step(ref, formula.PLAIN, cr, ci, r, -i)), (cr, ci, r, i)
+        assert same(step(ref, T, cr, ci, r, i), step(ref, plot.PLAIN, cr, ci, r, -i)), (cr, ci, r, i)
 
 
 def test_perpendicular_is_the_plain_step_of_minus_abs_r(ref):
     for cr, ci, r, i in INPUTS:
-        assert same(formula.step(ref, P, cr, ci, r, i), formula.step(ref, formula.PLAIN, cr, ci, -abs(r), i)), (cr, ci, r, i)
+        assert same(step(ref, P, cr, ci, r, i), step(ref, plot.PLAIN, cr, ci, -abs(r), i)), (cr, ci, r, i)
 
 
 def test_celtic_is_plain_and_buffalo_is_ship_where_t_is_not_negative(ref):
     seen = 0
     for cr, ci, r, i in INPUTS:
-        t = formula.step(ref, formula.PLAIN, 0.0, 0.0, r, i)[0]  # nr = 0 + t: the step's own rounded t (a -0 reads +0)
+        t = step(ref, plot.PLAIN, 0.0, 0.0, r, i)[0]  # nr = 0 + t: the step's own rounded t (a -0 reads +0)
         if not t >= 0.0 or bits(t) == bits(-0.0):
             continue
         seen += 1
-        assert same(formula.step(ref, C, cr, ci, r, i), formula.step(ref, formula.PLAIN, cr, ci, r, i)), (cr, ci, r, i)
-        assert same(formula.step(ref, B, cr, ci, r, i), formula.step(ref, formula.SHIP, cr, ci, r, i)), (cr, ci, r, i)
+        assert same(step(ref, C, cr, ci, r, i), step(ref, plot.PLAIN, cr, ci, r, i)), (cr, ci, r, i)
+        assert same(step(ref, B, cr, ci, r, i), step(ref, plot.SHIP, cr, ci, r, i)), (cr, ci, r, i)
     assert seen > 1000
 
 
@@ -81,21 +82,21 @@ def test_celtic_and_buffalo_differ_from_them_where_t_is_negative(ref):
     differ = 0
     for cr, ci, r, i in INPUTS[:3000]:
         if r * r - i * i < -0.01:
-            differ += not same(formula.step(ref, C, cr, ci, r, i), formula.step(ref, formula.PLAIN, cr, ci, r, i))
-            assert formula.step(ref, C, cr, ci, r, i)[1:2] == formula.step(ref, formula.PLAIN, cr, ci, r, i)[1:2]  # ni is
+            differ += not same(step(ref, C, cr, ci, r, i), step(ref, plot.PLAIN, cr, ci, r, i))
+            assert step(ref, C, cr, ci, r, i)[1:2] == step(ref, plot.PLAIN, cr, ci, r, i)[1:2]  # ni is
     assert differ > 500
 
 
 def test_celtic_tricorn_is_celtic_of_the_conjugate(ref):
     for cr, ci, r, i in INPUTS:
-        assert same(formula.step(ref, CT, cr, ci, r, i), formula.step(ref, C, cr, ci, r, -i)), (cr, ci, r, i)
+        assert same(step(ref, CT, cr, ci, r, i), step(ref, C, cr, ci, r, -i)), (cr, ci, r, i)
 
 
 def test_the_five_steps_are_five_different_maps(ref):
     # both signs of r, of i and of t: every sign and magnitude in the table shows on some point
     points = [(sr * a, si * b) for a, b in ((0.6, 0.9), (0.9, 0.6)) for sr in (1, -1) for si in (1, -1)]
-    maps = {tuple(formula.step(ref, f, 0.3, -0.2, r, i) for r, i in points)
-            for f in (formula.PLAIN, formula.SHIP, T, C, B, P, CT)}
+    maps = {tuple(step(ref, f, 0.3, -0.2, r, i) for r, i in points)
+            for f in (plot.PLAIN, plot.SHIP, T, C, B, P, CT)}
     assert len(maps) == 7
 
 
@@ -159,8 +160,8 @@ def test_python_constants():
         assert getattr(capi, name) == value
     assert capi.CB_KERNEL_FORMULA_MASK == 0xF0000
     assert [capi.CB_KERNEL_FORMULA(f) for f in range(1, 6)] == [0x10000, 0x20000, 0x30000, 0x40000, 0x50000]
-    assert capi.CB_FORMULA_NAMES == formula.NAMES
-    for name, code in formula.NAMES.items():
+    assert capi.CB_FORMULA_NAMES == plot.NAMES
+    for name, code in plot.NAMES.items():
         assert capi.CB_KERNEL_FORMULA(name) == code << 16
     for bad in (0, 6, -1, 16, "mandelbrot", "Tricorn"):
         with pytest.raises(ValueError):

@@ -1,5 +1,5 @@
 """The formula render (include/cudabrot_amd.h, "Formula step") on the GPU.  Every case three ways -- the product kernel
-(cb_debug_last_draw_kernel 16), the lock-step kernel (17), the CPU restatement (tests/formula_reference.c) -- bit for bit
+(cb_debug_last_draw_kernel 16), the lock-step kernel (17), the CPU restatement (tests/plot_reference.c) -- bit for bit
 on histogram, generator states and every counter but skipped_steps:
 
   1. every formula, whole and ragged grids, two launches on the same generators;
@@ -15,105 +15,30 @@ on histogram, generator states and every counter but skipped_steps:
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import formula_reference as formula
+import plot_harness
+import plot_reference as plot
 from conftest import read_state_file
-from palette_reference import demo_table
+from plot_harness import INVALID, SAME, SQUARE, exe, gpu_launches, omp_threads, planar_states, ref  # noqa: F401
+from plot_harness import gpu_run as run
+from plot_reference import demo_table
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 16, 17
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
 CROPPED = (-1.3, 0.9, -0.7, 0.55)
-INVALID = 1  # hipErrorInvalidValue
 C_JULIA, C_EDGE = (-0.8, 0.156), (2.0, -2.0)
-NAMES = list(formula.NAMES)
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return formula.load(tmp_path_factory.mktemp("formula_ref"))
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
-def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c=None, lut=None,
-                 projection=formula.IDENTITY):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) through the entry
-    point the arguments pick -- cb_draw_buddhabrot_palette with a table, cb_draw_buddhabrot_julia with a c, else
-    cb_draw_buddhabrot_projected -> (u64 hist [h, w] or [3, h, w], counters dict, cb_debug_last_draw_kernel, generator
-    states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    planes = 1 if lut is None else 3
-    out = torch.zeros(planes * w * h, dtype=torch.int64, device=dev)
-    if lut is not None:
-        table = np.ascontiguousarray(lut, dtype=np.uint32)
-        d_lut = torch.from_numpy(table.view(np.int32).copy()).to(dev)
-    for samples in launches:
-        if lut is not None:
-            cb.draw_buddhabrot_palette(dims, out.data_ptr(), it, projection, c, d_lut.data_ptr(), table.size,
-                                       states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
-        elif c is not None:
-            cb.draw_buddhabrot_julia(dims, out.data_ptr(), it, projection, c, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), variant, stream)
-        else:
-            cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, projection, states.data_ptr(), threads, samples,
-                                         counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    hist = out.cpu().numpy().view(np.uint64)
-    return (hist.reshape(h, w) if lut is None else hist.reshape(3, h, w)), cnt, kernel, states.cpu().numpy().view(np.uint32)
+NAMES = list(plot.NAMES)
 
 
 def three_ways(cb, ref, oracle, name, w=64, h=64, box=SQUARE, max_iter=500, min_iter=20, threads=4096, launches=(50,),
-               c=None, lut=None, projection=formula.IDENTITY, extra=None):
-    """Product == lock-step == restatement -> (restatement's hist, its counters, the product's counters, the lock-step
-    kernel's counters)."""
-    launches = list(launches)
-    st = oracle.init_states(1337, 0, threads)
-    want, wc = formula.draw(ref, w, h, max_iter, min_iter, threads, launches, name, c, lut, projection, box=box,
-                            omp_threads=omp_threads(), states=st, extra=extra)
-    assert wc["samples"] == threads * sum(launches) and wc["rejected"] == 0 and int(want.sum()) == wc["increments"]
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches,
-                                                   base | cb.CB_KERNEL_FORMULA(name), c, lut, projection)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert np.array_equal(hist, want), kernel
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        assert cb.lib.cb_debug_interior_map_level() == 0
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    return want, wc, got[PRODUCT], got[LOCKSTEP]
+               c=None, lut=None, projection=plot.IDENTITY):
+    """Product == lock-step == restatement, without an interior map -> plot_harness.ThreeWays."""
+    return plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), 0, w, h, box, max_iter, min_iter, threads, launches,
+                                   formula=name, c=c, lut=lut, projection=projection)
 
 
 # ---- 1. every formula ---------------------------------------------------------------------------------------------------
@@ -124,7 +49,7 @@ def three_ways(cb, ref, oracle, name, w=64, h=64, box=SQUARE, max_iter=500, min_
 def test_every_formula(cb, ref, oracle, name, threads, launches):
     """64 x 64 over [-2, 2]^2, -m 500 -c 20: checked with the restatement on the CPU before the shape was fixed, every
     formula meets the condition below at both grids; none needed another -m or -c."""
-    _, wc, _, _ = three_ways(cb, ref, oracle, name, threads=threads, launches=launches)
+    _, wc, _, _, _ = three_ways(cb, ref, oracle, name, threads=threads, launches=launches)
     assert wc["never_escaped"] > 0 and wc["too_fast"] > 0 and wc["recorded"] > 0 and wc["increments"] > wc["recorded"]
     assert wc["rejected"] == 0
 
@@ -138,7 +63,7 @@ EDGES = [(m, 0) for m in (0, 1, 11, 12, 13, 59, 60, 61, 120, 121)] + [(61, 60), 
 @pytest.mark.parametrize("max_iter,min_iter", EDGES, ids=["m%d_c%d" % e for e in EDGES])
 @pytest.mark.parametrize("name", ["tricorn", "buffalo"])
 def test_round_and_chunk_edges(cb, ref, oracle, name, max_iter, min_iter):
-    _, wc, _, _ = three_ways(cb, ref, oracle, name, max_iter=max_iter, min_iter=min_iter, threads=1024, launches=[20])
+    _, wc, _, _, _ = three_ways(cb, ref, oracle, name, max_iter=max_iter, min_iter=min_iter, threads=1024, launches=[20])
     assert wc["samples"] == 1024 * 20
     if max_iter == 0:
         assert wc["never_escaped"] == wc["samples"] and wc["iterate_steps"] == 0
@@ -158,8 +83,7 @@ def test_early_out_changes_only_the_executed_work(cb, ref, oracle, name):
     """-m 20000 on 512 threads x 20 samples: checked with the restatement before this shape was chosen, 490 (tricorn) and
     712 (celtic) of the 10 240 samples are bit for bit at an earlier chunk boundary's point at a later one (at least 100
     are asserted again below)."""
-    extra = {}
-    _, wc, product, lockstep = three_ways(cb, ref, oracle, name, max_iter=20000, threads=512, launches=[20], extra=extra)
+    _, wc, product, lockstep, extra = three_ways(cb, ref, oracle, name, max_iter=20000, threads=512, launches=[20])
     assert extra["chunk_repeats"] >= 100
     assert product["skipped_steps"] > 0
 
@@ -171,13 +95,13 @@ def test_early_out_changes_only_the_executed_work(cb, ref, oracle, name):
 
 # ---- 4. other planes -------------------------------------------------------------------------------------------------------
 
-MATRICES = {"zr_cr": formula.ZR_CR, "hologram": formula.HOLOGRAM}
+MATRICES = {"zr_cr": plot.ZR_CR, "hologram": plot.HOLOGRAM}
 
 
 @pytest.mark.parametrize("plane", list(MATRICES))
 @pytest.mark.parametrize("name", ["celtic", "perpendicular"])
 def test_other_planes_on_a_cropped_canvas(cb, ref, oracle, name, plane):
-    _, wc, _, _ = three_ways(cb, ref, oracle, name, w=333, h=77, box=CROPPED, threads=2048, projection=MATRICES[plane])
+    _, wc, _, _, _ = three_ways(cb, ref, oracle, name, w=333, h=77, box=CROPPED, threads=2048, projection=MATRICES[plane])
     assert 0 < wc["increments"] < wc["replay_steps"]  # points on the canvas and points off it
 
 
@@ -191,27 +115,27 @@ JULIA = {"inside": dict(c=C_JULIA), "edge": dict(c=C_EDGE, max_iter=100, min_ite
 @pytest.mark.parametrize("case", list(JULIA))
 @pytest.mark.parametrize("name", ["tricorn", "celtic"])
 def test_a_fixed_c_goes_into_the_same_step(cb, ref, oracle, name, case):
-    want, wc, _, _ = three_ways(cb, ref, oracle, name, threads=1000, launches=[50, 7], projection=formula.HOLOGRAM,
+    want, wc, _, _, _ = three_ways(cb, ref, oracle, name, threads=1000, launches=[50, 7], projection=plot.HOLOGRAM,
                                 **JULIA[case])
     assert wc["recorded"] > 0 and wc["increments"] > 0 and wc["rejected"] == 0
     # not the render that samples c
     shape = JULIA[case]
-    sampled, _ = formula.draw(ref, 64, 64, shape.get("max_iter", 500), shape.get("min_iter", 20), 1000, [50, 7], name,
-                              projection=formula.HOLOGRAM, box=shape.get("box", SQUARE))
+    sampled, _ = plot.draw(ref, 64, 64, shape.get("max_iter", 500), shape.get("min_iter", 20), 1000, [50, 7], formula=name,
+                           projection=plot.HOLOGRAM, box=shape.get("box", SQUARE))
     assert not np.array_equal(sampled, want)
 
 
 # ---- 6. a table ---------------------------------------------------------------------------------------------------------------
 
 PALETTE = {"tricorn_sampled": dict(name="tricorn"), "perpendicular_julia": dict(name="perpendicular", c=C_JULIA)}
-PLANES = {"identity": formula.IDENTITY, "zr_cr": formula.ZR_CR, "hologram": formula.HOLOGRAM}
+PLANES = {"identity": plot.IDENTITY, "zr_cr": plot.ZR_CR, "hologram": plot.HOLOGRAM}
 W, H = 250, 130  # w != h: a transposed plane stride shows
 
 
 @pytest.mark.parametrize("plane", list(PLANES))
 @pytest.mark.parametrize("case", list(PALETTE))
 def test_a_table_colours_the_orbits(cb, ref, oracle, case, plane):
-    want, wc, _, _ = three_ways(cb, ref, oracle, w=W, h=H, threads=1000, launches=[50, 7], lut=demo_table(500),
+    want, wc, _, _, _ = three_ways(cb, ref, oracle, w=W, h=H, threads=1000, launches=[50, 7], lut=demo_table(500),
                                 projection=PLANES[plane], **PALETTE[case])
     assert wc["recorded"] > 0 and wc["increments"] > wc["recorded"]  # weighted points
     assert want[0].any() and want[1].any() and want[2].any()
@@ -222,9 +146,7 @@ def test_zero_entries_are_not_replayed(cb, ref, oracle, case):
     lut = demo_table(500)
     lut[20:40] = 0
     lut[100:] = 0
-    extra = {}
-    _, wc, product, _ = three_ways(cb, ref, oracle, w=W, h=H, threads=1000, launches=[50, 7], lut=lut, extra=extra,
-                                   **PALETTE[case])
+    _, wc, product, _, extra = three_ways(cb, ref, oracle, w=W, h=H, threads=1000, launches=[50, 7], lut=lut, **PALETTE[case])
     assert wc["increments"] > 0 and extra["zero_entry_steps"] > 0
     # the same run under a table without zero entries skips everything else the same way
     full = np.full(500, 0x010101, dtype=np.uint32)
@@ -240,8 +162,8 @@ def test_constant_table_equals_the_render_without_one_three_times(cb, case, base
     kw = PALETTE[case]
     variant = base | cb.CB_KERNEL_FORMULA(kw["name"])
     shape = (W, H, SQUARE, 500, 20, 1000, [50, 7], variant, kw.get("c"))
-    hist, cnt, kernel, states = gpu_launches(cb, *shape, np.full(500, 0x010101, dtype=np.uint32), formula.HOLOGRAM)
-    plain, pc, plain_kernel, plain_states = gpu_launches(cb, *shape, None, formula.HOLOGRAM)
+    hist, cnt, kernel, states = gpu_launches(cb, *shape, np.full(500, 0x010101, dtype=np.uint32), plot.HOLOGRAM)
+    plain, pc, plain_kernel, plain_states = gpu_launches(cb, *shape, None, plot.HOLOGRAM)
     assert kernel == plain_kernel == (LOCKSTEP if base else PRODUCT)
     assert pc["increments"] > 0
     for j in range(3):
@@ -378,14 +300,14 @@ def test_renderer_passes_equal_the_restatement(cb, ref, oracle, base, kind):
         lut = demo_table(m)
         lut[50:70] = 0
     st = oracle.init_states(1337, 0, threads)
-    want, wc = formula.draw(ref, w, h, m, mn, threads, [50] * 3, name, c, lut, formula.HOLOGRAM,
-                            omp_threads=omp_threads(), states=st)
+    want, wc = plot.draw(ref, w, h, m, mn, threads, [50] * 3, formula=name, c=c, lut=lut, projection=plot.HOLOGRAM,
+                         omp_threads=omp_threads(), states=st)
     variant = base | cb.CB_KERNEL_FORMULA(name)
     with cb.Renderer(cb.FractalDimensions.make(w, h), cb.IterationControl(m, mn), device=0, n_threads=threads) as r:
         if kind == "julia":
-            r.set_julia(c, formula.HOLOGRAM)
+            r.set_julia(c, plot.HOLOGRAM)
         else:
-            r.set_projection(formula.HOLOGRAM)
+            r.set_projection(plot.HOLOGRAM)
         if kind == "palette":
             r.set_palette(lut)
         r.prepare(variant)  # must not fail
@@ -403,18 +325,6 @@ def test_renderer_passes_equal_the_restatement(cb, ref, oracle, base, kind):
     assert np.array_equal(states, planar_states(st))
 
 
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-
-
 SHAPE = ["-w", "64", "-h", "64", "-m", "100", "-c", "20"]
 
 
@@ -426,7 +336,7 @@ def test_cli_formula_image_stats_and_resume(exe, ref, cb, oracle, tmp_path):
     lines = r.stderr.strip().split("\n")
     assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
     assert json.loads(lines[1]) == {"formula": "tricorn"}
-    want, wc = formula.draw(ref, 64, 64, 100, 20, 512 * 512, [100], "tricorn", omp_threads=omp_threads())
+    want, wc = plot.draw(ref, 64, 64, 100, 20, 512 * 512, [100], formula="tricorn", omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc
     assert wc["increments"] > 100000
@@ -452,7 +362,7 @@ def test_cli_formula_with_a_palette_writes_the_matching_ppm(exe, ref, cb, tmp_pa
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stderr.strip().split("\n")
     assert json.loads(lines[1]) == {"formula": "tricorn"} and "palette" in json.loads(lines[2])
-    want, wc = formula.draw(ref, 64, 64, 100, 20, 512 * 512, [50], "tricorn", lut=lut, omp_threads=omp_threads())
+    want, wc = plot.draw(ref, 64, 64, 100, 20, 512 * 512, [50], formula="tricorn", lut=lut, omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc and wc["recorded"] > 10000
     gray, _, _ = cb.set_grayscale_pixels(want.reshape(3 * 64, 64), 2.2)  # "Palette render", Image: one common maximum

@@ -1,5 +1,5 @@
 """The Julia render (include/cudabrot_amd.h, "Julia render") on the GPU.  Every case three ways -- the product kernel
-(cb_debug_last_draw_kernel 12), the lock-step kernel (13), the CPU restatement (tests/julia_reference.c) -- bit for bit on
+(cb_debug_last_draw_kernel 12), the lock-step kernel (13), the CPU restatement (tests/plot_reference.c) -- bit for bit on
 histogram, generator states and every counter but skipped_steps:
 
   1. the parameters c that matter (a connected set, superattracting and parabolic interiors, dust, the ends of the
@@ -12,89 +12,28 @@ histogram, generator states and every counter but skipped_steps:
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import julia_reference as julia
+import plot_harness
+import plot_reference as plot
 from conftest import read_state_file
+from plot_harness import INVALID, SAME, SQUARE, exe, omp_threads, planar_states, ref, variant_of  # noqa: F401
+from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 12, 13
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
-INVALID = 1  # hipErrorInvalidValue
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return julia.load(tmp_path_factory.mktemp("julia_ref"))
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
-def variant_of(cb, base, degree, ship):
-    return base | (cb.CB_KERNEL_POWER(degree) if degree != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
-
-
-def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c, projection):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist
-    [h, w], counters dict, cb_debug_last_draw_kernel, generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    out = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    for samples in launches:
-        cb.draw_buddhabrot_julia(dims, out.data_ptr(), it, projection, c, states.data_ptr(), threads, samples,
-                                 counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    return out.cpu().numpy().view(np.uint64).reshape(h, w), cnt, kernel, states.cpu().numpy().view(np.uint32)
 
 
 def three_ways(cb, ref, oracle, c, degree=2, ship=False, max_iter=500, min_iter=20, w=256, h=256, box=SQUARE, threads=4096,
-               launches=(50,), projection=julia.IDENTITY):
-    """Product == lock-step == restatement -> (restatement's counters, product's counters, lock-step's counters)."""
-    launches = list(launches)
-    st = oracle.init_states(1337, 0, threads)
-    want, wc = julia.draw(ref, w, h, max_iter, min_iter, threads, launches, c, degree, ship, projection, box=box,
-                          omp_threads=omp_threads(), states=st)
-    assert wc["samples"] == threads * sum(launches) and wc["rejected"] == 0 and int(want.sum()) == wc["increments"]
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches,
-                                                   variant_of(cb, base, degree, ship), c, projection)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert np.array_equal(hist, want), kernel
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        assert cb.lib.cb_debug_interior_map_level() == 0
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    return wc, got[PRODUCT], got[LOCKSTEP]
+               launches=(50,), projection=plot.IDENTITY):
+    """Product == lock-step == restatement, without an interior map -> (restatement's counters, product's counters,
+    lock-step's counters)."""
+    r = plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), 0, w, h, box, max_iter, min_iter, threads, launches,
+                                c=c, degree=degree, ship=ship, projection=projection)
+    return r.wc, r.product, r.lockstep
 
 
 # ---- 1. the parameters -------------------------------------------------------------------------------------------------
@@ -107,7 +46,7 @@ def test_connected_set(cb, ref, oracle):
 
 def test_hologram_on_a_cropped_canvas_takes_its_constant_from_the_fixed_c(cb, ref, oracle):
     wc, _, _ = three_ways(cb, ref, oracle, (-0.8, 0.156), max_iter=500, min_iter=20, w=300, h=200,
-                          box=(-1.3, 0.9, -0.7, 0.55), launches=[100], projection=julia.HOLOGRAM)
+                          box=(-1.3, 0.9, -0.7, 0.55), launches=[100], projection=plot.HOLOGRAM)
     assert wc["recorded"] > 10000 and 0 < wc["increments"] < wc["replay_steps"]  # points on the canvas and off it
 
 
@@ -283,11 +222,11 @@ def test_renderer_refuses_julia_where_it_is_not_defined(cb):
 @pytest.mark.parametrize("degree", [2, 3])
 def test_julia_renderer_over_several_calls(cb, ref, oracle, base, degree):
     w, h, box, m, mn, threads, c = 300, 200, (-2.0, 1.0, -2.0, 1.0), 400, 10, 4096, (-0.8, 0.156)
-    p = julia.HOLOGRAM
+    p = plot.HOLOGRAM
     variant = variant_of(cb, base, degree, False)
     st = oracle.init_states(1337, 0, threads)
-    want, wc = julia.draw(ref, w, h, m, mn, threads, [50] * 4, c, degree, False, p, box=box, omp_threads=omp_threads(),
-                          states=st)
+    want, wc = plot.draw(ref, w, h, m, mn, threads, [50] * 4, c=c, degree=degree, projection=p, box=box,
+                         omp_threads=omp_threads(), states=st)
     dims = cb.FractalDimensions.make(w, h, *box)
     with cb.Renderer(dims, cb.IterationControl(m, mn), device=0, n_threads=threads) as r:
         r.set_julia(c, p)
@@ -306,18 +245,6 @@ def test_julia_renderer_over_several_calls(cb, ref, oracle, base, degree):
     assert np.array_equal(states, planar_states(st))
 
 
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-
-
 def test_cli_julia_buffer_equals_the_restatement_and_resumes(exe, ref, tmp_path):
     common = ["--julia", "-0.8,0.156", "-w", "256", "-h", "256", "-m", "500", "-c", "20", "-o", os.devnull]
     one_buf, one_side = str(tmp_path / "one.bin"), str(tmp_path / "one.rng")
@@ -326,7 +253,7 @@ def test_cli_julia_buffer_equals_the_restatement_and_resumes(exe, ref, tmp_path)
     lines = r.stderr.strip().split("\n")
     assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
     assert [float.fromhex(v) for v in json.loads(lines[1])["julia"]] == [-0.8, 0.156]
-    want, wc = julia.draw(ref, 256, 256, 500, 20, 512 * 512, [100], (-0.8, 0.156), omp_threads=omp_threads())
+    want, wc = plot.draw(ref, 256, 256, 500, 20, 512 * 512, [100], c=(-0.8, 0.156), omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc
     assert wc["recorded"] > 100000
@@ -349,8 +276,8 @@ def test_cli_julia_with_power_on_another_plane(exe, ref, tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stderr.strip().split("\n")
     assert json.loads(lines[1]) == {"power": 3} and "julia" in json.loads(lines[2])
-    want, wc = julia.draw(ref, 256, 256, 500, 20, 512 * 512, [50], (-0.8, 0.156), degree=3, projection=julia.ZR_CR,
-                          omp_threads=omp_threads())
+    want, wc = plot.draw(ref, 256, 256, 500, 20, 512 * 512, [50], c=(-0.8, 0.156), degree=3, projection=plot.ZR_CR,
+                         omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc
     assert np.array_equal(read_state_file(buf, 256, 256), want)

@@ -1,5 +1,5 @@
 """The palette render (include/cudabrot_amd.h, "Palette render") on the GPU.  Every case three ways -- the product kernel
-(cb_debug_last_draw_kernel 14), the lock-step kernel (15), the CPU restatement (tests/palette_reference.c) -- bit for bit on
+(cb_debug_last_draw_kernel 14), the lock-step kernel (15), the CPU restatement (tests/plot_reference.c) -- bit for bit on
 the three planes, the generator states and every counter but skipped_steps:
 
   1. the steps and both sources of c;
@@ -16,21 +16,19 @@ wave), two launches on the same generators, and a table whose neighbours differ 
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import palette_reference as palette
+import plot_harness
+import plot_reference as plot
 from conftest import read_state_file
+from plot_harness import INVALID, SAME, SQUARE, exe, omp_threads, planar_states, ref, variant_of  # noqa: F401
+from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 14, 15
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
-INVALID = 1  # hipErrorInvalidValue
 W, H, MAX, MIN, THREADS, LAUNCHES = 250, 130, 500, 20, 1000, (3, 2)
 C_JULIA = (-0.8, 0.156)
 # parameters at which the other steps have orbits with k >= 20 among 5000 starting points (at C_JULIA they have none:
@@ -39,95 +37,29 @@ C_CUBIC, C_SHIP = (0.4, 0.0), (0.3, 0.0)
 WINDOWS = [(20, 60), (60, 200), (100, 500)]  # G and B overlap
 
 
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
+def gpu_launches(cb, lut, variant, c=None, projection=plot.IDENTITY, w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN,
+                 threads=THREADS, launches=LAUNCHES):
+    """plot_harness.gpu_launches at this suite's shape.  lut None: the same render without a palette
+    (cb_draw_buddhabrot_projected, or cb_draw_buddhabrot_julia with a c) -> hist [h, w]."""
+    return plot_harness.gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c, lut, projection)
 
 
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return palette.load(tmp_path_factory.mktemp("palette_ref"))
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
-def variant_of(cb, base, degree=2, ship=False):
-    return base | (cb.CB_KERNEL_POWER(degree) if degree != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
-
-
-def gpu_launches(cb, lut, variant, c=None, projection=palette.IDENTITY, w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN,
-                 threads=THREADS, launches=LAUNCHES, plain=False, device_lut=None):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist
-    [3, h, w], counters dict, cb_debug_last_draw_kernel, generator states as u32 planes).  plain: the same render without
-    a palette (cb_draw_buddhabrot_projected, or cb_draw_buddhabrot_julia with a c) -> hist [h, w]."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    planes = 1 if plain else 3
-    out = torch.zeros(planes * w * h, dtype=torch.int64, device=dev)
-    if not plain:
-        table = np.ascontiguousarray(lut if device_lut is None else device_lut, dtype=np.uint32)
-        d_lut = torch.from_numpy(table.view(np.int32).copy()).to(dev)
-    for samples in launches:
-        if plain and c is None:
-            cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, projection, states.data_ptr(), threads, samples,
-                                         counters.data_ptr(), variant, stream)
-        elif plain:
-            cb.draw_buddhabrot_julia(dims, out.data_ptr(), it, projection, c, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), variant, stream)
-        else:
-            cb.draw_buddhabrot_palette(dims, out.data_ptr(), it, projection, c, d_lut.data_ptr(), table.size,
-                                       states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    hist = out.cpu().numpy().view(np.uint64)
-    return (hist.reshape(h, w) if plain else hist.reshape(3, h, w)), cnt, kernel, states.cpu().numpy().view(np.uint32)
-
-
-def three_ways(cb, ref, oracle, lut, c=None, degree=2, ship=False, projection=palette.IDENTITY, w=W, h=H, box=SQUARE,
+def three_ways(cb, ref, oracle, lut, c=None, degree=2, ship=False, projection=plot.IDENTITY, w=W, h=H, box=SQUARE,
                max_iter=MAX, min_iter=MIN, threads=THREADS, launches=LAUNCHES, device_lut=None):
     """Product == lock-step == restatement -> (restatement's hist, its counters, its zero-entry replay steps, the
-    product's counters)."""
-    launches = list(launches)
-    st = oracle.init_states(1337, 0, threads)
-    want, wc, zero_steps = palette.draw(ref, w, h, max_iter, min_iter, threads, launches, lut, c, degree, ship, projection,
-                                        box=box, omp_threads=omp_threads(), states=st)
-    assert wc["samples"] == threads * sum(launches) and int(want.sum()) == wc["increments"]
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = gpu_launches(cb, lut, variant_of(cb, base, degree, ship), c, projection, w, h, box,
-                                                   max_iter, min_iter, threads, launches, device_lut=device_lut)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        for j in range(3):
-            assert np.array_equal(hist[j], want[j]), (kernel, j)
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    assert got[PRODUCT]["skipped_steps"] >= zero_steps
-    return want, wc, zero_steps, got[PRODUCT]
+    product's counters).  The product kernel consults the interior map where cb_draw_buddhabrot_projected does: the
+    Mandelbrot step on a sampled c, max_iter above 20 (tests/test_gpu_project.py)."""
+    map_level = 1 if c is None and degree == 2 and not ship and max_iter > 20 else 0
+    r = plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), map_level, w, h, box, max_iter, min_iter, threads,
+                                launches, degree=degree, ship=ship, c=c, lut=lut, device_lut=device_lut, projection=projection)
+    return r.want, r.wc, r.extra["zero_entry_steps"], r.product
 
 
 # ---- 1. the steps and both sources of c -------------------------------------------------------------------------------------
 
 CASES = {
     "mandelbrot": dict(),
-    "hologram_cropped": dict(projection=palette.HOLOGRAM, box=(-1.3, 0.9, -0.7, 0.55)),
+    "hologram_cropped": dict(projection=plot.HOLOGRAM, box=(-1.3, 0.9, -0.7, 0.55)),
     "ship": dict(ship=True),
     "degree3": dict(degree=3),
     "degree8": dict(degree=8),
@@ -139,14 +71,14 @@ CASES = {
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_product_lockstep_and_restatement_agree(cb, ref, oracle, name):
-    want, wc, _, _ = three_ways(cb, ref, oracle, palette.demo_table(MAX), **CASES[name])
+    want, wc, _, _ = three_ways(cb, ref, oracle, plot.demo_table(MAX), **CASES[name])
     assert wc["recorded"] > 0 and wc["increments"] > wc["recorded"]  # weighted points
     assert want[0].any() and want[1].any() and want[2].any()
     assert (wc["rejected"] > 0) == (name in ("mandelbrot", "hologram_cropped"))  # cardioid and bulb: that step, sampled c
 
 
 def test_the_mandelbrot_step_on_a_sampled_c_uses_the_interior_map(cb):
-    lut = palette.demo_table(MAX)
+    lut = plot.demo_table(MAX)
     gpu_launches(cb, lut, cb.CB_KERNEL_DEFAULT)
     assert cb.lib.cb_debug_interior_map_level() > 0
     for kw in (dict(c=C_JULIA), dict(variant=cb.CB_KERNEL_SIMPLE), dict(variant=cb.CB_KERNEL_FLAG_BURNING_SHIP),
@@ -158,7 +90,7 @@ def test_the_mandelbrot_step_on_a_sampled_c_uses_the_interior_map(cb):
 @pytest.mark.parametrize("degree", [4, 5, 6, 7])
 @pytest.mark.parametrize("c", [None, (0.3, -0.2)], ids=["sampled", "fixed"])
 def test_the_other_degrees_are_their_own_instances(cb, ref, oracle, degree, c):
-    _, wc, _, _ = three_ways(cb, ref, oracle, palette.demo_table(100), c=c, degree=degree, max_iter=100, min_iter=0, w=64,
+    _, wc, _, _ = three_ways(cb, ref, oracle, plot.demo_table(100), c=c, degree=degree, max_iter=100, min_iter=0, w=64,
                              h=48, threads=300, launches=[4])
     assert wc["recorded"] > 0
 
@@ -170,8 +102,8 @@ def test_the_other_degrees_are_their_own_instances(cb, ref, oracle, degree, c):
 @pytest.mark.parametrize("c", [None, C_JULIA], ids=["projected", "julia"])
 def test_constant_table_equals_the_plain_render(cb, base, c):
     lut = np.full(MAX, 0x010101, dtype=np.uint32)
-    hist, cnt, kernel, states = gpu_launches(cb, lut, base, c, palette.HOLOGRAM)
-    plain, pc, plain_kernel, plain_states = gpu_launches(cb, None, base, c, palette.HOLOGRAM, plain=True)
+    hist, cnt, kernel, states = gpu_launches(cb, lut, base, c, plot.HOLOGRAM)
+    plain, pc, plain_kernel, plain_states = gpu_launches(cb, None, base, c, plot.HOLOGRAM)
     assert kernel == (LOCKSTEP if base else PRODUCT) and plain_kernel == (8 if c is None else 12) + base
     assert pc["increments"] > 0
     for j in range(3):
@@ -188,11 +120,11 @@ def test_constant_table_equals_the_plain_render(cb, base, c):
 @pytest.mark.parametrize("min_iter", [MIN, 5], ids=["every_k_in_a_window", "k_below_20_in_none"])
 @pytest.mark.parametrize("c", [None, C_JULIA], ids=["projected", "julia"])
 def test_window_table_equals_the_plain_render_of_each_window(cb, ref, oracle, c, min_iter):
-    lut = palette.window_table(MAX, WINDOWS)
+    lut = plot.window_table(MAX, WINDOWS)
     want, wc, zero_steps, product = three_ways(cb, ref, oracle, lut, c=c, min_iter=min_iter)
     hist, cnt, _, _ = gpu_launches(cb, lut, cb.CB_KERNEL_DEFAULT, c, min_iter=min_iter)
     for j, (lo, hi) in enumerate(WINDOWS):
-        plain, pc, _, _ = gpu_launches(cb, None, cb.CB_KERNEL_DEFAULT, c, max_iter=hi, min_iter=lo, plain=True)
+        plain, pc, _, _ = gpu_launches(cb, None, cb.CB_KERNEL_DEFAULT, c, max_iter=hi, min_iter=lo)
         assert pc["increments"] > 0
         assert np.array_equal(hist[j], plain), j
     # what the zero entries skip: the same run under the constant table skips everything else the same way
@@ -215,11 +147,11 @@ def ends_only(n, lo):
 
 
 EDGES = {
-    "min0_reads_entry_0": dict(lut=palette.demo_table(MAX) | np.uint32(0x030000), min_iter=0),
+    "min0_reads_entry_0": dict(lut=plot.demo_table(MAX) | np.uint32(0x030000), min_iter=0),
     "max1": dict(lut=np.array([0x0a0b0c], dtype=np.uint32), max_iter=1, min_iter=0),
     "only_k_min_and_k_max_minus_1": dict(lut=ends_only(MAX, MIN)),
     "weights_255": dict(lut=np.full(MAX, 0xFFFFFF, dtype=np.uint32)),
-    "julia_min0": dict(lut=palette.demo_table(60), c=C_JULIA, max_iter=60, min_iter=0),
+    "julia_min0": dict(lut=plot.demo_table(60), c=C_JULIA, max_iter=60, min_iter=0),
 }
 
 
@@ -237,7 +169,7 @@ def test_edges(cb, ref, oracle, name):
 
 
 def test_bits_24_to_31_of_the_device_table_change_nothing(cb, ref, oracle):
-    lut = palette.demo_table(MAX)
+    lut = plot.demo_table(MAX)
     lut[30:40] = 0  # zero entries stay zero entries under the high bits
     three_ways(cb, ref, oracle, lut, device_lut=lut | np.uint32(0xFF000000))
     three_ways(cb, ref, oracle, lut, c=C_JULIA, device_lut=lut | np.uint32(0x01000000))
@@ -376,13 +308,13 @@ def test_palette_renderer_over_several_calls(cb, ref, oracle, base, kind):
     box, m, mn = (-2.0, 1.0, -1.5, 1.5), 300, 10
     c = C_CUBIC if kind == "julia_degree3" else None
     degree = 3 if kind == "julia_degree3" else 2
-    p = palette.IDENTITY if kind == "alone" else palette.HOLOGRAM
+    p = plot.IDENTITY if kind == "alone" else plot.HOLOGRAM
     variant = variant_of(cb, base, degree)
-    lut = palette.demo_table(m)
+    lut = plot.demo_table(m)
     lut[50:70] = 0
     st = oracle.init_states(1337, 0, THREADS)
-    want, wc, _ = palette.draw(ref, W, H, m, mn, THREADS, [50] * 3, lut, c, degree, False, p, box=box,
-                               omp_threads=omp_threads(), states=st)
+    want, wc = plot.draw(ref, W, H, m, mn, THREADS, [50] * 3, lut=lut, c=c, degree=degree, projection=p, box=box,
+                         omp_threads=omp_threads(), states=st)
     dims = cb.FractalDimensions.make(W, H, *box)
     with cb.Renderer(dims, cb.IterationControl(m, mn), device=0, n_threads=THREADS) as r:
         if kind == "projected":
@@ -410,7 +342,7 @@ def rendered(cb):
     """One palette renderer with a few passes in it, and its histogram."""
     dims = cb.FractalDimensions.make(W, H)
     with cb.Renderer(dims, cb.IterationControl(MAX, MIN), device=0, n_threads=THREADS) as r:
-        r.set_palette(palette.demo_table(MAX))
+        r.set_palette(plot.demo_table(MAX))
         r.render_passes(3)
         yield r, r.read_histogram()
 
@@ -442,7 +374,7 @@ def test_write_then_read_round_trips_the_three_planes(cb):
     rng = np.random.default_rng(7)
     planes = rng.integers(0, 1 << 40, size=(3, H, W), dtype=np.uint64)
     with cb.Renderer(dims, cb.IterationControl(MAX, MIN), device=0, n_threads=THREADS) as r:
-        r.set_palette(palette.demo_table(MAX))
+        r.set_palette(plot.demo_table(MAX))
         r.write_histogram(planes)
         assert np.array_equal(r.read_histogram(), planes)
         with pytest.raises(ValueError):
@@ -453,18 +385,6 @@ def test_write_then_read_round_trips_the_three_planes(cb):
 
 
 # ---- 7. the binary -----------------------------------------------------------------------------------------------------------
-
-
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
 
 
 STOPS_TEXT = "20:000030,200:ff8000,499:ffffff"
@@ -482,7 +402,7 @@ def test_cli_palette_buffer_image_and_resume(cb, exe, ref, tmp_path):
     lines = r.stderr.strip().split("\n")
     assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
     assert json.loads(lines[1]) == {"palette": [[20, "000030"], [200, "ff8000"], [499, "ffffff"]]}
-    want, wc, _ = palette.draw(ref, W, H, MAX, MIN, 512 * 512, [100], lut, omp_threads=omp_threads())
+    want, wc = plot.draw(ref, W, H, MAX, MIN, 512 * 512, [100], lut=lut, omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc
     assert wc["recorded"] > 100000
@@ -516,8 +436,8 @@ def test_cli_palette_with_julia_and_power_on_another_plane(cb, exe, ref, tmp_pat
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stderr.strip().split("\n")
     assert json.loads(lines[1]) == {"power": 3} and "julia" in json.loads(lines[2]) and "palette" in json.loads(lines[3])
-    want, wc, _ = palette.draw(ref, W, H, MAX, MIN, 512 * 512, [50], cb.palette_from_stops(STOPS, MAX), C_CUBIC, degree=3,
-                               projection=palette.ZR_CR, omp_threads=omp_threads())
+    want, wc = plot.draw(ref, W, H, MAX, MIN, 512 * 512, [50], lut=cb.palette_from_stops(STOPS, MAX), c=C_CUBIC, degree=3,
+                         projection=plot.ZR_CR, omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc and stats["skipped_steps"] == 0
     assert wc["recorded"] > 10000

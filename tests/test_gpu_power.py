@@ -1,5 +1,5 @@
 """The Multibrot render (include/cudabrot_amd.h, "Multibrot step") on the GPU.  Every case three ways -- the product
-kernel (cb_debug_last_draw_kernel 10), the lock-step kernel (11), the CPU restatement (tests/power_reference.c) -- bit for
+kernel (cb_debug_last_draw_kernel 10), the lock-step kernel (11), the CPU restatement (tests/plot_reference.c) -- bit for
 bit on histogram, generator states and every counter but skipped_steps:
 
   1. every degree, whole and ragged grids, two launches on the same generators;
@@ -12,82 +12,24 @@ bit on histogram, generator states and every counter but skipped_steps:
 
 import ctypes as C
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import power_reference as power
+import plot_harness
+import plot_reference as plot
+from plot_harness import SAME, SQUARE, exe, omp_threads, planar_states, ref  # noqa: F401
+from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 10, 11
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
 
 
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return power.load(tmp_path_factory.mktemp("power_ref"))
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
-def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, degree, projection):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist
-    [h, w], counters dict, cb_debug_last_draw_kernel, generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    out = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    for samples in launches:
-        cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, projection, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), base | cb.CB_KERNEL_POWER(degree), stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(c[k]) for k, n in enumerate(names)}
-    return out.cpu().numpy().view(np.uint64).reshape(h, w), cnt, kernel, states.cpu().numpy().view(np.uint32)
-
-
-def three_ways(cb, ref, oracle, w, h, box, max_iter, min_iter, threads, launches, degree, projection=power.IDENTITY,
-               repeats=None):
-    """Product == lock-step == restatement -> (restatement's counters, product's counters, lock-step's counters)."""
-    st = oracle.init_states(1337, 0, threads)
-    want, wc = power.draw(ref, w, h, max_iter, min_iter, threads, launches, degree, projection, box=box,
-                          omp_threads=omp_threads(), states=st, repeats=repeats)
-    assert wc["rejected"] == 0 and int(want.sum()) == wc["increments"]
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, degree,
-                                                   projection)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert np.array_equal(hist, want), kernel
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        assert cb.lib.cb_debug_interior_map_level() == 0
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    return wc, got[PRODUCT], got[LOCKSTEP]
+def three_ways(cb, ref, oracle, w, h, box, max_iter, min_iter, threads, launches, degree, projection=plot.IDENTITY):
+    """Product == lock-step == restatement, without an interior map -> plot_harness.ThreeWays."""
+    return plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), 0, w, h, box, max_iter, min_iter, threads, launches,
+                                   degree=degree, projection=projection)
 
 
 # ---- 1. every degree ----------------------------------------------------------------------------------------------------
@@ -96,7 +38,7 @@ def three_ways(cb, ref, oracle, w, h, box, max_iter, min_iter, threads, launches
 @pytest.mark.parametrize("threads,launches", [(4096, [50]), (1000, [50, 7])], ids=["whole", "ragged"])
 @pytest.mark.parametrize("degree", range(3, 9))
 def test_every_degree(cb, ref, oracle, degree, threads, launches):
-    wc, _, _ = three_ways(cb, ref, oracle, 64, 64, SQUARE, 500, 20, threads, launches, degree)
+    wc = three_ways(cb, ref, oracle, 64, 64, SQUARE, 500, 20, threads, launches, degree).wc
     assert wc["samples"] == threads * sum(launches)
     assert wc["never_escaped"] > 0 and wc["too_fast"] > 0 and wc["recorded"] > 0 and wc["increments"] > wc["recorded"]
 
@@ -110,7 +52,7 @@ EDGES = [(m, 0) for m in (0, 1, 11, 12, 13, 59, 60, 61, 120, 121)] + [(61, 60), 
 @pytest.mark.parametrize("max_iter,min_iter", EDGES, ids=["m%d_c%d" % e for e in EDGES])
 @pytest.mark.parametrize("degree", [3, 8])
 def test_round_and_chunk_edges(cb, ref, oracle, degree, max_iter, min_iter):
-    wc, _, _ = three_ways(cb, ref, oracle, 64, 64, SQUARE, max_iter, min_iter, 1024, [20], degree)
+    wc = three_ways(cb, ref, oracle, 64, 64, SQUARE, max_iter, min_iter, 1024, [20], degree).wc
     assert wc["samples"] == 1024 * 20
     if max_iter == 0:
         assert wc["never_escaped"] == wc["samples"] and wc["iterate_steps"] == 0
@@ -129,9 +71,8 @@ def test_early_out_changes_only_the_executed_work(cb, ref, oracle):
     """max_iter 2000 at degree 3: checked with the restatement before this shape was chosen, 21 871 of the 204 800
     samples are bit for bit at an earlier chunk boundary's point at a multiple of 60 steps below max (at least 100 are
     asserted again below); no larger max_iter was needed."""
-    repeats = []
-    wc, product, lockstep = three_ways(cb, ref, oracle, 64, 64, SQUARE, 2000, 20, 4096, [50], 3, repeats=repeats)
-    assert repeats[0] >= 100
+    _, wc, product, lockstep, extra = three_ways(cb, ref, oracle, 64, 64, SQUARE, 2000, 20, 4096, [50], 3)
+    assert extra["chunk_repeats"] >= 100
     assert product["skipped_steps"] > 0
 
     def executed(c):
@@ -142,14 +83,13 @@ def test_early_out_changes_only_the_executed_work(cb, ref, oracle):
 
 # ---- 4. other planes -------------------------------------------------------------------------------------------------------
 
-MATRICES = {"zr_cr": power.ZR_CR, "hologram": power.HOLOGRAM}
+MATRICES = {"zr_cr": plot.ZR_CR, "hologram": plot.HOLOGRAM}
 
 
 @pytest.mark.parametrize("name", list(MATRICES))
 @pytest.mark.parametrize("degree", [3, 5])
 def test_other_planes_on_a_cropped_canvas(cb, ref, oracle, degree, name):
-    wc, _, _ = three_ways(cb, ref, oracle, 333, 77, (-1.3, 0.9, -0.7, 0.55), 500, 20, 2048, [50], degree,
-                          MATRICES[name])
+    wc = three_ways(cb, ref, oracle, 333, 77, (-1.3, 0.9, -0.7, 0.55), 500, 20, 2048, [50], degree, MATRICES[name]).wc
     assert 0 < wc["increments"] < wc["replay_steps"]  # points on the canvas and points off it
 
 
@@ -220,7 +160,7 @@ def test_a_degree_is_refused_wherever_it_is_not_defined(cb):
 def test_renderer_passes_equal_the_restatement(cb, ref, oracle, base):
     w, h, m, c, threads = 64, 64, 500, 20, 4096
     st = oracle.init_states(1337, 0, threads)
-    want, wc = power.draw(ref, w, h, m, c, threads, [50] * 3, 3, power.IDENTITY, omp_threads=omp_threads(), states=st)
+    want, wc = plot.draw(ref, w, h, m, c, threads, [50] * 3, degree=3, omp_threads=omp_threads(), states=st)
     dims = cb.FractalDimensions.make(w, h)
     variant = base | cb.CB_KERNEL_POWER(3)
     with cb.Renderer(dims, cb.IterationControl(m, c), device=0, n_threads=threads) as r:
@@ -236,18 +176,6 @@ def test_renderer_passes_equal_the_restatement(cb, ref, oracle, base):
     assert np.array_equal(states, planar_states(st))
 
 
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-
-
 @pytest.mark.parametrize("plane", [None, "zr,cr"], ids=["identity", "zr_cr"])
 def test_cli_power_image_equals_the_restatement(exe, ref, cb, oracle, tmp_path, plane):
     out = str(tmp_path / "x.pgm")
@@ -255,10 +183,10 @@ def test_cli_power_image_equals_the_restatement(exe, ref, cb, oracle, tmp_path, 
     r = run(exe, "--power", "3", "-w", "64", "-h", "64", "-m", "100", "-c", "20", "--passes", "1", "-o", out, "--stats",
             *extra)
     assert r.returncode == 0, r.stdout + r.stderr
-    p = power.ZR_CR if plane else power.IDENTITY
-    want, wc = power.draw(ref, 64, 64, 100, 20, 512 * 512, [50], 3, p, omp_threads=omp_threads())
+    p = plot.ZR_CR if plane else plot.IDENTITY
+    want, wc = plot.draw(ref, 64, 64, 100, 20, 512 * 512, [50], projection=p, degree=3, omp_threads=omp_threads())
     lines = r.stderr.strip().split("\n")
-    assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [float(x) for x in power.matrix(p)]
+    assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [float(x) for x in plot.matrix(p)]
     assert json.loads(lines[1]) == {"power": 3}
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == wc

@@ -2,7 +2,7 @@
 states and counters (all but skipped_steps and the clocks):
 
   1. the identity matrix against the normal path (cb_draw_buddhabrot: its lock-step kernel and its default product path);
-  2. general matrices: product kernel == lock-step kernel == the CPU restatement (tests/project_reference.c);
+  2. general matrices: product kernel == lock-step kernel == the CPU restatement (tests/plot_reference.c);
   3. the early-outs (interior map, exact periodicity) change nothing but the executed work;
   4. the renderer (set_projection, several calls, resume) and the binary against the restatement.
 """
@@ -10,69 +10,29 @@ states and counters (all but skipped_steps and the clocks):
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import project_reference as project
+import plot_harness
+import plot_reference as plot
 from conftest import read_state_file
+from plot_harness import SAME, SQUARE, exe, omp_threads, planar_states, ref  # noqa: F401
+from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 8, 9
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return project.load(tmp_path_factory.mktemp("project_ref"))
 
 
 def same(a, b):
     return {k: a[k] for k in SAME} == {k: b[k] for k in SAME}
 
 
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
 def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, ship=False, projection=None):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)), projected, or --
-    projection=None -- through cb_draw_buddhabrot without workspace and carry -> (u64 hist [h, w], counters dict,
-    cb_debug_last_draw_kernel, generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    variant = base | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
-    out = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    for samples in launches:
-        if projection is None:
-            cb.draw_buddhabrot(dims, out.data_ptr(), it, states.data_ptr(), threads, samples, counters.data_ptr(),
-                               variant, stream)
-        else:
-            cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, projection, states.data_ptr(), threads, samples,
-                                         counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(c[k]) for k, n in enumerate(names)}
-    return out.cpu().numpy().view(np.uint64).reshape(h, w), cnt, kernel, states.cpu().numpy().view(np.uint32)
+    """plot_harness.gpu_launches, projected, or -- projection=None -- through cb_draw_buddhabrot."""
+    return plot_harness.gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches,
+                                     plot_harness.variant_of(cb, base, ship=ship), projection=projection)
 
 
 # ---- 1. the identity matrix is a normal render ---------------------------------------------------------------------------
@@ -147,25 +107,17 @@ def test_projected_launches_refuse_what_they_do_not_define(cb):
 
 # ---- 2. general matrices against the restatement ---------------------------------------------------------------------------
 
-MATRICES = {"c_plane": project.C_PLANE, "zr_cr": project.ZR_CR, "hologram": project.HOLOGRAM}
+MATRICES = {"c_plane": plot.C_PLANE, "zr_cr": plot.ZR_CR, "hologram": plot.HOLOGRAM}
 
 
 @pytest.mark.parametrize("ship", [False, True], ids=["mandelbrot", "ship"])
 @pytest.mark.parametrize("name", list(MATRICES))
 def test_general_matrix_equals_the_restatement(cb, ref, oracle, name, ship):
     w, h, box, max_iter, min_iter, threads, launches = 320, 240, (-2.0, 1.5, -1.75, 1.75), 600, 15, 4000, [50, 70]
-    p = MATRICES[name]
-    st = oracle.init_states(1337, 0, threads)
-    want, wc = project.draw(ref, w, h, max_iter, min_iter, threads, launches, p, box=box, ship=ship,
-                            omp_threads=omp_threads(), states=st)
+    # the interior map is the Mandelbrot set's: the product kernel consults it (level 8 or above) unless the step is the ship's
+    want, wc, _, _, _ = plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), 0 if ship else 8, w, h, box, max_iter,
+                                                min_iter, threads, launches, ship=ship, projection=MATRICES[name])
     assert wc["increments"] > 1000
-    for base, kernel in ((cb.CB_KERNEL_SIMPLE, LOCKSTEP), (cb.CB_KERNEL_DEFAULT, PRODUCT)):
-        hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, ship,
-                                                   projection=p)
-        assert launched == kernel
-        assert cnt["status"] == 0 and same(cnt, wc), (cnt, wc)
-        assert np.array_equal(hist, want)
-        assert np.array_equal(states, planar_states(st))
     if name == "c_plane":  # every accepted sample's k + 1 points on the one pixel of c
         assert int(want.sum()) == wc["increments"] <= wc["replay_steps"]
 
@@ -175,7 +127,7 @@ def test_general_matrix_equals_the_restatement(cb, ref, oracle, name, ship):
 
 def test_early_outs_change_only_the_executed_work(cb, monkeypatch):
     w, h, box, max_iter, min_iter, threads, launches = 256, 256, SQUARE, 20000, 20, 4096, [50]
-    p = project.HOLOGRAM
+    p = plot.HOLOGRAM
     args = (cb, w, h, box, max_iter, min_iter, threads, launches)
     with_map = gpu_launches(*args, cb.CB_KERNEL_DEFAULT, projection=p)
     assert cb.lib.cb_debug_interior_map_level() >= 8
@@ -202,11 +154,11 @@ def test_early_outs_change_only_the_executed_work(cb, monkeypatch):
 def test_small_max_iter_does_not_consult_the_map(cb):
     """The rule of cb_draw_buddhabrot_projected: the map only where the normal product path has a LONG stage to save
     (max_iter above the 20 steps of its HEAD and MID stages at min_iter <= 16)."""
-    gpu_launches(cb, 64, 64, SQUARE, 20, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, projection=project.ZR_CR)
+    gpu_launches(cb, 64, 64, SQUARE, 20, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, projection=plot.ZR_CR)
     assert cb.lib.cb_debug_interior_map_level() == 0
-    gpu_launches(cb, 64, 64, SQUARE, 21, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, projection=project.ZR_CR)
+    gpu_launches(cb, 64, 64, SQUARE, 21, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, projection=plot.ZR_CR)
     assert cb.lib.cb_debug_interior_map_level() >= 8
-    gpu_launches(cb, 64, 64, SQUARE, 500, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, True, projection=project.ZR_CR)
+    gpu_launches(cb, 64, 64, SQUARE, 500, 5, 1024, [10], cb.CB_KERNEL_DEFAULT, True, projection=plot.ZR_CR)
     assert cb.lib.cb_debug_interior_map_level() == 0  # the map is the Mandelbrot set's
 
 
@@ -215,7 +167,7 @@ def test_small_max_iter_does_not_consult_the_map(cb):
 
 def test_renderer_refuses_a_projection_where_it_is_not_defined(cb):
     dims = cb.FractalDimensions.make(64, 64)
-    good = (C.c_double * 8)(*project.matrix(project.ZR_CR))
+    good = (C.c_double * 8)(*plot.matrix(plot.ZR_CR))
     out = (C.c_double * 8)(*([7.0] * 8))
     with cb.Renderer(dims, [(100, 20), (50, 5)], device=0, n_threads=1024) as r:
         assert cb.lib.cb_renderer_set_projection(r._h, good) == 1  # a channel renderer
@@ -223,12 +175,12 @@ def test_renderer_refuses_a_projection_where_it_is_not_defined(cb):
     with cb.Renderer(dims, cb.IterationControl(100, 20), device=0, n_threads=1024) as r:
         assert cb.lib.cb_renderer_projection(r._h, out) == 0 and list(out) == [7.0] * 8
         for index in (0, 3, 7):
-            p = list(project.matrix(project.ZR_CR))
+            p = list(plot.matrix(plot.ZR_CR))
             p[index] = float("nan") if index else float("inf")
             assert cb.lib.cb_renderer_set_projection(r._h, (C.c_double * 8)(*p)) == 1
         assert cb.lib.cb_renderer_set_projection(r._h, None) == 1
-        r.set_projection(project.ZR_CR)
-        assert np.array_equal(r.projection(), np.array(project.ZR_CR))
+        r.set_projection(plot.ZR_CR)
+        assert np.array_equal(r.projection(), np.array(plot.ZR_CR))
         assert cb.lib.cb_renderer_set_projection(r._h, good) == 1  # once
         assert cb.lib.cb_renderer_set_focus(r._h, 6, 2, 1, 0) == 1  # no focus on a projected renderer
         assert cb.lib.cb_renderer_render_passes(r._h, 1, cb.CB_KERNEL_FLAG_ANTI) == 1
@@ -246,10 +198,11 @@ def test_renderer_refuses_a_projection_where_it_is_not_defined(cb):
 @pytest.mark.parametrize("ship", [False, True], ids=["mandelbrot", "ship"])
 def test_projected_renderer_over_several_calls(cb, ref, oracle, base, ship):
     w, h, box, m, c, threads = 300, 200, (-2.0, 1.0, -2.0, 1.0), 400, 10, 4096
-    p = project.HOLOGRAM
+    p = plot.HOLOGRAM
     variant = base | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
     st = oracle.init_states(1337, 0, threads)
-    want, wc = project.draw(ref, w, h, m, c, threads, [50] * 4, p, box=box, ship=ship, omp_threads=omp_threads(), states=st)
+    want, wc = plot.draw(ref, w, h, m, c, threads, [50] * 4, projection=p, box=box, ship=ship, omp_threads=omp_threads(),
+                         states=st)
     dims = cb.FractalDimensions.make(w, h, *box)
     with cb.Renderer(dims, cb.IterationControl(m, c), device=0, n_threads=threads) as r:
         r.set_projection(p)
@@ -269,18 +222,6 @@ def test_projected_renderer_over_several_calls(cb, ref, oracle, base, ship):
     assert np.array_equal(gray.astype(np.uint16), want_gray)
 
 
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-
-
 def test_cli_plane_zr_zi_is_the_plain_command(exe, tmp_path):
     common = ["-w", "333", "-h", "77", "-m", "300", "-c", "10", "--passes", "2"]
     plain, plane = str(tmp_path / "plain.pgm"), str(tmp_path / "plane.pgm")
@@ -294,14 +235,14 @@ def test_cli_plane_zr_zi_is_the_plain_command(exe, tmp_path):
 
 @pytest.mark.parametrize("extra", [[], ["--kernel", "simple"], ["--burning-ship"]], ids=["product", "lockstep", "ship"])
 def test_cli_project_image_equals_the_restatement(exe, ref, cb, oracle, tmp_path, extra):
-    p = project.HOLOGRAM.reshape(-1)
+    p = plot.HOLOGRAM.reshape(-1)
     text = ",".join(float(x).hex() for x in p[:4]) + ":" + ",".join(float(x).hex() for x in p[4:])
-    out = str(tmp_path / "project.pgm")
+    out = str(tmp_path / "plot.pgm")
     r = run(exe, "--project", text, "-w", "160", "-h", "120", "-m", "300", "-c", "20", "--passes", "2", "--stats", "-o",
             out, "--tonemap", "host", *extra)
     assert r.returncode == 0, r.stdout + r.stderr
-    want, wc = project.draw(ref, 160, 120, 300, 20, 512 * 512, [100], p, ship="--burning-ship" in extra,
-                            omp_threads=omp_threads())
+    want, wc = plot.draw(ref, 160, 120, 300, 20, 512 * 512, [100], projection=p, ship="--burning-ship" in extra,
+                         omp_threads=omp_threads())
     lines = r.stderr.strip().split("\n")
     assert [float.fromhex(v) for v in json.loads(lines[0])["projection"]] == [float(x) for x in p]
     stats = json.loads(lines[-1])
@@ -327,6 +268,6 @@ def test_cli_project_true_resume(exe, ref, tmp_path):
         assert a.read() == b.read()
     # the run is defined by the matrix the binary states (the host's cos and sin made it)
     p = [float.fromhex(v) for v in json.loads(r3.stderr.split("\n")[0])["projection"]]
-    assert np.allclose(p, project.rotate(project.plane("zr", "cr"), "zi", "ci", 40.0).reshape(-1), rtol=0, atol=1e-15)
-    want, _ = project.draw(ref, 200, 100, 200, 20, 512 * 512, [150], p, omp_threads=omp_threads())
+    assert np.allclose(p, plot.rotate(plot.plane("zr", "cr"), "zi", "ci", 40.0).reshape(-1), rtol=0, atol=1e-15)
+    want, _ = plot.draw(ref, 200, 100, 200, 20, 512 * 512, [150], projection=p, omp_threads=omp_threads())
     assert np.array_equal(read_state_file(buf, 100, 200), want)

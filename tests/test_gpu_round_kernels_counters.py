@@ -24,7 +24,7 @@ import os
 import numpy as np
 import pytest
 
-import project_reference as project
+import plot_reference as plot
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ W = H = 128
 BOX = (-2.0, 2.0, -2.0, 2.0)
 THREADS, LAUNCHES, MAX_ITER, MIN_ITER = 4000, (50, 37), 2000, 20
 LEVEL = 4  # of the cell list and of the probe's mask
-PROJECTION = project.HOLOGRAM
+PROJECTION = plot.HOLOGRAM
 INSTANCES = ("anti", "focus_cells_hist", "focus_uniform_mask", "focus_uniform_hist", "project")
 CASES = [(instance, ship) for instance in INSTANCES for ship in (False, True)]
 

@@ -4,22 +4,10 @@ read from the `"projection"`, `"power"` and `"julia"` lines that --stats prints 
 
 import json
 import os
-import subprocess
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, **kw)
-
+from plot_harness import exe, run  # noqa: F401
 
 BAD_JULIA = "Invalid julia parameter (want RE,IM, two numbers from -2 to 2): "
 JULIA = ["--julia", "-0.8,0.156"]

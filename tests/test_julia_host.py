@@ -1,6 +1,7 @@
-"""The Julia render (include/cudabrot_amd.h, "Julia render") without a GPU: the CPU restatement (tests/julia_reference.c)
-pinned to a pure-Python restatement of the definition on the oracle's generator, its step pinned to z^d + c in exact
-rational arithmetic, and its independence of the OpenMP thread count."""
+"""The Julia render (include/cudabrot_amd.h, "Julia render") without a GPU, and with it every setting of the plotted
+renders' one CPU restatement (tests/plot_reference.c): pinned to a pure-Python restatement of the definitions on the
+oracle's generator -- a fixed and a sampled c, with and without rejection, a table, every formula --, its step pinned to
+z^d + c in exact rational arithmetic, and its independence of the OpenMP thread count."""
 
 import ctypes as C
 import math
@@ -9,12 +10,8 @@ from fractions import Fraction as F
 import numpy as np
 import pytest
 
-import julia_reference as julia
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return julia.load(tmp_path_factory.mktemp("julia_ref"))
+import plot_reference as plot
+from plot_harness import ref  # noqa: F401
 
 
 # ---- 1. the C restatement is the definition ---------------------------------------------------------------------------
@@ -28,13 +25,22 @@ def fma(a, b, c):
     return float(F(a) * F(b) + F(c))
 
 
-def py_step(degree, ship, cr, ci, r, i):
-    """The step of the definition in Python's own IEEE doubles -> (r', i', |z'|^2)."""
-    if degree == 2:
+def py_step(cr, ci, r, i, degree=2, ship=False, formula=0):
+    """The step of the definition in Python's own IEEE doubles -> (r', i', |z'|^2): the header's table for a formula
+    code, else the reference's step or its Burning Ship variant (degree 2), else the repeated product."""
+    if formula or degree == 2:
         ii = i * i
         t = fma(r, r, -ii)
-        nr = cr + t
-        ni = fma(abs(r) + abs(r), abs(i), ci) if ship else fma(r + r, i, ci)
+        real_part, a, b = {
+            0: (t, abs(r) + abs(r), abs(i)) if ship else (t, r + r, i),
+            1: (t, -(r + r), i),
+            2: (abs(t), r + r, i),
+            3: (abs(t), abs(r) + abs(r), abs(i)),
+            4: (t, -(abs(r) + abs(r)), i),
+            5: (abs(t), -(r + r), i),
+        }[formula]
+        nr = cr + real_part
+        ni = fma(a, b, ci)
     else:
         wr, wi = r, i
         for _ in range(degree - 1):
@@ -47,22 +53,27 @@ def py_step(degree, ship, cr, ci, r, i):
     return nr, ni, fma(ni, ni, nr * nr)
 
 
-def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, c, degree, ship, p, states):
-    """The definition, sample by sample, on the oracle's generator -> (hist, counters)."""
+def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, p, states, c=None, degree=2, ship=False, formula=0,
+            lut=None, reject=False):
+    """The definition, sample by sample, on the oracle's generator -> (hist, counters).  c None: c is the sample; reject:
+    the oracle's two shortcuts drop the sample; lut: three planes of the entry's bytes."""
     d = oracle.make_dims(w, h, *box)
-    hist = np.zeros((h, w), dtype=np.uint64)
-    cnt = dict.fromkeys(julia.COUNTER_NAMES, 0)
-    ku = fma(p[2], c[0], p[3] * c[1])
-    kv = fma(p[6], c[0], p[7] * c[1])
+    hist = np.zeros((h, w) if lut is None else (3, h, w), dtype=np.uint64)
+    planes = hist.reshape(-1, h, w)
+    cnt = dict.fromkeys(plot.COUNTER_NAMES, 0)
     for t in range(threads):
         g = oracle.Xorwow.from_buffer(states, t * states.dtype.itemsize)
         for _ in range(samples):
             sr = oracle.lib.orc_uniform_double(C.byref(g)) * 4.0 - 2.0
             si = oracle.lib.orc_uniform_double(C.byref(g)) * 4.0 - 2.0
+            cr, ci = (sr, si) if c is None else c
             cnt["samples"] += 1
+            if reject and (oracle.lib.orc_in_main_cardioid(sr, si) or oracle.lib.orc_in_order2_bulb(sr, si)):
+                cnt["rejected"] += 1
+                continue
             r, i, k = sr, si, max_iter
             for n in range(max_iter):
-                r, i, m = py_step(degree, ship, c[0], c[1], r, i)
+                r, i, m = py_step(cr, ci, r, i, degree, ship, formula)
                 if m > 4.0:
                     k = n
                     break
@@ -75,9 +86,13 @@ def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, c, degree, 
                 cnt["too_fast"] += 1
                 continue
             cnt["recorded"] += 1
+            entry = 1 if lut is None else int(lut[k])
+            weights = [(entry >> (8 * j)) & 255 for j in range(len(planes))]
+            ku = fma(p[2], cr, p[3] * ci)
+            kv = fma(p[6], cr, p[7] * ci)
             r, i = sr, si
             for _ in range(k + 1):
-                r, i, _ = py_step(degree, ship, c[0], c[1], r, i)
+                r, i, _ = py_step(cr, ci, r, i, degree, ship, formula)
                 cnt["replay_steps"] += 1
                 u = fma(p[0], r, fma(p[1], i, ku))
                 v = fma(p[4], r, fma(p[5], i, kv))
@@ -85,37 +100,58 @@ def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, c, degree, 
                     continue
                 col, row = int((u - d.min_real) / d.delta_real), int((v - d.min_imag) / d.delta_imag)
                 if 0 <= col < w and 0 <= row < h:
-                    hist[row, col] += 1
-                    cnt["increments"] += 1
+                    for j, weight in enumerate(weights):
+                        planes[j, row, col] += weight
+                        cnt["increments"] += weight
     return hist, cnt
 
 
-# (c, degree, ship, matrix): degree 2, the ship, the smallest and the largest Multibrot degree; one on another plane, so
-# that K_u and K_v from the fixed c are part of what is compared
+# The settings of the one restatement, each at 64 x 64, 8 threads x 20 samples, -m 200 -c 2 (min_iter where it is not 2).
+# A fixed c: degree 2, the ship, the smallest and the largest Multibrot degree; one on another plane, so that K_u and K_v
+# from the fixed c are part of what is compared.  Then one case per other axis: the sampled c with the product's
+# rejection and without any, a table on either source of c, each formula, and a formula with a fixed c and a table.  Each
+# was checked with py_draw to record and plot something (to reject something, to fill two planes) before it was fixed.
+C_JULIA = (-0.8, 0.156)
 TINY = {
-    "z2": ((-0.8, 0.156), 2, False, julia.IDENTITY),
-    "z2_hologram": ((-0.8, 0.156), 2, False, julia.HOLOGRAM),
-    "ship": ((-0.8, 0.156), 2, True, julia.IDENTITY),
-    "d3": ((0.0, 0.0), 3, False, julia.IDENTITY),
-    "d8": ((0.4, 0.2), 8, False, julia.IDENTITY),
+    "z2": dict(c=C_JULIA),
+    "z2_hologram": dict(c=C_JULIA, projection=plot.HOLOGRAM),
+    "ship": dict(c=C_JULIA, ship=True),
+    "d3": dict(c=(0.0, 0.0), degree=3),
+    "d8": dict(c=(0.4, 0.2), degree=8, min_iter=0),
+    "sampled_rejecting": dict(reject=True),
+    "sampled_d3_not_rejecting": dict(degree=3, reject=False),
+    "window_table_fixed_c": dict(c=C_JULIA, lut=plot.window_table(200, [(2, 6), (6, 200), (4, 12)])),
+    "demo_table_sampled": dict(lut=plot.demo_table(200), reject=True),
+    "tricorn": dict(formula=1),
+    "celtic": dict(formula=2),
+    "buffalo": dict(formula=3),
+    "perpendicular": dict(formula=4),
+    "celtic_tricorn": dict(formula=5),
+    "tricorn_fixed_c_table": dict(formula=1, c=C_JULIA, lut=plot.demo_table(200), projection=plot.HOLOGRAM),
 }
 
 
 @pytest.mark.parametrize("case", list(TINY))
 def test_c_restatement_is_the_python_restatement(ref, oracle, case):
-    c, degree, ship, p = TINY[case]
+    kw = dict(TINY[case])
     w = h = 64
     box = (-2.0, 2.0, -2.0, 2.0)
-    max_iter, min_iter, threads, samples = 200, 0 if degree == 8 else 2, 8, 20
+    max_iter, min_iter, threads, samples = 200, kw.pop("min_iter", 2), 8, 20
+    p = kw.pop("projection", plot.IDENTITY)
+    reject = kw.pop("reject", False)
     own = oracle.init_states(1337, 0, threads)
-    want, wc = py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, c, degree, ship, julia.matrix(p), own)
+    want, wc = py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, plot.matrix(p), own, reject=reject, **kw)
     states = oracle.init_states(1337, 0, threads)
-    hist, cnt = julia.draw(ref, w, h, max_iter, min_iter, threads, [samples], c, degree, ship, p, box=box, states=states)
-    assert wc["samples"] == threads * samples and wc["rejected"] == 0
+    # reject=True is what the product's rule (reject=None) gives in those cases: that rule is part of what is compared
+    hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, [samples], projection=p, box=box, states=states,
+                          reject=None if reject else False, **kw)
+    assert wc["samples"] == threads * samples and (wc["rejected"] > 0) == reject
     assert wc["recorded"] > 0 and wc["increments"] > 0
-    assert wc["never_escaped"] + wc["too_fast"] + wc["recorded"] == wc["samples"]
+    assert wc["rejected"] + wc["never_escaped"] + wc["too_fast"] + wc["recorded"] == wc["samples"]
+    if "lut" in kw:
+        assert sum(bool(plane.any()) for plane in want) >= 2
     assert cnt == wc
-    assert np.array_equal(hist, want)
+    assert hist.shape == want.shape and np.array_equal(hist, want)
     assert states.tobytes() == own.tobytes()
     assert int(hist.sum()) == cnt["increments"]
 
@@ -123,7 +159,7 @@ def test_c_restatement_is_the_python_restatement(ref, oracle, case):
 def test_the_plot_constant_comes_from_the_fixed_c(ref):
     """On the plane (c_re, c_im) every visited point lands on the pixel of the fixed c, whatever the sample."""
     c = (-0.8, 0.156)
-    hist, cnt = julia.draw(ref, 64, 64, 200, 0, 8, [20], c, projection=((0, 0, 1, 0), (0, 0, 0, 1)))
+    hist, cnt = plot.draw(ref, 64, 64, 200, 0, 8, [20], c=c, projection=((0, 0, 1, 0), (0, 0, 0, 1)))
     row, col = int((c[1] + 2.0) / 0.0625), int((c[0] + 2.0) / 0.0625)
     assert cnt["increments"] == cnt["replay_steps"] > 0
     assert int(hist[row, col]) == cnt["increments"] == int(hist.sum())
@@ -146,9 +182,9 @@ def test_step_is_z_to_the_d_plus_c(ref, degree):
     """Against z^d + c in exact rational arithmetic on the doubles.  Bound, per component: 64 * 2^-53 * (|z|^d + |c|) --
     each of the <= 7 complex multiplications contributes at most ~3 roundings' worth of relative error (one product, one
     fused sum, on magnitudes <= |z|^d), plus the addition of c: 7 * 3 + 1 = 22 units; 64 leaves a factor of two and the
-    last power of two (the bound of tests/test_power_host.py, here on the Julia restatement's own entry point)."""
+    last power of two (the bound of tests/test_power_host.py, here from the starting points of a Julia render, and with degree 2)."""
     for r, i, cr, ci in random_points(500, 200 + degree):
-        got_r, got_i, got_m = julia.step(ref, degree, False, cr, ci, r, i)
+        got_r, got_i, got_m = plot.step(ref, cr, ci, r, i, degree=degree)
         wr, wi = F(r), F(i)
         for _ in range(degree - 1):
             wr, wi = wr * F(r) - wi * F(i), wr * F(i) + wi * F(r)
@@ -156,13 +192,13 @@ def test_step_is_z_to_the_d_plus_c(ref, degree):
         err_r, err_i = abs(F(got_r) - (wr + F(cr))), abs(F(got_i) - (wi + F(ci)))
         assert err_r <= F(bound) and err_i <= F(bound), (degree, r, i, cr, ci)
         assert got_m == float(F(got_i) * F(got_i) + F(got_r * got_r))  # the test value: fma of the new point
-        assert (got_r, got_i, got_m) == py_step(degree, False, cr, ci, r, i)
+        assert (got_r, got_i, got_m) == py_step(cr, ci, r, i, degree)
 
 
 def test_ship_step_takes_the_magnitudes(ref):
     for r, i, cr, ci in random_points(200, 77):
-        assert julia.step(ref, 2, True, cr, ci, r, i) == julia.step(ref, 2, False, cr, ci, abs(r), abs(i))
-        assert julia.step(ref, 2, True, cr, ci, r, i) == py_step(2, True, cr, ci, r, i)
+        assert plot.step(ref, cr, ci, r, i, ship=True) == plot.step(ref, cr, ci, abs(r), abs(i))
+        assert plot.step(ref, cr, ci, r, i, ship=True) == py_step(cr, ci, r, i, ship=True)
 
 
 # ---- 3. the OpenMP variant ----------------------------------------------------------------------------------------------
@@ -170,12 +206,12 @@ def test_ship_step_takes_the_magnitudes(ref):
 
 @pytest.mark.parametrize("case", ["z2_hologram", "d8"])
 def test_result_does_not_depend_on_the_thread_count(ref, oracle, case):
-    c, degree, ship, p = TINY[case]
+    kw = {k: v for k, v in TINY[case].items() if k != "min_iter"}
     got = []
     for omp in (0, 4):
         states = oracle.init_states(1337, 0, 512)
-        hist, cnt = julia.draw(ref, 333, 77, 300, 0, 512, [50, 7], c, degree, ship, p, box=(-1.6, 0.9, -0.7, 0.55),
-                               omp_threads=omp, states=states)
+        hist, cnt = plot.draw(ref, 333, 77, 300, 0, 512, [50, 7], box=(-1.6, 0.9, -0.7, 0.55), omp_threads=omp,
+                              states=states, **kw)
         got.append((hist, cnt, states.tobytes()))
     assert got[0][1]["recorded"] > 100 and got[0][1]["increments"] > 100  # not empty
     assert np.array_equal(got[0][0], got[1][0]) and got[0][1] == got[1][1] and got[0][2] == got[1][2]

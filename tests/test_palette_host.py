@@ -2,8 +2,8 @@
 
   1. cb_palette_from_stops against a restatement in Python integers;
   2. what it refuses;
-  3. the tests' CPU restatement (tests/palette_reference.c) against the restatements that were there before it
-     (project_reference.c, julia_reference.c), so that the new yardstick is itself checked;
+  3. the tests' CPU restatement (tests/plot_reference.c) with a table against the same function without one -- two
+     settings of the one restatement, which tests/test_julia_host.py pins to the definition either way;
   4. the names in the header and the package.
 """
 
@@ -12,9 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import julia_reference as julia
-import palette_reference as palette
-import project_reference as project
+import plot_reference as plot
+from plot_harness import ref  # noqa: F401
 
 INVALID = 1  # hipErrorInvalidValue
 
@@ -108,7 +107,7 @@ def test_sizes_and_pointers_refused(cb):
     assert cb.lib.cb_palette_from_stops(one, 1, out.ctypes.data, 4) == 0 and np.all(out == 1 | 2 << 8 | 3 << 16)
 
 
-# ---- 3. the restatement against the restatements before it -------------------------------------------------------------
+# ---- 3. the restatement with a table against itself without one -----------------------------------------------------
 
 W = H = 64
 THREADS, MAX, MIN, LAUNCHES = 256, 200, 5, [3, 2]
@@ -116,37 +115,36 @@ WINDOWS = [(5, 20), (20, 80), (40, 200)]  # G and B overlap
 C_JULIA = (-0.8, 0.156)
 
 
-@pytest.fixture(scope="module")
-def refs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("palette_refs")
-    return palette.load(d), project.load(d), julia.load(d)
+def with_table(ref, lut, **case):
+    """-> (hist [3, h, w], counters, zero_entry_steps)."""
+    extra = {}
+    hist, cnt = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, lut=lut, extra=extra, **case)
+    return hist, cnt, extra["zero_entry_steps"]
 
 
-def earlier(refs, c, ship, degree, max_iter, min_iter, projection):
-    """The same render by the restatement that was there before: project_reference (sampled c, degree 2) or
-    julia_reference (a fixed c)."""
-    _, proj, jul = refs
-    if c is None:
-        return project.draw(proj, W, H, max_iter, min_iter, THREADS, LAUNCHES, projection, ship=ship)
-    return julia.draw(jul, W, H, max_iter, min_iter, THREADS, LAUNCHES, c, degree, ship, projection)
+def plain(ref, c, ship, degree, max_iter, min_iter, projection):
+    """The same render by the same restatement without a table: one plane of weight 1."""
+    return plot.draw(ref, W, H, max_iter, min_iter, THREADS, LAUNCHES, c=c, ship=ship, degree=degree,
+                     projection=projection)
 
 
 CASES = {
-    "mandelbrot": dict(c=None, ship=False, degree=2, projection=palette.IDENTITY),
-    "mandelbrot_hologram": dict(c=None, ship=False, degree=2, projection=palette.HOLOGRAM),
-    "ship": dict(c=None, ship=True, degree=2, projection=palette.IDENTITY),
-    "julia": dict(c=C_JULIA, ship=False, degree=2, projection=palette.IDENTITY),
-    "julia_degree3_zr_cr": dict(c=C_JULIA, ship=False, degree=3, projection=palette.ZR_CR),
-    "julia_ship": dict(c=C_JULIA, ship=True, degree=2, projection=palette.HOLOGRAM),
+    "mandelbrot": dict(c=None, ship=False, degree=2, projection=plot.IDENTITY),
+    "mandelbrot_hologram": dict(c=None, ship=False, degree=2, projection=plot.HOLOGRAM),
+    "ship": dict(c=None, ship=True, degree=2, projection=plot.IDENTITY),
+    "julia": dict(c=C_JULIA, ship=False, degree=2, projection=plot.IDENTITY),
+    "julia_degree3_zr_cr": dict(c=C_JULIA, ship=False, degree=3, projection=plot.ZR_CR),
+    "julia_ship": dict(c=C_JULIA, ship=True, degree=2, projection=plot.HOLOGRAM),
 }
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_constant_table_is_the_plain_render_in_every_plane(refs, name):
+def test_constant_table_is_the_plain_render_in_every_plane(ref, name):
+    """Table against no table: two settings of the one restatement."""
     case = CASES[name]
     lut = np.full(MAX, 0x010101, dtype=np.uint32)
-    hist, cnt, zero_steps = palette.draw(refs[0], W, H, MAX, MIN, THREADS, LAUNCHES, lut, **case)
-    want, wc = earlier(refs, max_iter=MAX, min_iter=MIN, **case)
+    hist, cnt, zero_steps = with_table(ref, lut, **case)
+    want, wc = plain(ref, max_iter=MAX, min_iter=MIN, **case)
     assert wc["recorded"] > 0 and wc["increments"] > 0
     for j in range(3):
         assert np.array_equal(hist[j], want), (name, j)
@@ -155,13 +153,14 @@ def test_constant_table_is_the_plain_render_in_every_plane(refs, name):
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_window_table_is_the_plain_render_of_each_window(refs, name):
+def test_window_table_is_the_plain_render_of_each_window(ref, name):
+    """Each plane against the render without a table at that window's -m and -c: two settings of the one restatement."""
     case = CASES[name]
-    lut = palette.window_table(MAX, WINDOWS)
-    hist, cnt, zero_steps = palette.draw(refs[0], W, H, MAX, MIN, THREADS, LAUNCHES, lut, **case)
+    lut = plot.window_table(MAX, WINDOWS)
+    hist, cnt, zero_steps = with_table(ref, lut, **case)
     total = 0
     for j, (lo, hi) in enumerate(WINDOWS):
-        want, wc = earlier(refs, max_iter=hi, min_iter=lo, **case)
+        want, wc = plain(ref, max_iter=hi, min_iter=lo, **case)
         assert np.array_equal(hist[j], want), (name, j)
         total += wc["increments"]
     assert cnt["increments"] == total == int(hist.sum())
@@ -169,22 +168,22 @@ def test_window_table_is_the_plain_render_of_each_window(refs, name):
     assert zero_steps == 0
 
 
-def test_weights_scale_the_planes_and_zero_entries_are_counted(refs):
+def test_weights_scale_the_planes_and_zero_entries_are_counted(ref):
     lut = np.full(MAX, 255 | 2 << 16, dtype=np.uint32)  # R 255, G 0, B 2
     lut[50:] = 0
-    hist, cnt, zero_steps = palette.draw(refs[0], W, H, MAX, MIN, THREADS, LAUNCHES, lut)
-    want, wc = earlier(refs, None, False, 2, 50, MIN, palette.IDENTITY)  # the orbits with k < 50
-    full, fc = earlier(refs, None, False, 2, MAX, MIN, palette.IDENTITY)
+    hist, cnt, zero_steps = with_table(ref, lut)
+    want, wc = plain(ref, None, False, 2, 50, MIN, plot.IDENTITY)  # the orbits with k < 50
+    full, fc = plain(ref, None, False, 2, MAX, MIN, plot.IDENTITY)
     assert np.array_equal(hist[0], 255 * want) and not hist[1].any() and np.array_equal(hist[2], 2 * want)
     assert cnt["increments"] == 257 * wc["increments"]
     assert cnt["recorded"] == fc["recorded"] and cnt["replay_steps"] == fc["replay_steps"]
     assert zero_steps == fc["replay_steps"] - wc["replay_steps"] > 0
 
 
-def test_bits_24_to_31_are_not_read(refs):
-    lut = palette.demo_table(MAX)
-    a = palette.draw(refs[0], W, H, MAX, MIN, THREADS, LAUNCHES, lut)
-    b = palette.draw(refs[0], W, H, MAX, MIN, THREADS, LAUNCHES, lut | np.uint32(0xAB000000))
+def test_bits_24_to_31_are_not_read(ref):
+    lut = plot.demo_table(MAX)
+    a = with_table(ref, lut)
+    b = with_table(ref, lut | np.uint32(0xAB000000))
     assert np.array_equal(a[0], b[0]) and a[1:] == b[1:]
 
 

@@ -4,22 +4,10 @@ read from the `"projection"` and `"power"` lines that --stats prints before any 
 
 import json
 import os
-import subprocess
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, **kw)
-
+from plot_harness import exe, run  # noqa: F401
 
 BAD_POWER = "Invalid power (want an integer from 3 to 8): "
 POWER = ["--power", "3"]

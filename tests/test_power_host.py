@@ -1,6 +1,6 @@
 """The Multibrot render (include/cudabrot_amd.h, "Multibrot step") without a GPU: the CPU restatement
-(tests/power_reference.c) pinned to the oracle through its degree-2 driver, its step pinned to z^d + c in exact rational
-arithmetic, and the Python side's constants."""
+(tests/plot_reference.c) pinned to the oracle through its degree-2 driver without rejection, its step pinned to z^d + c
+in exact rational arithmetic, and the Python side's constants."""
 
 import ctypes as C
 import math
@@ -9,12 +9,8 @@ from fractions import Fraction as F
 import numpy as np
 import pytest
 
-import power_reference as power
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return power.load(tmp_path_factory.mktemp("power_ref"))
+import plot_reference as plot
+from plot_harness import ref  # noqa: F401
 
 
 # ---- 1. the driver is the oracle's ------------------------------------------------------------------------------------
@@ -28,8 +24,8 @@ ANCHOR_CASES = {
 @pytest.mark.parametrize("case", sorted(ANCHOR_CASES))
 @pytest.mark.parametrize("omp", [0, 4])
 def test_degree_2_driver_is_the_oracle_without_rejection(ref, oracle, case, omp):
-    """Degree 2 in the restatement is the canonical z^2 + c step without cardioid / bulb rejection.  The oracle rejects
-    those samples unseen; where none of them would have escaped below max (asserted here, sample by sample), the two
+    """Degree 2 with rejection switched off is the canonical z^2 + c step on every sample.  The oracle rejects the
+    cardioid's and the bulb's samples unseen; where none of them would have escaped below max (asserted here, sample by sample), the two
     differ only in how they count them: never_escaped += rejected, iterate_steps += max * rejected."""
     w, h, box = ANCHOR_CASES[case]
     max_iter, min_iter, threads, launches = 500, 20, 1024, (50, 7)
@@ -46,7 +42,7 @@ def test_degree_2_driver_is_the_oracle_without_rejection(ref, oracle, case, omp)
                 assert oracle.lib.orc_iterate_mandelbrot(cr, ci, max_iter) == max_iter, (cr, ci)
     want_states = oracle.init_states(1337, 0, threads)
     want_hist = np.zeros((h, w), dtype=np.uint64)
-    want = dict.fromkeys(power.COUNTER_NAMES, 0)
+    want = dict.fromkeys(plot.COUNTER_NAMES, 0)
     for samples in launches:
         _, cnt = oracle.render(w, h, max_iter, min_iter, threads, 1, box=box, samples_per_thread=samples, hist=want_hist,
                                states=want_states)
@@ -54,8 +50,8 @@ def test_degree_2_driver_is_the_oracle_without_rejection(ref, oracle, case, omp)
             want[name] += cnt[name]
     assert want["rejected"] == rejected > 1000 and want["recorded"] > 100 and want["increments"] > 1000
     states = oracle.init_states(1337, 0, threads)
-    hist, cnt = power.draw(ref, w, h, max_iter, min_iter, threads, launches, 2, power.IDENTITY, box=box, omp_threads=omp,
-                           states=states)
+    hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, reject=False, box=box, omp_threads=omp,
+                          states=states)
     assert np.array_equal(hist, want_hist)
     assert states.tobytes() == want_states.tobytes() == own.tobytes()
     for name in ("samples", "too_fast", "recorded", "replay_steps", "increments"):
@@ -85,7 +81,7 @@ def test_step_is_z_to_the_d_plus_c(ref, degree):
     room for the last power of two."""
     worst = 0.0
     for r, i, cr, ci in random_points(1000, 100 + degree):
-        got_r, got_i, _ = power.step(ref, degree, cr, ci, r, i)
+        got_r, got_i, _ = plot.step(ref, cr, ci, r, i, degree=degree)
         wr, wi = F(r), F(i)
         for _ in range(degree - 1):
             wr, wi = wr * F(r) - wi * F(i), wr * F(i) + wi * F(r)
@@ -113,14 +109,14 @@ def test_degree_3_loop_is_the_step_written_out(ref):
         w3i = fma(w2r, i, s)
         nr, ni = cr + w3r, ci + w3i
         m = fma(ni, ni, nr * nr)
-        got = power.step(ref, 3, cr, ci, r, i)
+        got = plot.step(ref, cr, ci, r, i, degree=3)
         assert [x.hex() for x in got] == [nr.hex(), ni.hex(), m.hex()]
 
 
 def test_escape_test_is_fma_of_the_new_point(ref):
     for degree in range(3, 9):
         for r, i, cr, ci in random_points(50, 50 + degree):
-            nr, ni, m = power.step(ref, degree, cr, ci, r, i)
+            nr, ni, m = plot.step(ref, cr, ci, r, i, degree=degree)
             assert m == float(F(ni) * F(ni) + F(nr * nr))
 
 

@@ -5,24 +5,11 @@ parsed matrix is read from the `"projection"` line that --stats prints before an
 import json
 import math
 import os
-import subprocess
 
 import pytest
 
-import project_reference as project
-
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, **kw)
-
+import plot_reference as plot
+from plot_harness import exe, run  # noqa: F401
 
 BAD_PROJECTION = "Invalid projection (want a,b,c,d:e,f,g,h, eight finite numbers): "
 BAD_PLANE = "Invalid plane (want X,Y, two different axes of zr, zi, cr, ci): "
@@ -148,7 +135,7 @@ def test_planes_and_quarter_turns_give_exact_matrices(exe, tmp_path, args, want)
 
 def test_a_general_rotation_uses_the_hosts_cos_and_sin(exe, tmp_path):
     got, _ = parsed_matrix(exe, tmp_path, "--rotate", "zr,cr:30", "--rotate", "zi,ci:50")
-    want = project.HOLOGRAM.reshape(-1)
+    want = plot.HOLOGRAM.reshape(-1)
     # the run is defined by the matrix the binary prints; libm's last bit may differ from Python's
     assert all(math.isclose(g, w, rel_tol=0.0, abs_tol=4 * 2.0 ** -53) for g, w in zip(got, want))
     assert got[1] == 0.0 and got[3] == 0.0 and got[4] == 0.0 and got[6] == 0.0

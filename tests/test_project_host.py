@@ -1,5 +1,5 @@
 """The projected render (include/cudabrot_amd.h, "Projected render") without a GPU: the CPU restatement
-(tests/project_reference.c) pinned to the oracle through the identity matrix, and to an independent count through the
+(tests/plot_reference.c) pinned to the oracle through the identity matrix, and to an independent count through the
 c-plane."""
 
 import ctypes as C
@@ -7,12 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import project_reference as project
-
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return project.load(tmp_path_factory.mktemp("project_ref"))
+import plot_reference as plot
+from plot_harness import ref  # noqa: F401
 
 
 # (w, h, box, max_iter, min_iter, threads, passes, ship): a dyadic canvas, a 333 x 77 one, a cropped Burning Ship
@@ -31,8 +27,8 @@ def test_identity_matrix_is_the_oracle(ref, oracle, case, omp):
     want_hist, want_cnt = oracle.render(w, h, max_iter, min_iter, threads, passes, box=box, states=want_states,
                                         burning_ship=ship)
     states = oracle.init_states(1337, 0, threads)
-    hist, cnt = project.draw(ref, w, h, max_iter, min_iter, threads, [50] * passes, project.IDENTITY, box=box, ship=ship,
-                             omp_threads=omp, states=states)
+    hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, [50] * passes, projection=plot.IDENTITY, box=box, ship=ship,
+                          omp_threads=omp, states=states)
     assert want_cnt["increments"] > 0 and want_cnt["recorded"] > 0
     assert np.array_equal(hist, want_hist)
     assert states.tobytes() == want_states.tobytes()
@@ -40,9 +36,9 @@ def test_identity_matrix_is_the_oracle(ref, oracle, case, omp):
 
 
 def test_plane_zr_zi_is_the_identity():
-    assert np.array_equal(project.plane("zr", "zi"), np.array(project.IDENTITY))
-    assert np.array_equal(project.plane("cr", "ci"), np.array(project.C_PLANE))
-    assert np.array_equal(project.plane("zr", "cr"), np.array(project.ZR_CR))
+    assert np.array_equal(plot.plane("zr", "zi"), np.array(plot.IDENTITY))
+    assert np.array_equal(plot.plane("cr", "ci"), np.array(plot.C_PLANE))
+    assert np.array_equal(plot.plane("zr", "cr"), np.array(plot.ZR_CR))
 
 
 def test_c_plane_puts_the_whole_orbit_on_the_pixel_of_c(ref, oracle):
@@ -76,7 +72,7 @@ def test_c_plane_puts_the_whole_orbit_on_the_pixel_of_c(ref, oracle):
                 want[row, col] += k + 1
             else:
                 off_canvas += 1
-    hist, cnt = project.draw(ref, w, h, max_iter, min_iter, threads, [samples], project.C_PLANE, box=box, states=st)
+    hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, [samples], projection=plot.C_PLANE, box=box, states=st)
     assert recorded > 50 and off_canvas > 0
     assert cnt["recorded"] == recorded
     assert np.array_equal(hist, want)
@@ -85,7 +81,7 @@ def test_c_plane_puts_the_whole_orbit_on_the_pixel_of_c(ref, oracle):
 
 
 def test_a_general_point_is_four_fused_operations(ref):
-    """project_point against the definition written out in exact rational arithmetic, rounded once per operation."""
+    """plot_point against the definition written out in exact rational arithmetic, rounded once per operation."""
     from fractions import Fraction as F
 
     def fma(a, b, c):
@@ -95,7 +91,7 @@ def test_a_general_point_is_four_fused_operations(ref):
     for _ in range(200):
         p = rng.uniform(-2.0, 2.0, 8)
         zr, zi, cr, ci = rng.uniform(-2.0, 2.0, 4)
-        u, v = project.point(ref, p, zr, zi, cr, ci)
+        u, v = plot.point(ref, p, zr, zi, cr, ci)
         ku = fma(p[2], cr, float(F(p[3]) * F(ci)))
         kv = fma(p[6], cr, float(F(p[7]) * F(ci)))
         assert u == fma(p[0], zr, fma(p[1], zi, ku))
@@ -103,7 +99,7 @@ def test_a_general_point_is_four_fused_operations(ref):
 
 
 def test_hologram_matrix_is_a_pair_of_orthonormal_rows():
-    p = np.array(project.HOLOGRAM)
+    p = np.array(plot.HOLOGRAM)
     assert np.allclose(p @ p.T, np.eye(2), atol=1e-15)
     nonzero = p[p != 0.0]
     assert nonzero.size == 4 and not np.any(nonzero == np.round(nonzero))  # irrational entries, none exact
