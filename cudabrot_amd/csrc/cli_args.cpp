@@ -1,0 +1,554 @@
+// cli_args.cpp -- the parser of the `cudabrot` command line (cli_args.h): the reference's flags and messages
+// (cudabrot.cu:579-754: usage :579-620, flags :662-754; usage -> exit 0) and the extension flags, which the reference
+// answers with its usage text.  Everything a flag is lies in two tables: the flag table (name, kind of value, store;
+// a store returns the message of a bad value) and, for the flags that select a render of their own, the refusal table
+// (which other flags that render does not combine with, and in which order that is said).
+#include "cli_args.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <functional>
+#include <vector>
+
+namespace cb {
+namespace {
+
+// One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
+int axis_of(const char *text, char after, const char **rest) {
+  static const char *const kNames[4] = {"zr", "zi", "cr", "ci"};
+  for (int j = 0; j < 4; ++j) {
+    if (strncmp(text, kNames[j], 2) == 0 && text[2] == after) {
+      *rest = text + (after ? 3 : 2);
+      return j;
+    }
+  }
+  return -1;
+}
+
+// --project a,b,c,d:e,f,g,h: eight finite numbers, strtod's syntax (hexfloats included).
+bool parse_projection(const char *text, double out[8]) {
+  const char *at = text;
+  for (int j = 0; j < 8; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    out[j] = strtod(at, &end);
+    if (end == at || !isfinite(out[j]) || *end != (j == 7 ? 0 : (j == 3 ? ':' : ','))) return false;
+    at = end + 1;
+  }
+  return true;
+}
+
+// --julia RE,IM: two finite numbers in [-2, 2], strtod's syntax (hexfloats included).
+bool parse_julia(const char *text, double out[2]) {
+  const char *at = text;
+  for (int j = 0; j < 2; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    out[j] = strtod(at, &end);
+    if (end == at || !(out[j] >= -2.0 && out[j] <= 2.0) || *end != (j == 1 ? 0 : ',')) return false;
+    at = end + 1;
+  }
+  return true;
+}
+
+// --palette K:RRGGBB[,K:RRGGBB...]: 1 to CB_PALETTE_MAX_STOPS stops, K decimal digits and strictly ascending, the colour
+// six hex digits.  Returns the number of stops, 0 for anything else.
+int parse_palette(const char *text, cb_palette_stop out[CB_PALETTE_MAX_STOPS]) {
+  const char *at = text;
+  int n = 0;
+  for (;;) {
+    if (n == CB_PALETTE_MAX_STOPS || *at < '0' || *at > '9') return 0;
+    long k = 0;
+    for (; *at >= '0' && *at <= '9'; ++at) {
+      k = k * 10 + (*at - '0');
+      if (k > 0x7fffffffL) return 0;
+    }
+    if (*at++ != ':' || (n > 0 && k <= out[n - 1].k)) return 0;
+    int v[3] = {0, 0, 0};
+    for (int j = 0; j < 6; ++j, ++at) {
+      const char ch = *at;
+      const int digit = (ch >= '0' && ch <= '9') ? ch - '0' : (ch >= 'a' && ch <= 'f') ? ch - 'a' + 10 : (ch >= 'A' && ch <= 'F') ? ch - 'A' + 10 : -1;
+      if (digit < 0) return 0;
+      v[j / 2] = v[j / 2] * 16 + digit;
+    }
+    out[n++] = {(int) k, v[0], v[1], v[2]};
+    if (*at == 0) return n;
+    if (*at++ != ',') return 0;
+  }
+}
+
+// --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane.  An integer multiple of 90
+// degrees uses exact 0 and +-1 (a permutation of the two columns with signs); otherwise the host's cos and sin.
+bool rotate_projection(const char *text, double p[8]) {
+  const char *rest = nullptr;
+  const int x = axis_of(text, ',', &rest);
+  const int y = x < 0 ? -1 : axis_of(rest, ':', &rest);
+  if (x < 0 || y < 0 || x == y || *rest == 0 || *rest == ' ' || *rest == '\t') return false;
+  char *end = nullptr;
+  const double degrees = strtod(rest, &end);
+  if (end == rest || *end != 0 || !isfinite(degrees)) return false;
+  double co, si;
+  const double quarters = degrees / 90.0;
+  if (quarters == floor(quarters)) {
+    const int q = (int) fmod(fmod(quarters, 4.0) + 4.0, 4.0);
+    co = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
+    si = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
+  } else {
+    const double radians = degrees * (M_PI / 180.0);
+    co = cos(radians);
+    si = sin(radians);
+  }
+  for (int row = 0; row < 2; ++row) {
+    const double a = p[4 * row + x], b = p[4 * row + y];
+    p[4 * row + x] = (a * co - b * si) + 0.0;  // (+ 0.0: an exact zero is +0)
+    p[4 * row + y] = (a * si + b * co) + 0.0;
+  }
+  return true;
+}
+
+// The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
+const char kUsageBody[] =
+    "Options may be one or more of the following:\n"
+    "  --help: Prints these instructions.\n"
+    "  -d <device number>: Sets which GPU to use. Defaults to GPU 0.\n"
+    "  -o <output file name>: If provided, the rendered image will be saved\n"
+    "     to a .pgm file with the given name. Otherwise, saves the image\n"
+    "     to output.pgm.\n"
+    "  -m <max escape iterations>: The maximum number of iterations to use\n"
+    "     before giving up on seeing whether a point escapes.\n"
+    "  -c <min escape iterations>: If a point escapes before this number of\n"
+    "     iterations, it will be ignored.\n"
+    "  -g <gamma correction>: A gamma-correction value to use on the\n"
+    "     resulting image. If negative, no gamma correction will occur.\n"
+    "  -t <seconds to run>: A number of seconds to run the calculation for.\n"
+    "     Defaults to 10.0. If negative, the program will run continuously\n"
+    "     and will terminate (saving the image) when it receives a SIGINT.\n"
+    "  -w <width>: The width of the output image, in pixels. Defaults to\n"
+    "     1000.\n"
+    "  -h <height>: The height of the output image, in pixels. Defaults to\n"
+    "     1000.\n"
+    "  -s <save/load file>: If provided, this gives a file name into which\n"
+    "     the rendering buffer will be saved, for future continuation.\n"
+    "     If the program is loaded and the file exists, the buffer will be\n"
+    "     filled with the contents of the file, but the dimensions must\n"
+    "     match. Note that this file may be huge for high-resolution images.\n"
+    "\n"
+    "The following settings control the location of the output image on the\n"
+    "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
+    "set domain (-2-2i to 2+2i). So these settings can be used to save\n"
+    "memory or \"crop\" the output, but won't otherwise speed up rendering:\n"
+    "  --min-real <min real>: The minimum value along the real axis to\n"
+    "             include in the output image. Defaults to -2.0.\n"
+    "  --max-real <max real>: The maximum value along the real axis to\n"
+    "             include in the output image. Defaults to 2.0.\n"
+    "  --min-imag <min imag>: The minimum value along the imaginary axis to\n"
+    "             include in the output image. Defaults to -2.0.\n"
+    "  --max-imag <max imag>: The maximum value along the imaginary axis to\n"
+    "             include in the output image. Defaults to 2.0.\n";
+
+// Usage always ends the process with status 0, also after a bad argument (cudabrot.cu:619).
+[[noreturn]] void usage_and_exit(const char *program) {
+  printf("Usage: %s [options]\n\n", program);
+  fputs(kUsageBody, stdout);
+  exit(0);
+}
+
+// ---- argument table ----------------------------------------------------------------------------
+
+enum class Value { kNone, kInt, kLong, kDouble, kText };  // kInt: truncated to int like the reference's flags
+
+struct Flag {
+  const char *name;
+  Value value;
+  const char *missing_value_message;  // nullptr: "Argument %s needs a value."
+  bool revalidates_canvas;            // -w -h --min/max-*: canvas re-checked at once (:704-749)
+  // stores the value; returns kOk, or the message of a bad value, printed as "<message>: <the value's text>"
+  std::function<const char *(Settings &, long, double, const char *)> store;
+};
+const char *const kOk = nullptr;
+
+#define CB_TEXT_OF_(x) #x
+#define CB_TEXT_OF(x) CB_TEXT_OF_(x)  // a macro's value as text, for a message
+
+const std::vector<Flag> &flag_table() {
+  static const std::vector<Flag> table = {
+      {"-d", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) { s.device = (int) i; return kOk; }},
+      {"-o", Value::kText, "Missing output file name.", false,
+       [](Settings &s, long, double, const char *t) { s.output_image = t; return kOk; }},
+      {"-s", Value::kText, "Missing in-progress buffer file name.", false,
+       [](Settings &s, long, double, const char *t) { s.inprogress_file = t; return kOk; }},
+      {"-m", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.iterations.max_escape_iterations = (int) i;
+         if (s.iterations.max_escape_iterations > 60000) {  // cudabrot.cu:692-695
+           printf("Warning: Using a high number of iterations may cause the "
+                  "program respond slowly to Ctrl+C or time running out.\n");
+         }
+         return kOk;
+       }},
+      {"-c", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) { s.iterations.min_escape_iterations = (int) i; return kOk; }},
+      {"-w", Value::kInt, nullptr, true,
+       [](Settings &s, long i, double, const char *) { s.canvas.w = (int) i; return kOk; }},
+      {"-h", Value::kInt, nullptr, true,
+       [](Settings &s, long i, double, const char *) { s.canvas.h = (int) i; return kOk; }},
+      {"-g", Value::kDouble, nullptr, false,
+       [](Settings &s, long, double d, const char *) { s.gamma_correction = d; return kOk; }},
+      {"-t", Value::kDouble, nullptr, false,
+       [](Settings &s, long, double d, const char *) { s.seconds_to_run = d; return kOk; }},
+      {"--min-real", Value::kDouble, nullptr, true,
+       [](Settings &s, long, double d, const char *) { s.canvas.min_real = d; return kOk; }},
+      {"--max-real", Value::kDouble, nullptr, true,
+       [](Settings &s, long, double d, const char *) { s.canvas.max_real = d; return kOk; }},
+      {"--min-imag", Value::kDouble, nullptr, true,
+       [](Settings &s, long, double d, const char *) { s.canvas.min_imag = d; return kOk; }},
+      {"--max-imag", Value::kDouble, nullptr, true,
+       [](Settings &s, long, double d, const char *) { s.canvas.max_imag = d; return kOk; }},
+      // extensions, which the reference answers with its usage text
+      // --passes N: the run length in reference passes, not by the clock
+      {"--passes", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) { s.fixed_passes = i < 0 ? 0 : i; return kOk; }},
+      // --kernel simple|timed|full: a validation variant of the draw kernel (include/cudabrot_amd.h, CB_KERNEL_*)
+      {"--kernel", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.kernel_variant = (strcmp(t, "simple") == 0)  ? CB_KERNEL_SIMPLE
+                            : (strcmp(t, "timed") == 0) ? CB_KERNEL_TIMED
+                            : (strcmp(t, "full") == 0)  ? CB_KERNEL_FULL_ITERATE
+                                                        : CB_KERNEL_DEFAULT;
+         return kOk;
+       }},
+      // --stats: the counters of the run (and what defines a projected run) as JSON lines on stderr
+      {"--stats", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.print_stats = true; return kOk; }},
+      // --channel MAX:MIN:FILE, up to CB_MAX_CHANNELS times: one image per iteration window from one fused render
+      {"--channel", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         int mx = 0, mn = 0, used = 0;
+         if (s.n_channels >= CB_MAX_CHANNELS || sscanf(t, "%d:%d:%n", &mx, &mn, &used) < 2 || used == 0 ||
+             t[used] == 0) {
+           return "Invalid channel (want MAX:MIN:FILE, at most " CB_TEXT_OF(CB_MAX_CHANNELS) " of them)";
+         }
+         s.channel_window[s.n_channels] = {mx, mn};
+         s.channel_file[s.n_channels] = t + used;
+         s.n_channels++;
+         return kOk;
+       }},
+      // --gpus N: the render sharded over devices -d .. -d + N - 1, summed once at the end
+      {"--gpus", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) { s.gpus = (i < 1) ? 1 : (i > 64 ? 64 : (int) i); return kOk; }},
+      // --burning-ship: the reference's compile-time variant (cudabrot.cu:15-17) as a flag
+      {"--burning-ship", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.burning_ship = true; return kOk; }},
+      // --anti: the anti-Buddhabrot, the orbits that never escape (include/cudabrot_amd.h, CB_KERNEL_FLAG_ANTI)
+      {"--anti", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.anti = true; return kOk; }},
+      // --focus, --focus-level L, --focus-probe PASSES, --focus-dilate D: a cropped canvas sampled only from the cells of
+      // the plane whose samples reach it (include/cudabrot_amd.h, "Focused render"); each value flag turns --focus on
+      {"--focus", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.focus = true; return kOk; }},
+      {"--focus-level", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i < CB_FOCUS_MIN_LEVEL || i > CB_FOCUS_MAX_LEVEL) return "Invalid focus level (want 4 to 10)";
+         s.focus_level = (int) i;
+         return kOk;
+       }},
+      {"--focus-probe", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i < 1) return "Invalid focus probe (want at least 1 pass)";
+         s.focus_probe = i;
+         return kOk;
+       }},
+      {"--focus-dilate", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.focus = true;
+         if (i < 0) return "Invalid focus dilation (want 0 or more cells)";
+         s.focus_dilate = (int) i;
+         return kOk;
+       }},
+      // --project a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG: the plane of the 4-D set (z_re, z_im, c_re, c_im) the
+      // orbits are plotted on (include/cudabrot_amd.h, "Projected render")
+      {"--project", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.project_given = true;
+         return parse_projection(t, s.projection) ? kOk : "Invalid projection (want a,b,c,d:e,f,g,h, eight finite numbers)";
+       }},
+      {"--plane", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         const char *rest = nullptr;
+         const int x = axis_of(t, ',', &rest);
+         const int y = x < 0 ? -1 : axis_of(rest, 0, &rest);
+         s.plane_given = true;
+         if (x < 0 || y < 0 || x == y) return "Invalid plane (want X,Y, two different axes of zr, zi, cr, ci)";
+         // the rotations start from the plane
+         if (s.rotate_given) return "Invalid plane (--plane goes before the first --rotate)";
+         for (int j = 0; j < 8; ++j) s.projection[j] = 0.0;
+         s.projection[x] = 1.0;
+         s.projection[4 + y] = 1.0;
+         return kOk;
+       }},
+      {"--rotate", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.rotate_given = true;
+         if (s.project_given) return kOk;  // refused after parsing (the refusal table); the matrix given is not touched
+         return rotate_projection(t, s.projection)
+                    ? kOk
+                    : "Invalid rotation (want X,Y:DEG, two different axes of zr, zi, cr, ci and a finite angle)";
+       }},
+      // --power D: the Multibrot step z^D + c, D = 3 .. 8, on the projected path (include/cudabrot_amd.h, "Multibrot
+      // step"); text: a value that is no integer gets the flag's own message
+      {"--power", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         char *end = nullptr;
+         const long d = strtol(t, &end, 10);
+         if (t[0] == 0 || *end != 0 || d < CB_POWER_MIN || d > CB_POWER_MAX) {
+           return "Invalid power (want an integer from 3 to 8)";
+         }
+         s.power = (int) d;
+         return kOk;
+       }},
+      // --julia RE,IM: the Buddhabrot of the Julia set of c = RE + IM i: c fixed, the samples are the starting points;
+      // with --power or --burning-ship, on any plane (include/cudabrot_amd.h, "Julia render")
+      {"--julia", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.julia = true;
+         return parse_julia(t, s.julia_c) ? kOk : "Invalid julia parameter (want RE,IM, two numbers from -2 to 2)";
+       }},
+      // --palette K:RRGGBB[,K:RRGGBB...]: orbits coloured by their escape index: colour stops interpolated into a table of
+      // -m entries, three planes of integer weights, -o receives a 16-bit PPM; on the projected path with any plane,
+      // --power, --julia or --burning-ship (include/cudabrot_amd.h, "Palette render")
+      {"--palette", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.n_palette_stops = parse_palette(t, s.palette_stops);
+         return s.palette() ? kOk : "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops)";
+       }},
+      // --formula NAME: another step of the quadratic family, on the projected path with any plane, --julia or --palette
+      // (include/cudabrot_amd.h, "Formula step")
+      {"--formula", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         static const char *const kNames[CB_FORMULA_MAX] = {"tricorn", "celtic", "buffalo", "perpendicular",
+                                                            "celtic-tricorn"};  // codes 1 .. CB_FORMULA_MAX
+         for (int code = 1; code <= CB_FORMULA_MAX; ++code) {
+           if (strcmp(t, kNames[code - 1]) == 0) {
+             s.formula = code;
+             s.formula_name = kNames[code - 1];
+             return kOk;
+           }
+         }
+         return "Invalid formula (want tricorn, celtic, buffalo, perpendicular or celtic-tricorn)";
+       }},
+      // --seed N: the generator's seed, 64 bits wide (rocrand_init)
+      {"--seed", Value::kLong, nullptr, false,
+       [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; return kOk; }},
+      // --rng-state FILE: the generator states beside the -s buffer, so that a resumed run continues the sample stream
+      {"--rng-state", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) { s.rng_state_file = t; return kOk; }},
+      // --state-format native|raw: raw is the -s file as the reference's bare buffer, uint32 when every count fits
+      {"--state-format", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.raw_state = strcmp(t, "raw") == 0;
+         return s.raw_state || strcmp(t, "native") == 0 ? kOk : "Invalid state format (want native or raw)";
+       }},
+      // --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W: the three --channel planes composed into one
+      // 16-bit PPM (include/cudabrot_amd.h, "Colour image")
+      {"--color", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) { s.color_file = t; return kOk; }},
+      {"--compose", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         if (strcmp(t, "rgb") == 0) {
+           s.color.compose = CB_COMPOSE_RGB;
+         } else if (strcmp(t, "hsl") == 0) {
+           s.color.compose = CB_COMPOSE_HSL;
+         } else {
+           return "Invalid compose mode (want rgb or hsl)";
+         }
+         return kOk;
+       }},
+      {"--hue-shift", Value::kDouble, nullptr, false,
+       [](Settings &s, long, double d, const char *) {
+         if (!isfinite(d)) return "Invalid hue shift (want a finite number)";
+         s.color.hue_shift = d;
+         return kOk;
+       }},
+      {"--color-stretch", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         // B:W, two numbers: B % of the pixels go black, W % white (finite, B >= 0, W >= 0, B + W < 100)
+         char *end = nullptr;
+         const double b = strtod(t, &end);
+         bool ok = end != t && *end == ':';
+         double w = 0.0;
+         if (ok) {
+           const char *rest = end + 1;
+           w = strtod(rest, &end);
+           ok = end != rest && *end == 0;
+         }
+         if (!(ok && isfinite(b) && isfinite(w) && b >= 0.0 && w >= 0.0 && b + w < 100.0)) {
+           return "Invalid color stretch (want B:W, percentages with B + W < 100)";
+         }
+         s.color.black_percent = b;
+         s.color.white_percent = w;
+         return kOk;
+       }},
+      // --tonemap lut|thresholds|host: the form of the device tone map, or the reference's host loop
+      {"--tonemap", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.host_tonemap = strcmp(t, "host") == 0;
+         s.tone_mode = (strcmp(t, "lut") == 0)          ? CB_TONE_LUT
+                       : (strcmp(t, "thresholds") == 0) ? CB_TONE_THRESHOLDS
+                                                        : CB_TONE_AUTO;
+         return kOk;
+       }},
+  };
+  return table;
+}
+
+// ---- refusal table -----------------------------------------------------------------------------
+
+// What a render of its own may not be combined with: a predicate and the name it is refused by.
+struct Partner {
+  bool (*present)(const Settings &);
+  const char *name;
+};
+const Partner kPower = {[](const Settings &s) { return s.power != 0; }, "--power"};
+const Partner kShip = {[](const Settings &s) { return s.burning_ship; }, "--burning-ship"};
+const Partner kAnti = {[](const Settings &s) { return s.anti; }, "--anti"};
+const Partner kFocus = {[](const Settings &s) { return s.focus; }, "--focus"};
+const Partner kChannel = {[](const Settings &s) { return s.n_channels > 0 || s.color_file; }, "--channel"};
+const Partner kGpus = {[](const Settings &s) { return s.gpus > 1; }, "--gpus above 1"};
+const Partner kRaw = {[](const Settings &s) { return s.raw_state; }, "--state-format raw"};
+
+// The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
+// say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
+// where it has no partners, a message of its own.  The order of the rows and of each row's partners is observable
+// (tests/test_cli_refusals.py) and is each row's own.
+struct Refusal {
+  bool (*applies)(const Settings &);
+  const char *subject;
+  std::vector<Partner> partners;
+  void (*say)(const Settings &);
+};
+
+const std::vector<Refusal> &refusal_table() {
+  static const std::vector<Refusal> table = {
+      // a formula render is a projected render with a step of its own (include/cudabrot_amd.h, "Formula step"): its
+      // refusals come before those of the palette, the Multibrot step, c and the projection, which it would otherwise trip
+      {[](const Settings &s) { return s.formula != 0; }, "--formula", {kPower, kShip, kAnti, kFocus, kChannel, kGpus},
+       nullptr},
+      // a palette render is a projected render with three planes (include/cudabrot_amd.h, "Palette render"): its refusals
+      // come before those of the step, of c and of the projection, which it would otherwise trip
+      {[](const Settings &s) { return s.palette(); }, "--palette", {kAnti, kFocus, kChannel, kGpus, kRaw}, nullptr},
+      {[](const Settings &s) {  // the table has -m entries
+         return s.palette() && (s.iterations.max_escape_iterations < 1 ||
+                                s.iterations.max_escape_iterations > CB_PALETTE_MAX_ENTRIES);
+       },
+       nullptr, {}, [](const Settings &) { printf("--palette needs -m from 1 to %d.\n", CB_PALETTE_MAX_ENTRIES); }},
+      // a Multibrot render is a projected render with a step of its own (include/cudabrot_amd.h, "Multibrot step"): its
+      // refusals come before the projection's, which it would otherwise trip
+      {[](const Settings &s) { return s.power != 0; }, "--power", {kShip, kAnti, kFocus, kChannel, kGpus}, nullptr},
+      // a Julia render is a projected render as well (include/cudabrot_amd.h, "Julia render"), with either step but the
+      // Multibrot step's own refusals before its own
+      {[](const Settings &s) { return s.julia; }, "--julia", {kAnti, kFocus, kChannel, kGpus}, nullptr},
+      // a projected render is one plane of escaping orbits on one device, sampled uniformly (include/cudabrot_amd.h,
+      // cb_renderer_set_projection)
+      {[](const Settings &s) { return s.project_given && (s.plane_given || s.rotate_given); }, nullptr, {},
+       [](const Settings &) { printf("--project does not combine with --plane or --rotate.\n"); }},
+      {[](const Settings &s) { return s.projected(); }, "A projection", {kChannel, kAnti, kFocus, kGpus}, nullptr},
+      // a focused render is one plane of escaping orbits on one device (include/cudabrot_amd.h, cb_renderer_set_focus);
+      // with --gpus every rank would probe a mask of its own
+      {[](const Settings &s) { return s.focus; }, "--focus", {kChannel, kAnti, kGpus}, nullptr},
+      // no fused anti channels (include/cudabrot_amd.h)
+      {[](const Settings &s) { return s.anti; }, "--anti", {kChannel}, nullptr},
+      // after parsing: --color and the --channel flags come in any order
+      {[](const Settings &s) { return s.color_file && s.n_channels != 3; }, nullptr, {},
+       [](const Settings &s) { printf("--color needs exactly 3 --channel images, got %d.\n", s.n_channels); }},
+  };
+  return table;
+}
+
+// Canvas validation with the reference's messages (cudabrot.cu:505-527).
+bool canvas_ok(Settings &s) {
+  const char *why = nullptr;
+  if (cb_recompute_pixel_deltas(&s.canvas, &why)) return true;
+  printf("%s\n", why);
+  return false;
+}
+
+}  // namespace
+
+Settings parse_arguments(int argc, char **argv) {
+  Settings s;
+  if (!canvas_ok(s)) {  // cudabrot.cu:539-542
+    printf("Internal error setting default canvas boundaries!\n");
+    exit(1);
+  }
+  for (int i = 1; i < argc; i++) {
+    const char *arg = argv[i];
+    if (strcmp(arg, "--help") == 0) usage_and_exit(argv[0]);
+    const Flag *flag = nullptr;
+    for (const Flag &f : flag_table()) {
+      if (strcmp(arg, f.name) == 0) {
+        flag = &f;
+        break;
+      }
+    }
+    if (!flag) {
+      printf("Invalid argument: %s\n", arg);  // cudabrot.cu:751
+      usage_and_exit(argv[0]);
+    }
+    long as_int = 0;
+    double as_double = 0.0;
+    const char *text = nullptr;
+    if (flag->value != Value::kNone) {
+      if (i + 1 >= argc) {
+        if (flag->missing_value_message) {
+          printf("%s\n", flag->missing_value_message);
+        } else {
+          printf("Argument %s needs a value.\n", arg);  // cudabrot.cu:629,648
+        }
+        usage_and_exit(argv[0]);
+      }
+      text = argv[++i];
+      if (flag->value != Value::kText) {
+        // whole-string numbers only; an empty string is not a number (cudabrot.cu:632-639,651-656)
+        char *end = nullptr;
+        if (flag->value == Value::kInt) {
+          as_int = (int) strtol(text, &end, 10);  // truncated to int like the reference
+        } else if (flag->value == Value::kLong) {
+          as_int = (long) strtoull(text, &end, 10);
+        } else {
+          as_double = strtod(text, &end);
+        }
+        if (*end != 0 || text[0] == 0) {
+          printf("Invalid number given to argument %s: %s\n", arg, text);
+          usage_and_exit(argv[0]);
+        }
+      }
+    }
+    if (const char *bad = flag->store(s, as_int, as_double, text)) {
+      printf("%s: %s\n", bad, text);
+      usage_and_exit(argv[0]);
+    }
+    if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
+  }
+  for (const Refusal &row : refusal_table()) {
+    if (!row.applies(s)) continue;
+    if (row.say) {
+      row.say(s);
+      usage_and_exit(argv[0]);
+    }
+    for (const Partner &partner : row.partners) {
+      if (partner.present(s)) {
+        printf("%s does not combine with %s.\n", row.subject, partner.name);
+        usage_and_exit(argv[0]);
+      }
+    }
+  }
+  return s;
+}
+
+}  // namespace cb

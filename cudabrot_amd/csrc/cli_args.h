@@ -1,0 +1,73 @@
+// cli_args.h -- the `cudabrot` command line: what it sets (Settings) and its parser (cli_args.cpp).  Host code over
+// include/cudabrot_amd.h alone: no device is touched before the run (cli_main.cpp) starts.
+#pragma once
+
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/cudabrot_amd.h"
+
+namespace cb {
+
+struct Settings {
+  int device = 0;                                   // -d
+  const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
+  const char *inprogress_file = nullptr;            // -s
+  double seconds_to_run = 10.0;                     // -t   (cudabrot.cu:769)
+  double gamma_correction = 1.0;                    // -g   (cudabrot.cu:770)
+  cb_iteration_control iterations = {100, 20};      // -m -c (cudabrot.cu:765-766)
+  cb_fractal_dimensions canvas = {1000, 1000, -2.0, -2.0, 2.0, 2.0, 0.0, 0.0};  // cudabrot.cu:533-538
+  long fixed_passes = -1;                           // --passes (extension; <0: run by the clock)
+  int kernel_variant = CB_KERNEL_DEFAULT;           // --kernel (extension)
+  bool print_stats = false;                         // --stats  (extension)
+  bool burning_ship = false;                        // --burning-ship (extension; cudabrot.cu:15-17)
+  bool anti = false;                                // --anti (extension): the anti-Buddhabrot, CB_KERNEL_FLAG_ANTI
+  int gpus = 1;                                     // --gpus N (extension): devices -d .. -d + N - 1
+  // --channel MAX:MIN:FILE (extension, repeatable): fused multi-channel render, one image per window
+  int n_channels = 0;
+  cb_iteration_control channel_window[CB_MAX_CHANNELS] = {};
+  std::string channel_file[CB_MAX_CHANNELS];
+  uint64_t seed = CB_DEFAULT_RNG_SEED;              // --seed (extension; cudabrot.cu:37)
+  const char *rng_state_file = nullptr;             // --rng-state (extension): true-resume sidecar
+  bool raw_state = false;                           // --state-format raw (extension): -s as the reference's bare buffer
+  int tone_mode = CB_TONE_AUTO;                     // --tonemap (extension): device table / thresholds
+  bool host_tonemap = false;                        //   ... or the reference's host loop
+  // --color FILE (extension): the three --channel planes composed into one RGB image; --compose, --hue-shift,
+  // --color-stretch B:W set its cb_color_params (defaults: rgb, 0, ImageMagick's -normalize 2:1)
+  const char *color_file = nullptr;
+  cb_color_params color = {CB_COMPOSE_RGB, 2.0, 1.0, 0.0};
+  // --focus (extension): samples drawn only from the cells a probe found to reach the canvas (cb_renderer_set_focus)
+  bool focus = false;
+  int focus_level = 8;                              // --focus-level: cells of side 2^-L
+  long focus_probe = 64;                            // --focus-probe: reference passes of the probe
+  int focus_dilate = 1;                             // --focus-dilate: cells the probe's mask is widened by
+  // --project / --plane / --rotate (extensions): the plotted plane, P[2][4] over (zr, zi, cr, ci) (cb_renderer_set_projection)
+  bool project_given = false, plane_given = false, rotate_given = false;
+  double projection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+  // --power D (extension): the Multibrot step z^D + c, CB_KERNEL_POWER(D); makes the run a projected one (the identity
+  // unless a plane is given)
+  int power = 0;
+  // --julia RE,IM (extension): the Buddhabrot of the Julia set of c = RE + IM i (cb_renderer_set_julia); makes the run a
+  // projected one as --power does
+  bool julia = false;
+  double julia_c[2] = {0.0, 0.0};
+  // --palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a palette render (cb_palette_from_stops,
+  // cb_renderer_set_palette); makes the run a projected one as --power does
+  int n_palette_stops = 0;
+  cb_palette_stop palette_stops[CB_PALETTE_MAX_STOPS] = {};
+  bool palette() const { return n_palette_stops > 0; }
+  // --formula NAME (extension): a formula step, CB_KERNEL_FORMULA(code); makes the run a projected one as --power does
+  int formula = 0;
+  const char *formula_name = nullptr;
+  bool projected() const {
+    return project_given || plane_given || rotate_given || power != 0 || julia || palette() || formula != 0;
+  }
+};
+
+// argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an
+// unknown flag, a bad value, a combination the renders do not support -- ends the process here: its message and the
+// usage text on stdout, exit 0.
+Settings parse_arguments(int argc, char **argv);
+
+}  // namespace cb

@@ -1,10 +1,11 @@
 // cli_main.cpp -- `cudabrot`: command-line drop-in for the reference binary.
 //
 // The process boundary IS the reference's public interface: argv in, stdout text,
-// exit code, a 16-bit PGM and the raw -s buffer out.  This file reproduces that contract
-// (cudabrot.cu:579-791: flags :662-754, messages, usage -> exit 0, errors on stdout -> exit 1) on top of
-// the C ABI in include/cudabrot_amd.h.  Rendering is done by the hand-written gfx950 kernels only: there
-// is no CPU fallback, without a usable GPU the program prints the reference's error line and exits 1.
+// exit code, a 16-bit PGM and the raw -s buffer out.  This file and cli_args.cpp reproduce that contract
+// (cudabrot.cu:579-791: messages, usage -> exit 0, errors on stdout -> exit 1) on top of the C ABI in
+// include/cudabrot_amd.h: the parser there (flags :662-754), the run of what it returns here.  Rendering is done
+// by the hand-written gfx950 kernels only: there is no CPU fallback, without a usable GPU the program prints the
+// reference's error line and exits 1.
 //
 // Observable differences, all deliberate:
 //  * the -s buffer holds 64-bit counters behind a 32-byte header that names its own shape (magic, w, h, planes,
@@ -12,26 +13,8 @@
 //    file (exactly w*h*4 bytes of uint32, no header) is accepted on load, announced, and widened;
 //  * reference passes (512*512 threads x 50 samples) are fused into launches of about 0.2 s, so -t and
 //    Ctrl+C act at launch granularity; the printed pass count still counts reference-sized passes;
-//  * extension flags, which the reference answers with its usage text: --passes N, --kernel NAME,
-//    --stats, --tonemap FORM, --seed N, --rng-state FILE, --burning-ship, --anti (the anti-Buddhabrot: the orbits
-//    that never escape, include/cudabrot_amd.h CB_KERNEL_FLAG_ANTI), --channel MAX:MIN:FILE, --gpus N,
-//    --state-format native|raw (raw: the -s file as the reference's bare buffer, uint32 when every count fits),
-//    --color FILE, --compose rgb|hsl, --hue-shift X, --color-stretch B:W (the three --channel planes composed into
-//    one 16-bit PPM: include/cudabrot_amd.h, "Colour image"), --focus, --focus-level L, --focus-probe PASSES,
-//    --focus-dilate D (a cropped canvas sampled only from the cells of the plane whose samples reach it:
-//    include/cudabrot_amd.h, "Focused render"; each of the three value flags turns --focus on), --project
-//    a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG (the plane of the 4-D set (z_re, z_im, c_re, c_im) the orbits are
-//    plotted on: include/cudabrot_amd.h, "Projected render"), --power D (the Multibrot step z^D + c, D = 3 .. 8, on
-//    the projected path: include/cudabrot_amd.h, "Multibrot step"), --julia RE,IM (the Buddhabrot of the Julia set
-//    of c = RE + IM i: c fixed, the samples are the starting points; -2 <= RE, IM <= 2; with --power or
-//    --burning-ship, on any plane: include/cudabrot_amd.h, "Julia render"), --palette K:RRGGBB[,K:RRGGBB...] (orbits
-//    coloured by their escape index: colour stops interpolated into a table of -m entries, three planes of integer
-//    weights, -o receives a 16-bit PPM; on the projected path with any plane, --power, --julia or --burning-ship:
-//    include/cudabrot_amd.h, "Palette render"), --formula NAME (another step of the quadratic family: tricorn, celtic,
-//    buffalo, perpendicular or celtic-tricorn, on the projected path with any plane, --julia or --palette:
-//    include/cudabrot_amd.h, "Formula step").
-#include <errno.h>
-#include <math.h>
+//  * extension flags, which the reference answers with its usage text: they are listed where they are parsed, in the
+//    flag table of cli_args.cpp.
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -41,660 +24,20 @@
 
 #include <chrono>
 #include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/cudabrot_amd.h"
+#include "cli_args.h"
 #include "state_files.h"
 
 namespace {
 
+using cb::Settings;
+
 volatile sig_atomic_t g_quit_requested = 0;
-
-struct Settings {
-  int device = 0;                                   // -d
-  const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
-  const char *inprogress_file = nullptr;            // -s
-  double seconds_to_run = 10.0;                     // -t   (cudabrot.cu:769)
-  double gamma_correction = 1.0;                    // -g   (cudabrot.cu:770)
-  cb_iteration_control iterations = {100, 20};      // -m -c (cudabrot.cu:765-766)
-  cb_fractal_dimensions canvas = {1000, 1000, -2.0, -2.0, 2.0, 2.0, 0.0, 0.0};  // cudabrot.cu:533-538
-  long fixed_passes = -1;                           // --passes (extension; <0: run by the clock)
-  int kernel_variant = CB_KERNEL_DEFAULT;           // --kernel (extension)
-  bool print_stats = false;                         // --stats  (extension)
-  bool burning_ship = false;                        // --burning-ship (extension; cudabrot.cu:15-17)
-  bool anti = false;                                // --anti (extension): the anti-Buddhabrot, CB_KERNEL_FLAG_ANTI
-  int gpus = 1;                                     // --gpus N (extension): devices -d .. -d + N - 1
-  // --channel MAX:MIN:FILE (extension, repeatable): fused multi-channel render, one image per window
-  int n_channels = 0;
-  cb_iteration_control channel_window[CB_MAX_CHANNELS] = {};
-  std::string channel_file[CB_MAX_CHANNELS];
-  bool bad_channel = false;
-  uint64_t seed = CB_DEFAULT_RNG_SEED;              // --seed (extension; cudabrot.cu:37)
-  const char *rng_state_file = nullptr;             // --rng-state (extension): true-resume sidecar
-  bool raw_state = false;                           // --state-format raw (extension): -s as the reference's bare buffer
-  bool bad_state_format = false;
-  int tone_mode = CB_TONE_AUTO;                     // --tonemap (extension): device table / thresholds
-  bool host_tonemap = false;                        //   ... or the reference's host loop
-  // --color FILE (extension): the three --channel planes composed into one RGB image; --compose, --hue-shift,
-  // --color-stretch B:W set its cb_color_params (defaults: rgb, 0, ImageMagick's -normalize 2:1)
-  const char *color_file = nullptr;
-  cb_color_params color = {CB_COMPOSE_RGB, 2.0, 1.0, 0.0};
-  const char *bad_color_flag = nullptr;             // the message of a bad --compose / --hue-shift / --color-stretch
-  // --focus (extension): samples drawn only from the cells a probe found to reach the canvas (cb_renderer_set_focus)
-  bool focus = false;
-  int focus_level = 8;                              // --focus-level: cells of side 2^-L
-  long focus_probe = 64;                            // --focus-probe: reference passes of the probe
-  int focus_dilate = 1;                             // --focus-dilate: cells the probe's mask is widened by
-  const char *bad_focus_flag = nullptr;             // the message of a bad --focus-level / -probe / -dilate
-  // --project / --plane / --rotate (extensions): the plotted plane, P[2][4] over (zr, zi, cr, ci) (cb_renderer_set_projection)
-  bool project_given = false, plane_given = false, rotate_given = false;
-  double projection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
-  const char *bad_project_flag = nullptr;           // the message of a bad --project / --plane / --rotate
-  // --power D (extension): the Multibrot step z^D + c, CB_KERNEL_POWER(D); makes the run a projected one (the identity
-  // unless a plane is given)
-  int power = 0;
-  const char *bad_power_flag = nullptr;             // the message of a bad --power
-  // --julia RE,IM (extension): the Buddhabrot of the Julia set of c = RE + IM i (cb_renderer_set_julia); makes the run a
-  // projected one as --power does
-  bool julia = false;
-  double julia_c[2] = {0.0, 0.0};
-  const char *bad_julia_flag = nullptr;             // the message of a bad --julia
-  // --palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a palette render (cb_palette_from_stops,
-  // cb_renderer_set_palette); makes the run a projected one as --power does
-  int n_palette_stops = 0;
-  cb_palette_stop palette_stops[CB_PALETTE_MAX_STOPS] = {};
-  const char *bad_palette_flag = nullptr;           // the message of a bad --palette
-  bool palette() const { return n_palette_stops > 0; }
-  // --formula NAME (extension): a formula step, CB_KERNEL_FORMULA(code); makes the run a projected one as --power does
-  int formula = 0;
-  const char *formula_name = nullptr;
-  const char *bad_formula_flag = nullptr;           // the message of a bad --formula
-  bool projected() const {
-    return project_given || plane_given || rotate_given || power != 0 || julia || palette() || formula != 0;
-  }
-};
-
-// One of zr, zi, cr, ci at `text`, followed by `after` -> its column of P (else -1); *rest: behind `after`.
-int axis_of(const char *text, char after, const char **rest) {
-  static const char *const kNames[4] = {"zr", "zi", "cr", "ci"};
-  for (int j = 0; j < 4; ++j) {
-    if (strncmp(text, kNames[j], 2) == 0 && text[2] == after) {
-      *rest = text + (after ? 3 : 2);
-      return j;
-    }
-  }
-  return -1;
-}
-
-// --project a,b,c,d:e,f,g,h: eight finite numbers, strtod's syntax (hexfloats included).
-bool parse_projection(const char *text, double out[8]) {
-  const char *at = text;
-  for (int j = 0; j < 8; ++j) {
-    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
-    char *end = nullptr;
-    out[j] = strtod(at, &end);
-    if (end == at || !isfinite(out[j]) || *end != (j == 7 ? 0 : (j == 3 ? ':' : ','))) return false;
-    at = end + 1;
-  }
-  return true;
-}
-
-// --julia RE,IM: two finite numbers in [-2, 2], strtod's syntax (hexfloats included).
-bool parse_julia(const char *text, double out[2]) {
-  const char *at = text;
-  for (int j = 0; j < 2; ++j) {
-    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
-    char *end = nullptr;
-    out[j] = strtod(at, &end);
-    if (end == at || !(out[j] >= -2.0 && out[j] <= 2.0) || *end != (j == 1 ? 0 : ',')) return false;
-    at = end + 1;
-  }
-  return true;
-}
-
-// --palette K:RRGGBB[,K:RRGGBB...]: 1 to CB_PALETTE_MAX_STOPS stops, K decimal digits and strictly ascending, the colour
-// six hex digits.  Returns the number of stops, 0 for anything else.
-int parse_palette(const char *text, cb_palette_stop out[CB_PALETTE_MAX_STOPS]) {
-  const char *at = text;
-  int n = 0;
-  for (;;) {
-    if (n == CB_PALETTE_MAX_STOPS || *at < '0' || *at > '9') return 0;
-    long k = 0;
-    for (; *at >= '0' && *at <= '9'; ++at) {
-      k = k * 10 + (*at - '0');
-      if (k > 0x7fffffffL) return 0;
-    }
-    if (*at++ != ':' || (n > 0 && k <= out[n - 1].k)) return 0;
-    int v[3] = {0, 0, 0};
-    for (int j = 0; j < 6; ++j, ++at) {
-      const char ch = *at;
-      const int digit = (ch >= '0' && ch <= '9') ? ch - '0' : (ch >= 'a' && ch <= 'f') ? ch - 'a' + 10 : (ch >= 'A' && ch <= 'F') ? ch - 'A' + 10 : -1;
-      if (digit < 0) return 0;
-      v[j / 2] = v[j / 2] * 16 + digit;
-    }
-    out[n++] = {(int) k, v[0], v[1], v[2]};
-    if (*at == 0) return n;
-    if (*at++ != ',') return 0;
-  }
-}
-
-// --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane.  An integer multiple of 90
-// degrees uses exact 0 and +-1 (a permutation of the two columns with signs); otherwise the host's cos and sin.
-bool rotate_projection(const char *text, double p[8]) {
-  const char *rest = nullptr;
-  const int x = axis_of(text, ',', &rest);
-  const int y = x < 0 ? -1 : axis_of(rest, ':', &rest);
-  if (x < 0 || y < 0 || x == y || *rest == 0 || *rest == ' ' || *rest == '\t') return false;
-  char *end = nullptr;
-  const double degrees = strtod(rest, &end);
-  if (end == rest || *end != 0 || !isfinite(degrees)) return false;
-  double co, si;
-  const double quarters = degrees / 90.0;
-  if (quarters == floor(quarters)) {
-    const int q = (int) fmod(fmod(quarters, 4.0) + 4.0, 4.0);
-    co = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
-    si = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
-  } else {
-    const double radians = degrees * (M_PI / 180.0);
-    co = cos(radians);
-    si = sin(radians);
-  }
-  for (int row = 0; row < 2; ++row) {
-    const double a = p[4 * row + x], b = p[4 * row + y];
-    p[4 * row + x] = (a * co - b * si) + 0.0;  // (+ 0.0: an exact zero is +0)
-    p[4 * row + y] = (a * si + b * co) + 0.0;
-  }
-  return true;
-}
-
-// The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
-const char kUsageBody[] =
-    "Options may be one or more of the following:\n"
-    "  --help: Prints these instructions.\n"
-    "  -d <device number>: Sets which GPU to use. Defaults to GPU 0.\n"
-    "  -o <output file name>: If provided, the rendered image will be saved\n"
-    "     to a .pgm file with the given name. Otherwise, saves the image\n"
-    "     to output.pgm.\n"
-    "  -m <max escape iterations>: The maximum number of iterations to use\n"
-    "     before giving up on seeing whether a point escapes.\n"
-    "  -c <min escape iterations>: If a point escapes before this number of\n"
-    "     iterations, it will be ignored.\n"
-    "  -g <gamma correction>: A gamma-correction value to use on the\n"
-    "     resulting image. If negative, no gamma correction will occur.\n"
-    "  -t <seconds to run>: A number of seconds to run the calculation for.\n"
-    "     Defaults to 10.0. If negative, the program will run continuously\n"
-    "     and will terminate (saving the image) when it receives a SIGINT.\n"
-    "  -w <width>: The width of the output image, in pixels. Defaults to\n"
-    "     1000.\n"
-    "  -h <height>: The height of the output image, in pixels. Defaults to\n"
-    "     1000.\n"
-    "  -s <save/load file>: If provided, this gives a file name into which\n"
-    "     the rendering buffer will be saved, for future continuation.\n"
-    "     If the program is loaded and the file exists, the buffer will be\n"
-    "     filled with the contents of the file, but the dimensions must\n"
-    "     match. Note that this file may be huge for high-resolution images.\n"
-    "\n"
-    "The following settings control the location of the output image on the\n"
-    "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
-    "set domain (-2-2i to 2+2i). So these settings can be used to save\n"
-    "memory or \"crop\" the output, but won't otherwise speed up rendering:\n"
-    "  --min-real <min real>: The minimum value along the real axis to\n"
-    "             include in the output image. Defaults to -2.0.\n"
-    "  --max-real <max real>: The maximum value along the real axis to\n"
-    "             include in the output image. Defaults to 2.0.\n"
-    "  --min-imag <min imag>: The minimum value along the imaginary axis to\n"
-    "             include in the output image. Defaults to -2.0.\n"
-    "  --max-imag <max imag>: The maximum value along the imaginary axis to\n"
-    "             include in the output image. Defaults to 2.0.\n";
-
-// Usage always ends the process with status 0, also after a bad argument (cudabrot.cu:619).
-[[noreturn]] void usage_and_exit(const char *program) {
-  printf("Usage: %s [options]\n\n", program);
-  fputs(kUsageBody, stdout);
-  exit(0);
-}
-
-// ---- argument table ----------------------------------------------------------------------------
-
-enum class Value { kNone, kInt, kLong, kDouble, kText };  // kInt: truncated to int like the reference's flags
-
-struct Flag {
-  const char *name;
-  Value value;
-  const char *missing_value_message;  // nullptr: "Argument %s needs a value."
-  bool revalidates_canvas;            // -w -h --min/max-*: canvas re-checked at once (:704-749)
-  std::function<void(Settings &, long, double, const char *)> store;
-};
-
-const std::vector<Flag> &flag_table() {
-  static const std::vector<Flag> table = {
-      {"-d", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) { s.device = (int) i; }},
-      {"-o", Value::kText, "Missing output file name.", false,
-       [](Settings &s, long, double, const char *t) { s.output_image = t; }},
-      {"-s", Value::kText, "Missing in-progress buffer file name.", false,
-       [](Settings &s, long, double, const char *t) { s.inprogress_file = t; }},
-      {"-m", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.iterations.max_escape_iterations = (int) i;
-         if (s.iterations.max_escape_iterations > 60000) {  // cudabrot.cu:692-695
-           printf("Warning: Using a high number of iterations may cause the "
-                  "program respond slowly to Ctrl+C or time running out.\n");
-         }
-       }},
-      {"-c", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.iterations.min_escape_iterations = (int) i;
-       }},
-      {"-w", Value::kInt, nullptr, true,
-       [](Settings &s, long i, double, const char *) { s.canvas.w = (int) i; }},
-      {"-h", Value::kInt, nullptr, true,
-       [](Settings &s, long i, double, const char *) { s.canvas.h = (int) i; }},
-      {"-g", Value::kDouble, nullptr, false,
-       [](Settings &s, long, double d, const char *) { s.gamma_correction = d; }},
-      {"-t", Value::kDouble, nullptr, false,
-       [](Settings &s, long, double d, const char *) { s.seconds_to_run = d; }},
-      {"--min-real", Value::kDouble, nullptr, true,
-       [](Settings &s, long, double d, const char *) { s.canvas.min_real = d; }},
-      {"--max-real", Value::kDouble, nullptr, true,
-       [](Settings &s, long, double d, const char *) { s.canvas.max_real = d; }},
-      {"--min-imag", Value::kDouble, nullptr, true,
-       [](Settings &s, long, double d, const char *) { s.canvas.min_imag = d; }},
-      {"--max-imag", Value::kDouble, nullptr, true,
-       [](Settings &s, long, double d, const char *) { s.canvas.max_imag = d; }},
-      // extensions
-      {"--passes", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) { s.fixed_passes = i < 0 ? 0 : i; }},
-      {"--kernel", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.kernel_variant = (strcmp(t, "simple") == 0)  ? CB_KERNEL_SIMPLE
-                            : (strcmp(t, "timed") == 0) ? CB_KERNEL_TIMED
-                            : (strcmp(t, "full") == 0)  ? CB_KERNEL_FULL_ITERATE
-                                                        : CB_KERNEL_DEFAULT;
-       }},
-      {"--stats", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.print_stats = true; }},
-      {"--channel", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         int mx = 0, mn = 0, used = 0;
-         if (s.n_channels >= CB_MAX_CHANNELS || sscanf(t, "%d:%d:%n", &mx, &mn, &used) < 2 || used == 0 ||
-             t[used] == 0) {
-           s.bad_channel = true;
-           return;
-         }
-         s.channel_window[s.n_channels] = {mx, mn};
-         s.channel_file[s.n_channels] = t + used;
-         s.n_channels++;
-       }},
-      {"--gpus", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) { s.gpus = (i < 1) ? 1 : (i > 64 ? 64 : (int) i); }},
-      {"--burning-ship", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.burning_ship = true; }},
-      {"--anti", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.anti = true; }},
-      {"--focus", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.focus = true; }},
-      {"--focus-level", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i >= CB_FOCUS_MIN_LEVEL && i <= CB_FOCUS_MAX_LEVEL) {
-           s.focus_level = (int) i;
-         } else {
-           s.bad_focus_flag = "Invalid focus level (want 4 to 10)";
-         }
-       }},
-      {"--focus-probe", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i >= 1) {
-           s.focus_probe = i;
-         } else {
-           s.bad_focus_flag = "Invalid focus probe (want at least 1 pass)";
-         }
-       }},
-      {"--focus-dilate", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i >= 0) {
-           s.focus_dilate = (int) i;
-         } else {
-           s.bad_focus_flag = "Invalid focus dilation (want 0 or more cells)";
-         }
-       }},
-      {"--project", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.project_given = true;
-         if (!parse_projection(t, s.projection)) {
-           s.bad_project_flag = "Invalid projection (want a,b,c,d:e,f,g,h, eight finite numbers)";
-         }
-       }},
-      {"--plane", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         const char *rest = nullptr;
-         const int x = axis_of(t, ',', &rest);
-         const int y = x < 0 ? -1 : axis_of(rest, 0, &rest);
-         s.plane_given = true;
-         if (x < 0 || y < 0 || x == y) {
-           s.bad_project_flag = "Invalid plane (want X,Y, two different axes of zr, zi, cr, ci)";
-           return;
-         }
-         if (s.rotate_given) {  // the rotations start from the plane
-           s.bad_project_flag = "Invalid plane (--plane goes before the first --rotate)";
-           return;
-         }
-         for (int j = 0; j < 8; ++j) s.projection[j] = 0.0;
-         s.projection[x] = 1.0;
-         s.projection[4 + y] = 1.0;
-       }},
-      {"--rotate", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.rotate_given = true;
-         if (s.project_given) return;  // refused after parsing; the matrix given is not touched
-         if (!rotate_projection(t, s.projection)) {
-           s.bad_project_flag = "Invalid rotation (want X,Y:DEG, two different axes of zr, zi, cr, ci and a finite angle)";
-         }
-       }},
-      {"--power", Value::kText, nullptr, false,  // text: a value that is no integer gets the flag's own message
-       [](Settings &s, long, double, const char *t) {
-         char *end = nullptr;
-         const long d = strtol(t, &end, 10);
-         if (t[0] == 0 || *end != 0 || d < CB_POWER_MIN || d > CB_POWER_MAX) {
-           s.bad_power_flag = "Invalid power (want an integer from 3 to 8)";
-           return;
-         }
-         s.power = (int) d;
-       }},
-      {"--julia", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.julia = true;
-         if (!parse_julia(t, s.julia_c)) {
-           s.bad_julia_flag = "Invalid julia parameter (want RE,IM, two numbers from -2 to 2)";
-         }
-       }},
-      {"--palette", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.n_palette_stops = parse_palette(t, s.palette_stops);
-         if (s.n_palette_stops == 0) {
-           s.bad_palette_flag = "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops)";
-         }
-       }},
-      {"--formula", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         static const char *const kNames[CB_FORMULA_MAX] = {"tricorn", "celtic", "buffalo", "perpendicular",
-                                                            "celtic-tricorn"};  // codes 1 .. CB_FORMULA_MAX
-         for (int code = 1; code <= CB_FORMULA_MAX; ++code) {
-           if (strcmp(t, kNames[code - 1]) == 0) {
-             s.formula = code;
-             s.formula_name = kNames[code - 1];
-             return;
-           }
-         }
-         s.bad_formula_flag = "Invalid formula (want tricorn, celtic, buffalo, perpendicular or celtic-tricorn)";
-       }},
-      {"--seed", Value::kLong, nullptr, false,  // the generator's seed is 64 bits wide (rocrand_init)
-       [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; }},
-      {"--rng-state", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) { s.rng_state_file = t; }},
-      {"--state-format", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.raw_state = strcmp(t, "raw") == 0;
-         s.bad_state_format = !s.raw_state && strcmp(t, "native") != 0;
-       }},
-      {"--color", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) { s.color_file = t; }},
-      {"--compose", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         if (strcmp(t, "rgb") == 0) {
-           s.color.compose = CB_COMPOSE_RGB;
-         } else if (strcmp(t, "hsl") == 0) {
-           s.color.compose = CB_COMPOSE_HSL;
-         } else {
-           s.bad_color_flag = "Invalid compose mode (want rgb or hsl)";
-         }
-       }},
-      {"--hue-shift", Value::kDouble, nullptr, false,
-       [](Settings &s, long, double d, const char *) {
-         if (isfinite(d)) {
-           s.color.hue_shift = d;
-         } else {
-           s.bad_color_flag = "Invalid hue shift (want a finite number)";
-         }
-       }},
-      {"--color-stretch", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         // B:W, two numbers: B % of the pixels go black, W % white (finite, B >= 0, W >= 0, B + W < 100)
-         char *end = nullptr;
-         const double b = strtod(t, &end);
-         bool ok = end != t && *end == ':';
-         double w = 0.0;
-         if (ok) {
-           const char *rest = end + 1;
-           w = strtod(rest, &end);
-           ok = end != rest && *end == 0;
-         }
-         if (ok && isfinite(b) && isfinite(w) && b >= 0.0 && w >= 0.0 && b + w < 100.0) {
-           s.color.black_percent = b;
-           s.color.white_percent = w;
-         } else {
-           s.bad_color_flag = "Invalid color stretch (want B:W, percentages with B + W < 100)";
-         }
-       }},
-      {"--tonemap", Value::kText, nullptr, false,
-       [](Settings &s, long, double, const char *t) {
-         s.host_tonemap = strcmp(t, "host") == 0;
-         s.tone_mode = (strcmp(t, "lut") == 0)          ? CB_TONE_LUT
-                       : (strcmp(t, "thresholds") == 0) ? CB_TONE_THRESHOLDS
-                                                        : CB_TONE_AUTO;
-       }},
-  };
-  return table;
-}
-
-// Canvas validation with the reference's messages (cudabrot.cu:505-527).
-bool canvas_ok(Settings &s) {
-  const char *why = nullptr;
-  if (cb_recompute_pixel_deltas(&s.canvas, &why)) return true;
-  printf("%s\n", why);
-  return false;
-}
-
-Settings parse_arguments(int argc, char **argv) {
-  Settings s;
-  if (!canvas_ok(s)) {  // cudabrot.cu:539-542
-    printf("Internal error setting default canvas boundaries!\n");
-    exit(1);
-  }
-  for (int i = 1; i < argc; i++) {
-    const char *arg = argv[i];
-    if (strcmp(arg, "--help") == 0) usage_and_exit(argv[0]);
-    const Flag *flag = nullptr;
-    for (const Flag &f : flag_table()) {
-      if (strcmp(arg, f.name) == 0) {
-        flag = &f;
-        break;
-      }
-    }
-    if (!flag) {
-      printf("Invalid argument: %s\n", arg);  // cudabrot.cu:751
-      usage_and_exit(argv[0]);
-    }
-    long as_int = 0;
-    double as_double = 0.0;
-    const char *text = nullptr;
-    if (flag->value != Value::kNone) {
-      if (i + 1 >= argc) {
-        if (flag->missing_value_message) {
-          printf("%s\n", flag->missing_value_message);
-        } else {
-          printf("Argument %s needs a value.\n", arg);  // cudabrot.cu:629,648
-        }
-        usage_and_exit(argv[0]);
-      }
-      text = argv[++i];
-      if (flag->value != Value::kText) {
-        // whole-string numbers only; an empty string is not a number (cudabrot.cu:632-639,651-656)
-        char *end = nullptr;
-        if (flag->value == Value::kInt) {
-          as_int = (int) strtol(text, &end, 10);  // truncated to int like the reference
-        } else if (flag->value == Value::kLong) {
-          as_int = (long) strtoull(text, &end, 10);
-        } else {
-          as_double = strtod(text, &end);
-        }
-        if (*end != 0 || text[0] == 0) {
-          printf("Invalid number given to argument %s: %s\n", arg, text);
-          usage_and_exit(argv[0]);
-        }
-      }
-    }
-    flag->store(s, as_int, as_double, text);
-    if (s.bad_channel) {
-      printf("Invalid channel (want MAX:MIN:FILE, at most %d of them): %s\n", CB_MAX_CHANNELS, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_state_format) {
-      printf("Invalid state format (want native or raw): %s\n", text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_color_flag) {
-      printf("%s: %s\n", s.bad_color_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_focus_flag) {
-      printf("%s: %s\n", s.bad_focus_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_project_flag) {
-      printf("%s: %s\n", s.bad_project_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_power_flag) {
-      printf("%s: %s\n", s.bad_power_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_julia_flag) {
-      printf("%s: %s\n", s.bad_julia_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_palette_flag) {
-      printf("%s: %s\n", s.bad_palette_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (s.bad_formula_flag) {
-      printf("%s: %s\n", s.bad_formula_flag, text);
-      usage_and_exit(argv[0]);
-    }
-    if (flag->revalidates_canvas && !canvas_ok(s)) usage_and_exit(argv[0]);
-  }
-  // a formula render is a projected render with a step of its own (include/cudabrot_amd.h, "Formula step"): its refusals
-  // come before those of the palette, the Multibrot step, c and the projection, which it would otherwise trip
-  if (s.formula != 0) {
-    const char *with = s.power != 0                           ? "--power"
-                       : s.burning_ship                       ? "--burning-ship"
-                       : s.anti                               ? "--anti"
-                       : s.focus                              ? "--focus"
-                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
-                       : s.gpus > 1                           ? "--gpus above 1"
-                                                              : nullptr;
-    if (with) {
-      printf("--formula does not combine with %s.\n", with);
-      usage_and_exit(argv[0]);
-    }
-  }
-  // a palette render is a projected render with three planes (include/cudabrot_amd.h, "Palette render"): its refusals come
-  // before those of the step, of c and of the projection, which it would otherwise trip
-  if (s.palette()) {
-    const char *with = s.anti                                 ? "--anti"
-                       : s.focus                              ? "--focus"
-                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
-                       : s.gpus > 1                           ? "--gpus above 1"
-                       : s.raw_state                          ? "--state-format raw"
-                                                              : nullptr;
-    if (with) {
-      printf("--palette does not combine with %s.\n", with);
-      usage_and_exit(argv[0]);
-    }
-    if (s.iterations.max_escape_iterations < 1 || s.iterations.max_escape_iterations > CB_PALETTE_MAX_ENTRIES) {
-      printf("--palette needs -m from 1 to %d.\n", CB_PALETTE_MAX_ENTRIES);  // the table has -m entries
-      usage_and_exit(argv[0]);
-    }
-  }
-  // a Multibrot render is a projected render with a step of its own (include/cudabrot_amd.h, "Multibrot step"): its
-  // refusals come before the projection's, which it would otherwise trip
-  if (s.power != 0) {
-    const char *with = s.burning_ship                         ? "--burning-ship"
-                       : s.anti                               ? "--anti"
-                       : s.focus                              ? "--focus"
-                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
-                       : s.gpus > 1                           ? "--gpus above 1"
-                                                              : nullptr;
-    if (with) {
-      printf("--power does not combine with %s.\n", with);
-      usage_and_exit(argv[0]);
-    }
-  }
-  // a Julia render is a projected render as well (include/cudabrot_amd.h, "Julia render"), with either step but the
-  // Multibrot step's own refusals before its own
-  if (s.julia) {
-    const char *with = s.anti                                 ? "--anti"
-                       : s.focus                              ? "--focus"
-                       : (s.n_channels > 0 || s.color_file)   ? "--channel"
-                       : s.gpus > 1                           ? "--gpus above 1"
-                                                              : nullptr;
-    if (with) {
-      printf("--julia does not combine with %s.\n", with);
-      usage_and_exit(argv[0]);
-    }
-  }
-  // a projected render is one plane of escaping orbits on one device, sampled uniformly (include/cudabrot_amd.h,
-  // cb_renderer_set_projection)
-  if (s.project_given && (s.plane_given || s.rotate_given)) {
-    printf("--project does not combine with --plane or --rotate.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.projected() && (s.n_channels > 0 || s.color_file)) {
-    printf("A projection does not combine with --channel.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.projected() && s.anti) {
-    printf("A projection does not combine with --anti.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.projected() && s.focus) {
-    printf("A projection does not combine with --focus.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.projected() && s.gpus > 1) {
-    printf("A projection does not combine with --gpus above 1.\n");
-    usage_and_exit(argv[0]);
-  }
-  // a focused render is one plane of escaping orbits on one device (include/cudabrot_amd.h, cb_renderer_set_focus)
-  if (s.focus && (s.n_channels > 0 || s.color_file)) {
-    printf("--focus does not combine with --channel.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.focus && s.anti) {
-    printf("--focus does not combine with --anti.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.focus && s.gpus > 1) {  // every rank would probe a mask of its own
-    printf("--focus does not combine with --gpus above 1.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.anti && (s.n_channels > 0 || s.color_file)) {  // no fused anti channels (include/cudabrot_amd.h)
-    printf("--anti does not combine with --channel.\n");
-    usage_and_exit(argv[0]);
-  }
-  if (s.color_file && s.n_channels != 3) {  // after parsing: --color and the --channel flags come in any order
-    printf("--color needs exactly 3 --channel images, got %d.\n", s.n_channels);
-    usage_and_exit(argv[0]);
-  }
-  return s;
-}
 
 // ---- the run -------------------------------------------------------------------------------------
 
@@ -1247,7 +590,7 @@ extern "C" void on_sigint(int signal_number) {
 }
 
 int main(int argc, char **argv) {
-  const Settings settings = parse_arguments(argc, argv);
+  const Settings settings = cb::parse_arguments(argc, argv);
   if (signal(SIGINT, on_sigint) == SIG_ERR) {  // cudabrot.cu:774-778
     printf("Failed setting signal handler.\n");
     return 1;
