@@ -60,6 +60,7 @@ CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
 CB_PALETTE_MAX_ENTRIES, CB_PALETTE_MAX_STOPS = 1 << 24, 16  # palette render: the table's entries, the stops of one
+CB_DEPTH_MAX_SLICES = 256  # depth render: the planes of one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -126,6 +127,35 @@ class PaletteStop(C.Structure):
     """cb_palette_stop: one colour stop (k, r, g, b) of a palette."""
 
     _fields_ = [("k", C.c_int), ("r", C.c_int), ("g", C.c_int), ("b", C.c_int)]
+
+
+DEPTH_AXES = {"zr": 0, "zi": 1, "cr": 2, "ci": 3}  # the CLI's names of the columns of a row
+
+
+class Depth(C.Structure):
+    """cb_depth: the depth row, the window [min, max) and the number of slices of a depth render."""
+
+    _fields_ = [("row", C.c_double * 4), ("min", C.c_double), ("max", C.c_double), ("slices", C.c_int)]
+
+    @classmethod
+    def make(cls, row, lo, hi, slices=1):
+        """row: an axis name (zr, zi, cr, ci) or four numbers over (z_re, z_im, c_re, c_im)."""
+        if isinstance(row, str):
+            if row not in DEPTH_AXES:
+                raise ValueError("a depth axis is one of %s" % ", ".join(DEPTH_AXES))
+            row = [1.0 if j == DEPTH_AXES[row] else 0.0 for j in range(4)]
+        v = np.asarray(row, dtype=np.float64).reshape(-1)
+        if v.size != 4:
+            raise ValueError("a depth row is four numbers: D[4]")
+        return cls((C.c_double * 4)(*[float(x) for x in v]), float(lo), float(hi), int(slices))
+
+    def as_tuple(self):
+        return tuple(float(x) for x in self.row), float(self.min), float(self.max), int(self.slices)
+
+
+def _depth(depth):
+    """A Depth from a Depth or from (row, min, max[, slices])."""
+    return depth if isinstance(depth, Depth) else Depth.make(*depth)
 
 
 class Counters(C.Structure):
@@ -222,6 +252,7 @@ def _load():
     vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
     dims_p, it_p, cnt_p = C.POINTER(FractalDimensions), C.POINTER(IterationControl), C.POINTER(Counters)
     col_p = C.POINTER(ColorParams)
+    depth_p = C.POINTER(Depth)
     sigs = {
         "cb_abi_version": (i32, []),
         "cb_error_string": (C.c_char_p, [i32]),
@@ -283,6 +314,11 @@ def _load():
         "cb_renderer_set_palette": (i32, [vp, vp, u32]),
         "cb_renderer_palette": (i32, [vp, C.POINTER(u32)]),
         "cb_renderer_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_draw_buddhabrot_depth": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), depth_p, vp, u32,
+                                           u32, vp, i32, vp]),
+        "cb_renderer_set_depth": (i32, [vp, depth_p]),
+        "cb_renderer_depth": (i32, [vp, depth_p]),
+        "cb_renderer_depth_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -305,7 +341,8 @@ EXPORTED_SYMBOLS = (
     "cb_focus_mask_bytes cb_focus_probe cb_focus_cells cb_draw_buddhabrot_focus cb_renderer_set_focus cb_renderer_focus_cells "
     "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout "
     "cb_draw_buddhabrot_julia cb_renderer_set_julia cb_renderer_julia "
-    "cb_palette_from_stops cb_draw_buddhabrot_palette cb_renderer_set_palette cb_renderer_palette cb_renderer_palette_image"
+    "cb_palette_from_stops cb_draw_buddhabrot_palette cb_renderer_set_palette cb_renderer_palette cb_renderer_palette_image "
+    "cb_draw_buddhabrot_depth cb_renderer_set_depth cb_renderer_depth cb_renderer_depth_image"
 ).split()
 
 
@@ -478,6 +515,18 @@ def draw_buddhabrot_palette(dims, d_hist, iterations, projection, julia_c, d_lut
     )
 
 
+def draw_buddhabrot_depth(dims, d_hist, iterations, projection, julia_c, depth, d_states, n_threads, samples_per_thread,
+                          d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The depth draw on caller-owned device memory (cb_draw_buddhabrot_depth): d_hist is depth.slices planes; depth is a
+    Depth or (row, min, max[, slices]); julia_c None samples c (a projected render), else c is fixed."""
+    _check(
+        lib.cb_draw_buddhabrot_depth(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                     None if julia_c is None else _julia_c(julia_c), C.byref(_depth(depth)), d_states,
+                                     n_threads, samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_depth",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -490,6 +539,7 @@ class Renderer:
         self.n_threads = n_threads
         self._h = C.c_void_p()
         self.palette_entries = 0
+        self.depth_slices = 0
         if isinstance(iterations, IterationControl):
             self.n_channels = 0
             _check(
@@ -566,7 +616,32 @@ class Renderer:
                                              C.byref(scale)), "cb_renderer_palette_image")
         return rgb, int(mx.value), float(scale.value)
 
+    def set_depth(self, depth):
+        """Give this renderer a depth (cb_renderer_set_depth), before the first pass and after set_projection or
+        set_julia: depth is a Depth or (row, min, max[, slices]).  The histogram becomes `slices` planes."""
+        d = _depth(depth)
+        _check(lib.cb_renderer_set_depth(self._h, C.byref(d)), "cb_renderer_set_depth")
+        self.depth_slices = int(d.slices)
+
+    def depth(self):
+        """The depth of a renderer as a Depth; None for a renderer without one."""
+        out = Depth()
+        if not lib.cb_renderer_depth(self._h, C.byref(out)):
+            return None
+        return out
+
+    def depth_image(self, gamma=1.0, mode=0):
+        """The image of a renderer with a depth (cb_renderer_depth_image) -> (big-endian u16 images [slices, h, w] = the
+        bodies of the PGM sequence, the largest count of all planes, scale)."""
+        gray = np.empty((max(self.depth_slices, 1), self.dims.h, self.dims.w), dtype=">u2")
+        mx, scale = C.c_uint64(), C.c_double()
+        _check(lib.cb_renderer_depth_image(self._h, float(gamma), int(mode), gray.ctypes.data, C.byref(mx),
+                                           C.byref(scale)), "cb_renderer_depth_image")
+        return gray, int(mx.value), float(scale.value)
+
     def _planes(self):
+        if self.depth_slices:
+            return self.depth_slices
         return 3 if self.palette_entries else (self.n_channels or 1)
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
@@ -584,7 +659,7 @@ class Renderer:
         planes = self._planes()
         out = np.empty(planes * self.dims.w * self.dims.h, dtype=np.uint64)
         _check(lib.cb_renderer_read_histogram(self._h, out.ctypes.data), "cb_renderer_read_histogram")
-        if self.n_channels or self.palette_entries:
+        if self.n_channels or self.palette_entries or self.depth_slices:
             return out.reshape(planes, self.dims.h, self.dims.w)
         return out.reshape(self.dims.h, self.dims.w)
 

@@ -310,16 +310,28 @@ struct cb_renderer {
   bool palette;
   uint32_t *d_palette;
   uint32_t palette_entries;
+  // depth render (cb_renderer_set_depth): a projected or Julia renderer whose draws bin along a third row; d_hist is then
+  // depth.slices planes
+  bool has_depth;
+  cb_depth depth;
 };
 
 namespace {
 
-// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette renderer, else one.
-size_t renderer_planes(const cb_renderer *r) { return r->palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u); }
+// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette renderer, the slices of
+// a renderer with a depth, else one.
+size_t renderer_planes(const cb_renderer *r) {
+  if (r->has_depth) return (size_t) r->depth.slices;
+  return r->palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u);
+}
 
 int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
               const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
               uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
+int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+               const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
+               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream,
+               int *interior_level);
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
@@ -334,6 +346,11 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   }
   if (r->projected) {  // draw_plot.hip: direct atomics, no deferred scatter, no carry; what the setters took is checked
     if (passes == 0) return 0;
+    if (r->has_depth) {  // draw_depth.hip, likewise
+      return draw_depth(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr, &r->depth,
+                        r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
+                        &r->interior_level);
+    }
     return draw_plot(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
                      r->palette ? r->d_palette : nullptr, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
                      r->d_counters, kernel_variant, r->stream, &r->interior_level);
@@ -861,13 +878,11 @@ bool projection_ok(const double *p) {
   return true;
 }
 
-// The plotted draws (draw_plot.hip): what the three entry points below do once their own arguments have passed.  julia_c
-// null: c is sampled; d_lut null: one plane, no table.  interior_level (may be null): the level of the interior map the
-// launch used, 0 for none or when nothing was launched.
-int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+// The arguments of a plotted launch (draw_plot.hip, draw_depth.hip) from an entry point's, once its own have passed.
+// julia_c null: c is sampled; d_lut null: one plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.
+int plot_args(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
               const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
-              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
-  if (interior_level) *interior_level = 0;
+              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, cb::PlotArgs *out, bool *lockstep) {
   // A base of two and at most one of: a formula code CB_FORMULA_TRICORN .. CB_FORMULA_MAX ("Formula step"), a degree
   // CB_POWER_MIN .. CB_POWER_MAX ("Multibrot step"), the Burning Ship.  The plotted draws know neither anti nor drain.
   const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
@@ -880,7 +895,7 @@ int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iter
       (formula != 0 ? 1 : 0) + (power ? 1 : 0) + (ship ? 1 : 0) > 1) {
     return (int) hipErrorInvalidValue;
   }
-  cb::PlotArgs pa;
+  cb::PlotArgs &pa = *out;
   memset(&pa, 0, sizeof(pa));
   pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
   pa.d.burning_ship = ship ? 1 : 0;
@@ -895,7 +910,7 @@ int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iter
   pa.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
   pa.formula = formula;
   pa.palette = d_lut ? 1 : 0;
-  const bool lockstep = base_variant == CB_KERNEL_SIMPLE;
+  *lockstep = base_variant == CB_KERNEL_SIMPLE;
   // The interior map (the Mandelbrot set's: a sampled c, degree 2, no formula) where the normal product path consults it:
   // wants_interior_map's rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter
   // leaves that path a LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it
@@ -905,11 +920,67 @@ int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iter
     const int rc = attach_interior_map(pa.d, kernel_variant);
     if (rc) return rc;
   }
+  return 0;
+}
+
+// The plotted draws (draw_plot.hip): what the three entry points below do once their own arguments have passed.
+// interior_level (may be null): the level of the interior map the launch used, 0 for none or when nothing was launched.
+int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
+              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
+  if (interior_level) *interior_level = 0;
+  cb::PlotArgs pa;
+  bool lockstep = false;
+  {
+    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
+                             d_counters, kernel_variant, &pa, &lockstep);
+    if (rc) return rc;
+  }
   // cb_debug_last_draw_kernel names the entry point and the step: product / lock-step
-  const int id = formula != 0 ? 16 : d_lut ? 14 : julia_c ? 12 : power ? 10 : 8;
+  const int id = pa.formula != 0 ? 16 : d_lut ? 14 : julia_c ? 12 : pa.degree != 2 ? 10 : 8;
   g_last_draw_kernel.store(id + (lockstep ? 1 : 0), std::memory_order_relaxed);
   const int rc = (int) cb::launch_draw_plot(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
   if (interior_level && !rc && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
+  return rc;
+}
+
+// The depth of a depth render ("Depth render"): finite row and bounds, min < max with a finite difference, N in range, and
+// N * h rows still an int (the planes are tone-mapped as one w x N*h image).
+bool depth_ok(const cb_depth *d, int h) {
+  if (!d) return false;
+  for (int j = 0; j < 4; ++j) {
+    if (!isfinite(d->row[j])) return false;
+  }
+  if (!isfinite(d->min) || !isfinite(d->max) || !(d->min < d->max) || !isfinite(d->max - d->min)) return false;
+  if (d->slices < 1 || d->slices > CB_DEPTH_MAX_SLICES) return false;
+  return (long long) d->slices * (long long) h <= 0x7fffffffLL;
+}
+
+// The depth draw (draw_depth.hip): what cb_draw_buddhabrot_depth and a renderer with a depth do once their own arguments
+// have passed.
+int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+               const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
+               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream,
+               int *interior_level) {
+  if (interior_level) *interior_level = 0;
+  cb::DepthArgs da;
+  memset(&da, 0, sizeof(da));
+  bool lockstep = false;
+  {
+    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads,
+                             samples_per_thread, d_counters, kernel_variant, &da.p, &lockstep);
+    if (rc) return rc;
+  }
+  memcpy(da.row, depth->row, sizeof(da.row));
+  da.min = depth->min;
+  da.delta = (depth->max - depth->min) / (double) depth->slices;  // as cb_recompute_pixel_deltas makes delta_imag
+  if (!(da.delta > 0.0) || !isfinite(da.delta)) return (int) hipErrorInvalidValue;  // (a window wider than a double)
+  da.pow2 = exact_reciprocal(da.delta, &da.inv_delta) ? 1 : 0;
+  da.slices = depth->slices;
+  da.plane_pixels = da.p.plane_pixels;
+  g_last_draw_kernel.store(lockstep ? 19 : 18, std::memory_order_relaxed);
+  const int rc = (int) cb::launch_draw_depth(da, lockstep, reinterpret_cast<hipStream_t>(stream));
+  if (interior_level && !rc && da.p.d.interior_map) *interior_level = (int) da.p.d.interior_shift + 1;
   return rc;
 }
 
@@ -1015,7 +1086,7 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
 }
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
-  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || !lut_host ||
+  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || !lut_host ||
       !palette_entries_ok(n_entries, &r->iterations)) {
     return (int) hipErrorInvalidValue;
   }
@@ -1053,6 +1124,48 @@ int cb_renderer_palette(const cb_renderer *r, uint32_t *n_entries) {
   if (!r || !r->palette) return 0;
   if (n_entries) *n_entries = r->palette_entries;
   return 1;
+}
+
+// ---- depth render (draw_depth.hip; include/cudabrot_amd.h, "Depth render") ------------------------------------------
+
+int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
+                             uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                             void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  if (!depth_ok(depth, dims->h)) return (int) hipErrorInvalidValue;
+  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, d_states, n_threads, samples_per_thread,
+                    d_counters, kernel_variant, stream, nullptr);
+}
+
+int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
+  // a projected or Julia renderer (a palette renderer is projected too, a channel or focused one never is)
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || !depth_ok(depth, r->dims.h)) {
+    return (int) hipErrorInvalidValue;
+  }
+  CB_TRY(hipSetDevice(r->device));
+  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
+  const size_t hist_bytes = (size_t) depth->slices * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
+  cb_pixel *d_hist = nullptr;
+  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
+  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
+  if (rc) {
+    (void) hipFree(d_hist);
+    return rc;
+  }
+  (void) hipFree(r->d_hist);
+  r->d_hist = d_hist;
+  r->depth = *depth;
+  r->has_depth = true;
+  return 0;
+}
+
+int cb_renderer_depth(const cb_renderer *r, cb_depth *out) {
+  if (!r || !r->has_depth) return 0;
+  if (out) *out = r->depth;
+  return r->depth.slices;
 }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
@@ -1273,6 +1386,27 @@ int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint1
   return rc;
 }
 
+int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
+                            double *scale_out) {
+  if (!r || !r->has_depth || !host_gray_be) return (int) hipErrorInvalidValue;
+  CB_TRY(hipSetDevice(r->device));
+  {
+    int rc = finish(r);
+    if (rc) return rc;
+  }
+  const int slices = r->depth.slices;  // slices * h fits an int: cb_renderer_set_depth
+  const size_t bytes = (size_t) slices * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(uint16_t);
+  uint16_t *d_gray = nullptr;
+  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
+  // the planes as one w x N*h image: one maximum for all of them
+  int rc = cb_tone_map_device(r->d_hist, r->dims.w, slices * r->dims.h, gamma, tone_mode, d_gray, max_out, scale_out,
+                              r->stream);
+  if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
+  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
+  (void) hipFree(d_gray);
+  return rc;
+}
+
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
                             const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
@@ -1379,7 +1513,8 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
   for (int k = 0; k < n; ++k) {
     cb_renderer *r = renderers[k];
     if (!r || r->dims.w != renderers[0]->dims.w || r->dims.h != renderers[0]->dims.h ||
-        r->n_channels != renderers[0]->n_channels || r->palette != renderers[0]->palette) {
+        r->n_channels != renderers[0]->n_channels || r->palette != renderers[0]->palette ||
+        renderer_planes(r) != renderer_planes(renderers[0])) {
       return (int) hipErrorInvalidValue;
     }
     CB_TRY(hipSetDevice(r->device));

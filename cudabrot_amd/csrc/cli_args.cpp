@@ -54,6 +54,47 @@ bool parse_julia(const char *text, double out[2]) {
   return true;
 }
 
+// --depth ROW:MIN:MAX[:N]: ROW an axis name or four finite numbers a,b,c,d, MIN < MAX finite, N decimal digits, 1 ..
+// CB_DEPTH_MAX_SLICES (1 where it is left out); the numbers in strtod's syntax (hexfloats included).
+bool parse_depth(const char *text, cb_depth *out) {
+  const char *at = text;
+  const int axis = axis_of(at, ':', &at);
+  for (int j = 0; j < 4; ++j) {
+    if (axis >= 0) {
+      out->row[j] = j == axis ? 1.0 : 0.0;
+      continue;
+    }
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    out->row[j] = strtod(at, &end);
+    if (end == at || !isfinite(out->row[j]) || *end != (j == 3 ? ':' : ',')) return false;
+    at = end + 1;
+  }
+  double bounds[2];
+  for (int j = 0; j < 2; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;
+    char *end = nullptr;
+    bounds[j] = strtod(at, &end);
+    if (end == at || !isfinite(bounds[j]) || (j == 0 ? *end != ':' : (*end != ':' && *end != 0))) return false;
+    at = *end ? end + 1 : end;
+    if (j == 1 && *end == ':' && *at == 0) return false;  // a colon and no N
+  }
+  if (!(bounds[0] < bounds[1])) return false;
+  long n = 1;
+  if (*at != 0) {
+    n = 0;
+    for (; *at >= '0' && *at <= '9'; ++at) {
+      n = n * 10 + (*at - '0');
+      if (n > CB_DEPTH_MAX_SLICES) return false;
+    }
+    if (*at != 0 || n < 1) return false;
+  }
+  out->min = bounds[0];
+  out->max = bounds[1];
+  out->slices = (int) n;
+  return true;
+}
+
 // --palette K:RRGGBB[,K:RRGGBB...]: 1 to CB_PALETTE_MAX_STOPS stops, K decimal digits and strictly ascending, the colour
 // six hex digits.  Returns the number of stops, 0 for anything else.
 int parse_palette(const char *text, cb_palette_stop out[CB_PALETTE_MAX_STOPS]) {
@@ -342,6 +383,17 @@ const std::vector<Flag> &flag_table() {
          }
          return "Invalid formula (want tricorn, celtic, buffalo, perpendicular or celtic-tricorn)";
        }},
+      // --depth ROW:MIN:MAX[:N]: the 4-D set sliced along a third row into N planes, a section (N = 1) or a volume; on
+      // the projected path with any plane, --power, --julia, --formula or --burning-ship; -o receives N PGMs back to back
+      // (include/cudabrot_amd.h, "Depth render")
+      {"--depth", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.depth_given = true;
+         return parse_depth(t, &s.depth)
+                    ? kOk
+                    : "Invalid depth (want ROW:MIN:MAX[:N], ROW an axis zr, zi, cr, ci or four numbers, MIN < MAX, N from 1 "
+                      "to " CB_TEXT_OF(CB_DEPTH_MAX_SLICES) ")";
+       }},
       // --seed N: the generator's seed, 64 bits wide (rocrand_init)
       {"--seed", Value::kLong, nullptr, false,
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; return kOk; }},
@@ -421,6 +473,7 @@ const Partner kFocus = {[](const Settings &s) { return s.focus; }, "--focus"};
 const Partner kChannel = {[](const Settings &s) { return s.n_channels > 0 || s.color_file; }, "--channel"};
 const Partner kGpus = {[](const Settings &s) { return s.gpus > 1; }, "--gpus above 1"};
 const Partner kRaw = {[](const Settings &s) { return s.raw_state; }, "--state-format raw"};
+const Partner kPalette = {[](const Settings &s) { return s.palette(); }, "--palette"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -466,6 +519,9 @@ const std::vector<Refusal> &refusal_table() {
       // after parsing: --color and the --channel flags come in any order
       {[](const Settings &s) { return s.color_file && s.n_channels != 3; }, nullptr, {},
        [](const Settings &s) { printf("--color needs exactly 3 --channel images, got %d.\n", s.n_channels); }},
+      // a depth render is a projected render with N planes (include/cudabrot_amd.h, "Depth render"); behind every other
+      // row: where a flag that turns the projected path on is given as well, that flag's row has spoken already
+      {[](const Settings &s) { return s.depth_given; }, "--depth", {kPalette, kAnti, kFocus, kChannel, kGpus, kRaw}, nullptr},
   };
   return table;
 }

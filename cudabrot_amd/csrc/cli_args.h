@@ -63,6 +63,12 @@ struct Settings {
   bool projected() const {
     return project_given || plane_given || rotate_given || power != 0 || julia || palette() || formula != 0;
   }
+  // --depth ROW:MIN:MAX[:N] (extension): the set sliced along a third row into N planes (cb_renderer_set_depth); makes the
+  // run a projected one as --power does, but is no part of projected(): its refusals are a row of their own, behind the
+  // projection's
+  bool depth_given = false;
+  cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
+  bool plotted() const { return projected() || depth_given; }
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

@@ -65,13 +65,18 @@ class Run {
     printf("Creating %dx%d image, %d max iterations.\n", cfg_.canvas.w, cfg_.canvas.h,
            max_iterations);  // cudabrot.cu:779-780
     printf("Calculating image...\n");
-    if (cfg_.projected() && cfg_.print_stats) {  // the matrix defines the run: printed before any device is touched
+    if (cfg_.plotted() && cfg_.print_stats) {  // the matrix defines the run: printed before any device is touched
       const double *p = cfg_.projection;
       fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
               p[3], p[4], p[5], p[6], p[7]);
       if (cfg_.power != 0) fprintf(stderr, "{\"power\": %d}\n", cfg_.power);  // the step: it defines the run as well
       if (cfg_.formula != 0) fprintf(stderr, "{\"formula\": \"%s\"}\n", cfg_.formula_name);  // or this step
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
+      if (cfg_.depth_given) {  // and the third row with its window
+        const cb_depth &d = cfg_.depth;
+        fprintf(stderr, "{\"depth\": {\"row\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"min\": \"%a\", \"max\": \"%a\", \"slices\": %d}}\n",
+                d.row[0], d.row[1], d.row[2], d.row[3], d.min, d.max, d.slices);
+      }
       if (cfg_.palette()) {  // and the colours
         fprintf(stderr, "{\"palette\": [");
         for (int j = 0; j < cfg_.n_palette_stops; ++j) {
@@ -95,6 +100,10 @@ class Run {
       printf("Saving image.\n");
       report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
       printf("Done! Output image saved: %s\n", cfg_.output_image);
+    } else if (cfg_.depth_given) {
+      printf("Saving image.\n");
+      report_save(save_depth_images(cfg_.output_image));
+      printf("Done! Output image saved: %s\n", cfg_.output_image);
     } else {
       printf("Saving image.\n");
       save_image(cfg_.output_image);
@@ -115,11 +124,15 @@ class Run {
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
   std::vector<uint16_t> palette_rgb_be_;  // --palette: the PPM body
+  std::vector<uint16_t> depth_gray_be_;   // --depth: the bodies of the N PGMs, slice 0 first
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
   uint64_t pixel_count() const { return (uint64_t) cfg_.canvas.w * (uint64_t) cfg_.canvas.h; }
-  uint64_t planes() const { return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u); }
+  uint64_t planes() const {
+    if (cfg_.depth_given) return (uint64_t) cfg_.depth.slices;
+    return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u);
+  }
   uint64_t buffer_bytes() const { return planes() * pixel_count() * sizeof(cb_pixel); }
 
   void release() {  // cudabrot.cu:112-119
@@ -174,9 +187,10 @@ class Run {
     }
     if (cfg_.julia) {
       CB_CHECK(cb_renderer_set_julia(renderer_, cfg_.projection, cfg_.julia_c));
-    } else if (cfg_.projected()) {
+    } else if (cfg_.plotted()) {
       CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
     }
+    if (cfg_.depth_given) CB_CHECK(cb_renderer_set_depth(renderer_, &cfg_.depth));  // after the plane and c
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -312,6 +326,8 @@ class Run {
     if (cfg_.print_stats) print_stats();
     if (cfg_.palette()) {
       palette_image();
+    } else if (cfg_.depth_given) {
+      depth_image();
     } else if (cfg_.n_channels == 0) {
       tone_map(0);
     }
@@ -483,6 +499,40 @@ class Run {
                                          &scale));
     }
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+  }
+
+  // --depth: the N planes tone-mapped against their common maximum, as one w x N*h image -- on the device, or with
+  // --tonemap host by the reference's host loop; the bytes are the same.
+  void depth_image() {
+    uint64_t max = 0;
+    double scale = 0.0;
+    depth_gray_be_.resize(planes() * pixel_count());
+    if (cfg_.host_tonemap) {
+      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, cfg_.depth.slices * cfg_.canvas.h, cfg_.gamma_correction,
+                              depth_gray_be_.data(), &max, &scale);
+      for (uint16_t &v : depth_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
+    } else {
+      CB_CHECK(cb_renderer_depth_image(renderer_, cfg_.gamma_correction, cfg_.tone_mode, depth_gray_be_.data(), &max,
+                                       &scale));
+    }
+    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+  }
+
+  // --depth: N binary PGMs back to back in one file (Netpbm's format allows a sequence of images), each SaveImage's
+  // (cudabrot.cu:548-577); 0, or 1/2/3 = open / header / pixel-data failure as cb_save_image.
+  int save_depth_images(const char *path) {
+    FILE *f = fopen(path, "wb");
+    if (!f) return 1;
+    int rc = 0;
+    for (uint64_t s = 0; s < planes() && rc == 0; ++s) {
+      if (fprintf(f, "P5\n%d %d\n65535\n", cfg_.canvas.w, cfg_.canvas.h) <= 0) {
+        rc = 2;
+      } else if (fwrite(depth_gray_be_.data() + s * pixel_count(), sizeof(uint16_t), pixel_count(), f) != pixel_count()) {
+        rc = 3;
+      }
+    }
+    if (fclose(f) != 0 && rc == 0) rc = 3;
+    return rc;
   }
 
   // Fused multi-channel render: one image per window.

@@ -268,6 +268,26 @@ struct PlotArgs {
 };
 hipError_t launch_draw_plot(const PlotArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_depth.hip: the depth render ("Depth render" of include/cudabrot_amd.h) -- a plotted launch without a table whose
+// visited points are binned along a third row as well, into `slices` planes of the histogram.
+//   p        the launch of draw_plot.hip it extends: canvas, matrix, step and source of c as there; palette must be 0 and
+//            lut null.  p.d.hist is `slices` planes plane_pixels counters apart.
+//   row      the depth row D, columns (z_re, z_im, c_re, c_im), finite.
+//   min, delta, inv_delta, pow2   the depth window's lower bound and its step (max - min) / slices, made on the host as
+//            DrawArgs::delta_imag is; pow2 != 0: delta is a power of two and inv_delta its exact reciprocal.
+//   slices   N, 1 .. CB_DEPTH_MAX_SLICES.
+//   plane_pixels   w * h.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of p, a table, slices out of range, a delta
+// that is not positive, a plane_pixels that is not w * h.  lockstep: the definition, one lane per reference thread.
+struct DepthArgs {
+  PlotArgs p;
+  double row[4];
+  double min, delta, inv_delta;
+  int pow2, slices;
+  unsigned long long plane_pixels;
+};
+hipError_t launch_draw_depth(const DepthArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

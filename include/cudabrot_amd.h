@@ -532,6 +532,72 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
                                uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
                                cb_counters *d_counters, int kernel_variant, void *stream);
 
+/* ---- Depth render: the 4-D set sliced along a third axis into N planes --------------- *
+ *
+ * A projected render shows the shadow of the four-dimensional set on a plane: it integrates over the two directions that
+ * are not plotted.  A DEPTH render keeps one of them: it is a projected render ("Projected render" above; julia_c NULL)
+ * or a Julia render ("Julia render"; julia_c given) with one more parameter block, cb_depth below, and those sections,
+ * together with "Multibrot step" and "Formula step", apply unchanged: the sample stream, rejection, the interior map
+ * where the Mandelbrot step on a sampled c has one, the iteration, the escape index, the accept filter min <= k < max,
+ * the replayed points z_1 ... z_{k+1}, (u, v) and their binning.  N = 1 is a SECTION of the set (only the points whose
+ * depth lies in the window), N > 1 a VOLUME (the "3-D Buddhabrot" is the (z_re, z_im, c_re) case).  The project's own
+ * definition (the reference has none).  Normative:
+ *
+ *   Parameter.  cb_depth: the depth row D[4], columns in the order (z_re, z_im, c_re, c_im), every entry finite; the
+ *   depth window [min, max), both finite, min < max and max - min finite; the number of slices N, 1 <= N <=
+ *   CB_DEPTH_MAX_SLICES.  Anything else is hipErrorInvalidValue, and so is N * h > INT_MAX.
+ *
+ *   Depth of a visited point.
+ *       K_d = fma(D[2], c_re, D[3] * c_im)                        (once per sample; for a Julia render once, from the
+ *                                                                  fixed c)
+ *       d   = fma(D[0], z_re, fma(D[1], z_im, K_d))
+ *   -- the same fused operations as u and v: IEEE fp64, each fma one rounding, nothing else contracted.
+ *
+ *   Slice.  delta_d = (max - min) / (double) N, made on the host exactly as cb_recompute_pixel_deltas makes delta_imag.
+ *   The point is IN DEPTH iff !(d < min) and s = (int) ((d - min) / delta_d) satisfies 0 <= s < N: the reference's
+ *   binning of `im`, with the same early-out, the same truncation and the same bounds test.  (A kernel may multiply by
+ *   the reciprocal where delta_d is a power of two, as the binning of (u, v) does: that is the same value.)
+ *
+ *   Histogram.  N planes of w*h cb_pixel, contiguous, plane s at offset s*w*h (64-bit arithmetic).  A visited point that
+ *   is on the canvas and in depth adds 1 to its pixel of plane s.  Every other point adds nothing.
+ *
+ *   Counters.  increments counts the points added.  Every other counter is what the same render without a depth counts;
+ *   skipped_steps is the product kernel's executed-work discount as usual, and the lock-step kernel leaves it 0.
+ *
+ *   Consequences.  The sum of the planes is the projected or Julia render restricted to the points in depth; if the
+ *   window holds every visited point, that sum is the projected or Julia render itself, bit for bit.  (|z_0|^2 <= 8 and
+ *   every later point follows one with |z|^2 <= 4, so every visited |z| of a step of degree d is at most
+ *   (2 sqrt 2)^d + 2 sqrt 2: 8 + 2 sqrt 2 for degree 2.)
+ *
+ *   No table.  A depth render of a palette render -- 3 N planes -- is out of scope and refused.
+ *
+ *   Image.  Let M be the largest counter of all N planes together.  Each counter maps to cb_tone_value(count, M, gamma):
+ *   cb_set_grayscale_pixels applied to the planes as one w x N*h image.  A common maximum, because the ratio between
+ *   slices is the volume's density.  The file is N binary PGMs back to back (Netpbm's format allows a sequence of images
+ *   in a file), slice 0 first, each "P5\n%d %d\n65535\n" and w*h big-endian u16; with N = 1 an ordinary PGM.
+ *
+ * Two kernels (draw_depth.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c, lanes refilled from their
+ * own subsequence with the exact-periodicity early-out and, for the Mandelbrot step on a sampled c, the interior map
+ * under cb_draw_buddhabrot_projected's rule; CB_KERNEL_SIMPLE, the definition in lock-step.  Variants are
+ * cb_draw_buddhabrot_julia's: optionally | CB_KERNEL_FLAG_BURNING_SHIP, | CB_KERNEL_POWER(d) or | CB_KERNEL_FORMULA(f);
+ * anything else is hipErrorInvalidValue, with nothing launched or written.  Identical histograms, generator states and
+ * counters (but skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete when it ends.  The -s
+ * buffer has N planes and records the row and the window no more than it records the plane, the degree or c. */
+#define CB_DEPTH_MAX_SLICES 256
+typedef struct {
+  double row[4];   /* the depth row D: columns (z_re, z_im, c_re, c_im), finite */
+  double min, max; /* the depth window [min, max), finite, min < max */
+  int slices;      /* N, 1 .. CB_DEPTH_MAX_SLICES */
+} cb_depth;
+/* The depth draw on caller-owned device memory: d_hist is N = depth->slices planes of w*h cb_pixel.  julia_c NULL: c is
+ * sampled (a projected render); else the fixed c of a Julia render.  hipErrorInvalidValue, with nothing launched or
+ * written: a NULL depth, a non-finite row entry or bound, min >= max, N outside 1 .. CB_DEPTH_MAX_SLICES, N * h > INT_MAX,
+ * and everything cb_draw_buddhabrot_projected (julia_c NULL) or cb_draw_buddhabrot_julia refuses. */
+int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
+                             uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                             void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -601,6 +667,18 @@ int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n
 /* A palette renderer's table: returns 1 and sets *n_entries (may be NULL); returns 0 and leaves it alone for any other
  * renderer (or a NULL renderer). */
 int cb_renderer_palette(const cb_renderer *r, uint32_t *n_entries);
+/* Gives this renderer a DEPTH ("Depth render" above); on a projected or Julia renderer, before its first pass, once --
+ * the order on a renderer is projection, then julia, then depth.  The histogram is reallocated and zeroed as N =
+ * depth->slices planes; every later cb_renderer_render_passes launches depth draws with the variants of the renderer it
+ * was, and render_passes, finish, read / write_histogram (N planes), read_counters, the generator states and
+ * cb_renderer_grayscale_plane (planes 0 .. N - 1, each with its own maximum, as for channels) work on the N planes.
+ * hipErrorInvalidValue for a plain, channel, focused or palette renderer, a renderer that has rendered or has a depth
+ * already, and whatever "Depth render" refuses of *depth.  Afterwards cb_renderer_set_palette,
+ * cb_renderer_set_projection, cb_renderer_set_julia and cb_renderer_set_focus are refused. */
+int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth);
+/* A renderer's depth: returns N and fills *out (may be NULL); returns 0 and leaves it alone for a renderer without one
+ * (or a NULL renderer). */
+int cb_renderer_depth(const cb_renderer *r, cb_depth *out);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -674,6 +752,13 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
  * palette. */
 int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                               double *scale_out);
+
+/* The image of a renderer with a depth ("Depth render", Image; finishes carried work first): cb_tone_map_device over the
+ * N planes as one w x N*h image -- one maximum for all of them.  host_gray_be receives the N*w*h big-endian u16, slice
+ * 0 first (the bodies of the N PGMs); *max_out and *scale_out (may be NULL) the two numbers of the "Max value" line.
+ * hipErrorInvalidValue for a renderer without a depth. */
+int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
+                            double *scale_out);
 
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
@@ -768,7 +853,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * cb_draw_buddhabrot_projected with CB_KERNEL_POWER), 11 the Multibrot lock-step kernel, 12 the Julia product kernel
  * (draw_plot_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
  * (draw_plot_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel, 16 the formula product kernel
- * (draw_plot_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel.
+ * (draw_plot_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel, 18 the depth
+ * product kernel (draw_depth_kernel: cb_draw_buddhabrot_depth, whatever its step), 19 the depth lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

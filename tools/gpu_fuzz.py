@@ -19,6 +19,11 @@ and demands identical histograms and counters.
     POWER=1 python tools/gpu_fuzz.py ...           the Multibrot render (CB_KERNEL_POWER): draw_plot_kernel (PowerOrbit<D>) against
                                                    draw_power_simple_kernel (draw_plot.hip) -- random degree,
                                                    shapes and matrices, generator states compared as well
+    DEPTH=1 python tools/gpu_fuzz.py ...           the depth render (cb_draw_buddhabrot_depth): draw_depth_kernel against
+                                                   draw_depth_simple_kernel (draw_depth.hip) -- random step, source of
+                                                   c, canvas, window, matrix, depth row, depth window, N, thread count
+                                                   and launches, generator states compared as well; TRIALS=N ends the
+                                                   run after N trials where that comes before SECONDS
 """
 import os
 
@@ -306,6 +311,125 @@ def power_main(seconds, seed):
     return 0
 
 
+def depth_trial(rng):
+    """A depth launch sequence: any step and either source of c, max_iter at and around the scheduler's rounds (12 steps)
+    and chunks (60), ragged thread counts, several launches on the same generators, small canvases (the histogram is N
+    of them), a plane and a depth row out of unit rows or random entries, a depth window that is dyadic or not, that
+    holds everything, cuts the set or misses it."""
+    t = {}
+    t["w"] = rng.choice([1, 2, 7, 64, 100, 128, 129, 255, 256, 333])
+    t["h"] = rng.choice([1, 3, 8, 64, 100, 127, 128, 200, 256])
+    kind = rng.random()
+    if kind < 0.5:
+        t["box"] = (-2.0, 2.0, -2.0, 2.0)
+    elif kind < 0.9:
+        cx, cy = rng.uniform(-1.5, 0.5), rng.uniform(-1.0, 1.0)
+        rx, ry = rng.uniform(0.05, 2.0), rng.uniform(0.05, 2.0)
+        t["box"] = (cx - rx, cx + rx, cy - ry, cy + ry)
+    else:
+        t["box"] = (1.0, 3.0, 1.0, 2.5)
+    step = rng.choice(["reference", "reference", "ship", "power", "formula"])
+    t["degree"] = rng.randint(cb.CB_POWER_MIN, cb.CB_POWER_MAX) if step == "power" else 2
+    t["ship"] = step == "ship"
+    t["formula"] = rng.randint(cb.CB_FORMULA_TRICORN, cb.CB_FORMULA_MAX) if step == "formula" else 0
+    t["c"] = None if rng.random() < 0.6 else (rng.choice([-0.8, 0.3, 0.0, -2.0, 2.0, rng.uniform(-2.0, 2.0)]),
+                                              rng.choice([0.156, 0.0, 0.5, 2.0, rng.uniform(-2.0, 2.0)]))
+    t["max_iter"] = rng.choice([0, 1, 5, 11, 12, 13, 59, 60, 61, 119, 120, 121, 180, 257, 500, 1000, 2000])
+    t["min_iter"] = rng.choice([0, 0, 1, 2, 20, 59, 60, 99, 1000])
+    t["threads"] = rng.choice([1, 63, 64, 65, 200, 256, 1000, 1024, 1337, 4096])
+    if t["max_iter"] >= 1000:   # keep the lock-step kernel's run time in hand
+        t["threads"] = min(t["threads"], 1024)
+    t["launch_samples"] = [rng.choice([1, 2, 7, 50, 64]) for _ in range(rng.randint(1, 3))]
+    t["seed"] = rng.choice([1337, 1337, 1, 0xdeadbeefcafe])
+    t["first"] = rng.choice([0, 0, 1, 262144, 2097151])
+
+    def unit(j):
+        return [1.0 if k == j else 0.0 for k in range(4)]
+
+    kind = rng.random()
+    if kind < 0.3:
+        t["matrix"] = list(cb.IDENTITY_PROJECTION)
+    elif kind < 0.6:   # two different axes of (zr, zi, cr, ci)
+        x, y = rng.sample(range(4), 2)
+        t["matrix"] = unit(x) + unit(y)
+    else:
+        t["matrix"] = [rng.uniform(-1.5, 1.5) for _ in range(8)]
+    t["row"] = unit(rng.randrange(4)) if rng.random() < 0.5 else [rng.uniform(-1.5, 1.5) for _ in range(4)]
+    t["slices"] = rng.choice([1, 1, 2, 3, 4, 5, 7, 8, 16, 64, 100, 255, 256])
+    kind = rng.random()
+    if kind < 0.25:     # holds everything, dyadic for a power-of-two N
+        t["window"] = (-64.0, 64.0)
+    elif kind < 0.5:    # dyadic
+        t["window"] = rng.choice([(-2.0, 2.0), (-1.0, 1.0), (-2.0, 0.0), (0.0, 0.5), (-0.125, 0.125)])
+    elif kind < 0.9:    # anywhere near the set
+        lo = rng.uniform(-2.5, 1.0)
+        t["window"] = (lo, lo + rng.uniform(0.01, 3.0))
+    else:               # far from it: almost nothing lands
+        t["window"] = (5.0, 9.0)
+    return t
+
+
+def render_depth(t, variant):
+    """The launches of a depth trial -> (histogram, counters, generator states)."""
+    dev = torch.device("cuda", 0)
+    dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
+    it = cb.IterationControl(t["max_iter"], t["min_iter"])
+    n = t["threads"]
+    depth = cb.Depth.make(t["row"], t["window"][0], t["window"][1], t["slices"])
+    flags = ((cb.CB_KERNEL_POWER(t["degree"]) if t["degree"] != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
+             | (cb.CB_KERNEL_FORMULA(t["formula"]) if t["formula"] else 0))
+    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
+    hist = torch.zeros(t["slices"] * t["w"] * t["h"], dtype=torch.int64, device=dev)
+    counters = torch.zeros(17, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
+    for s in t["launch_samples"]:
+        cb.draw_buddhabrot_depth(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, states.data_ptr(), n, s,
+                                 counters.data_ptr(), variant | flags, stream)
+    torch.cuda.synchronize()
+    c = counters.cpu().numpy().view(np.uint64)
+    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
+    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
+
+
+def depth_main(seconds, seed):
+    rng = random.Random(seed)
+    t_end = time.time() + seconds
+    trials = int(os.environ.get("TRIALS", "0"))
+    n = early = filled = 0
+    last_print = time.time()
+    while time.time() < t_end and not (trials and n >= trials):
+        t = depth_trial(rng)
+        try:
+            want, wc, want_states = render_depth(t, cb.CB_KERNEL_SIMPLE)
+            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 19
+            got, gc, got_states = render_depth(t, cb.CB_KERNEL_DEFAULT)
+            product_ran = cb.lib.cb_debug_last_draw_kernel() == 18
+        except cb.CudabrotError as e:
+            print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
+            return 1
+        bad = [k for k in COMPARED if wc[k] != gc[k]]
+        if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
+                lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or int(want.sum()) != wc["increments"]:
+            print("MISMATCH at depth trial %d (seed %d): %r" % (n, seed, t))
+            print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
+            print("  counters that differ: %r; lock-step skipped_steps %d" % ([(k, wc[k], gc[k]) for k in bad],
+                                                                            wc["skipped_steps"]))
+            print("  generator states identical: %s" % np.array_equal(want_states, got_states))
+            print("  pixels that differ: %d of %d; sums %d vs %d; increments %d" % (
+                int((want != got).sum()), want.size, int(want.sum()), int(got.sum()), wc["increments"]), flush=True)
+            return 1
+        n += 1
+        early += 1 if gc["skipped_steps"] > 0 else 0
+        filled += 1 if wc["increments"] > 0 else 0
+        if time.time() - last_print > 30:
+            print("%d depth trials identical so far (%d with skipped_steps > 0)" % (n, early), flush=True)
+            last_print = time.time()
+    print("gpu_fuzz: %d depth trials (%d with skipped_steps > 0, %d with increments > 0), histograms, counters and "
+          "generator states identical (seed %d)" % (n, early, filled, seed))
+    return 0
+
+
 def heavy_trial(rng):
     """Product-sized launches: the deferred scatter (one and two sort levels, carry) against the same
     kernel with direct atomics -- the lock-step kernel would take minutes at these sizes."""
@@ -379,6 +503,8 @@ def main():
         return anti_main(seconds, seed)
     if os.environ.get("POWER") == "1":
         return power_main(seconds, seed)
+    if os.environ.get("DEPTH") == "1":
+        return depth_main(seconds, seed)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     n = 0
