@@ -319,6 +319,11 @@ def _load():
         "cb_renderer_set_depth": (i32, [vp, depth_p]),
         "cb_renderer_depth": (i32, [vp, depth_p]),
         "cb_renderer_depth_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_draw_buddhabrot_depth_palette": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), depth_p,
+                                                   vp, u32, vp, u32, u32, vp, i32, vp]),
+        "cb_renderer_set_depth_palette": (i32, [vp, depth_p, vp, u32]),
+        "cb_renderer_depth_palette": (i32, [vp, depth_p, C.POINTER(u32)]),
+        "cb_renderer_depth_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -342,7 +347,9 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_projected cb_renderer_set_projection cb_renderer_projection cb_debug_scatter_layout "
     "cb_draw_buddhabrot_julia cb_renderer_set_julia cb_renderer_julia "
     "cb_palette_from_stops cb_draw_buddhabrot_palette cb_renderer_set_palette cb_renderer_palette cb_renderer_palette_image "
-    "cb_draw_buddhabrot_depth cb_renderer_set_depth cb_renderer_depth cb_renderer_depth_image"
+    "cb_draw_buddhabrot_depth cb_renderer_set_depth cb_renderer_depth cb_renderer_depth_image "
+    "cb_draw_buddhabrot_depth_palette cb_renderer_set_depth_palette cb_renderer_depth_palette "
+    "cb_renderer_depth_palette_image"
 ).split()
 
 
@@ -527,6 +534,20 @@ def draw_buddhabrot_depth(dims, d_hist, iterations, projection, julia_c, depth, 
     )
 
 
+def draw_buddhabrot_depth_palette(dims, d_hist, iterations, projection, julia_c, depth, d_lut, n_entries, d_states,
+                                  n_threads, samples_per_thread, d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The depth-palette draw on caller-owned device memory (cb_draw_buddhabrot_depth_palette): d_hist is three planes,
+    d_lut the table of n_entries == depth.slices entries on the device; depth is a Depth or (row, min, max[, slices]);
+    julia_c None samples c (a projected render), else c is fixed."""
+    _check(
+        lib.cb_draw_buddhabrot_depth_palette(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                             None if julia_c is None else _julia_c(julia_c), C.byref(_depth(depth)), d_lut,
+                                             n_entries, d_states, n_threads, samples_per_thread, d_counters, kernel_variant,
+                                             stream),
+        "cb_draw_buddhabrot_depth_palette",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -540,6 +561,7 @@ class Renderer:
         self._h = C.c_void_p()
         self.palette_entries = 0
         self.depth_slices = 0
+        self.depth_palette_entries = 0
         if isinstance(iterations, IterationControl):
             self.n_channels = 0
             _check(
@@ -639,10 +661,35 @@ class Renderer:
                                            C.byref(scale)), "cb_renderer_depth_image")
         return gray, int(mx.value), float(scale.value)
 
+    def set_depth_palette(self, depth, lut):
+        """Give this renderer a depth palette (cb_renderer_set_depth_palette), before the first pass and after
+        set_projection or set_julia: depth is a Depth or (row, min, max[, slices]), lut the table, `slices` u32 entries.
+        The histogram becomes three planes."""
+        d = _depth(depth)
+        a = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+        _check(lib.cb_renderer_set_depth_palette(self._h, C.byref(d), a.ctypes.data, a.size), "cb_renderer_set_depth_palette")
+        self.depth_palette_entries = int(a.size)
+
+    def depth_palette(self):
+        """(Depth, entries of the table) of a renderer with a depth palette; None for any other renderer."""
+        out, n = Depth(), C.c_uint32()
+        if not lib.cb_renderer_depth_palette(self._h, C.byref(out), C.byref(n)):
+            return None
+        return out, int(n.value)
+
+    def depth_palette_image(self, gamma=1.0, mode=0):
+        """The image of a renderer with a depth palette (cb_renderer_depth_palette_image) -> (big-endian u16 image [h,w,3] =
+        the PPM body, the largest count of the three planes, scale)."""
+        rgb = np.empty((self.dims.h, self.dims.w, 3), dtype=">u2")
+        mx, scale = C.c_uint64(), C.c_double()
+        _check(lib.cb_renderer_depth_palette_image(self._h, float(gamma), int(mode), rgb.ctypes.data, C.byref(mx),
+                                                   C.byref(scale)), "cb_renderer_depth_palette_image")
+        return rgb, int(mx.value), float(scale.value)
+
     def _planes(self):
         if self.depth_slices:
             return self.depth_slices
-        return 3 if self.palette_entries else (self.n_channels or 1)
+        return 3 if self.palette_entries or self.depth_palette_entries else (self.n_channels or 1)
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""
@@ -659,7 +706,7 @@ class Renderer:
         planes = self._planes()
         out = np.empty(planes * self.dims.w * self.dims.h, dtype=np.uint64)
         _check(lib.cb_renderer_read_histogram(self._h, out.ctypes.data), "cb_renderer_read_histogram")
-        if self.n_channels or self.palette_entries or self.depth_slices:
+        if self.n_channels or self.palette_entries or self.depth_slices or self.depth_palette_entries:
             return out.reshape(planes, self.dims.h, self.dims.w)
         return out.reshape(self.dims.h, self.dims.w)
 

@@ -314,24 +314,29 @@ struct cb_renderer {
   // depth.slices planes
   bool has_depth;
   cb_depth depth;
+  // depth-palette render (cb_renderer_set_depth_palette): a projected or Julia renderer whose draws bin along `depth`'s row
+  // and weigh each point by the entry of its slice; d_hist is then three planes.  has_depth stays false: the planes are
+  // not the slices
+  bool depth_palette;
+  uint32_t *d_depth_lut;  // depth.slices entries
 };
 
 namespace {
 
-// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette renderer, the slices of
-// a renderer with a depth, else one.
+// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette or depth-palette
+// renderer, the slices of a renderer with a depth, else one.
 size_t renderer_planes(const cb_renderer *r) {
   if (r->has_depth) return (size_t) r->depth.slices;
-  return r->palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u);
+  return r->palette || r->depth_palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u);
 }
 
 int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
               const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
               uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
 int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-               const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
-               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream,
-               int *interior_level);
+               const double projection[8], const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut,
+               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+               int kernel_variant, void *stream, int *interior_level);
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
@@ -346,8 +351,9 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   }
   if (r->projected) {  // draw_plot.hip: direct atomics, no deferred scatter, no carry; what the setters took is checked
     if (passes == 0) return 0;
-    if (r->has_depth) {  // draw_depth.hip, likewise
+    if (r->has_depth || r->depth_palette) {  // draw_depth.hip, draw_depth_palette.hip, likewise
       return draw_depth(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr, &r->depth,
+                        r->depth_palette ? r->d_depth_lut : nullptr, r->depth_palette ? (uint32_t) r->depth.slices : 0u,
                         r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
                         &r->interior_level);
     }
@@ -956,12 +962,13 @@ bool depth_ok(const cb_depth *d, int h) {
   return (long long) d->slices * (long long) h <= 0x7fffffffLL;
 }
 
-// The depth draw (draw_depth.hip): what cb_draw_buddhabrot_depth and a renderer with a depth do once their own arguments
-// have passed.
+// The depth draws (draw_depth.hip, and with a table draw_depth_palette.hip): what cb_draw_buddhabrot_depth,
+// cb_draw_buddhabrot_depth_palette and a renderer with a depth or a depth palette do once their own arguments have passed.
+// d_lut null: N planes, no table; else the table of n_entries entries on the device and three planes.
 int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-               const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
-               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream,
-               int *interior_level) {
+               const double projection[8], const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut,
+               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+               int kernel_variant, void *stream, int *interior_level) {
   if (interior_level) *interior_level = 0;
   cb::DepthArgs da;
   memset(&da, 0, sizeof(da));
@@ -978,8 +985,15 @@ int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_ite
   da.pow2 = exact_reciprocal(da.delta, &da.inv_delta) ? 1 : 0;
   da.slices = depth->slices;
   da.plane_pixels = da.p.plane_pixels;
-  g_last_draw_kernel.store(lockstep ? 19 : 18, std::memory_order_relaxed);
-  const int rc = (int) cb::launch_draw_depth(da, lockstep, reinterpret_cast<hipStream_t>(stream));
+  int rc;
+  if (d_lut) {
+    const cb::DepthPaletteArgs dpa = {da, d_lut, da.plane_pixels};
+    g_last_draw_kernel.store(lockstep ? 21 : 20, std::memory_order_relaxed);
+    rc = (int) cb::launch_draw_depth_palette(dpa, n_entries, lockstep, reinterpret_cast<hipStream_t>(stream));
+  } else {
+    g_last_draw_kernel.store(lockstep ? 19 : 18, std::memory_order_relaxed);
+    rc = (int) cb::launch_draw_depth(da, lockstep, reinterpret_cast<hipStream_t>(stream));
+  }
   if (interior_level && !rc && da.p.d.interior_map) *interior_level = (int) da.p.d.interior_shift + 1;
   return rc;
 }
@@ -1086,8 +1100,8 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
 }
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
-  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || !lut_host ||
-      !palette_entries_ok(n_entries, &r->iterations)) {
+  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || r->depth_palette ||
+      !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
     return (int) hipErrorInvalidValue;
   }
   for (uint32_t k = 0; k < n_entries; ++k) {
@@ -1135,13 +1149,13 @@ int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
   if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
   if (!depth_ok(depth, dims->h)) return (int) hipErrorInvalidValue;
-  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, d_states, n_threads, samples_per_thread,
-                    d_counters, kernel_variant, stream, nullptr);
+  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, nullptr, 0u, d_states, n_threads,
+                    samples_per_thread, d_counters, kernel_variant, stream, nullptr);
 }
 
 int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
   // a projected or Julia renderer (a palette renderer is projected too, a channel or focused one never is)
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || !depth_ok(depth, r->dims.h)) {
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || !depth_ok(depth, r->dims.h)) {
     return (int) hipErrorInvalidValue;
   }
   CB_TRY(hipSetDevice(r->device));
@@ -1166,6 +1180,59 @@ int cb_renderer_depth(const cb_renderer *r, cb_depth *out) {
   if (!r || !r->has_depth) return 0;
   if (out) *out = r->depth;
   return r->depth.slices;
+}
+
+// ---- depth-palette render (draw_depth_palette.hip; include/cudabrot_amd.h, "Depth-palette render") -------------------
+
+int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                                     const cb_iteration_control *iterations, const double projection[8],
+                                     const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut, uint32_t n_entries,
+                                     void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                                     int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  if (!depth_ok(depth, dims->h) || !d_lut || n_entries != (uint32_t) depth->slices) return (int) hipErrorInvalidValue;
+  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, d_lut, n_entries, d_states, n_threads,
+                    samples_per_thread, d_counters, kernel_variant, stream, nullptr);
+}
+
+int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const uint32_t *lut_host, uint32_t n_entries) {
+  // where cb_renderer_set_depth is refused, and for a renderer that has a depth
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || !depth_ok(depth, r->dims.h) ||
+      !lut_host || n_entries != (uint32_t) depth->slices) {
+    return (int) hipErrorInvalidValue;
+  }
+  for (uint32_t k = 0; k < n_entries; ++k) {
+    if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;  // as cb_renderer_set_palette
+  }
+  CB_TRY(hipSetDevice(r->device));
+  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
+  const size_t hist_bytes = 3 * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
+  cb_pixel *d_hist = nullptr;
+  uint32_t *d_lut = nullptr;
+  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_lut), (size_t) n_entries * sizeof(uint32_t));
+  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
+  if (!rc) rc = (int) hipMemcpyAsync(d_lut, lut_host, (size_t) n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);  // lut_host is the caller's
+  if (rc) {
+    (void) hipFree(d_hist);
+    (void) hipFree(d_lut);
+    return rc;
+  }
+  (void) hipFree(r->d_hist);
+  r->d_hist = d_hist;
+  r->d_depth_lut = d_lut;
+  r->depth = *depth;
+  r->depth_palette = true;
+  return 0;
+}
+
+int cb_renderer_depth_palette(const cb_renderer *r, cb_depth *out, uint32_t *n_entries) {
+  if (!r || !r->depth_palette) return 0;
+  if (out) *out = r->depth;
+  if (n_entries) *n_entries = (uint32_t) r->depth.slices;
+  return 1;
 }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
@@ -1358,9 +1425,13 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
   return rc;
 }
 
-int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
-                              double *scale_out) {
-  if (!r || !r->palette || !host_rgb_be || r->dims.h > 0x7fffffff / 3) return (int) hipErrorInvalidValue;
+namespace {
+
+// The image of three planes R, G, B ("Palette render", Image): what cb_renderer_palette_image and
+// cb_renderer_depth_palette_image do once the renderer has passed as theirs.
+int three_plane_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                      double *scale_out) {
+  if (!host_rgb_be || r->dims.h > 0x7fffffff / 3) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   {
     int rc = finish(r);
@@ -1384,6 +1455,20 @@ int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint1
   (void) hipFree(d_planes);
   (void) hipFree(d_rgb);
   return rc;
+}
+
+}  // namespace
+
+int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                              double *scale_out) {
+  if (!r || !r->palette) return (int) hipErrorInvalidValue;
+  return three_plane_image(r, gamma, tone_mode, host_rgb_be, max_out, scale_out);
+}
+
+int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                                    double *scale_out) {
+  if (!r || !r->depth_palette) return (int) hipErrorInvalidValue;
+  return three_plane_image(r, gamma, tone_mode, host_rgb_be, max_out, scale_out);
 }
 
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
@@ -1493,6 +1578,7 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_carry);
   (void) hipFree(r->d_focus_cells);
   (void) hipFree(r->d_palette);
+  (void) hipFree(r->d_depth_lut);
   (void) hipFree(r->d_workspace[0]);
   (void) hipFree(r->d_workspace[1]);
   for (int k = 0; k < 2; ++k) {
@@ -1514,6 +1600,7 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
     cb_renderer *r = renderers[k];
     if (!r || r->dims.w != renderers[0]->dims.w || r->dims.h != renderers[0]->dims.h ||
         r->n_channels != renderers[0]->n_channels || r->palette != renderers[0]->palette ||
+        r->depth_palette != renderers[0]->depth_palette ||
         renderer_planes(r) != renderer_planes(renderers[0])) {
       return (int) hipErrorInvalidValue;
     }

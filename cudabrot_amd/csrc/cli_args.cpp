@@ -394,6 +394,14 @@ const std::vector<Flag> &flag_table() {
                     : "Invalid depth (want ROW:MIN:MAX[:N], ROW an axis zr, zi, cr, ci or four numbers, MIN < MAX, N from 1 "
                       "to " CB_TEXT_OF(CB_DEPTH_MAX_SLICES) ")";
        }},
+      // --depth-palette K:RRGGBB[,K:RRGGBB...]: the points of a --depth render coloured by their slice: --palette's
+      // syntax with K a slice index, the stops interpolated into a table of N entries, three planes of integer weights
+      // whatever N is, -o receives one 16-bit PPM (include/cudabrot_amd.h, "Depth-palette render")
+      {"--depth-palette", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.n_depth_palette_stops = parse_palette(t, s.depth_palette_stops);
+         return s.depth_palette() ? kOk : "Invalid depth palette (want K:RRGGBB,... K ascending, at most 16 stops)";
+       }},
       // --seed N: the generator's seed, 64 bits wide (rocrand_init)
       {"--seed", Value::kLong, nullptr, false,
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; return kOk; }},
@@ -522,6 +530,10 @@ const std::vector<Refusal> &refusal_table() {
       // a depth render is a projected render with N planes (include/cudabrot_amd.h, "Depth render"); behind every other
       // row: where a flag that turns the projected path on is given as well, that flag's row has spoken already
       {[](const Settings &s) { return s.depth_given; }, "--depth", {kPalette, kAnti, kFocus, kChannel, kGpus, kRaw}, nullptr},
+      // a depth-palette render is a depth render with a table (include/cudabrot_amd.h, "Depth-palette render"): whatever
+      // --depth refuses, its row above has refused
+      {[](const Settings &s) { return s.depth_palette() && !s.depth_given; }, nullptr, {},
+       [](const Settings &) { printf("--depth-palette needs --depth.\n"); }},
   };
   return table;
 }

@@ -69,6 +69,12 @@ struct Settings {
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
   bool plotted() const { return projected() || depth_given; }
+  // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
+  // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
+  // three
+  int n_depth_palette_stops = 0;
+  cb_palette_stop depth_palette_stops[CB_PALETTE_MAX_STOPS] = {};
+  bool depth_palette() const { return n_depth_palette_stops > 0; }
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

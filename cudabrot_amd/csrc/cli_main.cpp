@@ -77,6 +77,14 @@ class Run {
         fprintf(stderr, "{\"depth\": {\"row\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"min\": \"%a\", \"max\": \"%a\", \"slices\": %d}}\n",
                 d.row[0], d.row[1], d.row[2], d.row[3], d.min, d.max, d.slices);
       }
+      if (cfg_.depth_palette()) {  // and the colours of its slices
+        fprintf(stderr, "{\"depth_palette\": [");
+        for (int j = 0; j < cfg_.n_depth_palette_stops; ++j) {
+          const cb_palette_stop &stop = cfg_.depth_palette_stops[j];
+          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
+        }
+        fprintf(stderr, "]}\n");
+      }
       if (cfg_.palette()) {  // and the colours
         fprintf(stderr, "{\"palette\": [");
         for (int j = 0; j < cfg_.n_palette_stops; ++j) {
@@ -96,7 +104,7 @@ class Run {
     if (cfg_.n_channels > 0) {
       save_channels();
       if (cfg_.color_file) save_color();
-    } else if (cfg_.palette()) {
+    } else if (cfg_.palette() || cfg_.depth_palette()) {
       printf("Saving image.\n");
       report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
       printf("Done! Output image saved: %s\n", cfg_.output_image);
@@ -123,13 +131,14 @@ class Run {
   uint16_t *gray_ = nullptr;
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
-  std::vector<uint16_t> palette_rgb_be_;  // --palette: the PPM body
+  std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette: the PPM body
   std::vector<uint16_t> depth_gray_be_;   // --depth: the bodies of the N PGMs, slice 0 first
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
   uint64_t pixel_count() const { return (uint64_t) cfg_.canvas.w * (uint64_t) cfg_.canvas.h; }
   uint64_t planes() const {
+    if (cfg_.depth_palette()) return 3u;
     if (cfg_.depth_given) return (uint64_t) cfg_.depth.slices;
     return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u);
   }
@@ -190,7 +199,13 @@ class Run {
     } else if (cfg_.plotted()) {
       CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
     }
-    if (cfg_.depth_given) CB_CHECK(cb_renderer_set_depth(renderer_, &cfg_.depth));  // after the plane and c
+    if (cfg_.depth_palette()) {  // after the plane and c: the table of the stops, one entry per slice
+      std::vector<uint32_t> lut((size_t) cfg_.depth.slices);
+      CB_CHECK(cb_palette_from_stops(cfg_.depth_palette_stops, cfg_.n_depth_palette_stops, lut.data(), (uint32_t) lut.size()));
+      CB_CHECK(cb_renderer_set_depth_palette(renderer_, &cfg_.depth, lut.data(), (uint32_t) lut.size()));
+    } else if (cfg_.depth_given) {
+      CB_CHECK(cb_renderer_set_depth(renderer_, &cfg_.depth));  // after the plane and c
+    }
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -324,7 +339,7 @@ class Run {
     }
     printf("%ld Buddhabrot passes took %f seconds.\n", done, wall_seconds() - t0);
     if (cfg_.print_stats) print_stats();
-    if (cfg_.palette()) {
+    if (cfg_.palette() || cfg_.depth_palette()) {
       palette_image();
     } else if (cfg_.depth_given) {
       depth_image();
@@ -479,7 +494,7 @@ class Run {
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }
 
-  // --palette: the three planes tone-mapped against their common maximum, as one w x 3h image, and interleaved into the
+  // --palette, --depth-palette: the three planes tone-mapped against their common maximum, as one w x 3h image, and interleaved into the
   // PPM body -- on the device, or with --tonemap host by the reference's host loop; the bytes are the same.
   void palette_image() {
     uint64_t max = 0;
@@ -495,8 +510,8 @@ class Run {
         }
       }
     } else {
-      CB_CHECK(cb_renderer_palette_image(renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max,
-                                         &scale));
+      CB_CHECK((cfg_.depth_palette() ? cb_renderer_depth_palette_image : cb_renderer_palette_image)(
+          renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max, &scale));
     }
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }

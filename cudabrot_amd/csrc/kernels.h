@@ -288,6 +288,23 @@ struct DepthArgs {
 };
 hipError_t launch_draw_depth(const DepthArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_depth_palette.hip: the depth-palette render ("Depth-palette render" of include/cudabrot_amd.h) -- a depth launch
+// whose slice looks a colour up: a point on the canvas and in depth adds the three weights of lut[s] to its pixel of three
+// planes.
+//   d        the depth launch it extends, d.p.palette 0 and d.p.lut null as there (the table is not the palette render's:
+//            it is indexed by the slice).  d.p.d.hist is three planes.
+//   lut      the table on the device, d.slices entries in the palette's entry format.
+//   plane_pixels   w * h: the distance between the three planes.
+// n_entries: the table's length, which the kernels never see.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_depth refuses of d (but the table), a null table, n_entries
+// != d.slices, a plane_pixels that is not w * h.  lockstep: the definition, one lane per reference thread.
+struct DepthPaletteArgs {
+  DepthArgs d;  // first: the kernels read it through draw_depth.h's fresh_depth_args
+  const uint32_t *lut;
+  unsigned long long plane_pixels;
+};
+hipError_t launch_draw_depth_palette(const DepthPaletteArgs &a, uint32_t n_entries, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

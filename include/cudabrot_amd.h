@@ -598,6 +598,51 @@ int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                              void *stream);
 
+/* ---- Depth-palette render: orbit points coloured by their depth, into three planes --- *
+ *
+ * The N planes of a depth render are a volume, not a picture, and their memory grows with N.  A DEPTH-PALETTE render
+ * decides the colour where the point is plotted: the slice of a visited point indexes a table of N colours, and the point
+ * adds that colour's three integer weights to three planes -- the palette render's mechanism keyed by depth instead of
+ * escape index.  The histogram is three planes whatever N is, and the image is one PPM: the depth-cued colour render the
+ * "3-D Buddhabrot" is known for.  It is a depth render ("Depth render" above) with a table, and that section applies
+ * unchanged but for its Histogram, Counters, No table and Image.  The project's own definition.  Normative:
+ *
+ *   Inputs.  The cb_depth of "Depth render" (row D, window [min, max), N from 1 to CB_DEPTH_MAX_SLICES) and a table lut of
+ *   n_entries == N uint32_t entries in the palette's entry format ("Palette render", Table): R = bits 0-7, G = bits 8-15,
+ *   B = bits 16-23; bits 24-31 are not read by the kernels.  Entry s carries the weights of a point in slice s.
+ *
+ *   Unchanged from "Depth render".  The sample stream, rejection, the interior map under cb_draw_buddhabrot_projected's
+ *   rule, the iteration, the accept filter, the replayed points, u, v, d, K_d, delta_d, the slice s and its bounds test.
+ *
+ *   Histogram.  Three planes of w*h cb_pixel, plane 0 = R, 1 = G, 2 = B, contiguous.  A visited point that is on the
+ *   canvas and in depth adds weight_j(lut[s]) to its pixel of plane j, for every j with weight_j != 0.  Every other point
+ *   adds nothing.
+ *
+ *   Counters.  increments is the sum of the weights added.  Every other counter is what the depth render counts: the
+ *   lock-step kernel leaves skipped_steps 0, the product kernel's is its usual executed-work discount (the entry is known
+ *   per point, not per orbit: no orbit is left unreplayed for its colour).
+ *
+ *   Stops -> table.  cb_palette_from_stops(stops, n, lut, N), unchanged, with k read as a slice index.
+ *
+ *   Image.  As "Palette render", Image: the three planes tone-mapped against their common maximum, a P6 PPM.
+ *
+ *   Consequences.  With V the planes of cb_draw_buddhabrot_depth under the same arguments: plane j equals the sum over s
+ *   of weight_j(lut[s]) * V[s], bit for bit; a table that is 1 in plane 0 at one slice and 0 elsewhere gives that slice;
+ *   the constant table 0x010101 with N = 1 gives the section three times.
+ *
+ * Two kernels (draw_depth_palette.hip), with the variants, the refusals and the agreement of the depth render's two.  The
+ * product kernel keeps the table, at most 1 KiB, in LDS.  A palette render with a depth ("Palette render" by escape index
+ * AND N slices, 3 N planes) stays refused.  The -s buffer has three planes and records the table, the row and the window
+ * no more than it records the plane, the degree or c. */
+/* The depth-palette draw on caller-owned device memory: d_hist is THREE planes of w*h cb_pixel, d_lut the table on the
+ * device.  hipErrorInvalidValue, with nothing launched or written: a NULL table, n_entries != depth->slices, and
+ * everything cb_draw_buddhabrot_depth refuses. */
+int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
+                                     const cb_iteration_control *iterations, const double projection[8],
+                                     const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut, uint32_t n_entries,
+                                     void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                                     int kernel_variant, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -679,6 +724,19 @@ int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth);
 /* A renderer's depth: returns N and fills *out (may be NULL); returns 0 and leaves it alone for a renderer without one
  * (or a NULL renderer). */
 int cb_renderer_depth(const cb_renderer *r, cb_depth *out);
+/* Gives this renderer a DEPTH PALETTE ("Depth-palette render" above); on a projected or Julia renderer, before its first
+ * pass, once.  lut_host is the table in HOST memory, n_entries == depth->slices entries; it is copied to the device, and
+ * the histogram is reallocated and zeroed as three planes.  Every later cb_renderer_render_passes launches depth-palette
+ * draws with the variants of the renderer it was; render_passes, finish, read / write_histogram (three planes),
+ * read_counters, the generator states and cb_renderer_grayscale_plane (planes 0 .. 2) work on the three planes.
+ * hipErrorInvalidValue wherever cb_renderer_set_depth is refused, for a renderer that has a depth or a depth palette, a
+ * NULL table, a table with any bit 24-31 set, n_entries != depth->slices.  Afterwards cb_renderer_set_depth,
+ * cb_renderer_set_palette, cb_renderer_set_projection, cb_renderer_set_julia and cb_renderer_set_focus are refused; the
+ * renderer is neither a palette renderer nor one with a depth (cb_renderer_palette and cb_renderer_depth return 0). */
+int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const uint32_t *lut_host, uint32_t n_entries);
+/* A renderer's depth palette: returns 1, fills *out and sets *n_entries (either may be NULL); returns 0 and leaves them
+ * alone for any other renderer (or a NULL renderer). */
+int cb_renderer_depth_palette(const cb_renderer *r, cb_depth *out, uint32_t *n_entries);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -759,6 +817,11 @@ int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint1
  * hipErrorInvalidValue for a renderer without a depth. */
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                             double *scale_out);
+
+/* The image of a renderer with a depth palette ("Depth-palette render", Image): cb_renderer_palette_image's arithmetic
+ * and arguments on its three planes.  hipErrorInvalidValue for a renderer without a depth palette. */
+int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                                    double *scale_out);
 
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
@@ -854,7 +917,9 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * (draw_plot_kernel: cb_draw_buddhabrot_julia), 13 the Julia lock-step kernel, 14 the palette product kernel
  * (draw_plot_kernel: cb_draw_buddhabrot_palette), 15 the palette lock-step kernel, 16 the formula product kernel
  * (draw_plot_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel, 18 the depth
- * product kernel (draw_depth_kernel: cb_draw_buddhabrot_depth, whatever its step), 19 the depth lock-step kernel.
+ * product kernel (draw_depth_kernel: cb_draw_buddhabrot_depth, whatever its step), 19 the depth lock-step kernel, 20 the
+ * depth-palette product kernel (draw_depth_palette_kernel: cb_draw_buddhabrot_depth_palette, whatever its step), 21 the
+ * depth-palette lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

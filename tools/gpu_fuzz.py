@@ -24,6 +24,11 @@ and demands identical histograms and counters.
                                                    c, canvas, window, matrix, depth row, depth window, N, thread count
                                                    and launches, generator states compared as well; TRIALS=N ends the
                                                    run after N trials where that comes before SECONDS
+    DEPTHPALETTE=1 python tools/gpu_fuzz.py ...    the depth-palette render (cb_draw_buddhabrot_depth_palette):
+                                                   draw_depth_palette_kernel against draw_depth_palette_simple_kernel
+                                                   (draw_depth_palette.hip) -- DEPTH's trials with a random table of N
+                                                   entries (random weights with zeros among them, one colour, one-hot,
+                                                   noise in the bits that are not read), three planes; TRIALS as there
 """
 import os
 
@@ -369,8 +374,29 @@ def depth_trial(rng):
     return t
 
 
+def depth_palette_trial(rng):
+    """A depth trial with a table of N entries in t["lut"]."""
+    t = depth_trial(rng)
+    n = t["slices"]
+    kind = rng.random()
+    if kind < 0.5:      # any weights, a third of the components zero
+        lut = [sum((0 if rng.random() < 0.33 else rng.randint(1, 255)) << (8 * j) for j in range(3)) for _ in range(n)]
+    elif kind < 0.65:   # one colour for every slice
+        lut = [rng.choice([0x010101, 0x0000ff, 0xff00ff, 0x020100])] * n
+    elif kind < 0.85:   # one slice lit
+        lut = [0] * n
+        lut[rng.randrange(n)] = rng.choice([1, 0x000100, 0x030201])
+    else:               # small weights that differ from slice to slice
+        lut = [(s % 3 + 1) | ((s * 7) % 5) << 8 | ((s >> 1) % 4) << 16 for s in range(n)]
+    if rng.random() < 0.3:  # bits 24-31 are not read
+        lut = [v | rng.randrange(256) << 24 for v in lut]
+    t["lut"] = lut
+    return t
+
+
 def render_depth(t, variant):
-    """The launches of a depth trial -> (histogram, counters, generator states)."""
+    """The launches of a depth trial, or with t["lut"] of a depth-palette trial -> (histogram, counters, generator
+    states)."""
     dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
     it = cb.IterationControl(t["max_iter"], t["min_iter"])
@@ -379,39 +405,49 @@ def render_depth(t, variant):
     flags = ((cb.CB_KERNEL_POWER(t["degree"]) if t["degree"] != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
              | (cb.CB_KERNEL_FORMULA(t["formula"]) if t["formula"] else 0))
     states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(t["slices"] * t["w"] * t["h"], dtype=torch.int64, device=dev)
+    lut = t.get("lut")
+    hist = torch.zeros((3 if lut else t["slices"]) * t["w"] * t["h"], dtype=torch.int64, device=dev)
     counters = torch.zeros(17, dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
     cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
+    if lut:
+        d_lut = torch.from_numpy(np.array(lut, dtype=np.uint32).view(np.int32)).to(dev)
     for s in t["launch_samples"]:
-        cb.draw_buddhabrot_depth(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, states.data_ptr(), n, s,
-                                 counters.data_ptr(), variant | flags, stream)
+        if lut:
+            cb.draw_buddhabrot_depth_palette(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, d_lut.data_ptr(),
+                                             len(lut), states.data_ptr(), n, s, counters.data_ptr(), variant | flags, stream)
+        else:
+            cb.draw_buddhabrot_depth(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, states.data_ptr(), n, s,
+                                     counters.data_ptr(), variant | flags, stream)
     torch.cuda.synchronize()
     c = counters.cpu().numpy().view(np.uint64)
     cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
     return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
 
 
-def depth_main(seconds, seed):
+def depth_main(seconds, seed, palette=False):
+    """DEPTH's run, or with palette DEPTHPALETTE's: the same comparison on the other pair of kernels."""
+    name = "depth-palette" if palette else "depth"
+    lockstep_kernel, product_kernel = (21, 20) if palette else (19, 18)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     trials = int(os.environ.get("TRIALS", "0"))
     n = early = filled = 0
     last_print = time.time()
     while time.time() < t_end and not (trials and n >= trials):
-        t = depth_trial(rng)
+        t = depth_palette_trial(rng) if palette else depth_trial(rng)
         try:
             want, wc, want_states = render_depth(t, cb.CB_KERNEL_SIMPLE)
-            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 19
+            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == lockstep_kernel
             got, gc, got_states = render_depth(t, cb.CB_KERNEL_DEFAULT)
-            product_ran = cb.lib.cb_debug_last_draw_kernel() == 18
+            product_ran = cb.lib.cb_debug_last_draw_kernel() == product_kernel
         except cb.CudabrotError as e:
             print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
             return 1
         bad = [k for k in COMPARED if wc[k] != gc[k]]
         if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
                 lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or int(want.sum()) != wc["increments"]:
-            print("MISMATCH at depth trial %d (seed %d): %r" % (n, seed, t))
+            print("MISMATCH at %s trial %d (seed %d): %r" % (name, n, seed, t))
             print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
             print("  counters that differ: %r; lock-step skipped_steps %d" % ([(k, wc[k], gc[k]) for k in bad],
                                                                             wc["skipped_steps"]))
@@ -423,10 +459,10 @@ def depth_main(seconds, seed):
         early += 1 if gc["skipped_steps"] > 0 else 0
         filled += 1 if wc["increments"] > 0 else 0
         if time.time() - last_print > 30:
-            print("%d depth trials identical so far (%d with skipped_steps > 0)" % (n, early), flush=True)
+            print("%d %s trials identical so far (%d with skipped_steps > 0)" % (n, name, early), flush=True)
             last_print = time.time()
-    print("gpu_fuzz: %d depth trials (%d with skipped_steps > 0, %d with increments > 0), histograms, counters and "
-          "generator states identical (seed %d)" % (n, early, filled, seed))
+    print("gpu_fuzz: %d %s trials (%d with skipped_steps > 0, %d with increments > 0), histograms, counters and "
+          "generator states identical (seed %d)" % (n, name, early, filled, seed))
     return 0
 
 
@@ -505,6 +541,8 @@ def main():
         return power_main(seconds, seed)
     if os.environ.get("DEPTH") == "1":
         return depth_main(seconds, seed)
+    if os.environ.get("DEPTHPALETTE") == "1":
+        return depth_main(seconds, seed, palette=True)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     n = 0
