@@ -433,6 +433,52 @@ int finish(cb_renderer *r) {
   return status ? CB_ERROR_KERNEL_INVARIANT : 0;
 }
 
+// A cleared histogram of `planes` planes in the place of the renderer's first one and, with a table (lut_host not null), a
+// device copy of its n_entries in *d_lut: what the setters of a palette, a depth and a depth palette do once the renderer
+// has passed as theirs.  On failure nothing is kept and the renderer is as it was.
+int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint32_t n_entries, uint32_t **d_lut) {
+  CB_TRY(hipSetDevice(r->device));
+  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
+  const size_t hist_bytes = planes * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
+  const size_t lut_bytes = (size_t) n_entries * sizeof(uint32_t);
+  cb_pixel *d_hist = nullptr;
+  uint32_t *d_table = nullptr;
+  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
+  if (!rc && lut_host) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_table), lut_bytes);
+  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
+  if (!rc && lut_host) rc = (int) hipMemcpyAsync(d_table, lut_host, lut_bytes, hipMemcpyHostToDevice, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);  // lut_host is the caller's
+  if (rc) {
+    (void) hipFree(d_hist);
+    (void) hipFree(d_table);
+    return rc;
+  }
+  (void) hipFree(r->d_hist);
+  r->d_hist = d_hist;
+  if (lut_host) *d_lut = d_table;
+  return 0;
+}
+
+// `rows` rows of the histogram from `plane` on as one w x rows image, one maximum for all of it: finish, tone-map, copy
+// out.  What cb_renderer_grayscale_plane (one plane) and cb_renderer_depth_image (all of them) do after their checks.
+int gray_image(cb_renderer *r, size_t plane, int rows, double gamma, int mode, uint16_t *host_gray_be, uint64_t *max_out,
+               double *scale_out) {
+  CB_TRY(hipSetDevice(r->device));
+  {
+    int rc = finish(r);
+    if (rc) return rc;
+  }
+  const size_t bytes = (size_t) rows * (size_t) r->dims.w * sizeof(uint16_t);
+  uint16_t *d_gray = nullptr;
+  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
+  int rc = cb_tone_map_device(r->d_hist + plane * (size_t) r->dims.w * (size_t) r->dims.h, r->dims.w, rows, gamma, mode,
+                              d_gray, max_out, scale_out, r->stream);
+  if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
+  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
+  (void) hipFree(d_gray);
+  return rc;
+}
+
 __global__ void __launch_bounds__(256) add_histogram_kernel(unsigned long long *dst,
                                                             const unsigned long long *src, size_t n) {
   const size_t stride = (size_t) gridDim.x * blockDim.x;
@@ -1107,24 +1153,8 @@ int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n
   for (uint32_t k = 0; k < n_entries; ++k) {
     if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;
   }
-  CB_TRY(hipSetDevice(r->device));
-  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
-  const size_t hist_bytes = 3 * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
-  cb_pixel *d_hist = nullptr;
-  uint32_t *d_lut = nullptr;
-  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_lut), (size_t) n_entries * sizeof(uint32_t));
-  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
-  if (!rc) rc = (int) hipMemcpyAsync(d_lut, lut_host, (size_t) n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream);
-  if (!rc) rc = (int) hipStreamSynchronize(r->stream);  // lut_host is the caller's
-  if (rc) {
-    (void) hipFree(d_hist);
-    (void) hipFree(d_lut);
-    return rc;
-  }
-  (void) hipFree(r->d_hist);
-  r->d_hist = d_hist;
-  r->d_palette = d_lut;
+  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->d_palette);
+  if (rc) return rc;
   r->palette_entries = n_entries;
   r->palette = true;
   if (!r->projected) {  // alone: the identity projection
@@ -1158,19 +1188,8 @@ int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
   if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || !depth_ok(depth, r->dims.h)) {
     return (int) hipErrorInvalidValue;
   }
-  CB_TRY(hipSetDevice(r->device));
-  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
-  const size_t hist_bytes = (size_t) depth->slices * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
-  cb_pixel *d_hist = nullptr;
-  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
-  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
-  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
-  if (rc) {
-    (void) hipFree(d_hist);
-    return rc;
-  }
-  (void) hipFree(r->d_hist);
-  r->d_hist = d_hist;
+  const int rc = swap_in_planes(r, (size_t) depth->slices, nullptr, 0u, nullptr);
+  if (rc) return rc;
   r->depth = *depth;
   r->has_depth = true;
   return 0;
@@ -1205,24 +1224,8 @@ int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const u
   for (uint32_t k = 0; k < n_entries; ++k) {
     if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;  // as cb_renderer_set_palette
   }
-  CB_TRY(hipSetDevice(r->device));
-  CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
-  const size_t hist_bytes = 3 * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
-  cb_pixel *d_hist = nullptr;
-  uint32_t *d_lut = nullptr;
-  int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_hist), hist_bytes);
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_lut), (size_t) n_entries * sizeof(uint32_t));
-  if (!rc) rc = (int) hipMemsetAsync(d_hist, 0, hist_bytes, r->stream);
-  if (!rc) rc = (int) hipMemcpyAsync(d_lut, lut_host, (size_t) n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream);
-  if (!rc) rc = (int) hipStreamSynchronize(r->stream);  // lut_host is the caller's
-  if (rc) {
-    (void) hipFree(d_hist);
-    (void) hipFree(d_lut);
-    return rc;
-  }
-  (void) hipFree(r->d_hist);
-  r->d_hist = d_hist;
-  r->d_depth_lut = d_lut;
+  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->d_depth_lut);
+  if (rc) return rc;
   r->depth = *depth;
   r->depth_palette = true;
   return 0;
@@ -1409,20 +1412,7 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
   if (!r || !host_gray_be || plane < 0 || (size_t) plane >= renderer_planes(r)) {
     return (int) hipErrorInvalidValue;
   }
-  CB_TRY(hipSetDevice(r->device));
-  {
-    int rc = finish(r);
-    if (rc) return rc;
-  }
-  const size_t bytes = (size_t) r->dims.w * (size_t) r->dims.h * sizeof(uint16_t);
-  uint16_t *d_gray = nullptr;
-  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
-  int rc = cb_tone_map_device(r->d_hist + (size_t) plane * (size_t) r->dims.w * (size_t) r->dims.h, r->dims.w,
-                              r->dims.h, gamma, mode, d_gray, max_out, scale_out, r->stream);
-  if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
-  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
-  (void) hipFree(d_gray);
-  return rc;
+  return gray_image(r, (size_t) plane, r->dims.h, gamma, mode, host_gray_be, max_out, scale_out);
 }
 
 namespace {
@@ -1474,22 +1464,8 @@ int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode,
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                             double *scale_out) {
   if (!r || !r->has_depth || !host_gray_be) return (int) hipErrorInvalidValue;
-  CB_TRY(hipSetDevice(r->device));
-  {
-    int rc = finish(r);
-    if (rc) return rc;
-  }
-  const int slices = r->depth.slices;  // slices * h fits an int: cb_renderer_set_depth
-  const size_t bytes = (size_t) slices * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(uint16_t);
-  uint16_t *d_gray = nullptr;
-  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
-  // the planes as one w x N*h image: one maximum for all of them
-  int rc = cb_tone_map_device(r->d_hist, r->dims.w, slices * r->dims.h, gamma, tone_mode, d_gray, max_out, scale_out,
-                              r->stream);
-  if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
-  if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
-  (void) hipFree(d_gray);
-  return rc;
+  // the planes as one w x N*h image: one maximum for all of them (N * h fits an int: cb_renderer_set_depth)
+  return gray_image(r, 0, r->depth.slices * r->dims.h, gamma, tone_mode, host_gray_be, max_out, scale_out);
 }
 
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,

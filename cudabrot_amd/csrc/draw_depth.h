@@ -1,7 +1,6 @@
 // draw_depth.h -- what the kernels that bin along a third row share (draw_depth.hip, draw_depth_palette.hip;
 // include/cudabrot_amd.h, "Depth render"): the lock-step kernels' step, the arguments read afresh, the slice of a depth, the
-// launcher's checks, the order of the product instances, and DepthMode, the mode of draw_rounds.h's scheduler that both
-// product kernels run.
+// launcher's checks, and DepthMode, the mode of draw_rounds.h's scheduler that both product kernels run.
 #pragma once
 
 #include "draw_plot.h"
@@ -41,33 +40,14 @@ __device__ __forceinline__ bool slice_of(double d, double min, double delta, dou
   return (s >= 0) && (s < slices);
 }
 
-// What both launchers refuse of a DepthArgs, the table apart: whatever launch_draw_plot refuses of p, slices out of range,
-// a delta that is not positive, a plane_pixels that is not w * h.
+// What both launchers refuse of a DepthArgs, the table apart: whatever launch_draw_plot refuses of p (draw_plot.h,
+// plot_launch_ok), slices out of range, a delta that is not positive, a plane_pixels that is not w * h.
 inline bool depth_launch_ok(const DepthArgs &da) {
   const PlotArgs &a = da.p;
-  const bool power = a.degree != 2;
-  const bool ship = a.d.burning_ship != 0;
-  if (power && (a.degree < CB_POWER_MIN || a.degree > CB_POWER_MAX)) return false;
-  if (a.formula < 0 || a.formula > CB_FORMULA_MAX) return false;
-  if (a.formula != 0 && (power || ship)) return false;  // a formula is a step of its own
-  if (power && ship) return false;                      // the Multibrot step has no Burning Ship variant
-  for (int j = 0; a.julia != 0 && j < 2; ++j) {
-    if (!(a.c[j] >= -2.0 && a.c[j] <= 2.0)) return false;  // a NaN fails both comparisons
-  }
   // every slice the kernel can compute is a plane of the histogram: 1 <= N, and the window and its step are what
   // slice_of divides by
-  return da.slices >= 1 && da.slices <= CB_DEPTH_MAX_SLICES && da.delta > 0.0 && a.d.w > 0 && a.d.h > 0 &&
-         da.plane_pixels == (unsigned long long) a.d.w * (unsigned long long) a.d.h;
-}
-
-// The product kernels of a family, by step, in draw_plot.hip's order: the reference's, its Burning Ship variant, degrees
-// CB_POWER_MIN .. CB_POWER_MAX, codes CB_FORMULA_TRICORN .. CB_FORMULA_MAX.
-constexpr int kFirstPowerStep = 2 - CB_POWER_MIN;
-constexpr int kFirstFormulaStep = kFirstPowerStep + CB_POWER_MAX + 1 - CB_FORMULA_TRICORN;
-constexpr int kDepthSteps = kFirstFormulaStep + CB_FORMULA_MAX + 1;
-inline int depth_step_index(const PlotArgs &a) {
-  return a.formula != 0 ? kFirstFormulaStep + a.formula
-                        : a.degree != 2 ? kFirstPowerStep + a.degree : (a.d.burning_ship != 0 ? 1 : 0);
+  return plot_launch_ok(a) && da.slices >= 1 && da.slices <= CB_DEPTH_MAX_SLICES && da.delta > 0.0 && a.d.w > 0 &&
+         a.d.h > 0 && da.plane_pixels == (unsigned long long) a.d.w * (unsigned long long) a.d.h;
 }
 
 // The round scheduler of draw_rounds.h with DepthMode: PlotMode (a sampled c) or JuliaMode (a fixed one) of draw_plot.h

@@ -123,25 +123,14 @@ namespace {
 
 typedef void (*DepthKernel)(DepthArgs);
 
-// The product kernels of one step: [fixed c].
+// The product kernels of one step, [fixed c], and every one there is, by step (draw_plot.h, plot_step_index).
 struct StepKernels {
   DepthKernel by[2];
 };
-template <class Step>
-constexpr StepKernels step_kernels() {
-  return {{draw_depth_kernel<Step, false>, draw_depth_kernel<Step, true>}};
-}
-
-// Every product kernel there is, by step (draw_depth.h, depth_step_index).
-constexpr StepKernels kDepthKernels[] = {
-    step_kernels<ReferenceOrbit<false>>(), step_kernels<ReferenceOrbit<true>>(),
-    step_kernels<PowerOrbit<3>>(), step_kernels<PowerOrbit<4>>(), step_kernels<PowerOrbit<5>>(),
-    step_kernels<PowerOrbit<6>>(), step_kernels<PowerOrbit<7>>(), step_kernels<PowerOrbit<8>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_TRICORN>>(), step_kernels<FormulaOrbit<CB_FORMULA_CELTIC>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_BUFFALO>>(), step_kernels<FormulaOrbit<CB_FORMULA_PERPENDICULAR>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_CELTIC_TRICORN>>(),
-};
-static_assert(sizeof(kDepthKernels) / sizeof(kDepthKernels[0]) == kDepthSteps, "one row per step");
+#define CB_ROW(Step) {{draw_depth_kernel<Step, false>, draw_depth_kernel<Step, true>}},
+constexpr StepKernels kDepthKernels[] = {CB_PLOT_STEPS(CB_ROW)};
+#undef CB_ROW
+static_assert(sizeof(kDepthKernels) / sizeof(kDepthKernels[0]) == kPlotSteps, "one row per step");
 
 }  // namespace
 
@@ -154,7 +143,7 @@ hipError_t launch_draw_depth(const DepthArgs &da, bool lockstep, hipStream_t str
   if (lockstep) {
     kernel = draw_depth_simple_kernel;
   } else {
-    kernel = kDepthKernels[depth_step_index(a)].by[a.julia != 0];
+    kernel = kDepthKernels[plot_step_index(a)].by[a.julia != 0];
   }
   hipLaunchKernelGGL(kernel, dim3((a.d.n_threads + 255u) / 256u), dim3(256), 0, stream, da);
   return hipGetLastError();

@@ -186,25 +186,15 @@ namespace {
 
 typedef void (*DepthPaletteKernel)(DepthPaletteArgs);
 
-// The product kernels of one step: [fixed c].
+// The product kernels of one step, [fixed c], and every one there is, by step (draw_plot.h, plot_step_index):
+// draw_depth.hip's instance set.
 struct StepKernels {
   DepthPaletteKernel by[2];
 };
-template <class Step>
-constexpr StepKernels step_kernels() {
-  return {{draw_depth_palette_kernel<Step, false>, draw_depth_palette_kernel<Step, true>}};
-}
-
-// Every product kernel there is, by step (draw_depth.h, depth_step_index): draw_depth.hip's instance set.
-constexpr StepKernels kDepthPaletteKernels[] = {
-    step_kernels<ReferenceOrbit<false>>(), step_kernels<ReferenceOrbit<true>>(),
-    step_kernels<PowerOrbit<3>>(), step_kernels<PowerOrbit<4>>(), step_kernels<PowerOrbit<5>>(),
-    step_kernels<PowerOrbit<6>>(), step_kernels<PowerOrbit<7>>(), step_kernels<PowerOrbit<8>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_TRICORN>>(), step_kernels<FormulaOrbit<CB_FORMULA_CELTIC>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_BUFFALO>>(), step_kernels<FormulaOrbit<CB_FORMULA_PERPENDICULAR>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_CELTIC_TRICORN>>(),
-};
-static_assert(sizeof(kDepthPaletteKernels) / sizeof(kDepthPaletteKernels[0]) == kDepthSteps, "one row per step");
+#define CB_ROW(Step) {{draw_depth_palette_kernel<Step, false>, draw_depth_palette_kernel<Step, true>}},
+constexpr StepKernels kDepthPaletteKernels[] = {CB_PLOT_STEPS(CB_ROW)};
+#undef CB_ROW
+static_assert(sizeof(kDepthPaletteKernels) / sizeof(kDepthPaletteKernels[0]) == kPlotSteps, "one row per step");
 
 }  // namespace
 
@@ -219,7 +209,7 @@ hipError_t launch_draw_depth_palette(const DepthPaletteArgs &dpa, uint32_t n_ent
   }
   if (a.d.n_threads == 0 || a.d.samples_per_thread == 0) return hipSuccess;
   const DepthPaletteKernel kernel =
-      lockstep ? draw_depth_palette_simple_kernel : kDepthPaletteKernels[depth_step_index(a)].by[a.julia != 0];
+      lockstep ? draw_depth_palette_simple_kernel : kDepthPaletteKernels[plot_step_index(a)].by[a.julia != 0];
   hipLaunchKernelGGL(kernel, dim3((a.d.n_threads + 255u) / 256u), dim3(256), 0, stream, dpa);
   return hipGetLastError();
 }

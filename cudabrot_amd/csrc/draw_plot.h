@@ -1,7 +1,8 @@
 // draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_plot.hip; include/cudabrot_amd.h,
 // "Projected render"): the four fused operations of a plotted point, the plot of a replayed point for the modes of
-// draw_rounds.h's scheduler, the steps those modes are instantiated with, and the modes themselves -- a sampled c, a fixed
-// one, and the palette render's mode, which builds on either.
+// draw_rounds.h's scheduler, the steps those modes are instantiated with, the modes themselves -- a sampled c, a fixed
+// one, and the palette render's mode, which builds on either --, and what the launchers of every family that plots share
+// (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip): the list of the steps, a step's index and the checks of one.
 #pragma once
 
 #include <type_traits>
@@ -195,6 +196,39 @@ struct PaletteMode {
   }
 };
 
+
+// ---- the steps, for the launchers ----------------------------------------------------------------------------------------
+
+// Every step there is, in the order of plot_step_index: the reference's, its Burning Ship variant, degrees CB_POWER_MIN ..
+// CB_POWER_MAX, codes CB_FORMULA_TRICORN .. CB_FORMULA_MAX.  A family's table of product kernels is CB_PLOT_STEPS(ROW),
+// ROW(Step) the family's kernels of one step.
+#define CB_PLOT_STEPS(ROW)                                                                                             \
+  ROW(ReferenceOrbit<false>) ROW(ReferenceOrbit<true>)                                                                 \
+  ROW(PowerOrbit<3>) ROW(PowerOrbit<4>) ROW(PowerOrbit<5>) ROW(PowerOrbit<6>) ROW(PowerOrbit<7>) ROW(PowerOrbit<8>)    \
+  ROW(FormulaOrbit<CB_FORMULA_TRICORN>) ROW(FormulaOrbit<CB_FORMULA_CELTIC>) ROW(FormulaOrbit<CB_FORMULA_BUFFALO>)     \
+  ROW(FormulaOrbit<CB_FORMULA_PERPENDICULAR>) ROW(FormulaOrbit<CB_FORMULA_CELTIC_TRICORN>)
+constexpr int kFirstPowerStep = 2 - CB_POWER_MIN;
+constexpr int kFirstFormulaStep = kFirstPowerStep + CB_POWER_MAX + 1 - CB_FORMULA_TRICORN;
+constexpr int kPlotSteps = kFirstFormulaStep + CB_FORMULA_MAX + 1;
+inline int plot_step_index(const PlotArgs &a) {
+  return a.formula != 0 ? kFirstFormulaStep + a.formula
+                        : a.degree != 2 ? kFirstPowerStep + a.degree : (a.d.burning_ship != 0 ? 1 : 0);
+}
+
+// What every launcher refuses of a PlotArgs, the tables apart: a step that is none of the list's, a fixed c outside
+// [-2, 2]^2.
+inline bool plot_launch_ok(const PlotArgs &a) {
+  const bool power = a.degree != 2;
+  const bool ship = a.d.burning_ship != 0;
+  if (power && (a.degree < CB_POWER_MIN || a.degree > CB_POWER_MAX)) return false;
+  if (a.formula < 0 || a.formula > CB_FORMULA_MAX) return false;
+  if (a.formula != 0 && (power || ship)) return false;  // a formula is a step of its own
+  if (power && ship) return false;                      // the Multibrot step has no Burning Ship variant
+  for (int j = 0; a.julia != 0 && j < 2; ++j) {
+    if (!(a.c[j] >= -2.0 && a.c[j] <= 2.0)) return false;  // a NaN fails both comparisons
+  }
+  return true;
+}
 
 }  // namespace
 

@@ -441,59 +441,37 @@ namespace {
 
 typedef void (*PlotKernel)(PlotArgs);
 
-// The product kernels of one step: [fixed c][table].
+// The product kernels of one step, [fixed c][table], and every one there is, by step (draw_plot.h, plot_step_index).
 struct StepKernels {
   PlotKernel by[2][2];
 };
-template <class Step>
-constexpr StepKernels step_kernels() {
-  return {{{draw_plot_kernel<Step, false, false>, draw_plot_kernel<Step, false, true>},
-           {draw_plot_kernel<Step, true, false>, draw_plot_kernel<Step, true, true>}}};
-}
-
-// Every product kernel there is, by step: the reference's, its Burning Ship variant, degrees CB_POWER_MIN ..
-// CB_POWER_MAX, codes CB_FORMULA_TRICORN .. CB_FORMULA_MAX.
-constexpr int kFirstPowerStep = 2 - CB_POWER_MIN;
-constexpr int kFirstFormulaStep = kFirstPowerStep + CB_POWER_MAX + 1 - CB_FORMULA_TRICORN;
-constexpr StepKernels kPlotKernels[] = {
-    step_kernels<ReferenceOrbit<false>>(), step_kernels<ReferenceOrbit<true>>(),
-    step_kernels<PowerOrbit<3>>(), step_kernels<PowerOrbit<4>>(), step_kernels<PowerOrbit<5>>(),
-    step_kernels<PowerOrbit<6>>(), step_kernels<PowerOrbit<7>>(), step_kernels<PowerOrbit<8>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_TRICORN>>(), step_kernels<FormulaOrbit<CB_FORMULA_CELTIC>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_BUFFALO>>(), step_kernels<FormulaOrbit<CB_FORMULA_PERPENDICULAR>>(),
-    step_kernels<FormulaOrbit<CB_FORMULA_CELTIC_TRICORN>>(),
-};
-static_assert(sizeof(kPlotKernels) / sizeof(kPlotKernels[0]) == kFirstFormulaStep + CB_FORMULA_MAX + 1, "one row per step");
+#define CB_ROW(Step)                                                                    \
+  {{{draw_plot_kernel<Step, false, false>, draw_plot_kernel<Step, false, true>},        \
+    {draw_plot_kernel<Step, true, false>, draw_plot_kernel<Step, true, true>}}},
+constexpr StepKernels kPlotKernels[] = {CB_PLOT_STEPS(CB_ROW)};
+#undef CB_ROW
+static_assert(sizeof(kPlotKernels) / sizeof(kPlotKernels[0]) == kPlotSteps, "one row per step");
 
 }  // namespace
 
 hipError_t launch_draw_plot(const PlotArgs &a, bool lockstep, hipStream_t stream) {
-  const bool power = a.degree != 2;
-  const bool ship = a.d.burning_ship != 0;
   const bool julia = a.julia != 0;
   const bool palette = a.palette != 0;
-  if (power && (a.degree < CB_POWER_MIN || a.degree > CB_POWER_MAX)) return hipErrorInvalidValue;
-  if (a.formula != 0 && (power || ship)) return hipErrorInvalidValue;  // a formula is a step of its own
-  if (power && ship) return hipErrorInvalidValue;                      // the Multibrot step has no Burning Ship variant
-  for (int j = 0; julia && j < 2; ++j) {
-    if (!(a.c[j] >= -2.0 && a.c[j] <= 2.0)) return hipErrorInvalidValue;  // a NaN fails both comparisons
-  }
+  if (!plot_launch_ok(a)) return hipErrorInvalidValue;
   // every accepted k indexes the table: the table covers [0, max_iter)
   if (palette && (a.lut == nullptr || a.d.max_iter < 1 || a.d.max_iter > CB_PALETTE_MAX_ENTRIES)) {
     return hipErrorInvalidValue;
   }
-  if (a.formula < 0 || a.formula > CB_FORMULA_MAX) return hipErrorInvalidValue;
   if (a.d.n_threads == 0 || a.d.samples_per_thread == 0) return hipSuccess;
   PlotKernel kernel = nullptr;
   if (lockstep) {
-    kernel = a.formula != 0 ? draw_formula_simple_kernel
-             : palette      ? draw_palette_simple_kernel
-             : julia        ? draw_julia_simple_kernel
-             : power        ? draw_power_simple_kernel
-                            : draw_project_simple_kernel;
+    kernel = a.formula != 0  ? draw_formula_simple_kernel
+             : palette       ? draw_palette_simple_kernel
+             : julia         ? draw_julia_simple_kernel
+             : a.degree != 2 ? draw_power_simple_kernel
+                             : draw_project_simple_kernel;
   } else {
-    const int step = a.formula != 0 ? kFirstFormulaStep + a.formula : power ? kFirstPowerStep + a.degree : (ship ? 1 : 0);
-    kernel = kPlotKernels[step].by[julia][palette];
+    kernel = kPlotKernels[plot_step_index(a)].by[julia][palette];
   }
   hipLaunchKernelGGL(kernel, dim3((a.d.n_threads + 255u) / 256u), dim3(256), 0, stream, a);
   return hipGetLastError();

@@ -1,7 +1,7 @@
-"""What the plotted renders' suites share (projected, Multibrot, Julia, palette, formula) -- test infrastructure only: the
-fixtures for the restatement and the binary, the launches on the GPU, and the three-way comparison product kernel ==
-lock-step kernel == CPU restatement (tests/plot_reference.c).  A fixture imported into a test module is a fixture of that
-module."""
+"""What the plotted renders' suites share (projected, Multibrot, Julia, palette, formula, depth, depth palette) -- test
+infrastructure only: the fixtures for the restatement and the binary, the launches on the GPU, and the three-way
+comparison product kernel == lock-step kernel == CPU restatement (tests/plot_reference.c).  A fixture imported into a test
+module is a fixture of that module."""
 
 import collections
 import os
@@ -16,6 +16,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAME = plot.COUNTER_NAMES  # every counter but skipped_steps, the clocks and status
 SQUARE = (-2.0, 2.0, -2.0, 2.0)
 INVALID = 1  # hipErrorInvalidValue
+NOT_INCREMENTS = [k for k in SAME if k != "increments"]
+
+# What the two depth suites share.  The shape, small on purpose: 64 x 48 (a transposed plane stride shows), 1000 threads (a
+# ragged last wave and workgroup), launches of 3, 50 and 1 samples on the same generators, -m 500 -c 20 (orbits cross
+# several 60-step chunk boundaries, so the exact-periodicity early-out is reached).
+DEPTH_SHAPE = 64, 48, 500, 20, 1000, (3, 50, 1)  # w, h, max_iter, min_iter, threads, launches
+C_JULIA = (-0.8, 0.156)
+# the z_re axis turned by three angles: a unit row with four irrational entries
+IRRATIONAL_ROW = plot.rotate(plot.rotate(plot.rotate(plot.IDENTITY, "zr", "zi", 25.0), "zr", "cr", 40.0), "zi", "ci", 55.0)[0]
 
 
 def omp_threads():
@@ -56,11 +65,14 @@ def variant_of(cb, base, degree=2, ship=False, formula=0):
             | (cb.CB_KERNEL_FORMULA(formula) if formula else 0))
 
 
-def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c=None, lut=None, projection=plot.IDENTITY):
+def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c=None, lut=None, projection=plot.IDENTITY,
+                 depth=None, depth_lut=None):
     """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) through the entry
-    point the arguments pick -- cb_draw_buddhabrot_palette with a table, cb_draw_buddhabrot_julia with a c, else
-    cb_draw_buddhabrot_projected, or, projection=None, the normal path: cb_draw_buddhabrot without workspace and carry
-    -> (u64 hist [h, w] or [3, h, w], counters dict, cb_debug_last_draw_kernel, generator states as u32 planes)."""
+    point the arguments pick -- with depth = (row, min, max, slices) cb_draw_buddhabrot_depth_palette (depth_lut, a table
+    of `slices` entries) or cb_draw_buddhabrot_depth; else cb_draw_buddhabrot_palette with a table, cb_draw_buddhabrot_julia
+    with a c, else cb_draw_buddhabrot_projected, or, projection=None, the normal path: cb_draw_buddhabrot without workspace
+    and carry -> (u64 hist [h, w], or [planes, h, w] with a table (3) or a depth (3 with its table, else slices), counters
+    dict, cb_debug_last_draw_kernel, generator states as u32 planes)."""
     import torch
 
     dev = torch.device("cuda", 0)
@@ -70,13 +82,22 @@ def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, 
     states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
     cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    planes = 1 if lut is None else 3
+    dd = None if depth is None else cb.Depth.make(*depth)
+    assert lut is None if depth is not None else depth_lut is None  # a table by escape index under a depth is not defined
+    lut = lut if depth is None else depth_lut
+    planes = 3 if lut is not None else 1 if depth is None else dd.slices
     out = torch.zeros(planes * w * h, dtype=torch.int64, device=dev)
     if lut is not None:
         table = np.ascontiguousarray(lut, dtype=np.uint32)
         d_lut = torch.from_numpy(table.view(np.int32).copy()).to(dev)
     for samples in launches:
-        if lut is not None:
+        if depth is not None and lut is not None:
+            cb.draw_buddhabrot_depth_palette(dims, out.data_ptr(), it, projection, c, dd, d_lut.data_ptr(), table.size,
+                                             states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
+        elif depth is not None:
+            cb.draw_buddhabrot_depth(dims, out.data_ptr(), it, projection, c, dd, states.data_ptr(), threads, samples,
+                                     counters.data_ptr(), variant, stream)
+        elif lut is not None:
             cb.draw_buddhabrot_palette(dims, out.data_ptr(), it, projection, c, d_lut.data_ptr(), table.size,
                                        states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
         elif c is not None:
@@ -94,33 +115,41 @@ def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, 
     v = counters.cpu().numpy().view(np.uint64)
     cnt = {n: int(v[k]) for k, n in enumerate(names)}
     hist = out.cpu().numpy().view(np.uint64)
-    return (hist.reshape(h, w) if lut is None else hist.reshape(3, h, w)), cnt, kernel, states.cpu().numpy().view(np.uint32)
+    hist = hist.reshape(h, w) if planes == 1 and depth is None else hist.reshape(planes, h, w)
+    return hist, cnt, kernel, states.cpu().numpy().view(np.uint32)
 
 
 # want, wc: the restatement's histogram and counters; product, lockstep: the two kernels' counters; extra: the
-# restatement's zero_entry_steps and chunk_repeats
+# restatement's zero_entry_steps and chunk_repeats and, under a depth with a table, "planes": the N planes of the
+# restatement of the same depth without the table
 ThreeWays = collections.namedtuple("ThreeWays", "want wc product lockstep extra")
 
 
 def three_ways(cb, ref, oracle, kernels, map_level, w, h, box, max_iter, min_iter, threads, launches, *, degree=2,
-               ship=False, formula=0, c=None, lut=None, device_lut=None, projection=plot.IDENTITY):
+               ship=False, formula=0, c=None, lut=None, device_lut=None, projection=plot.IDENTITY, depth=None):
     """Product == lock-step == restatement, bit for bit on histogram, generator states and the counters of SAME.
     kernels: the family's (product, lock-step) values of cb_debug_last_draw_kernel.  map_level: 0, or the least
-    interior-map level the product kernel's launch must report (the lock-step kernel's reports 0 always).  device_lut:
-    the table the GPU is given where it is not `lut` itself."""
+    interior-map level the product kernel's launch must report (the lock-step kernel's reports 0 always); None is
+    cb_draw_buddhabrot_projected's rule, 1 exactly under the Mandelbrot step on a sampled c.  device_lut: the table the
+    GPU is given where it is not `lut` itself.  depth: (row, min, max, slices); lut is then the table by slice."""
     launches = list(launches)
     st = oracle.init_states(1337, 0, threads)
     extra = {}
-    want, wc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, projection=projection, degree=degree, ship=ship,
-                         formula=formula, c=c, lut=lut, box=box, omp_threads=omp_threads(), states=st, extra=extra)
+    kw = dict(projection=projection, degree=degree, ship=ship, formula=formula, c=c, box=box, omp_threads=omp_threads())
+    want, wc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, lut=lut, depth=depth, states=st, extra=extra, **kw)
     assert wc["samples"] == threads * sum(launches) and int(want.sum()) == wc["increments"]
-    if c is not None or formula or degree != 2 or ship:  # nothing is rejected but under the reference's own step
-        assert wc["rejected"] == 0
+    assert want.shape == ((3, h, w) if lut is not None else (h, w) if depth is None else (depth[3], h, w))
+    mandelbrot = c is None and not formula and degree == 2 and not ship
+    assert (wc["rejected"] > 0) == mandelbrot  # nothing is rejected but under the reference's own step on a sampled c
+    if map_level is None:
+        map_level = 1 if mandelbrot else 0
+    table = lut if device_lut is None else device_lut
     got = {}
     for base, kernel in zip((cb.CB_KERNEL_DEFAULT, cb.CB_KERNEL_SIMPLE), kernels):
         hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches,
                                                    variant_of(cb, base, degree, ship, formula), c,
-                                                   lut if device_lut is None else device_lut, projection)
+                                                   table if depth is None else None, projection, depth,
+                                                   None if depth is None else table)
         print(kernel, cnt)
         assert launched == kernel
         assert cnt["status"] == 0
@@ -137,4 +166,15 @@ def three_ways(cb, ref, oracle, kernels, map_level, w, h, box, max_iter, min_ite
     product, lockstep = (got[k] for k in kernels)
     assert lockstep["skipped_steps"] == 0
     assert product["skipped_steps"] >= extra["zero_entry_steps"]
+    if depth is not None:
+        # the depth renders' executed-work discount: something is skipped exactly where the interior map or a sample the
+        # restatement saw repeat a point at a chunk boundary offers it -- under a table too: nothing is skipped for a colour
+        print("chunk_repeats", extra["chunk_repeats"], "product skipped_steps", product["skipped_steps"])
+        assert extra["zero_entry_steps"] == 0
+        assert (product["skipped_steps"] > 0) == (mandelbrot or extra["chunk_repeats"] > 0)
+    if depth is not None and lut is not None:  # against the restatement of the depth alone
+        planes, vc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, depth=depth, **kw)
+        assert np.array_equal(want, plot.combine(lut, planes))
+        assert {k: vc[k] for k in NOT_INCREMENTS} == {k: wc[k] for k in NOT_INCREMENTS}
+        extra["planes"] = planes
     return ThreeWays(want, wc, product, lockstep, extra)

@@ -1,12 +1,21 @@
 /* plot_reference.c -- CPU restatement of the plotted renders (include/cudabrot_amd.h, "Projected render", "Multibrot
- * step", "Julia render", "Palette render", "Formula step"), for the tests only.  Plain C on the oracle's generator and
- * shortcuts (oracle/liboracle.so), written from the definitions, not from the kernels; compiled by the tests with
+ * step", "Julia render", "Palette render", "Formula step", "Depth render", "Depth-palette render"), for the tests only.
+ * Plain C on the oracle's generator and shortcuts (oracle/liboracle.so), written from the definitions, not from the
+ * kernels; compiled by the tests with
  *   gcc -O2 -shared -fPIC -ffp-contract=off -mfma [-fopenmp]
- *   plot_step   one step of one point
- *   plot_point  the plot of one point alone: (u, v) of (z, c) under P
- *   plot_draw   one launch: samples_per_thread samples from each generator; c is the sample (c_fixed NULL) or fixed (a
- *               Julia render: the sample is then z_0); every in-canvas point of an accepted orbit adds 1 to its pixel
- *               (lut NULL: one plane) or the three weights of lut[k], k the escape index, to its pixel in three planes
+ *   plot_step         one step of one point
+ *   plot_point        the plot of one point alone: (u, v) of (z, c) under P
+ *   plot_depth        the depth of one point alone: d of (z, c) under D
+ *   plot_slice        the slice of one depth alone: s, or -1 for a depth outside the window
+ *   plot_weight       weight_j of an entry
+ *   plot_slice_entry  the entry of one depth alone, or -1 for a depth outside the window
+ *   plot_draw         one launch: samples_per_thread samples from each generator; c is the sample (c_fixed NULL) or fixed
+ *                     (a Julia render: the sample is then z_0); a launch is a step, a source of c and a sink -- where an
+ *                     in-canvas point of an accepted orbit goes, and with what weight:
+ *                       no depth, no table  1 to its pixel of the one plane
+ *                       table               the three weights of lut[k], k the escape index, to its pixel of three planes
+ *                       depth               1 to its pixel of plane s of N, s the slice of its depth; none outside the window
+ *                       depth and table     the three weights of lut[s] to its pixel of three planes; lut has N entries
  * plot_draw has an OpenMP variant (n_omp > 0: that many workers, atomic increments); without -fopenmp the pragmas are
  * ignored and it runs on one thread. */
 #include <math.h>
@@ -87,12 +96,38 @@ static int bin_of(const orc_dims *d, double u, double v, uint64_t *index) {
   return 1;
 }
 
+/* D is D[4]: columns (z_re, z_im, c_re, c_im). */
+double plot_depth(const double *D, double zr, double zi, double cr, double ci) {
+  const double kd = fma(D[2], cr, D[3] * ci);
+  return fma(D[0], zr, fma(D[1], zi, kd));
+}
+
+/* delta_d as the host makes it: (max - min) / (double) N, as cb_recompute_pixel_deltas makes delta_imag. */
+static double depth_delta(double min, double max, int slices) { return (max - min) / (double) slices; }
+
+/* The reference's binning of `im` with the window in the place of the canvas's rows. */
+int plot_slice(double d, double min, double max, int slices) {
+  if (d < min) return -1;
+  const int s = (int) ((d - min) / depth_delta(min, max, slices));
+  if (s < 0 || s >= slices) return -1;
+  return s;
+}
+
+/* weight_j of an entry: plane 0 = R (bits 0-7), 1 = G (8-15), 2 = B (16-23); bits 24-31 are not read. */
+uint64_t plot_weight(uint32_t entry, int plane) { return (uint64_t) ((entry >> (8 * plane)) & 0xffu); }
+
+/* The entry of a depth: lut[s] without its unread bits for a depth in slice s of the window, -1 for a depth outside it. */
+int64_t plot_slice_entry(double depth, double dmin, double dmax, int slices, const uint32_t *lut) {
+  const int s = plot_slice(depth, dmin, dmax, slices);
+  return s < 0 ? -1 : (int64_t) (lut[s] & 0xffffffu);
+}
+
 static int same_bits(double a, double b) { return memcmp(&a, &b, sizeof(a)) == 0; }
 
-/* One sample (sr, si): z_0, and c as well unless c is fixed. */
+/* One sample (sr, si): z_0, and c as well unless c is fixed.  D NULL: no depth. */
 static void one_sample(const orc_dims *d, const orc_iters *it, int formula, int degree, int ship, int reject,
-                       const double *P, const double *c_fixed, const uint32_t *lut, double sr, double si, uint64_t *hist,
-                       int atomic, plot_counters *cnt) {
+                       const double *P, const double *c_fixed, const uint32_t *lut, const double *D, double dmin,
+                       double dmax, int slices, double sr, double si, uint64_t *hist, int atomic, plot_counters *cnt) {
   const int max = it->max_escape_iterations;
   const double cr = c_fixed ? c_fixed[0] : sr, ci = c_fixed ? c_fixed[1] : si;
   cnt->samples++;
@@ -128,9 +163,10 @@ static void one_sample(const orc_dims *d, const orc_iters *it, int formula, int 
     return;
   }
   cnt->recorded++;
-  const uint32_t entry = lut ? lut[k] : 1u; /* no table: weight 1 in the one plane */
-  const uint64_t weight[3] = {entry & 0xffu, (entry >> 8) & 0xffu, (entry >> 16) & 0xffu};
-  if ((entry & 0xffffffu) == 0u) cnt->zero_entry_steps += (uint64_t) k + 1u;
+  /* the orbit's entry: lut[k] of a table by escape index, else weight 1 in one plane -- under a depth the point's
+   * slice says which plane, or (a table by depth) replaces the entry; no orbit is skipped on account of a colour then */
+  const uint32_t orbit_entry = (lut && !D) ? lut[k] : 1u;
+  if ((orbit_entry & 0xffffffu) == 0u) cnt->zero_entry_steps += (uint64_t) k + 1u;
   const uint64_t plane_pixels = (uint64_t) d->w * (uint64_t) d->h;
   const double ku = fma(P[2], cr, P[3] * ci); /* once per sample */
   const double kv = fma(P[6], cr, P[7] * ci);
@@ -144,14 +180,28 @@ static void one_sample(const orc_dims *d, const orc_iters *it, int formula, int 
     const double v = fma(P[4], r, fma(P[5], i, kv));
     uint64_t index;
     if (!bin_of(d, u, v, &index)) continue;
-    for (int j = 0; j < 3; ++j) {
-      if (weight[j] == 0u) continue;
-      if (atomic) {
-        __atomic_fetch_add(hist + (uint64_t) j * plane_pixels + index, weight[j], __ATOMIC_RELAXED);
+    uint32_t entry = orbit_entry;
+    uint64_t first_plane = 0u;
+    if (D) {
+      const double depth = plot_depth(D, r, i, cr, ci);
+      const int64_t in_depth = lut ? plot_slice_entry(depth, dmin, dmax, slices, lut) : plot_slice(depth, dmin, dmax, slices);
+      if (in_depth < 0) continue;
+      if (lut) {
+        entry = (uint32_t) in_depth;
       } else {
-        hist[(uint64_t) j * plane_pixels + index] += weight[j];
+        first_plane = (uint64_t) in_depth;
       }
-      cnt->increments += weight[j];
+    }
+    for (int j = 0; j < 3; ++j) {
+      const uint64_t weight = plot_weight(entry, j);
+      if (weight == 0u) continue;
+      uint64_t *at = hist + (first_plane + (uint64_t) j) * plane_pixels + index;
+      if (atomic) {
+        __atomic_fetch_add(at, weight, __ATOMIC_RELAXED);
+      } else {
+        *at += weight;
+      }
+      cnt->increments += weight;
     }
   }
 }
@@ -162,13 +212,14 @@ static void counters_add(plot_counters *dst, const plot_counters *src) {
   for (size_t k = 0; k < sizeof(plot_counters) / sizeof(uint64_t); ++k) a[k] += b[k];
 }
 
-/* samples_per_thread samples from each of states[0 .. n_threads), advancing them; four draws per sample.  hist: one
- * plane of w*h counters (lut NULL) or three; lut: max_escape_iterations entries; c_fixed NULL: c is the sample; reject:
- * samples in the main cardioid or the period-2 bulb are counted and dropped unseen (the caller's choice -- the product
- * does so exactly for a sampled c under the reference's own step). */
+/* samples_per_thread samples from each of states[0 .. n_threads), advancing them; four draws per sample.  hist: planes
+ * of w*h counters -- one (lut NULL, D NULL), `slices` (D alone) or three (lut); lut: max_escape_iterations entries, or
+ * `slices` with D; c_fixed NULL: c is the sample; reject: samples in the main cardioid or the period-2 bulb are counted
+ * and dropped unseen (the caller's choice -- the product does so exactly for a sampled c under the reference's own
+ * step). */
 void plot_draw(const orc_dims *d, uint64_t *hist, const orc_iters *it, int formula, int degree, int ship, int reject,
-               const double *P, const double *c_fixed, const uint32_t *lut, orc_xorwow *states, uint64_t n_threads,
-               int samples_per_thread, plot_counters *out, int n_omp) {
+               const double *P, const double *c_fixed, const uint32_t *lut, const double *D, double dmin, double dmax,
+               int slices, orc_xorwow *states, uint64_t n_threads, int samples_per_thread, plot_counters *out, int n_omp) {
   plot_counters total;
   memset(&total, 0, sizeof(total));
   const int workers = n_omp > 0 ? n_omp : 1;
@@ -181,7 +232,8 @@ void plot_draw(const orc_dims *d, uint64_t *hist, const orc_iters *it, int formu
       for (int s = 0; s < samples_per_thread; ++s) {
         const double sr = orc_uniform_double(&states[t]) * 4.0 - 2.0;
         const double si = orc_uniform_double(&states[t]) * 4.0 - 2.0;
-        one_sample(d, it, formula, degree, ship, reject, P, c_fixed, lut, sr, si, hist, n_omp > 0, &mine);
+        one_sample(d, it, formula, degree, ship, reject, P, c_fixed, lut, D, dmin, dmax, slices, sr, si, hist, n_omp > 0,
+                   &mine);
       }
     }
 #pragma omp critical(plot_counters_sum)

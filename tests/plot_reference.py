@@ -64,6 +64,17 @@ def demo_table(n):
     return (k & 255) | (((k * 7) & 255) << 8) | (((k >> 1) & 255) << 16)
 
 
+def row_of(row):
+    """A depth row from an axis name (zr, zi, cr, ci) or four numbers."""
+    if isinstance(row, str):
+        out = np.zeros(4)
+        out[AXES[row]] = 1.0
+        return out
+    out = np.ascontiguousarray(np.asarray(row, dtype=np.float64).reshape(-1))
+    assert out.size == 4
+    return out
+
+
 def window_table(n, windows):
     """Plane j has weight 1 on [lo_j, hi_j), 0 elsewhere: windows = [(lo, hi)] * 3."""
     k = np.arange(n, dtype=np.uint32)
@@ -93,12 +104,20 @@ def load(directory):
     lib = C.CDLL(so)
     vp, i32, u64, f64 = C.c_void_p, C.c_int, C.c_uint64, C.c_double
     dims_p, it_p, cnt_p = C.POINTER(binding.Dims), C.POINTER(binding.Iters), C.POINTER(Counters)
-    lib.plot_draw.argtypes = [dims_p, vp, it_p, i32, i32, i32, i32, vp, vp, vp, vp, u64, i32, cnt_p, i32]
+    lib.plot_draw.argtypes = [dims_p, vp, it_p, i32, i32, i32, i32, vp, vp, vp, vp, f64, f64, i32, vp, u64, i32, cnt_p, i32]
     lib.plot_draw.restype = None
     lib.plot_step.argtypes = [i32, i32, i32, f64, f64, C.POINTER(f64), C.POINTER(f64)]
     lib.plot_step.restype = f64
     lib.plot_point.argtypes = [vp, f64, f64, f64, f64, C.POINTER(f64), C.POINTER(f64)]
     lib.plot_point.restype = None
+    lib.plot_depth.argtypes = [vp, f64, f64, f64, f64]
+    lib.plot_depth.restype = f64
+    lib.plot_slice.argtypes = [f64, f64, f64, i32]
+    lib.plot_slice.restype = i32
+    lib.plot_weight.argtypes = [C.c_uint32, i32]
+    lib.plot_weight.restype = u64
+    lib.plot_slice_entry.argtypes = [f64, f64, f64, i32, vp]
+    lib.plot_slice_entry.restype = C.c_int64
     return lib
 
 
@@ -124,12 +143,52 @@ def point(lib, projection, zr, zi, cr, ci):
     return float(u.value), float(v.value)
 
 
+def depth_of(lib, row, zr, zi, cr, ci):
+    """The depth of one point under the row."""
+    d = row_of(row)
+    return float(lib.plot_depth(d.ctypes.data, zr, zi, cr, ci))
+
+
+def slice_of(lib, d, lo, hi, slices):
+    """The slice of the depth d in the window [lo, hi) cut into `slices`; None outside."""
+    s = int(lib.plot_slice(float(d), float(lo), float(hi), int(slices)))
+    return None if s < 0 else s
+
+
+def entry_of(lib, d, lo, hi, lut):
+    """The entry of the depth d in the window [lo, hi) cut into len(lut) slices; None outside."""
+    table = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+    e = int(lib.plot_slice_entry(float(d), float(lo), float(hi), int(table.size), table.ctypes.data))
+    return None if e < 0 else e
+
+
+def weights(lut):
+    """[n, 3] u64: weight_j of every entry of a table."""
+    t = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+    return np.stack([(t >> np.uint32(8 * j)) & np.uint32(0xFF) for j in range(3)], axis=1).astype(np.uint64)
+
+
+def combine(lut, planes):
+    """Consequence 1 of "Depth-palette render": [3, h, w], plane j = sum over s of weight_j(lut[s]) * planes[s], in
+    uint64."""
+    w = weights(lut)
+    assert w.shape[0] == planes.shape[0]
+    out = np.zeros((3,) + planes.shape[1:], dtype=np.uint64)
+    for s in range(planes.shape[0]):
+        for j in range(3):
+            if w[s, j]:
+                out[j] += w[s, j] * planes[s]
+    return out
+
+
 def draw(lib, w, h, max_iter, min_iter, n_threads, launches, *, projection=IDENTITY, degree=2, ship=False, formula=0,
-         c=None, lut=None, reject=None, box=(-2.0, 2.0, -2.0, 2.0), omp_threads=0, seed=1337, first_subsequence=0,
-         states=None, hist=None, extra=None):
-    """One launch per entry of `launches` (samples per thread) on the same generators -> (u64 hist [h, w], or [3, h, w]
-    with a table, counters dict).  formula: a code or a name, 0 for none; c None: c is sampled, else the fixed c of a
-    Julia render; lut None: one plane.  reject: whether samples in the cardioid or the bulb are dropped unseen; None is the
+         c=None, lut=None, depth=None, reject=None, box=(-2.0, 2.0, -2.0, 2.0), omp_threads=0, seed=1337,
+         first_subsequence=0, states=None, hist=None, extra=None):
+    """One launch per entry of `launches` (samples per thread) on the same generators -> (u64 hist, counters dict).
+    formula: a code or a name, 0 for none; c None: c is sampled, else the fixed c of a Julia render.  The sink: hist is
+    [h, w]; with lut, a table of max_iter entries by escape index, [3, h, w]; with depth = (row, min, max, slices),
+    [slices, h, w]; with depth and lut, a table of `slices` entries by slice, [3, h, w] -- a table by escape index under a
+    depth is not defined.  reject: whether samples in the cardioid or the bulb are dropped unseen; None is the
     product's rule -- exactly when c is sampled under the reference's own step (no formula, degree 2, no ship).  Given
     `states` are advanced in place, a given `hist` is added to; a given dict `extra` receives zero_entry_steps (the replay
     steps of the accepted orbits whose entry has no weight) and chunk_repeats (the samples that met a bit-identical earlier
@@ -142,19 +201,22 @@ def draw(lib, w, h, max_iter, min_iter, n_threads, launches, *, projection=IDENT
     d = binding.make_dims(w, h, *box)
     it = binding.Iters(max_iter, min_iter)
     st = binding.init_states(seed, first_subsequence, n_threads) if states is None else states
+    row, lo, hi, slices = (None, 0.0, 0.0, 0) if depth is None else depth
+    dr = None if depth is None else row_of(row)
     if hist is None:
-        hist = np.zeros((h, w) if lut is None else (3, h, w), dtype=np.uint64)
+        hist = np.zeros((3, h, w) if lut is not None else (h, w) if depth is None else (slices, h, w), dtype=np.uint64)
     p = matrix(projection)
     table = None
     if lut is not None:
-        table = np.ascontiguousarray(lut, dtype=np.uint32)
-        assert table.size == max_iter
+        table = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+        assert table.size == (max_iter if depth is None else slices)  # by escape index, or by slice: never both
     cc = None if c is None else np.array([float(c[0]), float(c[1])], dtype=np.float64)
     cnt = Counters()
     for samples in launches:
         lib.plot_draw(C.byref(d), hist.ctypes.data, C.byref(it), f, degree, 1 if ship else 0, 1 if reject else 0,
                       p.ctypes.data, None if cc is None else cc.ctypes.data, None if table is None else table.ctypes.data,
-                      st.ctypes.data, n_threads, samples, C.byref(cnt), omp_threads)
+                      None if dr is None else dr.ctypes.data, float(lo), float(hi), int(slices), st.ctypes.data, n_threads,
+                      samples, C.byref(cnt), omp_threads)
     if extra is not None:
         extra["zero_entry_steps"] = int(cnt.zero_entry_steps)
         extra["chunk_repeats"] = int(cnt.chunk_repeats)

@@ -1,6 +1,6 @@
-"""The depth render without a GPU (include/cudabrot_amd.h, "Depth render"): the CPU restatement (tests/depth_reference.c)
-against the plotted renders' restatement it extends and against the definition by hand, the header's text, and the
-validation of cb_depth where it needs no device."""
+"""The depth render without a GPU (include/cudabrot_amd.h, "Depth render"): the depth sink of the CPU restatement
+(tests/plot_reference.c) against the same restatement without a depth and against the definition by hand, the header's
+text, and the validation of cb_depth where it needs no device."""
 
 import ctypes as C
 import math
@@ -9,17 +9,11 @@ import os
 import numpy as np
 import pytest
 
-import depth_reference as depth
 import plot_reference as plot
 from plot_harness import INVALID, ref  # noqa: F401  (a fixture)
 
 
-@pytest.fixture(scope="module")
-def dref(tmp_path_factory):
-    return depth.load(tmp_path_factory.mktemp("depth_ref"))
-
-
-# ---- 1. the restatement against the plotted renders' ---------------------------------------------------------------
+# ---- 1. the depth sink against the restatement without a depth -----------------------------------------------------
 
 # Every visited coordinate of a degree-2 step is below 8 + 2 sqrt 2 in magnitude, of degree 3 below (2 sqrt 2)^3 +
 # 2 sqrt 2; a row of the hologram has entries of magnitude at most 1 and two of them non-zero per axis pair, so [-64, 64)
@@ -38,14 +32,14 @@ COVERING = {
 
 
 @pytest.mark.parametrize("case", list(COVERING))
-def test_planes_sum_to_the_projected_render_when_the_window_covers(ref, dref, oracle, case):
+def test_planes_sum_to_the_projected_render_when_the_window_covers(ref, oracle, case):
     kw = dict(COVERING[case])
     d = kw.pop("depth")
     w, h, max_iter, min_iter, threads, launches = 64, 48, 200, 2, 64, [20, 3]
     own = oracle.init_states(1337, 0, threads)
     want, wc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, states=own, **kw)
     states = oracle.init_states(1337, 0, threads)
-    hist, cnt = depth.draw(dref, w, h, max_iter, min_iter, threads, launches, d, states=states, **kw)
+    hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, depth=d, states=states, **kw)
     assert wc["recorded"] > 0 and wc["increments"] > 0
     assert hist.shape == (d[3], h, w)
     assert np.array_equal(hist.sum(axis=0), want)
@@ -56,25 +50,25 @@ def test_planes_sum_to_the_projected_render_when_the_window_covers(ref, dref, or
         assert sum(bool(p.any()) for p in hist) == 1  # a fixed c on a c axis: one depth for every point
 
 
-def test_one_slice_with_a_covering_window_is_the_projected_render(ref, dref):
+def test_one_slice_with_a_covering_window_is_the_projected_render(ref):
     want, wc = plot.draw(ref, 64, 48, 200, 2, 64, [20], projection=plot.ZR_CR)
-    hist, cnt = depth.draw(dref, 64, 48, 200, 2, 64, [20], ("zi", -16.0, 16.0, 1), projection=plot.ZR_CR)
+    hist, cnt = plot.draw(ref, 64, 48, 200, 2, 64, [20], depth=("zi", -16.0, 16.0, 1), projection=plot.ZR_CR)
     assert hist.shape == (1, 48, 64) and np.array_equal(hist[0], want) and cnt == wc
 
 
-def test_a_narrow_window_drops_points_and_only_increments_notices(ref, dref):
+def test_a_narrow_window_drops_points_and_only_increments_notices(ref):
     want, wc = plot.draw(ref, 64, 48, 200, 2, 64, [20])
-    hist, cnt = depth.draw(dref, 64, 48, 200, 2, 64, [20], ("ci", -0.02, 0.02, 1))
+    hist, cnt = plot.draw(ref, 64, 48, 200, 2, 64, [20], depth=("ci", -0.02, 0.02, 1))
     assert 0 < cnt["increments"] < wc["increments"] and int(hist.sum()) == cnt["increments"]
     assert {k: v for k, v in cnt.items() if k != "increments"} == {k: v for k, v in wc.items() if k != "increments"}
     assert np.all(hist[0] <= want)
 
 
-def test_result_does_not_depend_on_the_thread_count(dref, oracle):
+def test_result_does_not_depend_on_the_thread_count(ref, oracle):
     got = []
     for omp in (0, 4):
         states = oracle.init_states(1337, 0, 256)
-        hist, cnt = depth.draw(dref, 33, 17, 300, 0, 256, [50, 7], ("cr", -2.0, 0.5, 5), omp_threads=omp, states=states)
+        hist, cnt = plot.draw(ref, 33, 17, 300, 0, 256, [50, 7], depth=("cr", -2.0, 0.5, 5), omp_threads=omp, states=states)
         got.append((hist, cnt, states.tobytes()))
     assert got[0][1]["increments"] > 100
     assert np.array_equal(got[0][0], got[1][0]) and got[0][1] == got[1][1] and got[0][2] == got[1][2]
@@ -92,45 +86,38 @@ def by_hand(d, lo, hi, n):
 
 
 @pytest.mark.parametrize("lo, hi, n", [(-2.0, 2.0, 4), (-2.0, 0.5, 5), (-0.02, 0.02, 1), (0.1, 0.7, 256), (-16.0, 16.0, 64)])
-def test_planted_depths_land_where_the_definition_says(dref, lo, hi, n):
+def test_planted_depths_land_where_the_definition_says(ref, lo, hi, n):
     delta = (hi - lo) / float(n)
     dyadic = math.frexp(delta)[0] == 0.5
-    assert depth.slice_of(dref, lo, lo, hi, n) == 0  # exactly at min: in, slice 0
-    assert depth.slice_of(dref, math.nextafter(lo, -math.inf), lo, hi, n) is None  # just below min: the early-out
-    assert depth.slice_of(dref, hi, lo, hi, n) == by_hand(hi, lo, hi, n)
+    assert plot.slice_of(ref, lo, lo, hi, n) == 0  # exactly at min: in, slice 0
+    assert plot.slice_of(ref, math.nextafter(lo, -math.inf), lo, hi, n) is None  # just below min: the early-out
+    assert plot.slice_of(ref, hi, lo, hi, n) == by_hand(hi, lo, hi, n)
     below_max = math.nextafter(hi, -math.inf)
-    assert depth.slice_of(dref, below_max, lo, hi, n) == by_hand(below_max, lo, hi, n)
+    assert plot.slice_of(ref, below_max, lo, hi, n) == by_hand(below_max, lo, hi, n)
     for s in range(n):
         edge = lo + s * delta
-        assert depth.slice_of(dref, edge, lo, hi, n) == by_hand(edge, lo, hi, n)
+        assert plot.slice_of(ref, edge, lo, hi, n) == by_hand(edge, lo, hi, n)
         inside = lo + (s + 0.5) * delta
-        assert depth.slice_of(dref, inside, lo, hi, n) == s
+        assert plot.slice_of(ref, inside, lo, hi, n) == s
         # one ulp below an edge: d - min is a rounded difference, so the neighbour of an edge may still reach the edge's
         # slice (-7.5 - ulp in [-16, 16) / 64: d - min rounds to 8.5); the definition says which, not the real line
         near = math.nextafter(edge, -math.inf)
-        assert depth.slice_of(dref, near, lo, hi, n) == by_hand(near, lo, hi, n)
+        assert plot.slice_of(ref, near, lo, hi, n) == by_hand(near, lo, hi, n)
         if dyadic:  # every edge and every quotient is exact: the slice begins at its edge
-            assert depth.slice_of(dref, edge, lo, hi, n) == s
+            assert plot.slice_of(ref, edge, lo, hi, n) == s
     if dyadic:
-        assert depth.slice_of(dref, hi, lo, hi, n) is None  # max itself is out
-    assert depth.slice_of(dref, math.nan, lo, hi, n) is None  # !(d < min) lets it through, the bounds test does not
-    assert depth.slice_of(dref, 1e300, lo, hi, n) is None and depth.slice_of(dref, -1e300, lo, hi, n) is None
+        assert plot.slice_of(ref, hi, lo, hi, n) is None  # max itself is out
+    assert plot.slice_of(ref, math.nan, lo, hi, n) is None  # !(d < min) lets it through, the bounds test does not
+    assert plot.slice_of(ref, 1e300, lo, hi, n) is None and plot.slice_of(ref, -1e300, lo, hi, n) is None
 
 
-def test_depth_of_a_point(dref):
+def test_depth_of_a_point(ref):
     z, c = (0.3, -0.7), (-1.25, 0.4)
     for j, axis in enumerate(("zr", "zi", "cr", "ci")):
-        assert depth.point(dref, axis, *z, *c) == (z + c)[j]
+        assert plot.depth_of(ref, axis, *z, *c) == (z + c)[j]
     # the same fused operations as u: a row of the matrix and the depth row give the same number
     row = plot.HOLOGRAM[1]
-    assert depth.point(dref, row, *z, *c) == plot.point(ref_lib(dref), np.vstack([row, row]), *z, *c)[0]
-
-
-def ref_lib(dref):
-    """depth_reference.c includes plot_reference.c: the library has plot_point too."""
-    dref.plot_point.argtypes = [C.c_void_p] + [C.c_double] * 4 + [C.POINTER(C.c_double)] * 2
-    dref.plot_point.restype = None
-    return dref
+    assert plot.depth_of(ref, row, *z, *c) == plot.point(ref, np.vstack([row, row]), *z, *c)[0]
 
 
 # ---- 3. the header and the package ------------------------------------------------------------------------------------

@@ -6,24 +6,17 @@ every kernel, at most 128 VGPRs and at least 4 waves per SIMD -- the bar every p
 compiler's reported figures and the assembly's text only."""
 
 import os
-import re
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, at_most, compile_kernels
+from test_round_kernels_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, plot_instance_of
 
-STEPS = ([("ReferenceOrbit", "0"), ("ReferenceOrbit", "1")] + [("PowerOrbit", str(d)) for d in range(3, 9)]
-         + [("FormulaOrbit", str(f)) for f in range(1, 6)])
-INSTANCES = [(s, j) for s in STEPS for j in "01"]  # 13 steps x {sampled c, fixed c}
+INSTANCES = [(s, j) for s in PLOT_STEPS for j in "01"]  # 13 steps x {sampled c, fixed c}
 
 
 def instance_of(name):
-    """(step, fixed c) of a mangled draw_depth_kernel<Step, kJulia>: Step is ReferenceOrbit<bool> (ILb.E), PowerOrbit<int>
-    or FormulaOrbit<int> (ILi.E); Lb0E sampled c, Lb1E fixed c."""
-    m = re.search(r"draw_depth_kernelINS_\d+(ReferenceOrbit|PowerOrbit|FormulaOrbit)IL([bi])(\d+)EEELb(\d)EEEvNS_9DepthArgsE$", name)
-    assert m, name
-    assert m.group(2) == ("b" if m.group(1) == "ReferenceOrbit" else "i"), name
-    return (m.group(1), m.group(3)), m.group(4)
+    """(step, fixed c) of a mangled draw_depth_kernel<Step, kJulia>: Lb0E sampled c, Lb1E fixed c."""
+    return plot_instance_of(name, "draw_depth_kernel", 1, "9DepthArgs")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

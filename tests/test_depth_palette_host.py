@@ -1,6 +1,6 @@
-"""The depth-palette render without a GPU (include/cudabrot_amd.h, "Depth-palette render"): the CPU restatement
-(tests/depth_palette_reference.c) against the depth render's restatement it extends -- the definition's three consequences
--- and against the definition by hand, the header's text, the stops' table, and the validation that needs no device."""
+"""The depth-palette render without a GPU (include/cudabrot_amd.h, "Depth-palette render"): the table-by-slice sink of the
+CPU restatement (tests/plot_reference.c) against its depth sink without a table -- the definition's three consequences --
+and against the definition by hand, the header's text, the stops' table, and the validation that needs no device."""
 
 import ctypes as C
 import math
@@ -9,16 +9,8 @@ import os
 import numpy as np
 import pytest
 
-import depth_palette_reference as dp
-import depth_reference as depth
 import plot_reference as plot
-from plot_harness import INVALID
-
-
-@pytest.fixture(scope="module")
-def pref(tmp_path_factory):
-    return dp.load(tmp_path_factory.mktemp("depth_palette_ref"))
-
+from plot_harness import INVALID, ref  # noqa: F401  (a fixture)
 
 W, H, MAX, MIN, THREADS, LAUNCHES = 64, 48, 200, 2, 64, [20, 3]
 
@@ -27,7 +19,7 @@ def gradient(cb, n, stops):
     return cb.palette_from_stops(stops, n)
 
 
-# ---- 1. the three consequences, against depth_reference ------------------------------------------------------------------
+# ---- 1. the three consequences, against the depth sink ------------------------------------------------------------------
 
 CASES = {
     "mandelbrot_cr_5": dict(d=("cr", -2.0, 0.5, 5)),
@@ -43,63 +35,64 @@ CASES = {
 
 
 @pytest.mark.parametrize("case", list(CASES))
-def test_planes_are_the_weighted_sums_of_the_depth_renders_planes(pref, oracle, case):
+def test_planes_are_the_weighted_sums_of_the_depth_renders_planes(ref, oracle, case):
     kw = dict(CASES[case])
     d = kw.pop("d")
     lut = plot.demo_table(d[3]) + np.uint32(0x030201)  # every neighbour differs, no entry is all zero
     own = oracle.init_states(1337, 0, THREADS)
-    planes, vc = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, states=own, **kw)
+    planes, vc = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d, states=own, **kw)
     states = oracle.init_states(1337, 0, THREADS)
-    hist, cnt = dp.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, lut, states=states, **kw)
+    hist, cnt = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d, lut=lut, states=states, **kw)
     assert vc["increments"] > 0 and sum(bool(p.any()) for p in planes) >= 2
-    assert hist.shape == (3, H, W) and np.array_equal(hist, dp.combine(lut, planes))
+    assert hist.shape == (3, H, W) and np.array_equal(hist, plot.combine(lut, planes))
     assert int(hist.sum()) == cnt["increments"] > vc["increments"]
     assert {k: v for k, v in cnt.items() if k != "increments"} == {k: v for k, v in vc.items() if k != "increments"}
     assert states.tobytes() == own.tobytes()
 
 
-def test_a_one_hot_table_gives_that_slice(pref):
+def test_a_one_hot_table_gives_that_slice(ref):
     d = ("cr", -2.0, 0.5, 5)
-    planes, vc = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d)
+    planes, vc = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d)
     populated = [s for s in range(5) if planes[s].any()]
     assert len(populated) >= 2
     for s in populated[:2]:
         lut = np.zeros(5, dtype=np.uint32)
         lut[s] = 1
-        hist, cnt = dp.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, lut)
+        hist, cnt = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d, lut=lut)
         assert np.array_equal(hist[0], planes[s]) and not hist[1].any() and not hist[2].any()
         assert cnt["increments"] == int(planes[s].sum()) and cnt["replay_steps"] == vc["replay_steps"]
 
 
-def test_the_constant_table_gives_the_section_three_times(pref):
+def test_the_constant_table_gives_the_section_three_times(ref):
     d = ("ci", -0.3, 0.3, 1)
-    planes, vc = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d)
-    hist, cnt = dp.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, [0x010101])
+    planes, vc = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d)
+    hist, cnt = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d, lut=[0x010101])
     assert planes[0].any() and all(np.array_equal(hist[j], planes[0]) for j in range(3))
     assert cnt["increments"] == 3 * vc["increments"]
 
 
-def test_a_zero_entry_adds_nothing_and_only_increments_notices(pref):
+def test_a_zero_entry_adds_nothing_and_only_increments_notices(ref):
     d = ("cr", -2.0, 0.5, 5)
-    planes, vc = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d)
+    planes, vc = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d)
     s = int(np.argmax([int(p.sum()) for p in planes]))  # the fullest slice goes dark
     lut = np.array([0x0000ff, 0x00ff00, 0xff0000, 0x010203, 0x7f0001], dtype=np.uint32)
     lut[s] = 0xff000000  # bits 24-31 are not read: an entry without a weight
-    hist, cnt = dp.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, lut)
+    hist, cnt = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=d, lut=lut)
     lit = lut.copy()
     lit[s] = 0
-    assert np.array_equal(hist, dp.combine(lit, planes))
+    assert np.array_equal(hist, plot.combine(lit, planes))
     assert cnt["increments"] == int(hist.sum()) > 0
     assert {k: v for k, v in cnt.items() if k != "increments"} == {k: v for k, v in vc.items() if k != "increments"}
     assert int(planes[s].sum()) > 0 and any(planes[t].any() for t in range(5) if t != s)  # it had points, and others have
 
 
-def test_result_does_not_depend_on_the_thread_count(pref, oracle):
+def test_result_does_not_depend_on_the_thread_count(ref, oracle):
     got = []
     lut = plot.demo_table(5) + np.uint32(1)
     for omp in (0, 4):
         states = oracle.init_states(1337, 0, 256)
-        hist, cnt = dp.draw(pref, 33, 17, 300, 0, 256, [50, 7], ("cr", -2.0, 0.5, 5), lut, omp_threads=omp, states=states)
+        hist, cnt = plot.draw(ref, 33, 17, 300, 0, 256, [50, 7], depth=("cr", -2.0, 0.5, 5), lut=lut, omp_threads=omp,
+                              states=states)
         got.append((hist, cnt, states.tobytes()))
     assert got[0][1]["increments"] > 100
     assert np.array_equal(got[0][0], got[1][0]) and got[0][1] == got[1][1] and got[0][2] == got[1][2]
@@ -118,31 +111,31 @@ def by_hand(d, lo, hi, lut):
 
 
 @pytest.mark.parametrize("lo, hi, n", [(-2.0, 2.0, 4), (-2.0, 0.5, 5), (-0.02, 0.02, 1), (0.1, 0.7, 256)])
-def test_planted_depths_at_slice_edges_take_the_entry_the_definition_says(pref, lo, hi, n):
+def test_planted_depths_at_slice_edges_take_the_entry_the_definition_says(ref, lo, hi, n):
     lut = (plot.demo_table(n) + np.uint32(0x010101)) | np.uint32(0xAB000000)  # neighbours differ; the top byte is noise
     assert len(set(int(v) & 0xFFFFFF for v in lut)) == n
     delta = (hi - lo) / float(n)
     dyadic = math.frexp(delta)[0] == 0.5
-    assert dp.entry_of(pref, lo, lo, hi, lut) == int(lut[0]) & 0xFFFFFF
-    assert dp.entry_of(pref, math.nextafter(lo, -math.inf), lo, hi, lut) is None
+    assert plot.entry_of(ref, lo, lo, hi, lut) == int(lut[0]) & 0xFFFFFF
+    assert plot.entry_of(ref, math.nextafter(lo, -math.inf), lo, hi, lut) is None
     for s in range(n):
         edge = lo + s * delta
         for d in (edge, math.nextafter(edge, -math.inf), math.nextafter(edge, math.inf)):
-            assert dp.entry_of(pref, d, lo, hi, lut) == by_hand(d, lo, hi, lut), (s, d)
-        assert dp.entry_of(pref, lo + (s + 0.5) * delta, lo, hi, lut) == int(lut[s]) & 0xFFFFFF
+            assert plot.entry_of(ref, d, lo, hi, lut) == by_hand(d, lo, hi, lut), (s, d)
+        assert plot.entry_of(ref, lo + (s + 0.5) * delta, lo, hi, lut) == int(lut[s]) & 0xFFFFFF
         if dyadic and s > 0:  # exact edges and quotients: the slice's entry begins at its edge, its neighbour's ends below
-            # (how far below is the definition's to say: d - min is a rounded difference -- depth_reference's note)
-            assert dp.entry_of(pref, edge, lo, hi, lut) == int(lut[s]) & 0xFFFFFF
-            assert dp.entry_of(pref, edge - delta / 1024.0, lo, hi, lut) == int(lut[s - 1]) & 0xFFFFFF
-    assert dp.entry_of(pref, hi, lo, hi, lut) == by_hand(hi, lo, hi, lut)
+            # (how far below is the definition's to say: d - min is a rounded difference -- tests/test_depth_host.py's note)
+            assert plot.entry_of(ref, edge, lo, hi, lut) == int(lut[s]) & 0xFFFFFF
+            assert plot.entry_of(ref, edge - delta / 1024.0, lo, hi, lut) == int(lut[s - 1]) & 0xFFFFFF
+    assert plot.entry_of(ref, hi, lo, hi, lut) == by_hand(hi, lo, hi, lut)
     if dyadic:
-        assert dp.entry_of(pref, hi, lo, hi, lut) is None
-    assert dp.entry_of(pref, math.nan, lo, hi, lut) is None
+        assert plot.entry_of(ref, hi, lo, hi, lut) is None
+    assert plot.entry_of(ref, math.nan, lo, hi, lut) is None
 
 
-def test_weights_of_an_entry(pref):
-    assert [int(pref.depth_palette_weight(0xAA030201, j)) for j in range(3)] == [1, 2, 3]
-    assert dp.weights([0x00FF00, 0x7F0001]).tolist() == [[0, 255, 0], [1, 0, 127]]
+def test_weights_of_an_entry(ref):
+    assert [int(ref.plot_weight(0xAA030201, j)) for j in range(3)] == [1, 2, 3]
+    assert plot.weights([0x00FF00, 0x7F0001]).tolist() == [[0, 255, 0], [1, 0, 127]]
 
 
 # ---- 3. the stops' table ----------------------------------------------------------------------------------------------

@@ -8,24 +8,17 @@ four bytes, one per thread of the workgroup), none for the lock-step kernel, whi
 from the compiler's reported figures and the assembly's text only."""
 
 import os
-import re
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, at_most, compile_kernels
+from test_round_kernels_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, plot_instance_of
 
-STEPS = ([("ReferenceOrbit", "0"), ("ReferenceOrbit", "1")] + [("PowerOrbit", str(d)) for d in range(3, 9)]
-         + [("FormulaOrbit", str(f)) for f in range(1, 6)])
-INSTANCES = [(s, j) for s in STEPS for j in "01"]  # 13 steps x {sampled c, fixed c}: draw_depth.hip's instance set
+INSTANCES = [(s, j) for s in PLOT_STEPS for j in "01"]  # 13 steps x {sampled c, fixed c}: draw_depth.hip's instance set
 
 
 def instance_of(name):
     """(step, fixed c) of a mangled draw_depth_palette_kernel<Step, kJulia> (tests/test_depth_kernels_resources.py)."""
-    m = re.search(r"draw_depth_palette_kernelINS_\d+(ReferenceOrbit|PowerOrbit|FormulaOrbit)IL([bi])(\d+)EEELb(\d)EEEv"
-                  r"NS_16DepthPaletteArgsE$", name)
-    assert m, name
-    assert m.group(2) == ("b" if m.group(1) == "ReferenceOrbit" else "i"), name
-    return (m.group(1), m.group(3)), m.group(4)
+    return plot_instance_of(name, "draw_depth_palette_kernel", 1, "16DepthPaletteArgs")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

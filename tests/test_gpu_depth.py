@@ -1,7 +1,7 @@
 """The depth render (include/cudabrot_amd.h, "Depth render") on the GPU:
 
   1. every case three ways -- the product kernel (cb_debug_last_draw_kernel 18), the lock-step kernel (19), the CPU
-     restatement (tests/depth_reference.c) -- bit for bit on the N planes, the generator states and every counter but
+     restatement (tests/plot_reference.c) -- bit for bit on the N planes, the generator states and every counter but
      skipped_steps;
   2. against the projected and Julia renders, which are proven against the CPU on their own: no restatement involved;
   3. the renderer, its refusals and its image;
@@ -23,90 +23,31 @@ import os
 import numpy as np
 import pytest
 
-import depth_reference as depth
 import plot_harness
 import plot_reference as plot
 from conftest import read_state_file
-from plot_harness import INVALID, SAME, SQUARE, exe, omp_threads, planar_states, variant_of  # noqa: F401
+from plot_harness import C_JULIA, DEPTH_SHAPE, INVALID, IRRATIONAL_ROW, SAME, SQUARE  # noqa: F401
+from plot_harness import exe, omp_threads, planar_states, ref, variant_of  # noqa: F401
 from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
 PRODUCT, LOCKSTEP = 18, 19
-W, H, MAX, MIN, THREADS, LAUNCHES = 64, 48, 500, 20, 1000, (3, 50, 1)
-C_JULIA = (-0.8, 0.156)
-# the z_re axis turned by three angles: a unit row with four irrational entries
-IRRATIONAL_ROW = plot.rotate(plot.rotate(plot.rotate(plot.IDENTITY, "zr", "zi", 25.0), "zr", "cr", 40.0), "zi", "ci", 55.0)[0]
+W, H, MAX, MIN, THREADS, LAUNCHES = DEPTH_SHAPE
 
 
-@pytest.fixture(scope="module")
-def dref(tmp_path_factory):
-    return depth.load(tmp_path_factory.mktemp("depth_ref"))
+def gpu_launches(cb, variant, c=None, projection=plot.IDENTITY, depth=None, w=W, h=H, box=SQUARE):
+    """plot_harness.gpu_launches at this suite's shape: through cb_draw_buddhabrot_depth -> hist [slices, h, w], or,
+    depth None, the same launches through cb_draw_buddhabrot_projected, or cb_draw_buddhabrot_julia with a c -> [h, w]."""
+    return plot_harness.gpu_launches(cb, w, h, box, MAX, MIN, THREADS, LAUNCHES, variant, c, None, projection, depth)
 
 
-def gpu_depth(cb, d, variant, c=None, projection=plot.IDENTITY, w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN,
-              threads=THREADS, launches=LAUNCHES):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) through
-    cb_draw_buddhabrot_depth, d = (row, min, max, slices) -> (u64 hist [slices, h, w], counters dict,
-    cb_debug_last_draw_kernel, generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    dd = cb.Depth.make(*d)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    out = torch.zeros(dd.slices * w * h, dtype=torch.int64, device=dev)
-    for samples in launches:
-        cb.draw_buddhabrot_depth(dims, out.data_ptr(), it, projection, c, dd, states.data_ptr(), threads, samples,
-                                 counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    hist = out.cpu().numpy().view(np.uint64).reshape(dd.slices, h, w)
-    return hist, cnt, kernel, states.cpu().numpy().view(np.uint32)
-
-
-def gpu_plain(cb, variant, c=None, projection=plot.IDENTITY, w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN):
-    """The same launches through cb_draw_buddhabrot_projected, or cb_draw_buddhabrot_julia with a c."""
-    return plot_harness.gpu_launches(cb, w, h, box, max_iter, min_iter, THREADS, LAUNCHES, variant, c, None, projection)
-
-
-def three_ways(cb, dref, oracle, d, *, degree=2, ship=False, formula=0, c=None, projection=plot.IDENTITY, box=SQUARE):
-    """Product == lock-step == restatement, bit for bit on histogram [N, h, w], generator states and the counters of SAME
-    -> (the restatement's histogram, its counters, the product's counters)."""
-    st = oracle.init_states(1337, 0, THREADS)
-    extra = {}
-    want, wc = depth.draw(dref, W, H, MAX, MIN, THREADS, LAUNCHES, d, projection=projection, degree=degree, ship=ship,
-                          formula=formula, c=c, box=box, omp_threads=omp_threads(), states=st, extra=extra)
-    assert wc["samples"] == THREADS * sum(LAUNCHES) and int(want.sum()) == wc["increments"]
-    mandelbrot = c is None and not formula and degree == 2 and not ship
-    assert (wc["rejected"] > 0) == mandelbrot  # nothing is rejected but under the reference's own step on a sampled c
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = gpu_depth(cb, d, variant_of(cb, base, degree, ship, formula), c, projection, box=box)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert hist.shape == want.shape == (d[3], H, W) and np.array_equal(hist, want), kernel
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        level = cb.lib.cb_debug_interior_map_level()
-        if mandelbrot and base == cb.CB_KERNEL_DEFAULT:  # the interior map under cb_draw_buddhabrot_projected's rule
-            assert level >= 1, (kernel, level)
-        else:
-            assert level == 0, (kernel, level)
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    print("chunk_repeats", extra["chunk_repeats"], "product skipped_steps", got[PRODUCT]["skipped_steps"])
-    assert (got[PRODUCT]["skipped_steps"] > 0) == (mandelbrot or extra["chunk_repeats"] > 0)
-    return want, wc, got[PRODUCT]
+def three_ways(cb, ref, oracle, d, *, box=SQUARE, **kw):
+    """plot_harness.three_ways at this suite's shape -> (the restatement's histogram, its counters, the product's
+    counters)."""
+    r = plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), None, W, H, box, MAX, MIN, THREADS, LAUNCHES, depth=d,
+                                **kw)
+    return r.want, r.wc, r.product
 
 
 # ---- 1. three ways ------------------------------------------------------------------------------------------------------
@@ -127,16 +68,16 @@ CASES = {
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_product_lockstep_and_restatement_agree(cb, dref, oracle, name):
+def test_product_lockstep_and_restatement_agree(cb, ref, oracle, name):
     kw = dict(CASES[name])
     d = kw.pop("d")
-    want, wc, product = three_ways(cb, dref, oracle, d, **kw)
+    want, wc, product = three_ways(cb, ref, oracle, d, **kw)
     assert wc["recorded"] > 0 and 0 < wc["increments"] < wc["replay_steps"]  # some points are dropped
     assert sum(bool(p.any()) for p in want) >= 2  # and the rest spread over slices
     if name in ("mandelbrot_cr_inner", "mandelbrot_zi_inner_dyadic"):
         # points beyond both ends of the window: the wider window of the case before holds more at either end
         wider = CASES["mandelbrot_cr_5" if name == "mandelbrot_cr_inner" else "mandelbrot_zi_4_dyadic"]["d"]
-        outer, oc = depth.draw(dref, W, H, MAX, MIN, THREADS, LAUNCHES, wider, omp_threads=omp_threads())
+        outer, oc = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=wider, omp_threads=omp_threads())
         lo, hi = d[1], d[2]
         edges = wider[1] + np.arange(wider[3] + 1) * ((wider[2] - wider[1]) / wider[3])
         below = sum(int(outer[s].sum()) for s in range(wider[3]) if edges[s + 1] <= lo)
@@ -144,15 +85,15 @@ def test_product_lockstep_and_restatement_agree(cb, dref, oracle, name):
         assert below > 0 and above > 0 and oc["increments"] - wc["increments"] >= below + above
 
 
-def test_julia_on_a_c_axis_has_one_depth(cb, dref, oracle):
+def test_julia_on_a_c_axis_has_one_depth(cb, ref, oracle):
     """The depth of every point is that of the fixed c: all of them in one slice, or none in any."""
-    want, wc, _ = three_ways(cb, dref, oracle, ("cr", -2.0, 0.5, 5), c=C_JULIA)
+    want, wc, _ = three_ways(cb, ref, oracle, ("cr", -2.0, 0.5, 5), c=C_JULIA)
     s = int((C_JULIA[0] + 2.0) / 0.5)
     assert wc["increments"] > 0 and int(want[s].sum()) == wc["increments"]
-    want, wc, _ = three_ways(cb, dref, oracle, ("ci", 0.2, 1.0, 3), c=C_JULIA)  # c_im = 0.156 is below the window
+    want, wc, _ = three_ways(cb, ref, oracle, ("ci", 0.2, 1.0, 3), c=C_JULIA)  # c_im = 0.156 is below the window
     assert wc["increments"] == 0 and wc["recorded"] > 0 and wc["replay_steps"] > 0
     # a row over both: K_d from the fixed c moves the window of z_im
-    three_ways(cb, dref, oracle, ((0.0, 1.0, 0.5, -2.0), -1.0, 1.0, 4), c=C_JULIA)
+    three_ways(cb, ref, oracle, ((0.0, 1.0, 0.5, -2.0), -1.0, 1.0, 4), c=C_JULIA)
 
 
 # ---- 2. against the projected and Julia renders ---------------------------------------------------------------------------
@@ -173,8 +114,8 @@ def test_slices_of_a_covering_window_sum_to_the_plain_render(cb, name, base):
     kw = dict(COVERING[name])
     d = kw.pop("d")
     variant = variant_of(cb, base, kw.pop("degree", 2))
-    hist, cnt, kernel, states = gpu_depth(cb, d, variant, **kw)
-    plain, pc, plain_kernel, plain_states = gpu_plain(cb, variant, **kw)
+    hist, cnt, kernel, states = gpu_launches(cb, variant, depth=d, **kw)
+    plain, pc, plain_kernel, plain_states = gpu_launches(cb, variant, **kw)
     assert kernel == PRODUCT + base and plain_kernel in (8 + base, 10 + base, 12 + base)
     assert pc["increments"] > 0 and cnt["status"] == 0
     assert np.array_equal(hist.sum(axis=0), plain)  # also the check that the window covers
@@ -187,8 +128,8 @@ def test_slices_of_a_covering_window_sum_to_the_plain_render(cb, name, base):
 @pytest.mark.parametrize("base", [0, 1], ids=["product", "lockstep"])
 @pytest.mark.parametrize("c", [None, C_JULIA], ids=["projected", "julia"])
 def test_one_slice_of_a_covering_window_is_the_plain_render(cb, c, base):
-    hist, cnt, _, _ = gpu_depth(cb, ("cr", -16.0, 16.0, 1), base, c, plot.HOLOGRAM)
-    plain, pc, _, _ = gpu_plain(cb, base, c, plot.HOLOGRAM)
+    hist, cnt, _, _ = gpu_launches(cb, base, c, plot.HOLOGRAM, ("cr", -16.0, 16.0, 1))
+    plain, pc, _, _ = gpu_launches(cb, base, c, plot.HOLOGRAM)
     assert hist.shape == (1, H, W) and pc["increments"] > 0 and np.array_equal(hist[0], plain)
     assert {k: cnt[k] for k in SAME} == {k: pc[k] for k in SAME}
 
@@ -202,9 +143,9 @@ def test_the_slice_arithmetic_is_the_row_arithmetic(cb, window, base):
     lo, hi, n = window
     u_row, d_row = plot.HOLOGRAM[0], IRRATIONAL_ROW
     v_row = np.array([0.0, 1.0, 0.0, 0.0])
-    hist, cnt, _, _ = gpu_depth(cb, (d_row, lo, hi, n), base, None, np.vstack([u_row, v_row]), h=1,
-                                box=(-2.0, 2.0, -16.0, 16.0))
-    rows, rc, _, _ = gpu_plain(cb, base, None, np.vstack([u_row, d_row]), h=n, box=(-2.0, 2.0, lo, hi))
+    hist, cnt, _, _ = gpu_launches(cb, base, None, np.vstack([u_row, v_row]), (d_row, lo, hi, n), h=1,
+                                   box=(-2.0, 2.0, -16.0, 16.0))
+    rows, rc, _, _ = gpu_launches(cb, base, None, np.vstack([u_row, d_row]), h=n, box=(-2.0, 2.0, lo, hi))
     assert hist.shape == (n, 1, W) and rows.shape == (n, W)
     assert 0 < rc["increments"] < rc["replay_steps"] and np.array_equal(hist[:, 0, :], rows)
     assert {k: cnt[k] for k in SAME} == {k: rc[k] for k in SAME}
@@ -215,7 +156,7 @@ def test_the_slice_arithmetic_is_the_row_arithmetic(cb, window, base):
 
 @pytest.mark.parametrize("base", [0, 1], ids=["product", "lockstep"])
 @pytest.mark.parametrize("kind", ["projected", "julia_power_3"])
-def test_renderer_resumed_from_its_files_equals_one_run(cb, dref, oracle, base, kind):
+def test_renderer_resumed_from_its_files_equals_one_run(cb, ref, oracle, base, kind):
     c, degree = ((0.4, 0.0), 3) if kind == "julia_power_3" else (None, 2)
     d = ("zi", -1.0, 1.1, 6)
     variant = variant_of(cb, base, degree)
@@ -255,8 +196,8 @@ def test_renderer_resumed_from_its_files_equals_one_run(cb, dref, oracle, base, 
     assert wc["status"] == 0 and wc["increments"] > 100 and int(want.sum()) == wc["increments"]
     assert np.array_equal(got, want) and np.array_equal(got_states, want_states)
     st = oracle.init_states(1337, 0, THREADS)
-    ref_hist, rc = depth.draw(dref, W, H, 300, 10, THREADS, [150], d, projection=plot.HOLOGRAM, degree=degree, c=c,
-                              omp_threads=omp_threads(), states=st)
+    ref_hist, rc = plot.draw(ref, W, H, 300, 10, THREADS, [150], depth=d, projection=plot.HOLOGRAM, degree=degree, c=c,
+                             omp_threads=omp_threads(), states=st)
     assert np.array_equal(want, ref_hist) and {k: wc[k] for k in SAME} == rc
     assert np.array_equal(want_states.view(np.uint32), planar_states(st))
 
@@ -444,7 +385,7 @@ def parse_pgm_sequence(data):
     return images
 
 
-def test_cli_depth_images_buffer_and_stats(cb, exe, dref, tmp_path):
+def test_cli_depth_images_buffer_and_stats(cb, exe, ref, tmp_path):
     common = ["--depth", "cr:-2:0.5:3", "--plane", "zr,zi", "-w", "64", "-h", "48", "-m", "300", "-c", "20", "--passes", "2"]
     buf, pgm, host_pgm = str(tmp_path / "d.bin"), str(tmp_path / "d.pgm"), str(tmp_path / "host.pgm")
     r = run(exe, *common, "-s", buf, "--stats", "-o", pgm)
@@ -468,7 +409,7 @@ def test_cli_depth_images_buffer_and_stats(cb, exe, dref, tmp_path):
         assert np.array_equal(body, want[s]), s
     assert all(p.any() for p in hist)
     # and the buffer is the restatement's
-    ref_hist, rc = depth.draw(dref, 64, 48, 300, 20, 512 * 512, [100], ("cr", -2.0, 0.5, 3), omp_threads=omp_threads())
+    ref_hist, rc = plot.draw(ref, 64, 48, 300, 20, 512 * 512, [100], depth=("cr", -2.0, 0.5, 3), omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == rc and np.array_equal(hist, ref_hist)
 

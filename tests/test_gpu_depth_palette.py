@@ -1,7 +1,7 @@
 """The depth-palette render (include/cudabrot_amd.h, "Depth-palette render") on the GPU:
 
   1. every case three ways -- the product kernel (cb_debug_last_draw_kernel 20), the lock-step kernel (21), the CPU
-     restatement (tests/depth_palette_reference.c) -- bit for bit on the three planes, the generator states and every
+     restatement (tests/plot_reference.c) -- bit for bit on the three planes, the generator states and every
      counter but skipped_steps;
   2. against the depth render's entry point, which is proven against the CPU on its own: no restatement involved;
   3. the renderer, its refusals and its image;
@@ -22,26 +22,17 @@ import os
 import numpy as np
 import pytest
 
-import depth_palette_reference as dp
-import depth_reference as depth
+import plot_harness
 import plot_reference as plot
 from conftest import read_state_file
-from plot_harness import INVALID, SAME, SQUARE, exe, omp_threads, planar_states, variant_of  # noqa: F401
+from plot_harness import C_JULIA, DEPTH_SHAPE, INVALID, IRRATIONAL_ROW, NOT_INCREMENTS, SAME, SQUARE  # noqa: F401
+from plot_harness import exe, omp_threads, planar_states, ref, variant_of  # noqa: F401
 from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
 PRODUCT, LOCKSTEP = 20, 21
-W, H, MAX, MIN, THREADS, LAUNCHES = 64, 48, 500, 20, 1000, (3, 50, 1)
-C_JULIA = (-0.8, 0.156)
-# the z_re axis turned by three angles: a unit row with four irrational entries (tests/test_gpu_depth.py)
-IRRATIONAL_ROW = plot.rotate(plot.rotate(plot.rotate(plot.IDENTITY, "zr", "zi", 25.0), "zr", "cr", 40.0), "zi", "ci", 55.0)[0]
-NOT_INCREMENTS = [k for k in SAME if k != "increments"]
-
-
-@pytest.fixture(scope="module")
-def pref(tmp_path_factory):
-    return dp.load(tmp_path_factory.mktemp("depth_palette_ref"))
+W, H, MAX, MIN, THREADS, LAUNCHES = DEPTH_SHAPE
 
 
 def gradient(cb, n):
@@ -61,83 +52,25 @@ def sixteen_stops(cb):
     return cb.palette_from_stops(stops, 256)
 
 
-def launches_on_the_gpu(cb, d, lut, variant, c=None, projection=plot.IDENTITY, w=W, h=H, box=SQUARE, max_iter=MAX,
-                        min_iter=MIN, threads=THREADS, launches=LAUNCHES):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)), d = (row, min, max,
-    slices): through cb_draw_buddhabrot_depth_palette with a table -> u64 hist [3, h, w]; lut None through
-    cb_draw_buddhabrot_depth -> [slices, h, w].  Also the counters dict, cb_debug_last_draw_kernel and the generator states
-    as u32 planes."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    dd = cb.Depth.make(*d)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
-    planes = dd.slices if lut is None else 3
-    out = torch.zeros(planes * w * h, dtype=torch.int64, device=dev)
-    if lut is not None:
-        table = np.ascontiguousarray(lut, dtype=np.uint32)
-        d_lut = torch.from_numpy(table.view(np.int32).copy()).to(dev)
-    for samples in launches:
-        if lut is None:
-            cb.draw_buddhabrot_depth(dims, out.data_ptr(), it, projection, c, dd, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), variant, stream)
-        else:
-            cb.draw_buddhabrot_depth_palette(dims, out.data_ptr(), it, projection, c, dd, d_lut.data_ptr(), table.size,
-                                             states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    hist = out.cpu().numpy().view(np.uint64).reshape(planes, h, w)
-    return hist, cnt, kernel, states.cpu().numpy().view(np.uint32)
+def gpu_launches(cb, d, lut, variant, c=None, projection=plot.IDENTITY):
+    """plot_harness.gpu_launches at this suite's shape, d = (row, min, max, slices): through
+    cb_draw_buddhabrot_depth_palette with a table -> hist [3, h, w]; lut None through cb_draw_buddhabrot_depth -> [slices,
+    h, w]."""
+    return plot_harness.gpu_launches(cb, W, H, SQUARE, MAX, MIN, THREADS, LAUNCHES, variant, c, None, projection, d, lut)
 
 
-def three_ways(cb, pref, oracle, d, lut, *, degree=2, ship=False, formula=0, c=None, projection=plot.IDENTITY, box=SQUARE):
-    """Product == lock-step == restatement, bit for bit on histogram [3, h, w], generator states and the counters of SAME
-    -> (the restatement's histogram, its counters, the depth restatement's N planes)."""
-    st = oracle.init_states(1337, 0, THREADS)
-    extra = {}
-    kw = dict(projection=projection, degree=degree, ship=ship, formula=formula, c=c, box=box, omp_threads=omp_threads())
-    want, wc = dp.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, lut, states=st, extra=extra, **kw)
-    assert wc["samples"] == THREADS * sum(LAUNCHES) and int(want.sum()) == wc["increments"]
-    mandelbrot = c is None and not formula and degree == 2 and not ship
-    assert (wc["rejected"] > 0) == mandelbrot  # nothing is rejected but under the reference's own step on a sampled c
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, states = launches_on_the_gpu(cb, d, lut, variant_of(cb, base, degree, ship, formula), c,
-                                                          projection, box=box)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert hist.shape == want.shape == (3, H, W) and np.array_equal(hist, want), kernel
-        assert np.array_equal(states, planar_states(st)), kernel
-        assert int(hist.sum()) == cnt["increments"]
-        level = cb.lib.cb_debug_interior_map_level()
-        if mandelbrot and base == cb.CB_KERNEL_DEFAULT:  # the interior map under cb_draw_buddhabrot_projected's rule
-            assert level >= 1, (kernel, level)
-        else:
-            assert level == 0, (kernel, level)
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    print("chunk_repeats", extra["chunk_repeats"], "product skipped_steps", got[PRODUCT]["skipped_steps"])
-    # the depth render's executed-work discount: nothing is skipped on account of a colour
-    assert (got[PRODUCT]["skipped_steps"] > 0) == (mandelbrot or extra["chunk_repeats"] > 0)
-    planes, vc = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, d, **kw)
-    assert np.array_equal(want, dp.combine(lut, planes)) and {k: vc[k] for k in NOT_INCREMENTS} == {k: wc[k] for k in NOT_INCREMENTS}
-    return want, wc, planes
+def three_ways(cb, ref, oracle, d, lut, **kw):
+    """plot_harness.three_ways at this suite's shape -> (the restatement's histogram, its counters, the depth
+    restatement's N planes)."""
+    r = plot_harness.three_ways(cb, ref, oracle, (PRODUCT, LOCKSTEP), None, W, H, SQUARE, MAX, MIN, THREADS, LAUNCHES,
+                                depth=d, lut=lut, **kw)
+    return r.want, r.wc, r.extra["planes"]
 
 
 def tells_planes_and_slices_apart(lut, planes):
     """Some weight is zero in a slice that receives points, and two slices with different entries receive points."""
     populated = [s for s in range(len(lut)) if planes[s].any()]
-    w = dp.weights(lut)
+    w = plot.weights(lut)
     assert any((w[s] == 0).any() for s in populated) and any(w[s].any() for s in populated)
     assert len({int(lut[s]) & 0xFFFFFF for s in populated}) >= 2, populated
 
@@ -157,52 +90,52 @@ CASES = {
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_product_lockstep_and_restatement_agree(cb, pref, oracle, name):
+def test_product_lockstep_and_restatement_agree(cb, ref, oracle, name):
     kw = dict(CASES[name])
     d = kw.pop("d")
     lut = gradient(cb, d[3])
-    want, wc, planes = three_ways(cb, pref, oracle, d, lut, **kw)
+    want, wc, planes = three_ways(cb, ref, oracle, d, lut, **kw)
     assert wc["recorded"] > 0 and wc["increments"] > 0 and int(planes.sum()) < wc["replay_steps"]  # some points are dropped
     assert all(p.any() for p in want)
     tells_planes_and_slices_apart(lut, planes)
     if name == "mandelbrot_cr_inner":  # points beyond both ends of the window: the wider window holds more at either end
         wider = CASES["mandelbrot_cr_5"]["d"]
-        outer, _ = depth.draw(pref, W, H, MAX, MIN, THREADS, LAUNCHES, wider, omp_threads=omp_threads())
+        outer, _ = plot.draw(ref, W, H, MAX, MIN, THREADS, LAUNCHES, depth=wider, omp_threads=omp_threads())
         edges = wider[1] + np.arange(wider[3] + 1) * ((wider[2] - wider[1]) / wider[3])
         assert sum(int(outer[s].sum()) for s in range(wider[3]) if edges[s + 1] <= d[1]) > 0
         assert sum(int(outer[s].sum()) for s in range(wider[3]) if edges[s] >= d[2]) > 0
 
 
-def test_256_slices_read_every_slot_of_the_staged_table(cb, pref, oracle):
+def test_256_slices_read_every_slot_of_the_staged_table(cb, ref, oracle):
     lut = sixteen_stops(cb)
     assert len({int(v) for v in lut}) > 200
     # |z| of a visited point stays below 8 + 2 sqrt 2; the window [-2, 2) holds the set's bulk: 1/64 per slice
-    want, wc, planes = three_ways(cb, pref, oracle, ("zr", -2.0, 2.0, 256), lut)
+    want, wc, planes = three_ways(cb, ref, oracle, ("zr", -2.0, 2.0, 256), lut)
     tells_planes_and_slices_apart(lut, planes)
     populated = [s for s in range(256) if planes[s].any()]
     print("populated slices", len(populated), populated[0], populated[-1])
     assert len(populated) >= 200 and populated[0] < 8 and populated[-1] > 247  # both ends of the table are read
 
 
-def test_one_slice(cb, pref, oracle):
+def test_one_slice(cb, ref, oracle):
     lut = gradient(cb, 1)
-    want, wc, planes = three_ways(cb, pref, oracle, ("ci", -0.3, 0.3, 1), lut)
+    want, wc, planes = three_ways(cb, ref, oracle, ("ci", -0.3, 0.3, 1), lut)
     assert planes[0].any() and np.array_equal(want[0], 255 * planes[0]) and not want[1].any()
     assert np.array_equal(want[2], 3 * planes[0])
 
 
-def test_julia_on_a_c_axis_has_one_colour_or_none(cb, pref, oracle):
+def test_julia_on_a_c_axis_has_one_colour_or_none(cb, ref, oracle):
     """The depth of every point is that of the fixed c: all of them take one entry, or none is in depth."""
     lut = np.array([0x010000, 0x000200, 0x0300FF, 0x040404, 0x050000], dtype=np.uint32)
-    want, wc, planes = three_ways(cb, pref, oracle, ("cr", -2.0, 0.5, 5), lut, c=C_JULIA)
+    want, wc, planes = three_ways(cb, ref, oracle, ("cr", -2.0, 0.5, 5), lut, c=C_JULIA)
     s = int((C_JULIA[0] + 2.0) / 0.5)  # 2: R 255, G 0, B 3
     assert int(planes[s].sum()) == int(planes.sum()) > 0
-    assert [int(want[j].sum()) for j in range(3)] == [int(x) * int(planes[s].sum()) for x in dp.weights(lut)[s]]
-    assert (dp.weights(lut)[s] == 0).any() and len(set(dp.weights(lut)[s].tolist())) == 3
-    want, wc, _ = three_ways(cb, pref, oracle, ("ci", 0.2, 1.0, 3), gradient(cb, 3), c=C_JULIA)  # c_im is below the window
+    assert [int(want[j].sum()) for j in range(3)] == [int(x) * int(planes[s].sum()) for x in plot.weights(lut)[s]]
+    assert (plot.weights(lut)[s] == 0).any() and len(set(plot.weights(lut)[s].tolist())) == 3
+    want, wc, _ = three_ways(cb, ref, oracle, ("ci", 0.2, 1.0, 3), gradient(cb, 3), c=C_JULIA)  # c_im is below the window
     assert wc["increments"] == 0 and wc["recorded"] > 0 and wc["replay_steps"] > 0
     # a row over both: K_d from the fixed c moves the window of z_im
-    want, wc, planes = three_ways(cb, pref, oracle, ((0.0, 1.0, 0.5, -2.0), -1.0, 1.0, 4), gradient(cb, 4), c=C_JULIA)
+    want, wc, planes = three_ways(cb, ref, oracle, ((0.0, 1.0, 0.5, -2.0), -1.0, 1.0, 4), gradient(cb, 4), c=C_JULIA)
     tells_planes_and_slices_apart(gradient(cb, 4), planes)
 
 
@@ -210,8 +143,8 @@ def test_bits_24_to_31_of_the_device_table_change_nothing(cb):
     d = ("cr", -2.0, 0.5, 5)
     lut = gradient(cb, 5)
     for base in (cb.CB_KERNEL_DEFAULT, cb.CB_KERNEL_SIMPLE):
-        clean, cc, _, cs = launches_on_the_gpu(cb, d, lut, base)
-        noisy, nc, _, ns = launches_on_the_gpu(cb, d, lut | np.uint32(0xA5000000), base)
+        clean, cc, _, cs = gpu_launches(cb, d, lut, base)
+        noisy, nc, _, ns = gpu_launches(cb, d, lut | np.uint32(0xA5000000), base)
         assert cc["increments"] > 0 and np.array_equal(clean, noisy) and cc == nc and np.array_equal(cs, ns)
 
 
@@ -234,7 +167,7 @@ def depth_planes(cb):
         d = kw.pop("d")
         degree = kw.pop("degree", 2)
         for base in (0, 1):
-            planes, cnt, kernel, states = launches_on_the_gpu(cb, d, None, variant_of(cb, base, degree), **kw)
+            planes, cnt, kernel, states = gpu_launches(cb, d, None, variant_of(cb, base, degree), **kw)
             assert kernel == 18 + base and cnt["status"] == 0
             planes.setflags(write=False)
             out[name, base] = (planes, cnt, states)
@@ -250,9 +183,9 @@ def test_planes_are_the_weighted_sums_of_the_depth_renders_planes(cb, depth_plan
     planes, vc, v_states = depth_planes[name, base]
     lut = gradient(cb, d[3])
     tells_planes_and_slices_apart(lut, planes)
-    hist, cnt, kernel, states = launches_on_the_gpu(cb, d, lut, variant, **kw)
+    hist, cnt, kernel, states = gpu_launches(cb, d, lut, variant, **kw)
     assert kernel == PRODUCT + base and cnt["status"] == 0
-    assert np.array_equal(hist, dp.combine(lut, planes))
+    assert np.array_equal(hist, plot.combine(lut, planes))
     assert cnt["increments"] == int(hist.sum()) > vc["increments"] > 0
     assert {k: cnt[k] for k in NOT_INCREMENTS} == {k: vc[k] for k in NOT_INCREMENTS}
     assert cnt["skipped_steps"] == vc["skipped_steps"]  # the same early-outs, the same map, nothing skipped for a colour
@@ -263,7 +196,7 @@ def test_planes_are_the_weighted_sums_of_the_depth_renders_planes(cb, depth_plan
         assert planes[s].any()
         one_hot = np.zeros(d[3], dtype=np.uint32)
         one_hot[s] = 1
-        hist, cnt, _, _ = launches_on_the_gpu(cb, d, one_hot, variant, **kw)
+        hist, cnt, _, _ = gpu_launches(cb, d, one_hot, variant, **kw)
         assert np.array_equal(hist[0], planes[s]) and not hist[1].any() and not hist[2].any()
         assert cnt["increments"] == int(planes[s].sum())
 
@@ -272,8 +205,8 @@ def test_planes_are_the_weighted_sums_of_the_depth_renders_planes(cb, depth_plan
 @pytest.mark.parametrize("c", [None, C_JULIA], ids=["projected", "julia"])
 def test_the_constant_table_with_one_slice_is_the_section_three_times(cb, c, base):
     d = ("zi", -0.3, 0.3, 1)
-    planes, vc, _, v_states = launches_on_the_gpu(cb, d, None, base, c, plot.HOLOGRAM)
-    hist, cnt, kernel, states = launches_on_the_gpu(cb, d, [0x010101], base, c, plot.HOLOGRAM)
+    planes, vc, _, v_states = gpu_launches(cb, d, None, base, c, plot.HOLOGRAM)
+    hist, cnt, kernel, states = gpu_launches(cb, d, [0x010101], base, c, plot.HOLOGRAM)
     assert kernel == PRODUCT + base and 0 < vc["increments"] < vc["replay_steps"]
     assert all(np.array_equal(hist[j], planes[0]) for j in range(3)) and cnt["increments"] == 3 * vc["increments"]
     assert {k: cnt[k] for k in NOT_INCREMENTS} == {k: vc[k] for k in NOT_INCREMENTS} and np.array_equal(states, v_states)
@@ -284,7 +217,7 @@ def test_the_constant_table_with_one_slice_is_the_section_three_times(cb, c, bas
 
 @pytest.mark.parametrize("base", [0, 1], ids=["product", "lockstep"])
 @pytest.mark.parametrize("kind", ["projected", "julia_power_3"])
-def test_renderer_resumed_from_its_files_equals_one_run(cb, pref, oracle, base, kind):
+def test_renderer_resumed_from_its_files_equals_one_run(cb, ref, oracle, base, kind):
     c, degree = ((0.4, 0.0), 3) if kind == "julia_power_3" else (None, 2)
     d = ("zi", -1.0, 1.1, 6)
     lut = gradient(cb, 6)
@@ -329,8 +262,8 @@ def test_renderer_resumed_from_its_files_equals_one_run(cb, pref, oracle, base, 
     assert wc["status"] == 0 and wc["increments"] > 100 and int(want.sum()) == wc["increments"]
     assert np.array_equal(got, want) and np.array_equal(got_states, want_states)
     st = oracle.init_states(1337, 0, THREADS)
-    ref_hist, rc = dp.draw(pref, W, H, 300, 10, THREADS, [150], d, lut, projection=plot.HOLOGRAM, degree=degree, c=c,
-                           omp_threads=omp_threads(), states=st)
+    ref_hist, rc = plot.draw(ref, W, H, 300, 10, THREADS, [150], depth=d, lut=lut, projection=plot.HOLOGRAM, degree=degree,
+                             c=c, omp_threads=omp_threads(), states=st)
     assert np.array_equal(want, ref_hist) and {k: wc[k] for k in SAME} == rc
     assert np.array_equal(want_states.view(np.uint32), planar_states(st))
 
@@ -541,7 +474,7 @@ def read_ppm(path, w, h):
     return data, np.frombuffer(data, dtype=">u2", offset=len(header)).reshape(h, w, 3)
 
 
-def test_cli_image_buffer_stats_and_kernels(cb, exe, pref, tmp_path):
+def test_cli_image_buffer_stats_and_kernels(cb, exe, ref, tmp_path):
     common = ["--depth", "cr:-2:0.5:5", "--depth-palette", STOPS_TEXT, "-g", "2.2", "-w", "64", "-h", "48", "-m", "300",
               "-c", "20", "--passes", "2"]
     lut = cb.palette_from_stops(STOPS, 5)
@@ -563,7 +496,8 @@ def test_cli_image_buffer_stats_and_kernels(cb, exe, pref, tmp_path):
     with open(host_ppm, "rb") as f:
         assert f.read() == data  # the reference's host loop gives the same file
     # and the buffer is the restatement's
-    ref_hist, rc = dp.draw(pref, 64, 48, 300, 20, 512 * 512, [100], ("cr", -2.0, 0.5, 5), lut, omp_threads=omp_threads())
+    ref_hist, rc = plot.draw(ref, 64, 48, 300, 20, 512 * 512, [100], depth=("cr", -2.0, 0.5, 5), lut=lut,
+                             omp_threads=omp_threads())
     stats = json.loads(lines[-1])
     assert stats["status"] == 0 and {k: stats[k] for k in SAME} == rc and np.array_equal(hist, ref_hist)
     # --kernel picks the kernel: the product kernel (20) consults the interior map and skips steps, the lock-step kernel

@@ -1,6 +1,7 @@
 """The Julia render (include/cudabrot_amd.h, "Julia render") without a GPU, and with it every setting of the plotted
 renders' one CPU restatement (tests/plot_reference.c): pinned to a pure-Python restatement of the definitions on the
-oracle's generator -- a fixed and a sampled c, with and without rejection, a table, every formula --, its step pinned to
+oracle's generator -- a fixed and a sampled c, with and without rejection, a table, every formula, a depth with and
+without its table --, its step pinned to
 z^d + c in exact rational arithmetic, and its independence of the OpenMP thread count."""
 
 import ctypes as C
@@ -54,12 +55,16 @@ def py_step(cr, ci, r, i, degree=2, ship=False, formula=0):
 
 
 def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, p, states, c=None, degree=2, ship=False, formula=0,
-            lut=None, reject=False):
+            lut=None, reject=False, depth=None, notes=None):
     """The definition, sample by sample, on the oracle's generator -> (hist, counters).  c None: c is the sample; reject:
-    the oracle's two shortcuts drop the sample; lut: three planes of the entry's bytes."""
+    the oracle's two shortcuts drop the sample; lut: three planes of the entry's bytes; depth = (row, min, max, N): N
+    planes, a point in the plane of its slice and none outside the window -- or, with lut, three planes of the bytes of
+    the slice's entry.  A given dict `notes` receives the on-canvas points dropped for their depth and the slices hit."""
     d = oracle.make_dims(w, h, *box)
-    hist = np.zeros((h, w) if lut is None else (3, h, w), dtype=np.uint64)
+    row_d, lo, hi, slices = (None, 0.0, 0.0, 0) if depth is None else (plot.row_of(depth[0]),) + tuple(depth[1:])
+    hist = np.zeros((3, h, w) if lut is not None else (h, w) if depth is None else (slices, h, w), dtype=np.uint64)
     planes = hist.reshape(-1, h, w)
+    dropped, hit = 0, set()
     cnt = dict.fromkeys(plot.COUNTER_NAMES, 0)
     for t in range(threads):
         g = oracle.Xorwow.from_buffer(states, t * states.dtype.itemsize)
@@ -86,10 +91,10 @@ def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, p, states, 
                 cnt["too_fast"] += 1
                 continue
             cnt["recorded"] += 1
-            entry = 1 if lut is None else int(lut[k])
-            weights = [(entry >> (8 * j)) & 255 for j in range(len(planes))]
+            entry = 1 if lut is None or depth is not None else int(lut[k])  # a table by escape index
             ku = fma(p[2], cr, p[3] * ci)
             kv = fma(p[6], cr, p[7] * ci)
+            kd = 0.0 if depth is None else fma(row_d[2], cr, row_d[3] * ci)
             r, i = sr, si
             for _ in range(k + 1):
                 r, i, _ = py_step(cr, ci, r, i, degree, ship, formula)
@@ -99,10 +104,27 @@ def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, p, states, 
                 if u < d.min_real or v < d.min_imag:
                     continue
                 col, row = int((u - d.min_real) / d.delta_real), int((v - d.min_imag) / d.delta_imag)
-                if 0 <= col < w and 0 <= row < h:
-                    for j, weight in enumerate(weights):
-                        planes[j, row, col] += weight
+                if not (0 <= col < w and 0 <= row < h):
+                    continue
+                first = 0
+                if depth is not None:
+                    dd = fma(row_d[0], r, fma(row_d[1], i, kd))
+                    s = -1 if dd < lo else int((dd - lo) / ((hi - lo) / float(slices)))
+                    if not 0 <= s < slices:
+                        dropped += 1
+                        continue
+                    hit.add(s)
+                    if lut is None:
+                        first = s
+                    else:
+                        entry = int(lut[s]) & 0xFFFFFF  # a table by slice
+                for j in range(3):
+                    weight = (entry >> (8 * j)) & 255
+                    if weight:
+                        planes[first + j, row, col] += weight
                         cnt["increments"] += weight
+    if notes is not None:
+        notes.update(dropped_for_depth=dropped, slices=hit)
     return hist, cnt
 
 
@@ -111,7 +133,11 @@ def py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, p, states, 
 # from the fixed c are part of what is compared.  Then one case per other axis: the sampled c with the product's
 # rejection and without any, a table on either source of c, each formula, and a formula with a fixed c and a table.  Each
 # was checked with py_draw to record and plot something (to reject something, to fill two planes) before it was fixed.
+# Then the two sinks of a depth: without a table on a sampled c with rejection and on a fixed c, with a table on a sampled
+# c (an irrational row) and under a formula.  Their windows are cut inside the set, so that on-canvas points fall outside
+# them, and every entry of their tables lacks a colour; the test asserts both, and that two slices are hit.
 C_JULIA = (-0.8, 0.156)
+SLICE_TABLE = np.array([0x0000FF, 0x00FF00, 0x030000, 0x000201, 0x7F0001, 0x00FF00], dtype=np.uint32)
 TINY = {
     "z2": dict(c=C_JULIA),
     "z2_hologram": dict(c=C_JULIA, projection=plot.HOLOGRAM),
@@ -128,6 +154,10 @@ TINY = {
     "perpendicular": dict(formula=4),
     "celtic_tricorn": dict(formula=5),
     "tricorn_fixed_c_table": dict(formula=1, c=C_JULIA, lut=plot.demo_table(200), projection=plot.HOLOGRAM),
+    "depth_sampled_rejecting": dict(depth=("cr", -1.5, 0.4, 5), reject=True),
+    "depth_fixed_c": dict(c=C_JULIA, depth=("zi", -0.5, 0.6, 4)),
+    "depth_table_sampled": dict(depth=(plot.HOLOGRAM[1], -0.7, 0.9, 6), lut=SLICE_TABLE, reject=True),
+    "depth_table_tricorn": dict(formula=1, depth=("zr", -1.0, 0.5, 5), lut=SLICE_TABLE[:5]),
 }
 
 
@@ -140,7 +170,9 @@ def test_c_restatement_is_the_python_restatement(ref, oracle, case):
     p = kw.pop("projection", plot.IDENTITY)
     reject = kw.pop("reject", False)
     own = oracle.init_states(1337, 0, threads)
-    want, wc = py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, plot.matrix(p), own, reject=reject, **kw)
+    notes = {}
+    want, wc = py_draw(oracle, w, h, box, max_iter, min_iter, threads, samples, plot.matrix(p), own, reject=reject,
+                       notes=notes, **kw)
     states = oracle.init_states(1337, 0, threads)
     # reject=True is what the product's rule (reject=None) gives in those cases: that rule is part of what is compared
     hist, cnt = plot.draw(ref, w, h, max_iter, min_iter, threads, [samples], projection=p, box=box, states=states,
@@ -150,6 +182,11 @@ def test_c_restatement_is_the_python_restatement(ref, oracle, case):
     assert wc["rejected"] + wc["never_escaped"] + wc["too_fast"] + wc["recorded"] == wc["samples"]
     if "lut" in kw:
         assert sum(bool(plane.any()) for plane in want) >= 2
+    if "depth" in kw:  # points in two slices at least, and points on the canvas that are dropped for their depth alone
+        assert len(notes["slices"]) >= 2 and notes["dropped_for_depth"] > 0
+        assert want.shape == ((3, h, w) if "lut" in kw else (kw["depth"][3], h, w))
+    if "depth" in kw and "lut" in kw:  # a slice that receives points has a weight of zero
+        assert any((plot.weights(kw["lut"])[s] == 0).any() for s in notes["slices"])
     assert cnt == wc
     assert hist.shape == want.shape and np.array_equal(hist, want)
     assert states.tobytes() == own.tobytes()

@@ -7,11 +7,10 @@ no scratch, no AGPRs and no LDS for every instance, at most 128 VGPRs and at lea
 stated on its own below.  Judged from the compiler's reported figures and the assembly's text only."""
 
 import os
-import re
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, at_most, compile_kernels
+from test_round_kernels_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, plot_instance_of
 
 LOCKSTEP = ["draw_project_simple_kernel", "draw_power_simple_kernel", "draw_julia_simple_kernel",
             "draw_palette_simple_kernel", "draw_formula_simple_kernel"]
@@ -25,24 +24,21 @@ FAMILIES = {
     "palette": (lambda s, j, p: s[0] != "FormulaOrbit" and p == "1", "draw_palette_simple_kernel", at_most(128, 4)),
     "formula": (lambda s, j, p: s[0] == "FormulaOrbit", "draw_formula_simple_kernel", at_most(128, 4)),
 }
-STEPS = [("ReferenceOrbit", "0"), ("ReferenceOrbit", "1")] + [("PowerOrbit", str(d)) for d in range(3, 9)]
+STEPS = PLOT_STEPS[:8]  # without a formula
 # the instances of each family, as the render's own file instantiated them
 INSTANCES = {
     "projected": [(s, "0", "0") for s in STEPS[:2]],                          # <ship> x 2
     "Multibrot": [(s, "0", "0") for s in STEPS[2:]],                          # one per degree
     "Julia": [(s, "1", "0") for s in STEPS],                                  # Mandelbrot step, Burning Ship, degrees 3 .. 8
     "palette": [(s, j, "1") for s in STEPS for j in "01"],                    # those eight x {sampled c, fixed c}
-    "formula": [(("FormulaOrbit", str(f)), j, p) for f in range(1, 6) for j in "01" for p in "01"],  # five codes x 2 x 2
+    "formula": [(s, j, p) for s in PLOT_STEPS[8:] for j in "01" for p in "01"],  # five codes x 2 x 2
 }
 
 
 def instance_of(name):
-    """(step, fixed c, table) of a mangled draw_plot_kernel<Step, kJulia, kPalette>: Step is ReferenceOrbit<bool> (ILb.E),
-    PowerOrbit<int> or FormulaOrbit<int> (ILi.E); Lb0E sampled c / one plane, Lb1E fixed c / the table."""
-    m = re.search(r"draw_plot_kernelINS_\d+(ReferenceOrbit|PowerOrbit|FormulaOrbit)IL([bi])(\d+)EEELb(\d)ELb(\d)EEEvNS_8PlotArgsE$", name)
-    assert m, name
-    assert m.group(2) == ("b" if m.group(1) == "ReferenceOrbit" else "i"), name
-    return (m.group(1), m.group(3)), m.group(4), m.group(5)
+    """(step, fixed c, table) of a mangled draw_plot_kernel<Step, kJulia, kPalette>: Lb0E sampled c / one plane, Lb1E fixed
+    c / the table."""
+    return plot_instance_of(name, "draw_plot_kernel", 2, "8PlotArgs")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

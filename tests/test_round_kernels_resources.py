@@ -43,6 +43,23 @@ def compile_kernels(tmp_path, name):
         return kernels, f.read()
 
 
+# The steps every plotted family's product kernel is instantiated with (draw_plot.h, CB_PLOT_STEPS), as (template, its
+# argument): the reference's step and its Burning Ship variant, degrees 3 .. 8, formula codes 1 .. 5.  For the resource
+# tests of draw_plot.hip, draw_depth.hip and draw_depth_palette.hip.
+PLOT_STEPS = ([("ReferenceOrbit", "0"), ("ReferenceOrbit", "1")] + [("PowerOrbit", str(d)) for d in range(3, 9)]
+              + [("FormulaOrbit", str(f)) for f in range(1, 6)])
+
+
+def plot_instance_of(name, kernel, flags, args):
+    """(step, flag, ...) of a mangled kernel<Step, bool x flags>(args): Step is ReferenceOrbit<bool> (ILb.E), PowerOrbit<int>
+    or FormulaOrbit<int> (ILi.E); a flag is Lb0E or Lb1E; args is the argument type with its length, as mangled."""
+    m = re.search(kernel + r"INS_\d+(ReferenceOrbit|PowerOrbit|FormulaOrbit)IL([bi])(\d+)EEE" + r"Lb(\d)E" * flags + "EEvNS_"
+                  + args + "E$", name)
+    assert m, name
+    assert m.group(2) == ("b" if m.group(1) == "ReferenceOrbit" else "i"), name
+    return ((m.group(1), m.group(3)),) + m.groups()[3:]
+
+
 # file -> (product kernel, its instances, its bar, lock-step kernel, its bar, kernels in the file)
 FILES = {
     # <ship> x 2; the lock-step kernel takes the ship as a run-time flag
