@@ -1,20 +1,23 @@
 """What the plotted renders' suites share (projected, Multibrot, Julia, palette, formula, depth, depth palette) -- test
 infrastructure only: the fixtures for the restatement and the binary, the launches on the GPU, and the three-way
 comparison product kernel == lock-step kernel == CPU restatement (tests/plot_reference.c).  A fixture imported into a test
-module is a fixture of that module."""
+module is a fixture of that module.
+
+The launch scaffolding itself -- buffers, generators, the launches and the read-back -- is tools/gpu_launches.py's,
+imported as device_launches and shared with every other GPU suite and with tools/gpu_fuzz.py; gpu_launches here only
+picks the entry point and its arguments.  SAME, SQUARE, omp_threads, planar_states, run and gpu_run are re-exported from there for the plotted suites."""
 
 import collections
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import plot_reference as plot
+from device_launches import SAME, SQUARE, Launches, gpu_run, omp_threads, planar_states, run  # noqa: F401 (re-exported)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = plot.COUNTER_NAMES  # every counter but skipped_steps, the clocks and status
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
+assert SAME == plot.COUNTER_NAMES
 INVALID = 1  # hipErrorInvalidValue
 NOT_INCREMENTS = [k for k in SAME if k != "increments"]
 
@@ -25,11 +28,6 @@ DEPTH_SHAPE = 64, 48, 500, 20, 1000, (3, 50, 1)  # w, h, max_iter, min_iter, thr
 C_JULIA = (-0.8, 0.156)
 # the z_re axis turned by three angles: a unit row with four irrational entries
 IRRATIONAL_ROW = plot.rotate(plot.rotate(plot.rotate(plot.IDENTITY, "zr", "zi", 25.0), "zr", "cr", 40.0), "zi", "ci", 55.0)[0]
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
 
 
 @pytest.fixture(scope="module")
@@ -45,21 +43,6 @@ def exe():
     return path
 
 
-def run(exe, *args, timeout=120, **kw):
-    """The binary where it touches no device, or ends at once on a box without one."""
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, **kw)
-
-
-def gpu_run(exe, *args):
-    """The binary where it renders."""
-    return run(exe, *args, timeout=600)
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
 def variant_of(cb, base, degree=2, ship=False, formula=0):
     return (base | (cb.CB_KERNEL_POWER(degree) if degree != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
             | (cb.CB_KERNEL_FORMULA(formula) if formula else 0))
@@ -73,50 +56,27 @@ def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, 
     with a c, else cb_draw_buddhabrot_projected, or, projection=None, the normal path: cb_draw_buddhabrot without workspace
     and carry -> (u64 hist [h, w], or [planes, h, w] with a table (3) or a depth (3 with its table, else slices), counters
     dict, cb_debug_last_draw_kernel, generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
     dd = None if depth is None else cb.Depth.make(*depth)
     assert lut is None if depth is not None else depth_lut is None  # a table by escape index under a depth is not defined
     lut = lut if depth is None else depth_lut
-    planes = 3 if lut is not None else 1 if depth is None else dd.slices
-    out = torch.zeros(planes * w * h, dtype=torch.int64, device=dev)
+    planes = 3 if lut is not None else None if depth is None else dd.slices
+    run = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, planes=planes,
+                   tables={} if lut is None else {"lut": lut})
+    args = dict(iterations=cb.IterationControl(max_iter, min_iter), projection=projection)
     if lut is not None:
-        table = np.ascontiguousarray(lut, dtype=np.uint32)
-        d_lut = torch.from_numpy(table.view(np.int32).copy()).to(dev)
-    for samples in launches:
-        if depth is not None and lut is not None:
-            cb.draw_buddhabrot_depth_palette(dims, out.data_ptr(), it, projection, c, dd, d_lut.data_ptr(), table.size,
-                                             states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
-        elif depth is not None:
-            cb.draw_buddhabrot_depth(dims, out.data_ptr(), it, projection, c, dd, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), variant, stream)
-        elif lut is not None:
-            cb.draw_buddhabrot_palette(dims, out.data_ptr(), it, projection, c, d_lut.data_ptr(), table.size,
-                                       states.data_ptr(), threads, samples, counters.data_ptr(), variant, stream)
-        elif c is not None:
-            cb.draw_buddhabrot_julia(dims, out.data_ptr(), it, projection, c, states.data_ptr(), threads, samples,
-                                     counters.data_ptr(), variant, stream)
-        elif projection is not None:
-            cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, projection, states.data_ptr(), threads, samples,
-                                         counters.data_ptr(), variant, stream)
-        else:
-            cb.draw_buddhabrot(dims, out.data_ptr(), it, states.data_ptr(), threads, samples, counters.data_ptr(), variant,
-                               stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    v = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(v[k]) for k, n in enumerate(names)}
-    hist = out.cpu().numpy().view(np.uint64)
-    hist = hist.reshape(h, w) if planes == 1 and depth is None else hist.reshape(planes, h, w)
-    return hist, cnt, kernel, states.cpu().numpy().view(np.uint32)
+        args.update(d_lut=run.tables["lut"].data_ptr(), n_entries=run.tables["lut"].numel())
+    if depth is not None:
+        entry = cb.draw_buddhabrot_depth if lut is None else cb.draw_buddhabrot_depth_palette
+        args.update(julia_c=c, depth=dd)
+    elif lut is not None or c is not None:
+        entry = cb.draw_buddhabrot_julia if lut is None else cb.draw_buddhabrot_palette
+        args.update(julia_c=c)
+    elif projection is not None:
+        entry = cb.draw_buddhabrot_projected
+    else:
+        entry = cb.draw_buddhabrot
+        del args["projection"]
+    return run.launches(entry, launches, variant, **args).read()
 
 
 # want, wc: the restatement's histogram and counters; product, lockstep: the two kernels' counters; extra: the

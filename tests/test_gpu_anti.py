@@ -8,24 +8,17 @@
 """
 
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import anti_reference as anti
+from device_launches import SAME, SQUARE, Launches, assert_same, gpu_run as run, omp_threads  # noqa: F401 (the edge suite's too)
+from plot_harness import exe  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 4, 5
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
 
 
 @pytest.fixture(scope="module")
@@ -36,42 +29,17 @@ def ref(tmp_path_factory):
 def gpu_anti(cb, w, h, box, max_iter, threads, passes, base, ship=False, *, seed=None, first=0, launches=None,
              min_iter=20, flags=0, hist0=None, counters0=None, no_counters=False, workspace=None, carry=None):
     """One launch of `passes` reference passes on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist
-    [h, w], counters dict, cb_debug_last_draw_kernel, generator states as bytes).
+    [h, w], counters dict, cb_debug_last_draw_kernel, generator states as u32 planes).
     seed, first: other generators; launches: samples per thread of each launch, one after another on the same states,
-    instead of one of passes x 50; flags: OR-ed into the variant; hist0 (u64 [h, w]) and counters0 (17 u64): what the
-    buffers hold before; no_counters: d_counters = NULL (the counters come back as zeros); workspace = (torch buffer,
-    bytes) and carry (torch buffer): passed to every launch."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    if hist0 is None:
-        hist = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    else:
-        hist = torch.from_numpy(np.ascontiguousarray(hist0, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
-    if counters0 is None:
-        counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    else:
-        counters = torch.from_numpy(np.ascontiguousarray(counters0, dtype=np.uint64).view(np.int64)).to(dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED if seed is None else seed, first, threads, states.data_ptr(), stream)
+    instead of one of passes x 50; flags: OR-ed into the variant; hist0 (u64 [h, w]) and counters0 (one u64 per counter):
+    what the buffers hold before; no_counters: d_counters = NULL (the counters come back as zeros); workspace = (torch
+    buffer, bytes) and carry (torch buffer): passed to every launch."""
+    seq = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, hist0=hist0, seed=seed, first=first,
+                   counters0=counters0, no_counters=no_counters, workspace=workspace or 0, carry=carry)
     variant = base | cb.CB_KERNEL_FLAG_ANTI | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0) | flags
-    ws_ptr, ws_bytes = (workspace[0].data_ptr(), workspace[1]) if workspace else (0, 0)
-    for samples in ([passes * cb.CB_SAMPLES_PER_THREAD] if launches is None else launches):
-        cb.draw_buddhabrot(dims, hist.data_ptr(), cb.IterationControl(max_iter, min_iter), states.data_ptr(), threads,
-                           samples, 0 if no_counters else counters.data_ptr(), variant, stream, ws_ptr, ws_bytes,
-                           carry.data_ptr() if carry is not None else 0)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(c[k]) for k, n in enumerate(names)}
-    return hist.cpu().numpy().view(np.uint64).reshape(h, w), cnt, kernel, states.cpu().numpy()
-
-
-def same(a, b):
-    return {k: a[k] for k in SAME} == {k: b[k] for k in SAME}
+    launches = [passes * cb.CB_SAMPLES_PER_THREAD] if launches is None else launches
+    return seq.launches(cb.draw_buddhabrot, launches, variant, flush=False,  # an anti launch defers nothing
+                        iterations=cb.IterationControl(max_iter, min_iter)).read()
 
 
 CANVASES = {
@@ -89,9 +57,8 @@ def test_lockstep_anti_equals_the_restatement(cb, ref, canvas, max_iter, threads
     hist, cnt, kernel, _ = gpu_anti(cb, w, h, box, max_iter, threads, 2, cb.CB_KERNEL_SIMPLE, ship)
     assert kernel == LOCKSTEP
     want, wc = anti.render(ref, w, h, max_iter, threads, 2, box=box, ship=ship, omp_threads=omp_threads())
-    assert cnt["status"] == 0 and cnt["skipped_steps"] == 0
-    assert same(cnt, wc), (cnt, wc)
-    assert np.array_equal(hist, want)
+    assert cnt["skipped_steps"] == 0
+    assert_same((hist, cnt), (want, wc))
     assert int(hist.sum()) == cnt["increments"]
 
 
@@ -109,9 +76,7 @@ def test_product_anti_equals_lockstep(cb, w, h, box, max_iter, threads, ship):
     p_hist, p_cnt, p_kernel, p_states = gpu_anti(cb, w, h, box, max_iter, threads, 2, cb.CB_KERNEL_DEFAULT, ship)
     l_hist, l_cnt, l_kernel, l_states = gpu_anti(cb, w, h, box, max_iter, threads, 2, cb.CB_KERNEL_SIMPLE, ship)
     assert (p_kernel, l_kernel) == (PRODUCT, LOCKSTEP)
-    assert p_cnt["status"] == 0 and l_cnt["status"] == 0
-    assert same(p_cnt, l_cnt), (p_cnt, l_cnt)
-    assert np.array_equal(p_hist, l_hist)
+    assert_same((p_hist, p_cnt), (l_hist, l_cnt))
     assert np.array_equal(p_states, l_states)  # both advance every generator by the same samples
     assert p_cnt["skipped_steps"] > 0 and l_cnt["skipped_steps"] == 0  # the cycles were compressed
     assert p_cnt["skipped_steps"] < p_cnt["iterate_steps"] + p_cnt["replay_steps"]
@@ -127,11 +92,9 @@ def test_renderer_sized_anti_launch(cb, ref):
         hist = r.read_histogram()
         cnt = r.read_counters().as_dict()
     want, wc = anti.render(ref, w, h, 200, cb.CB_DEFAULT_THREADS, 128, omp_threads=omp_threads())
-    assert cnt["status"] == 0
-    assert same(cnt, wc), (cnt, wc)
+    assert_same((hist.reshape(h, w), cnt), (want, wc))
     assert cnt["iterate_steps"] > 2 ** 32 and cnt["increments"] > 2 ** 32
     assert int(hist.sum()) == cnt["increments"]
-    assert np.array_equal(hist.reshape(h, w), want)
 
 
 def test_renderer_switches_between_normal_and_anti_passes(cb, ref, oracle):
@@ -154,18 +117,6 @@ def test_renderer_switches_between_normal_and_anti_passes(cb, ref, oracle):
     assert cnt["samples"] == c1["samples"] + c2["samples"] + c3["samples"]
     assert cnt["increments"] == c1["increments"] + c2["increments"] + c3["increments"]
     assert np.array_equal(hist, h1 + h2 + h3)
-
-
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
 
 
 def test_cli_anti_image_equals_the_restatement(exe, ref, oracle, tmp_path):

@@ -20,7 +20,8 @@ import pytest
 
 import anti_reference as anti
 from conftest import read_state_file
-from test_gpu_anti import CANVASES, LOCKSTEP, PRODUCT, SQUARE, gpu_anti, omp_threads, same
+from device_launches import SQUARE, Launches, assert_same, counter_names, omp_threads, planar_states
+from test_gpu_anti import CANVASES, LOCKSTEP, PRODUCT, gpu_anti
 
 pytestmark = pytest.mark.gpu
 
@@ -34,29 +35,21 @@ def ref(tmp_path_factory):
     return anti.load(tmp_path_factory.mktemp("anti_ref"))
 
 
-def device_bytes(st):
-    """The oracle's generator states in the layout of the device buffer: the planes x0 .. x4, d of n words each."""
-    words = np.concatenate([np.ascontiguousarray(st["x"].T).reshape(-1), st["d"]]).astype("<u4")
-    return words.view(np.uint8)
-
-
 def definition(ref, oracle, w, h, box, max_iter, threads, ship=False, seed=1337, first=0, samples=100):
     """One run of `samples` samples per thread -> (naive hist, naive counters, the compressed mode's skipped_steps, the
-    generator states afterwards as the device holds them)."""
+    generator states afterwards as the device's u32 planes)."""
     st = oracle.init_states(seed, first, threads)
     args = dict(box=box, ship=ship, omp_threads=omp_threads(), samples_per_thread=samples)
     hist, cnt = anti.render(ref, w, h, max_iter, threads, 1, mode=anti.NAIVE, states=st, **args)
     _, cc = anti.render(ref, w, h, max_iter, threads, 1, mode=anti.COMPRESSED, seed=seed, first_subsequence=first, **args)
-    return hist, cnt, cc["skipped_steps"], device_bytes(st)
+    return hist, cnt, cc["skipped_steps"], planar_states(st)
 
 
 def check(got, want, product):
     hist, cnt, kernel, states = got
     w_hist, w_cnt, w_skipped, w_states = want
     assert kernel == (PRODUCT if product else LOCKSTEP)
-    assert cnt["status"] == 0
-    assert same(cnt, w_cnt), (cnt, w_cnt)
-    assert np.array_equal(hist, w_hist)
+    assert_same((hist, cnt), (w_hist, w_cnt))
     assert int(hist.sum()) == cnt["increments"]
     # both follow one schedule (chunks of 60, the refined Brent saves), so the steps not executed are the same number
     assert cnt["skipped_steps"] == (w_skipped if product else 0), (cnt["skipped_steps"], w_skipped)
@@ -119,13 +112,13 @@ def test_three_launches_of_any_shape_equal_one_run_of_the_definition(cb, ref, or
 @pytest.mark.parametrize("base", ["product", "lockstep"])
 def test_a_launch_of_no_samples_changes_nothing(cb, oracle, base):
     hist0 = (np.arange(256 * 256, dtype=np.uint64) % 1000 + 1).reshape(256, 256)
-    counters0 = np.arange(1, 18, dtype=np.uint64) * 1000
+    counters0 = np.arange(1, len(counter_names(cb)) + 1, dtype=np.uint64) * 1000
     variant = cb.CB_KERNEL_DEFAULT if base == "product" else cb.CB_KERNEL_SIMPLE
     hist, cnt, _, states = gpu_anti(cb, 256, 256, SQUARE, 181, 1337, 0, variant, hist0=hist0, counters0=counters0,
                                     launches=[0])
     assert np.array_equal(hist, hist0)
     assert list(cnt.values()) == [int(v) for v in counters0]
-    assert np.array_equal(states, device_bytes(oracle.init_states(1337, 0, 1337)))
+    assert np.array_equal(states, planar_states(oracle.init_states(1337, 0, 1337)))
 
 
 # ---- B3: the contract of include/cudabrot_amd.h -------------------------------------------------------------------
@@ -156,8 +149,8 @@ def test_a_launch_adds_to_the_histogram_and_the_counters(cb, ref, oracle):
     w, h, box, m, threads = 300, 200, CANVASES["zoom"][2], 181, 1337
     want_hist, want_cnt, want_skipped, want_states = definition(ref, oracle, w, h, box, m, threads)
     hist0 = (np.arange(w * h, dtype=np.uint64) * 2654435761 % 100003).reshape(h, w)
-    counters0 = np.arange(1, 18, dtype=np.uint64) * 1000003
-    counters0[9] = 0  # status: flags, not a count
+    counters0 = np.arange(1, len(counter_names(cb)) + 1, dtype=np.uint64) * 1000003
+    counters0[counter_names(cb).index("status")] = 0  # flags, not a count
     hist, cnt, kernel, states = gpu_anti(cb, w, h, box, m, threads, 2, cb.CB_KERNEL_DEFAULT, hist0=hist0,
                                          counters0=counters0)
     assert kernel == PRODUCT
@@ -182,8 +175,9 @@ def test_min_escape_iterations_is_ignored(cb, base):
     runs = [gpu_anti(cb, 256, 256, SQUARE, 181, 1337, 2, variant, min_iter=c) for c in (0, 20, 10 ** 6)]
     assert runs[0][1]["recorded"] > 0
     for hist, cnt, kernel, states in runs[1:]:
-        assert np.array_equal(hist, runs[0][0]) and np.array_equal(states, runs[0][3])
-        assert same(cnt, runs[0][1]) and cnt["skipped_steps"] == runs[0][1]["skipped_steps"] and cnt["status"] == 0
+        assert np.array_equal(states, runs[0][3])
+        assert_same((hist, cnt), runs[0])
+        assert cnt["skipped_steps"] == runs[0][1]["skipped_steps"]
         assert kernel == runs[0][2]
 
 
@@ -196,16 +190,13 @@ def test_variants_that_do_not_take_the_anti_flag_are_refused(cb):
 
     w = h = 64
     threads = 256
-    dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(w, h)
     stream = torch.cuda.current_stream().cuda_stream
     # a good lock-step launch first: cb_debug_last_draw_kernel then says 5, and a refusal must leave it there
     _, _, kernel, _ = gpu_anti(cb, w, h, SQUARE, 13, threads, 1, cb.CB_KERNEL_SIMPLE)
     assert kernel == LOCKSTEP
-    hist = torch.full((2 * w * h,), 7, dtype=torch.int64, device=dev)
-    counters = torch.full((17,), 11, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), stream)
+    bufs = Launches(cb, dims, threads, planes=2)
+    hist, counters, states = bufs.out.fill_(7), bufs.counters.fill_(11), bufs.states
     torch.cuda.synchronize()
     states0 = states.clone()
     it = cb.IterationControl(181, 20)
@@ -257,11 +248,10 @@ def test_renderer_splits_anti_passes_into_several_launches(ref, oracle, tmp_path
     cnt = dict(zip([str(n) for n in got["names"]], [int(v) for v in got["counters"]]))
     want_hist, want_cnt, want_skipped, want_states = definition(ref, oracle, 300, 200, CANVASES["zoom"][2], 181, 1337,
                                                                 samples=250)
-    assert int(got["kernel"]) == PRODUCT and cnt["status"] == 0
-    assert same(cnt, want_cnt), (cnt, want_cnt)
+    assert int(got["kernel"]) == PRODUCT
+    assert_same((got["hist"], cnt), (want_hist, want_cnt))
     assert cnt["skipped_steps"] == want_skipped
-    assert np.array_equal(got["hist"], want_hist)
-    assert np.array_equal(got["states"], want_states)
+    assert np.array_equal(got["states"].view(np.uint32), want_states)
 
 
 def test_two_renderers_and_the_reduce_after_anti_passes(cb, ref, oracle):
@@ -288,8 +278,8 @@ def test_two_renderers_and_the_reduce_after_anti_passes(cb, ref, oracle):
     assert np.array_equal(first_hist + second_hist, whole)  # the two ranges are the one run of 2 t threads
     assert np.array_equal(second, second_hist) and np.array_equal(untouched, second_hist)
     assert np.array_equal(got, whole)
-    assert same(counters[0], first_cnt) and same(counters[1], second_cnt)
-    assert counters[0]["status"] == 0 and counters[1]["status"] == 0
+    assert_same((None, counters[0]), (None, first_cnt))
+    assert_same((None, counters[1]), (None, second_cnt))
 
 
 def test_binary_anti_on_two_ranks_equals_one_run_of_2t_threads(ref, tmp_path):

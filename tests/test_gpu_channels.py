@@ -4,42 +4,19 @@ once per channel): plane j of one fused run must equal a separate run with windo
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from device_launches import SQUARE as BOX, Launches
 
-BOX = (-2.0, 2.0, -2.0, 2.0)
+pytestmark = pytest.mark.gpu
 
 
 def _fused(cb, w, h, windows, t, passes, mode, box=BOX, per_launch=1):
-    import torch
-
-    dev = torch.device("cuda:0")
     dims = cb.FractalDimensions.make(w, h, *box)
-    k = len(windows)
-    states = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(k * h * w, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
     spt = 50 * per_launch
     ws_bytes = cb.scatter_workspace_bytes(dims, t, spt * 4, n_channels=len(windows)) if mode != "atomics" else 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    carry = torch.zeros(cb.carry_bytes(t), dtype=torch.uint8, device=dev) if mode == "carry" else None
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, t, states.data_ptr(), stream)
-
-    def launch(samples):
-        cb.draw_buddhabrot_channels(dims, hist.data_ptr(), windows, states.data_ptr(), t, samples, counters.data_ptr(),
-                                    cb.CB_KERNEL_DEFAULT, stream, ws.data_ptr() if ws_bytes else 0, ws_bytes,
-                                    carry.data_ptr() if carry is not None else 0)
-        if ws_bytes:
-            cb.flush_scatter_channels(dims, hist.data_ptr(), k, t, ws.data_ptr(), ws_bytes, stream)
-
-    for _ in range(passes // per_launch):
-        launch(spt)
-    if carry is not None:
-        launch(0)       # drain the carried orbits
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    return hist.cpu().numpy().view(np.uint64).reshape(k, h, w), cnt
+    seq = Launches(cb, dims, t, planes=len(windows), workspace=ws_bytes, carry=mode == "carry" or None)
+    seq.launches(cb.draw_buddhabrot_channels, [spt] * (passes // per_launch), drain="launch" if mode == "carry" else None,
+                 windows=windows)
+    return seq.read()[:2]
 
 
 WINDOWS = [
@@ -123,36 +100,21 @@ def test_four_planes_of_the_recipe_canvas_are_more_than_65536_tiles(cb):
     by the tests above; the oracle itself would need minutes for this size).  Compared on the device."""
     import torch
 
-    dev = torch.device("cuda:0")
     w, h, t, spt = 20000, 15000, 65536, 100
     box = (-2.0, 2.0, -1.5, 1.5)
     windows = [(3000, 1000), (1000, 200), (200, 20), (3000, 20)]     # the last one overlaps the others
     dims = cb.FractalDimensions.make(w, h, *box)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def states():
-        s = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-        cb.initialize_rng(1337, 0, t, s.data_ptr(), stream)
-        return s
-
-    planes = torch.zeros(len(windows) * w * h, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    ws_bytes = cb.scatter_workspace_bytes(dims, t, spt, n_channels=len(windows))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    st = states()
-    cb.draw_buddhabrot_channels(dims, planes.data_ptr(), windows, st.data_ptr(), t, spt, counters.data_ptr(),
-                                cb.CB_KERNEL_DEFAULT, stream, ws.data_ptr(), ws_bytes)
-    cb.flush_scatter_channels(dims, planes.data_ptr(), len(windows), t, ws.data_ptr(), ws_bytes, stream)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    assert int(c[9]) == 0
+    fused = Launches(cb, dims, t, planes=len(windows),
+                     workspace=cb.scatter_workspace_bytes(dims, t, spt, n_channels=len(windows)))
+    fused.launch(cb.draw_buddhabrot_channels, spt, windows=windows)
+    planes, c = fused.out, fused.read_counters()
+    assert c["status"] == 0
     total = 0
     for j, (m, cmin) in enumerate(windows):
-        one = torch.zeros(w * h, dtype=torch.int64, device=dev)
-        st = states()
-        cb.draw_buddhabrot(dims, one.data_ptr(), cb.IterationControl(m, cmin), st.data_ptr(), t, spt)
+        single = Launches(cb, dims, t, no_counters=True)
+        single.launch(cb.draw_buddhabrot, spt, iterations=cb.IterationControl(m, cmin))
         torch.cuda.synchronize()
-        assert torch.equal(planes[j * w * h:(j + 1) * w * h], one), "plane %d" % j
-        total += int(one.sum().item())
-        del one
-    assert total == int(c[7]) > 0       # `increments` counts all planes
+        assert torch.equal(planes[j * w * h:(j + 1) * w * h], single.out), "plane %d" % j
+        total += int(single.out.sum().item())
+        del single
+    assert total == c["increments"] > 0       # `increments` counts all planes

@@ -11,21 +11,12 @@ import numpy as np
 import pytest
 
 from conftest import STATE_HEADER_BYTES, read_state_file
+from device_launches import gpu_run as run
+from plot_harness import exe  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 T = 512 * 512  # the CLI always runs the reference's 512 x 512 threads (cudabrot.cu:20,23)
-
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    assert os.access(path, os.X_OK), "./cudabrot is not built"
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, **kw)
 
 
 @pytest.fixture(scope="module")

@@ -4,12 +4,13 @@ numpy one (tests/color_reference.py) on the same tone-mapped planes."""
 
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import color_reference as ref
+from device_launches import gpu_run as run
+from plot_harness import exe  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -97,17 +98,6 @@ def test_renderer_color_image_equals_host_compose_of_its_planes(cb):
 
 
 # ---- the binary ----
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    assert os.access(path, os.X_OK), "./cudabrot is not built"
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, **kw)
-
 
 WINDOWS = [(100, 20), (400, 100), (1500, 400)]
 

@@ -272,14 +272,11 @@ def test_renderer_refuses_a_depth_where_it_is_not_defined(cb):
 def test_depth_launches_refuse_what_they_do_not_define(cb):
     import torch
 
-    dev = torch.device("cuda", 0)
     threads = 256
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
-    buf = torch.zeros(5 * 64 * 64, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, threads, planes=5)
+    buf, counters, states = bufs.out, bufs.counters, bufs.states
     torch.cuda.synchronize()
     before = states.cpu().numpy().copy()
     good = (C.c_double * 8)(*cb.IDENTITY_PROJECTION)

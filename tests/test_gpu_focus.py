@@ -11,25 +11,18 @@ states and counters (all but skipped_steps):
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import focus_reference as focus
+from device_launches import SAME, SQUARE, Launches, assert_same, gpu_run as run, omp_threads, planar_states  # noqa: F401
+from plot_harness import exe  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAME = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 PRODUCT, LOCKSTEP = 6, 7
-SQUARE = (-2.0, 2.0, -2.0, 2.0)
 PROBE_LAUNCHES = [50] * 8  # 8 reference passes of 4096 threads: 1.6e6 samples
-
-
-def omp_threads():
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
 
 
 @pytest.fixture(scope="module")
@@ -37,51 +30,17 @@ def ref(tmp_path_factory):
     return focus.load(tmp_path_factory.mktemp("focus_ref"))
 
 
-def same(a, b):
-    return {k: a[k] for k in SAME} == {k: b[k] for k in SAME}
-
-
-def planar_states(states):
-    """The oracle's generator states (d, x[5]) as the library's six planes x0 .. x4, d."""
-    return np.concatenate([states["x"][:, j] for j in range(5)] + [states["d"]]).astype(np.uint32)
-
-
 def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, ship=False, level=0, cell_list=None,
                  probe=False):
     """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist [h, w]
     or, probe=True, the mask's u32 words; counters dict; cb_debug_last_draw_kernel; generator states as u32 planes)."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(w, h, *box)
-    it = cb.IterationControl(max_iter, min_iter)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
+    seq = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, words=focus.mask_words(level) if probe else None,
+                   tables={} if cell_list is None else {"cells": cell_list})
     variant = base | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
-    if probe:
-        out = torch.zeros(focus.mask_words(level), dtype=torch.int32, device=dev)
-    else:
-        out = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    cells = None
-    if cell_list is not None:
-        cells = torch.from_numpy(np.ascontiguousarray(cell_list, dtype=np.uint32).view(np.int32)).to(dev)
-    for samples in launches:
-        if probe:
-            cb.focus_probe(dims, it, states.data_ptr(), threads, samples, level, out.data_ptr(), counters.data_ptr(),
-                           variant, stream)
-        else:
-            cb.draw_buddhabrot_focus(dims, out.data_ptr(), it, states.data_ptr(), threads, samples, counters.data_ptr(),
-                                     variant, level, cells.data_ptr() if cells is not None else 0,
-                                     cells.numel() if cells is not None else 0, stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    names = [f[0] for f in cb.Counters._fields_]
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = {n: int(c[k]) for k, n in enumerate(names)}
-    result = out.cpu().numpy().view(np.uint32) if probe else out.cpu().numpy().view(np.uint64).reshape(h, w)
-    return result, cnt, kernel, states.cpu().numpy().view(np.uint32)
+    args = dict(iterations=cb.IterationControl(max_iter, min_iter), level=level)
+    if not probe and cell_list is not None:
+        args.update(d_cells=seq.tables["cells"].data_ptr(), n_cells=seq.tables["cells"].numel())
+    return seq.launches(cb.focus_probe if probe else cb.draw_buddhabrot_focus, launches, variant, **args).read()
 
 
 # ---- 1. the uniform source: a normal render through the focus kernels -------------------------------------------------
@@ -118,12 +77,10 @@ def test_uniform_source_equals_the_oracle(cb, oracle, canvas, max_iter, min_iter
 def test_focus_launches_refuse_what_they_do_not_define(cb):
     import torch
 
-    dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
-    buf = torch.zeros(1 << 16, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(64), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, 64, states.data_ptr(), 0)
+    bufs = Launches(cb, dims, 64, planes=16)  # 1 << 16 words
+    buf, states = bufs.out, bufs.states
     torch.cuda.synchronize()
     draw = cb.lib.cb_draw_buddhabrot_focus
     args = (C.byref(dims), buf.data_ptr(), C.byref(it), states.data_ptr(), 64, 1, None)
@@ -167,9 +124,8 @@ def test_probe_equals_the_restatement(cb, probed, name, level, m, c):
     for base, kernel_id in ((cb.CB_KERNEL_SIMPLE, LOCKSTEP), (cb.CB_KERNEL_DEFAULT, PRODUCT)):
         mask, cnt, kernel, st = gpu_launches(cb, 256, 256, focus.BOXES[name], m, c, 4096, PROBE_LAUNCHES, base,
                                              level=level, probe=True)
-        assert kernel == kernel_id and cnt["status"] == 0
-        assert same(cnt, wc), (cnt, wc)
-        assert np.array_equal(mask, want)
+        assert kernel == kernel_id
+        assert_same((mask, cnt), (want, wc))
         assert states is None or np.array_equal(states, st)
         states = st
 
@@ -180,7 +136,7 @@ def test_probe_of_the_burning_ship_equals_the_restatement(cb, ref):
     assert 0 < int(np.unpackbits(want.view(np.uint8)).sum()) < 256 * 256
     for base in (cb.CB_KERNEL_SIMPLE, cb.CB_KERNEL_DEFAULT):
         mask, cnt, _, _ = gpu_launches(cb, 128, 128, box, 300, 10, 4000, [50, 137], base, ship=True, level=6, probe=True)
-        assert same(cnt, wc) and np.array_equal(mask, want)
+        assert_same((mask, cnt), (want, wc))
 
 
 # ---- 3. the focused draw ----------------------------------------------------------------------------------------------
@@ -194,11 +150,9 @@ def check_focused_draw(cb, ref, w, h, box, m, c, threads, launches, level, cells
     p_hist, p_cnt, p_kernel, p_states = gpu_launches(cb, w, h, box, m, c, threads, launches, cb.CB_KERNEL_DEFAULT, ship,
                                                      level, cells)
     assert (l_kernel, p_kernel) == (LOCKSTEP, PRODUCT)
-    assert l_cnt["status"] == 0 and p_cnt["status"] == 0 and l_cnt["skipped_steps"] == 0
-    assert same(l_cnt, wc), (l_cnt, wc)
-    assert np.array_equal(l_hist, want)
-    assert same(p_cnt, l_cnt), (p_cnt, l_cnt)
-    assert np.array_equal(p_hist, l_hist)
+    assert l_cnt["skipped_steps"] == 0
+    assert_same((l_hist, l_cnt), (want, wc))
+    assert_same((p_hist, p_cnt), (l_hist, l_cnt))
     assert np.array_equal(p_states, l_states)
     assert wc["samples"] == threads * sum(launches) and int(want.sum()) == wc["increments"]
     return wc, p_cnt
@@ -285,8 +239,7 @@ def test_renderer_set_focus_and_three_passes(cb, ref, base):
         assert cb.lib.cb_renderer_set_focus(r._h, 6, 8, 1, base) == 1
         assert cb.lib.cb_renderer_render_passes(r._h, 1, base | cb.CB_KERNEL_FLAG_ANTI) == 1
         assert cb.lib.cb_renderer_render_passes(r._h, 1, base | cb.CB_KERNEL_FLAG_BURNING_SHIP) == 1
-    assert cnt["status"] == 0 and same(cnt, wc), (cnt, wc)
-    assert np.array_equal(hist, want)
+    assert_same((hist, cnt), (want, wc))
     with cb.Renderer(dims, cb.IterationControl(m, c), device=0, n_threads=threads) as fresh:
         assert np.array_equal(before, fresh.read_rng_states())  # the probe ran on generators of its own
 
@@ -308,18 +261,6 @@ def test_renderer_refuses_focus_where_it_is_not_defined(cb):
         with pytest.raises(cb.CudabrotError) as e:
             r.set_focus(6, 2, 1)
         assert e.value.code == cb.CB_ERROR_FOCUS_EMPTY and "probe" in str(e.value)
-
-
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
 
 
 def box_flags(box):
@@ -383,7 +324,8 @@ def test_focused_samples_reach_the_canvas_more_often(cb, ref, probed, name):
     _, g_fc, _, _ = gpu_launches(cb, 256, 256, box, m, c, threads, launches, cb.CB_KERNEL_DEFAULT, level=level,
                                  cell_list=cells)
     _, g_nc, _, _ = gpu_launches(cb, 256, 256, box, m, c, threads, launches, cb.CB_KERNEL_DEFAULT)
-    assert same(g_fc, fc) and same(g_nc, nc)
+    assert_same((None, g_fc), (None, fc))
+    assert_same((None, g_nc), (None, nc))
     focused, normal = fc["increments"] / fc["samples"], nc["increments"] / nc["samples"]
     n2 = (4 << level) ** 2
     print("%s: %d of %d cells (plane / list = %.1f); increments per sample focused %.5f, normal %.5f: %.1f x"

@@ -185,13 +185,11 @@ def test_a_formula_is_refused_wherever_it_is_not_defined(cb):
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
     windows = (cb.IterationControl * 2)(cb.IterationControl(100, 20), cb.IterationControl(50, 5))
-    buf = torch.zeros(3 * 64 * 64, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
     mask = torch.zeros(cb.focus_mask_bytes(6), dtype=torch.uint8, device=dev)
     cells = torch.zeros(4, dtype=torch.int32, device=dev)
     d_lut = torch.full((100,), 0x010101, dtype=torch.int32, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, threads, planes=3)
+    buf, counters, states = bufs.out, bufs.counters, bufs.states
     torch.cuda.synchronize()
     before = states.cpu().numpy().copy()
     good = (C.c_double * 8)(*cb.IDENTITY_PROJECTION)

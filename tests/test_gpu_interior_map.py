@@ -11,7 +11,10 @@ cb_counters.status (CB_STATUS_INTERIOR_MAP)."""
 import numpy as np
 import pytest
 
+from device_launches import SAME, SQUARE, assert_same, renderer_render
+
 pytestmark = pytest.mark.gpu
+
 
 def built_level():
     """The level of the map kept in the tree (its header), which `make` embeds in the library."""
@@ -25,25 +28,11 @@ def built_level():
     return level
 
 
-KEYS = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments")
 WIDE = 2
 
 
-def render(cb, w, h, max_iter, threads, passes, box=(-2.0, 2.0, -2.0, 2.0), variant=None):
-    variant = cb.CB_KERNEL_DEFAULT if variant is None else variant
-    dims = cb.FractalDimensions.make(w, h, *box)
-    with cb.Renderer(dims, cb.IterationControl(max_iter, 20), n_threads=threads) as r:
-        r.render_passes(passes, variant)
-        hist = r.read_histogram()
-        cnt = r.read_counters().as_dict()
-    return hist, cnt, cb.lib.cb_debug_last_draw_kernel(), cb.lib.cb_debug_interior_map_level()
-
-
-def same(a, b):
-    assert a[1]["status"] == 0 and b[1]["status"] == 0
-    assert np.array_equal(a[0], b[0]), "histograms differ at %d pixels" % int((a[0] != b[0]).sum())
-    for k in KEYS:
-        assert a[1][k] == b[1][k], (k, a[1][k], b[1][k])
+def render(cb, w, h, max_iter, threads, passes, box=SQUARE, variant=None):
+    return renderer_render(cb, w, h, max_iter, 20, threads, passes, box=box, variant=variant)
 
 
 def test_the_map_is_built_loaded_and_used(cb, oracle, monkeypatch):
@@ -55,11 +44,11 @@ def test_the_map_is_built_loaded_and_used(cb, oracle, monkeypatch):
     monkeypatch.setenv("CUDABROT_AMD_NO_INTERIOR_MAP", "1")
     without = render(cb, *args)
     assert without[2] == WIDE and without[3] == 0
-    same(with_map, without)
+    assert_same(with_map, without)
     assert with_map[1]["skipped_steps"] > without[1]["skipped_steps"] > 0
     ref = oracle.render(512, 512, 2000, 20, 8192, 8, omp_threads=0)
     assert np.array_equal(with_map[0], ref[0])
-    for k in ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps", "increments"):
+    for k in SAME:
         assert with_map[1][k] == ref[1][k], (k, with_map[1][k], ref[1][k])
 
 
@@ -128,7 +117,7 @@ def test_ten_billion_samples_against_full_iteration(cb):
     assert product[1]["samples"] >= 10 ** 10
     full = render(cb, *args, variant=cb.CB_KERNEL_FULL_ITERATE)
     assert full[3] == 0 and full[1]["skipped_steps"] == 0
-    same(product, full)
+    assert_same(product, full)
     assert product[1]["skipped_steps"] > 0.8 * product[1]["iterate_steps"]
 
 
@@ -152,7 +141,7 @@ def test_windows_made_of_interior(cb, box):
     product = render(cb, *args, box=box)
     assert product[2] == WIDE and product[3] == built_level()
     full = render(cb, *args, box=box, variant=cb.CB_KERNEL_FULL_ITERATE)
-    same(product, full)
+    assert_same(product, full)
 
 
 def marked_cells_and_depths():

@@ -133,13 +133,11 @@ def test_edges(cb, ref, oracle, name):
 def test_julia_launches_refuse_what_they_do_not_define(cb):
     import torch
 
-    dev = torch.device("cuda", 0)
     threads = 256
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
-    buf = torch.zeros(64 * 64, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, threads, no_counters=True)
+    buf, states = bufs.out, bufs.states
     torch.cuda.synchronize()
     before = states.cpu().numpy().copy()
     good = (C.c_double * 8)(*cb.IDENTITY_PROJECTION)

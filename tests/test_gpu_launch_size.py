@@ -24,14 +24,12 @@ import numpy as np
 import pytest
 
 import bench  # read-only: the workload's constants and dump_outputs
+from device_launches import SAME, SQUARE as BOX, Launches, assert_same, omp_threads
 
 pytestmark = pytest.mark.gpu
 
-COUNTER_KEYS = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps",
-                "increments")
 WIDE, WAVE = 2, 1
 LOCKSTEP_PASSES = 8
-BOX = (-2.0, 2.0, -2.0, 2.0)
 RENDERER_PASSES = 128   # kRendererPassesPerLaunch (capi.hip)
 # the lock-step passes every test of this file asks for, as cumulative sums from the generators' start: one sweep per
 # (config, window) serves them all (C3: bench's timed steps [64, 192), the renderer's [0, 256) and [0, 135); C4:
@@ -46,48 +44,32 @@ def canvas(cb, name):
     return cb.FractalDimensions.make(w, h, *box), windows
 
 
-def omp_threads():
-    """The oracle's OpenMP workers: what the environment grants this command (never the machine's core count)."""
-    v = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
-    return int(v) if v.isdigit() and int(v) > 0 else 16
-
-
 class LockStep:
     """draw_simple_kernel over generator subsequences [first, first + threads) of seed 1337, one (max, min) window,
     into a u64 histogram and counters of its own (device tensors)."""
 
     def __init__(self, cb, dims, window, threads=bench.THREADS, first=0):
-        import torch
-
-        self.cb, self.torch, self.dims, self.threads = cb, torch, dims, threads
-        self.it = cb.IterationControl(*window)
-        dev = torch.device("cuda", 0)
-        self.hist = torch.zeros(dims.w * dims.h, dtype=torch.int64, device=dev)
-        self.counters = torch.zeros(17, dtype=torch.int64, device=dev)
-        self.states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-        self.stream = torch.cuda.current_stream().cuda_stream
-        cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, first, threads, self.states.data_ptr(), self.stream)
+        self.cb, self.it = cb, cb.IterationControl(*window)
+        self.seq = Launches(cb, dims, threads, first=first)
+        self.hist = self.seq.out
         self.seconds = 0.0
 
     def run(self, passes):
-        cb = self.cb
         t0 = time.perf_counter()
         while passes > 0:
             n = min(passes, LOCKSTEP_PASSES)
-            cb.draw_buddhabrot(self.dims, self.hist.data_ptr(), self.it, self.states.data_ptr(), self.threads,
-                               n * bench.SAMPLES_PER_PASS, self.counters.data_ptr(), cb.CB_KERNEL_SIMPLE, self.stream)
-            assert cb.lib.cb_debug_last_draw_kernel() == 3
-            self.torch.cuda.synchronize()
+            assert self.seq.launch(self.cb.draw_buddhabrot, n * bench.SAMPLES_PER_PASS, self.cb.CB_KERNEL_SIMPLE,
+                                   iterations=self.it) == 3
+            self.counter_values()  # synchronises: no launch of it queues behind another
             passes -= n
         self.seconds += time.perf_counter() - t0
         return self
 
     def counter_values(self):
-        return dict(zip(self.cb.Counters().as_dict().keys(),
-                        (int(v) for v in self.counters.cpu().numpy().view(np.uint64))))
+        return self.seq.read_counters()
 
     def host_histogram(self):
-        return self.hist.cpu().numpy().view(np.uint64).reshape(self.dims.h, self.dims.w)
+        return self.seq.read()[0]
 
 
 @pytest.fixture(scope="module")
@@ -105,7 +87,7 @@ def lockstep(cb):
         if key not in sweeps:
             dims, windows = canvas(cb, name)
             ls = LockStep(cb, dims, windows[plane])
-            snaps, done = {0: (None, {k: 0 for k in COUNTER_KEYS + ("status",)})}, 0
+            snaps, done = {0: (None, {k: 0 for k in SAME + ("status",)})}, 0
             for c in CHECKPOINTS[name]:
                 ls.run(c - done)
                 done = c
@@ -115,7 +97,7 @@ def lockstep(cb):
             del ls
             sweeps[key] = snaps
         (ha, ca), (hb, cb_) = sweeps[key][a], sweeps[key][b]
-        cnt = {k: cb_[k] - ca[k] for k in COUNTER_KEYS}
+        cnt = {k: cb_[k] - ca[k] for k in SAME}
         cnt["status"] = cb_["status"] | ca["status"]
         return (hb if ha is None else hb - ha), cnt
 
@@ -127,19 +109,6 @@ def lockstep(cb):
 def to_host(t, h, w, planes=1):
     a = t.cpu().numpy().view(np.uint64)
     return a.reshape(h, w) if planes == 1 else a.reshape(planes, h, w)
-
-
-def assert_same_histogram(got, ref, what):
-    if not np.array_equal(got, ref):
-        diff = np.argwhere(got != ref)
-        raise AssertionError("%s: histograms differ at %d pixels, first %r: %d vs %d" % (
-            what, len(diff), tuple(diff[0]), got[tuple(diff[0])], ref[tuple(diff[0])]))
-
-
-def assert_same_counters(got, ref, what, keys=COUNTER_KEYS):
-    assert got["status"] == 0 and ref["status"] == 0, (what, got["status"], ref["status"])
-    for k in keys:
-        assert got[k] == ref[k], (what, k, got[k], ref[k])
 
 
 # ---- 1. bench's dump against the lock-step kernel -------------------------------------------------------------------
@@ -247,10 +216,10 @@ def test_renderer_launches_equal_the_lock_step_kernel(cb, lockstep, name, split)
         # share the box, and so the samples that escape inside it)
         assert cnt["increments"] / launches > 2 ** 31
     ref, rc = lockstep(name, 0, 0, passes)
-    assert_same_counters(cnt, rc, name)
+    assert_same((None, cnt), (None, rc), what=name)
     assert cnt["samples"] == bench.THREADS * bench.SAMPLES_PER_PASS * passes
     w, h, _, _ = bench.CONFIGS[name]
-    assert_same_histogram(hist, to_host(ref, h, w), name)
+    assert_same((hist, None), (to_host(ref, h, w), None), what=name)
 
 
 def test_renderer_fused_c5_launch_equals_the_lock_step_kernel(cb, lockstep):
@@ -273,7 +242,7 @@ def test_renderer_fused_c5_launch_equals_the_lock_step_kernel(cb, lockstep):
         ref, rc = lockstep("C5", p, 0, passes)
         assert rc["status"] == 0 and rc["samples"] == cnt["samples"]
         increments += rc["increments"]
-        assert_same_histogram(hist[p], to_host(ref, h, w), "C5 window %r" % (bench.C5_WINDOWS[p],))
+        assert_same((hist[p], None), (to_host(ref, h, w), None), what="C5 window %r" % (bench.C5_WINDOWS[p],))
         del ref
     assert cnt["increments"] == increments
 
@@ -310,11 +279,9 @@ def test_slices_equal_the_oracle(cb, oracle, name, plane):
                                 first_subsequence=first, omp_threads=omp_threads())
         print("oracle %s: %.1f s" % (what, time.perf_counter() - t0))
         rc = dict(rc, status=0)
-        assert_same_counters(lcnt, rc, "lock-step " + what)
-        assert_same_histogram(lhist, ref, "lock-step " + what)
+        assert_same((lhist, lcnt), (ref, rc), what="lock-step " + what)
         del lhist
-        assert_same_counters(cnt, rc, what)
-        assert_same_histogram(got, ref, what)
+        assert_same((got, cnt), (ref, rc), what=what)
         del got, ref
 
 
@@ -327,37 +294,20 @@ def test_a_drained_carry_buffer_is_any_kernels_to_start_from(cb, first_wide):
     not) and its drain.  The drain leaves nothing carried, so the second kernel has nothing foreign to report
     (CB_STATUS_CARRY_FOREIGN is for orbits in flight: test_gpu_wide.py), and the sequence equals the lock-step kernel's
     over the same samples."""
-    import torch
-
     w, h, threads, max_iter, samples = 512, 512, 4096, 2000, 8 * bench.SAMPLES_PER_PASS
     dims = cb.FractalDimensions.make(w, h)
     order = [(20, WIDE), (1000, WAVE)] if first_wide else [(1000, WAVE), (20, WIDE)]
-    dev = torch.device("cuda", 0)
-    hist = torch.zeros(w * h, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    size = cb.scatter_workspace_bytes(dims, threads, samples)
-    ws = torch.empty(size, dtype=torch.uint8, device=dev)
-    carry = torch.zeros(cb.carry_bytes(threads), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(cb.CB_DEFAULT_RNG_SEED, 0, threads, states.data_ptr(), stream)
+    seq = Launches(cb, dims, threads, workspace=cb.scatter_workspace_bytes(dims, threads, samples), carry=True)
     for min_iter, kernel in order:
         it = cb.IterationControl(max_iter, min_iter)
         for n in (samples, 0):                  # the launch, then the drain of what it carried
-            cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), threads, n, counters.data_ptr(),
-                               cb.CB_KERNEL_DEFAULT, stream, ws.data_ptr(), size, carry.data_ptr())
-            assert cb.lib.cb_debug_last_draw_kernel() == kernel, (min_iter, n)
-            cb.flush_scatter(dims, hist.data_ptr(), threads, ws.data_ptr(), size, stream)
-            torch.cuda.synchronize()
-            status = int(counters.cpu().numpy().view(np.uint64)[9])
+            assert seq.launch(cb.draw_buddhabrot, n, iterations=it) == kernel, (min_iter, n)
+            status = seq.read_counters()["status"]
             assert status == 0, "status %d after the %s of min_iter %d" % (status, "drain" if n == 0 else "launch", min_iter)
-    torch.cuda.synchronize()
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in counters.cpu().numpy().view(np.uint64))))
-    got = hist.cpu().numpy().view(np.uint64).reshape(h, w)
+    got, cnt = seq.read()[:2]
 
     ls = LockStep(cb, dims, (max_iter, order[0][0]), threads=threads)
     ls.run(8)
     ls.it = cb.IterationControl(max_iter, order[1][0])
     ls.run(8)
-    assert_same_counters(cnt, ls.counter_values(), "carry handed over")
-    assert_same_histogram(got, ls.host_histogram(), "carry handed over")
+    assert_same((got, cnt), (ls.host_histogram(), ls.counter_values()), what="carry handed over")

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 
 from conftest import read_state_file
+from device_launches import gpu_run
+from plot_harness import exe  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,16 +37,9 @@ def _device_count():
 needs_two = pytest.mark.skipif(_device_count() < 2, reason="needs two visible GPUs (the driver's multi-GPU node)")
 
 
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    assert os.access(path, os.X_OK), "./cudabrot is not built"
-    return path
-
-
 def run(exe, *args, **kw):
     env = {k: v for k, v in os.environ.items() if k not in ("CUDABROT_AMD_FAKE_GPUS", "CUDABROT_AMD_FORCE_RCCL")}
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env, **kw)
+    return gpu_run(exe, *args, env=env, **kw)
 
 
 @needs_two

@@ -185,11 +185,9 @@ def test_palette_launches_refuse_what_they_do_not_define(cb):
     threads = 256
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
-    buf = torch.zeros(3 * 64 * 64, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
     d_lut = torch.full((100,), 0x010101, dtype=torch.int32, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, threads, planes=3)
+    buf, counters, states = bufs.out, bufs.counters, bufs.states
     torch.cuda.synchronize()
     before = states.cpu().numpy().copy()
     good = (C.c_double * 8)(*cb.IDENTITY_PROJECTION)

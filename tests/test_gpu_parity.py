@@ -7,38 +7,14 @@ Bar: bit-exact u64 histograms and exact workload counters on the same seeded RNG
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from device_launches import SAME, SQUARE as BOX, Launches, assert_same, planar_states, renderer_render
 
-BOX = (-2.0, 2.0, -2.0, 2.0)
-COUNTER_KEYS = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps",
-                "replay_steps", "increments")
+pytestmark = pytest.mark.gpu
 
 
 def gpu_render(cb, w, h, max_iter, min_iter, threads, passes, box=BOX, first=0, variant=None, fused=True):
-    variant = cb.CB_KERNEL_DEFAULT if variant is None else variant
-    dims = cb.FractalDimensions.make(w, h, box[0], box[1], box[2], box[3])
-    it = cb.IterationControl(max_iter, min_iter)
-    with cb.Renderer(dims, it, first_subsequence=first, n_threads=threads) as r:
-        if fused:
-            r.render_passes(passes, variant)
-        else:
-            for _ in range(passes):
-                r.render_passes(1, variant)
-        hist = r.read_histogram()
-        cnt = r.read_counters().as_dict()
-    return hist, cnt
-
-
-def assert_same(gpu, cpu):
-    gh, gc = gpu
-    ch, cc = cpu
-    assert gc["status"] == 0, "kernel reported an internal invariant violation: %r" % gc
-    if not np.array_equal(gh, ch):
-        diff = np.argwhere(gh != ch)
-        raise AssertionError("histograms differ at %d pixels, first %r: gpu %d cpu %d" % (
-            len(diff), tuple(diff[0]), gh[tuple(diff[0])], ch[tuple(diff[0])]))
-    for k in COUNTER_KEYS:
-        assert gc[k] == cc[k], "counter %s: gpu %d cpu %d" % (k, gc[k], cc[k])
+    return renderer_render(cb, w, h, max_iter, min_iter, threads, passes, box=box, first=first, variant=variant,
+                           fused=fused)[:2]
 
 
 def test_goldens_wave_kernel(cb, oracle, golden):
@@ -141,7 +117,7 @@ def test_two_shards_sum_to_one_big_run(cb):
     s0 = gpu_render(cb, 400, 400, 1000, 20, t, 2, first=0)
     s1 = gpu_render(cb, 400, 400, 1000, 20, t, 2, first=t)
     assert np.array_equal(whole[0], s0[0] + s1[0])
-    for k in COUNTER_KEYS:
+    for k in SAME:
         assert whole[1][k] == s0[1][k] + s1[1][k]
 
 
@@ -194,67 +170,25 @@ def test_carry_buffer_hands_in_flight_orbits_to_the_next_launch(cb, oracle, use_
     """With a carry buffer a launch stops when its samples are drawn; the orbits still in flight are
     finished by later launches, the last one being a drain (samples_per_thread = 0).  Only then do the
     histogram and the counters match the reference."""
-    import torch
-
-    dev = torch.device("cuda:0")
     w, h, t, launches = 384, 256, 4096, 5
     dims = cb.FractalDimensions.make(w, h)
+    seq = Launches(cb, dims, t, workspace=cb.scatter_workspace_bytes(dims, t, 100) if use_workspace else 0, carry=True)
     it = cb.IterationControl(5000, 20)
-    states = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(h * w, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    carry = torch.zeros(cb.carry_bytes(t), dtype=torch.uint8, device=dev)
-    ws_bytes = cb.scatter_workspace_bytes(dims, t, 100) if use_workspace else 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, t, states.data_ptr(), stream)
-
-    def launch(samples):
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), t, samples, counters.data_ptr(),
-                           cb.CB_KERNEL_DEFAULT, stream, ws.data_ptr() if ws_bytes else 0, ws_bytes, carry.data_ptr())
-        if ws_bytes:
-            cb.flush_scatter(dims, hist.data_ptr(), t, ws.data_ptr(), ws_bytes, stream)
-
-    for _ in range(launches):
-        launch(100)   # two reference passes per launch
-    torch.cuda.synchronize()
+    seq.launches(cb.draw_buddhabrot, [100] * launches, iterations=it)   # two reference passes per launch
     cpu, cc = oracle.render(w, h, 5000, 20, t, 2 * launches)
-    partial = hist.cpu().numpy().view(np.uint64).reshape(h, w)
-    c = counters.cpu().numpy().view(np.uint64)
-    assert int(c[0]) == cc["samples"]                              # every sample has been drawn ...
+    partial, c = seq.read()[:2]
+    assert c["samples"] == cc["samples"]                           # every sample has been drawn ...
     assert int(partial.sum()) < int(cpu.sum())                     # ... but some orbits are still in flight
     assert np.all(partial <= cpu)
-    launch(0)         # drain
-    torch.cuda.synchronize()
-    got = hist.cpu().numpy().view(np.uint64).reshape(h, w)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in counters.cpu().numpy().view(np.uint64))))
-    assert_same((got, cnt), (cpu, cc))
-    launch(0)         # a second drain finds nothing left
-    torch.cuda.synchronize()
-    assert np.array_equal(hist.cpu().numpy().view(np.uint64).reshape(h, w), cpu)
+    seq.launch(cb.draw_buddhabrot, 0, iterations=it)               # drain
+    assert_same(seq.read(), (cpu, cc))
+    seq.launch(cb.draw_buddhabrot, 0, iterations=it)               # a second drain finds nothing left
+    assert np.array_equal(seq.read()[0], cpu)
 
 
 def _torch_render(cb, w, h, max_iter, min_iter, t, passes, workspace_bytes, box=BOX):
-    import torch
-
-    dev = torch.device("cuda:0")
-    dims = cb.FractalDimensions.make(w, h, box[0], box[1], box[2], box[3])
-    it = cb.IterationControl(max_iter, min_iter)
-    states = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(h * w, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(workspace_bytes, 1), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, t, states.data_ptr(), stream)
-    for _ in range(passes):
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), t, 50, counters.data_ptr(),
-                           cb.CB_KERNEL_DEFAULT, stream, ws.data_ptr() if workspace_bytes else 0, workspace_bytes)
-        if workspace_bytes:
-            cb.flush_scatter(dims, hist.data_ptr(), t, ws.data_ptr(), workspace_bytes, stream)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    return hist.cpu().numpy().view(np.uint64).reshape(h, w), cnt
+    seq = Launches(cb, cb.FractalDimensions.make(w, h, *box), t, workspace=workspace_bytes)
+    return seq.launches(cb.draw_buddhabrot, [50] * passes, iterations=cb.IterationControl(max_iter, min_iter)).read()[:2]
 
 
 @pytest.mark.parametrize("workspace", ["suggested", "tiny", "one_region_short", "none"])
@@ -346,34 +280,18 @@ def test_chunked_stream_that_runs_out_of_chunks(cb, oracle, fraction):
 
 def test_low_level_entry_points_on_torch_memory(cb, oracle):
     """cb_initialize_rng / cb_draw_buddhabrot on caller-owned device memory (torch as the allocator)."""
-    import torch
-
-    dev = torch.device("cuda:0")
     t, w, h = 4096, 256, 256
-    dims = cb.FractalDimensions.make(w, h)
-    it = cb.IterationControl(300, 20)
-    states = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(h * w, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, t, states.data_ptr(), stream)
-    for _ in range(3):
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), t, 50, counters.data_ptr(),
-                           cb.CB_KERNEL_DEFAULT, stream)
-    torch.cuda.synchronize()
-    got = hist.cpu().numpy().view(np.uint64).reshape(h, w)
+    seq = Launches(cb, cb.FractalDimensions.make(w, h), t)
+    seq.launches(cb.draw_buddhabrot, [50] * 3, iterations=cb.IterationControl(300, 20))
+    got, c, _, st = seq.read()
     cpu, cc = oracle.render(w, h, 300, 20, t, 3)
     assert np.array_equal(got, cpu)
-    c = counters.cpu().numpy()
-    assert int(c[9]) == 0
-    assert int(c[0]) == cc["samples"] and int(c[7]) == cc["increments"]
+    assert c["status"] == 0
+    assert c["samples"] == cc["samples"] and c["increments"] == cc["increments"]
     # generator states after the run match the oracle's (planes x0..x4, d)
-    st = states.cpu().numpy().view(np.uint32).reshape(6, t)
     ost = oracle.init_states(1337, 0, t)
     oracle.render(w, h, 300, 20, t, 3, states=ost)
-    assert np.array_equal(st[5], ost["d"])
-    for k in range(5):
-        assert np.array_equal(st[k], ost["x"][:, k])
+    assert np.array_equal(st, planar_states(ost))
 
 
 def test_rng_states_round_trip_makes_a_true_resume(cb, oracle):
@@ -441,30 +359,11 @@ def test_full_size_configs_against_the_oracle(cb, oracle, name, w, h, max_iter, 
 def test_drain_flag_completes_in_flight_orbits_in_the_last_launch(cb, oracle):
     """CB_KERNEL_FLAG_DRAIN: with a carry buffer, the flagged launch draws its samples AND finishes every
     orbit in flight -- no separate drain launch."""
-    import torch
-
-    dev = torch.device("cuda:0")
     w, h, t, launches = 384, 320, 8192, 3
     dims = cb.FractalDimensions.make(w, h)
-    it = cb.IterationControl(1500, 20)
-    states = torch.empty(cb.rng_state_bytes(t), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(h * w, dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    carry = torch.zeros(cb.carry_bytes(t), dtype=torch.uint8, device=dev)
-    ws_bytes = cb.scatter_workspace_bytes(dims, t, 100)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, t, states.data_ptr(), stream)
-    for n in range(launches):
-        flag = cb.CB_KERNEL_FLAG_DRAIN if n + 1 == launches else 0
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), t, 100, counters.data_ptr(),
-                           cb.CB_KERNEL_DEFAULT | flag, stream, ws.data_ptr(), ws_bytes, carry.data_ptr())
-        cb.flush_scatter(dims, hist.data_ptr(), t, ws.data_ptr(), ws_bytes, stream)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    got = hist.cpu().numpy().view(np.uint64).reshape(h, w)
-    assert_same((got, cnt), oracle.render(w, h, 1500, 20, t, 2 * launches))
+    seq = Launches(cb, dims, t, workspace=cb.scatter_workspace_bytes(dims, t, 100), carry=True)
+    seq.launches(cb.draw_buddhabrot, [100] * launches, drain="flag", iterations=cb.IterationControl(1500, 20))
+    assert_same(seq.read(), oracle.render(w, h, 1500, 20, t, 2 * launches))
 
 
 def test_burning_ship_goldens_on_the_gpu(cb, oracle):

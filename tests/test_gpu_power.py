@@ -104,11 +104,10 @@ def test_a_degree_is_refused_wherever_it_is_not_defined(cb):
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
     windows = (cb.IterationControl * 2)(cb.IterationControl(100, 20), cb.IterationControl(50, 5))
-    buf = torch.zeros(2 * 64 * 64, dtype=torch.int64, device=dev)
     mask = torch.zeros(cb.focus_mask_bytes(6), dtype=torch.uint8, device=dev)
     cells = torch.zeros(4, dtype=torch.int32, device=dev)
-    states = torch.empty(cb.rng_state_bytes(threads), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, threads, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, threads, planes=2, no_counters=True)
+    buf, states = bufs.out, bufs.states
     torch.cuda.synchronize()
     before = states.cpu().numpy().copy()
     invalid = 1  # hipErrorInvalidValue

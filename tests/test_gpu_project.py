@@ -82,12 +82,10 @@ def test_identity_matrix_equals_the_normal_path(cb, case):
 def test_projected_launches_refuse_what_they_do_not_define(cb):
     import torch
 
-    dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(64, 64)
     it = cb.IterationControl(100, 20)
-    buf = torch.zeros(64 * 64, dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(64), dtype=torch.uint8, device=dev)
-    cb.initialize_rng(1337, 0, 64, states.data_ptr(), 0)
+    bufs = plot_harness.Launches(cb, dims, 64, no_counters=True)
+    buf, states = bufs.out, bufs.states
     torch.cuda.synchronize()
     draw = cb.lib.cb_draw_buddhabrot_projected
     good = (C.c_double * 8)(*cb.IDENTITY_PROJECTION)

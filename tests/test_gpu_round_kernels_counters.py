@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import plot_reference as plot
+from device_launches import Launches, counter_names
 
 pytestmark = pytest.mark.gpu
 
@@ -56,49 +57,33 @@ def digest(array):
 def run(cb, instance, ship):
     """The two launches of one product instance -> {"kernel", "counters" (all of cb_counters, in its order), "out" and "states"
     (digests of the histogram -- the probe: the mask -- and of the generator states)}."""
-    import torch
-
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(W, H, *BOX)
-    it = cb.IterationControl(MAX_ITER, MIN_ITER)
-    counters = torch.zeros(len(cb.Counters._fields_), dtype=torch.int64, device=dev)
-    states = torch.empty(cb.rng_state_bytes(THREADS), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(1337, 0, THREADS, states.data_ptr(), stream)
-    variant = cb.CB_KERNEL_DEFAULT | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
     probe = instance == "focus_uniform_mask"
-    out = torch.zeros((4 << LEVEL) ** 2 // 32 if probe else W * H, dtype=torch.int32 if probe else torch.int64, device=dev)
-    cells = torch.from_numpy(planted_cells(LEVEL).view(np.int32)).to(dev)
-    for samples in LAUNCHES:
-        common = (states.data_ptr(), THREADS, samples)
-        if instance == "anti":
-            cb.draw_buddhabrot(dims, out.data_ptr(), it, *common, counters.data_ptr(), variant | cb.CB_KERNEL_FLAG_ANTI,
-                               stream)
-        elif instance == "focus_cells_hist":
-            cb.draw_buddhabrot_focus(dims, out.data_ptr(), it, *common, counters.data_ptr(), variant, LEVEL,
-                                     cells.data_ptr(), cells.numel(), stream)
-        elif instance == "focus_uniform_hist":
-            cb.draw_buddhabrot_focus(dims, out.data_ptr(), it, *common, counters.data_ptr(), variant, 0, 0, 0, stream)
-        elif instance == "focus_uniform_mask":
-            cb.focus_probe(dims, it, *common, LEVEL, out.data_ptr(), counters.data_ptr(), variant, stream)
-        else:
-            cb.draw_buddhabrot_projected(dims, out.data_ptr(), it, PROJECTION, *common, counters.data_ptr(), variant,
-                                         stream)
-    kernel = cb.lib.cb_debug_last_draw_kernel()
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
+    seq = Launches(cb, cb.FractalDimensions.make(W, H, *BOX), THREADS, words=(4 << LEVEL) ** 2 // 32 if probe else None,
+                   tables={"cells": planted_cells(LEVEL)})
+    variant = cb.CB_KERNEL_DEFAULT | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
+    cells = seq.tables["cells"]
+    entry, args = {
+        "anti": (cb.draw_buddhabrot, {}),
+        "focus_cells_hist": (cb.draw_buddhabrot_focus, dict(level=LEVEL, d_cells=cells.data_ptr(), n_cells=cells.numel())),
+        "focus_uniform_hist": (cb.draw_buddhabrot_focus, {}),
+        "focus_uniform_mask": (cb.focus_probe, dict(level=LEVEL)),
+        "project": (cb.draw_buddhabrot_projected, dict(projection=PROJECTION)),
+    }[instance]
+    seq.launches(entry, LAUNCHES, variant | (cb.CB_KERNEL_FLAG_ANTI if instance == "anti" else 0),
+                 iterations=cb.IterationControl(MAX_ITER, MIN_ITER), **args)
+    out, cnt, kernel, states = seq.read()
     return {
         "kernel": int(kernel),
-        "counters": [int(x) for x in c],  # in cb_counters' order
-        "out": digest(out.cpu().numpy()),
-        "states": digest(states.cpu().numpy()),
+        "counters": list(cnt.values()),  # in cb_counters' order
+        "out": digest(out),
+        "states": digest(states),
     }
 
 
 @pytest.mark.parametrize("instance,ship", CASES, ids=["%s-%s" % (i, "ship" if s else "mandelbrot") for i, s in CASES])
 def test_round_kernels_reproduce_the_recorded_counters(cb, instance, ship):
     got = run(cb, instance, ship)
-    names = [f[0] for f in cb.Counters._fields_]
+    names = counter_names(cb)
     c = dict(zip(names, got["counters"]))
     print(instance, "ship" if ship else "mandelbrot", json.dumps(got))
     # the case tests something: the product kernel, and (uniform Mandelbrot samples) orbits retired at chunk boundaries

@@ -29,6 +29,7 @@ and demands identical histograms and counters.
                                                    (draw_depth_palette.hip) -- DEPTH's trials with a random table of N
                                                    entries (random weights with zeros among them, one colour, one-hot,
                                                    noise in the bits that are not read), three planes; TRIALS as there
+                                                   (and for ANTI and POWER: the four are rows of AB_MODES, one loop)
 """
 import os
 
@@ -44,6 +45,7 @@ import numpy as np
 import torch
 
 import cudabrot_amd as cb
+from gpu_launches import Launches  # beside this script: the launch scaffolding the GPU tests use too
 
 COMPARED = ("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps",
             "increments", "status")
@@ -100,19 +102,18 @@ def trial(rng):
     return t
 
 
+def read(seq, on_device=False):
+    """-> (histogram, flat; counters; generator states) of a finished launch sequence."""
+    hist, cnt, _, states = seq.read(on_device)
+    return hist.reshape(-1), cnt, states
+
+
 def render(t, variant, window=None, fused=False, on_device=False):
     """window: (max, min) instead of the trial's; fused: all of t["windows"] in one launch (planes)."""
-    dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
-    it = cb.IterationControl(*(window or (t["max_iter"], t["min_iter"])))
     planes = len(t["windows"]) if fused else 1
     n = t["threads"]
     flags = cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0
-    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(planes * t["w"] * t["h"], dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
     simple = variant == cb.CB_KERNEL_SIMPLE
     if t["two_level"] and not simple:
         os.environ["CUDABROT_AMD_TWO_LEVEL"] = "1"
@@ -124,36 +125,15 @@ def render(t, variant, window=None, fused=False, on_device=False):
         ws_bytes = cb.scatter_workspace_bytes(dims, n, max(t["launch_samples"]), n_channels=max(planes, 1))
         if t["workspace"] == "short":
             ws_bytes = ws_bytes // 3
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     use_carry = (not simple) and t["carry"] != "none"
-    carry = torch.zeros(cb.carry_bytes(n) if use_carry else 1, dtype=torch.uint8, device=dev)
-
-    def launch(samples, extra=0):
-        if fused:
-            cb.draw_buddhabrot_channels(dims, hist.data_ptr(), t["windows"], states.data_ptr(), n, samples,
-                                        counters.data_ptr(), variant | flags | extra, stream,
-                                        ws.data_ptr() if ws_bytes else 0, ws_bytes,
-                                        carry.data_ptr() if use_carry else 0)
-            if ws_bytes:
-                cb.flush_scatter_channels(dims, hist.data_ptr(), planes, n, ws.data_ptr(), ws_bytes, stream)
-            return
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), n, samples, counters.data_ptr(),
-                           variant | flags | extra, stream, ws.data_ptr() if ws_bytes else 0, ws_bytes,
-                           carry.data_ptr() if use_carry else 0)
-        if ws_bytes:
-            cb.flush_scatter(dims, hist.data_ptr(), n, ws.data_ptr(), ws_bytes, stream)
-
-    for i, s in enumerate(t["launch_samples"]):
-        last = i == len(t["launch_samples"]) - 1
-        launch(s, cb.CB_KERNEL_FLAG_DRAIN if (use_carry and last and t["carry"] == "drain_flag") else 0)
-    if use_carry and t["carry"] == "drain_launch":
-        launch(0)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    if on_device:
-        return hist, cnt
-    return hist.cpu().numpy().view(np.uint64), cnt
+    seq = Launches(cb, dims, n, planes=planes, seed=t["seed"], first=t["first"], workspace=ws_bytes, carry=use_carry or None)
+    drain = {"drain_launch": "launch", "drain_flag": "flag"}[t["carry"]] if use_carry else None
+    if fused:
+        seq.launches(cb.draw_buddhabrot_channels, t["launch_samples"], variant | flags, drain=drain, windows=t["windows"])
+    else:
+        seq.launches(cb.draw_buddhabrot, t["launch_samples"], variant | flags, drain=drain,
+                     iterations=cb.IterationControl(*(window or (t["max_iter"], t["min_iter"]))))
+    return read(seq, on_device)[:2]
 
 
 def anti_trial(rng):
@@ -176,63 +156,13 @@ def anti_trial(rng):
 
 def render_anti(t, variant):
     """The launches of an anti trial -> (histogram, counters, generator states)."""
-    dev = torch.device("cuda", 0)
     dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
-    it = cb.IterationControl(t["max_iter"], t["min_iter"])
     n = t["threads"]
     flags = cb.CB_KERNEL_FLAG_ANTI | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
-    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(t["w"] * t["h"], dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
     ws_bytes = max(cb.scatter_workspace_bytes(dims, n, max(t["launch_samples"])), 4096) if t["buffers"] else 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    carry = torch.zeros(cb.carry_bytes(n) if t["buffers"] else 1, dtype=torch.uint8, device=dev)
-    for s in t["launch_samples"]:
-        cb.draw_buddhabrot(dims, hist.data_ptr(), it, states.data_ptr(), n, s, counters.data_ptr(), variant | flags,
-                           stream, ws.data_ptr() if t["buffers"] else 0, ws_bytes,
-                           carry.data_ptr() if t["buffers"] else 0)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
-
-
-def anti_main(seconds, seed):
-    rng = random.Random(seed)
-    t_end = time.time() + seconds
-    n = compressed = 0
-    last_print = time.time()
-    while time.time() < t_end:
-        t = anti_trial(rng)
-        try:
-            want, wc, want_states = render_anti(t, cb.CB_KERNEL_SIMPLE)
-            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 5
-            got, gc, got_states = render_anti(t, cb.CB_KERNEL_DEFAULT)
-            product_ran = cb.lib.cb_debug_last_draw_kernel() == 4
-        except cb.CudabrotError as e:
-            print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
-            return 1
-        bad = [k for k in COMPARED if wc[k] != gc[k]]
-        if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
-                lockstep_ran and product_ran) or wc["skipped_steps"] != 0:
-            print("MISMATCH at anti trial %d (seed %d): %r" % (n, seed, t))
-            print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
-            print("  counters that differ: %r; lock-step skipped_steps %d" % ([(k, wc[k], gc[k]) for k in bad],
-                                                                            wc["skipped_steps"]))
-            print("  generator states identical: %s" % np.array_equal(want_states, got_states))
-            print("  pixels that differ: %d of %d; sums %d vs %d" % (int((want != got).sum()), want.size,
-                                                                     int(want.sum()), int(got.sum())), flush=True)
-            return 1
-        n += 1
-        compressed += 1 if gc["skipped_steps"] > 0 else 0
-        if time.time() - last_print > 30:
-            print("%d anti trials identical so far (%d with skipped_steps > 0)" % (n, compressed), flush=True)
-            last_print = time.time()
-    print("gpu_fuzz: %d anti trials (%d with skipped_steps > 0), histograms, counters and generator states identical "
-          "(seed %d)" % (n, compressed, seed))
-    return 0
+    seq = Launches(cb, dims, n, seed=t["seed"], first=t["first"], workspace=ws_bytes, carry=t["buffers"] or None)
+    return read(seq.launches(cb.draw_buddhabrot, t["launch_samples"], variant | flags, flush=False,  # nothing is deferred
+                             iterations=cb.IterationControl(t["max_iter"], t["min_iter"])))
 
 
 def power_trial(rng):
@@ -262,58 +192,9 @@ def power_trial(rng):
 
 def render_power(t, variant):
     """The launches of a Multibrot trial -> (histogram, counters, generator states)."""
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
-    it = cb.IterationControl(t["max_iter"], t["min_iter"])
-    n = t["threads"]
-    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
-    hist = torch.zeros(t["w"] * t["h"], dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
-    for s in t["launch_samples"]:
-        cb.draw_buddhabrot_projected(dims, hist.data_ptr(), it, t["matrix"], states.data_ptr(), n, s, counters.data_ptr(),
-                                     variant | cb.CB_KERNEL_POWER(t["degree"]), stream)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
-
-
-def power_main(seconds, seed):
-    rng = random.Random(seed)
-    t_end = time.time() + seconds
-    n = early = 0
-    last_print = time.time()
-    while time.time() < t_end:
-        t = power_trial(rng)
-        try:
-            want, wc, want_states = render_power(t, cb.CB_KERNEL_SIMPLE)
-            lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == 11
-            got, gc, got_states = render_power(t, cb.CB_KERNEL_DEFAULT)
-            product_ran = cb.lib.cb_debug_last_draw_kernel() == 10
-        except cb.CudabrotError as e:
-            print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
-            return 1
-        bad = [k for k in COMPARED if wc[k] != gc[k]]
-        if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
-                lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or wc["rejected"] != 0:
-            print("MISMATCH at power trial %d (seed %d): %r" % (n, seed, t))
-            print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
-            print("  counters that differ: %r; lock-step skipped_steps %d, rejected %d" % (
-                [(k, wc[k], gc[k]) for k in bad], wc["skipped_steps"], wc["rejected"]))
-            print("  generator states identical: %s" % np.array_equal(want_states, got_states))
-            print("  pixels that differ: %d of %d; sums %d vs %d" % (int((want != got).sum()), want.size,
-                                                                     int(want.sum()), int(got.sum())), flush=True)
-            return 1
-        n += 1
-        early += 1 if gc["skipped_steps"] > 0 else 0
-        if time.time() - last_print > 30:
-            print("%d power trials identical so far (%d with skipped_steps > 0)" % (n, early), flush=True)
-            last_print = time.time()
-    print("gpu_fuzz: %d power trials (%d with skipped_steps > 0), histograms, counters and generator states identical "
-          "(seed %d)" % (n, early, seed))
-    return 0
+    seq = Launches(cb, cb.FractalDimensions.make(t["w"], t["h"], *t["box"]), t["threads"], seed=t["seed"], first=t["first"])
+    return read(seq.launches(cb.draw_buddhabrot_projected, t["launch_samples"], variant | cb.CB_KERNEL_POWER(t["degree"]),
+                             iterations=cb.IterationControl(t["max_iter"], t["min_iter"]), projection=t["matrix"]))
 
 
 def depth_trial(rng):
@@ -397,63 +278,68 @@ def depth_palette_trial(rng):
 def render_depth(t, variant):
     """The launches of a depth trial, or with t["lut"] of a depth-palette trial -> (histogram, counters, generator
     states)."""
-    dev = torch.device("cuda", 0)
-    dims = cb.FractalDimensions.make(t["w"], t["h"], *t["box"])
-    it = cb.IterationControl(t["max_iter"], t["min_iter"])
-    n = t["threads"]
-    depth = cb.Depth.make(t["row"], t["window"][0], t["window"][1], t["slices"])
     flags = ((cb.CB_KERNEL_POWER(t["degree"]) if t["degree"] != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
              | (cb.CB_KERNEL_FORMULA(t["formula"]) if t["formula"] else 0))
-    states = torch.empty(cb.rng_state_bytes(n), dtype=torch.uint8, device=dev)
     lut = t.get("lut")
-    hist = torch.zeros((3 if lut else t["slices"]) * t["w"] * t["h"], dtype=torch.int64, device=dev)
-    counters = torch.zeros(17, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    cb.initialize_rng(t["seed"], t["first"], n, states.data_ptr(), stream)
+    seq = Launches(cb, cb.FractalDimensions.make(t["w"], t["h"], *t["box"]), t["threads"], planes=3 if lut else t["slices"],
+                   seed=t["seed"], first=t["first"], tables={"lut": lut} if lut else None)
+    args = dict(iterations=cb.IterationControl(t["max_iter"], t["min_iter"]), projection=t["matrix"], julia_c=t["c"],
+                depth=cb.Depth.make(t["row"], t["window"][0], t["window"][1], t["slices"]))
     if lut:
-        d_lut = torch.from_numpy(np.array(lut, dtype=np.uint32).view(np.int32)).to(dev)
-    for s in t["launch_samples"]:
-        if lut:
-            cb.draw_buddhabrot_depth_palette(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, d_lut.data_ptr(),
-                                             len(lut), states.data_ptr(), n, s, counters.data_ptr(), variant | flags, stream)
-        else:
-            cb.draw_buddhabrot_depth(dims, hist.data_ptr(), it, t["matrix"], t["c"], depth, states.data_ptr(), n, s,
-                                     counters.data_ptr(), variant | flags, stream)
-    torch.cuda.synchronize()
-    c = counters.cpu().numpy().view(np.uint64)
-    cnt = dict(zip(cb.Counters().as_dict().keys(), (int(v) for v in c)))
-    return hist.cpu().numpy().view(np.uint64), cnt, states.cpu().numpy()
+        args.update(d_lut=seq.tables["lut"].data_ptr(), n_entries=len(lut))
+    entry = cb.draw_buddhabrot_depth_palette if lut else cb.draw_buddhabrot_depth
+    return read(seq.launches(entry, t["launch_samples"], variant | flags, **args))
 
 
-def depth_main(seconds, seed, palette=False):
-    """DEPTH's run, or with palette DEPTHPALETTE's: the same comparison on the other pair of kernels."""
-    name = "depth-palette" if palette else "depth"
-    lockstep_kernel, product_kernel = (21, 20) if palette else (19, 18)
+def sums_up(want, wc):
+    return int(want.sum()) == wc["increments"]
+
+
+# One row per mode of the lock-step / product A/B that compares generator states as well: the trial generator and its
+# render; the values of cb_debug_last_draw_kernel (lock-step, product); `extra`, what else the lock-step run must satisfy
+# -- (wanted histogram, its counters) -> bool -- and what a MISMATCH block says about it (counters_note, pixels_note); and
+# `filled`: the final line also tallies the trials with increments > 0.
+AB_MODES = {
+    "ANTI": dict(name="anti", trial=anti_trial, render=render_anti, kernels=(5, 4)),
+    "POWER": dict(name="power", trial=power_trial, render=render_power, kernels=(11, 10),
+                  extra=lambda want, wc: wc["rejected"] == 0, counters_note=", rejected %(rejected)d"),
+    "DEPTH": dict(name="depth", trial=depth_trial, render=render_depth, kernels=(19, 18), extra=sums_up,
+                  pixels_note="; increments %(increments)d", filled=True),
+    "DEPTHPALETTE": dict(name="depth-palette", trial=depth_palette_trial, render=render_depth, kernels=(21, 20),
+                         extra=sums_up, pixels_note="; increments %(increments)d", filled=True),
+}
+
+
+def ab_main(mode, seconds, seed):
+    """One mode of AB_MODES until SECONDS have passed, or TRIALS trials where that comes first."""
+    name, render_mode, (lockstep_kernel, product_kernel) = mode["name"], mode["render"], mode["kernels"]
     rng = random.Random(seed)
     t_end = time.time() + seconds
     trials = int(os.environ.get("TRIALS", "0"))
     n = early = filled = 0
     last_print = time.time()
     while time.time() < t_end and not (trials and n >= trials):
-        t = depth_palette_trial(rng) if palette else depth_trial(rng)
+        t = mode["trial"](rng)
         try:
-            want, wc, want_states = render_depth(t, cb.CB_KERNEL_SIMPLE)
+            want, wc, want_states = render_mode(t, cb.CB_KERNEL_SIMPLE)
             lockstep_ran = cb.lib.cb_debug_last_draw_kernel() == lockstep_kernel
-            got, gc, got_states = render_depth(t, cb.CB_KERNEL_DEFAULT)
+            got, gc, got_states = render_mode(t, cb.CB_KERNEL_DEFAULT)
             product_ran = cb.lib.cb_debug_last_draw_kernel() == product_kernel
         except cb.CudabrotError as e:
             print("trial %d: error %s\n  %r" % (n, e, t), flush=True)
             return 1
         bad = [k for k in COMPARED if wc[k] != gc[k]]
         if not np.array_equal(want, got) or bad or not np.array_equal(want_states, got_states) or not (
-                lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or int(want.sum()) != wc["increments"]:
+                lockstep_ran and product_ran) or wc["skipped_steps"] != 0 or (
+                "extra" in mode and not mode["extra"](want, wc)):
             print("MISMATCH at %s trial %d (seed %d): %r" % (name, n, seed, t))
             print("  kernels as expected: lock-step %s, product %s" % (lockstep_ran, product_ran))
-            print("  counters that differ: %r; lock-step skipped_steps %d" % ([(k, wc[k], gc[k]) for k in bad],
-                                                                            wc["skipped_steps"]))
+            print("  counters that differ: %r; lock-step skipped_steps %d%s" % (
+                [(k, wc[k], gc[k]) for k in bad], wc["skipped_steps"], mode.get("counters_note", "") % wc))
             print("  generator states identical: %s" % np.array_equal(want_states, got_states))
-            print("  pixels that differ: %d of %d; sums %d vs %d; increments %d" % (
-                int((want != got).sum()), want.size, int(want.sum()), int(got.sum()), wc["increments"]), flush=True)
+            print("  pixels that differ: %d of %d; sums %d vs %d%s" % (
+                int((want != got).sum()), want.size, int(want.sum()), int(got.sum()), mode.get("pixels_note", "") % wc),
+                flush=True)
             return 1
         n += 1
         early += 1 if gc["skipped_steps"] > 0 else 0
@@ -461,8 +347,9 @@ def depth_main(seconds, seed, palette=False):
         if time.time() - last_print > 30:
             print("%d %s trials identical so far (%d with skipped_steps > 0)" % (n, name, early), flush=True)
             last_print = time.time()
-    print("gpu_fuzz: %d %s trials (%d with skipped_steps > 0, %d with increments > 0), histograms, counters and "
-          "generator states identical (seed %d)" % (n, name, early, filled, seed))
+    tallies = "%d with skipped_steps > 0" % early + (", %d with increments > 0" % filled if mode.get("filled") else "")
+    print("gpu_fuzz: %d %s trials (%s), histograms, counters and generator states identical (seed %d)" % (
+        n, name, tallies, seed))
     return 0
 
 
@@ -535,14 +422,9 @@ def render_with_renderer(t):
 def main():
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    if os.environ.get("ANTI") == "1":
-        return anti_main(seconds, seed)
-    if os.environ.get("POWER") == "1":
-        return power_main(seconds, seed)
-    if os.environ.get("DEPTH") == "1":
-        return depth_main(seconds, seed)
-    if os.environ.get("DEPTHPALETTE") == "1":
-        return depth_main(seconds, seed, palette=True)
+    for knob, mode in AB_MODES.items():
+        if os.environ.get(knob) == "1":
+            return ab_main(mode, seconds, seed)
     rng = random.Random(seed)
     t_end = time.time() + seconds
     n = 0
