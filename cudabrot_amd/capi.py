@@ -61,6 +61,7 @@ CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_S
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
 CB_PALETTE_MAX_ENTRIES, CB_PALETTE_MAX_STOPS = 1 << 24, 16  # palette render: the table's entries, the stops of one
 CB_DEPTH_MAX_SLICES = 256  # depth render: the planes of one
+CB_FRAMES_MAX = 256  # frames render: the matrices (and planes) of one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -324,6 +325,12 @@ def _load():
         "cb_renderer_set_depth_palette": (i32, [vp, depth_p, vp, u32]),
         "cb_renderer_depth_palette": (i32, [vp, depth_p, C.POINTER(u32)]),
         "cb_renderer_depth_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_rotate_projection": (i32, [C.POINTER(C.c_double), i32, i32, C.c_double]),
+        "cb_frames_from_sweep": (i32, [C.POINTER(C.c_double), i32, i32, C.c_double, C.c_double, i32, vp, vp]),
+        "cb_draw_buddhabrot_frames": (i32, [dims_p, vp, it_p, vp, i32, C.POINTER(C.c_double), vp, u32, u32, vp, i32, vp]),
+        "cb_renderer_set_frames": (i32, [vp, vp, i32]),
+        "cb_renderer_frames": (i32, [vp, vp]),
+        "cb_renderer_frames_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -349,7 +356,9 @@ EXPORTED_SYMBOLS = (
     "cb_palette_from_stops cb_draw_buddhabrot_palette cb_renderer_set_palette cb_renderer_palette cb_renderer_palette_image "
     "cb_draw_buddhabrot_depth cb_renderer_set_depth cb_renderer_depth cb_renderer_depth_image "
     "cb_draw_buddhabrot_depth_palette cb_renderer_set_depth_palette cb_renderer_depth_palette "
-    "cb_renderer_depth_palette_image"
+    "cb_renderer_depth_palette_image "
+    "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
+    "cb_renderer_frames_image"
 ).split()
 
 
@@ -548,6 +557,40 @@ def draw_buddhabrot_depth_palette(dims, d_hist, iterations, projection, julia_c,
     )
 
 
+def _frames(frames):
+    """The matrices of a frames render, F x P[2][4], as a contiguous float64 array [F, 8]."""
+    a = np.ascontiguousarray(frames, dtype=np.float64)
+    if a.size == 0 or a.size % 8 != 0:
+        raise ValueError("frames are F matrices of eight numbers each: P[2][4]")
+    return a.reshape(-1, 8)
+
+
+def frames_from_sweep(base, axes, deg0, deg1, n_frames):
+    """The matrices of a rotation sweep (cb_frames_from_sweep): base rotated in the coordinate plane axes = (X, Y) -- names
+    of DEPTH_AXES or columns 0 .. 3 -- by a_f = deg0 + ((deg1 - deg0) * f) / n_frames -> (matrices [F, 8], angles [F])."""
+    x, y = (DEPTH_AXES.get(a, a) if isinstance(a, str) else a for a in axes)
+    if isinstance(x, str) or isinstance(y, str):
+        raise ValueError("a sweep axis is one of %s" % ", ".join(DEPTH_AXES))
+    n = int(n_frames)
+    out = np.empty((max(n, 0), 8), dtype=np.float64)
+    angles = np.empty(max(n, 0), dtype=np.float64)
+    _check(lib.cb_frames_from_sweep(_projection(base), int(x), int(y), float(deg0), float(deg1), n, out.ctypes.data,
+                                    angles.ctypes.data), "cb_frames_from_sweep")
+    return out, angles
+
+
+def draw_buddhabrot_frames(dims, d_hist, iterations, d_frames, n_frames, julia_c, d_states, n_threads, samples_per_thread,
+                           d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The frames draw on caller-owned device memory (cb_draw_buddhabrot_frames): d_hist is n_frames planes, d_frames the
+    n_frames matrices (8 doubles each) on the device; julia_c None samples c (a projected render), else c is fixed."""
+    _check(
+        lib.cb_draw_buddhabrot_frames(C.byref(dims), d_hist, C.byref(iterations), d_frames, int(n_frames),
+                                      None if julia_c is None else _julia_c(julia_c), d_states, n_threads,
+                                      samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_frames",
+    )
+
+
 class Renderer:
     """SetupCUDA + RenderImage (cudabrot.cu:153-189, 471-501) over the C ABI's cb_renderer."""
 
@@ -562,6 +605,7 @@ class Renderer:
         self.palette_entries = 0
         self.depth_slices = 0
         self.depth_palette_entries = 0
+        self.n_frames = 0
         if isinstance(iterations, IterationControl):
             self.n_channels = 0
             _check(
@@ -686,9 +730,34 @@ class Renderer:
                                                    C.byref(scale)), "cb_renderer_depth_palette_image")
         return rgb, int(mx.value), float(scale.value)
 
+    def set_frames(self, frames):
+        """Give this renderer frames (cb_renderer_set_frames), before the first pass and after set_projection or
+        set_julia: frames is F matrices, [F, 8].  The histogram becomes F planes."""
+        a = _frames(frames)
+        _check(lib.cb_renderer_set_frames(self._h, a.ctypes.data, a.shape[0]), "cb_renderer_set_frames")
+        self.n_frames = int(a.shape[0])
+
+    def frames(self):
+        """The matrices of a renderer with frames, [F, 8]; None for a renderer without them."""
+        n = lib.cb_renderer_frames(self._h, None)
+        if not n:
+            return None
+        out = np.empty((n, 8), dtype=np.float64)
+        lib.cb_renderer_frames(self._h, out.ctypes.data)
+        return out
+
+    def frames_image(self, gamma=1.0, mode=0):
+        """The image of a renderer with frames (cb_renderer_frames_image) -> (big-endian u16 images [F, h, w] = the bodies
+        of the PGM sequence, the largest count of all planes, scale)."""
+        gray = np.empty((max(self.n_frames, 1), self.dims.h, self.dims.w), dtype=">u2")
+        mx, scale = C.c_uint64(), C.c_double()
+        _check(lib.cb_renderer_frames_image(self._h, float(gamma), int(mode), gray.ctypes.data, C.byref(mx),
+                                            C.byref(scale)), "cb_renderer_frames_image")
+        return gray, int(mx.value), float(scale.value)
+
     def _planes(self):
-        if self.depth_slices:
-            return self.depth_slices
+        if self.depth_slices or self.n_frames:
+            return self.depth_slices or self.n_frames
         return 3 if self.palette_entries or self.depth_palette_entries else (self.n_channels or 1)
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
@@ -706,7 +775,7 @@ class Renderer:
         planes = self._planes()
         out = np.empty(planes * self.dims.w * self.dims.h, dtype=np.uint64)
         _check(lib.cb_renderer_read_histogram(self._h, out.ctypes.data), "cb_renderer_read_histogram")
-        if self.n_channels or self.palette_entries or self.depth_slices or self.depth_palette_entries:
+        if self.n_channels or self.palette_entries or self.depth_slices or self.depth_palette_entries or self.n_frames:
             return out.reshape(planes, self.dims.h, self.dims.w)
         return out.reshape(self.dims.h, self.dims.w)
 

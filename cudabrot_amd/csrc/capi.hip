@@ -319,6 +319,11 @@ struct cb_renderer {
   // not the slices
   bool depth_palette;
   uint32_t *d_depth_lut;  // depth.slices entries
+  // frames render (cb_renderer_set_frames): a projected or Julia renderer whose draws plot with n_frames matrices; d_hist
+  // is then n_frames planes
+  int n_frames;
+  double *d_frames;             // n_frames x 8 doubles
+  std::vector<double> *frames;  // the same on the host (cb_renderer_frames)
 };
 
 namespace {
@@ -327,6 +332,7 @@ namespace {
 // renderer, the slices of a renderer with a depth, else one.
 size_t renderer_planes(const cb_renderer *r) {
   if (r->has_depth) return (size_t) r->depth.slices;
+  if (r->n_frames) return (size_t) r->n_frames;
   return r->palette || r->depth_palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u);
 }
 
@@ -337,6 +343,10 @@ int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_ite
                const double projection[8], const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut,
                uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                int kernel_variant, void *stream, int *interior_level);
+
+int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                const double *d_frames, int n_frames, const double julia_c[2], void *d_states, uint32_t n_threads,
+                uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
@@ -356,6 +366,11 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
                         r->depth_palette ? r->d_depth_lut : nullptr, r->depth_palette ? (uint32_t) r->depth.slices : 0u,
                         r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
                         &r->interior_level);
+    }
+    if (r->n_frames) {  // draw_frames.hip, likewise
+      return draw_frames(&r->dims, r->d_hist, &r->iterations, r->d_frames, r->n_frames, r->julia ? r->julia_c : nullptr,
+                         r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
+                         &r->interior_level);
     }
     return draw_plot(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
                      r->palette ? r->d_palette : nullptr, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
@@ -922,6 +937,8 @@ int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n
 
 namespace {
 
+const double kIdentityProjection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+
 bool projection_ok(const double *p) {
   if (!p) return false;
   for (int j = 0; j < 8; ++j) {
@@ -1044,6 +1061,39 @@ int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_ite
   return rc;
 }
 
+// The matrices of a frames render ("Frames render"): F in range, every entry finite, and F * h rows still an int (the
+// planes are tone-mapped as one w x F*h image).
+bool frames_ok(const double *frames_host, int n_frames, int h) {
+  if (!frames_host || n_frames < 1 || n_frames > CB_FRAMES_MAX) return false;
+  for (int j = 0; j < 8 * n_frames; ++j) {
+    if (!isfinite(frames_host[j])) return false;
+  }
+  return (long long) n_frames * (long long) h <= 0x7fffffffLL;
+}
+
+// The frames draws (draw_frames.hip): what cb_draw_buddhabrot_frames and a renderer with frames do once their own
+// arguments, the matrices' entries among them, have passed.
+int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                const double *d_frames, int n_frames, const double julia_c[2], void *d_states, uint32_t n_threads,
+                uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
+  if (interior_level) *interior_level = 0;
+  cb::FramesArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  bool lockstep = false;
+  {
+    const int rc = plot_args(dims, d_hist, iterations, kIdentityProjection, julia_c, nullptr, d_states, n_threads,
+                             samples_per_thread, d_counters, kernel_variant, &fa.p, &lockstep);
+    if (rc) return rc;
+  }
+  fa.frames = d_frames;
+  fa.n_frames = n_frames;
+  fa.plane_pixels = fa.p.plane_pixels;
+  g_last_draw_kernel.store(lockstep ? 23 : 22, std::memory_order_relaxed);
+  const int rc = (int) cb::launch_draw_frames(fa, lockstep, reinterpret_cast<hipStream_t>(stream));
+  if (interior_level && !rc && fa.p.d.interior_map) *interior_level = (int) fa.p.d.interior_shift + 1;
+  return rc;
+}
+
 }  // namespace
 
 int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
@@ -1074,8 +1124,6 @@ int cb_renderer_projection(const cb_renderer *r, double out[8]) {
 // ---- Julia render (draw_plot.hip; include/cudabrot_amd.h, "Julia render") -------------------------------------------
 
 namespace {
-
-const double kIdentityProjection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
 
 bool julia_c_ok(const double *c) {  // both in [-2, 2]; a NaN fails the comparisons
   return c && c[0] >= -2.0 && c[0] <= 2.0 && c[1] >= -2.0 && c[1] <= 2.0;
@@ -1147,7 +1195,7 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
   if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || r->depth_palette ||
-      !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
+      r->n_frames || !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
     return (int) hipErrorInvalidValue;
   }
   for (uint32_t k = 0; k < n_entries; ++k) {
@@ -1185,7 +1233,8 @@ int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist
 
 int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
   // a projected or Julia renderer (a palette renderer is projected too, a channel or focused one never is)
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || !depth_ok(depth, r->dims.h)) {
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+      !depth_ok(depth, r->dims.h)) {
     return (int) hipErrorInvalidValue;
   }
   const int rc = swap_in_planes(r, (size_t) depth->slices, nullptr, 0u, nullptr);
@@ -1217,8 +1266,8 @@ int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel
 
 int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const uint32_t *lut_host, uint32_t n_entries) {
   // where cb_renderer_set_depth is refused, and for a renderer that has a depth
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || !depth_ok(depth, r->dims.h) ||
-      !lut_host || n_entries != (uint32_t) depth->slices) {
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+      !depth_ok(depth, r->dims.h) || !lut_host || n_entries != (uint32_t) depth->slices) {
     return (int) hipErrorInvalidValue;
   }
   for (uint32_t k = 0; k < n_entries; ++k) {
@@ -1236,6 +1285,54 @@ int cb_renderer_depth_palette(const cb_renderer *r, cb_depth *out, uint32_t *n_e
   if (out) *out = r->depth;
   if (n_entries) *n_entries = (uint32_t) r->depth.slices;
   return 1;
+}
+
+// ---- frames render (draw_frames.hip; include/cudabrot_amd.h, "Frames render") ---------------------------------------
+
+int cb_draw_buddhabrot_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                              const double *d_frames, int n_frames, const double julia_c[2], void *d_states,
+                              uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                              void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!d_frames || n_frames < 1 || n_frames > CB_FRAMES_MAX || (julia_c && !julia_c_ok(julia_c))) {
+    return (int) hipErrorInvalidValue;
+  }
+  // the matrices are the caller's device memory: their entries are looked at in a host copy, made on the caller's stream
+  std::vector<double> copy(8 * (size_t) n_frames);
+  CB_TRY(hipMemcpyAsync(copy.data(), d_frames, copy.size() * sizeof(double), hipMemcpyDeviceToHost,
+                        reinterpret_cast<hipStream_t>(stream)));
+  CB_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+  if (!frames_ok(copy.data(), n_frames, dims->h)) return (int) hipErrorInvalidValue;
+  return draw_frames(dims, d_hist, iterations, d_frames, n_frames, julia_c, d_states, n_threads, samples_per_thread,
+                     d_counters, kernel_variant, stream, nullptr);
+}
+
+int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_frames) {
+  // where cb_renderer_set_depth is refused, and for a renderer that has frames
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+      !frames_ok(frames_host, n_frames, r->dims.h)) {
+    return (int) hipErrorInvalidValue;
+  }
+  CB_TRY(hipSetDevice(r->device));
+  const size_t bytes = 8 * (size_t) n_frames * sizeof(double);
+  double *d_frames = nullptr;
+  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_frames), bytes));
+  int rc = (int) hipMemcpy(d_frames, frames_host, bytes, hipMemcpyHostToDevice);
+  if (!rc) rc = swap_in_planes(r, (size_t) n_frames, nullptr, 0u, nullptr);
+  if (rc) {
+    (void) hipFree(d_frames);
+    return rc;
+  }
+  r->d_frames = d_frames;
+  r->frames = new std::vector<double>(frames_host, frames_host + 8 * (size_t) n_frames);
+  r->n_frames = n_frames;
+  return 0;
+}
+
+int cb_renderer_frames(const cb_renderer *r, double *out) {
+  if (!r || !r->n_frames) return 0;
+  if (out) memcpy(out, r->frames->data(), r->frames->size() * sizeof(double));
+  return r->n_frames;
 }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
@@ -1468,6 +1565,13 @@ int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_
   return gray_image(r, 0, r->depth.slices * r->dims.h, gamma, tone_mode, host_gray_be, max_out, scale_out);
 }
 
+int cb_renderer_frames_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
+                             double *scale_out) {
+  if (!r || !r->n_frames || !host_gray_be) return (int) hipErrorInvalidValue;
+  // likewise: one w x F*h image (F * h fits an int: cb_renderer_set_frames)
+  return gray_image(r, 0, r->n_frames * r->dims.h, gamma, tone_mode, host_gray_be, max_out, scale_out);
+}
+
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
                             const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
@@ -1555,6 +1659,8 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_focus_cells);
   (void) hipFree(r->d_palette);
   (void) hipFree(r->d_depth_lut);
+  (void) hipFree(r->d_frames);
+  delete r->frames;
   (void) hipFree(r->d_workspace[0]);
   (void) hipFree(r->d_workspace[1]);
   for (int k = 0; k < 2; ++k) {

@@ -121,8 +121,8 @@ int parse_palette(const char *text, cb_palette_stop out[CB_PALETTE_MAX_STOPS]) {
   }
 }
 
-// --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane.  An integer multiple of 90
-// degrees uses exact 0 and +-1 (a permutation of the two columns with signs); otherwise the host's cos and sin.
+// --rotate X,Y:DEG on the current matrix: both rows are rotated in the (X, Y) coordinate plane, by cb_rotate_projection
+// (host_abi.cpp; an integer multiple of 90 degrees is exact).
 bool rotate_projection(const char *text, double p[8]) {
   const char *rest = nullptr;
   const int x = axis_of(text, ',', &rest);
@@ -131,22 +131,32 @@ bool rotate_projection(const char *text, double p[8]) {
   char *end = nullptr;
   const double degrees = strtod(rest, &end);
   if (end == rest || *end != 0 || !isfinite(degrees)) return false;
-  double co, si;
-  const double quarters = degrees / 90.0;
-  if (quarters == floor(quarters)) {
-    const int q = (int) fmod(fmod(quarters, 4.0) + 4.0, 4.0);
-    co = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
-    si = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
-  } else {
-    const double radians = degrees * (M_PI / 180.0);
-    co = cos(radians);
-    si = sin(radians);
+  return cb_rotate_projection(p, x, y, degrees) == 0;
+}
+
+// --sweep X,Y:DEG0:DEG1:F: two different axes, two finite angles in strtod's syntax (hexfloats included), F decimal
+// digits, 1 .. CB_FRAMES_MAX.
+bool parse_sweep(const char *text, Sweep *out) {
+  const char *at = nullptr;
+  const int x = axis_of(text, ',', &at);
+  const int y = x < 0 ? -1 : axis_of(at, ':', &at);
+  if (x < 0 || y < 0 || x == y) return false;
+  double degrees[2];
+  for (int j = 0; j < 2; ++j) {
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    degrees[j] = strtod(at, &end);
+    if (end == at || !isfinite(degrees[j]) || *end != ':') return false;
+    at = end + 1;
   }
-  for (int row = 0; row < 2; ++row) {
-    const double a = p[4 * row + x], b = p[4 * row + y];
-    p[4 * row + x] = (a * co - b * si) + 0.0;  // (+ 0.0: an exact zero is +0)
-    p[4 * row + y] = (a * si + b * co) + 0.0;
+  long n = 0;
+  if (*at == 0) return false;
+  for (; *at >= '0' && *at <= '9'; ++at) {
+    n = n * 10 + (*at - '0');
+    if (n > CB_FRAMES_MAX) return false;
   }
+  if (*at != 0 || n < 1) return false;
+  *out = {x, y, degrees[0], degrees[1], (int) n};
   return true;
 }
 
@@ -402,6 +412,18 @@ const std::vector<Flag> &flag_table() {
          s.n_depth_palette_stops = parse_palette(t, s.depth_palette_stops);
          return s.depth_palette() ? kOk : "Invalid depth palette (want K:RRGGBB,... K ascending, at most 16 stops)";
        }},
+      // --sweep X,Y:DEG0:DEG1:F: F frames of the plane as it stands after every --plane / --rotate / --project, rotated in
+      // the (X, Y) coordinate plane from DEG0 to DEG1 (exclusive), from ONE orbit pass; F planes, -o receives F PGMs back
+      // to back with one common exposure (include/cudabrot_amd.h, "Frames render").  Applied last, wherever it stands.
+      {"--sweep", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         const bool again = s.sweep_given;
+         s.sweep_given = true;
+         return !again && parse_sweep(t, &s.sweep)
+                    ? kOk
+                    : "Invalid sweep (want X,Y:DEG0:DEG1:F, two different axes of zr, zi, cr, ci, two finite angles and 1 to "
+                      CB_TEXT_OF(CB_FRAMES_MAX) " frames)";
+       }},
       // --seed N: the generator's seed, 64 bits wide (rocrand_init)
       {"--seed", Value::kLong, nullptr, false,
        [](Settings &s, long i, double, const char *) { s.seed = (uint64_t) i; return kOk; }},
@@ -482,6 +504,8 @@ const Partner kChannel = {[](const Settings &s) { return s.n_channels > 0 || s.c
 const Partner kGpus = {[](const Settings &s) { return s.gpus > 1; }, "--gpus above 1"};
 const Partner kRaw = {[](const Settings &s) { return s.raw_state; }, "--state-format raw"};
 const Partner kPalette = {[](const Settings &s) { return s.palette(); }, "--palette"};
+const Partner kDepth = {[](const Settings &s) { return s.depth_given; }, "--depth"};
+const Partner kDepthPalette = {[](const Settings &s) { return s.depth_palette(); }, "--depth-palette"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -534,6 +558,10 @@ const std::vector<Refusal> &refusal_table() {
       // --depth refuses, its row above has refused
       {[](const Settings &s) { return s.depth_palette() && !s.depth_given; }, nullptr, {},
        [](const Settings &) { printf("--depth-palette needs --depth.\n"); }},
+      // a frames render is a projected render with F planes (include/cudabrot_amd.h, "Frames render"); the last row: where
+      // an older row refuses the line, that row has spoken already
+      {[](const Settings &s) { return s.sweep_given; }, "--sweep",
+       {kPalette, kDepth, kDepthPalette, kAnti, kFocus, kChannel, kGpus, kRaw}, nullptr},
   };
   return table;
 }

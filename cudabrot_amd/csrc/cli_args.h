@@ -10,6 +10,13 @@
 
 namespace cb {
 
+// --sweep X,Y:DEG0:DEG1:F as given: the two axes (columns of P), the angles and the number of frames.
+struct Sweep {
+  int axis_x, axis_y;
+  double deg0, deg1;
+  int frames;
+};
+
 struct Settings {
   int device = 0;                                   // -d
   const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
@@ -68,13 +75,18 @@ struct Settings {
   // projection's
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
-  bool plotted() const { return projected() || depth_given; }
+  bool plotted() const { return projected() || depth_given || sweep_given; }
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
   int n_depth_palette_stops = 0;
   cb_palette_stop depth_palette_stops[CB_PALETTE_MAX_STOPS] = {};
   bool depth_palette() const { return n_depth_palette_stops > 0; }
+  // --sweep X,Y:DEG0:DEG1:F (extension): F frames of the plane rotated in (X, Y), one orbit pass (cb_frames_from_sweep,
+  // cb_renderer_set_frames); makes the run a projected one as --depth does, with a last refusal row of its own.  The base
+  // is `projection` as it stands when the flags have been read: the sweep is applied last, at most once.
+  bool sweep_given = false;
+  Sweep sweep = {0, 1, 0.0, 0.0, 0};
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

@@ -65,6 +65,16 @@ class Run {
     printf("Creating %dx%d image, %d max iterations.\n", cfg_.canvas.w, cfg_.canvas.h,
            max_iterations);  // cudabrot.cu:779-780
     printf("Calculating image...\n");
+    if (cfg_.sweep_given) {  // the matrices of the frames, from the plane as every other flag has left it
+      const cb::Sweep &w = cfg_.sweep;
+      frames_.resize(8 * (size_t) w.frames);
+      sweep_angles_.resize((size_t) w.frames);
+      if (cb_frames_from_sweep(cfg_.projection, w.axis_x, w.axis_y, w.deg0, w.deg1, w.frames, frames_.data(),
+                               sweep_angles_.data()) != 0) {
+        printf("Invalid sweep: the angles of its frames are not finite.\n");
+        return 1;
+      }
+    }
     if (cfg_.plotted() && cfg_.print_stats) {  // the matrix defines the run: printed before any device is touched
       const double *p = cfg_.projection;
       fprintf(stderr, "{\"projection\": [\"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\", \"%a\"]}\n", p[0], p[1], p[2],
@@ -76,6 +86,14 @@ class Run {
         const cb_depth &d = cfg_.depth;
         fprintf(stderr, "{\"depth\": {\"row\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"min\": \"%a\", \"max\": \"%a\", \"slices\": %d}}\n",
                 d.row[0], d.row[1], d.row[2], d.row[3], d.min, d.max, d.slices);
+      }
+      if (cfg_.sweep_given) {  // and the sweep: --rotate X,Y:<angles[f]> on the matrix above reproduces frame f
+        static const char *const kAxes[4] = {"zr", "zi", "cr", "ci"};
+        const cb::Sweep &w = cfg_.sweep;
+        fprintf(stderr, "{\"sweep\": {\"axes\": [\"%s\", \"%s\"], \"from\": \"%a\", \"to\": \"%a\", \"frames\": %d, \"angles\": [",
+                kAxes[w.axis_x], kAxes[w.axis_y], w.deg0, w.deg1, w.frames);
+        for (int f = 0; f < w.frames; ++f) fprintf(stderr, "%s\"%a\"", f ? ", " : "", sweep_angles_[(size_t) f]);
+        fprintf(stderr, "]}}\n");
       }
       if (cfg_.depth_palette()) {  // and the colours of its slices
         fprintf(stderr, "{\"depth_palette\": [");
@@ -108,9 +126,9 @@ class Run {
       printf("Saving image.\n");
       report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
       printf("Done! Output image saved: %s\n", cfg_.output_image);
-    } else if (cfg_.depth_given) {
+    } else if (cfg_.depth_given || cfg_.sweep_given) {
       printf("Saving image.\n");
-      report_save(save_depth_images(cfg_.output_image));
+      report_save(save_plane_images(cfg_.output_image));
       printf("Done! Output image saved: %s\n", cfg_.output_image);
     } else {
       printf("Saving image.\n");
@@ -132,7 +150,8 @@ class Run {
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
   std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette: the PPM body
-  std::vector<uint16_t> depth_gray_be_;   // --depth: the bodies of the N PGMs, slice 0 first
+  std::vector<uint16_t> planes_gray_be_;  // --depth, --sweep: the bodies of the N PGMs, slice or frame 0 first
+  std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
@@ -140,6 +159,7 @@ class Run {
   uint64_t planes() const {
     if (cfg_.depth_palette()) return 3u;
     if (cfg_.depth_given) return (uint64_t) cfg_.depth.slices;
+    if (cfg_.sweep_given) return (uint64_t) cfg_.sweep.frames;
     return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u);
   }
   uint64_t buffer_bytes() const { return planes() * pixel_count() * sizeof(cb_pixel); }
@@ -206,6 +226,7 @@ class Run {
     } else if (cfg_.depth_given) {
       CB_CHECK(cb_renderer_set_depth(renderer_, &cfg_.depth));  // after the plane and c
     }
+    if (cfg_.sweep_given) CB_CHECK(cb_renderer_set_frames(renderer_, frames_.data(), cfg_.sweep.frames));  // likewise
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -341,8 +362,8 @@ class Run {
     if (cfg_.print_stats) print_stats();
     if (cfg_.palette() || cfg_.depth_palette()) {
       palette_image();
-    } else if (cfg_.depth_given) {
-      depth_image();
+    } else if (cfg_.depth_given || cfg_.sweep_given) {
+      planes_image();
     } else if (cfg_.n_channels == 0) {
       tone_map(0);
     }
@@ -516,33 +537,33 @@ class Run {
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }
 
-  // --depth: the N planes tone-mapped against their common maximum, as one w x N*h image -- on the device, or with
-  // --tonemap host by the reference's host loop; the bytes are the same.
-  void depth_image() {
+  // --depth, --sweep: the N planes tone-mapped against their common maximum, as one w x N*h image -- on the device, or
+  // with --tonemap host by the reference's host loop; the bytes are the same.
+  void planes_image() {
     uint64_t max = 0;
     double scale = 0.0;
-    depth_gray_be_.resize(planes() * pixel_count());
+    planes_gray_be_.resize(planes() * pixel_count());
     if (cfg_.host_tonemap) {
-      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, cfg_.depth.slices * cfg_.canvas.h, cfg_.gamma_correction,
-                              depth_gray_be_.data(), &max, &scale);
-      for (uint16_t &v : depth_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
+      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, (int) planes() * cfg_.canvas.h, cfg_.gamma_correction,
+                              planes_gray_be_.data(), &max, &scale);
+      for (uint16_t &v : planes_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
     } else {
-      CB_CHECK(cb_renderer_depth_image(renderer_, cfg_.gamma_correction, cfg_.tone_mode, depth_gray_be_.data(), &max,
-                                       &scale));
+      CB_CHECK((cfg_.sweep_given ? cb_renderer_frames_image : cb_renderer_depth_image)(
+          renderer_, cfg_.gamma_correction, cfg_.tone_mode, planes_gray_be_.data(), &max, &scale));
     }
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }
 
-  // --depth: N binary PGMs back to back in one file (Netpbm's format allows a sequence of images), each SaveImage's
-  // (cudabrot.cu:548-577); 0, or 1/2/3 = open / header / pixel-data failure as cb_save_image.
-  int save_depth_images(const char *path) {
+  // --depth, --sweep: N binary PGMs back to back in one file (Netpbm's format allows a sequence of images), each
+  // SaveImage's (cudabrot.cu:548-577); 0, or 1/2/3 = open / header / pixel-data failure as cb_save_image.
+  int save_plane_images(const char *path) {
     FILE *f = fopen(path, "wb");
     if (!f) return 1;
     int rc = 0;
     for (uint64_t s = 0; s < planes() && rc == 0; ++s) {
       if (fprintf(f, "P5\n%d %d\n65535\n", cfg_.canvas.w, cfg_.canvas.h) <= 0) {
         rc = 2;
-      } else if (fwrite(depth_gray_be_.data() + s * pixel_count(), sizeof(uint16_t), pixel_count(), f) != pixel_count()) {
+      } else if (fwrite(planes_gray_be_.data() + s * pixel_count(), sizeof(uint16_t), pixel_count(), f) != pixel_count()) {
         rc = 3;
       }
     }

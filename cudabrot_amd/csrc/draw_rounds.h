@@ -74,7 +74,7 @@ __device__ __forceinline__ bool brent_save(uint32_t chunks) {
 // time.  The wave advances in ROUNDS of kRound steps; in a round each lane makes up to kRound steps of its own phase,
 // and between rounds each lane, on its own, does its bookkeeping.  What a kernel adds is its MODE: a struct with the
 // step (kShip, or a step of its own: round_step below), whatever per-lane state it needs beyond RoundLane, and four
-// inlined hooks, named where they are called:
+// inlined hooks, named where they are called (a fifth, optional: round_converged below):
 //   NEXT     the lane's next sample, or DONE when it has none left.  mode.next draws c and says what becomes of it: it
 //            is iterated, or retired as drawn -- rejected (cardioid, bulb), or proven interior and counted as the
 //            reference counts a sample that never escapes -- and the next one drawn.  (max_iter 0 needs no case of its
@@ -115,6 +115,18 @@ template <class Mode>
 __device__ __forceinline__ double round_step(Mode &, RoundLane &l, long) {
   return orbit_step<Mode::kShip>(l.cr, l.ci, l.r, l.i);
 }
+
+// The convergent hook of a round: the mode's own `void converged(RoundLane &, LaneStats &, bool last)` where it has one,
+// else nothing.  run_rounds calls it with all 64 lanes of the wave active -- after every step of a round, whatever each
+// lane did in it, and once more (last = true) when no lane has work left, before the generators and the counters are
+// stored -- so a mode may do there what needs the whole wave: cross-lane work on what its lanes noted in mode.point.
+template <class Mode>
+__device__ __forceinline__ auto round_converged(Mode &mode, RoundLane &l, LaneStats &st, bool last, int)
+    -> decltype(mode.converged(l, st, last)) {
+  return mode.converged(l, st, last);
+}
+template <class Mode>
+__device__ __forceinline__ void round_converged(Mode &, RoundLane &, LaneStats &, bool, long) {}
 
 // The escape accounting of an escape render's mode (not the anti-Buddhabrot's, which records the other samples).
 // mode.escaped: the sample went l.end steps; through the accept filter min <= k < max, k = l.end - 1, to REPLAY (true).
@@ -194,6 +206,7 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
           l.k = stop;  // no more steps this round
         }
       }
+      round_converged(mode, l, st, false, 0);
     }
     bool replay = false;
     if (phase == kRoundReplay) {
@@ -220,6 +233,7 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
       phase = kRoundReplay;
     }
   }
+  round_converged(mode, l, st, true, 0);
   if (valid) store_rng(a.states, a.n_threads, tid, rng);
   flush_stats(a.counters, st);
 }

@@ -1,5 +1,6 @@
 // host_abi.cpp -- the entry points of the C ABI that are plain host arithmetic (no device call), kept apart from
 // capi.hip so that the sanitized CPU build (tests/asan) links them without the HIP runtime.
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -130,6 +131,59 @@ int cb_palette_from_stops(const cb_palette_stop *stops, int n_stops, uint32_t *l
       }
     }
     lut_out[k] = rgb[0] | (rgb[1] << 8) | (rgb[2] << 16);
+  }
+  return 0;
+}
+
+// ---- frames render: one rotation, and the matrices of a sweep (include/cudabrot_amd.h, "Frames render") -------------
+
+// The one place a projection is rotated: the `--rotate` flag (cli_args.cpp) and cb_frames_from_sweep both come here.
+int cb_rotate_projection(double p[8], int axis_x, int axis_y, double degrees) {
+  const int kInvalidValue = 1;  // hipErrorInvalidValue
+  if (!p || axis_x < 0 || axis_x > 3 || axis_y < 0 || axis_y > 3 || axis_x == axis_y || !isfinite(degrees)) {
+    return kInvalidValue;
+  }
+  // An integer multiple of 90 degrees uses exact 0 and +-1 (a permutation of the two columns with signs); otherwise the
+  // host's cos and sin.
+  double co, si;
+  const double quarters = degrees / 90.0;
+  if (quarters == floor(quarters)) {
+    const int q = (int) fmod(fmod(quarters, 4.0) + 4.0, 4.0);
+    co = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
+    si = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
+  } else {
+    const double radians = degrees * (M_PI / 180.0);
+    co = cos(radians);
+    si = sin(radians);
+  }
+  for (int row = 0; row < 2; ++row) {
+    const double a = p[4 * row + axis_x], b = p[4 * row + axis_y];
+    p[4 * row + axis_x] = (a * co - b * si) + 0.0;  // (+ 0.0: an exact zero is +0)
+    p[4 * row + axis_y] = (a * si + b * co) + 0.0;
+  }
+  return 0;
+}
+
+int cb_frames_from_sweep(const double base[8], int axis_x, int axis_y, double deg0, double deg1, int n_frames, double *out,
+                         double *angles_out) {
+  const int kInvalidValue = 1;  // hipErrorInvalidValue
+  if (!base || !out || axis_x < 0 || axis_x > 3 || axis_y < 0 || axis_y > 3 || axis_x == axis_y || !isfinite(deg0) ||
+      !isfinite(deg1) || n_frames < 1 || n_frames > CB_FRAMES_MAX) {
+    return kInvalidValue;
+  }
+  for (int j = 0; j < 8; ++j) {
+    if (!isfinite(base[j])) return kInvalidValue;
+  }
+  // (deg1 - deg0 of two finite angles can overflow: every a_f is looked at before anything is written)
+  for (int f = 0; f < n_frames; ++f) {
+    if (!isfinite(deg0 + ((deg1 - deg0) * (double) f) / (double) n_frames)) return kInvalidValue;
+  }
+  for (int f = 0; f < n_frames; ++f) {
+    const double a_f = deg0 + ((deg1 - deg0) * (double) f) / (double) n_frames;
+    double *p = out + 8 * (size_t) f;
+    memcpy(p, base, 8 * sizeof(double));  // every frame from the base, never from the frame before
+    (void) cb_rotate_projection(p, axis_x, axis_y, a_f);
+    if (angles_out) angles_out[f] = a_f;
   }
   return 0;
 }

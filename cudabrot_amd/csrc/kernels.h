@@ -305,6 +305,24 @@ struct DepthPaletteArgs {
 };
 hipError_t launch_draw_depth_palette(const DepthPaletteArgs &a, uint32_t n_entries, bool lockstep, hipStream_t stream);
 
+// draw_frames.hip: the frames render ("Frames render" of include/cudabrot_amd.h) -- a plotted launch without a table whose
+// visited points are plotted with n_frames matrices instead of one, each into a plane of its own.
+//   p        the launch of draw_plot.hip it extends: canvas, step and source of c as there; palette must be 0 and lut null;
+//            p.p is not read.  p.d.hist is n_frames planes plane_pixels counters apart.
+//   frames   the matrices on the device, n_frames x 8 doubles, each P[2][4] as PlotArgs::p, finite (the caller's word).
+//   n_frames F, 1 .. CB_FRAMES_MAX.
+//   plane_pixels   w * h.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of p, a table, null matrices, n_frames out of
+// range, a plane_pixels that is not w * h, n_frames * h above INT_MAX.  lockstep: the definition, one lane per reference
+// thread.
+struct FramesArgs {
+  PlotArgs p;
+  const double *frames;
+  int n_frames;
+  unsigned long long plane_pixels;
+};
+hipError_t launch_draw_frames(const FramesArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

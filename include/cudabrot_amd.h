@@ -643,6 +643,74 @@ int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel
                                      void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                      int kernel_variant, void *stream);
 
+/* ---- Frames render: F rotated (or otherwise projected) frames from one orbit pass ---- *
+ *
+ * The picture the 4-D set is known for is the turn: the Buddhabrot rotating into the bifurcation diagram.  The iteration
+ * is the part of a plotted render that does not depend on the plane, so one pass can serve every frame.  A FRAMES render
+ * is a projected render ("Projected render" above; julia_c NULL) or a Julia render ("Julia render"; julia_c given) with F
+ * matrices instead of one, and those sections, "Multibrot step" and "Formula step" apply unchanged but for the plot, the
+ * histogram and one counter.  The project's own definition.  Normative:
+ *
+ *   Inputs.  n_frames = F, 1 <= F <= CB_FRAMES_MAX; F matrices P_f[2][4], contiguous, 8 doubles each in the order of
+ *   "Projected render", every entry finite; F * h <= INT_MAX.  Anything else is hipErrorInvalidValue, with nothing
+ *   launched or written.
+ *
+ *   Unchanged.  The sample stream (four draws per sample), rejection, the interior map under
+ *   cb_draw_buddhabrot_projected's rule, the iteration, the escape index, the accept filter min <= k < max, and the
+ *   replayed points z_1 .. z_{k+1}.
+ *
+ *   Plot.  For every visited point and every f:
+ *     K_u = fma(P_f[0][2], c_re, P_f[0][3] * c_im)
+ *     u   = fma(P_f[0][0], z_re, fma(P_f[0][1], z_im, K_u))
+ *   and v likewise from row 1 -- the projected render's four fused operations -- then its binning.  A point on the canvas
+ *   of frame f adds 1 to its pixel of plane f.
+ *
+ *   Histogram.  F planes of w*h cb_pixel, plane f at offset f*w*h (64-bit arithmetic): the depth render's layout.
+ *
+ *   Counters.  increments counts the points added, over all planes.  Every other counter is what ONE projected or Julia
+ *   render with any one of the matrices counts: an accepted orbit counts once in recorded and its k+1 steps once in
+ *   replay_steps.  skipped_steps is the product kernel's executed-work discount; the lock-step kernel leaves it 0.
+ *
+ *   Consequence.  Plane f equals the histogram of cb_draw_buddhabrot_projected (or _julia) with P_f, bit for bit, under the
+ *   same dims, iteration control, variant, generators and launch sequence; the generator states and every counter but
+ *   increments are equal as well, and the frames render's increments is the sum of the F renders'.  F = 1 is that render
+ *   in everything.
+ *
+ *   Sweep -> matrices.  cb_frames_from_sweep below: frame f is `base` rotated in the (X, Y) coordinate plane by
+ *     a_f = deg0 + ((deg1 - deg0) * (double) f) / (double) n_frames
+ *   -- three fp64 operations in that order; deg1 is exclusive, so 0:360:F closes a loop -- with the arithmetic of
+ *   cb_rotate_projection, which is the `--rotate` flag's.  Every frame is made from `base`, never from the frame before.
+ *
+ *   Image.  As "Depth render", Image: M is the largest counter of all F planes, each counter maps to cb_tone_value(count,
+ *   M, gamma), and the file is F binary PGMs back to back, frame 0 first.  The common maximum is the point: the sequence
+ *   has one exposure.
+ *
+ * Two kernels (draw_frames.hip): CB_KERNEL_DEFAULT, one instance per step and per source of c, lanes refilled from their
+ * own subsequence, the visited points queued per wave in LDS and plotted 64 lanes wide; CB_KERNEL_SIMPLE, the definition
+ * in lock-step.  Variants and their refusals are cb_draw_buddhabrot_julia's.  Frames of a depth or palette render are out
+ * of scope and refused. */
+#define CB_FRAMES_MAX 256
+/* Rotates both rows of p in the (axis_x, axis_y) coordinate plane by `degrees`: with (a, b) the two entries of a row,
+ * a' = (a co - b si) + 0.0 and b' = (a si + b co) + 0.0 (an exact zero is +0).  An integer multiple of 90 degrees uses
+ * exact co, si in {0, +-1}; otherwise co = cos(degrees * (M_PI / 180.0)) and si = sin of the same, the host's.  Returns 0;
+ * hipErrorInvalidValue with p untouched for a NULL p, equal axes, an axis outside 0 .. 3 or a non-finite angle.  Host only. */
+int cb_rotate_projection(double p[8], int axis_x, int axis_y, double degrees);
+/* The matrices of a rotation sweep ("Frames render", Sweep -> matrices): out receives n_frames x 8 doubles, angles_out
+ * (may be NULL) the n_frames angles a_f.  hipErrorInvalidValue with out and angles_out untouched: a NULL base or out,
+ * equal axes or an axis outside 0 .. 3, a non-finite deg0, deg1 or entry of base, n_frames outside 1 .. CB_FRAMES_MAX.
+ * Host only. */
+int cb_frames_from_sweep(const double base[8], int axis_x, int axis_y, double deg0, double deg1, int n_frames, double *out,
+                         double *angles_out);
+/* The frames draw on caller-owned device memory: d_hist is F = n_frames planes of w*h cb_pixel, d_frames the F matrices ON
+ * THE DEVICE.  julia_c NULL: c is sampled.  The matrices are validated from a host copy: the call copies them back on
+ * `stream` and waits for it before it launches.  hipErrorInvalidValue, with nothing launched or written: a NULL d_frames,
+ * F outside 1 .. CB_FRAMES_MAX, a non-finite entry, F * h > INT_MAX, a julia_c outside [-2, 2]^2, and any kernel_variant
+ * cb_draw_buddhabrot_julia refuses (CB_KERNEL_FLAG_ANTI and CB_KERNEL_FLAG_DRAIN among them). */
+int cb_draw_buddhabrot_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                              const double *d_frames, int n_frames, const double julia_c[2], void *d_states,
+                              uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                              void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -737,6 +805,20 @@ int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const u
 /* A renderer's depth palette: returns 1, fills *out and sets *n_entries (either may be NULL); returns 0 and leaves them
  * alone for any other renderer (or a NULL renderer). */
 int cb_renderer_depth_palette(const cb_renderer *r, cb_depth *out, uint32_t *n_entries);
+/* Gives this renderer FRAMES ("Frames render" above); on a projected or Julia renderer, before its first pass, once -- the
+ * order on a renderer is projection, then julia, then frames.  frames_host is the n_frames matrices in HOST memory; they
+ * are copied to the device, and the histogram is reallocated and zeroed as F = n_frames planes.  The renderer's own
+ * projection is no longer plotted.  Every later cb_renderer_render_passes launches frames draws with the variants of the
+ * renderer it was; render_passes, finish, read / write_histogram (F planes), read_counters, the generator states and
+ * cb_renderer_grayscale_plane (planes 0 .. F - 1, each with its own maximum) work on the F planes.
+ * hipErrorInvalidValue for a plain, channel, focused or palette renderer, a renderer with a depth, a depth palette or
+ * frames already, a renderer that has rendered, and whatever "Frames render" refuses of the matrices.  Afterwards
+ * cb_renderer_set_palette, cb_renderer_set_depth, cb_renderer_set_depth_palette, cb_renderer_set_projection,
+ * cb_renderer_set_julia and cb_renderer_set_focus are refused. */
+int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_frames);
+/* A renderer's frames: returns F and fills out[8 F] (may be NULL); returns 0 and leaves it alone for a renderer without
+ * frames (or a NULL renderer). */
+int cb_renderer_frames(const cb_renderer *r, double *out);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -817,6 +899,11 @@ int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint1
  * hipErrorInvalidValue for a renderer without a depth. */
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                             double *scale_out);
+
+/* The image of a renderer with frames ("Frames render", Image): cb_renderer_depth_image's arithmetic and arguments on the
+ * F planes, frame 0 first.  hipErrorInvalidValue for a renderer without frames. */
+int cb_renderer_frames_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
+                             double *scale_out);
 
 /* The image of a renderer with a depth palette ("Depth-palette render", Image): cb_renderer_palette_image's arithmetic
  * and arguments on its three planes.  hipErrorInvalidValue for a renderer without a depth palette. */
@@ -919,7 +1006,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * (draw_plot_kernel: the three plotted draws with CB_KERNEL_FORMULA), 17 the formula lock-step kernel, 18 the depth
  * product kernel (draw_depth_kernel: cb_draw_buddhabrot_depth, whatever its step), 19 the depth lock-step kernel, 20 the
  * depth-palette product kernel (draw_depth_palette_kernel: cb_draw_buddhabrot_depth_palette, whatever its step), 21 the
- * depth-palette lock-step kernel.
+ * depth-palette lock-step kernel, 22 the frames product kernel (draw_frames_kernel: cb_draw_buddhabrot_frames, whatever
+ * its step), 23 the frames lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

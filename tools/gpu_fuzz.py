@@ -29,7 +29,11 @@ and demands identical histograms and counters.
                                                    (draw_depth_palette.hip) -- DEPTH's trials with a random table of N
                                                    entries (random weights with zeros among them, one colour, one-hot,
                                                    noise in the bits that are not read), three planes; TRIALS as there
-                                                   (and for ANTI and POWER: the four are rows of AB_MODES, one loop)
+                                                   (and for ANTI and POWER: the five are rows of AB_MODES, one loop)
+    FRAMES=1 python tools/gpu_fuzz.py ...          the frames render (cb_draw_buddhabrot_frames): draw_frames_kernel against
+                                                   draw_frames_simple_kernel (draw_frames.hip) -- DEPTH's step, source
+                                                   of c, canvas, window, thread count and launches with F <= 16 matrices
+                                                   (a sweep, unit planes, random entries, copies of one); TRIALS as there
 """
 import os
 
@@ -291,6 +295,46 @@ def render_depth(t, variant):
     return read(seq.launches(entry, t["launch_samples"], variant | flags, **args))
 
 
+def frames_trial(rng):
+    """A depth trial's step, source of c, canvas, window, iteration control, threads and launches, with F <= 16 matrices in
+    t["frames"]: a rotation sweep of the trial's matrix, unit planes, random entries, or copies of one matrix."""
+    t = depth_trial(rng)
+    n = rng.choice([1, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16])
+    kind = rng.random()
+    if kind < 0.4:
+        x, y = rng.sample(range(4), 2)
+        lo = rng.choice([0.0, 0.0, -90.0, rng.uniform(-360.0, 360.0)])
+        frames, _ = cb.frames_from_sweep(t["matrix"], (x, y), lo, lo + rng.choice([90.0, 360.0, rng.uniform(-400.0, 400.0)]), n)
+        t["frames"] = [float(v) for v in frames.reshape(-1)]
+    elif kind < 0.6:
+        t["frames"] = []
+        for _ in range(n):
+            x, y = rng.sample(range(4), 2)
+            t["frames"] += [1.0 if k == x else 0.0 for k in range(4)] + [1.0 if k == y else 0.0 for k in range(4)]
+    elif kind < 0.85:
+        t["frames"] = [rng.uniform(-1.5, 1.5) for _ in range(8 * n)]
+    else:
+        t["frames"] = list(t["matrix"]) * n
+    for k in ("matrix", "row", "slices", "window"):
+        del t[k]
+    return t
+
+
+def render_frames(t, variant):
+    """The launches of a frames trial -> (histogram, counters, generator states)."""
+    flags = ((cb.CB_KERNEL_POWER(t["degree"]) if t["degree"] != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
+             | (cb.CB_KERNEL_FORMULA(t["formula"]) if t["formula"] else 0))
+    n = len(t["frames"]) // 8
+    seq = Launches(cb, cb.FractalDimensions.make(t["w"], t["h"], *t["box"]), t["threads"], planes=n, seed=t["seed"],
+                   first=t["first"])
+    d_frames = seq.on_device(np.array(t["frames"], dtype=np.float64).view(np.uint64), np.uint64)  # alive to the read
+    out = read(seq.launches(cb.draw_buddhabrot_frames, t["launch_samples"], variant | flags,
+                            iterations=cb.IterationControl(t["max_iter"], t["min_iter"]), d_frames=d_frames.data_ptr(),
+                            n_frames=n, julia_c=t["c"]))
+    del d_frames
+    return out
+
+
 def sums_up(want, wc):
     return int(want.sum()) == wc["increments"]
 
@@ -307,6 +351,8 @@ AB_MODES = {
                   pixels_note="; increments %(increments)d", filled=True),
     "DEPTHPALETTE": dict(name="depth-palette", trial=depth_palette_trial, render=render_depth, kernels=(21, 20),
                          extra=sums_up, pixels_note="; increments %(increments)d", filled=True),
+    "FRAMES": dict(name="frames", trial=frames_trial, render=render_frames, kernels=(23, 22), extra=sums_up,
+                   pixels_note="; increments %(increments)d", filled=True),
 }
 
 
