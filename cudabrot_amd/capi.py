@@ -315,6 +315,10 @@ def _load():
         "cb_renderer_set_palette": (i32, [vp, vp, u32]),
         "cb_renderer_palette": (i32, [vp, C.POINTER(u32)]),
         "cb_renderer_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_draw_buddhabrot_phoenix": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), vp, u32, u32, vp, i32, vp]),
+        "cb_renderer_set_phoenix": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_renderer_phoenix": (i32, [vp, C.POINTER(C.c_double)]),
         "cb_draw_buddhabrot_depth": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), depth_p, vp, u32,
                                            u32, vp, i32, vp]),
         "cb_renderer_set_depth": (i32, [vp, depth_p]),
@@ -357,6 +361,7 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_depth cb_renderer_set_depth cb_renderer_depth cb_renderer_depth_image "
     "cb_draw_buddhabrot_depth_palette cb_renderer_set_depth_palette cb_renderer_depth_palette "
     "cb_renderer_depth_palette_image "
+    "cb_draw_buddhabrot_phoenix cb_renderer_set_phoenix cb_renderer_phoenix "
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
     "cb_renderer_frames_image"
 ).split()
@@ -504,6 +509,26 @@ def draw_buddhabrot_julia(dims, d_hist, iterations, projection, julia_c, d_state
                                      _julia_c(julia_c), d_states, n_threads, samples_per_thread, d_counters,
                                      kernel_variant, stream),
         "cb_draw_buddhabrot_julia",
+    )
+
+
+def _phoenix_p(p):
+    """The parameter of a Phoenix render, (p_re, p_im), as two C doubles."""
+    v = np.asarray(p, dtype=np.float64).reshape(-1)
+    if v.size != 2:
+        raise ValueError("a Phoenix parameter is two numbers: (p_re, p_im)")
+    return (C.c_double * 2)(float(v[0]), float(v[1]))
+
+
+def draw_buddhabrot_phoenix(dims, d_hist, iterations, projection, julia_c, phoenix_p, d_states, n_threads,
+                            samples_per_thread, d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The Phoenix draw on caller-owned device memory (cb_draw_buddhabrot_phoenix): the step z^2 + c + p z_prev;
+    julia_c None samples c (z_0 = c), else c is fixed and the sample is z_0.  One plane."""
+    _check(
+        lib.cb_draw_buddhabrot_phoenix(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                       None if julia_c is None else _julia_c(julia_c), _phoenix_p(phoenix_p), d_states,
+                                       n_threads, samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_phoenix",
     )
 
 
@@ -655,6 +680,18 @@ class Renderer:
         """The c of a Julia renderer as (c_re, c_im); None for any other renderer."""
         out = (C.c_double * 2)()
         if not lib.cb_renderer_julia(self._h, out):
+            return None
+        return float(out[0]), float(out[1])
+
+    def set_phoenix(self, phoenix_p):
+        """Give this renderer the Phoenix step with parameter p (cb_renderer_set_phoenix), before the first pass and after
+        set_projection or set_julia.  The histogram stays one plane."""
+        _check(lib.cb_renderer_set_phoenix(self._h, _phoenix_p(phoenix_p)), "cb_renderer_set_phoenix")
+
+    def phoenix(self):
+        """The p of a Phoenix renderer as (p_re, p_im); None for any other renderer."""
+        out = (C.c_double * 2)()
+        if not lib.cb_renderer_phoenix(self._h, out):
             return None
         return float(out[0]), float(out[1])
 

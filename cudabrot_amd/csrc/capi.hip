@@ -324,6 +324,10 @@ struct cb_renderer {
   int n_frames;
   double *d_frames;             // n_frames x 8 doubles
   std::vector<double> *frames;  // the same on the host (cb_renderer_frames)
+  // Phoenix render (cb_renderer_set_phoenix): a projected or Julia renderer whose draws take the step with memory and this
+  // parameter p; one plane
+  bool phoenix;
+  double phoenix_p[2];
 };
 
 namespace {
@@ -347,6 +351,9 @@ int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_ite
 int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                 const double *d_frames, int n_frames, const double julia_c[2], void *d_states, uint32_t n_threads,
                 uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
+int draw_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                 const double projection[8], const double julia_c[2], const double phoenix_p[2], void *d_states,
+                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream);
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
@@ -371,6 +378,12 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
       return draw_frames(&r->dims, r->d_hist, &r->iterations, r->d_frames, r->n_frames, r->julia ? r->julia_c : nullptr,
                          r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
                          &r->interior_level);
+    }
+    if (r->phoenix) {  // draw_phoenix.hip, likewise; it knows no interior map
+      r->interior_level = 0;
+      return draw_phoenix(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
+                          r->phoenix_p, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
+                          kernel_variant, r->stream);
     }
     return draw_plot(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
                      r->palette ? r->d_palette : nullptr, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
@@ -949,9 +962,11 @@ bool projection_ok(const double *p) {
 
 // The arguments of a plotted launch (draw_plot.hip, draw_depth.hip) from an entry point's, once its own have passed.
 // julia_c null: c is sampled; d_lut null: one plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.
+// interior false: the launch's step is not the Mandelbrot set's, whatever the variant says (draw_phoenix.hip): no map.
 int plot_args(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
               const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
-              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, cb::PlotArgs *out, bool *lockstep) {
+              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, cb::PlotArgs *out, bool *lockstep,
+              bool interior = true) {
   // A base of two and at most one of: a formula code CB_FORMULA_TRICORN .. CB_FORMULA_MAX ("Formula step"), a degree
   // CB_POWER_MIN .. CB_POWER_MAX ("Multibrot step"), the Burning Ship.  The plotted draws know neither anti nor drain.
   const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
@@ -985,7 +1000,7 @@ int plot_args(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iter
   // leaves that path a LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it
   // retires nothing through the map either.
   g_interior_level.store(0, std::memory_order_relaxed);
-  if (!julia_c && !power && formula == 0 && pa.d.long_steps > 0) {
+  if (interior && !julia_c && !power && formula == 0 && pa.d.long_steps > 0) {
     const int rc = attach_interior_map(pa.d, kernel_variant);
     if (rc) return rc;
   }
@@ -1094,6 +1109,29 @@ int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_it
   return rc;
 }
 
+// The parameter of a Phoenix render ("Phoenix render"): both parts in [-2, 2]; a NaN fails the comparisons.
+bool phoenix_p_ok(const double *p) { return p && p[0] >= -2.0 && p[0] <= 2.0 && p[1] >= -2.0 && p[1] <= 2.0; }
+
+// The Phoenix draws (draw_phoenix.hip): what cb_draw_buddhabrot_phoenix and a renderer with a p do once their own
+// arguments have passed.  The step is the render's own: a variant with any flag bit is refused here.
+int draw_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                 const double projection[8], const double julia_c[2], const double phoenix_p[2], void *d_states,
+                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
+  if (kernel_variant != CB_KERNEL_DEFAULT && kernel_variant != CB_KERNEL_SIMPLE) return (int) hipErrorInvalidValue;
+  cb::PhoenixArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  bool lockstep = false;
+  {
+    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads,
+                             samples_per_thread, d_counters, kernel_variant, &pa.plot, &lockstep, false);
+    if (rc) return rc;
+  }
+  pa.p[0] = phoenix_p[0];
+  pa.p[1] = phoenix_p[1];
+  g_last_draw_kernel.store(lockstep ? 25 : 24, std::memory_order_relaxed);
+  return (int) cb::launch_draw_phoenix(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
@@ -1195,7 +1233,7 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
   if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || r->depth_palette ||
-      r->n_frames || !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
+      r->n_frames || r->phoenix || !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
     return (int) hipErrorInvalidValue;
   }
   for (uint32_t k = 0; k < n_entries; ++k) {
@@ -1233,7 +1271,7 @@ int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist
 
 int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
   // a projected or Julia renderer (a palette renderer is projected too, a channel or focused one never is)
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
       !depth_ok(depth, r->dims.h)) {
     return (int) hipErrorInvalidValue;
   }
@@ -1266,7 +1304,7 @@ int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel
 
 int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const uint32_t *lut_host, uint32_t n_entries) {
   // where cb_renderer_set_depth is refused, and for a renderer that has a depth
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
       !depth_ok(depth, r->dims.h) || !lut_host || n_entries != (uint32_t) depth->slices) {
     return (int) hipErrorInvalidValue;
   }
@@ -1309,7 +1347,7 @@ int cb_draw_buddhabrot_frames(const cb_fractal_dimensions *dims, cb_pixel *d_his
 
 int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_frames) {
   // where cb_renderer_set_depth is refused, and for a renderer that has frames
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames ||
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
       !frames_ok(frames_host, n_frames, r->dims.h)) {
     return (int) hipErrorInvalidValue;
   }
@@ -1333,6 +1371,38 @@ int cb_renderer_frames(const cb_renderer *r, double *out) {
   if (!r || !r->n_frames) return 0;
   if (out) memcpy(out, r->frames->data(), r->frames->size() * sizeof(double));
   return r->n_frames;
+}
+
+// ---- Phoenix render (draw_phoenix.hip; include/cudabrot_amd.h, "Phoenix render") ------------------------------------
+
+int cb_draw_buddhabrot_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2], const double phoenix_p[2],
+                               void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                               int kernel_variant, void *stream) {
+  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
+  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  if (!phoenix_p_ok(phoenix_p)) return (int) hipErrorInvalidValue;
+  return draw_phoenix(dims, d_hist, iterations, projection, julia_c, phoenix_p, d_states, n_threads, samples_per_thread,
+                      d_counters, kernel_variant, stream);
+}
+
+int cb_renderer_set_phoenix(cb_renderer *r, const double phoenix_p[2]) {
+  // where cb_renderer_set_depth is refused, and for a renderer that has a p; the histogram stays the one plane it is
+  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
+      !phoenix_p_ok(phoenix_p)) {
+    return (int) hipErrorInvalidValue;
+  }
+  r->phoenix_p[0] = phoenix_p[0];
+  r->phoenix_p[1] = phoenix_p[1];
+  r->phoenix = true;
+  return 0;
+}
+
+int cb_renderer_phoenix(const cb_renderer *r, double out[2]) {
+  if (!r || !out || !r->phoenix) return 0;
+  out[0] = r->phoenix_p[0];
+  out[1] = r->phoenix_p[1];
+  return 1;
 }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
@@ -1432,10 +1502,15 @@ void prepare_for_variant(cb_renderer *r, int kernel_variant) {
   }
 }
 
+// A renderer with the Phoenix step takes the two base variants and no flag bit ("Phoenix render"): the step is its own.
+bool phoenix_variant_ok(const cb_renderer *r, int kernel_variant) {
+  return !r->phoenix || kernel_variant == CB_KERNEL_DEFAULT || kernel_variant == CB_KERNEL_SIMPLE;
+}
+
 }  // namespace
 
 int cb_renderer_prepare(cb_renderer *r, int kernel_variant) {
-  if (!r) return (int) hipErrorInvalidValue;
+  if (!r || !phoenix_variant_ok(r, kernel_variant)) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   prepare_for_variant(r, kernel_variant);
   return (int) hipDeviceSynchronize();
@@ -1446,6 +1521,7 @@ int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_varian
   if ((kernel_variant & (CB_KERNEL_POWER_MASK | CB_KERNEL_FORMULA_MASK)) != 0 && !r->projected) {
     return (int) hipErrorInvalidValue;  // a degree, a formula: on a projected, Julia or palette renderer only
   }
+  if (!phoenix_variant_ok(r, kernel_variant)) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   const uint32_t max_passes_per_launch = ::max_passes_per_launch();
   prepare_for_variant(r, kernel_variant);

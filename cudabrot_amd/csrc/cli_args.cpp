@@ -370,6 +370,13 @@ const std::vector<Flag> &flag_table() {
          s.julia = true;
          return parse_julia(t, s.julia_c) ? kOk : "Invalid julia parameter (want RE,IM, two numbers from -2 to 2)";
        }},
+      // --phoenix RE,IM: the Phoenix step z^2 + c + p z_prev with p = RE + IM i, a step with memory, on the projected path
+      // with any plane and with --julia (include/cudabrot_amd.h, "Phoenix render"); parsed as --julia's value is
+      {"--phoenix", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.phoenix = true;
+         return parse_julia(t, s.phoenix_p) ? kOk : "Invalid phoenix parameter (want RE,IM, two numbers from -2 to 2)";
+       }},
       // --palette K:RRGGBB[,K:RRGGBB...]: orbits coloured by their escape index: colour stops interpolated into a table of
       // -m entries, three planes of integer weights, -o receives a 16-bit PPM; on the projected path with any plane,
       // --power, --julia or --burning-ship (include/cudabrot_amd.h, "Palette render")
@@ -506,6 +513,8 @@ const Partner kRaw = {[](const Settings &s) { return s.raw_state; }, "--state-fo
 const Partner kPalette = {[](const Settings &s) { return s.palette(); }, "--palette"};
 const Partner kDepth = {[](const Settings &s) { return s.depth_given; }, "--depth"};
 const Partner kDepthPalette = {[](const Settings &s) { return s.depth_palette(); }, "--depth-palette"};
+const Partner kFormula = {[](const Settings &s) { return s.formula != 0; }, "--formula"};
+const Partner kSweep = {[](const Settings &s) { return s.sweep_given; }, "--sweep"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -558,10 +567,14 @@ const std::vector<Refusal> &refusal_table() {
       // --depth refuses, its row above has refused
       {[](const Settings &s) { return s.depth_palette() && !s.depth_given; }, nullptr, {},
        [](const Settings &) { printf("--depth-palette needs --depth.\n"); }},
-      // a frames render is a projected render with F planes (include/cudabrot_amd.h, "Frames render"); the last row: where
-      // an older row refuses the line, that row has spoken already
+      // a frames render is a projected render with F planes (include/cudabrot_amd.h, "Frames render"); behind every older
+      // row: where one of them refuses the line, that row has spoken already
       {[](const Settings &s) { return s.sweep_given; }, "--sweep",
        {kPalette, kDepth, kDepthPalette, kAnti, kFocus, kChannel, kGpus, kRaw}, nullptr},
+      // a Phoenix render is a projected or Julia render with a step of its own and one plane (include/cudabrot_amd.h,
+      // "Phoenix render"); the last row, likewise
+      {[](const Settings &s) { return s.phoenix; }, "--phoenix",
+       {kPower, kFormula, kShip, kPalette, kDepth, kDepthPalette, kSweep, kAnti, kFocus, kChannel, kGpus}, nullptr},
   };
   return table;
 }

@@ -75,7 +75,7 @@ struct Settings {
   // projection's
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
-  bool plotted() const { return projected() || depth_given || sweep_given; }
+  bool plotted() const { return projected() || depth_given || sweep_given || phoenix; }
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
@@ -87,6 +87,10 @@ struct Settings {
   // is `projection` as it stands when the flags have been read: the sweep is applied last, at most once.
   bool sweep_given = false;
   Sweep sweep = {0, 1, 0.0, 0.0, 0};
+  // --phoenix RE,IM (extension): the Phoenix step with p = RE + IM i (cb_renderer_set_phoenix); makes the run a projected
+  // one as --depth does, with a last refusal row of its own; combines with --julia
+  bool phoenix = false;
+  double phoenix_p[2] = {0.0, 0.0};
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

@@ -74,7 +74,7 @@ __device__ __forceinline__ bool brent_save(uint32_t chunks) {
 // time.  The wave advances in ROUNDS of kRound steps; in a round each lane makes up to kRound steps of its own phase,
 // and between rounds each lane, on its own, does its bookkeeping.  What a kernel adds is its MODE: a struct with the
 // step (kShip, or a step of its own: round_step below), whatever per-lane state it needs beyond RoundLane, and four
-// inlined hooks, named where they are called (a fifth, optional: round_converged below):
+// inlined hooks, named where they are called (more, optional: round_converged and the state hooks below):
 //   NEXT     the lane's next sample, or DONE when it has none left.  mode.next draws c and says what becomes of it: it
 //            is iterated, or retired as drawn -- rejected (cardioid, bulb), or proven interior and counted as the
 //            reference counts a sample that never escapes -- and the next one drawn.  (max_iter 0 needs no case of its
@@ -127,6 +127,35 @@ __device__ __forceinline__ auto round_converged(Mode &mode, RoundLane &l, LaneSt
 }
 template <class Mode>
 __device__ __forceinline__ void round_converged(Mode &, RoundLane &, LaneStats &, bool, long) {}
+
+// The state hooks of a round, for a step with memory -- one whose next point is a function of more than (z, c), so that
+// the mode keeps the rest of the orbit's state per lane.  Each is the mode's own where it has one, else nothing:
+//   void start(RoundLane &)   the orbit begins: run_rounds has set z = z_0 and k = 0, for ITERATE or for REPLAY, and the
+//                             mode sets the rest of its state to its beginning, so that the replay retraces the iteration;
+//   void save(RoundLane &)    run_rounds has saved z as the point of the exact-periodicity test, and the mode saves the rest;
+//   bool same(RoundLane &)    the rest of the state equals what save kept, bit for bit.  round_same forms the conjunction
+//                             with the scheduler's own same_bits(z, z_saved): a mode can only make the test stricter.  It
+//                             has to, where its step has memory: z_k == z_saved alone says nothing about z_{k+1} then.
+template <class Mode>
+__device__ __forceinline__ auto round_start(Mode &mode, RoundLane &l, int) -> decltype(mode.start(l)) {
+  return mode.start(l);
+}
+template <class Mode>
+__device__ __forceinline__ void round_start(Mode &, RoundLane &, long) {}
+template <class Mode>
+__device__ __forceinline__ auto round_save(Mode &mode, RoundLane &l, int) -> decltype(mode.save(l)) {
+  return mode.save(l);
+}
+template <class Mode>
+__device__ __forceinline__ void round_save(Mode &, RoundLane &, long) {}
+template <class Mode>
+__device__ __forceinline__ auto round_same(Mode &mode, RoundLane &l, bool z_same, int) -> decltype(mode.same(l)) {
+  return z_same && mode.same(l);
+}
+template <class Mode>
+__device__ __forceinline__ bool round_same(Mode &, RoundLane &, bool z_same, long) {
+  return z_same;
+}
 
 // The escape accounting of an escape render's mode (not the anti-Buddhabrot's, which records the other samples).
 // mode.escaped: the sample went l.end steps; through the accept filter min <= k < max, k = l.end - 1, to REPLAY (true).
@@ -181,6 +210,7 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
         l.i = l.ci;
         l.k = 0;
         l.saved = 0;
+        round_start(mode, l, 0);
         phase = kRoundIterate;
         break;
       }
@@ -216,7 +246,7 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
       if (!replay) phase = kRoundNext;
     } else if (phase == kRoundIterate) {
       const bool boundary = (l.k % kChunk) == 0;
-      const bool cycle = boundary && l.saved > 0 && same_bits(l.r, l.i, l.sr, l.si);
+      const bool cycle = round_same(mode, l, boundary && l.saved > 0 && same_bits(l.r, l.i, l.sr, l.si), 0);
       if (cycle || l.k == l.max_iter) {
         replay = mode.never_escapes(l, st, cycle);
         if (!replay) phase = kRoundNext;
@@ -224,12 +254,14 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
         l.sr = l.r;
         l.si = l.i;
         l.saved = l.k;
+        round_save(mode, l, 0);
       }
     }
     if (replay) {
       l.r = l.cr;
       l.i = l.ci;
       l.k = 0;
+      round_start(mode, l, 0);
       phase = kRoundReplay;
     }
   }

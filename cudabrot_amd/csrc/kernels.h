@@ -323,6 +323,20 @@ struct FramesArgs {
 };
 hipError_t launch_draw_frames(const FramesArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_phoenix.hip: the Phoenix render ("Phoenix render" of include/cudabrot_amd.h) -- a projected or Julia launch whose
+// step has memory: z_{n+1} = z_n^2 + c + p z_{n-1}.
+//   plot     the launch of draw_plot.hip it extends: canvas, matrix and source of c as there; degree must be 2, formula,
+//            d.burning_ship and palette 0 and lut null.  d.interior_map is not read: nothing is rejected or retired as
+//            drawn.
+//   p        the parameter (p_re, p_im), both in [-2, 2].
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of plot, a degree other than 2, a formula, the
+// Burning Ship, a table, a p outside [-2, 2], a NaN included.  lockstep: the definition, one lane per reference thread.
+struct PhoenixArgs {
+  PlotArgs plot;
+  double p[2];
+};
+hipError_t launch_draw_phoenix(const PhoenixArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

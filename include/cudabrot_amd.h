@@ -711,6 +711,64 @@ int cb_draw_buddhabrot_frames(const cb_fractal_dimensions *dims, cb_pixel *d_his
                               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                               void *stream);
 
+/* ---- Phoenix render: a step with memory, z^2 + c + p z_prev, on the projected path -------- *
+ *
+ * Every other step is memoryless: the next point is a function of (z, c).  The PHOENIX recurrence (Ushiki) is
+ * z_{n+1} = z_n^2 + c + p z_{n-1}; with real data it is the Henon map (c = -a, p = b).  A Phoenix render is a projected
+ * render ("Projected render"; julia_c NULL) or a Julia render ("Julia render"; julia_c given) with that step and one more
+ * parameter, p.  The project's own definition (the reference has none).  Normative:
+ *
+ *   Parameter.  phoenix_p[2] = (p_re, p_im), both finite and in [-2, 2]; anything else is hipErrorInvalidValue.  p = (0, 0)
+ *   is allowed.
+ *
+ *   Samples.  The normal stream: four XORWOW draws per sample, two coordinates (s_re, s_im) in [-2, 2)^2.  Without a fixed c
+ *   the sample is c and z_0 = c, as in a projected render; with julia_c the sample is z_0 and c is fixed, exactly as in
+ *   "Julia render".  Nothing is rejected, whatever p is: no cardioid or bulb test and no interior map (neither is valid for
+ *   p != 0, and one rule is simpler than two), so rejected = 0.
+ *
+ *   State and step.  The state of an orbit is the pair (z, y), y the point before z, and y_0 = 0.  With z = (r, i), one step
+ *   is mandel_step's four operations followed by four fused ones:
+ *       ii = i*i;  t = fma(r, r, -ii);  nr = cr + t;  ni = fma(r + r, i, ci);            (mandel_step, bit for bit)
+ *       nr = fma(p_re, y_re, nr);  nr = fma(-p_im, y_im, nr);
+ *       ni = fma(p_re, y_im, ni);  ni = fma( p_im, y_re, ni);
+ *       y = (r, i);  z = (nr, ni);  m = fma(ni, ni, nr*nr)                               (|z|^2 as tested)
+ *   -- IEEE fp64, every fma one rounding, nothing else contracted; the negation of p_im is exact.  The iteration and the
+ *   replay make the same step, so a replayed orbit retraces the tested one bit for bit.
+ *
+ *   Escape index.  k is the index of the first z_{k+1} with |z|^2 > 4 among z_1 ... z_max; if there is none, k = max and
+ *   the sample is never_escaped.  z_0 is neither tested nor plotted.
+ *
+ *   Accept filter and replay.  min <= k < max; the replay starts from (z_0, y_0 = 0) and visits z_1 ... z_{k+1}, the
+ *   escaping point included.
+ *
+ *   Plot.  The visited point is (z_re, z_im, c_re, c_im) under P[2][4]: K_u, K_v, u, v and the binning are the projected
+ *   render's, from the sample where c is sampled and from julia_c where it is fixed.  y is state, not a plotted
+ *   coordinate.
+ *
+ *   Counters keep their meaning; skipped_steps is the product kernel's executed-work discount, and the lock-step kernel
+ *   leaves it 0.
+ *
+ *   Every visited point is finite: |z_0|^2 <= 8; every later step follows a z with |z|^2 <= 4 and a y that is 0, z_0 or
+ *   such a z, so |z| <= 4 + 2 sqrt 2 + 2 sqrt 2 |p| at worst, |p| <= 2 sqrt 2.  Zero entries of P therefore contribute
+ *   exact +-0.
+ *
+ *   Consequences.  fma(+-0, finite, x) = x up to the sign of a zero, which changes neither an escape test nor a bin
+ *   ("Identity" above).  So with p = (0, 0) and julia_c = C the Phoenix render equals cb_draw_buddhabrot_julia with the same
+ *   C -- histogram, generator states and every counter but skipped_steps --, and with p = (0, 0) and a sampled c it equals
+ *   the projected render without its rejection and its interior map.
+ *
+ * Two kernels (draw_phoenix.hip): CB_KERNEL_DEFAULT, the round scheduler with one instance per source of c, and
+ * CB_KERNEL_SIMPLE, the definition in lock-step.  The scheduler's exact-periodicity test compares the whole state (z, y)
+ * with the saved one: for a step with memory z_k == z_saved alone proves nothing about z_{k+1}.  The step is the render's
+ * own, so ANY flag bit of kernel_variant -- the Burning Ship, anti, a power, a formula, drain -- is hipErrorInvalidValue with
+ * nothing launched or written.  Identical histograms, generator states and counters (but skipped_steps).  Direct atomics,
+ * no workspace, no carry: every launch is complete when it ends.  Plotting y (a 2 x 6 matrix), and Phoenix with a palette,
+ * a depth, frames, a focus, channels or the anti render, are out of scope and refused. */
+int cb_draw_buddhabrot_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2] /* NULL: sampled c */,
+                               const double phoenix_p[2], void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
+                               cb_counters *d_counters, int kernel_variant, void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -819,6 +877,19 @@ int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_fram
 /* A renderer's frames: returns F and fills out[8 F] (may be NULL); returns 0 and leaves it alone for a renderer without
  * frames (or a NULL renderer). */
 int cb_renderer_frames(const cb_renderer *r, double *out);
+/* Gives this renderer the PHOENIX step ("Phoenix render" above) with parameter p; on a projected or Julia renderer, before
+ * its first pass, once -- the order on a renderer is projection, then julia, then phoenix.  The histogram stays one plane:
+ * render_passes, prepare, finish, read / write_histogram, read_counters, the generator states and
+ * cb_renderer_grayscale_image work as for a Julia renderer.  Every later cb_renderer_render_passes / cb_renderer_prepare
+ * takes CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE without any flag bit: anything else is hipErrorInvalidValue.
+ * hipErrorInvalidValue for a plain, channel, focused or palette renderer, a renderer with a depth, a depth palette, frames
+ * or a p already, a renderer that has rendered, and a p that is not two numbers in [-2, 2].  Afterwards
+ * cb_renderer_set_palette, cb_renderer_set_depth, cb_renderer_set_depth_palette, cb_renderer_set_frames,
+ * cb_renderer_set_projection, cb_renderer_set_julia and cb_renderer_set_focus are refused. */
+int cb_renderer_set_phoenix(cb_renderer *r, const double phoenix_p[2]);
+/* A Phoenix renderer's p: returns 1 and fills out[2]; returns 0 and leaves `out` alone for any other renderer (or a NULL
+ * argument). */
+int cb_renderer_phoenix(const cb_renderer *r, double out[2]);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -1007,7 +1078,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * product kernel (draw_depth_kernel: cb_draw_buddhabrot_depth, whatever its step), 19 the depth lock-step kernel, 20 the
  * depth-palette product kernel (draw_depth_palette_kernel: cb_draw_buddhabrot_depth_palette, whatever its step), 21 the
  * depth-palette lock-step kernel, 22 the frames product kernel (draw_frames_kernel: cb_draw_buddhabrot_frames, whatever
- * its step), 23 the frames lock-step kernel.
+ * its step), 23 the frames lock-step kernel, 24 the Phoenix product kernel (draw_phoenix_kernel:
+ * cb_draw_buddhabrot_phoenix), 25 the Phoenix lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

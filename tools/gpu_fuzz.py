@@ -34,6 +34,11 @@ and demands identical histograms and counters.
                                                    draw_frames_simple_kernel (draw_frames.hip) -- DEPTH's step, source
                                                    of c, canvas, window, thread count and launches with F <= 16 matrices
                                                    (a sweep, unit planes, random entries, copies of one); TRIALS as there
+    PHOENIX=1 python tools/gpu_fuzz.py ...         the Phoenix render (cb_draw_buddhabrot_phoenix): draw_phoenix_kernel against
+                                                   draw_phoenix_simple_kernel (draw_phoenix.hip) -- DEPTH's source of c,
+                                                   canvas, window, matrix, iteration control, thread count and launches
+                                                   with a random p (zero, real, the classic -0.5, the corners, anywhere
+                                                   in [-2, 2]^2); TRIALS as there
 """
 import os
 
@@ -335,6 +340,33 @@ def render_frames(t, variant):
     return out
 
 
+def phoenix_trial(rng):
+    """A depth trial's source of c, canvas, window, matrix, iteration control, threads and launches, with a parameter p in
+    t["p"]; the step is the render's own."""
+    t = depth_trial(rng)
+    kind = rng.random()
+    if kind < 0.15:
+        t["p"] = (0.0, 0.0)
+    elif kind < 0.45:   # real p: with a real c and z_0 the Henon map
+        t["p"] = (rng.choice([-0.5, 0.25, 0.3, -1.0, rng.uniform(-1.0, 1.0)]), 0.0)
+    elif kind < 0.55:   # the ends of the range
+        t["p"] = (rng.choice([-2.0, 2.0]), rng.choice([-2.0, 0.0, 2.0]))
+    else:
+        t["p"] = (rng.uniform(-1.0, 1.0), rng.uniform(-1.0, 1.0)) if rng.random() < 0.7 else (rng.uniform(-2.0, 2.0),
+                                                                                            rng.uniform(-2.0, 2.0))
+    for k in ("degree", "ship", "formula", "row", "slices", "window"):
+        del t[k]
+    return t
+
+
+def render_phoenix(t, variant):
+    """The launches of a Phoenix trial -> (histogram, counters, generator states)."""
+    seq = Launches(cb, cb.FractalDimensions.make(t["w"], t["h"], *t["box"]), t["threads"], seed=t["seed"], first=t["first"])
+    return read(seq.launches(cb.draw_buddhabrot_phoenix, t["launch_samples"], variant,
+                             iterations=cb.IterationControl(t["max_iter"], t["min_iter"]), projection=t["matrix"],
+                             julia_c=t["c"], phoenix_p=t["p"]))
+
+
 def sums_up(want, wc):
     return int(want.sum()) == wc["increments"]
 
@@ -353,6 +385,9 @@ AB_MODES = {
                          extra=sums_up, pixels_note="; increments %(increments)d", filled=True),
     "FRAMES": dict(name="frames", trial=frames_trial, render=render_frames, kernels=(23, 22), extra=sums_up,
                    pixels_note="; increments %(increments)d", filled=True),
+    "PHOENIX": dict(name="phoenix", trial=phoenix_trial, render=render_phoenix, kernels=(25, 24),
+                    extra=lambda want, wc: sums_up(want, wc) and wc["rejected"] == 0,
+                    counters_note=", rejected %(rejected)d", pixels_note="; increments %(increments)d", filled=True),
 }
 
 
