@@ -627,10 +627,6 @@ class Renderer:
         self.iterations = iterations
         self.n_threads = n_threads
         self._h = C.c_void_p()
-        self.palette_entries = 0
-        self.depth_slices = 0
-        self.depth_palette_entries = 0
-        self.n_frames = 0
         if isinstance(iterations, IterationControl):
             self.n_channels = 0
             _check(
@@ -701,7 +697,6 @@ class Renderer:
         planes."""
         a = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
         _check(lib.cb_renderer_set_palette(self._h, a.ctypes.data, a.size), "cb_renderer_set_palette")
-        self.palette_entries = int(a.size)
 
     def palette(self):
         """The number of entries of a palette renderer's table; None for any other renderer."""
@@ -713,18 +708,13 @@ class Renderer:
     def palette_image(self, gamma=1.0, mode=0):
         """The image of a palette renderer (cb_renderer_palette_image) -> (big-endian u16 image [h,w,3] = the PPM body,
         the largest count of the three planes, scale)."""
-        rgb = np.empty((self.dims.h, self.dims.w, 3), dtype=">u2")
-        mx, scale = C.c_uint64(), C.c_double()
-        _check(lib.cb_renderer_palette_image(self._h, float(gamma), int(mode), rgb.ctypes.data, C.byref(mx),
-                                             C.byref(scale)), "cb_renderer_palette_image")
-        return rgb, int(mx.value), float(scale.value)
+        return self._image("cb_renderer_palette_image", (self.dims.h, self.dims.w, 3), gamma, mode)
 
     def set_depth(self, depth):
         """Give this renderer a depth (cb_renderer_set_depth), before the first pass and after set_projection or
         set_julia: depth is a Depth or (row, min, max[, slices]).  The histogram becomes `slices` planes."""
         d = _depth(depth)
         _check(lib.cb_renderer_set_depth(self._h, C.byref(d)), "cb_renderer_set_depth")
-        self.depth_slices = int(d.slices)
 
     def depth(self):
         """The depth of a renderer as a Depth; None for a renderer without one."""
@@ -736,11 +726,8 @@ class Renderer:
     def depth_image(self, gamma=1.0, mode=0):
         """The image of a renderer with a depth (cb_renderer_depth_image) -> (big-endian u16 images [slices, h, w] = the
         bodies of the PGM sequence, the largest count of all planes, scale)."""
-        gray = np.empty((max(self.depth_slices, 1), self.dims.h, self.dims.w), dtype=">u2")
-        mx, scale = C.c_uint64(), C.c_double()
-        _check(lib.cb_renderer_depth_image(self._h, float(gamma), int(mode), gray.ctypes.data, C.byref(mx),
-                                           C.byref(scale)), "cb_renderer_depth_image")
-        return gray, int(mx.value), float(scale.value)
+        slices = lib.cb_renderer_depth(self._h, None)
+        return self._image("cb_renderer_depth_image", (max(slices, 1), self.dims.h, self.dims.w), gamma, mode)
 
     def set_depth_palette(self, depth, lut):
         """Give this renderer a depth palette (cb_renderer_set_depth_palette), before the first pass and after
@@ -749,7 +736,6 @@ class Renderer:
         d = _depth(depth)
         a = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
         _check(lib.cb_renderer_set_depth_palette(self._h, C.byref(d), a.ctypes.data, a.size), "cb_renderer_set_depth_palette")
-        self.depth_palette_entries = int(a.size)
 
     def depth_palette(self):
         """(Depth, entries of the table) of a renderer with a depth palette; None for any other renderer."""
@@ -761,18 +747,13 @@ class Renderer:
     def depth_palette_image(self, gamma=1.0, mode=0):
         """The image of a renderer with a depth palette (cb_renderer_depth_palette_image) -> (big-endian u16 image [h,w,3] =
         the PPM body, the largest count of the three planes, scale)."""
-        rgb = np.empty((self.dims.h, self.dims.w, 3), dtype=">u2")
-        mx, scale = C.c_uint64(), C.c_double()
-        _check(lib.cb_renderer_depth_palette_image(self._h, float(gamma), int(mode), rgb.ctypes.data, C.byref(mx),
-                                                   C.byref(scale)), "cb_renderer_depth_palette_image")
-        return rgb, int(mx.value), float(scale.value)
+        return self._image("cb_renderer_depth_palette_image", (self.dims.h, self.dims.w, 3), gamma, mode)
 
     def set_frames(self, frames):
         """Give this renderer frames (cb_renderer_set_frames), before the first pass and after set_projection or
         set_julia: frames is F matrices, [F, 8].  The histogram becomes F planes."""
         a = _frames(frames)
         _check(lib.cb_renderer_set_frames(self._h, a.ctypes.data, a.shape[0]), "cb_renderer_set_frames")
-        self.n_frames = int(a.shape[0])
 
     def frames(self):
         """The matrices of a renderer with frames, [F, 8]; None for a renderer without them."""
@@ -786,16 +767,21 @@ class Renderer:
     def frames_image(self, gamma=1.0, mode=0):
         """The image of a renderer with frames (cb_renderer_frames_image) -> (big-endian u16 images [F, h, w] = the bodies
         of the PGM sequence, the largest count of all planes, scale)."""
-        gray = np.empty((max(self.n_frames, 1), self.dims.h, self.dims.w), dtype=">u2")
+        n = lib.cb_renderer_frames(self._h, None)
+        return self._image("cb_renderer_frames_image", (max(n, 1), self.dims.h, self.dims.w), gamma, mode)
+
+    def _image(self, name, shape, gamma, mode):
+        """One of the four image calls above into a big-endian u16 buffer of `shape` -> (image, largest count, scale)."""
+        out = np.empty(shape, dtype=">u2")
         mx, scale = C.c_uint64(), C.c_double()
-        _check(lib.cb_renderer_frames_image(self._h, float(gamma), int(mode), gray.ctypes.data, C.byref(mx),
-                                            C.byref(scale)), "cb_renderer_frames_image")
-        return gray, int(mx.value), float(scale.value)
+        _check(getattr(lib, name)(self._h, float(gamma), int(mode), out.ctypes.data, C.byref(mx), C.byref(scale)), name)
+        return out, int(mx.value), float(scale.value)
 
     def _planes(self):
-        if self.depth_slices or self.n_frames:
-            return self.depth_slices or self.n_frames
-        return 3 if self.palette_entries or self.depth_palette_entries else (self.n_channels or 1)
+        """The planes of the histogram, asked of the library; 0: the one plane that read_histogram returns as [h, w]."""
+        if lib.cb_renderer_palette(self._h, None) or lib.cb_renderer_depth_palette(self._h, None, None):
+            return 3
+        return lib.cb_renderer_depth(self._h, None) or lib.cb_renderer_frames(self._h, None) or self.n_channels
 
     def prepare(self, kernel_variant=CB_KERNEL_DEFAULT):
         """Allocate now what the first render_passes would (the scatter workspaces)."""
@@ -810,11 +796,9 @@ class Renderer:
 
     def read_histogram(self):
         planes = self._planes()
-        out = np.empty(planes * self.dims.w * self.dims.h, dtype=np.uint64)
+        out = np.empty(max(planes, 1) * self.dims.w * self.dims.h, dtype=np.uint64)
         _check(lib.cb_renderer_read_histogram(self._h, out.ctypes.data), "cb_renderer_read_histogram")
-        if self.n_channels or self.palette_entries or self.depth_slices or self.depth_palette_entries or self.n_frames:
-            return out.reshape(planes, self.dims.h, self.dims.w)
-        return out.reshape(self.dims.h, self.dims.w)
+        return out.reshape(planes, self.dims.h, self.dims.w) if planes else out.reshape(self.dims.h, self.dims.w)
 
     def read_rng_states(self):
         """True-resume checkpoint (N3): the generator states as bytes (six u32 planes of n_threads)."""
@@ -855,7 +839,7 @@ class Renderer:
 
     def write_histogram(self, hist):
         a = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
-        if a.size != self._planes() * self.dims.w * self.dims.h:
+        if a.size != max(self._planes(), 1) * self.dims.w * self.dims.h:
             raise ValueError("histogram size does not match the canvas")
         _check(lib.cb_renderer_write_histogram(self._h, a.ctypes.data), "cb_renderer_write_histogram")
 

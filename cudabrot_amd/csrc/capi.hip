@@ -260,6 +260,40 @@ constexpr double kEntriesPerSample = 2.5;
 // 32-bit entry indices.  Costs workspace: 2 x 23.7 GiB at 4096^2.
 constexpr uint32_t kRendererPassesPerLaunch = 128;
 
+// What a render is: the normal one (of a renderer: its n_channels windows fused, if any), the focused one, or a plotted one
+// (draw_plot.hip and its kin: direct atomics, no deferred scatter, no carry) named by its sink -- one plane, the palette's
+// three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one.  Whether c is sampled or fixed
+// (Plotted::julia) is the source beside it.  What varies with the kind is kind_row and draw_plotted's switch.
+enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix };
+bool is_plotted(Kind k) { return k != kNormal && k != kFocus; }
+
+// What every draw launch is given: the public entry points fill it from their arguments, a renderer from itself and the
+// passes asked for.
+struct Launch {
+  const cb_fractal_dimensions *dims;
+  cb_pixel *d_hist;
+  const cb_iteration_control *iterations;
+  void *d_states;
+  uint32_t n_threads, samples_per_thread;
+  cb_counters *d_counters;
+  int kernel_variant;
+  void *stream;
+};
+
+// What a plotted launch adds; a renderer keeps one as what it is (cb_renderer::what), and then owns the device memory.
+struct Plotted {
+  Kind kind;
+  double projection[8];  // the matrix P[2][4] (kFrames: kept for cb_renderer_projection, the launch takes `d_frames`)
+  bool julia;            // c is julia_c and the sample is z_0
+  double julia_c[2];
+  const uint32_t *d_lut;  // kPalette: n_entries = max_iter entries; kDepthPalette: n_entries = depth.slices entries
+  uint32_t n_entries;
+  cb_depth depth;          // kDepth, kDepthPalette
+  const double *d_frames;  // kFrames: n_frames x 8 doubles
+  int n_frames;
+  double phoenix_p[2];  // kPhoenix
+};
+
 }  // namespace
 
 struct cb_renderer {
@@ -285,7 +319,7 @@ struct cb_renderer {
   void *d_carry;
   bool carry_pending;
   int carry_variant;
-  // fused multi-channel render: n_channels > 0 windows, d_hist holds that many planes
+  // fused multi-channel render: n_channels > 0 windows, d_hist holds that many planes; a count of the normal kind only
   int n_channels;
   cb_iteration_control windows[CB_MAX_CHANNELS];
   // the level of the interior map this renderer's last launch used (0: none) -- its own record: the process-wide
@@ -294,71 +328,267 @@ struct cb_renderer {
   // what the generators were made from (cb_renderer_set_focus probes on fresh ones) and whether a pass was rendered
   uint64_t seed, first_subsequence;
   bool rendered;
-  // focused render (cb_renderer_set_focus): the grid's level (0: none), the cell list and the probe's step
+  // focused render (what.kind == kFocus): the grid's level (0: none), the cell list and the probe's step
   int focus_level;
   uint32_t *d_focus_cells;
   uint32_t focus_n_cells;
   bool focus_ship;
-  // projected render (cb_renderer_set_projection): the matrix P[2][4]
-  bool projected;
-  double projection[8];
-  // Julia render (cb_renderer_set_julia): a projected renderer whose draws take this fixed c and the sample as z_0
-  bool julia;
-  double julia_c[2];
-  // palette render (cb_renderer_set_palette): a projected or Julia renderer whose draws weigh orbits by this table; d_hist
-  // is then three planes
-  bool palette;
-  uint32_t *d_palette;
-  uint32_t palette_entries;
-  // depth render (cb_renderer_set_depth): a projected or Julia renderer whose draws bin along a third row; d_hist is then
-  // depth.slices planes
-  bool has_depth;
-  cb_depth depth;
-  // depth-palette render (cb_renderer_set_depth_palette): a projected or Julia renderer whose draws bin along `depth`'s row
-  // and weigh each point by the entry of its slice; d_hist is then three planes.  has_depth stays false: the planes are
-  // not the slices
-  bool depth_palette;
-  uint32_t *d_depth_lut;  // depth.slices entries
-  // frames render (cb_renderer_set_frames): a projected or Julia renderer whose draws plot with n_frames matrices; d_hist
-  // is then n_frames planes
-  int n_frames;
-  double *d_frames;             // n_frames x 8 doubles
-  std::vector<double> *frames;  // the same on the host (cb_renderer_frames)
-  // Phoenix render (cb_renderer_set_phoenix): a projected or Julia renderer whose draws take the step with memory and this
-  // parameter p; one plane
-  bool phoenix;
-  double phoenix_p[2];
+  // What the renderer is, and for a plotted kind what its launches add: the setters (`admits`) are the only writers.  d_hist
+  // has kind_row(what).planes planes, or n_channels.
+  Plotted what;
+  std::vector<double> *frames;  // kFrames: what.d_frames on the host (cb_renderer_frames)
 };
 
 namespace {
 
-// The planes of a renderer's histogram: the windows of a channel renderer, R, G and B of a palette or depth-palette
-// renderer, the slices of a renderer with a depth, else one.
-size_t renderer_planes(const cb_renderer *r) {
-  if (r->has_depth) return (size_t) r->depth.slices;
-  if (r->n_frames) return (size_t) r->n_frames;
-  return r->palette || r->depth_palette ? 3u : (r->n_channels ? (size_t) r->n_channels : 1u);
+enum Image { kImageSingle, kImageStacked, kImageRgb };
+
+// What varies with a render's kind beside the launch itself (draw_plotted's switch): the planes of its histogram, what its
+// image call makes of them (one gray plane; all planes one above the other, gray; three planes as R, G, B), and whether its
+// launches take a bare base variant only -- CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, no flag bit: the step is the render's.
+struct KindRow {
+  size_t planes;
+  Image image;
+  bool bare_variant;
+};
+KindRow kind_row(const Plotted &p) {
+  switch (p.kind) {
+    case kNormal: return {1, kImageSingle, false};  // (a channel renderer: n_channels planes, renderer_planes)
+    case kFocus: return {1, kImageSingle, false};
+    case kPlot: return {1, kImageSingle, false};
+    case kPalette: return {3, kImageRgb, false};
+    case kDepth: return {(size_t) p.depth.slices, kImageStacked, false};
+    case kDepthPalette: return {3, kImageRgb, false};
+    case kFrames: return {(size_t) p.n_frames, kImageStacked, false};
+    case kPhoenix: return {1, kImageSingle, true};
+  }
+  return {0, kImageSingle, false};  // (no kind)
 }
 
-int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
-              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
-int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-               const double projection[8], const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut,
-               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
-               int kernel_variant, void *stream, int *interior_level);
+size_t renderer_planes(const cb_renderer *r) { return r->n_channels ? (size_t) r->n_channels : kind_row(r->what).planes; }
 
-int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-                const double *d_frames, int n_frames, const double julia_c[2], void *d_states, uint32_t n_threads,
-                uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level);
-int draw_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-                 const double projection[8], const double julia_c[2], const double phoenix_p[2], void *d_states,
-                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream);
+bool variant_ok(const Plotted &p, int kernel_variant) {
+  return !kind_row(p).bare_variant || kernel_variant == CB_KERNEL_DEFAULT || kernel_variant == CB_KERNEL_SIMPLE;
+}
+
+// May the renderer become `want`?  The one rule of every setter: only before the first pass; a channel renderer, a focused
+// one and one with a sink stay what they are; a plain one takes a focus, a projection (with or without a fixed c) or a
+// palette, which brings the identity projection; a projected or Julia one without a sink takes any sink.
+bool admits(const cb_renderer *r, Kind want) {
+  if (!r || r->rendered || r->n_channels > 0) return false;
+  switch (r->what.kind) {
+    case kNormal: return want == kFocus || want == kPlot || want == kPalette;
+    case kPlot: return is_plotted(want) && want != kPlot;
+    case kFocus:
+    case kPalette:
+    case kDepth:
+    case kDepthPalette:
+    case kFrames:
+    case kPhoenix: return false;
+  }
+  return false;
+}
+
+// ---- what the setters and the entry points ask of their own arguments ------------------------------------------------
+
+const double kIdentityProjection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+
+bool projection_ok(const double *p) {
+  if (!p) return false;
+  for (int j = 0; j < 8; ++j) {
+    if (!isfinite(p[j])) return false;
+  }
+  return true;
+}
+
+bool julia_c_ok(const double *c) {  // both in [-2, 2]; a NaN fails the comparisons
+  return c && c[0] >= -2.0 && c[0] <= 2.0 && c[1] >= -2.0 && c[1] <= 2.0;
+}
+
+bool palette_entries_ok(uint32_t n_entries, const cb_iteration_control *iterations) {
+  return n_entries >= 1u && n_entries <= (uint32_t) CB_PALETTE_MAX_ENTRIES && iterations->max_escape_iterations >= 1 &&
+         (uint32_t) iterations->max_escape_iterations == n_entries;
+}
+
+// A table on the host, in the palette's entry format: the top byte of every entry is zero.
+bool lut_host_ok(const uint32_t *lut_host, uint32_t n_entries) {
+  if (!lut_host) return false;
+  for (uint32_t k = 0; k < n_entries; ++k) {
+    if ((lut_host[k] >> 24) != 0u) return false;
+  }
+  return true;
+}
+
+// The depth of a depth render ("Depth render"): finite row and bounds, min < max with a finite difference, N in range, and
+// N * h rows still an int (the planes are tone-mapped as one w x N*h image).
+bool depth_ok(const cb_depth *d, int h) {
+  if (!d) return false;
+  for (int j = 0; j < 4; ++j) {
+    if (!isfinite(d->row[j])) return false;
+  }
+  if (!isfinite(d->min) || !isfinite(d->max) || !(d->min < d->max) || !isfinite(d->max - d->min)) return false;
+  if (d->slices < 1 || d->slices > CB_DEPTH_MAX_SLICES) return false;
+  return (long long) d->slices * (long long) h <= 0x7fffffffLL;
+}
+
+// The matrices of a frames render ("Frames render"): F in range, every entry finite, and F * h rows still an int (the
+// planes are tone-mapped as one w x F*h image).
+bool frames_ok(const double *frames_host, int n_frames, int h) {
+  if (!frames_host || n_frames < 1 || n_frames > CB_FRAMES_MAX) return false;
+  for (int j = 0; j < 8 * n_frames; ++j) {
+    if (!isfinite(frames_host[j])) return false;
+  }
+  return (long long) n_frames * (long long) h <= 0x7fffffffLL;
+}
+
+// The parameter of a Phoenix render ("Phoenix render"): both parts in [-2, 2]; a NaN fails the comparisons.
+bool phoenix_p_ok(const double *p) { return p && p[0] >= -2.0 && p[0] <= 2.0 && p[1] >= -2.0 && p[1] <= 2.0; }
+
+// What every draw entry point asks of its pointers and its canvas.
+bool launch_ok(const Launch &l) {
+  return l.dims && l.iterations && l.d_hist && l.d_states && l.dims->w > 0 && l.dims->h > 0;
+}
+
+// *p = a plotted render of `kind` with this matrix and source of c (julia_c null: c is sampled) and nothing else yet;
+// false, *p untouched: a matrix or a c that does not pass.
+bool plotted_source(Plotted *p, Kind kind, const double *projection, const double *julia_c) {
+  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return false;
+  memset(p, 0, sizeof(*p));
+  p->kind = kind;
+  memcpy(p->projection, projection, sizeof(p->projection));
+  if (julia_c) {
+    p->julia = true;
+    p->julia_c[0] = julia_c[0];
+    p->julia_c[1] = julia_c[1];
+  }
+  return true;
+}
+
+// ---- the plotted launch (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip, draw_frames.hip, draw_phoenix.hip) ----
+
+// The arguments all plotted launches share, once the caller's own have passed.  julia_c null: c is sampled; d_lut null: one
+// plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.  interior false: the launch's step is not the
+// Mandelbrot set's, whatever the variant says (draw_phoenix.hip): no map.
+int plot_args(const Launch &l, const double projection[8], const double julia_c[2], const uint32_t *d_lut, bool interior,
+              cb::PlotArgs *out, bool *lockstep) {
+  // A base of two and at most one of: a formula code CB_FORMULA_TRICORN .. CB_FORMULA_MAX ("Formula step"), a degree
+  // CB_POWER_MIN .. CB_POWER_MAX ("Multibrot step"), the Burning Ship.  The plotted draws know neither anti nor drain.
+  const int kernel_variant = l.kernel_variant;
+  const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
+  const int degree_bits = (kernel_variant & CB_KERNEL_POWER_MASK) >> 12;
+  const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  const int base_variant = kernel_variant & ~(CB_KERNEL_FORMULA_MASK | CB_KERNEL_POWER_MASK | CB_KERNEL_FLAG_BURNING_SHIP);
+  const bool power = degree_bits != 0;
+  if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE) || formula > CB_FORMULA_MAX ||
+      (power && (degree_bits < CB_POWER_MIN || degree_bits > CB_POWER_MAX)) ||
+      (formula != 0 ? 1 : 0) + (power ? 1 : 0) + (ship ? 1 : 0) > 1) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::PlotArgs &pa = *out;
+  memset(&pa, 0, sizeof(pa));
+  pa.d = make_args(l.dims, l.iterations, l.d_hist, l.d_states, l.n_threads, l.samples_per_thread, l.d_counters, nullptr, 0,
+                   nullptr);
+  pa.d.burning_ship = ship ? 1 : 0;
+  memcpy(pa.p, projection, sizeof(pa.p));
+  pa.degree = power ? degree_bits : 2;
+  if (julia_c) {
+    pa.julia = 1;
+    pa.c[0] = julia_c[0];
+    pa.c[1] = julia_c[1];
+  }
+  pa.lut = d_lut;
+  pa.plane_pixels = (unsigned long long) l.dims->w * (unsigned long long) l.dims->h;
+  pa.formula = formula;
+  pa.palette = d_lut ? 1 : 0;
+  *lockstep = base_variant == CB_KERNEL_SIMPLE;
+  // The interior map (the Mandelbrot set's: a sampled c, degree 2, no formula) where the normal product path consults it:
+  // wants_interior_map's rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter
+  // leaves that path a LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it
+  // retires nothing through the map either.
+  g_interior_level.store(0, std::memory_order_relaxed);
+  if (interior && !julia_c && !power && formula == 0 && pa.d.long_steps > 0) {
+    const int rc = attach_interior_map(pa.d, kernel_variant);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// One plotted launch: what the seven cb_draw_buddhabrot_{projected .. phoenix} entry points and a plotted renderer do once
+// their own arguments have passed.  interior_level (may be null): the level of the interior map the launch used, 0 for none
+// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 25.
+int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
+  if (interior_level) *interior_level = 0;
+  if (!variant_ok(p, l.kernel_variant)) return (int) hipErrorInvalidValue;
+  cb::PlotArgs pa;
+  bool lockstep = false;
+  {
+    const int rc = plot_args(l, p.kind == kFrames ? kIdentityProjection : p.projection, p.julia ? p.julia_c : nullptr,
+                             p.kind == kPalette ? p.d_lut : nullptr, p.kind != kPhoenix, &pa, &lockstep);
+    if (rc) return rc;
+  }
+  const hipStream_t stream = reinterpret_cast<hipStream_t>(l.stream);
+  const auto report = [lockstep](int id) { g_last_draw_kernel.store(id + (lockstep ? 1 : 0), std::memory_order_relaxed); };
+  hipError_t e = hipErrorInvalidValue;
+  switch (p.kind) {
+    case kNormal:
+    case kFocus: break;  // (not plotted: cb_draw_buddhabrot, cb_draw_buddhabrot_focus)
+    case kPlot:
+    case kPalette:
+      report(pa.formula != 0 ? 16 : p.kind == kPalette ? 14 : p.julia ? 12 : pa.degree != 2 ? 10 : 8);
+      e = cb::launch_draw_plot(pa, lockstep, stream);
+      break;
+    case kDepth:
+    case kDepthPalette: {  // with a table of n_entries entries on the device: three planes; without: N
+      cb::DepthArgs da;
+      memset(&da, 0, sizeof(da));
+      da.p = pa;
+      memcpy(da.row, p.depth.row, sizeof(da.row));
+      da.min = p.depth.min;
+      da.delta = (p.depth.max - p.depth.min) / (double) p.depth.slices;  // as cb_recompute_pixel_deltas makes delta_imag
+      if (!(da.delta > 0.0) || !isfinite(da.delta)) return (int) hipErrorInvalidValue;  // (a window wider than a double)
+      da.pow2 = exact_reciprocal(da.delta, &da.inv_delta) ? 1 : 0;
+      da.slices = p.depth.slices;
+      da.plane_pixels = pa.plane_pixels;
+      if (p.kind == kDepthPalette) {
+        const cb::DepthPaletteArgs dpa = {da, p.d_lut, da.plane_pixels};
+        report(20);
+        e = cb::launch_draw_depth_palette(dpa, p.n_entries, lockstep, stream);
+      } else {
+        report(18);
+        e = cb::launch_draw_depth(da, lockstep, stream);
+      }
+      break;
+    }
+    case kFrames: {
+      cb::FramesArgs fa;
+      memset(&fa, 0, sizeof(fa));
+      fa.p = pa;
+      fa.frames = p.d_frames;
+      fa.n_frames = p.n_frames;
+      fa.plane_pixels = pa.plane_pixels;
+      report(22);
+      e = cb::launch_draw_frames(fa, lockstep, stream);
+      break;
+    }
+    case kPhoenix: {  // it knows no interior map
+      cb::PhoenixArgs xa;
+      memset(&xa, 0, sizeof(xa));
+      xa.plot = pa;
+      xa.p[0] = p.phoenix_p[0];
+      xa.p[1] = p.phoenix_p[1];
+      report(24);
+      e = cb::launch_draw_phoenix(xa, lockstep, stream);
+      break;
+    }
+  }
+  if (interior_level && e == hipSuccess && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
+  return (int) e;
+}
 
 // Adds one launch (or, with passes == 0, the drain of the carried work) and its flush to the
 // renderer's streams.
 int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
-  if (r->focus_level) {  // draw_focus.hip: direct atomics, no deferred scatter, no carry, no interior map
+  if (r->what.kind == kFocus) {  // draw_focus.hip: direct atomics, no deferred scatter, no carry, no interior map
     r->interior_level = 0;
     if (passes == 0) return 0;
     if (((kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0) != r->focus_ship) return (int) hipErrorInvalidValue;
@@ -366,28 +596,11 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
                                     passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->focus_level,
                                     r->d_focus_cells, r->focus_n_cells, r->stream);
   }
-  if (r->projected) {  // draw_plot.hip: direct atomics, no deferred scatter, no carry; what the setters took is checked
+  if (is_plotted(r->what.kind)) {  // what the setters took is checked
     if (passes == 0) return 0;
-    if (r->has_depth || r->depth_palette) {  // draw_depth.hip, draw_depth_palette.hip, likewise
-      return draw_depth(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr, &r->depth,
-                        r->depth_palette ? r->d_depth_lut : nullptr, r->depth_palette ? (uint32_t) r->depth.slices : 0u,
-                        r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
-                        &r->interior_level);
-    }
-    if (r->n_frames) {  // draw_frames.hip, likewise
-      return draw_frames(&r->dims, r->d_hist, &r->iterations, r->d_frames, r->n_frames, r->julia ? r->julia_c : nullptr,
-                         r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->stream,
-                         &r->interior_level);
-    }
-    if (r->phoenix) {  // draw_phoenix.hip, likewise; it knows no interior map
-      r->interior_level = 0;
-      return draw_phoenix(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
-                          r->phoenix_p, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD, r->d_counters,
-                          kernel_variant, r->stream);
-    }
-    return draw_plot(&r->dims, r->d_hist, &r->iterations, r->projection, r->julia ? r->julia_c : nullptr,
-                     r->palette ? r->d_palette : nullptr, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
-                     r->d_counters, kernel_variant, r->stream, &r->interior_level);
+    const Launch l = {&r->dims, r->d_hist, &r->iterations, r->d_states, r->n_threads, passes * CB_SAMPLES_PER_THREAD,
+                      r->d_counters, kernel_variant, r->stream};
+    return draw_plotted(l, r->what, &r->interior_level);
   }
   // the lock-step kernel and the anti kernels: direct atomics, no deferred scatter, no carry
   const bool wave = (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE && (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0;
@@ -464,7 +677,7 @@ int finish(cb_renderer *r) {
 // A cleared histogram of `planes` planes in the place of the renderer's first one and, with a table (lut_host not null), a
 // device copy of its n_entries in *d_lut: what the setters of a palette, a depth and a depth palette do once the renderer
 // has passed as theirs.  On failure nothing is kept and the renderer is as it was.
-int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint32_t n_entries, uint32_t **d_lut) {
+int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint32_t n_entries, const uint32_t **d_lut) {
   CB_TRY(hipSetDevice(r->device));
   CB_TRY(hipStreamSynchronize(r->stream));  // (the histogram's first memset)
   const size_t hist_bytes = planes * (size_t) r->dims.w * (size_t) r->dims.h * sizeof(cb_pixel);
@@ -488,7 +701,7 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
 }
 
 // `rows` rows of the histogram from `plane` on as one w x rows image, one maximum for all of it: finish, tone-map, copy
-// out.  What cb_renderer_grayscale_plane (one plane) and cb_renderer_depth_image (all of them) do after their checks.
+// out.  What cb_renderer_grayscale_plane (one plane) and kind_image (all of them) do after their checks.
 int gray_image(cb_renderer *r, size_t plane, int rows, double gamma, int mode, uint16_t *host_gray_be, uint64_t *max_out,
                double *scale_out) {
   CB_TRY(hipSetDevice(r->device));
@@ -895,8 +1108,8 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
 }
 
 int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
-  if (!r || r->n_channels > 0 || r->rendered || r->focus_level != 0 || r->projected || probe_passes == 0 || dilate < 0 ||
-      level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !focus_variant_ok(kernel_variant)) {
+  if (!admits(r, kFocus) || probe_passes == 0 || dilate < 0 || level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL ||
+      !focus_variant_ok(kernel_variant)) {
     return (int) hipErrorInvalidValue;
   }
   CB_TRY(hipSetDevice(r->device));
@@ -931,6 +1144,7 @@ int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int 
     (void) hipFree(d_cells);
     return rc;
   }
+  r->what.kind = kFocus;
   r->focus_level = level;
   r->d_focus_cells = d_cells;
   r->focus_n_cells = n_cells;
@@ -946,267 +1160,57 @@ int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n
   return 0;
 }
 
-// ---- projected render (draw_plot.hip; include/cudabrot_amd.h, "Projected render") -------------------------------
-
-namespace {
-
-const double kIdentityProjection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
-
-bool projection_ok(const double *p) {
-  if (!p) return false;
-  for (int j = 0; j < 8; ++j) {
-    if (!isfinite(p[j])) return false;
-  }
-  return true;
-}
-
-// The arguments of a plotted launch (draw_plot.hip, draw_depth.hip) from an entry point's, once its own have passed.
-// julia_c null: c is sampled; d_lut null: one plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.
-// interior false: the launch's step is not the Mandelbrot set's, whatever the variant says (draw_phoenix.hip): no map.
-int plot_args(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
-              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, cb::PlotArgs *out, bool *lockstep,
-              bool interior = true) {
-  // A base of two and at most one of: a formula code CB_FORMULA_TRICORN .. CB_FORMULA_MAX ("Formula step"), a degree
-  // CB_POWER_MIN .. CB_POWER_MAX ("Multibrot step"), the Burning Ship.  The plotted draws know neither anti nor drain.
-  const int formula = (kernel_variant & CB_KERNEL_FORMULA_MASK) >> 16;
-  const int degree_bits = (kernel_variant & CB_KERNEL_POWER_MASK) >> 12;
-  const bool ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
-  const int base_variant = kernel_variant & ~(CB_KERNEL_FORMULA_MASK | CB_KERNEL_POWER_MASK | CB_KERNEL_FLAG_BURNING_SHIP);
-  const bool power = degree_bits != 0;
-  if ((base_variant != CB_KERNEL_DEFAULT && base_variant != CB_KERNEL_SIMPLE) || formula > CB_FORMULA_MAX ||
-      (power && (degree_bits < CB_POWER_MIN || degree_bits > CB_POWER_MAX)) ||
-      (formula != 0 ? 1 : 0) + (power ? 1 : 0) + (ship ? 1 : 0) > 1) {
-    return (int) hipErrorInvalidValue;
-  }
-  cb::PlotArgs &pa = *out;
-  memset(&pa, 0, sizeof(pa));
-  pa.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  pa.d.burning_ship = ship ? 1 : 0;
-  memcpy(pa.p, projection, sizeof(pa.p));
-  pa.degree = power ? degree_bits : 2;
-  if (julia_c) {
-    pa.julia = 1;
-    pa.c[0] = julia_c[0];
-    pa.c[1] = julia_c[1];
-  }
-  pa.lut = d_lut;
-  pa.plane_pixels = (unsigned long long) dims->w * (unsigned long long) dims->h;
-  pa.formula = formula;
-  pa.palette = d_lut ? 1 : 0;
-  *lockstep = base_variant == CB_KERNEL_SIMPLE;
-  // The interior map (the Mandelbrot set's: a sampled c, degree 2, no formula) where the normal product path consults it:
-  // wants_interior_map's rule (not the lock-step kernel, not the Burning Ship, not with the knob), and only when max_iter
-  // leaves that path a LONG stage (max_iter > head + mid steps of plan_stages, 20 for min_iter <= 16) -- below that it
-  // retires nothing through the map either.
-  g_interior_level.store(0, std::memory_order_relaxed);
-  if (interior && !julia_c && !power && formula == 0 && pa.d.long_steps > 0) {
-    const int rc = attach_interior_map(pa.d, kernel_variant);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// The plotted draws (draw_plot.hip): what the three entry points below do once their own arguments have passed.
-// interior_level (may be null): the level of the interior map the launch used, 0 for none or when nothing was launched.
-int draw_plot(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-              const double projection[8], const double julia_c[2], const uint32_t *d_lut, void *d_states, uint32_t n_threads,
-              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
-  if (interior_level) *interior_level = 0;
-  cb::PlotArgs pa;
-  bool lockstep = false;
-  {
-    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
-                             d_counters, kernel_variant, &pa, &lockstep);
-    if (rc) return rc;
-  }
-  // cb_debug_last_draw_kernel names the entry point and the step: product / lock-step
-  const int id = pa.formula != 0 ? 16 : d_lut ? 14 : julia_c ? 12 : pa.degree != 2 ? 10 : 8;
-  g_last_draw_kernel.store(id + (lockstep ? 1 : 0), std::memory_order_relaxed);
-  const int rc = (int) cb::launch_draw_plot(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
-  if (interior_level && !rc && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
-  return rc;
-}
-
-// The depth of a depth render ("Depth render"): finite row and bounds, min < max with a finite difference, N in range, and
-// N * h rows still an int (the planes are tone-mapped as one w x N*h image).
-bool depth_ok(const cb_depth *d, int h) {
-  if (!d) return false;
-  for (int j = 0; j < 4; ++j) {
-    if (!isfinite(d->row[j])) return false;
-  }
-  if (!isfinite(d->min) || !isfinite(d->max) || !(d->min < d->max) || !isfinite(d->max - d->min)) return false;
-  if (d->slices < 1 || d->slices > CB_DEPTH_MAX_SLICES) return false;
-  return (long long) d->slices * (long long) h <= 0x7fffffffLL;
-}
-
-// The depth draws (draw_depth.hip, and with a table draw_depth_palette.hip): what cb_draw_buddhabrot_depth,
-// cb_draw_buddhabrot_depth_palette and a renderer with a depth or a depth palette do once their own arguments have passed.
-// d_lut null: N planes, no table; else the table of n_entries entries on the device and three planes.
-int draw_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-               const double projection[8], const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut,
-               uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
-               int kernel_variant, void *stream, int *interior_level) {
-  if (interior_level) *interior_level = 0;
-  cb::DepthArgs da;
-  memset(&da, 0, sizeof(da));
-  bool lockstep = false;
-  {
-    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads,
-                             samples_per_thread, d_counters, kernel_variant, &da.p, &lockstep);
-    if (rc) return rc;
-  }
-  memcpy(da.row, depth->row, sizeof(da.row));
-  da.min = depth->min;
-  da.delta = (depth->max - depth->min) / (double) depth->slices;  // as cb_recompute_pixel_deltas makes delta_imag
-  if (!(da.delta > 0.0) || !isfinite(da.delta)) return (int) hipErrorInvalidValue;  // (a window wider than a double)
-  da.pow2 = exact_reciprocal(da.delta, &da.inv_delta) ? 1 : 0;
-  da.slices = depth->slices;
-  da.plane_pixels = da.p.plane_pixels;
-  int rc;
-  if (d_lut) {
-    const cb::DepthPaletteArgs dpa = {da, d_lut, da.plane_pixels};
-    g_last_draw_kernel.store(lockstep ? 21 : 20, std::memory_order_relaxed);
-    rc = (int) cb::launch_draw_depth_palette(dpa, n_entries, lockstep, reinterpret_cast<hipStream_t>(stream));
-  } else {
-    g_last_draw_kernel.store(lockstep ? 19 : 18, std::memory_order_relaxed);
-    rc = (int) cb::launch_draw_depth(da, lockstep, reinterpret_cast<hipStream_t>(stream));
-  }
-  if (interior_level && !rc && da.p.d.interior_map) *interior_level = (int) da.p.d.interior_shift + 1;
-  return rc;
-}
-
-// The matrices of a frames render ("Frames render"): F in range, every entry finite, and F * h rows still an int (the
-// planes are tone-mapped as one w x F*h image).
-bool frames_ok(const double *frames_host, int n_frames, int h) {
-  if (!frames_host || n_frames < 1 || n_frames > CB_FRAMES_MAX) return false;
-  for (int j = 0; j < 8 * n_frames; ++j) {
-    if (!isfinite(frames_host[j])) return false;
-  }
-  return (long long) n_frames * (long long) h <= 0x7fffffffLL;
-}
-
-// The frames draws (draw_frames.hip): what cb_draw_buddhabrot_frames and a renderer with frames do once their own
-// arguments, the matrices' entries among them, have passed.
-int draw_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-                const double *d_frames, int n_frames, const double julia_c[2], void *d_states, uint32_t n_threads,
-                uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream, int *interior_level) {
-  if (interior_level) *interior_level = 0;
-  cb::FramesArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  bool lockstep = false;
-  {
-    const int rc = plot_args(dims, d_hist, iterations, kIdentityProjection, julia_c, nullptr, d_states, n_threads,
-                             samples_per_thread, d_counters, kernel_variant, &fa.p, &lockstep);
-    if (rc) return rc;
-  }
-  fa.frames = d_frames;
-  fa.n_frames = n_frames;
-  fa.plane_pixels = fa.p.plane_pixels;
-  g_last_draw_kernel.store(lockstep ? 23 : 22, std::memory_order_relaxed);
-  const int rc = (int) cb::launch_draw_frames(fa, lockstep, reinterpret_cast<hipStream_t>(stream));
-  if (interior_level && !rc && fa.p.d.interior_map) *interior_level = (int) fa.p.d.interior_shift + 1;
-  return rc;
-}
-
-// The parameter of a Phoenix render ("Phoenix render"): both parts in [-2, 2]; a NaN fails the comparisons.
-bool phoenix_p_ok(const double *p) { return p && p[0] >= -2.0 && p[0] <= 2.0 && p[1] >= -2.0 && p[1] <= 2.0; }
-
-// The Phoenix draws (draw_phoenix.hip): what cb_draw_buddhabrot_phoenix and a renderer with a p do once their own
-// arguments have passed.  The step is the render's own: a variant with any flag bit is refused here.
-int draw_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
-                 const double projection[8], const double julia_c[2], const double phoenix_p[2], void *d_states,
-                 uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
-  if (kernel_variant != CB_KERNEL_DEFAULT && kernel_variant != CB_KERNEL_SIMPLE) return (int) hipErrorInvalidValue;
-  cb::PhoenixArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  bool lockstep = false;
-  {
-    const int rc = plot_args(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads,
-                             samples_per_thread, d_counters, kernel_variant, &pa.plot, &lockstep, false);
-    if (rc) return rc;
-  }
-  pa.p[0] = phoenix_p[0];
-  pa.p[1] = phoenix_p[1];
-  g_last_draw_kernel.store(lockstep ? 25 : 24, std::memory_order_relaxed);
-  return (int) cb::launch_draw_phoenix(pa, lockstep, reinterpret_cast<hipStream_t>(stream));
-}
-
-}  // namespace
+// ---- the plotted renders (include/cudabrot_amd.h, "Projected render" .. "Phoenix render") ----------------------------
+//
+// Every entry point: the shared checks, its own, fill, draw_plotted.  Every setter: `admits`, its own checks, then the
+// renderer becomes what was asked for.
 
 int cb_draw_buddhabrot_projected(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
                                  const cb_iteration_control *iterations, const double projection[8], void *d_states,
                                  uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                  int kernel_variant, void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection)) return (int) hipErrorInvalidValue;
-  return draw_plot(dims, d_hist, iterations, projection, nullptr, nullptr, d_states, n_threads, samples_per_thread,
-                   d_counters, kernel_variant, stream, nullptr);
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kPlot, projection, nullptr)) return (int) hipErrorInvalidValue;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_projection(cb_renderer *r, const double projection[8]) {
-  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->projected || !projection_ok(projection)) {
-    return (int) hipErrorInvalidValue;
-  }
-  memcpy(r->projection, projection, sizeof(r->projection));
-  r->projected = true;
+  if (!admits(r, kPlot) || !plotted_source(&r->what, kPlot, projection, nullptr)) return (int) hipErrorInvalidValue;
   return 0;
 }
 
 int cb_renderer_projection(const cb_renderer *r, double out[8]) {
-  if (!r || !out || !r->projected) return 0;
-  memcpy(out, r->projection, sizeof(r->projection));
+  if (!r || !out || !is_plotted(r->what.kind)) return 0;
+  memcpy(out, r->what.projection, sizeof(r->what.projection));
   return 1;
 }
-
-// ---- Julia render (draw_plot.hip; include/cudabrot_amd.h, "Julia render") -------------------------------------------
-
-namespace {
-
-bool julia_c_ok(const double *c) {  // both in [-2, 2]; a NaN fails the comparisons
-  return c && c[0] >= -2.0 && c[0] <= 2.0 && c[1] >= -2.0 && c[1] <= 2.0;
-}
-
-}  // namespace
 
 int cb_draw_buddhabrot_julia(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                              const double projection[8], const double julia_c[2], void *d_states, uint32_t n_threads,
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection) || !julia_c_ok(julia_c)) return (int) hipErrorInvalidValue;
-  return draw_plot(dims, d_hist, iterations, projection, julia_c, nullptr, d_states, n_threads, samples_per_thread,
-                   d_counters, kernel_variant, stream, nullptr);
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !julia_c || !plotted_source(&p, kPlot, projection, julia_c)) return (int) hipErrorInvalidValue;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_julia(cb_renderer *r, const double projection[8], const double julia_c[2]) {
-  const double *p = projection ? projection : kIdentityProjection;
-  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->projected || !projection_ok(p) ||
-      !julia_c_ok(julia_c)) {
+  if (!admits(r, kPlot) || !julia_c ||
+      !plotted_source(&r->what, kPlot, projection ? projection : kIdentityProjection, julia_c)) {
     return (int) hipErrorInvalidValue;
   }
-  memcpy(r->projection, p, sizeof(r->projection));
-  r->julia_c[0] = julia_c[0];
-  r->julia_c[1] = julia_c[1];
-  r->projected = true;  // what cb_renderer_set_focus and cb_renderer_set_projection refuse
-  r->julia = true;
   return 0;
 }
 
 int cb_renderer_julia(const cb_renderer *r, double out[2]) {
-  if (!r || !out || !r->julia) return 0;
-  out[0] = r->julia_c[0];
-  out[1] = r->julia_c[1];
+  if (!r || !out || !r->what.julia) return 0;
+  out[0] = r->what.julia_c[0];
+  out[1] = r->what.julia_c[1];
   return 1;
 }
 
-// ---- palette render (draw_plot.hip; include/cudabrot_amd.h, "Palette render") ---------------------------------------
-
 namespace {
-
-bool palette_entries_ok(uint32_t n_entries, const cb_iteration_control *iterations) {
-  return n_entries >= 1u && n_entries <= (uint32_t) CB_PALETTE_MAX_ENTRIES && iterations->max_escape_iterations >= 1 &&
-         (uint32_t) iterations->max_escape_iterations == n_entries;
-}
 
 // out[3 i + j] = planes[j n + i]: the three planes of big-endian values as the R, G, B of a PPM body.
 __global__ void __launch_bounds__(256) interleave_planes_kernel(const uint16_t *planes, size_t n, uint16_t *out) {
@@ -1224,133 +1228,116 @@ int cb_draw_buddhabrot_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hi
                                const double projection[8], const double julia_c[2], const uint32_t *d_lut,
                                uint32_t n_entries, void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
                                cb_counters *d_counters, int kernel_variant, void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kPalette, projection, julia_c)) return (int) hipErrorInvalidValue;
   if (!d_lut || !palette_entries_ok(n_entries, iterations)) return (int) hipErrorInvalidValue;
-  return draw_plot(dims, d_hist, iterations, projection, julia_c, d_lut, d_states, n_threads, samples_per_thread,
-                   d_counters, kernel_variant, stream, nullptr);
+  p.d_lut = d_lut;
+  p.n_entries = n_entries;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries) {
-  if (!r || r->n_channels > 0 || r->focus_level != 0 || r->rendered || r->palette || r->has_depth || r->depth_palette ||
-      r->n_frames || r->phoenix || !lut_host || !palette_entries_ok(n_entries, &r->iterations)) {
+  if (!admits(r, kPalette) || !palette_entries_ok(n_entries, &r->iterations) || !lut_host_ok(lut_host, n_entries)) {
     return (int) hipErrorInvalidValue;
   }
-  for (uint32_t k = 0; k < n_entries; ++k) {
-    if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;
-  }
-  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->d_palette);
+  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->what.d_lut);
   if (rc) return rc;
-  r->palette_entries = n_entries;
-  r->palette = true;
-  if (!r->projected) {  // alone: the identity projection
-    memcpy(r->projection, kIdentityProjection, sizeof(r->projection));
-    r->projected = true;  // what cb_renderer_set_focus, cb_renderer_set_projection and cb_renderer_set_julia refuse
-  }
+  if (r->what.kind == kNormal) memcpy(r->what.projection, kIdentityProjection, sizeof(r->what.projection));  // alone
+  r->what.n_entries = n_entries;
+  r->what.kind = kPalette;
   return 0;
 }
 
 int cb_renderer_palette(const cb_renderer *r, uint32_t *n_entries) {
-  if (!r || !r->palette) return 0;
-  if (n_entries) *n_entries = r->palette_entries;
+  if (!r || r->what.kind != kPalette) return 0;
+  if (n_entries) *n_entries = r->what.n_entries;
   return 1;
 }
-
-// ---- depth render (draw_depth.hip; include/cudabrot_amd.h, "Depth render") ------------------------------------------
 
 int cb_draw_buddhabrot_depth(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                              const double projection[8], const double julia_c[2], const cb_depth *depth, void *d_states,
                              uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                              void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kDepth, projection, julia_c)) return (int) hipErrorInvalidValue;
   if (!depth_ok(depth, dims->h)) return (int) hipErrorInvalidValue;
-  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, nullptr, 0u, d_states, n_threads,
-                    samples_per_thread, d_counters, kernel_variant, stream, nullptr);
+  p.depth = *depth;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_depth(cb_renderer *r, const cb_depth *depth) {
-  // a projected or Julia renderer (a palette renderer is projected too, a channel or focused one never is)
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
-      !depth_ok(depth, r->dims.h)) {
-    return (int) hipErrorInvalidValue;
-  }
+  if (!admits(r, kDepth) || !depth_ok(depth, r->dims.h)) return (int) hipErrorInvalidValue;
   const int rc = swap_in_planes(r, (size_t) depth->slices, nullptr, 0u, nullptr);
   if (rc) return rc;
-  r->depth = *depth;
-  r->has_depth = true;
+  r->what.depth = *depth;
+  r->what.kind = kDepth;
   return 0;
 }
 
 int cb_renderer_depth(const cb_renderer *r, cb_depth *out) {
-  if (!r || !r->has_depth) return 0;
-  if (out) *out = r->depth;
-  return r->depth.slices;
+  if (!r || r->what.kind != kDepth) return 0;
+  if (out) *out = r->what.depth;
+  return r->what.depth.slices;
 }
-
-// ---- depth-palette render (draw_depth_palette.hip; include/cudabrot_amd.h, "Depth-palette render") -------------------
 
 int cb_draw_buddhabrot_depth_palette(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
                                      const cb_iteration_control *iterations, const double projection[8],
                                      const double julia_c[2], const cb_depth *depth, const uint32_t *d_lut, uint32_t n_entries,
                                      void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                      int kernel_variant, void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kDepthPalette, projection, julia_c)) return (int) hipErrorInvalidValue;
   if (!depth_ok(depth, dims->h) || !d_lut || n_entries != (uint32_t) depth->slices) return (int) hipErrorInvalidValue;
-  return draw_depth(dims, d_hist, iterations, projection, julia_c, depth, d_lut, n_entries, d_states, n_threads,
-                    samples_per_thread, d_counters, kernel_variant, stream, nullptr);
+  p.depth = *depth;
+  p.d_lut = d_lut;
+  p.n_entries = n_entries;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_depth_palette(cb_renderer *r, const cb_depth *depth, const uint32_t *lut_host, uint32_t n_entries) {
-  // where cb_renderer_set_depth is refused, and for a renderer that has a depth
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
-      !depth_ok(depth, r->dims.h) || !lut_host || n_entries != (uint32_t) depth->slices) {
+  if (!admits(r, kDepthPalette) || !depth_ok(depth, r->dims.h) || n_entries != (uint32_t) depth->slices ||
+      !lut_host_ok(lut_host, n_entries)) {
     return (int) hipErrorInvalidValue;
   }
-  for (uint32_t k = 0; k < n_entries; ++k) {
-    if ((lut_host[k] >> 24) != 0u) return (int) hipErrorInvalidValue;  // as cb_renderer_set_palette
-  }
-  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->d_depth_lut);
+  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->what.d_lut);
   if (rc) return rc;
-  r->depth = *depth;
-  r->depth_palette = true;
+  r->what.depth = *depth;
+  r->what.n_entries = n_entries;
+  r->what.kind = kDepthPalette;
   return 0;
 }
 
 int cb_renderer_depth_palette(const cb_renderer *r, cb_depth *out, uint32_t *n_entries) {
-  if (!r || !r->depth_palette) return 0;
-  if (out) *out = r->depth;
-  if (n_entries) *n_entries = (uint32_t) r->depth.slices;
+  if (!r || r->what.kind != kDepthPalette) return 0;
+  if (out) *out = r->what.depth;
+  if (n_entries) *n_entries = r->what.n_entries;
   return 1;
 }
-
-// ---- frames render (draw_frames.hip; include/cudabrot_amd.h, "Frames render") ---------------------------------------
 
 int cb_draw_buddhabrot_frames(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                               const double *d_frames, int n_frames, const double julia_c[2], void *d_states,
                               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                               void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!d_frames || n_frames < 1 || n_frames > CB_FRAMES_MAX || (julia_c && !julia_c_ok(julia_c))) {
-    return (int) hipErrorInvalidValue;
-  }
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kFrames, kIdentityProjection, julia_c)) return (int) hipErrorInvalidValue;
+  if (!d_frames || n_frames < 1 || n_frames > CB_FRAMES_MAX) return (int) hipErrorInvalidValue;
   // the matrices are the caller's device memory: their entries are looked at in a host copy, made on the caller's stream
   std::vector<double> copy(8 * (size_t) n_frames);
   CB_TRY(hipMemcpyAsync(copy.data(), d_frames, copy.size() * sizeof(double), hipMemcpyDeviceToHost,
                         reinterpret_cast<hipStream_t>(stream)));
   CB_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
   if (!frames_ok(copy.data(), n_frames, dims->h)) return (int) hipErrorInvalidValue;
-  return draw_frames(dims, d_hist, iterations, d_frames, n_frames, julia_c, d_states, n_threads, samples_per_thread,
-                     d_counters, kernel_variant, stream, nullptr);
+  p.d_frames = d_frames;
+  p.n_frames = n_frames;
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_frames) {
-  // where cb_renderer_set_depth is refused, and for a renderer that has frames
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
-      !frames_ok(frames_host, n_frames, r->dims.h)) {
-    return (int) hipErrorInvalidValue;
-  }
+  if (!admits(r, kFrames) || !frames_ok(frames_host, n_frames, r->dims.h)) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   const size_t bytes = 8 * (size_t) n_frames * sizeof(double);
   double *d_frames = nullptr;
@@ -1361,47 +1348,44 @@ int cb_renderer_set_frames(cb_renderer *r, const double *frames_host, int n_fram
     (void) hipFree(d_frames);
     return rc;
   }
-  r->d_frames = d_frames;
   r->frames = new std::vector<double>(frames_host, frames_host + 8 * (size_t) n_frames);
-  r->n_frames = n_frames;
+  r->what.d_frames = d_frames;
+  r->what.n_frames = n_frames;
+  r->what.kind = kFrames;
   return 0;
 }
 
 int cb_renderer_frames(const cb_renderer *r, double *out) {
-  if (!r || !r->n_frames) return 0;
+  if (!r || r->what.kind != kFrames) return 0;
   if (out) memcpy(out, r->frames->data(), r->frames->size() * sizeof(double));
-  return r->n_frames;
+  return r->what.n_frames;
 }
-
-// ---- Phoenix render (draw_phoenix.hip; include/cudabrot_amd.h, "Phoenix render") ------------------------------------
 
 int cb_draw_buddhabrot_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                                const double projection[8], const double julia_c[2], const double phoenix_p[2],
                                void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
                                int kernel_variant, void *stream) {
-  if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!projection_ok(projection) || (julia_c && !julia_c_ok(julia_c))) return (int) hipErrorInvalidValue;
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kPhoenix, projection, julia_c)) return (int) hipErrorInvalidValue;
   if (!phoenix_p_ok(phoenix_p)) return (int) hipErrorInvalidValue;
-  return draw_phoenix(dims, d_hist, iterations, projection, julia_c, phoenix_p, d_states, n_threads, samples_per_thread,
-                      d_counters, kernel_variant, stream);
+  p.phoenix_p[0] = phoenix_p[0];
+  p.phoenix_p[1] = phoenix_p[1];
+  return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_phoenix(cb_renderer *r, const double phoenix_p[2]) {
-  // where cb_renderer_set_depth is refused, and for a renderer that has a p; the histogram stays the one plane it is
-  if (!r || !r->projected || r->palette || r->rendered || r->has_depth || r->depth_palette || r->n_frames || r->phoenix ||
-      !phoenix_p_ok(phoenix_p)) {
-    return (int) hipErrorInvalidValue;
-  }
-  r->phoenix_p[0] = phoenix_p[0];
-  r->phoenix_p[1] = phoenix_p[1];
-  r->phoenix = true;
+  if (!admits(r, kPhoenix) || !phoenix_p_ok(phoenix_p)) return (int) hipErrorInvalidValue;  // the histogram stays one plane
+  r->what.phoenix_p[0] = phoenix_p[0];
+  r->what.phoenix_p[1] = phoenix_p[1];
+  r->what.kind = kPhoenix;
   return 0;
 }
 
 int cb_renderer_phoenix(const cb_renderer *r, double out[2]) {
-  if (!r || !out || !r->phoenix) return 0;
-  out[0] = r->phoenix_p[0];
-  out[1] = r->phoenix_p[1];
+  if (!r || !out || r->what.kind != kPhoenix) return 0;
+  out[0] = r->what.phoenix_p[0];
+  out[1] = r->what.phoenix_p[1];
   return 1;
 }
 
@@ -1478,7 +1462,7 @@ void prepare_for_variant(cb_renderer *r, int kernel_variant) {
       g_wave_dump = nullptr;
     }
   }
-  if (!r->workspace_tried && r->focus_level == 0 && !r->projected &&  // the focus and projection kernels add directly
+  if (!r->workspace_tried && r->what.kind == kNormal &&  // the focus and plotted kernels add directly
       (kernel_variant & ~kVariantFlags) != CB_KERNEL_SIMPLE &&
       (kernel_variant & CB_KERNEL_FLAG_ANTI) == 0 &&  // the anti kernels add directly
       cb_debug_knob("CUDABROT_AMD_NO_WORKSPACE") == nullptr) {
@@ -1502,15 +1486,10 @@ void prepare_for_variant(cb_renderer *r, int kernel_variant) {
   }
 }
 
-// A renderer with the Phoenix step takes the two base variants and no flag bit ("Phoenix render"): the step is its own.
-bool phoenix_variant_ok(const cb_renderer *r, int kernel_variant) {
-  return !r->phoenix || kernel_variant == CB_KERNEL_DEFAULT || kernel_variant == CB_KERNEL_SIMPLE;
-}
-
 }  // namespace
 
 int cb_renderer_prepare(cb_renderer *r, int kernel_variant) {
-  if (!r || !phoenix_variant_ok(r, kernel_variant)) return (int) hipErrorInvalidValue;
+  if (!r || !variant_ok(r->what, kernel_variant)) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   prepare_for_variant(r, kernel_variant);
   return (int) hipDeviceSynchronize();
@@ -1518,10 +1497,10 @@ int cb_renderer_prepare(cb_renderer *r, int kernel_variant) {
 
 int cb_renderer_render_passes(cb_renderer *r, uint32_t passes, int kernel_variant) {
   if (!r) return (int) hipErrorInvalidValue;
-  if ((kernel_variant & (CB_KERNEL_POWER_MASK | CB_KERNEL_FORMULA_MASK)) != 0 && !r->projected) {
+  if ((kernel_variant & (CB_KERNEL_POWER_MASK | CB_KERNEL_FORMULA_MASK)) != 0 && !is_plotted(r->what.kind)) {
     return (int) hipErrorInvalidValue;  // a degree, a formula: on a projected, Julia or palette renderer only
   }
-  if (!phoenix_variant_ok(r, kernel_variant)) return (int) hipErrorInvalidValue;
+  if (!variant_ok(r->what, kernel_variant)) return (int) hipErrorInvalidValue;  // (a Phoenix renderer)
   CB_TRY(hipSetDevice(r->device));
   const uint32_t max_passes_per_launch = ::max_passes_per_launch();
   prepare_for_variant(r, kernel_variant);
@@ -1590,11 +1569,10 @@ int cb_renderer_grayscale_plane(cb_renderer *r, int plane, double gamma, int mod
 
 namespace {
 
-// The image of three planes R, G, B ("Palette render", Image): what cb_renderer_palette_image and
-// cb_renderer_depth_palette_image do once the renderer has passed as theirs.
+// The image of three planes R, G, B ("Palette render", Image).
 int three_plane_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                       double *scale_out) {
-  if (!host_rgb_be || r->dims.h > 0x7fffffff / 3) return (int) hipErrorInvalidValue;
+  if (r->dims.h > 0x7fffffff / 3) return (int) hipErrorInvalidValue;
   CB_TRY(hipSetDevice(r->device));
   {
     int rc = finish(r);
@@ -1620,32 +1598,41 @@ int three_plane_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *hos
   return rc;
 }
 
+// The image of a renderer of `kind` and no other, all its planes under one maximum: what the four cb_renderer_*_image calls
+// of the plotted kinds do.
+int kind_image(cb_renderer *r, Kind kind, double gamma, int tone_mode, uint16_t *host_be, uint64_t *max_out,
+               double *scale_out) {
+  if (!r || r->what.kind != kind || !host_be) return (int) hipErrorInvalidValue;
+  const KindRow row = kind_row(r->what);
+  switch (row.image) {
+    case kImageRgb: return three_plane_image(r, gamma, tone_mode, host_be, max_out, scale_out);
+    case kImageSingle:
+    case kImageStacked:  // one w x N*h image (N * h fits an int: depth_ok, frames_ok)
+      return gray_image(r, 0, (int) row.planes * r->dims.h, gamma, tone_mode, host_be, max_out, scale_out);
+  }
+  return (int) hipErrorInvalidValue;
+}
+
 }  // namespace
 
 int cb_renderer_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                               double *scale_out) {
-  if (!r || !r->palette) return (int) hipErrorInvalidValue;
-  return three_plane_image(r, gamma, tone_mode, host_rgb_be, max_out, scale_out);
+  return kind_image(r, kPalette, gamma, tone_mode, host_rgb_be, max_out, scale_out);
 }
 
 int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                                     double *scale_out) {
-  if (!r || !r->depth_palette) return (int) hipErrorInvalidValue;
-  return three_plane_image(r, gamma, tone_mode, host_rgb_be, max_out, scale_out);
+  return kind_image(r, kDepthPalette, gamma, tone_mode, host_rgb_be, max_out, scale_out);
 }
 
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                             double *scale_out) {
-  if (!r || !r->has_depth || !host_gray_be) return (int) hipErrorInvalidValue;
-  // the planes as one w x N*h image: one maximum for all of them (N * h fits an int: cb_renderer_set_depth)
-  return gray_image(r, 0, r->depth.slices * r->dims.h, gamma, tone_mode, host_gray_be, max_out, scale_out);
+  return kind_image(r, kDepth, gamma, tone_mode, host_gray_be, max_out, scale_out);
 }
 
 int cb_renderer_frames_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                              double *scale_out) {
-  if (!r || !r->n_frames || !host_gray_be) return (int) hipErrorInvalidValue;
-  // likewise: one w x F*h image (F * h fits an int: cb_renderer_set_frames)
-  return gray_image(r, 0, r->n_frames * r->dims.h, gamma, tone_mode, host_gray_be, max_out, scale_out);
+  return kind_image(r, kFrames, gamma, tone_mode, host_gray_be, max_out, scale_out);
 }
 
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
@@ -1733,9 +1720,8 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_counters);
   (void) hipFree(r->d_carry);
   (void) hipFree(r->d_focus_cells);
-  (void) hipFree(r->d_palette);
-  (void) hipFree(r->d_depth_lut);
-  (void) hipFree(r->d_frames);
+  (void) hipFree(const_cast<uint32_t *>(r->what.d_lut));
+  (void) hipFree(const_cast<double *>(r->what.d_frames));
   delete r->frames;
   (void) hipFree(r->d_workspace[0]);
   (void) hipFree(r->d_workspace[1]);
@@ -1757,8 +1743,9 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
   for (int k = 0; k < n; ++k) {
     cb_renderer *r = renderers[k];
     if (!r || r->dims.w != renderers[0]->dims.w || r->dims.h != renderers[0]->dims.h ||
-        r->n_channels != renderers[0]->n_channels || r->palette != renderers[0]->palette ||
-        r->depth_palette != renderers[0]->depth_palette ||
+        r->n_channels != renderers[0]->n_channels ||
+        (r->what.kind == kPalette) != (renderers[0]->what.kind == kPalette) ||
+        (r->what.kind == kDepthPalette) != (renderers[0]->what.kind == kDepthPalette) ||
         renderer_planes(r) != renderer_planes(renderers[0])) {
       return (int) hipErrorInvalidValue;
     }
