@@ -319,6 +319,10 @@ def _load():
                                              C.POINTER(C.c_double), vp, u32, u32, vp, i32, vp]),
         "cb_renderer_set_phoenix": (i32, [vp, C.POINTER(C.c_double)]),
         "cb_renderer_phoenix": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_draw_buddhabrot_bounded": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, u32,
+                                             vp, i32, vp]),
+        "cb_renderer_set_bounded": (i32, [vp]),
+        "cb_renderer_bounded": (i32, [vp]),
         "cb_draw_buddhabrot_depth": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), depth_p, vp, u32,
                                            u32, vp, i32, vp]),
         "cb_renderer_set_depth": (i32, [vp, depth_p]),
@@ -362,6 +366,7 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_depth_palette cb_renderer_set_depth_palette cb_renderer_depth_palette "
     "cb_renderer_depth_palette_image "
     "cb_draw_buddhabrot_phoenix cb_renderer_set_phoenix cb_renderer_phoenix "
+    "cb_draw_buddhabrot_bounded cb_renderer_set_bounded cb_renderer_bounded "
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
     "cb_renderer_frames_image"
 ).split()
@@ -532,6 +537,19 @@ def draw_buddhabrot_phoenix(dims, d_hist, iterations, projection, julia_c, phoen
     )
 
 
+def draw_buddhabrot_bounded(dims, d_hist, iterations, projection, julia_c, d_states, n_threads, samples_per_thread,
+                            d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The bounded draw on caller-owned device memory (cb_draw_buddhabrot_bounded): the orbits that never escape, z_1 ..
+    z_max, plotted at P (z_re, z_im, c_re, c_im); julia_c None samples c (z_0 = c), else c is fixed and the sample is z_0.
+    One plane."""
+    _check(
+        lib.cb_draw_buddhabrot_bounded(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                       None if julia_c is None else _julia_c(julia_c), d_states, n_threads,
+                                       samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_bounded",
+    )
+
+
 def palette_from_stops(stops, n_entries):
     """The table of a list of colour stops (cb_palette_from_stops): stops = [(k, r, g, b), ...], k ascending -> u32 array
     of n_entries entries, entry k = r | g << 8 | b << 16 of an orbit with escape index k."""
@@ -683,6 +701,16 @@ class Renderer:
         """Give this renderer the Phoenix step with parameter p (cb_renderer_set_phoenix), before the first pass and after
         set_projection or set_julia.  The histogram stays one plane."""
         _check(lib.cb_renderer_set_phoenix(self._h, _phoenix_p(phoenix_p)), "cb_renderer_set_phoenix")
+
+    def set_bounded(self):
+        """Make this a bounded renderer (cb_renderer_set_bounded), before the first pass: the orbits that never escape are
+        plotted.  Alone it brings the identity projection; after set_projection or set_julia it keeps theirs.  The
+        histogram stays one plane."""
+        _check(lib.cb_renderer_set_bounded(self._h), "cb_renderer_set_bounded")
+
+    def bounded(self):
+        """Whether this is a bounded renderer."""
+        return bool(lib.cb_renderer_bounded(self._h))
 
     def phoenix(self):
         """The p of a Phoenix renderer as (p_re, p_im); None for any other renderer."""

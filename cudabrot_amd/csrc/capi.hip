@@ -262,9 +262,10 @@ constexpr uint32_t kRendererPassesPerLaunch = 128;
 
 // What a render is: the normal one (of a renderer: its n_channels windows fused, if any), the focused one, or a plotted one
 // (draw_plot.hip and its kin: direct atomics, no deferred scatter, no carry) named by its sink -- one plane, the palette's
-// three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one.  Whether c is sampled or fixed
+// three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one, the bounded orbits' one.  Whether
+// c is sampled or fixed
 // (Plotted::julia) is the source beside it.  What varies with the kind is kind_row and draw_plotted's switch.
-enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix };
+enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix, kBounded };
 bool is_plotted(Kind k) { return k != kNormal && k != kFocus; }
 
 // What every draw launch is given: the public entry points fill it from their arguments, a renderer from itself and the
@@ -361,6 +362,7 @@ KindRow kind_row(const Plotted &p) {
     case kDepthPalette: return {3, kImageRgb, false};
     case kFrames: return {(size_t) p.n_frames, kImageStacked, false};
     case kPhoenix: return {1, kImageSingle, true};
+    case kBounded: return {1, kImageSingle, false};
   }
   return {0, kImageSingle, false};  // (no kind)
 }
@@ -373,18 +375,19 @@ bool variant_ok(const Plotted &p, int kernel_variant) {
 
 // May the renderer become `want`?  The one rule of every setter: only before the first pass; a channel renderer, a focused
 // one and one with a sink stay what they are; a plain one takes a focus, a projection (with or without a fixed c) or a
-// palette, which brings the identity projection; a projected or Julia one without a sink takes any sink.
+// palette or the bounded sink, which bring the identity projection; a projected or Julia one without a sink takes any sink.
 bool admits(const cb_renderer *r, Kind want) {
   if (!r || r->rendered || r->n_channels > 0) return false;
   switch (r->what.kind) {
-    case kNormal: return want == kFocus || want == kPlot || want == kPalette;
+    case kNormal: return want == kFocus || want == kPlot || want == kPalette || want == kBounded;
     case kPlot: return is_plotted(want) && want != kPlot;
     case kFocus:
     case kPalette:
     case kDepth:
     case kDepthPalette:
     case kFrames:
-    case kPhoenix: return false;
+    case kPhoenix:
+    case kBounded: return false;
   }
   return false;
 }
@@ -464,7 +467,8 @@ bool plotted_source(Plotted *p, Kind kind, const double *projection, const doubl
   return true;
 }
 
-// ---- the plotted launch (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip, draw_frames.hip, draw_phoenix.hip) ----
+// ---- the plotted launch (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip, draw_frames.hip, draw_phoenix.hip,
+// draw_bounded.hip) ----
 
 // The arguments all plotted launches share, once the caller's own have passed.  julia_c null: c is sampled; d_lut null: one
 // plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.  interior false: the launch's step is not the
@@ -513,9 +517,9 @@ int plot_args(const Launch &l, const double projection[8], const double julia_c[
   return 0;
 }
 
-// One plotted launch: what the seven cb_draw_buddhabrot_{projected .. phoenix} entry points and a plotted renderer do once
+// One plotted launch: what the eight cb_draw_buddhabrot_{projected .. bounded} entry points and a plotted renderer do once
 // their own arguments have passed.  interior_level (may be null): the level of the interior map the launch used, 0 for none
-// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 25.
+// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 27.
 int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   if (interior_level) *interior_level = 0;
   if (!variant_ok(p, l.kernel_variant)) return (int) hipErrorInvalidValue;
@@ -523,7 +527,8 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   bool lockstep = false;
   {
     const int rc = plot_args(l, p.kind == kFrames ? kIdentityProjection : p.projection, p.julia ? p.julia_c : nullptr,
-                             p.kind == kPalette ? p.d_lut : nullptr, p.kind != kPhoenix, &pa, &lockstep);
+                             p.kind == kPalette ? p.d_lut : nullptr, p.kind != kPhoenix && p.kind != kBounded, &pa,
+                             &lockstep);
     if (rc) return rc;
   }
   const hipStream_t stream = reinterpret_cast<hipStream_t>(l.stream);
@@ -580,6 +585,10 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
       e = cb::launch_draw_phoenix(xa, lockstep, stream);
       break;
     }
+    case kBounded:  // nothing is rejected or retired as drawn: no interior map
+      report(26);
+      e = cb::launch_draw_bounded(pa, lockstep, stream);
+      break;
   }
   if (interior_level && e == hipSuccess && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
   return (int) e;
@@ -1388,6 +1397,24 @@ int cb_renderer_phoenix(const cb_renderer *r, double out[2]) {
   out[1] = r->what.phoenix_p[1];
   return 1;
 }
+
+int cb_draw_buddhabrot_bounded(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2], void *d_states, uint32_t n_threads,
+                               uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kBounded, projection, julia_c)) return (int) hipErrorInvalidValue;
+  return draw_plotted(l, p, nullptr);
+}
+
+int cb_renderer_set_bounded(cb_renderer *r) {
+  if (!admits(r, kBounded)) return (int) hipErrorInvalidValue;  // the histogram stays one plane
+  if (r->what.kind == kNormal) memcpy(r->what.projection, kIdentityProjection, sizeof(r->what.projection));  // alone
+  r->what.kind = kBounded;
+  return 0;
+}
+
+int cb_renderer_bounded(const cb_renderer *r) { return r && r->what.kind == kBounded ? 1 : 0; }
 
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
                        const cb_iteration_control *iterations, uint64_t seed,

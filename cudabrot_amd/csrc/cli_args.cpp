@@ -377,6 +377,10 @@ const std::vector<Flag> &flag_table() {
          s.phoenix = true;
          return parse_julia(t, s.phoenix_p) ? kOk : "Invalid phoenix parameter (want RE,IM, two numbers from -2 to 2)";
        }},
+      // --bounded: the orbits that never escape, plotted on any plane under any step of the projected path, with --julia
+      // too (include/cudabrot_amd.h, "Bounded render"): --anti's orbits on the plotted path
+      {"--bounded", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.bounded = true; return kOk; }},
       // --palette K:RRGGBB[,K:RRGGBB...]: orbits coloured by their escape index: colour stops interpolated into a table of
       // -m entries, three planes of integer weights, -o receives a 16-bit PPM; on the projected path with any plane,
       // --power, --julia or --burning-ship (include/cudabrot_amd.h, "Palette render")
@@ -515,6 +519,7 @@ const Partner kDepth = {[](const Settings &s) { return s.depth_given; }, "--dept
 const Partner kDepthPalette = {[](const Settings &s) { return s.depth_palette(); }, "--depth-palette"};
 const Partner kFormula = {[](const Settings &s) { return s.formula != 0; }, "--formula"};
 const Partner kSweep = {[](const Settings &s) { return s.sweep_given; }, "--sweep"};
+const Partner kPhoenix = {[](const Settings &s) { return s.phoenix; }, "--phoenix"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -529,6 +534,12 @@ struct Refusal {
 
 const std::vector<Refusal> &refusal_table() {
   static const std::vector<Refusal> table = {
+      // a bounded render is a projected or Julia render, under any of their steps, that plots the other orbits into one
+      // plane (include/cudabrot_amd.h, "Bounded render").  The first row: it combines with --formula, --power, --julia and
+      // a projection, whose rows would otherwise say what it refuses in their own name -- and no line without --bounded
+      // meets it
+      {[](const Settings &s) { return s.bounded; }, "--bounded",
+       {kAnti, kPalette, kDepth, kDepthPalette, kSweep, kPhoenix, kFocus, kChannel, kGpus}, nullptr},
       // a formula render is a projected render with a step of its own (include/cudabrot_amd.h, "Formula step"): its
       // refusals come before those of the palette, the Multibrot step, c and the projection, which it would otherwise trip
       {[](const Settings &s) { return s.formula != 0; }, "--formula", {kPower, kShip, kAnti, kFocus, kChannel, kGpus},

@@ -75,7 +75,7 @@ struct Settings {
   // projection's
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
-  bool plotted() const { return projected() || depth_given || sweep_given || phoenix; }
+  bool plotted() const { return projected() || depth_given || sweep_given || phoenix || bounded; }
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
@@ -91,6 +91,10 @@ struct Settings {
   // one as --depth does, with a last refusal row of its own; combines with --julia
   bool phoenix = false;
   double phoenix_p[2] = {0.0, 0.0};
+  // --bounded (extension): the orbits that never escape, on the plotted path (cb_renderer_set_bounded); makes the run a
+  // projected one as --depth does, with a refusal row of its own; combines with every plane, step and --julia.  -c is not
+  // read, as under --anti
+  bool bounded = false;
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

@@ -83,6 +83,7 @@ class Run {
       if (cfg_.formula != 0) fprintf(stderr, "{\"formula\": \"%s\"}\n", cfg_.formula_name);  // or this step
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       if (cfg_.phoenix) fprintf(stderr, "{\"phoenix\": [\"%a\", \"%a\"]}\n", cfg_.phoenix_p[0], cfg_.phoenix_p[1]);  // and p
+      if (cfg_.bounded) fprintf(stderr, "{\"bounded\": true}\n");  // and which orbits are plotted
       if (cfg_.depth_given) {  // and the third row with its window
         const cb_depth &d = cfg_.depth;
         fprintf(stderr, "{\"depth\": {\"row\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"min\": \"%a\", \"max\": \"%a\", \"slices\": %d}}\n",
@@ -229,6 +230,7 @@ class Run {
     }
     if (cfg_.sweep_given) CB_CHECK(cb_renderer_set_frames(renderer_, frames_.data(), cfg_.sweep.frames));  // likewise
     if (cfg_.phoenix) CB_CHECK(cb_renderer_set_phoenix(renderer_, cfg_.phoenix_p));  // likewise
+    if (cfg_.bounded) CB_CHECK(cb_renderer_set_bounded(renderer_));                  // likewise
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));

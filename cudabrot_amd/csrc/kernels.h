@@ -337,6 +337,13 @@ struct PhoenixArgs {
 };
 hipError_t launch_draw_phoenix(const PhoenixArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_bounded.hip: the bounded render ("Bounded render" of include/cudabrot_amd.h) -- a plotted launch that plots the
+// orbits that do NOT escape, z_1 .. z_M, as the anti-Buddhabrot records them: nothing rejected, d.min_iter and
+// d.interior_map not read, one plane.  Step and source of c as launch_draw_plot's; palette must be 0 and lut null.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of a, a table.  lockstep: the definition, one
+// lane per reference thread, every point with weight 1; else the cycle-compressed product kernel.
+hipError_t launch_draw_bounded(const PlotArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

@@ -769,6 +769,65 @@ int cb_draw_buddhabrot_phoenix(const cb_fractal_dimensions *dims, cb_pixel *d_hi
                                const double phoenix_p[2], void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
                                cb_counters *d_counters, int kernel_variant, void *stream);
 
+/* ---- Bounded render: the orbits that never escape, on any plane, under any plotted step -- *
+ *
+ * CB_KERNEL_FLAG_ANTI plots the orbits that do not escape on (z_re, z_im) under the reference's step or the Burning Ship.
+ * A BOUNDED render plots the same orbits on the plane a matrix picks, under any step of the plotted path and with a sampled
+ * or a fixed c: the attractor of the 4-D set where the projected render plots its escaping halo.  On the plane (z_re, c_re)
+ * it is the bifurcation diagram of the logistic map itself.  The project's own definition (the reference has none).
+ * Normative:
+ *
+ *   Samples and step.  The same sample stream as every render: four XORWOW draws per sample, two coordinates
+ *   (s_re, s_im) in [-2, 2)^2, and lane t advances generator t by exactly its samples.  The step S is any step of the
+ *   plotted path: the reference's, its Burning Ship variant (CB_KERNEL_FLAG_BURNING_SHIP), z^D + c for D = 3 ... 8
+ *   (CB_KERNEL_POWER, "Multibrot step") or one of the five formulas (CB_KERNEL_FORMULA, "Formula step"), each bit for bit
+ *   the step of those renders.
+ *
+ *   Source of c.  julia_c NULL: c is the sample and z_0 = c.  julia_c given: c = julia_c is fixed, both parts in [-2, 2],
+ *   and z_0 is the sample, exactly as in "Julia render".
+ *
+ *   Escape.  With z_k = S(z_{k-1}, c) and M = max_escape_iterations, a sample escapes if |z_k|^2 > 4 for some
+ *   1 <= k <= M.  z_0 is neither tested nor plotted.
+ *
+ *   Nothing is rejected: there is no cardioid or bulb test and no interior map, whatever the step and the source of c; the
+ *   launch reports interior-map level 0.  min_escape_iterations is ignored.
+ *
+ *   An escaping sample adds nothing.  A sample that does not escape adds the M points (z_k, c), k = 1 ... M: each is the
+ *   point (z_re, z_im, c_re, c_im) under P[2][4], projected with the four fused operations of "Projected render" in the
+ *   same order -- K_u = fma(P[0][2], c_re, P[0][3] * c_im), u = fma(P[0][0], z_re, fma(P[0][1], z_im, K_u)), v likewise
+ *   from row 1 -- and (u, v) binned as the projected render bins it, into ONE plane of w*h cb_pixel.
+ *
+ *   M <= 0.  Nothing is tested and nothing is added, as under CB_KERNEL_FLAG_ANTI.
+ *
+ *   Counters, exactly as CB_KERNEL_FLAG_ANTI defines them: rejected = 0; never_escaped = recorded = the samples that do not
+ *   escape; too_fast = the escaping samples; iterate_steps = sum of k over the escaping samples (k the step that escaped)
+ *   + M per sample that does not; replay_steps = M * recorded; increments = what the histogram gains; skipped_steps = the
+ *   part of iterate_steps + replay_steps not executed, the only counter the two kernels may differ in.
+ *
+ *   Consequence.  With the identity matrix and a sampled c, u = z_re and v = z_im up to the sign of a zero ("Identity"
+ *   above), so the bounded render under the reference's step or the Burning Ship equals cb_draw_buddhabrot with
+ *   CB_KERNEL_FLAG_ANTI: histogram, generator states and every counter but skipped_steps.
+ *
+ * Two kernels (draw_bounded.hip).  CB_KERNEL_SIMPLE is the definition in lock-step: every point with weight 1.
+ * CB_KERNEL_DEFAULT is the product kernel, one instance per step and per source of c, with the anti render's cycle
+ * compression: c is constant along an orbit and the plotted point is a function of (z_k, c) only, so if z_n == z_s bit for
+ * bit the orbit from z_s on is the cycle z_s ... z_{n-1} repeated and so are its plotted points; the histogram of the
+ * transient z_1 ... z_{s-1} once plus ONE period, in which the point z_{s+j} carries the weight floor((M - s - j) / p) + 1,
+ * p = n - s, equals the naive one bit for bit (integer adds commute).  Identical histograms, generator states and counters
+ * (but skipped_steps).  Direct atomics, no workspace, no carry: every launch is complete when it ends.
+ *
+ * kernel_variant: what cb_draw_buddhabrot_julia accepts -- CB_KERNEL_DEFAULT or CB_KERNEL_SIMPLE, optionally with ONE of
+ * CB_KERNEL_FLAG_BURNING_SHIP, CB_KERNEL_POWER(D), CB_KERNEL_FORMULA(F).  hipErrorInvalidValue, with nothing launched and
+ * the histogram, the counters and the generators untouched: CB_KERNEL_FLAG_ANTI, CB_KERNEL_FLAG_DRAIN, the timed and
+ * full-iterate variants and every other base variant, the Burning Ship with a degree, a formula with the Burning Ship or a
+ * degree, a degree or a code out of range, a non-finite matrix entry, a julia_c outside [-2, 2]^2 (a NaN included).
+ * Bounded orbits under the Phoenix step, into a palette, a depth or frames, with a focus or channels, and on more than one
+ * GPU are out of scope. */
+int cb_draw_buddhabrot_bounded(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2] /* NULL: sampled c */, void *d_states,
+                               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                               void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -890,6 +949,17 @@ int cb_renderer_set_phoenix(cb_renderer *r, const double phoenix_p[2]);
 /* A Phoenix renderer's p: returns 1 and fills out[2]; returns 0 and leaves `out` alone for any other renderer (or a NULL
  * argument). */
 int cb_renderer_phoenix(const cb_renderer *r, double out[2]);
+/* Makes this a BOUNDED renderer ("Bounded render" above), before its first pass, once: on a plain renderer it brings the
+ * identity projection, as the palette does; a projected or Julia renderer keeps its matrix and its c.  The histogram stays
+ * one plane: render_passes, prepare, finish, read / write_histogram, read_counters, the generator states and
+ * cb_renderer_grayscale_image work as for a projected renderer, and every later cb_renderer_render_passes launches bounded
+ * draws with the variants cb_draw_buddhabrot_bounded accepts.  hipErrorInvalidValue for a channel, focused or palette
+ * renderer, a renderer with a depth, a depth palette, frames or the Phoenix step, a bounded renderer, and a renderer that
+ * has rendered.  Afterwards every setter -- focus, projection, julia, palette, depth, depth palette, frames, phoenix,
+ * bounded -- is refused. */
+int cb_renderer_set_bounded(cb_renderer *r);
+/* 1 for a bounded renderer, 0 for any other (or a NULL renderer). */
+int cb_renderer_bounded(const cb_renderer *r);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -1079,7 +1149,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * depth-palette product kernel (draw_depth_palette_kernel: cb_draw_buddhabrot_depth_palette, whatever its step), 21 the
  * depth-palette lock-step kernel, 22 the frames product kernel (draw_frames_kernel: cb_draw_buddhabrot_frames, whatever
  * its step), 23 the frames lock-step kernel, 24 the Phoenix product kernel (draw_phoenix_kernel:
- * cb_draw_buddhabrot_phoenix), 25 the Phoenix lock-step kernel.
+ * cb_draw_buddhabrot_phoenix), 25 the Phoenix lock-step kernel, 26 the bounded product kernel (draw_bounded_kernel:
+ * cb_draw_buddhabrot_bounded, whatever its step), 27 the bounded lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
