@@ -61,6 +61,7 @@ CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_S
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
 CB_PALETTE_MAX_ENTRIES, CB_PALETTE_MAX_STOPS = 1 << 24, 16  # palette render: the table's entries, the stops of one
 CB_DEPTH_MAX_SLICES = 256  # depth render: the planes of one
+CB_PERIOD_MAX_ENTRIES = 1024  # period-palette render: the table's entries (periods 0 .. 1023)
 CB_FRAMES_MAX = 256  # frames render: the matrices (and planes) of one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -323,6 +324,11 @@ def _load():
                                              vp, i32, vp]),
         "cb_renderer_set_bounded": (i32, [vp]),
         "cb_renderer_bounded": (i32, [vp]),
+        "cb_draw_buddhabrot_periods": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32,
+                                             C.c_double, vp, u32, u32, vp, i32, vp]),
+        "cb_renderer_set_period_palette": (i32, [vp, vp, u32, C.c_double]),
+        "cb_renderer_period_palette": (i32, [vp, C.POINTER(u32), C.POINTER(C.c_double)]),
+        "cb_renderer_period_palette_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
         "cb_draw_buddhabrot_depth": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), depth_p, vp, u32,
                                            u32, vp, i32, vp]),
         "cb_renderer_set_depth": (i32, [vp, depth_p]),
@@ -367,6 +373,8 @@ EXPORTED_SYMBOLS = (
     "cb_renderer_depth_palette_image "
     "cb_draw_buddhabrot_phoenix cb_renderer_set_phoenix cb_renderer_phoenix "
     "cb_draw_buddhabrot_bounded cb_renderer_set_bounded cb_renderer_bounded "
+    "cb_draw_buddhabrot_periods cb_renderer_set_period_palette cb_renderer_period_palette "
+    "cb_renderer_period_palette_image "
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
     "cb_renderer_frames_image"
 ).split()
@@ -550,6 +558,19 @@ def draw_buddhabrot_bounded(dims, d_hist, iterations, projection, julia_c, d_sta
     )
 
 
+def draw_buddhabrot_periods(dims, d_hist, iterations, projection, julia_c, d_lut, n_entries, period_eps, d_states,
+                            n_threads, samples_per_thread, d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The period-palette draw on caller-owned device memory (cb_draw_buddhabrot_periods): the bounded draw into three
+    planes, each bounded orbit in the colour d_lut (n_entries entries, 2 .. CB_PERIOD_MAX_ENTRIES, on the device) has for
+    its period: the least j <= n_entries - 1 with |z_{max+j} - z_max|^2 <= period_eps, 0 if there is none."""
+    _check(
+        lib.cb_draw_buddhabrot_periods(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                       None if julia_c is None else _julia_c(julia_c), d_lut, n_entries, period_eps,
+                                       d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream),
+        "cb_draw_buddhabrot_periods",
+    )
+
+
 def palette_from_stops(stops, n_entries):
     """The table of a list of colour stops (cb_palette_from_stops): stops = [(k, r, g, b), ...], k ascending -> u32 array
     of n_entries entries, entry k = r | g << 8 | b << 16 of an orbit with escape index k."""
@@ -712,6 +733,27 @@ class Renderer:
         """Whether this is a bounded renderer."""
         return bool(lib.cb_renderer_bounded(self._h))
 
+    def set_period_palette(self, lut, eps=2.0 ** -66):
+        """Make this a period-palette renderer (cb_renderer_set_period_palette), before the first pass, where set_bounded
+        is admitted: lut is the table, 2 .. CB_PERIOD_MAX_ENTRIES u32 entries, entry k the colour of the bounded orbits of
+        period k (0: no period up to len(lut) - 1); eps the tolerance of the return test.  The histogram becomes three
+        planes."""
+        a = np.ascontiguousarray(lut, dtype=np.uint32).reshape(-1)
+        _check(lib.cb_renderer_set_period_palette(self._h, a.ctypes.data, a.size, float(eps)),
+               "cb_renderer_set_period_palette")
+
+    def period_palette(self):
+        """(entries of the table, eps) of a period-palette renderer; None for any other renderer."""
+        n, eps = C.c_uint32(), C.c_double()
+        if not lib.cb_renderer_period_palette(self._h, C.byref(n), C.byref(eps)):
+            return None
+        return int(n.value), float(eps.value)
+
+    def period_palette_image(self, gamma=1.0, mode=0):
+        """The image of a period-palette renderer (cb_renderer_period_palette_image) -> (big-endian u16 image [h,w,3] = the
+        PPM body, the largest count of the three planes, scale)."""
+        return self._image("cb_renderer_period_palette_image", (self.dims.h, self.dims.w, 3), gamma, mode)
+
     def phoenix(self):
         """The p of a Phoenix renderer as (p_re, p_im); None for any other renderer."""
         out = (C.c_double * 2)()
@@ -807,7 +849,8 @@ class Renderer:
 
     def _planes(self):
         """The planes of the histogram, asked of the library; 0: the one plane that read_histogram returns as [h, w]."""
-        if lib.cb_renderer_palette(self._h, None) or lib.cb_renderer_depth_palette(self._h, None, None):
+        if (lib.cb_renderer_palette(self._h, None) or lib.cb_renderer_depth_palette(self._h, None, None)
+                or lib.cb_renderer_period_palette(self._h, None, None)):
             return 3
         return lib.cb_renderer_depth(self._h, None) or lib.cb_renderer_frames(self._h, None) or self.n_channels
 

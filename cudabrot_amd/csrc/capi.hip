@@ -262,10 +262,10 @@ constexpr uint32_t kRendererPassesPerLaunch = 128;
 
 // What a render is: the normal one (of a renderer: its n_channels windows fused, if any), the focused one, or a plotted one
 // (draw_plot.hip and its kin: direct atomics, no deferred scatter, no carry) named by its sink -- one plane, the palette's
-// three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one, the bounded orbits' one.  Whether
-// c is sampled or fixed
-// (Plotted::julia) is the source beside it.  What varies with the kind is kind_row and draw_plotted's switch.
-enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix, kBounded };
+// three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one, the bounded orbits' one, the
+// period palette's three.  Whether c is sampled or fixed (Plotted::julia) is the source beside it.  What varies with the
+// kind is kind_row and draw_plotted's switch.
+enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix, kBounded, kPeriodPalette };
 bool is_plotted(Kind k) { return k != kNormal && k != kFocus; }
 
 // What every draw launch is given: the public entry points fill it from their arguments, a renderer from itself and the
@@ -287,12 +287,14 @@ struct Plotted {
   double projection[8];  // the matrix P[2][4] (kFrames: kept for cb_renderer_projection, the launch takes `d_frames`)
   bool julia;            // c is julia_c and the sample is z_0
   double julia_c[2];
-  const uint32_t *d_lut;  // kPalette: n_entries = max_iter entries; kDepthPalette: n_entries = depth.slices entries
+  const uint32_t *d_lut;  // kPalette: n_entries = max_iter entries; kDepthPalette: n_entries = depth.slices entries;
+                          // kPeriodPalette: n_entries = the largest period + 1
   uint32_t n_entries;
   cb_depth depth;          // kDepth, kDepthPalette
   const double *d_frames;  // kFrames: n_frames x 8 doubles
   int n_frames;
   double phoenix_p[2];  // kPhoenix
+  double period_eps;    // kPeriodPalette
 };
 
 }  // namespace
@@ -363,6 +365,7 @@ KindRow kind_row(const Plotted &p) {
     case kFrames: return {(size_t) p.n_frames, kImageStacked, false};
     case kPhoenix: return {1, kImageSingle, true};
     case kBounded: return {1, kImageSingle, false};
+    case kPeriodPalette: return {3, kImageRgb, false};
   }
   return {0, kImageSingle, false};  // (no kind)
 }
@@ -375,11 +378,12 @@ bool variant_ok(const Plotted &p, int kernel_variant) {
 
 // May the renderer become `want`?  The one rule of every setter: only before the first pass; a channel renderer, a focused
 // one and one with a sink stay what they are; a plain one takes a focus, a projection (with or without a fixed c) or a
-// palette or the bounded sink, which bring the identity projection; a projected or Julia one without a sink takes any sink.
+// palette, the bounded or the period-palette sink, which bring the identity projection; a projected or Julia one without a
+// sink takes any sink.
 bool admits(const cb_renderer *r, Kind want) {
   if (!r || r->rendered || r->n_channels > 0) return false;
   switch (r->what.kind) {
-    case kNormal: return want == kFocus || want == kPlot || want == kPalette || want == kBounded;
+    case kNormal: return want == kFocus || want == kPlot || want == kPalette || want == kBounded || want == kPeriodPalette;
     case kPlot: return is_plotted(want) && want != kPlot;
     case kFocus:
     case kPalette:
@@ -387,7 +391,8 @@ bool admits(const cb_renderer *r, Kind want) {
     case kDepthPalette:
     case kFrames:
     case kPhoenix:
-    case kBounded: return false;
+    case kBounded:
+    case kPeriodPalette: return false;
   }
   return false;
 }
@@ -444,6 +449,12 @@ bool frames_ok(const double *frames_host, int n_frames, int h) {
   return (long long) n_frames * (long long) h <= 0x7fffffffLL;
 }
 
+// The table length and the tolerance of a period-palette render ("Period-palette render"): 2 .. CB_PERIOD_MAX_ENTRIES
+// entries, eps finite and >= 0 (a NaN fails the comparisons).
+bool period_palette_ok(uint32_t n_entries, double eps) {
+  return n_entries >= 2u && n_entries <= (uint32_t) CB_PERIOD_MAX_ENTRIES && eps >= 0.0 && isfinite(eps);
+}
+
 // The parameter of a Phoenix render ("Phoenix render"): both parts in [-2, 2]; a NaN fails the comparisons.
 bool phoenix_p_ok(const double *p) { return p && p[0] >= -2.0 && p[0] <= 2.0 && p[1] >= -2.0 && p[1] <= 2.0; }
 
@@ -468,7 +479,7 @@ bool plotted_source(Plotted *p, Kind kind, const double *projection, const doubl
 }
 
 // ---- the plotted launch (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip, draw_frames.hip, draw_phoenix.hip,
-// draw_bounded.hip) ----
+// draw_bounded.hip, draw_periods.hip) ----
 
 // The arguments all plotted launches share, once the caller's own have passed.  julia_c null: c is sampled; d_lut null: one
 // plane, no table.  *lockstep: the variant's base is CB_KERNEL_SIMPLE.  interior false: the launch's step is not the
@@ -517,9 +528,9 @@ int plot_args(const Launch &l, const double projection[8], const double julia_c[
   return 0;
 }
 
-// One plotted launch: what the eight cb_draw_buddhabrot_{projected .. bounded} entry points and a plotted renderer do once
+// One plotted launch: what the nine cb_draw_buddhabrot_{projected .. periods} entry points and a plotted renderer do once
 // their own arguments have passed.  interior_level (may be null): the level of the interior map the launch used, 0 for none
-// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 27.
+// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 29.
 int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   if (interior_level) *interior_level = 0;
   if (!variant_ok(p, l.kernel_variant)) return (int) hipErrorInvalidValue;
@@ -527,8 +538,8 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   bool lockstep = false;
   {
     const int rc = plot_args(l, p.kind == kFrames ? kIdentityProjection : p.projection, p.julia ? p.julia_c : nullptr,
-                             p.kind == kPalette ? p.d_lut : nullptr, p.kind != kPhoenix && p.kind != kBounded, &pa,
-                             &lockstep);
+                             p.kind == kPalette ? p.d_lut : nullptr,
+                             p.kind != kPhoenix && p.kind != kBounded && p.kind != kPeriodPalette, &pa, &lockstep);
     if (rc) return rc;
   }
   const hipStream_t stream = reinterpret_cast<hipStream_t>(l.stream);
@@ -589,6 +600,12 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
       report(26);
       e = cb::launch_draw_bounded(pa, lockstep, stream);
       break;
+    case kPeriodPalette: {  // the bounded launch with a table keyed by the period: three planes, no interior map
+      const cb::PeriodArgs qa = {pa, p.d_lut, (int) p.n_entries, p.period_eps, pa.plane_pixels};
+      report(28);
+      e = cb::launch_draw_periods(qa, lockstep, stream);
+      break;
+    }
   }
   if (interior_level && e == hipSuccess && pa.d.interior_map) *interior_level = (int) pa.d.interior_shift + 1;
   return (int) e;
@@ -1416,6 +1433,40 @@ int cb_renderer_set_bounded(cb_renderer *r) {
 
 int cb_renderer_bounded(const cb_renderer *r) { return r && r->what.kind == kBounded ? 1 : 0; }
 
+int cb_draw_buddhabrot_periods(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2], const uint32_t *d_lut,
+                               uint32_t n_entries, double period_eps, void *d_states, uint32_t n_threads,
+                               uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, void *stream) {
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, kPeriodPalette, projection, julia_c)) return (int) hipErrorInvalidValue;
+  if (!d_lut || !period_palette_ok(n_entries, period_eps)) return (int) hipErrorInvalidValue;
+  p.d_lut = d_lut;
+  p.n_entries = n_entries;
+  p.period_eps = period_eps;
+  return draw_plotted(l, p, nullptr);
+}
+
+int cb_renderer_set_period_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries, double eps) {
+  if (!admits(r, kPeriodPalette) || !period_palette_ok(n_entries, eps) || !lut_host_ok(lut_host, n_entries)) {
+    return (int) hipErrorInvalidValue;
+  }
+  const int rc = swap_in_planes(r, 3, lut_host, n_entries, &r->what.d_lut);
+  if (rc) return rc;
+  if (r->what.kind == kNormal) memcpy(r->what.projection, kIdentityProjection, sizeof(r->what.projection));  // alone
+  r->what.n_entries = n_entries;
+  r->what.period_eps = eps;
+  r->what.kind = kPeriodPalette;
+  return 0;
+}
+
+int cb_renderer_period_palette(const cb_renderer *r, uint32_t *n_entries, double *eps) {
+  if (!r || r->what.kind != kPeriodPalette) return 0;
+  if (n_entries) *n_entries = r->what.n_entries;
+  if (eps) *eps = r->what.period_eps;
+  return 1;
+}
+
 int cb_renderer_create(cb_renderer **out, int device, const cb_fractal_dimensions *dims,
                        const cb_iteration_control *iterations, uint64_t seed,
                        uint64_t first_subsequence, uint32_t n_threads) {
@@ -1652,6 +1703,11 @@ int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode,
   return kind_image(r, kDepthPalette, gamma, tone_mode, host_rgb_be, max_out, scale_out);
 }
 
+int cb_renderer_period_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                                     double *scale_out) {
+  return kind_image(r, kPeriodPalette, gamma, tone_mode, host_rgb_be, max_out, scale_out);
+}
+
 int cb_renderer_depth_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_gray_be, uint64_t *max_out,
                             double *scale_out) {
   return kind_image(r, kDepth, gamma, tone_mode, host_gray_be, max_out, scale_out);
@@ -1773,6 +1829,7 @@ int cb_renderers_reduce(cb_renderer *const *renderers, int n) {
         r->n_channels != renderers[0]->n_channels ||
         (r->what.kind == kPalette) != (renderers[0]->what.kind == kPalette) ||
         (r->what.kind == kDepthPalette) != (renderers[0]->what.kind == kDepthPalette) ||
+        (r->what.kind == kPeriodPalette) != (renderers[0]->what.kind == kPeriodPalette) ||
         renderer_planes(r) != renderer_planes(renderers[0])) {
       return (int) hipErrorInvalidValue;
     }

@@ -381,6 +381,24 @@ const std::vector<Flag> &flag_table() {
       // too (include/cudabrot_amd.h, "Bounded render"): --anti's orbits on the plotted path
       {"--bounded", Value::kNone, nullptr, false,
        [](Settings &s, long, double, const char *) { s.bounded = true; return kOk; }},
+      // --period-palette K:RRGGBB[,K:RRGGBB...]: the orbits of a --bounded render coloured by the period of the cycle they
+      // fall onto: --palette's syntax with K a period, 0 the colour of the orbits without one; three planes of integer
+      // weights, -o receives one 16-bit PPM (include/cudabrot_amd.h, "Period-palette render").  --period-eps X: the
+      // tolerance of its return test (hexfloats accepted)
+      {"--period-palette", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         s.n_period_stops = parse_palette(t, s.period_stops);
+         if (s.period_palette() && s.period_stops[s.n_period_stops - 1].k >= CB_PERIOD_MAX_ENTRIES) s.n_period_stops = 0;
+         return s.period_palette() ? kOk
+                                   : "Invalid period palette (want K:RRGGBB,... K ascending from 0 to 1023, at most 16 stops)";
+       }},
+      {"--period-eps", Value::kDouble, nullptr, false,
+       [](Settings &s, long, double d, const char *) {
+         s.period_eps_given = true;
+         if (!(d >= 0.0) || !isfinite(d)) return "Invalid period eps (want a finite number, 0 or more)";
+         s.period_eps = d;
+         return kOk;
+       }},
       // --palette K:RRGGBB[,K:RRGGBB...]: orbits coloured by their escape index: colour stops interpolated into a table of
       // -m entries, three planes of integer weights, -o receives a 16-bit PPM; on the projected path with any plane,
       // --power, --julia or --burning-ship (include/cudabrot_amd.h, "Palette render")
@@ -534,6 +552,14 @@ struct Refusal {
 
 const std::vector<Refusal> &refusal_table() {
   static const std::vector<Refusal> table = {
+      // a period-palette render is a bounded render with a table (include/cudabrot_amd.h, "Period-palette render"): its
+      // rows stand ahead of --bounded's, which refuses everything else in its own name -- and no line without the two flags
+      // meets them
+      {[](const Settings &s) { return s.period_eps_given && !s.period_palette(); }, nullptr, {},
+       [](const Settings &) { printf("--period-eps needs --period-palette.\n"); }},
+      {[](const Settings &s) { return s.period_palette() && !s.bounded; }, nullptr, {},
+       [](const Settings &) { printf("--period-palette needs --bounded.\n"); }},
+      {[](const Settings &s) { return s.period_palette(); }, "--period-palette", {kRaw}, nullptr},
       // a bounded render is a projected or Julia render, under any of their steps, that plots the other orbits into one
       // plane (include/cudabrot_amd.h, "Bounded render").  The first row: it combines with --formula, --power, --julia and
       // a projection, whose rows would otherwise say what it refuses in their own name -- and no line without --bounded

@@ -95,6 +95,19 @@ struct Settings {
   // projected one as --depth does, with a refusal row of its own; combines with every plane, step and --julia.  -c is not
   // read, as under --anti
   bool bounded = false;
+  // --period-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a period-palette render, K a period from 0 to
+  // CB_PERIOD_MAX_ENTRIES - 1 (cb_palette_from_stops with the largest K + 1 entries, at least 2,
+  // cb_renderer_set_period_palette); needs --bounded, whose one plane becomes three.  --period-eps X: the tolerance of the
+  // return test, which needs --period-palette
+  int n_period_stops = 0;
+  cb_palette_stop period_stops[CB_PALETTE_MAX_STOPS] = {};
+  bool period_palette() const { return n_period_stops > 0; }
+  uint32_t period_entries() const {  // the largest K given + 1, and at least 2
+    const int last = n_period_stops > 0 ? period_stops[n_period_stops - 1].k : 0;
+    return last < 1 ? 2u : (uint32_t) last + 1u;
+  }
+  bool period_eps_given = false;
+  double period_eps = 0x1p-66;
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

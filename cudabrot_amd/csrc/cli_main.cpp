@@ -84,6 +84,14 @@ class Run {
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       if (cfg_.phoenix) fprintf(stderr, "{\"phoenix\": [\"%a\", \"%a\"]}\n", cfg_.phoenix_p[0], cfg_.phoenix_p[1]);  // and p
       if (cfg_.bounded) fprintf(stderr, "{\"bounded\": true}\n");  // and which orbits are plotted
+      if (cfg_.period_palette()) {  // and the colours of their periods, with the tolerance of the return test
+        fprintf(stderr, "{\"period_palette\": [");
+        for (int j = 0; j < cfg_.n_period_stops; ++j) {
+          const cb_palette_stop &stop = cfg_.period_stops[j];
+          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
+        }
+        fprintf(stderr, "], \"period_eps\": \"%a\"}\n", cfg_.period_eps);
+      }
       if (cfg_.depth_given) {  // and the third row with its window
         const cb_depth &d = cfg_.depth;
         fprintf(stderr, "{\"depth\": {\"row\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"min\": \"%a\", \"max\": \"%a\", \"slices\": %d}}\n",
@@ -124,7 +132,7 @@ class Run {
     if (cfg_.n_channels > 0) {
       save_channels();
       if (cfg_.color_file) save_color();
-    } else if (cfg_.palette() || cfg_.depth_palette()) {
+    } else if (cfg_.palette() || cfg_.depth_palette() || cfg_.period_palette()) {
       printf("Saving image.\n");
       report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
       printf("Done! Output image saved: %s\n", cfg_.output_image);
@@ -151,7 +159,7 @@ class Run {
   uint16_t *gray_ = nullptr;
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
-  std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette: the PPM body
+  std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette, --period-palette: the PPM body
   std::vector<uint16_t> planes_gray_be_;  // --depth, --sweep: the bodies of the N PGMs, slice or frame 0 first
   std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
 
@@ -159,7 +167,7 @@ class Run {
 
   uint64_t pixel_count() const { return (uint64_t) cfg_.canvas.w * (uint64_t) cfg_.canvas.h; }
   uint64_t planes() const {
-    if (cfg_.depth_palette()) return 3u;
+    if (cfg_.depth_palette() || cfg_.period_palette()) return 3u;
     if (cfg_.depth_given) return (uint64_t) cfg_.depth.slices;
     if (cfg_.sweep_given) return (uint64_t) cfg_.sweep.frames;
     return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u);
@@ -230,7 +238,13 @@ class Run {
     }
     if (cfg_.sweep_given) CB_CHECK(cb_renderer_set_frames(renderer_, frames_.data(), cfg_.sweep.frames));  // likewise
     if (cfg_.phoenix) CB_CHECK(cb_renderer_set_phoenix(renderer_, cfg_.phoenix_p));  // likewise
-    if (cfg_.bounded) CB_CHECK(cb_renderer_set_bounded(renderer_));                  // likewise
+    if (cfg_.period_palette()) {  // likewise: the table of the stops, one entry per period up to the largest given
+      std::vector<uint32_t> lut((size_t) cfg_.period_entries());
+      CB_CHECK(cb_palette_from_stops(cfg_.period_stops, cfg_.n_period_stops, lut.data(), (uint32_t) lut.size()));
+      CB_CHECK(cb_renderer_set_period_palette(renderer_, lut.data(), (uint32_t) lut.size(), cfg_.period_eps));
+    } else if (cfg_.bounded) {
+      CB_CHECK(cb_renderer_set_bounded(renderer_));  // likewise
+    }
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -364,7 +378,7 @@ class Run {
     }
     printf("%ld Buddhabrot passes took %f seconds.\n", done, wall_seconds() - t0);
     if (cfg_.print_stats) print_stats();
-    if (cfg_.palette() || cfg_.depth_palette()) {
+    if (cfg_.palette() || cfg_.depth_palette() || cfg_.period_palette()) {
       palette_image();
     } else if (cfg_.depth_given || cfg_.sweep_given) {
       planes_image();
@@ -519,8 +533,9 @@ class Run {
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
   }
 
-  // --palette, --depth-palette: the three planes tone-mapped against their common maximum, as one w x 3h image, and interleaved into the
-  // PPM body -- on the device, or with --tonemap host by the reference's host loop; the bytes are the same.
+  // --palette, --depth-palette, --period-palette: the three planes tone-mapped against their common maximum, as one
+  // w x 3h image, and interleaved into the PPM body -- on the device, or with --tonemap host by the reference's host loop;
+  // the bytes are the same.
   void palette_image() {
     uint64_t max = 0;
     double scale = 0.0;
@@ -535,7 +550,9 @@ class Run {
         }
       }
     } else {
-      CB_CHECK((cfg_.depth_palette() ? cb_renderer_depth_palette_image : cb_renderer_palette_image)(
+      CB_CHECK((cfg_.depth_palette()    ? cb_renderer_depth_palette_image
+                : cfg_.period_palette() ? cb_renderer_period_palette_image
+                                        : cb_renderer_palette_image)(
           renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max, &scale));
     }
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437

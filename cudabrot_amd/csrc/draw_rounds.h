@@ -74,7 +74,7 @@ __device__ __forceinline__ bool brent_save(uint32_t chunks) {
 // time.  The wave advances in ROUNDS of kRound steps; in a round each lane makes up to kRound steps of its own phase,
 // and between rounds each lane, on its own, does its bookkeeping.  What a kernel adds is its MODE: a struct with the
 // step (kShip, or a step of its own: round_step below), whatever per-lane state it needs beyond RoundLane, and four
-// inlined hooks, named where they are called (more, optional: round_converged and the state hooks below):
+// inlined hooks, named where they are called (more, optional: round_converged, the state hooks and round_again below):
 //   NEXT     the lane's next sample, or DONE when it has none left.  mode.next draws c and says what becomes of it: it
 //            is iterated, or retired as drawn -- rejected (cardioid, bulb), or proven interior and counted as the
 //            reference counts a sample that never escapes -- and the next one drawn.  (max_iter 0 needs no case of its
@@ -87,7 +87,7 @@ __device__ __forceinline__ bool brent_save(uint32_t chunks) {
 //            else Brent's save.  On such a cycle, or at k == max_iter, mode.never_escapes counts the sample (the steps
 //            not made go to skipped_steps) and decides: true, REPLAY up to the `end` it has set.
 //   REPLAY   z_1 .. z_end from z_0 = c, the same steps bit for bit; mode.point bins each, and may end the replay there
-//            by returning true.
+//            by returning true.  Where the mode has the chaining hook (round_again), another such pass may follow.
 // A lane that completes a phase mid-round idles to the round's end: kRound steps are the grain of the refill.  Rounds
 // divide kChunk, so an iterating lane is at a chunk boundary exactly when k % kChunk == 0.
 constexpr int kRound = 12;
@@ -155,6 +155,20 @@ __device__ __forceinline__ auto round_same(Mode &mode, RoundLane &l, bool z_same
 template <class Mode>
 __device__ __forceinline__ bool round_same(Mode &, RoundLane &, bool z_same, long) {
   return z_same;
+}
+
+// The chaining hook of a round: the mode's own `bool again(RoundLane &, LaneStats &)` where it has one, else false.
+// run_rounds calls it between rounds when a lane's REPLAY-like pass has ended -- at l.k == l.end, or because mode.point
+// returned true -- and on true starts another pass as it started the first: z = z_0, k = 0, round_start, up to the `end`
+// the mode has set.  A mode that walks from somewhere else than z_0 places z there in its `start` (draw_periods.hip: the
+// period search runs as such a pass, scheduled like any other, and the replay of the orbit is chained after it).
+template <class Mode>
+__device__ __forceinline__ auto round_again(Mode &mode, RoundLane &l, LaneStats &st, int) -> decltype(mode.again(l, st)) {
+  return mode.again(l, st);
+}
+template <class Mode>
+__device__ __forceinline__ bool round_again(Mode &, RoundLane &, LaneStats &, long) {
+  return false;
 }
 
 // The escape accounting of an escape render's mode (not the anti-Buddhabrot's, which records the other samples).
@@ -239,8 +253,13 @@ __device__ __forceinline__ void run_rounds(const DrawArgs &a, Mode &mode) {
       round_converged(mode, l, st, false, 0);
     }
     bool replay = false;
-    if (phase == kRoundReplay) {
-      if (l.k == l.end) phase = kRoundNext;
+    if (phase == kRoundNext) {  // mode.point ended the REPLAY
+      replay = round_again(mode, l, st, 0);
+    } else if (phase == kRoundReplay) {
+      if (l.k == l.end) {
+        phase = kRoundNext;
+        replay = round_again(mode, l, st, 0);
+      }
     } else if (phase == kRoundEscaped) {
       replay = mode.escaped(l, st);
       if (!replay) phase = kRoundNext;

@@ -344,6 +344,26 @@ hipError_t launch_draw_phoenix(const PhoenixArgs &a, bool lockstep, hipStream_t 
 // lane per reference thread, every point with weight 1; else the cycle-compressed product kernel.
 hipError_t launch_draw_bounded(const PlotArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_periods.hip: the period-palette render ("Period-palette render" of include/cudabrot_amd.h) -- a bounded launch whose
+// bounded orbits look a colour up by the period of the cycle they fall onto: each of the M points adds the three weights of
+// lut[period] to its pixel of three planes.
+//   p        the bounded launch it extends, p.palette 0 and p.lut null as there (the table is not the palette render's: it
+//            is indexed by the period).  p.d.hist is three planes.
+//   lut      the table on the device, n_entries entries in the palette's entry format, 2 .. CB_PERIOD_MAX_ENTRIES.
+//   eps      the tolerance of the return test, finite and >= 0.
+//   plane_pixels   w * h: the distance between the three planes.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_bounded refuses of p, a null table, n_entries out of range,
+// an eps that is negative, infinite or a NaN, a plane_pixels that is not w * h.  lockstep: the definition, one lane per
+// reference thread; else the cycle-compressed product kernel with its scheduled search.
+struct PeriodArgs {
+  PlotArgs p;
+  const uint32_t *lut;
+  int n_entries;
+  double eps;
+  unsigned long long plane_pixels;
+};
+hipError_t launch_draw_periods(const PeriodArgs &a, bool lockstep, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

@@ -828,6 +828,70 @@ int cb_draw_buddhabrot_bounded(const cb_fractal_dimensions *dims, cb_pixel *d_hi
                                uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                                void *stream);
 
+/* ---- Period-palette render: bounded orbits coloured by their cycle's period ----------- *
+ *
+ * The bounded render is the one family without colour, for a bounded orbit has no escape index.  Its natural key is the
+ * PERIOD of the cycle it falls onto: with it the plane (c_re, c_im) shows every hyperbolic component of the Mandelbrot set
+ * in the colour of its period, and the plane (z_re, c_re) the Feigenbaum diagram with every branch in the colour of its
+ * period.  The period the product kernel's cycle compression sees is a multiple of its chunk and a period of the fp64 limit
+ * cycle, not of the map; even the least bitwise return is the wrong key (a sample spiralling onto an attracting fixed
+ * point has a rounding 2-cycle, or none at all, long before it has converged).  The key is a TOLERANT return time from
+ * z_M, as period-colouring programs define it.  A PERIOD-PALETTE render is a bounded render ("Bounded render" above) plus
+ * a table, and that section applies unchanged -- the sample stream, the step, the source of c, which samples are bounded,
+ * the M points z_1 ... z_M of a bounded sample, the projection and the binning, nothing rejected, no interior map,
+ * min_escape_iterations not read, M <= 0 tests and adds nothing -- but for its Histogram and Counters.  The project's own
+ * definition.  Normative:
+ *
+ *   Inputs.  A table lut of n_entries uint32_t entries in the palette's entry format ("Palette render", Table): R = bits
+ *   0-7, G = bits 8-15, B = bits 16-23; bits 24-31 are not read.  2 <= n_entries <= CB_PERIOD_MAX_ENTRIES (1024); let
+ *   J = n_entries - 1.  A tolerance eps, a finite double >= 0.
+ *
+ *   Period of a bounded sample.  Its orbit is continued past z_M with the same step and the same c, and no escape test is
+ *   made.  For j = 1 ... J, in this operation order and in fp64:
+ *     dr = re(z_{M+j}) - re(z_M)
+ *     di = im(z_{M+j}) - im(z_M)
+ *     d2 = fma(dr, dr, di * di)
+ *   The period is the least j with d2 <= eps, and 0 if there is none; a NaN compares false.  It is a pure function of the
+ *   sample, M, J, eps, the step and c: no schedule enters.  eps = 0 is an exact return, with +0 and -0 alike.
+ *
+ *   Histogram.  Three planes of w*h cb_pixel, plane 0 = R, 1 = G, 2 = B, contiguous.  Each of the M points of a bounded
+ *   sample with period pi adds weight_j(lut[pi]) to its pixel of plane j, for every j with a non-zero weight.  Entry 0 is
+ *   the colour of "no period <= J".
+ *
+ *   Counters.  The bounded render's, with two differences: increments is the sum of the weights added, and skipped_steps
+ *   is the product kernel's executed-work discount (the lock-step kernel leaves it 0).  The steps of the period search are
+ *   counted nowhere.  A bounded sample whose entry is all zero still counts in recorded and replay_steps; the product
+ *   kernel does not replay it, and books the replay it did not make into skipped_steps.
+ *
+ *   Stops -> table.  cb_palette_from_stops(stops, n, lut, n_entries), unchanged, with k read as a period.
+ *
+ *   Image.  As "Palette render", Image: the three planes tone-mapped against their common maximum, a P6 PPM.
+ *
+ *   Consequences.  The constant table 0x010101 makes each plane equal the bounded render's histogram, bit for bit, with
+ *   the same generator states and counters but increments, which is three times as large.  With B_pi the render of the
+ *   table that is 0x000001 at entry pi and 0 elsewhere, the sum over pi of B_pi's plane 0 is the bounded histogram, and
+ *   any table's plane j is the sum over pi of weight_j(lut[pi]) * B_pi.  Under the reference's step with a sampled c,
+ *   eps = 0x1p+10 gives every bounded sample the period 1 (|z_M| <= 2 and |z_{M+1}| < 7).
+ *
+ * Two kernels (draw_periods.hip), with the variants and the refusals of the bounded render's two.  CB_KERNEL_SIMPLE is the
+ * definition in lock-step.  CB_KERNEL_DEFAULT is the product kernel: the bounded render's cycle compression with the
+ * search as a scheduled pass in front of the replay.  If z_k == z_s bit for bit, with p = k - s and rem = (M - s) mod p,
+ * then z_M is the cycle point z_{s+rem} bit for bit and z_{M+j} what the step makes of it, so walking on from z_s gives the
+ * probe after rem steps and every z_{M+j} after that; the replay and its weights are the bounded render's.  Identical
+ * histograms, generator states and counters (but skipped_steps).  The table is read once per bounded orbit from global
+ * memory.  Periods under the Phoenix step, of the anti render, above 1023, and colouring by the multiplier or the internal
+ * angle are out of scope. */
+#define CB_PERIOD_MAX_ENTRIES 1024
+/* The period-palette draw on caller-owned device memory: d_hist is THREE planes of w*h cb_pixel, d_lut the table on the
+ * device.  kernel_variant: what cb_draw_buddhabrot_bounded accepts.  hipErrorInvalidValue, with nothing launched or
+ * written: a NULL table, n_entries outside 2 .. CB_PERIOD_MAX_ENTRIES, a period_eps that is negative, infinite or a NaN,
+ * and everything cb_draw_buddhabrot_bounded refuses.  No interior map is attached. */
+int cb_draw_buddhabrot_periods(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                               const double projection[8], const double julia_c[2] /* NULL: sampled c */,
+                               const uint32_t *d_lut, uint32_t n_entries, double period_eps, void *d_states,
+                               uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                               void *stream);
+
 /* ---- Renderer: SetupCUDA + RenderImage + the -s buffer, as an owned object ---------------------- */
 
 typedef struct cb_renderer cb_renderer;
@@ -960,6 +1024,18 @@ int cb_renderer_phoenix(const cb_renderer *r, double out[2]);
 int cb_renderer_set_bounded(cb_renderer *r);
 /* 1 for a bounded renderer, 0 for any other (or a NULL renderer). */
 int cb_renderer_bounded(const cb_renderer *r);
+/* Makes this a PERIOD-PALETTE renderer ("Period-palette render" above), before its first pass, once, where
+ * cb_renderer_set_bounded is admitted: on a plain renderer it brings the identity projection; a projected or Julia renderer
+ * without a sink keeps its matrix and its c.  lut_host: n_entries entries on the host, 2 .. CB_PERIOD_MAX_ENTRIES, the top
+ * byte of each zero; eps finite and >= 0.  The histogram becomes three planes, as for a palette renderer: read /
+ * write_histogram move all three, cb_renderer_period_palette_image makes the picture, and every later
+ * cb_renderer_render_passes launches period-palette draws with the variants cb_draw_buddhabrot_bounded accepts.
+ * hipErrorInvalidValue, the renderer unchanged: whatever cb_renderer_set_bounded refuses, a NULL table, an entry with a top
+ * byte, n_entries out of range, an eps that is negative, infinite or a NaN.  Afterwards every setter is refused. */
+int cb_renderer_set_period_palette(cb_renderer *r, const uint32_t *lut_host, uint32_t n_entries, double eps);
+/* A period-palette renderer's table length and tolerance: returns 1 and fills what is not NULL; returns 0 and leaves both
+ * alone for any other renderer (or a NULL renderer). */
+int cb_renderer_period_palette(const cb_renderer *r, uint32_t *n_entries, double *eps);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -1050,6 +1126,11 @@ int cb_renderer_frames_image(cb_renderer *r, double gamma, int tone_mode, uint16
  * and arguments on its three planes.  hipErrorInvalidValue for a renderer without a depth palette. */
 int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                                     double *scale_out);
+
+/* The image of a period-palette renderer ("Period-palette render", Image): cb_renderer_palette_image's arithmetic and
+ * arguments on its three planes, the common maximum over all three.  hipErrorInvalidValue for any other renderer. */
+int cb_renderer_period_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
+                                     double *scale_out);
 
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
@@ -1150,7 +1231,8 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * depth-palette lock-step kernel, 22 the frames product kernel (draw_frames_kernel: cb_draw_buddhabrot_frames, whatever
  * its step), 23 the frames lock-step kernel, 24 the Phoenix product kernel (draw_phoenix_kernel:
  * cb_draw_buddhabrot_phoenix), 25 the Phoenix lock-step kernel, 26 the bounded product kernel (draw_bounded_kernel:
- * cb_draw_buddhabrot_bounded, whatever its step), 27 the bounded lock-step kernel.
+ * cb_draw_buddhabrot_bounded, whatever its step), 27 the bounded lock-step kernel, 28 the period-palette product kernel
+ * (draw_periods_kernel: cb_draw_buddhabrot_periods, whatever its step), 29 the period-palette lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the

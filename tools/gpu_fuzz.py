@@ -39,6 +39,11 @@ and demands identical histograms and counters.
                                                    canvas, window, matrix, iteration control, thread count and launches
                                                    with a random p (zero, real, the classic -0.5, the corners, anywhere
                                                    in [-2, 2]^2); TRIALS as there
+    PERIODS=1 python tools/gpu_fuzz.py ...         the period-palette render (cb_draw_buddhabrot_periods): draw_periods_kernel
+                                                   against draw_periods_simple_kernel (draw_periods.hip) -- DEPTH's step,
+                                                   source of c, canvas, window, matrix, iteration control, thread count and
+                                                   launches with a random table of 2 .. 1024 entries (zeros among them) and
+                                                   a tolerance from 0 to 0x1p+10, three planes; TRIALS as there
 """
 import os
 
@@ -367,6 +372,44 @@ def render_phoenix(t, variant):
                              julia_c=t["c"], phoenix_p=t["p"]))
 
 
+def periods_trial(rng):
+    """A depth trial's step, source of c, canvas, window, matrix, iteration control, threads and launches, with a table of
+    2 .. CB_PERIOD_MAX_ENTRIES entries in t["lut"] and a tolerance in t["eps"]."""
+    t = depth_trial(rng)
+    for k in ("row", "slices", "window"):
+        del t[k]
+    n = rng.choice([2, 2, 3, 4, 13, 60, 61, 62, 256, cb.CB_PERIOD_MAX_ENTRIES, rng.randint(2, cb.CB_PERIOD_MAX_ENTRIES)])
+    if t["max_iter"] >= 1000:   # keep the lock-step kernel's run time in hand: its search is up to n - 1 steps per orbit
+        n = min(n, 256)
+    kind = rng.random()
+    if kind < 0.5:      # any weights, a third of the components zero
+        lut = [sum((0 if rng.random() < 0.33 else rng.randint(1, 255)) << (8 * j) for j in range(3)) for _ in range(n)]
+    elif kind < 0.65:   # one colour for every period
+        lut = [rng.choice([0x010101, 0x0000ff, 0xff00ff, 0x020100])] * n
+    elif kind < 0.85:   # one period lit: every other orbit is not replayed
+        lut = [0] * n
+        lut[rng.choice([0, 1, 1, rng.randrange(n)])] = rng.choice([1, 0x000100, 0x030201])
+    else:               # small weights that differ from period to period
+        lut = [(s % 3 + 1) | ((s * 7) % 5) << 8 | ((s >> 1) % 4) << 16 for s in range(n)]
+    if rng.random() < 0.3:  # bits 24-31 are not read
+        lut = [v | rng.randrange(256) << 24 for v in lut]
+    t["lut"] = lut
+    t["eps"] = rng.choice([0.0, 2.0 ** -66, 2.0 ** -66, 1e-20, 2.0 ** -30, 1e-3, 2.0 ** 10])
+    return t
+
+
+def render_periods(t, variant):
+    """The launches of a period-palette trial -> (planes, counters, generator states)."""
+    flags = ((cb.CB_KERNEL_POWER(t["degree"]) if t["degree"] != 2 else 0) | (cb.CB_KERNEL_FLAG_BURNING_SHIP if t["ship"] else 0)
+             | (cb.CB_KERNEL_FORMULA(t["formula"]) if t["formula"] else 0))
+    seq = Launches(cb, cb.FractalDimensions.make(t["w"], t["h"], *t["box"]), t["threads"], planes=3, seed=t["seed"],
+                   first=t["first"], tables={"lut": t["lut"]})
+    return read(seq.launches(cb.draw_buddhabrot_periods, t["launch_samples"], variant | flags,
+                             iterations=cb.IterationControl(t["max_iter"], t["min_iter"]), projection=t["matrix"],
+                             julia_c=t["c"], d_lut=seq.tables["lut"].data_ptr(), n_entries=len(t["lut"]),
+                             period_eps=t["eps"]))
+
+
 def sums_up(want, wc):
     return int(want.sum()) == wc["increments"]
 
@@ -386,6 +429,9 @@ AB_MODES = {
     "FRAMES": dict(name="frames", trial=frames_trial, render=render_frames, kernels=(23, 22), extra=sums_up,
                    pixels_note="; increments %(increments)d", filled=True),
     "PHOENIX": dict(name="phoenix", trial=phoenix_trial, render=render_phoenix, kernels=(25, 24),
+                    extra=lambda want, wc: sums_up(want, wc) and wc["rejected"] == 0,
+                    counters_note=", rejected %(rejected)d", pixels_note="; increments %(increments)d", filled=True),
+    "PERIODS": dict(name="periods", trial=periods_trial, render=render_periods, kernels=(29, 28),
                     extra=lambda want, wc: sums_up(want, wc) and wc["rejected"] == 0,
                     counters_note=", rejected %(rejected)d", pixels_note="; increments %(increments)d", filled=True),
 }
