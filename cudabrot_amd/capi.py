@@ -56,6 +56,7 @@ def CB_KERNEL_FORMULA(formula):
 
 CB_FOCUS_MIN_LEVEL, CB_FOCUS_MAX_LEVEL = 4, 10  # focused render: cells of side 2^-level
 CB_ERROR_KERNEL_INVARIANT, CB_ERROR_FOCUS_EMPTY = 100001, 100002
+CB_ERROR_AIM_EMPTY = 100003  # cb_renderer_set_aim: the probe marked no cell
 # cb_counters.status bits (include/cudabrot_amd.h)
 CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_STATUS_CARRY_FOREIGN = 1, 2, 4, 8
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
@@ -322,6 +323,12 @@ def _load():
         "cb_renderer_phoenix": (i32, [vp, C.POINTER(C.c_double)]),
         "cb_draw_buddhabrot_bounded": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, u32,
                                              vp, i32, vp]),
+        "cb_aim_probe": (i32, [dims_p, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp, u32, u32, i32, vp, vp,
+                               i32, vp]),
+        "cb_draw_buddhabrot_aimed": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp, u32, u32,
+                                           vp, i32, i32, vp, u32, vp]),
+        "cb_renderer_set_aim": (i32, [vp, i32, u32, i32, i32]),
+        "cb_renderer_aim_cells": (i32, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cb_renderer_set_bounded": (i32, [vp]),
         "cb_renderer_bounded": (i32, [vp]),
         "cb_draw_buddhabrot_periods": (i32, [dims_p, vp, it_p, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32,
@@ -373,6 +380,7 @@ EXPORTED_SYMBOLS = (
     "cb_renderer_depth_palette_image "
     "cb_draw_buddhabrot_phoenix cb_renderer_set_phoenix cb_renderer_phoenix "
     "cb_draw_buddhabrot_bounded cb_renderer_set_bounded cb_renderer_bounded "
+    "cb_aim_probe cb_draw_buddhabrot_aimed cb_renderer_set_aim cb_renderer_aim_cells "
     "cb_draw_buddhabrot_periods cb_renderer_set_period_palette cb_renderer_period_palette "
     "cb_renderer_period_palette_image "
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
@@ -558,6 +566,33 @@ def draw_buddhabrot_bounded(dims, d_hist, iterations, projection, julia_c, d_sta
     )
 
 
+def aim_probe(dims, iterations, projection, julia_c, bounded, d_states, n_threads, samples_per_thread, level, d_mask,
+              d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
+    """The probe of an aimed render on caller-owned device memory (cb_aim_probe): the un-aimed render -- projected or, with
+    bounded, bounded; julia_c None samples c -- on the normal stream, which ORs into d_mask the cells of the sample plane
+    whose samples have a plotted orbit point on the canvas."""
+    _check(
+        lib.cb_aim_probe(C.byref(dims), C.byref(iterations), _projection(projection),
+                         None if julia_c is None else _julia_c(julia_c), 1 if bounded else 0, d_states, n_threads,
+                         samples_per_thread, int(level), d_mask, d_counters, kernel_variant, stream),
+        "cb_aim_probe",
+    )
+
+
+def draw_buddhabrot_aimed(dims, d_hist, iterations, projection, julia_c, bounded, d_states, n_threads, samples_per_thread,
+                          d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, level=0, d_cells=0, n_cells=0, stream=0):
+    """The aimed draw on caller-owned device memory (cb_draw_buddhabrot_aimed): the projected or bounded render with its
+    samples from d_cells[0 .. n_cells) of the level's grid (level 0, no cells: the uniform source, the un-aimed render
+    through the aim kernel)."""
+    _check(
+        lib.cb_draw_buddhabrot_aimed(C.byref(dims), d_hist, C.byref(iterations), _projection(projection),
+                                     None if julia_c is None else _julia_c(julia_c), 1 if bounded else 0, d_states,
+                                     n_threads, samples_per_thread, d_counters, kernel_variant, int(level), d_cells, n_cells,
+                                     stream),
+        "cb_draw_buddhabrot_aimed",
+    )
+
+
 def draw_buddhabrot_periods(dims, d_hist, iterations, projection, julia_c, d_lut, n_entries, period_eps, d_states,
                             n_threads, samples_per_thread, d_counters=0, kernel_variant=CB_KERNEL_DEFAULT, stream=0):
     """The period-palette draw on caller-owned device memory (cb_draw_buddhabrot_periods): the bounded draw into three
@@ -693,6 +728,19 @@ class Renderer:
         """(cells listed, cells of the grid) of a focused renderer; (0, 0) without focus."""
         n, total = C.c_uint32(), C.c_uint32()
         _check(lib.cb_renderer_focus_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_focus_cells")
+        return int(n.value), int(total.value)
+
+    def set_aim(self, level=8, probe_passes=64, dilate=1, kernel_variant=CB_KERNEL_DEFAULT):
+        """Make this an aimed renderer (cb_renderer_set_aim), before the first pass -> (cells listed, cells of the grid).
+        Raises CudabrotError with code CB_ERROR_AIM_EMPTY when the probe marks no cell."""
+        _check(lib.cb_renderer_set_aim(self._h, int(level), int(probe_passes), int(dilate), kernel_variant),
+               "cb_renderer_set_aim")
+        return self.aim_cells()
+
+    def aim_cells(self):
+        """(cells listed, cells of the grid) of an aimed renderer; (0, 0) for any other."""
+        n, total = C.c_uint32(), C.c_uint32()
+        _check(lib.cb_renderer_aim_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_aim_cells")
         return int(n.value), int(total.value)
 
     def set_projection(self, projection):

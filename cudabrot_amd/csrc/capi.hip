@@ -263,9 +263,11 @@ constexpr uint32_t kRendererPassesPerLaunch = 128;
 // What a render is: the normal one (of a renderer: its n_channels windows fused, if any), the focused one, or a plotted one
 // (draw_plot.hip and its kin: direct atomics, no deferred scatter, no carry) named by its sink -- one plane, the palette's
 // three, the depth's slices, the depth palette's three, the frames, the Phoenix step's one, the bounded orbits' one, the
-// period palette's three.  Whether c is sampled or fixed (Plotted::julia) is the source beside it.  What varies with the
+// period palette's three, and the aimed kinds: the projected and the bounded render drawn from a cell list (draw_aim.hip).
+// Whether c is sampled or fixed (Plotted::julia) is the source beside it.  What varies with the
 // kind is kind_row and draw_plotted's switch.
-enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix, kBounded, kPeriodPalette };
+enum Kind { kNormal = 0, kFocus, kPlot, kPalette, kDepth, kDepthPalette, kFrames, kPhoenix, kBounded, kPeriodPalette,
+            kAimed, kAimedBounded };
 bool is_plotted(Kind k) { return k != kNormal && k != kFocus; }
 
 // What every draw launch is given: the public entry points fill it from their arguments, a renderer from itself and the
@@ -295,6 +297,12 @@ struct Plotted {
   int n_frames;
   double phoenix_p[2];  // kPhoenix
   double period_eps;    // kPeriodPalette
+  // kAimed, kAimedBounded: the grid's level and the cell list (level 0, no cells: the uniform source), and the step bits of
+  // the kernel variant the list was probed with -- a launch with other bits is refused
+  int aim_level;
+  const uint32_t *d_aim_cells;
+  uint32_t aim_n_cells;
+  int aim_step_bits;
 };
 
 }  // namespace
@@ -366,6 +374,8 @@ KindRow kind_row(const Plotted &p) {
     case kPhoenix: return {1, kImageSingle, true};
     case kBounded: return {1, kImageSingle, false};
     case kPeriodPalette: return {3, kImageRgb, false};
+    case kAimed: return {1, kImageSingle, false};
+    case kAimedBounded: return {1, kImageSingle, false};
   }
   return {0, kImageSingle, false};  // (no kind)
 }
@@ -379,20 +389,24 @@ bool variant_ok(const Plotted &p, int kernel_variant) {
 // May the renderer become `want`?  The one rule of every setter: only before the first pass; a channel renderer, a focused
 // one and one with a sink stay what they are; a plain one takes a focus, a projection (with or without a fixed c) or a
 // palette, the bounded or the period-palette sink, which bring the identity projection; a projected or Julia one without a
-// sink takes any sink.
+// sink takes any sink; an aim (kAimed) is taken by a plain one, which gains the identity projection, and by a projected or
+// Julia one without a sink, and a bounded one takes the bounded aim (kAimedBounded); an aimed one takes nothing.
 bool admits(const cb_renderer *r, Kind want) {
   if (!r || r->rendered || r->n_channels > 0) return false;
   switch (r->what.kind) {
-    case kNormal: return want == kFocus || want == kPlot || want == kPalette || want == kBounded || want == kPeriodPalette;
-    case kPlot: return is_plotted(want) && want != kPlot;
+    case kNormal: return want == kFocus || want == kPlot || want == kPalette || want == kBounded || want == kPeriodPalette ||
+                         want == kAimed;
+    case kPlot: return is_plotted(want) && want != kPlot && want != kAimedBounded;
+    case kBounded: return want == kAimedBounded;
     case kFocus:
     case kPalette:
     case kDepth:
     case kDepthPalette:
     case kFrames:
     case kPhoenix:
-    case kBounded:
-    case kPeriodPalette: return false;
+    case kPeriodPalette:
+    case kAimed:
+    case kAimedBounded: return false;
   }
   return false;
 }
@@ -528,9 +542,23 @@ int plot_args(const Launch &l, const double projection[8], const double julia_c[
   return 0;
 }
 
-// One plotted launch: what the nine cb_draw_buddhabrot_{projected .. periods} entry points and a plotted renderer do once
-// their own arguments have passed.  interior_level (may be null): the level of the interior map the launch used, 0 for none
-// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 29.
+// The step of a plotted launch in its kernel variant: a formula, a degree or the Burning Ship.
+constexpr int kStepBits = CB_KERNEL_FORMULA_MASK | CB_KERNEL_POWER_MASK | CB_KERNEL_FLAG_BURNING_SHIP;
+
+// The grid of an aimed launch (level 0: none).
+void aim_grid(cb::AimArgs &aa, int level) {
+  aa.level = level;
+  if (level) {
+    aa.cell_side = ldexp(1.0, -level);
+    aa.cell_scale = ldexp(1.0, -(level + 2));
+    aa.cells_per_unit = ldexp(1.0, level);
+  }
+}
+
+// One plotted launch: what the ten cb_draw_buddhabrot_{projected .. periods, aimed} entry points and a plotted renderer
+// do once their own arguments have passed.  interior_level (may be null): the level of the interior map the launch used, 0 for none
+// or when nothing was launched.  cb_debug_last_draw_kernel names the kind and the step, product / lock-step: 8 .. 31
+// (cb_aim_probe, which has no histogram, fills its AimArgs itself and reports 30 / 31 as well).
 int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   if (interior_level) *interior_level = 0;
   if (!variant_ok(p, l.kernel_variant)) return (int) hipErrorInvalidValue;
@@ -539,7 +567,8 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
   {
     const int rc = plot_args(l, p.kind == kFrames ? kIdentityProjection : p.projection, p.julia ? p.julia_c : nullptr,
                              p.kind == kPalette ? p.d_lut : nullptr,
-                             p.kind != kPhoenix && p.kind != kBounded && p.kind != kPeriodPalette, &pa, &lockstep);
+                             p.kind != kPhoenix && p.kind != kBounded && p.kind != kPeriodPalette && p.kind != kAimedBounded,
+                             &pa, &lockstep);
     if (rc) return rc;
   }
   const hipStream_t stream = reinterpret_cast<hipStream_t>(l.stream);
@@ -604,6 +633,20 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
       const cb::PeriodArgs qa = {pa, p.d_lut, (int) p.n_entries, p.period_eps, pa.plane_pixels};
       report(28);
       e = cb::launch_draw_periods(qa, lockstep, stream);
+      break;
+    }
+    case kAimed:
+    case kAimedBounded: {  // the projected or the bounded launch from the cell list; the map by plot_args' rule, above
+      if ((l.kernel_variant & kStepBits) != p.aim_step_bits) return (int) hipErrorInvalidValue;  // not the probe's step
+      cb::AimArgs aa;
+      memset(&aa, 0, sizeof(aa));
+      aa.p = pa;
+      aa.bounded = p.kind == kAimedBounded ? 1 : 0;
+      aa.cells = p.d_aim_cells;
+      aa.n_cells = p.aim_n_cells;
+      aim_grid(aa, p.aim_level);
+      report(30);
+      e = cb::launch_draw_aim(aa, lockstep, stream);
       break;
     }
   }
@@ -850,6 +893,9 @@ const char *cb_error_string(int code) {
   }
   if (code == CB_ERROR_FOCUS_EMPTY) {
     return "the focus probe marked no cell: no probed sample has an accepted orbit that enters the canvas";
+  }
+  if (code == CB_ERROR_AIM_EMPTY) {
+    return "the aim probe marked no cell: no probed sample has a plotted orbit that enters the canvas";
   }
   return hipGetErrorString((hipError_t) code);
 }
@@ -1431,7 +1477,113 @@ int cb_renderer_set_bounded(cb_renderer *r) {
   return 0;
 }
 
-int cb_renderer_bounded(const cb_renderer *r) { return r && r->what.kind == kBounded ? 1 : 0; }
+int cb_renderer_bounded(const cb_renderer *r) {
+  return r && (r->what.kind == kBounded || r->what.kind == kAimedBounded) ? 1 : 0;
+}
+
+// ---- aimed render (draw_aim.hip; include/cudabrot_amd.h, "Aimed render") ----------------------------------------------
+
+int cb_aim_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *iterations, const double projection[8],
+                 const double julia_c[2], int bounded, void *d_states, uint32_t n_threads, uint32_t samples_per_thread,
+                 int level, uint32_t *d_mask, cb_counters *d_counters, int kernel_variant, void *stream) {
+  const Launch l = {dims, nullptr, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!dims || !iterations || !d_states || !d_mask || dims->w <= 0 || dims->h <= 0 ||
+      !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c) || level < CB_FOCUS_MIN_LEVEL ||
+      level > CB_FOCUS_MAX_LEVEL) {
+    return (int) hipErrorInvalidValue;
+  }
+  cb::AimArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  bool lockstep = false;
+  const int rc = plot_args(l, p.projection, p.julia ? p.julia_c : nullptr, nullptr, !bounded, &aa.p, &lockstep);
+  if (rc) return rc;
+  aa.bounded = bounded ? 1 : 0;
+  aa.mask = d_mask;
+  aim_grid(aa, level);
+  const hipError_t e = cb::launch_draw_aim(aa, lockstep, reinterpret_cast<hipStream_t>(stream));
+  if (e == hipSuccess) g_last_draw_kernel.store(lockstep ? 31 : 30, std::memory_order_relaxed);  // a refusal names nothing
+  return (int) e;
+}
+
+int cb_draw_buddhabrot_aimed(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2], int bounded, void *d_states,
+                             uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
+                             int level, const uint32_t *d_cells, uint32_t n_cells, void *stream) {
+  const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
+  Plotted p;
+  if (!launch_ok(l) || !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c)) {
+    return (int) hipErrorInvalidValue;
+  }
+  const bool uniform = d_cells == nullptr && n_cells == 0 && level == 0;  // the un-aimed render through this kernel
+  if (!uniform && (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !d_cells || n_cells == 0)) {
+    return (int) hipErrorInvalidValue;
+  }
+  p.aim_level = level;
+  p.d_aim_cells = d_cells;
+  p.aim_n_cells = n_cells;
+  p.aim_step_bits = kernel_variant & kStepBits;
+  return draw_plotted(l, p, nullptr);
+}
+
+int cb_renderer_set_aim(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
+  if (!r) return (int) hipErrorInvalidValue;
+  const bool bounded = r->what.kind == kBounded;
+  if (!admits(r, bounded ? kAimedBounded : kAimed) || probe_passes == 0 || dilate < 0 || level < CB_FOCUS_MIN_LEVEL ||
+      level > CB_FOCUS_MAX_LEVEL) {
+    return (int) hipErrorInvalidValue;
+  }
+  const double *projection = r->what.kind == kNormal ? kIdentityProjection : r->what.projection;  // alone: the identity
+  const double *julia_c = r->what.kind != kNormal && r->what.julia ? r->what.julia_c : nullptr;
+  CB_TRY(hipSetDevice(r->device));
+  const size_t mask_bytes = cb_focus_mask_bytes(level);
+  void *d_states = nullptr;
+  uint32_t *d_mask = nullptr, *d_cells = nullptr;
+  std::vector<uint32_t> mask(mask_bytes / sizeof(uint32_t)), cells;
+  uint32_t n_cells = 0;
+  int rc = (int) hipMalloc(&d_states, cb_rng_state_bytes(r->n_threads));
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_mask), mask_bytes);
+  if (!rc) rc = (int) hipMemsetAsync(d_mask, 0, mask_bytes, r->stream);
+  if (!rc) rc = cb_initialize_rng(r->seed, r->first_subsequence, r->n_threads, d_states, r->stream);
+  for (uint32_t left = probe_passes; !rc && left > 0;) {
+    const uint32_t now = left < kRendererPassesPerLaunch ? left : kRendererPassesPerLaunch;
+    rc = cb_aim_probe(&r->dims, &r->iterations, projection, julia_c, bounded ? 1 : 0, d_states, r->n_threads,
+                      now * CB_SAMPLES_PER_THREAD, level, d_mask, nullptr, kernel_variant, r->stream);
+    left -= now;
+  }
+  if (!rc) rc = (int) hipMemcpyAsync(mask.data(), d_mask, mask_bytes, hipMemcpyDeviceToHost, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
+  if (!rc) rc = cb_focus_cells(level, mask.data(), dilate, nullptr, &n_cells);
+  if (!rc && n_cells == 0) rc = CB_ERROR_AIM_EMPTY;
+  if (!rc) {
+    cells.resize(n_cells);
+    rc = cb_focus_cells(level, mask.data(), dilate, cells.data(), &n_cells);
+  }
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_cells), (size_t) n_cells * sizeof(uint32_t));
+  if (!rc) rc = (int) hipMemcpy(d_cells, cells.data(), (size_t) n_cells * sizeof(uint32_t), hipMemcpyHostToDevice);
+  (void) hipFree(d_states);
+  (void) hipFree(d_mask);
+  if (rc) {
+    (void) hipFree(d_cells);
+    return rc;
+  }
+  if (r->what.kind == kNormal) memcpy(r->what.projection, kIdentityProjection, sizeof(r->what.projection));
+  r->what.kind = bounded ? kAimedBounded : kAimed;
+  r->what.aim_level = level;
+  r->what.d_aim_cells = d_cells;
+  r->what.aim_n_cells = n_cells;
+  r->what.aim_step_bits = kernel_variant & kStepBits;
+  return 0;
+}
+
+int cb_renderer_aim_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total) {
+  if (!r) return (int) hipErrorInvalidValue;
+  const bool aimed = r->what.kind == kAimed || r->what.kind == kAimedBounded;
+  const uint32_t n = aimed ? 4u << r->what.aim_level : 0u;
+  if (n_cells) *n_cells = aimed ? r->what.aim_n_cells : 0u;
+  if (n_total) *n_total = n * n;
+  return 0;
+}
 
 int cb_draw_buddhabrot_periods(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
                                const double projection[8], const double julia_c[2], const uint32_t *d_lut,
@@ -1803,6 +1955,7 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_counters);
   (void) hipFree(r->d_carry);
   (void) hipFree(r->d_focus_cells);
+  (void) hipFree(const_cast<uint32_t *>(r->what.d_aim_cells));
   (void) hipFree(const_cast<uint32_t *>(r->what.d_lut));
   (void) hipFree(const_cast<double *>(r->what.d_frames));
   delete r->frames;

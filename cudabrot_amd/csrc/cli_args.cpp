@@ -322,6 +322,31 @@ const std::vector<Flag> &flag_table() {
          s.focus_dilate = (int) i;
          return kOk;
        }},
+      // --aim, --aim-level L, --aim-probe PASSES, --aim-dilate D: a cropped plotted render sampled only from the cells of its
+      // sample plane whose samples reach the canvas (include/cudabrot_amd.h, "Aimed render"); each value flag turns --aim on
+      {"--aim", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.aim = true; return kOk; }},
+      {"--aim-level", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.aim = true;
+         if (i < CB_FOCUS_MIN_LEVEL || i > CB_FOCUS_MAX_LEVEL) return "Invalid aim level (want 4 to 10)";
+         s.aim_level = (int) i;
+         return kOk;
+       }},
+      {"--aim-probe", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.aim = true;
+         if (i < 1) return "Invalid aim probe (want at least 1 pass)";
+         s.aim_probe = i;
+         return kOk;
+       }},
+      {"--aim-dilate", Value::kInt, nullptr, false,
+       [](Settings &s, long i, double, const char *) {
+         s.aim = true;
+         if (i < 0) return "Invalid aim dilation (want 0 or more cells)";
+         s.aim_dilate = (int) i;
+         return kOk;
+       }},
       // --project a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG: the plane of the 4-D set (z_re, z_im, c_re, c_im) the
       // orbits are plotted on (include/cudabrot_amd.h, "Projected render")
       {"--project", Value::kText, nullptr, false,
@@ -538,6 +563,7 @@ const Partner kDepthPalette = {[](const Settings &s) { return s.depth_palette();
 const Partner kFormula = {[](const Settings &s) { return s.formula != 0; }, "--formula"};
 const Partner kSweep = {[](const Settings &s) { return s.sweep_given; }, "--sweep"};
 const Partner kPhoenix = {[](const Settings &s) { return s.phoenix; }, "--phoenix"};
+const Partner kPeriodPalette = {[](const Settings &s) { return s.period_palette(); }, "--period-palette"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -552,6 +578,11 @@ struct Refusal {
 
 const std::vector<Refusal> &refusal_table() {
   static const std::vector<Refusal> table = {
+      // an aimed render is a projected, Julia or bounded render of one plane without a table, drawn from a cell list
+      // (include/cudabrot_amd.h, "Aimed render").  The first row: it combines with --bounded, --formula, --power, --julia and
+      // a projection, whose rows would otherwise say what it refuses in their own name -- and no line without --aim meets it
+      {[](const Settings &s) { return s.aim; }, "--aim",
+       {kFocus, kAnti, kPalette, kPeriodPalette, kDepth, kDepthPalette, kSweep, kPhoenix, kChannel, kGpus}, nullptr},
       // a period-palette render is a bounded render with a table (include/cudabrot_amd.h, "Period-palette render"): its
       // rows stand ahead of --bounded's, which refuses everything else in its own name -- and no line without the two flags
       // meets them

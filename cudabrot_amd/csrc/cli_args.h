@@ -75,7 +75,7 @@ struct Settings {
   // projection's
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
-  bool plotted() const { return projected() || depth_given || sweep_given || phoenix || bounded; }
+  bool plotted() const { return projected() || depth_given || sweep_given || phoenix || bounded || aim; }
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
@@ -108,6 +108,13 @@ struct Settings {
   }
   bool period_eps_given = false;
   double period_eps = 0x1p-66;
+  // --aim (extension): a plotted render -- projected or Julia, under any of their steps, or --bounded -- whose samples are
+  // drawn only from the cells of the sample plane a probe found to reach the canvas (cb_renderer_set_aim); makes the run a
+  // projected one as --depth does (alone: the identity), with a first refusal row of its own
+  bool aim = false;
+  int aim_level = 8;                                // --aim-level: cells of side 2^-L
+  long aim_probe = 64;                              // --aim-probe: reference passes of the probe
+  int aim_dilate = 1;                               // --aim-dilate: cells the probe's mask is widened by
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

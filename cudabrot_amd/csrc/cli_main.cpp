@@ -84,6 +84,10 @@ class Run {
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       if (cfg_.phoenix) fprintf(stderr, "{\"phoenix\": [\"%a\", \"%a\"]}\n", cfg_.phoenix_p[0], cfg_.phoenix_p[1]);  // and p
       if (cfg_.bounded) fprintf(stderr, "{\"bounded\": true}\n");  // and which orbits are plotted
+      if (cfg_.aim) {  // and where the samples come from: the list is a function of these and of the lines above
+        fprintf(stderr, "{\"aim\": {\"level\": %d, \"probe\": %ld, \"dilate\": %d}}\n", cfg_.aim_level, cfg_.aim_probe,
+                cfg_.aim_dilate);
+      }
       if (cfg_.period_palette()) {  // and the colours of their periods, with the tolerance of the return test
         fprintf(stderr, "{\"period_palette\": [");
         for (int j = 0; j < cfg_.n_period_stops; ++j) {
@@ -331,6 +335,7 @@ class Run {
                         (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0) | (cfg_.power ? CB_KERNEL_POWER(cfg_.power) : 0) |
                         (cfg_.formula ? CB_KERNEL_FORMULA(cfg_.formula) : 0);
     if (cfg_.focus) set_focus(variant);
+    if (cfg_.aim) set_aim(variant);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));
     for (cb_renderer *p : peers_) CB_CHECK(cb_renderer_prepare(p, variant));
@@ -401,6 +406,21 @@ class Run {
     CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
     printf("Focus: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", n_cells, n_total,
            cfg_.focus_level, cfg_.focus_probe, cfg_.focus_dilate);
+    fflush(stdout);
+  }
+
+  // --aim: likewise for a plotted render, after every setter that makes the renderer what it is.
+  void set_aim(int variant) {
+    const int rc = cb_renderer_set_aim(renderer_, cfg_.aim_level, (uint32_t) cfg_.aim_probe, cfg_.aim_dilate, variant);
+    if (rc == CB_ERROR_AIM_EMPTY) {
+      printf("Aim: no sample of the %ld probe passes reaches the canvas; nothing to render.\n", cfg_.aim_probe);
+      die();
+    }
+    CB_CHECK(rc);
+    uint32_t n_cells = 0, n_total = 0;
+    CB_CHECK(cb_renderer_aim_cells(renderer_, &n_cells, &n_total));
+    printf("Aim: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", n_cells, n_total,
+           cfg_.aim_level, cfg_.aim_probe, cfg_.aim_dilate);
     fflush(stdout);
   }
 
@@ -655,6 +675,12 @@ class Run {
       uint32_t n_cells = 0, n_total = 0;
       CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
       fprintf(stderr, "\"focus_cells\": %u, \"focus_total\": %u, \"focus_fraction\": %.9g, ", n_cells, n_total,
+              n_total ? (double) n_cells / (double) n_total : 0.0);
+    }
+    if (cfg_.aim) {  // likewise for an aimed render
+      uint32_t n_cells = 0, n_total = 0;
+      CB_CHECK(cb_renderer_aim_cells(renderer_, &n_cells, &n_total));
+      fprintf(stderr, "\"aim_cells\": %u, \"aim_total\": %u, \"aim_fraction\": %.9g, ", n_cells, n_total,
               n_total ? (double) n_cells / (double) n_total : 0.0);
     }
     fprintf(stderr,

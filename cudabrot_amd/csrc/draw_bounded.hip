@@ -24,19 +24,6 @@
 
 namespace cb {
 
-namespace {
-
-// One step with c = (c_re, c_im), every choice a run-time argument: a formula code, else a degree other than 2, else the
-// reference's step or its Burning Ship variant.
-__device__ __forceinline__ double bounded_step(int formula, int degree, bool ship, double c_re, double c_im, double &r,
-                                               double &i) {
-  if (formula != 0) return formula_step(formula, c_re, c_im, r, i);
-  if (degree != 2) return power_step(degree, c_re, c_im, r, i);
-  return ship ? mandel_step_ship(c_re, c_im, r, i) : mandel_step(c_re, c_im, r, i);
-}
-
-}  // namespace
-
 // ------------------------------------------------------------------------------------------------
 // draw_bounded_simple_kernel: the definition, verbatim, written out
 // ------------------------------------------------------------------------------------------------
@@ -111,68 +98,6 @@ __global__ void __launch_bounds__(256) draw_bounded_simple_kernel(PlotArgs pa) {
 // A sampled c: NEXT draws c, z_0 = c, and the plot's constant is made from it when the sample is known not to escape.  A
 // fixed c: NEXT draws z_0 into the lane's (cr, ci), where the scheduler starts z and restarts it for REPLAY; the step takes
 // the kernel's c, wave-uniform, and the plot's constant is made from it once, before the first round.
-
-namespace {
-
-template <class Step, bool kJulia>
-struct BoundedMode {
-  Plot plot;
-  const double c_re, c_im;  // kJulia: the fixed c
-  int cyc = 0;              // REPLAY: s, the first cycle point (> max_iter: no cycle)
-  int rem = 0;              // REPLAY: weight q + 1 up to z_{s+rem}, q after it
-  unsigned long long q = 0ull;
-
-  __device__ __forceinline__ double step(RoundLane &l) {
-    return kJulia ? Step::step(c_re, c_im, l.r, l.i) : Step::step(l.cr, l.ci, l.r, l.i);
-  }
-
-  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    uniform_sample(rng, l.cr, l.ci);
-    return kSampleIterate;
-  }
-
-  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {  // nothing recorded
-    st.too_fast++;
-    st.iterate_steps += (unsigned long long) l.end;
-    return false;
-  }
-
-  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool cycle) {
-    if (cycle) {  // z_k == z_saved: p = k - saved (a multiple of the least period)
-      const int p = l.k - l.saved;
-      cyc = l.saved;
-      l.end = l.saved - 1 + p;
-      q = (unsigned long long) ((l.max_iter - l.saved) / p);
-      rem = (l.max_iter - l.saved) % p;
-      st.reserved += (unsigned long long) (l.max_iter - l.k) + (unsigned long long) (l.max_iter - l.end);
-    } else {
-      cyc = l.max_iter + 1;  // no cycle seen: all M points with weight 1
-      l.end = l.max_iter;
-      q = 0ull;
-      rem = 0;
-    }
-    st.never_escaped++;
-    st.recorded++;
-    st.iterate_steps += (unsigned long long) l.max_iter;
-    st.replay_steps += (unsigned long long) l.max_iter;
-    if (!kJulia) plot.constant(l.cr, l.ci);
-    return true;
-  }
-
-  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
-    const double u = project_point(plot.pa.p[0], plot.pa.p[1], l.r, l.i, plot.ku);
-    const double v = project_point(plot.pa.p[4], plot.pa.p[5], l.r, l.i, plot.kv);
-    int row, col;
-    if (pixel_of(u, v, plot.cv, row, col)) {
-      const unsigned long long w = l.k < cyc ? 1ull : (l.k - cyc <= rem ? q + 1ull : q);
-      add_to_pixel(plot.pa.d.hist, plot.cv, row, col, w);
-      st.increments += w;
-    }
-    return false;
-  }
-};
-
-}  // namespace
 
 // The body stands in the kernel, not in a function the kernel calls.
 template <class Step, bool kJulia>

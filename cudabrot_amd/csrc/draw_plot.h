@@ -1,7 +1,8 @@
 // draw_plot.h -- what the kernels that plot on a plane of the 4-D set share (draw_plot.hip; include/cudabrot_amd.h,
 // "Projected render"): the four fused operations of a plotted point, the plot of a replayed point for the modes of
 // draw_rounds.h's scheduler, the steps those modes are instantiated with, the modes themselves -- a sampled c, a fixed
-// one, and the palette render's mode, which builds on either --, and what the launchers of every family that plots share
+// one, the palette render's mode, which builds on either, and the bounded render's (draw_bounded.hip), which the aimed
+// render (draw_aim.hip) wraps as it wraps the first two --, and what the launchers of every family that plots share
 // (draw_plot.hip, draw_depth.hip, draw_depth_palette.hip): the list of the steps, a step's index and the checks of one.
 #pragma once
 
@@ -79,12 +80,28 @@ __device__ __forceinline__ unsigned long long palette_weight(uint32_t entry, int
 
 namespace {
 
+// One step with c = (c_re, c_im), every choice a run-time argument: a formula code, else a degree other than 2, else the
+// reference's step or its Burning Ship variant.
+__device__ __forceinline__ double bounded_step(int formula, int degree, bool ship, double c_re, double c_im, double &r,
+                                               double &i) {
+  if (formula != 0) return formula_step(formula, c_re, c_im, r, i);
+  if (degree != 2) return power_step(degree, c_re, c_im, r, i);
+  return ship ? mandel_step_ship(c_re, c_im, r, i) : mandel_step(c_re, c_im, r, i);
+}
+
 // The interior map (DrawArgs::interior_map), on undoubled coordinates: column floor((c_re + 2) 2^level), row
-// floor(|c_im| 2^level), level = interior_shift + 1; c_re + 2 is exact for every sample of the stream.  true: every
-// sample of the cell that holds c provably never escapes.
+// floor(|c_im| 2^level), level = interior_shift + 1.  true: every sample of the cell that holds c provably never escapes.
+// kAnySample false: c is a sample of the normal stream, for which c_re + 2 is exact, and the column is made from that sum.
+// kAnySample true: c is any double in [-2, 2] -- a sample of a cell list (draw_aim.hip) is corner + offset, ONE rounded
+// addition, and for c_re > -1 its ulp is finer than that of c_re + 2, so the sum would round, and could round up onto the
+// next cell's edge.  The column is then floor(c_re 2^level) + 2 2^level: the scaling by a power of two and the floor are
+// both exact, so the cell looked up is the cell that holds c, and the map's proof covers the sample.  For a sample of
+// the normal stream both forms give the same column.
+template <bool kAnySample = false>
 __device__ __forceinline__ bool interior_marked(const DrawArgs &a, double cr, double ci) {
   const int level = (int) a.interior_shift + 1;
-  const double x = __builtin_ldexp(cr + 2.0, level);
+  const double x = kAnySample ? __builtin_floor(__builtin_ldexp(cr, level)) + __builtin_ldexp(2.0, level)
+                              : __builtin_ldexp(cr + 2.0, level);
   const double y = __builtin_ldexp(__builtin_fabs(ci), level);
   if (!(x >= 0.0)) return false;
   const uint32_t col = (uint32_t) x;
@@ -102,13 +119,19 @@ struct PlotMode {
 
   __device__ __forceinline__ double step(RoundLane &l) { return Step::step(l.cr, l.ci, l.r, l.i); }
 
-  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    uniform_sample(rng, l.cr, l.ci);
+  // What becomes of the sample drawn into (l.cr, l.ci).  kAnySample: it may come from another source than the normal
+  // stream (draw_aim.hip draws from a cell list), and the map is looked up with the exact column (interior_marked).
+  template <bool kAnySample = false>
+  __device__ __forceinline__ int drawn(RoundLane &l) {
     if (!Step::kMandelbrot) return kSampleIterate;
     if (in_main_cardioid(l.cr, l.ci) || in_order2_bulb(l.cr, l.ci)) return kSampleRejected;
     const DrawArgs &a = plot.pa.d;
-    if (a.interior_map != nullptr && interior_marked(a, l.cr, l.ci)) return kSampleInterior;  // not iterated
+    if (a.interior_map != nullptr && interior_marked<kAnySample>(a, l.cr, l.ci)) return kSampleInterior;  // not iterated
     return kSampleIterate;
+  }
+  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
+    uniform_sample(rng, l.cr, l.ci);
+    return drawn(l);
   }
 
   __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
@@ -133,9 +156,11 @@ struct JuliaMode {
 
   __device__ __forceinline__ double step(RoundLane &l) { return Step::step(c_re, c_im, l.r, l.i); }
 
+  template <bool kAnySample = false>
+  __device__ __forceinline__ int drawn(RoundLane &) { return kSampleIterate; }
   __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
     uniform_sample(rng, l.cr, l.ci);
-    return kSampleIterate;
+    return drawn(l);
   }
 
   __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {
@@ -191,6 +216,69 @@ struct PaletteMode {
           st.increments += weight;
         }
       }
+    }
+    return false;
+  }
+};
+
+
+// The mode of a bounded render (draw_bounded.hip has the commentary): either source of c, the orbits that do not escape
+// replayed cycle-compressed, each point with its exact integer weight.
+template <class Step, bool kJulia>
+struct BoundedMode {
+  Plot plot;
+  const double c_re, c_im;  // kJulia: the fixed c
+  int cyc = 0;              // REPLAY: s, the first cycle point (> max_iter: no cycle)
+  int rem = 0;              // REPLAY: weight q + 1 up to z_{s+rem}, q after it
+  unsigned long long q = 0ull;
+
+  __device__ __forceinline__ double step(RoundLane &l) {
+    return kJulia ? Step::step(c_re, c_im, l.r, l.i) : Step::step(l.cr, l.ci, l.r, l.i);
+  }
+
+  template <bool kAnySample = false>
+  __device__ __forceinline__ int drawn(RoundLane &) { return kSampleIterate; }
+  __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
+    uniform_sample(rng, l.cr, l.ci);
+    return drawn(l);
+  }
+
+  __device__ __forceinline__ bool escaped(RoundLane &l, LaneStats &st) {  // nothing recorded
+    st.too_fast++;
+    st.iterate_steps += (unsigned long long) l.end;
+    return false;
+  }
+
+  __device__ __forceinline__ bool never_escapes(RoundLane &l, LaneStats &st, bool cycle) {
+    if (cycle) {  // z_k == z_saved: p = k - saved (a multiple of the least period)
+      const int p = l.k - l.saved;
+      cyc = l.saved;
+      l.end = l.saved - 1 + p;
+      q = (unsigned long long) ((l.max_iter - l.saved) / p);
+      rem = (l.max_iter - l.saved) % p;
+      st.reserved += (unsigned long long) (l.max_iter - l.k) + (unsigned long long) (l.max_iter - l.end);
+    } else {
+      cyc = l.max_iter + 1;  // no cycle seen: all M points with weight 1
+      l.end = l.max_iter;
+      q = 0ull;
+      rem = 0;
+    }
+    st.never_escaped++;
+    st.recorded++;
+    st.iterate_steps += (unsigned long long) l.max_iter;
+    st.replay_steps += (unsigned long long) l.max_iter;
+    if (!kJulia) plot.constant(l.cr, l.ci);
+    return true;
+  }
+
+  __device__ __forceinline__ bool point(RoundLane &l, LaneStats &st) {
+    const double u = project_point(plot.pa.p[0], plot.pa.p[1], l.r, l.i, plot.ku);
+    const double v = project_point(plot.pa.p[4], plot.pa.p[5], l.r, l.i, plot.kv);
+    int row, col;
+    if (pixel_of(u, v, plot.cv, row, col)) {
+      const unsigned long long w = l.k < cyc ? 1ull : (l.k - cyc <= rem ? q + 1ull : q);
+      add_to_pixel(plot.pa.d.hist, plot.cv, row, col, w);
+      st.increments += w;
     }
     return false;
   }

@@ -344,6 +344,34 @@ hipError_t launch_draw_phoenix(const PhoenixArgs &a, bool lockstep, hipStream_t 
 // lane per reference thread, every point with weight 1; else the cycle-compressed product kernel.
 hipError_t launch_draw_bounded(const PlotArgs &a, bool lockstep, hipStream_t stream);
 
+// draw_aim.hip: the aimed render ("Aimed render" of include/cudabrot_amd.h) -- an un-aimed render (a projected or Julia
+// launch of draw_plot.hip without a table, or a bounded launch of draw_bounded.hip) behind the focused render's source and
+// in front of its sink:
+//   p        the un-aimed launch: canvas, matrix, step and source of c as there; palette must be 0 and lut null.
+//            p.d.interior_map is read by the escaping kind with the Mandelbrot step on a sampled c only.
+//   bounded  0: the escaping orbits that pass the accept filter (launch_draw_plot); else the orbits that do not escape
+//            (launch_draw_bounded).
+//   cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample), the
+//            cells those of the SAMPLE plane: c when c is sampled, z_0 when c is fixed;
+//   mask == null:  the histogram sink (p.d.hist, what the un-aimed launch adds); else the probe's mask (one bit per cell, set
+//            by a sample whose plotted orbit has an in-canvas point; the replay stops there, p.d.hist is not read).
+//   The grid fields are FocusArgs', read when cells or mask is given.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of p, a table, cells and mask together, cells
+// with n_cells == 0, a level outside CB_FOCUS_MIN_LEVEL .. CB_FOCUS_MAX_LEVEL when either is given.  lockstep: the
+// definition, one lane per reference thread, every point with weight 1.
+struct AimArgs {
+  PlotArgs p;
+  int bounded;
+  int level;              // cells of side 2^-level (cells or mask given)
+  uint32_t n_cells;       // entries of `cells`
+  const uint32_t *cells;  // ascending cell indices row * n + col, n = 4 << level
+  uint32_t *mask;         // n * n bits
+  double cell_side;       // 2^-level
+  double cell_scale;      // 2^-(level + 2): (x + 2) * cell_scale lies in (0, 2^-level]
+  double cells_per_unit;  // 2^level
+};
+hipError_t launch_draw_aim(const AimArgs &a, bool lockstep, hipStream_t stream);
+
 // draw_periods.hip: the period-palette render ("Period-palette render" of include/cudabrot_amd.h) -- a bounded launch whose
 // bounded orbits look a colour up by the period of the cycle they fall onto: each of the M points adds the three weights of
 // lut[period] to its pixel of three planes.

@@ -233,6 +233,8 @@ typedef struct {
 /* Returned (instead of a hipError_t) by cb_renderer_set_focus when the probe marked no cell: no sample of the probe has
  * an accepted orbit that enters the canvas, so a focused render would have nothing to sample from. */
 #define CB_ERROR_FOCUS_EMPTY 100002
+/* cb_renderer_set_aim: the probe marked no cell ("Aimed render"). */
+#define CB_ERROR_AIM_EMPTY 100003
 
 /* RecomputePixelDeltas (cudabrot.cu:505-527).  Returns 1 and fills delta_* if the canvas is valid,
  * else 0 and, if msg is not NULL, *msg points at the reference's message for the failed check. */
@@ -828,6 +830,68 @@ int cb_draw_buddhabrot_bounded(const cb_fractal_dimensions *dims, cb_pixel *d_hi
                                uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant,
                                void *stream);
 
+/* ---- Aimed render: a cropped plotted render sampled only from the cells that reach it -- *
+ *
+ * Every plotted render draws its samples uniformly over [-2, 2)^2, so a crop -- a zoom into the Feigenbaum diagram, one
+ * window of a Julia set's orbits -- costs what the full picture costs and is far noisier.  The AIMED render is to the
+ * plotted renders what the focused render ("Focused render" above) is to the normal one.  The project's own definition.
+ * Normative:
+ *
+ *   An aimed render is an UN-AIMED render plus a cell list.  The un-aimed render is a projected render ("Projected
+ *   render": matrix P, any step of the plotted renders, c sampled or fixed by julia_c) or a bounded render ("Bounded
+ *   render"), with one plane and no table.
+ *
+ *   Sample plane, grid, mask, list.  The sample plane is the plane the stream's samples lie in: with a sampled c that is
+ *   c (and z_0 = c); with a fixed c it is z_0.  Grid, level (CB_FOCUS_MIN_LEVEL .. CB_FOCUS_MAX_LEVEL), mask layout,
+ *   dilation and the ascending list are exactly the focused render's: cb_focus_mask_bytes and cb_focus_cells serve both.
+ *
+ *   Probe.  A launch of the un-aimed render on the normal stream (four draws per sample) that adds nothing to a histogram.
+ *   A sample marks the cell that holds the SAMPLE when its plotted orbit -- z_1 .. z_{k+1} of an accepted escaping orbit,
+ *   z_1 .. z_M of a bounded one -- has at least one point that the binning accepts.  The cell is found as the focused
+ *   render finds it: exact scaling, and the value 2.0 clamped into the last cell.  The replay ends at that point.  The mask
+ *   is a union of bits, so it does not depend on the schedule.
+ *
+ *   Probe counters.  Everything up to the replay is counted as the un-aimed render counts it.  recorded is the number of
+ *   marking samples; replay_steps the steps made up to and including the first in-canvas point, or all of them where there
+ *   is none; increments is 0.  For a bounded orbit replayed cycle-compressed the index of the first in-canvas point is the
+ *   naive replay's: the compressed replay visits z_1 .. z_{s-1+p} in the naive order, and any later point is bit for bit
+ *   one of those.
+ *
+ *   Aimed draw.  Each sample takes six generator outputs, mapped exactly as "Focused render" maps them.  From the sample on
+ *   everything is the un-aimed render's, with the un-aimed render's counter meanings: cardioid / bulb rejection only for
+ *   the Mandelbrot step with a sampled c on the escaping kind; the interior map by the projected render's own rule for
+ *   that same case, and never for bounded; the accept filter; the cycle-compressed weights for bounded.
+ *
+ *   Bias.  As "Focused render": the image is the un-aimed image of the same samples density minus what the unlisted cells
+ *   would have added; a cell no probed sample reached from is dark.
+ *
+ *   Consequences.  With no list (level 0, no cells) the aimed draw is the un-aimed render bit for bit: histogram,
+ *   generator states and counters.  With the identity matrix, the reference's step, a sampled c and escaping orbits the
+ *   probe's mask is cb_focus_probe's and the draw from a list is cb_draw_buddhabrot_focus's -- histogram, generator states
+ *   and counters, skipped_steps apart (the aimed draw consults the interior map, the focused one has none).
+ *
+ * Kernels (draw_aim.hip).  CB_KERNEL_SIMPLE is the definition in lock-step, every point with weight 1; CB_KERNEL_DEFAULT
+ * the product kernels on the round scheduler, the un-aimed render's mode behind the cell source.  The variants are those
+ * cb_draw_buddhabrot_julia / cb_draw_buddhabrot_bounded accept.  Aimed renders into a palette, period-palette, depth,
+ * depth-palette or frames sink, under the Phoenix step, weighted cells and more than one GPU are out of scope. */
+
+/* The probe: ORs into d_mask (cb_focus_mask_bytes(level) bytes on the device, zeroed by the caller before the first
+ * launch) the cells whose samples reach the canvas.  julia_c NULL: c is sampled.  bounded != 0: the bounded kind.
+ * hipErrorInvalidValue, nothing written: a NULL pointer but julia_c / d_counters / stream, a canvas without pixels, a matrix
+ * that is not finite, a c outside [-2, 2]^2, a level out of range, a variant the un-aimed entry point refuses. */
+int cb_aim_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *iterations, const double projection[8],
+                 const double julia_c[2] /* NULL: sampled c */, int bounded, void *d_states, uint32_t n_threads,
+                 uint32_t samples_per_thread, int level, uint32_t *d_mask, cb_counters *d_counters, int kernel_variant,
+                 void *stream);
+/* The aimed draw from d_cells[0 .. n_cells) of the level's grid (device memory, ascending, as cb_focus_cells lists them).
+ * level 0 with d_cells NULL and n_cells 0 is the uniform source: the un-aimed render through this kernel.
+ * hipErrorInvalidValue, nothing written: whatever cb_draw_buddhabrot_julia / _bounded refuse, and any other combination of
+ * level, d_cells and n_cells. */
+int cb_draw_buddhabrot_aimed(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
+                             const double projection[8], const double julia_c[2] /* NULL: sampled c */, int bounded,
+                             void *d_states, uint32_t n_threads, uint32_t samples_per_thread, cb_counters *d_counters,
+                             int kernel_variant, int level, const uint32_t *d_cells, uint32_t n_cells, void *stream);
+
 /* ---- Period-palette render: bounded orbits coloured by their cycle's period ----------- *
  *
  * The bounded render is the one family without colour, for a bounded orbit has no escape index.  Its natural key is the
@@ -1036,6 +1100,19 @@ int cb_renderer_set_period_palette(cb_renderer *r, const uint32_t *lut_host, uin
 /* A period-palette renderer's table length and tolerance: returns 1 and fills what is not NULL; returns 0 and leaves both
  * alone for any other renderer (or a NULL renderer). */
 int cb_renderer_period_palette(const cb_renderer *r, uint32_t *n_entries, double *eps);
+/* Makes this an AIMED renderer ("Aimed render" above), before its first pass, once.  A plain renderer takes it and gains
+ * the identity projection; a projected or Julia renderer without a sink takes it and keeps its matrix and its c; a bounded
+ * renderer takes it and stays bounded; nothing else does.  Probes probe_passes passes (>= 1) on fresh generators made from
+ * the renderer's seed in temporary buffers, exactly as cb_renderer_set_focus does, dilates the mask by `dilate` (>= 0)
+ * cells and keeps the list, so the list is a pure function of (seed, threads, canvas, iterations, matrix, step, c, kind,
+ * level, probe passes, dilate) and a resumed run rebuilds it.  kernel_variant names the step (and CB_KERNEL_SIMPLE the
+ * lock-step probe); every later cb_renderer_render_passes must carry the same step bits, else hipErrorInvalidValue with
+ * nothing launched.  CB_ERROR_AIM_EMPTY when the list is empty (the renderer is then unchanged).  An aimed renderer takes
+ * no later setter, cb_renderer_set_aim included. */
+int cb_renderer_set_aim(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant);
+/* (cells listed, cells of the grid) of an aimed renderer; 0, 0 for any other.  cb_renderer_focus_cells of an aimed renderer
+ * stays 0, 0. */
+int cb_renderer_aim_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total);
 /* Optional, before the first cb_renderer_render_passes: allocates now what that call would allocate for
  * this kernel variant (the scatter workspaces: tens of GB on a large canvas), so that a caller who times
  * the pass loop -- like the reference's "passes took" line, cudabrot.cu:499-500 -- does not time hipMalloc. */
@@ -1232,7 +1309,9 @@ int cb_debug_scatter_layout(const cb_fractal_dimensions *dims, int n_channels, u
  * its step), 23 the frames lock-step kernel, 24 the Phoenix product kernel (draw_phoenix_kernel:
  * cb_draw_buddhabrot_phoenix), 25 the Phoenix lock-step kernel, 26 the bounded product kernel (draw_bounded_kernel:
  * cb_draw_buddhabrot_bounded, whatever its step), 27 the bounded lock-step kernel, 28 the period-palette product kernel
- * (draw_periods_kernel: cb_draw_buddhabrot_periods, whatever its step), 29 the period-palette lock-step kernel.
+ * (draw_periods_kernel: cb_draw_buddhabrot_periods, whatever its step), 29 the period-palette lock-step kernel, 30 the
+ * aim product kernels (draw_aim_kernel: cb_draw_buddhabrot_aimed, and draw_aim_probe_kernel: cb_aim_probe, whatever their
+ * step), 31 the aim lock-step kernel.
  * The kernels give identical results; tests use this to know what they covered. */
 int cb_debug_last_draw_kernel(void);
 /* The level of the interior map the last cb_draw_buddhabrot call of this process used (cells of side 2^-level of the
