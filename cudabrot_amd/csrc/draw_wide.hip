@@ -16,8 +16,9 @@
 //           looked up in the interior map (DrawArgs::interior_map, tools/interior_map.c): a sample of a cell PROVEN
 //           never-escaping is retired here instead of costing the LONG stage ~2000 iterations;
 //   LONG    FOUR orbits per lane, interleaved instruction by instruction (escape test once per chunk);
-//   REPLAY  software-pipelined: the pixel of point n is formed and stored while point n+1 is computed; a lane's
-//           state between bursts is "z_n computed, not yet recorded".
+//   REPLAY  software-pipelined: the pixel of point n is formed while point n+1 is computed; a lane's state between
+//           bursts is "z_n computed, not yet recorded".  On a one-level stream a lane's words of four steps leave
+//           together, as one 16-byte block (kernels.h, kStreamBlocked); on a chunked one, word by word.
 //
 // Launched for: a scatter workspace of one level (canvases of up to 1024 tiles) or a chunked one, one channel, the usual stage
 // split with min_iter == the start of the LONG stage (every BASELINE config with the default -c 20), a carry
@@ -49,6 +50,7 @@ constexpr int kHeadSteps = 4;
 constexpr int kQ1Low = 32;              // run MID while fewer deep orbits than this are queued
 constexpr int kReplayMin = 56;          // suspend REPLAY below this many busy lanes (unless draining)
 constexpr uint32_t kReplayBurst = 32;   // replay steps per asm burst
+static_assert(kReplayBurst % 4u == 0u, "a burst is whole groups of four steps (CBW_REPLAY_LOOP_BLOCKED)");
 constexpr int kPrioBehind = 2;          // s_setprio of the wave of a SIMD that has more left to draw ...
 constexpr int kPrioAhead = 1;           // ... and of the other
 constexpr uint32_t kBrentBits = 2;      // periodicity check: re-save when the chunk count has no bits below its top 2
@@ -795,7 +797,8 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
 //   leave if |z_n|^2 > 4   (cudabrot.cu:363) -- after recording the escaped point, like the reference
 //   z_{n+1} <- z_n^2 + c   (mandel_step2's six instructions, same order) and its |.|^2
 // and the instructions of "record z_n" alternate with those of "z_{n+1}": the two depend on z_n only.  A lane that
-// leaves has computed one point too many, which nothing reads.  17 vector instructions per step.
+// leaves has computed one point too many, which nothing reads.  17 vector instructions per step where every step
+// stores its word (the direct form; it was the one-level stream's too), 15.75 in the blocked loop below.
 #define CBW_REPLAY_BIN_POW2                               \
   "v_fma_f64 %[fx], %[r], %[sx], %[ox]\n\t"               \
   "v_fma_f64 %[fy], %[i], %[sy], %[oy]\n\t"
@@ -879,7 +882,7 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
   "s_cselect_b32 %[ctr], 1, %[minact]\n\t"              \
   "s_cmp_ge_u32 %[t], %[ctr]\n\t"                       \
   "s_cbranch_scc0 2f\n\t"
-#define CBW_REPLAY_HEAD                                   \
+#define CBW_REPLAY_HEAD(PRE)                              \
   "s_sub_u32 %[ctr], %[n], 1\n\t"       /* the loop below runs ctr + 1 = n steps */ \
   "s_mov_b32 %[ch], %[fill]\n\t"        /* (the hits of the burst: fill afterwards - fill before) */ \
   "s_mov_b64 exec, %[act]\n\t"                            \
@@ -887,6 +890,7 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
   "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"                  \
   "s_cmp_lg_u32 %[direct], 0\n\t"                         \
   "s_cbranch_scc1 7f\n\t"                                 \
+  PRE                                                     \
   "1:\n\t"                                                \
   "s_bcnt1_i32_b64 %[t], %[act]\n\t"
 // The loop's tail.  As few scalar instructions and taken branches as it can do with: at two waves per SIMD nothing
@@ -902,32 +906,75 @@ __device__ __forceinline__ void long_retire4(const Orbit (&o)[kSlots], double (&
   "v_cvt_i32_f64 %[col], %[fx]\n\t"                       \
   "v_fma_f64 %[r], %[a], 0.5, %[cr]\n\t"                  \
   "v_cvt_i32_f64 %[row], %[fy]\n\t"
-// The stream's stores keep the default cache policy: the stream is written once and read once, a launch later.
-#define CBW_REPLAY_LOOP                                   \
+// The loop on a one-level stream, BLOCKED (BinLayout, kStreamBlocked): a lane's consecutive points leave together.
+// A lane never changes its orbit inside a burst (CBW_REPLAY_REFILL runs in front of it), so in step j of a GROUP of
+// four steps a lane that records its point -- bounds and `act`, as ever -- forms the word row << 16 | col in
+// accumulator j, and one that records nothing leaves the sentinel 0xFFFFFFFF there (row and col 65535: a pixel that no
+// one-level canvas has).  Behind the fourth step the lanes that hold a real word (`blk`: the steps' masks, or-ed) are
+// ranked ONCE and store their four dwords with one 16-byte store at base + 16 * (fill / 4 + rank): a quarter of the
+// stores, each 1 KiB contiguous and on a 16-byte boundary, and per step one vector instruction (the word) plus a
+// quarter of {four sentinels, two v_mbcnt, the address} in place of {word, two v_mbcnt, address}: 15.75 vector
+// instructions per step.  `fill` counts SLOTS and moves on by whole blocks; the hits are counted step by step (ch).
+// Every way out of the loop -- the last lane gone, the count used up, in any step of a group -- passes the flush at
+// 18: nothing stays in the accumulators when the statement ends.  One taken branch per group.
+// The accumulators are v[124:127] by name (a 16-byte store takes four consecutive registers, and an operand's parts
+// cannot be named): clobbers of the statement, free between statements.  BIN: the text that forms fx, fy.
+#define CBW_BLOCK_FLUSH                                   \
+  "s_mov_b64 vcc, %[blk]\n\t"                             \
+  "s_mov_b64 exec, vcc\n\t"                               \
+  "s_lshr_b32 %[t], %[fill], 2\n\t"                       \
+  "v_mbcnt_lo_u32_b32 %[pidx], vcc_lo, 0\n\t"             \
+  "v_mbcnt_hi_u32_b32 %[pidx], vcc_hi, %[pidx]\n\t"       \
+  "v_add_lshl_u32 %[pidx], %[pidx], %[t], 4\n\t"          \
+  "s_bcnt1_i32_b64 %[t], vcc\n\t"                         \
+  "global_store_dwordx4 %[pidx], v[124:127], %[base]\n\t" \
+  "s_lshl_b32 %[t], %[t], 2\n\t"                          \
+  "s_add_u32 %[fill], %[fill], %[t]\n\t"                  \
+  "s_nop 1\n\t"                       /* (the store reads its four registers before anything writes them) */
+#define CBW_BLOCK_CLEAR                                   \
+  "s_mov_b64 %[blk], 0\n\t"                               \
+  "s_mov_b64 exec, -1\n\t"            /* every lane: one that is not replaying holds sentinels too */ \
+  "v_mov_b32 v124, -1\n\t"                                \
+  "v_mov_b32 v125, -1\n\t"                                \
+  "v_mov_b32 v126, -1\n\t"                                \
+  "v_mov_b32 v127, -1\n\t"                                \
+  "s_mov_b64 exec, %[act]\n\t"
+#define CBW_BLOCK_CLOBBERS "v124", "v125", "v126", "v127"
+#define CBW_REPLAY_BLOCKED_PRE                            \
+  "s_mov_b32 %[ch], 0\n\t"                                \
+  CBW_BLOCK_CLEAR
+#define CBW_BLOCK_STEP(EJ)                                \
   CBW_REPLAY_STEP_COMMON                                  \
   "s_and_b64 vcc, vcc, %[hx]\n\t"                         \
   "v_mul_f64 %[a], %[r], %[r]\n\t"                        \
-  "v_lshl_or_b32 %[e], %[row], 16, %[col]\n\t"            \
-  "v_mbcnt_lo_u32_b32 %[pidx], vcc_lo, 0\n\t"             \
+  "s_or_b64 %[blk], %[blk], vcc\n\t"                      \
   "v_fma_f64 %[a], %[i], %[i], %[a]\n\t"                  \
-  "v_mbcnt_hi_u32_b32 %[pidx], vcc_hi, %[pidx]\n\t"       \
   "s_bcnt1_i32_b64 %[t], vcc\n\t"                         \
-  "v_add_lshl_u32 %[pidx], %[pidx], %[fill], 2\n\t"       \
   "s_and_b64 %[act], %[act], %[alive]\n\t"                \
   "s_mov_b64 exec, vcc\n\t"                               \
-  "global_store_dword %[pidx], %[e], %[base]\n\t"         \
-  "s_add_u32 %[fill], %[fill], %[t]\n\t"                  \
+  "v_lshl_or_b32 " EJ ", %[row], 16, %[col]\n\t"          \
+  "s_add_u32 %[ch], %[ch], %[t]\n\t"                      \
   "s_mov_b64 exec, %[act]\n\t"                            \
-  "s_cbranch_execz 8f\n\t"              /* (not taken but once) */ \
-  "s_sub_u32 %[ctr], %[ctr], 1\n\t"     /* scc = borrow: the count had reached 0 */ \
-  "s_cbranch_scc0 1b\n\t"                                 \
+  "s_cbranch_execz 8f\n\t"            /* (not taken but once) */ \
+  "s_sub_u32 %[ctr], %[ctr], 1\n\t"   /* scc = borrow: the count had reached 0 */ \
+  "s_cbranch_scc1 28f\n\t"
+#define CBW_BLOCK_NEXT                                    \
+  "s_bcnt1_i32_b64 %[t], %[act]\n\t"
+#define CBW_REPLAY_LOOP_BLOCKED(BIN)                      \
+  BIN CBW_BLOCK_STEP("v124")                              \
+  CBW_BLOCK_NEXT BIN CBW_BLOCK_STEP("v125")               \
+  CBW_BLOCK_NEXT BIN CBW_BLOCK_STEP("v126")               \
+  CBW_BLOCK_NEXT BIN CBW_BLOCK_STEP("v127")               \
+  CBW_BLOCK_FLUSH CBW_BLOCK_CLEAR                         \
+  "s_branch 1b\n\t"                                       \
+  "28:\n\t"                                               \
   "s_add_u32 %[clk], %[clk], %[n]\n\t"  /* the clock moves on by the steps made: all n ... */ \
   "s_branch 18f\n\t"                                      \
   "8:\n\t"                                                \
   "s_sub_u32 %[t], %[n], %[ctr]\n\t"    /* ... or, the last lane gone in step j = n - ctr, that many */ \
   "s_add_u32 %[clk], %[clk], %[t]\n\t"                    \
   "18:\n\t"                                               \
-  "s_sub_u32 %[ch], %[fill], %[ch]\n\t"
+  CBW_BLOCK_FLUSH
 // The loop on a CHUNKED stream (BinLayout::chunked: canvases beyond 1024 tiles; draw_wave.hip, CB_REPLAY_CHUNKED): the word
 // goes to the current chunk of its GROUP of 1024 tiles -- group = tile >> 10; the group's {next word, end of chunk} sit
 // in the wave's LDS at gcl + 8 * group; a returning add takes the place.  The step is ordered so that the LDS round
@@ -1044,7 +1091,7 @@ __device__ __forceinline__ uint32_t replay_stage(uint32_t enable, unsigned long 
   uint32_t cs, ch, ctr, t, nn;
   double a, fx, fy, d0, d1, d2, d3, ox, oy;
   uint32_t pidx, e, col, row;
-  unsigned long long over = 0ull, hit;
+  unsigned long long over = 0ull, hit, blk;
   uint32_t pos = 0u, lim = 0u;
   const uint32_t tlx = kChunked ? kernel_args()->bin.tiles_x : 0u;
   cursors_lds = __builtin_amdgcn_readfirstlane(cursors_lds);
@@ -1081,7 +1128,7 @@ __device__ __forceinline__ uint32_t replay_stage(uint32_t enable, unsigned long 
   if (kPow2 && kChunked) {
     asm volatile("v_mov_b64 %[ox], %[oxs]\n\t"
                  "v_mov_b64 %[oy], %[oys]\n\t"
-                 CBW_REPLAY_REFILL CBW_REPLAY_HEAD CBW_REPLAY_BIN_POW2 CBW_REPLAY_LOOP_CHUNKED
+                 CBW_REPLAY_REFILL CBW_REPLAY_HEAD("") CBW_REPLAY_BIN_POW2 CBW_REPLAY_LOOP_CHUNKED
                  CBW_REPLAY_DIRECT(CBW_REPLAY_BIN_POW2) CBW_REPLAY_END
                  : CBW_REPLAY_OUT, [ox] "=&v"(ox), [oy] "=&v"(oy), CBW_CHUNKED_OUT
                  : CBW_REPLAY_IN, [oxs] "s"(oxs), [oys] "s"(oys), CBW_CHUNKED_IN
@@ -1089,15 +1136,15 @@ __device__ __forceinline__ uint32_t replay_stage(uint32_t enable, unsigned long 
   } else if (kPow2) {
     asm volatile("v_mov_b64 %[ox], %[oxs]\n\t"  // (in every lane: EXEC is all ones here, not behind the refill)
                  "v_mov_b64 %[oy], %[oys]\n\t"
-                 CBW_REPLAY_REFILL CBW_REPLAY_HEAD CBW_REPLAY_BIN_POW2 CBW_REPLAY_LOOP
+                 CBW_REPLAY_REFILL CBW_REPLAY_HEAD(CBW_REPLAY_BLOCKED_PRE) CBW_REPLAY_LOOP_BLOCKED(CBW_REPLAY_BIN_POW2)
                  CBW_REPLAY_DIRECT(CBW_REPLAY_BIN_POW2) CBW_REPLAY_END
-                 : CBW_REPLAY_OUT, [ox] "=&v"(ox), [oy] "=&v"(oy)
+                 : CBW_REPLAY_OUT, [ox] "=&v"(ox), [oy] "=&v"(oy), [blk] "=&s"(blk)
                  : CBW_REPLAY_IN, [oxs] "s"(oxs), [oys] "s"(oys)
-                 : "vcc", "scc", "memory");
+                 : "vcc", "scc", "memory", CBW_BLOCK_CLOBBERS);
   } else if (kChunked) {
     const double rx = ka->rcp_delta_real, ry = ka->rcp_delta_imag;
     const double kg = 0.5 - 0x1p-24;
-    asm volatile(CBW_REPLAY_REFILL CBW_REPLAY_HEAD CBW_REPLAY_BIN_DIV CBW_REPLAY_LOOP_CHUNKED
+    asm volatile(CBW_REPLAY_REFILL CBW_REPLAY_HEAD("") CBW_REPLAY_BIN_DIV CBW_REPLAY_LOOP_CHUNKED
                  CBW_REPLAY_DIRECT(CBW_REPLAY_BIN_DIV2) CBW_REPLAY_END
                  : CBW_REPLAY_OUT, [scp] "=&s"(scp), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3),
                    CBW_CHUNKED_OUT
@@ -1106,11 +1153,12 @@ __device__ __forceinline__ uint32_t replay_stage(uint32_t enable, unsigned long 
   } else {
     const double rx = ka->rcp_delta_real, ry = ka->rcp_delta_imag;
     const double kg = 0.5 - 0x1p-24;
-    asm volatile(CBW_REPLAY_REFILL CBW_REPLAY_HEAD CBW_REPLAY_BIN_DIV CBW_REPLAY_LOOP
+    asm volatile(CBW_REPLAY_REFILL CBW_REPLAY_HEAD(CBW_REPLAY_BLOCKED_PRE) CBW_REPLAY_LOOP_BLOCKED(CBW_REPLAY_BIN_DIV)
                  CBW_REPLAY_DIRECT(CBW_REPLAY_BIN_DIV2) CBW_REPLAY_END
-                 : CBW_REPLAY_OUT, [scp] "=&s"(scp), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3)
+                 : CBW_REPLAY_OUT, [scp] "=&s"(scp), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3),
+                   [blk] "=&s"(blk)
                  : CBW_REPLAY_IN, [ox] "s"(oxs), [oy] "s"(oys), [rx] "s"(rx), [ry] "s"(ry), [kg] "s"(kg)
-                 : "vcc", "scc", "memory");
+                 : "vcc", "scc", "memory", CBW_BLOCK_CLOBBERS);
   }
 #undef CBW_CHUNKED_OUT
 #undef CBW_CHUNKED_IN
@@ -1621,8 +1669,9 @@ draw_wide_kernel(DrawArgs a) {                            // scatter's four (64 
   } else if (lane_id() == 0) {  // the wave's segment as the two segments the scatter knows
     uint32_t *const wc = ea->bin.wave_count;
     const uint32_t cap = ea->bin.cap;
-    wc[2u * wave_id] = region_fill < cap ? region_fill : cap;
-    wc[2u * wave_id + 1u] = region_fill < cap ? 0u : region_fill - cap;
+    // (blocks of four slots: cap is a multiple of 8, so no block lies across the two)
+    wc[2u * wave_id] = (region_fill < cap ? region_fill : cap) | kStreamBlocked;
+    wc[2u * wave_id + 1u] = (region_fill < cap ? 0u : region_fill - cap) | kStreamBlocked;
   }
   {  // leave queues and orbit slots for the next launch (empty after a drain)
     unsigned long long *carry = ea->carry + (size_t) wave_id * (2u * kCarryWordsPerWave);

@@ -45,6 +45,14 @@ constexpr uint32_t kGroupReplicas = 4;              // level-A keys per group of
 constexpr uint32_t kChunkWords = 1024;
 constexpr uint32_t kRegionChunks = 32;              // 32 * 1024 = the 32768 entries of a region sort
 constexpr uint32_t kChunkedGroupsMax = 64;          // cursors: 64 x {next word, end of chunk} = 512 B of LDS per wave
+// One level, BLOCKED (draw_wide_kernel's stream): a segment is a row of blocks of four slots, 16 bytes on a 16-byte
+// boundary; a block holds up to four consecutive points of ONE lane's orbit, and a slot without a point holds
+// kStreamSentinel (row and col 65535: a pixel no canvas of at most 1024 tiles has).  Every block the draw kernel writes
+// holds a point; a reader takes any.  wave_count[w] counts SLOTS and carries kStreamBlocked; a segment without the
+// bit (draw_wave_kernel's, a planted one) is a row of words.  Counts stay below 2^31: a workspace holds fewer
+// than 2^32 entries in all (make_bin_layout), and a segment is at most half of it.
+constexpr uint32_t kStreamBlocked = 1u << 31;       // in wave_count[w], and in region_count[r] until the region is sorted
+constexpr uint32_t kStreamSentinel = 0xffffffffu;
 
 struct BinLayout {
   uint32_t enabled;     // 0: REPLAY adds to the histogram directly
@@ -72,13 +80,13 @@ struct BinLayout {
   uint32_t e_row_shift, e_col_mask, e_row_mask, e_chan_shift, e_chan_mask;
   uint32_t n_planes, tiles_y;
   unsigned long long plane_pixels;  // w * h: distance between the planes of the histogram
-  uint32_t *wave_count;           // [n_waves]            entries written by each wave
-  uint32_t *stream;               // [n_waves][cap]       packed row << 16 | col
+  uint32_t *wave_count;           // [n_waves]            entries written by each wave (| kStreamBlocked: slots, in blocks)
+  uint32_t *stream;               // [n_waves][cap]       packed row << 16 | col; blocked: or kStreamSentinel
   uint32_t *a_count;              // [n_groups*replicas][n_waves]  level A counts, then prefix over waves
   unsigned long long *a_base;     // [n_groups*replicas + 1]  level A exclusive prefix over keys
   uint32_t *grouped;              // [n_waves * cap]      the stream, grouped (two levels)
   unsigned long long *region_start;  // [max_regions]     regions of the (grouped) stream: first entry ...
-  uint32_t *region_count;         // [max_regions]        ... entries (<= 32768) ...
+  uint32_t *region_count;         // [max_regions]        ... entries (<= 32768; once sorted: the entries PLACED) ...
   uint32_t *region_group;         // [max_regions]        ... and group (0 with one level)
   uint32_t *owner_first;          // [max(n_waves, groups) + 1]  first region of every wave (one level) / group
   uint32_t *group_first;          // [n_groups]           a group's regions are consecutive: the first ...

@@ -1,8 +1,10 @@
 // scatter.hip -- the deferred, tile-binned scatter (see kernels.h, BinLayout).
 //
 // Input: the pixel stream the REPLAY stage of draw_wave_kernel wrote -- per wave a segment of packed
-// (row << 16 | col) words.  Output: the same increments added to the u64 histogram, with one
-// 64-byte memory-side request per 8 pixels of a tile slice instead of one per increment.
+// (row << 16 | col) words -- or, from draw_wide_kernel on a one-level canvas, of BLOCKS of four slots that hold such
+// a word or a sentinel (kernels.h, kStreamBlocked; the segment's wave_count says which).  Output: the same
+// increments added to the u64 histogram, with one 64-byte memory-side request per 8 pixels of a tile slice
+// instead of one per increment.
 //
 // One level (canvases of up to 1024 tiles of 128 x 128 pixels; C2 / C3: exactly 1024):
 //   regions     the stream is cut into regions of at most 32768 entries (a wave's segment = consecutive
@@ -34,6 +36,7 @@
 //
 // Increments commute, so the histogram is the same whatever the order; nothing here depends on timing
 // except the order of entries inside a run, which nothing reads.
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -87,8 +90,12 @@ __device__ __forceinline__ void lds_inc(uint32_t *p) {
   __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ds_add_u32
 }
 __device__ __forceinline__ uint32_t wave_count_of(const BinLayout &b, uint32_t w) {
-  const uint32_t n = b.wave_count[w];  // written by the draw kernel; never beyond the segment
+  const uint32_t n = b.wave_count[w] & ~kStreamBlocked;  // written by the draw kernel; never beyond the segment
   return n < b.cap ? n : b.cap;
+}
+// kStreamBlocked if segment w is a row of blocks (kernels.h; one level only), else 0
+__device__ __forceinline__ uint32_t wave_form_of(const BinLayout &b, uint32_t w) {
+  return (b.two_level || b.chunked) ? 0u : (b.wave_count[w] & kStreamBlocked);
 }
 
 // Exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total.
@@ -239,7 +246,8 @@ __global__ void __launch_bounds__(256) bin_fill_regions_kernel(BinLayout b) {
   owner_extent(b, lo, &begin, &entries, &piece);
   const unsigned long long offset = (unsigned long long) (r - b.owner_first[lo]) * piece;
   b.region_start[r] = begin + offset;
-  b.region_count[r] = (uint32_t) ((entries - offset) < piece ? (entries - offset) : piece);
+  // (a region of a blocked segment says so until it is sorted: bin_region_sort_kernel then leaves the entries it PLACED)
+  b.region_count[r] = (uint32_t) ((entries - offset) < piece ? (entries - offset) : piece) | wave_form_of(b, lo);
   b.region_group[r] = b.two_level ? lo : 0u;
 }
 
@@ -376,7 +384,10 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     push_run(0u);
     continue;
   }
-  uint32_t n = kChunked ? 0u : b.region_count[r];
+  // (a region of a BLOCKED segment -- kernels.h, kStreamBlocked; wave-uniform -- has slots that hold kStreamSentinel)
+  const uint32_t region_word = kChunked ? 0u : b.region_count[r];
+  const bool blocked = (region_word & kStreamBlocked) != 0u;
+  uint32_t n = region_word & ~kStreamBlocked;
   const unsigned long long start = kChunked ? (unsigned long long) r * kRegionEntries : b.region_start[r];
   const uint32_t *src = kChunked ? b.stream : (b.two_level ? b.grouped : b.stream) + start;
   const uint32_t k0 = b.region_group[r] << kGroupShift;
@@ -399,9 +410,9 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
 
   // A FULL region of a plain stream on a 16-byte boundary (ten of a wave's eleven at C3): no masks, no dummy key, and
   // every entry carries the LDS byte address of its tile's counter instead of the key, the counters count bytes of the
-  // image, so that the ranking pass is ONE vector instruction per entry (the address out of the packed word).  10
-  // vector instructions per entry all told instead of 36: alone on the GPU the sort is memory-bound either way, beside
-  // the two-waves-per-SIMD draw kernel its vector instructions are what it costs.
+  // image, so that the ranking pass is ONE vector instruction per entry (the address out of the packed word).  11
+  // vector instructions per entry all told (10 before the sentinel's clamp, below) instead of 36: alone on the GPU the
+  // sort is memory-bound either way, beside the two-waves-per-SIMD draw kernel its vector instructions are what it costs.
   const bool lean_region = kPlain && n != 0u && (kChunked || (start & 7ull) == 0ull);
   if (!kLean && skip_lean != 0u && lean_region) continue;  // (the lean instance's)
   if (kLean && !lean_region) {
@@ -421,6 +432,12 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     constexpr uint32_t kBatch = kChunked ? 2u : kLeanBatch;  // 16-byte loads in flight per thread (chunked: 64-bit addresses)
     // kMasked: a region that is not full (a wave's last): loads clamped to the region, the slots beyond it count into the
     // replica's dummy counter and are not placed -- two or three more instructions per entry, on a tenth of them
+    // A slot that holds kStreamSentinel (a blocked region) counts as ONE MORE KEY behind the tiles, kSentKey: its
+    // tile-to-be, (511 * tiles_x + 511), is clamped to it -- one v_min per entry, on every stream (a real tile lies below
+    // it; the host keeps canvases whose sentinel would not lie above it from this instance).  The sentinels are then
+    // ranked and placed like a tile's entries, as the image's LAST run, where nothing reads them: the region publishes
+    // the entries placed in front of it as its count, which is where the gather ends the last tile's run.
+    constexpr uint32_t kSentKey = kDummyKey + 1u;
     const auto sort_region = [&](auto masked) {
     constexpr bool kMasked = decltype(masked)::value;
     const uint32_t dummy_at = lds0 + (uint32_t) (((threadIdx.x % kCntReplicas) * kCntStride + kDummyKey) * sizeof(uint32_t));
@@ -434,7 +451,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
       return kChunked ? 4u * G >= n_chunks : (kMasked && G * 4u * kSortThreads >= n);
     };
     uint32_t e[kSortPerThread];
-    // 1. the entries, once: e = counter address << 16 | in-tile offset (7 vector instructions per entry); the counters
+    // 1. the entries, once: e = counter address << 16 | in-tile offset (8 vector instructions per entry); the counters
     //    count BYTES of the image (2 per entry), so that the ranking below gets an entry's place as an address
 #pragma unroll
     for (uint32_t part = 0; part < kSortPerThread / 4u / kBatch; ++part) {
@@ -460,7 +477,8 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q) {
           const uint32_t w = words[q];  // row << 16 | col; not chunked: col < 16384 (the host's condition for the instance)
-          const uint32_t key = __umul24(w >> (16 + kTileShift), tiles_x) + __builtin_amdgcn_ubfe(w, kTileShift, 16 - kTileShift);
+          uint32_t key = __umul24(w >> (16 + kTileShift), tiles_x) + __builtin_amdgcn_ubfe(w, kTileShift, 16 - kTileShift);
+          if (!kChunked) key = key < kSentKey ? key : kSentKey;
           uint32_t addr = cnt_at + (key << 2);  // < 2^16: at most 8 replicas of 272 or 2 of 1040 counters
           if (kChunked ? !(4u * in_chunk + q < words_g[j])
                        : (kMasked && !((part * kBatch + j) * 4u * kSortThreads + q + slot0 < n))) {
@@ -490,6 +508,15 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
       uint32_t first = sort_exclusive_scan(sum, wave_totals);
       __syncthreads();
       push_run(first >> 1);  // (a thread beyond the group's tiles: the region's entries, which nobody reads)
+      if (!kChunked && blocked && threadIdx.x == kSortThreads - 1u) {  // the sentinels' run: behind the last tile's
+        uint32_t at = first + sum;
+        b.region_count[r] = at >> 1;  // the entries placed (every region is sorted once)
+        for (uint32_t k = 0; k < kCntReplicas; ++k) {
+          const uint32_t c_sent = lds[k * kCntStride + kSentKey];
+          lds[k * kCntStride + kSentKey] = image_at + at;
+          at += c_sent;
+        }
+      }
 #pragma unroll
       for (uint32_t k = 0; k < kCntReplicas; ++k) {
         if (has_key) lds[k * kCntStride + threadIdx.x] = image_at + first;
@@ -599,10 +626,11 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
         const uint32_t i = (k * kSortThreads + threadIdx.x) * 4u;
         const uint32_t w0 = sort_word<kPlain>(v[j].x, k0, b), w1 = sort_word<kPlain>(v[j].y, k0, b);
         const uint32_t w2 = sort_word<kPlain>(v[j].z, k0, b), w3 = sort_word<kPlain>(v[j].w, k0, b);
-        e[4 * k + 0] = (i >= head && i < lim) ? w0 : ~0u;
-        e[4 * k + 1] = (i + 1u >= head && i + 1u < lim) ? w1 : ~0u;
-        e[4 * k + 2] = (i + 2u >= head && i + 2u < lim) ? w2 : ~0u;
-        e[4 * k + 3] = (i + 3u < lim) ? w3 : ~0u;
+        // (a blocked region -- one level: head == 0 -- has slots that hold the sentinel: beyond the region like the rest)
+        e[4 * k + 0] = (i >= head && i < lim && !(blocked && v[j].x == kStreamSentinel)) ? w0 : ~0u;
+        e[4 * k + 1] = (i + 1u >= head && i + 1u < lim && !(blocked && v[j].y == kStreamSentinel)) ? w1 : ~0u;
+        e[4 * k + 2] = (i + 2u >= head && i + 2u < lim && !(blocked && v[j].z == kStreamSentinel)) ? w2 : ~0u;
+        e[4 * k + 3] = (i + 3u < lim && !(blocked && v[j].w == kStreamSentinel)) ? w3 : ~0u;
       }
 #pragma unroll
       for (uint32_t k = half * (kSortPerThread / 2u); k < (half + 1u) * (kSortPerThread / 2u); ++k) {
@@ -625,6 +653,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) bin_region_sort_kernel(BinLay
     uint32_t first = sort_exclusive_scan(sum, wave_totals);
     __syncthreads();  // every count has been read
     if (threadIdx.x < nk) b.run_start[(size_t) threadIdx.x * b.max_regions + r] = (uint16_t) first;
+    if (blocked && threadIdx.x == kSortThreads - 1u) b.region_count[r] = first + sum;  // the entries placed
 #pragma unroll
     for (uint32_t k = 0; k < kCntReplicas; ++k) {
       if (has_key) lds[k * kCntStride + threadIdx.x] = first;
@@ -850,7 +879,7 @@ __global__ void __launch_bounds__(64) chunk_count_kernel(BinLayout b) {
   const uint32_t w = blockIdx.x;
   cnt[threadIdx.x] = 0u;
   __syncthreads();
-  const uint32_t n = b.wave_count[w] < b.chunks_per_wave ? b.wave_count[w] : b.chunks_per_wave;
+  const uint32_t n = wave_count_of(b, w) < b.chunks_per_wave ? wave_count_of(b, w) : b.chunks_per_wave;
   const uint32_t *desc = b.chunk_desc + (size_t) w * b.chunks_per_wave;
   for (uint32_t j = threadIdx.x; j < n; j += 64u) {
     const uint32_t g = desc[j] >> 16;
@@ -865,7 +894,7 @@ __global__ void __launch_bounds__(64) chunk_list_kernel(BinLayout b) {
   const uint32_t w = blockIdx.x;
   cnt[threadIdx.x] = 0u;
   __syncthreads();
-  const uint32_t n = b.wave_count[w] < b.chunks_per_wave ? b.wave_count[w] : b.chunks_per_wave;
+  const uint32_t n = wave_count_of(b, w) < b.chunks_per_wave ? wave_count_of(b, w) : b.chunks_per_wave;
   const uint32_t *desc = b.chunk_desc + (size_t) w * b.chunks_per_wave;
   for (uint32_t j = threadIdx.x; j < n; j += 64u) {
     const uint32_t d = desc[j], g = d >> 16;
@@ -1153,7 +1182,9 @@ BinLayout make_bin_layout(void *workspace, size_t bytes, int w, int h, uint32_t 
   unsigned long long cap = (p_end - p) / (per_entry * (size_t) n_waves);
   const unsigned long long cap_limit = 0xffffffffull / n_waves;  // all entries together < 2^32
   if (cap > cap_limit) cap = cap_limit;
+  if (cap >= kStreamBlocked) cap = kStreamBlocked - 1u;  // wave_count[w] <= cap leaves its top bit to the stream's form
   cap = cap / unit * unit;
+  assert(cap < kStreamBlocked);
   const auto fits = [&](unsigned long long c) {
     const uint32_t mr = max_regions_for(s, n_waves, c * n_waves);
     return p + fixed_bytes(s, n_waves, mr) + (size_t) c * n_waves * per_entry + 1024 <= p_end;
@@ -1260,8 +1291,10 @@ hipError_t launch_binned_scatter(const BinLayout &b, unsigned long long *hist, i
   if (b.chunked) {
     se = plain ? launch_sort(bin_region_sort_kernel<true, false, true, true>, SortLds<false>::kBytes, kRunBatch)
                : launch_sort(bin_region_sort_kernel<false, false, true>, SortLds<false>::kBytes);
-  } else if (plain && !b.two_level && b.tiles_x <= 128u) {  // (columns below 16384: the lean instance's word)
-    // the full regions first (lean instance: 10 vector instructions per entry), then the waves' last, partial ones
+  } else if (plain && !b.two_level && b.tiles_x <= 128u && (few || b.tiles_x >= 2u)) {
+    // (columns below 16384: the lean instance's word; and the sentinel of a blocked stream beyond its counters' keys,
+    // 511 * tiles_x + 511 > 1025 -- one tile column and more than 256 tile rows: the general instance's)
+    // the full regions first (lean instance: 11 vector instructions per entry), then the waves' last, partial ones
     se = few ? launch_sort(bin_region_sort_kernel<true, true, false, true>, SortLds<true>::kBytes, kRunBatch)
              : launch_sort(bin_region_sort_kernel<true, false, false, true>, SortLds<false>::kBytes, kRunBatch);
     // (a one-level plain stream: every region starts on a 16-byte boundary of its wave's segment -- cap is a multiple
