@@ -717,31 +717,35 @@ class Renderer:
                 "cb_renderer_create_channels",
             )
 
+    def _set_cells(self, which, level, probe_passes, dilate, kernel_variant):
+        """cb_renderer_set_<which>, then cb_renderer_<which>_cells: the focused and the aimed renderer's setter."""
+        name = "cb_renderer_set_" + which
+        _check(getattr(lib, name)(self._h, int(level), int(probe_passes), int(dilate), kernel_variant), name)
+        return self._cells(which)
+
+    def _cells(self, which):
+        name = "cb_renderer_%s_cells" % which
+        n, total = C.c_uint32(), C.c_uint32()
+        _check(getattr(lib, name)(self._h, C.byref(n), C.byref(total)), name)
+        return int(n.value), int(total.value)
+
     def set_focus(self, level=8, probe_passes=64, dilate=1, kernel_variant=CB_KERNEL_DEFAULT):
         """Make this a focused renderer (cb_renderer_set_focus), before the first pass -> (cells listed, cells of the
         grid).  Raises CudabrotError with code CB_ERROR_FOCUS_EMPTY when the probe marks no cell."""
-        _check(lib.cb_renderer_set_focus(self._h, int(level), int(probe_passes), int(dilate), kernel_variant),
-               "cb_renderer_set_focus")
-        return self.focus_cells()
+        return self._set_cells("focus", level, probe_passes, dilate, kernel_variant)
 
     def focus_cells(self):
         """(cells listed, cells of the grid) of a focused renderer; (0, 0) without focus."""
-        n, total = C.c_uint32(), C.c_uint32()
-        _check(lib.cb_renderer_focus_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_focus_cells")
-        return int(n.value), int(total.value)
+        return self._cells("focus")
 
     def set_aim(self, level=8, probe_passes=64, dilate=1, kernel_variant=CB_KERNEL_DEFAULT):
         """Make this an aimed renderer (cb_renderer_set_aim), before the first pass -> (cells listed, cells of the grid).
         Raises CudabrotError with code CB_ERROR_AIM_EMPTY when the probe marks no cell."""
-        _check(lib.cb_renderer_set_aim(self._h, int(level), int(probe_passes), int(dilate), kernel_variant),
-               "cb_renderer_set_aim")
-        return self.aim_cells()
+        return self._set_cells("aim", level, probe_passes, dilate, kernel_variant)
 
     def aim_cells(self):
         """(cells listed, cells of the grid) of an aimed renderer; (0, 0) for any other."""
-        n, total = C.c_uint32(), C.c_uint32()
-        _check(lib.cb_renderer_aim_cells(self._h, C.byref(n), C.byref(total)), "cb_renderer_aim_cells")
-        return int(n.value), int(total.value)
+        return self._cells("aim")
 
     def set_projection(self, projection):
         """Make this a projected renderer (cb_renderer_set_projection), before the first pass."""

@@ -283,6 +283,16 @@ struct Launch {
   void *stream;
 };
 
+// The cell list of a focused or an aimed render (level 0, no cells: the uniform source), and the step bits of the kernel
+// variant it was probed with -- the Burning Ship's flag alone for a focus, kStepBits for an aim; a renderer's launch with
+// other bits is refused.  The renderer that keeps one owns d_cells; an entry point only lends its caller's.
+struct CellList {
+  int level;
+  uint32_t *d_cells;
+  uint32_t n_cells;
+  int step_bits;
+};
+
 // What a plotted launch adds; a renderer keeps one as what it is (cb_renderer::what), and then owns the device memory.
 struct Plotted {
   Kind kind;
@@ -297,12 +307,7 @@ struct Plotted {
   int n_frames;
   double phoenix_p[2];  // kPhoenix
   double period_eps;    // kPeriodPalette
-  // kAimed, kAimedBounded: the grid's level and the cell list (level 0, no cells: the uniform source), and the step bits of
-  // the kernel variant the list was probed with -- a launch with other bits is refused
-  int aim_level;
-  const uint32_t *d_aim_cells;
-  uint32_t aim_n_cells;
-  int aim_step_bits;
+  CellList cells;       // kAimed, kAimedBounded; of a renderer: kFocus too
 };
 
 }  // namespace
@@ -339,11 +344,6 @@ struct cb_renderer {
   // what the generators were made from (cb_renderer_set_focus probes on fresh ones) and whether a pass was rendered
   uint64_t seed, first_subsequence;
   bool rendered;
-  // focused render (what.kind == kFocus): the grid's level (0: none), the cell list and the probe's step
-  int focus_level;
-  uint32_t *d_focus_cells;
-  uint32_t focus_n_cells;
-  bool focus_ship;
   // What the renderer is, and for a plotted kind what its launches add: the setters (`admits`) are the only writers.  d_hist
   // has kind_row(what).planes planes, or n_channels.
   Plotted what;
@@ -545,14 +545,66 @@ int plot_args(const Launch &l, const double projection[8], const double julia_c[
 // The step of a plotted launch in its kernel variant: a formula, a degree or the Burning Ship.
 constexpr int kStepBits = CB_KERNEL_FORMULA_MASK | CB_KERNEL_POWER_MASK | CB_KERNEL_FLAG_BURNING_SHIP;
 
-// The grid of an aimed launch (level 0: none).
-void aim_grid(cb::AimArgs &aa, int level) {
-  aa.level = level;
-  if (level) {
-    aa.cell_side = ldexp(1.0, -level);
-    aa.cell_scale = ldexp(1.0, -(level + 2));
-    aa.cells_per_unit = ldexp(1.0, level);
+// ---- the cell source of the focused and the aimed render (draw_focus.hip, draw_aim.hip) ----
+
+// A probe's level, and a draw's list: level 0 and no cells is the uniform source (the tests' un-listed render through the
+// same kernel); else a level in range and a list with entries.
+bool cell_level_ok(int level) { return level >= CB_FOCUS_MIN_LEVEL && level <= CB_FOCUS_MAX_LEVEL; }
+bool cell_list_ok(int level, const uint32_t *d_cells, uint32_t n_cells) {
+  const bool uniform = d_cells == nullptr && n_cells == 0 && level == 0;
+  return uniform || (cell_level_ok(level) && d_cells && n_cells > 0);
+}
+
+// Probe to list, what cb_renderer_set_focus and cb_renderer_set_aim do once the renderer admits the kind and their own
+// arguments have passed: probe_passes passes on generators made afresh from the renderer's seed, in launches of at most
+// kRendererPassesPerLaunch -- probe(d_states, samples_per_thread, d_mask) issues one on r->stream --, the mask dilated into
+// the list, the list on the device.  0: r->what.cells holds level, list and count (kind and step bits are the caller's).
+// Else, `empty` for a mask without a bit included, the renderer is what it was and nothing stays allocated.
+template <class Probe>
+int probe_cells(cb_renderer *r, int level, uint32_t probe_passes, int dilate, Probe probe, int empty) {
+  CB_TRY(hipSetDevice(r->device));
+  const size_t mask_bytes = cb_focus_mask_bytes(level);
+  void *d_states = nullptr;
+  uint32_t *d_mask = nullptr, *d_cells = nullptr;
+  std::vector<uint32_t> mask(mask_bytes / sizeof(uint32_t)), cells;
+  uint32_t n_cells = 0;
+  int rc = (int) hipMalloc(&d_states, cb_rng_state_bytes(r->n_threads));
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_mask), mask_bytes);
+  if (!rc) rc = (int) hipMemsetAsync(d_mask, 0, mask_bytes, r->stream);
+  if (!rc) rc = cb_initialize_rng(r->seed, r->first_subsequence, r->n_threads, d_states, r->stream);
+  for (uint32_t left = probe_passes; !rc && left > 0;) {
+    const uint32_t now = left < kRendererPassesPerLaunch ? left : kRendererPassesPerLaunch;
+    rc = probe(d_states, now * CB_SAMPLES_PER_THREAD, d_mask);
+    left -= now;
   }
+  if (!rc) rc = (int) hipMemcpyAsync(mask.data(), d_mask, mask_bytes, hipMemcpyDeviceToHost, r->stream);
+  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
+  if (!rc) rc = cb_focus_cells(level, mask.data(), dilate, nullptr, &n_cells);
+  if (!rc && n_cells == 0) rc = empty;
+  if (!rc) {
+    cells.resize(n_cells);
+    rc = cb_focus_cells(level, mask.data(), dilate, cells.data(), &n_cells);
+  }
+  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_cells), (size_t) n_cells * sizeof(uint32_t));
+  if (!rc) rc = (int) hipMemcpy(d_cells, cells.data(), (size_t) n_cells * sizeof(uint32_t), hipMemcpyHostToDevice);
+  (void) hipFree(d_states);
+  (void) hipFree(d_mask);
+  if (rc) {
+    (void) hipFree(d_cells);
+    return rc;
+  }
+  r->what.cells.level = level;
+  r->what.cells.d_cells = d_cells;
+  r->what.cells.n_cells = n_cells;
+  return 0;
+}
+
+// The listed cells and the grid's n * n of a renderer that keeps a list (`listed`), 0 and 0 of one that does not.
+int renderer_cells(const cb_renderer *r, bool listed, uint32_t *n_cells, uint32_t *n_total) {
+  const uint32_t n = listed ? 4u << r->what.cells.level : 0u;
+  if (n_cells) *n_cells = listed ? r->what.cells.n_cells : 0u;
+  if (n_total) *n_total = n * n;
+  return 0;
 }
 
 // One plotted launch: what the ten cb_draw_buddhabrot_{projected .. periods, aimed} entry points and a plotted renderer
@@ -637,14 +689,14 @@ int draw_plotted(const Launch &l, const Plotted &p, int *interior_level) {
     }
     case kAimed:
     case kAimedBounded: {  // the projected or the bounded launch from the cell list; the map by plot_args' rule, above
-      if ((l.kernel_variant & kStepBits) != p.aim_step_bits) return (int) hipErrorInvalidValue;  // not the probe's step
+      if ((l.kernel_variant & kStepBits) != p.cells.step_bits) return (int) hipErrorInvalidValue;  // not the probe's step
       cb::AimArgs aa;
       memset(&aa, 0, sizeof(aa));
       aa.p = pa;
       aa.bounded = p.kind == kAimedBounded ? 1 : 0;
-      aa.cells = p.d_aim_cells;
-      aa.n_cells = p.aim_n_cells;
-      aim_grid(aa, p.aim_level);
+      aa.cells = p.cells.d_cells;
+      aa.n_cells = p.cells.n_cells;
+      cb::set_grid_level(aa, p.cells.level);
       report(30);
       e = cb::launch_draw_aim(aa, lockstep, stream);
       break;
@@ -660,10 +712,11 @@ int enqueue_launch(cb_renderer *r, uint32_t passes, int kernel_variant) {
   if (r->what.kind == kFocus) {  // draw_focus.hip: direct atomics, no deferred scatter, no carry, no interior map
     r->interior_level = 0;
     if (passes == 0) return 0;
-    if (((kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0) != r->focus_ship) return (int) hipErrorInvalidValue;
+    const CellList &c = r->what.cells;
+    if ((kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != c.step_bits) return (int) hipErrorInvalidValue;
     return cb_draw_buddhabrot_focus(&r->dims, r->d_hist, &r->iterations, r->d_states, r->n_threads,
-                                    passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, r->focus_level,
-                                    r->d_focus_cells, r->focus_n_cells, r->stream);
+                                    passes * CB_SAMPLES_PER_THREAD, r->d_counters, kernel_variant, c.level, c.d_cells,
+                                    c.n_cells, r->stream);
   }
   if (is_plotted(r->what.kind)) {  // what the setters took is checked
     if (passes == 0) return 0;
@@ -1130,13 +1183,9 @@ bool focus_variant_ok(int kernel_variant) {
   return base_variant == CB_KERNEL_DEFAULT || base_variant == CB_KERNEL_SIMPLE;
 }
 
-int launch_focus(cb::FocusArgs &f, int kernel_variant, hipStream_t stream) {
+int launch_focus(cb::FocusArgs &f, int level, int kernel_variant, hipStream_t stream) {
   f.d.burning_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0 ? 1 : 0;
-  if (f.level) {
-    f.cell_side = ldexp(1.0, -f.level);
-    f.cell_scale = ldexp(1.0, -(f.level + 2));
-    f.cells_per_unit = ldexp(1.0, f.level);
-  }
+  cb::set_grid_level(f.g, level);
   const bool lockstep = (kernel_variant & ~CB_KERNEL_FLAG_BURNING_SHIP) == CB_KERNEL_SIMPLE;
   g_last_draw_kernel.store(lockstep ? 7 : 6, std::memory_order_relaxed);
   g_interior_level.store(0, std::memory_order_relaxed);
@@ -1149,15 +1198,12 @@ int cb_focus_probe(const cb_fractal_dimensions *dims, const cb_iteration_control
                    uint32_t n_threads, uint32_t samples_per_thread, int level, uint32_t *d_mask,
                    cb_counters *d_counters, int kernel_variant, void *stream) {
   if (!dims || !iterations || !d_states || !d_mask || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !focus_variant_ok(kernel_variant)) {
-    return (int) hipErrorInvalidValue;
-  }
+  if (!cell_level_ok(level) || !focus_variant_ok(kernel_variant)) return (int) hipErrorInvalidValue;
   cb::FocusArgs f;
   memset(&f, 0, sizeof(f));
   f.d = make_args(dims, iterations, nullptr, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  f.level = level;
-  f.mask = d_mask;
-  return launch_focus(f, kernel_variant, reinterpret_cast<hipStream_t>(stream));
+  f.g.mask = d_mask;
+  return launch_focus(f, level, kernel_variant, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist,
@@ -1165,71 +1211,33 @@ int cb_draw_buddhabrot_focus(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              uint32_t samples_per_thread, cb_counters *d_counters, int kernel_variant, int level,
                              const uint32_t *d_cells, uint32_t n_cells, void *stream) {
   if (!dims || !iterations || !d_hist || !d_states || dims->w <= 0 || dims->h <= 0) return (int) hipErrorInvalidValue;
-  if (!focus_variant_ok(kernel_variant)) return (int) hipErrorInvalidValue;
-  const bool uniform = d_cells == nullptr && n_cells == 0 && level == 0;  // the tests' normal render through this kernel
-  if (!uniform && (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !d_cells || n_cells == 0)) {
-    return (int) hipErrorInvalidValue;
-  }
+  if (!focus_variant_ok(kernel_variant) || !cell_list_ok(level, d_cells, n_cells)) return (int) hipErrorInvalidValue;
   cb::FocusArgs f;
   memset(&f, 0, sizeof(f));
   f.d = make_args(dims, iterations, d_hist, d_states, n_threads, samples_per_thread, d_counters, nullptr, 0, nullptr);
-  f.level = level;
-  f.cells = d_cells;
-  f.n_cells = n_cells;
-  return launch_focus(f, kernel_variant, reinterpret_cast<hipStream_t>(stream));
+  f.g.cells = d_cells;
+  f.g.n_cells = n_cells;
+  return launch_focus(f, level, kernel_variant, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cb_renderer_set_focus(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
-  if (!admits(r, kFocus) || probe_passes == 0 || dilate < 0 || level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL ||
-      !focus_variant_ok(kernel_variant)) {
+  if (!admits(r, kFocus) || probe_passes == 0 || dilate < 0 || !cell_level_ok(level) || !focus_variant_ok(kernel_variant)) {
     return (int) hipErrorInvalidValue;
   }
-  CB_TRY(hipSetDevice(r->device));
-  const size_t mask_bytes = cb_focus_mask_bytes(level);
-  void *d_states = nullptr;
-  uint32_t *d_mask = nullptr, *d_cells = nullptr;
-  std::vector<uint32_t> mask(mask_bytes / sizeof(uint32_t)), cells;
-  uint32_t n_cells = 0;
-  int rc = (int) hipMalloc(&d_states, cb_rng_state_bytes(r->n_threads));
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_mask), mask_bytes);
-  if (!rc) rc = (int) hipMemsetAsync(d_mask, 0, mask_bytes, r->stream);
-  if (!rc) rc = cb_initialize_rng(r->seed, r->first_subsequence, r->n_threads, d_states, r->stream);
-  for (uint32_t left = probe_passes; !rc && left > 0;) {
-    const uint32_t now = left < kRendererPassesPerLaunch ? left : kRendererPassesPerLaunch;
-    rc = cb_focus_probe(&r->dims, &r->iterations, d_states, r->n_threads, now * CB_SAMPLES_PER_THREAD, level, d_mask,
-                        nullptr, kernel_variant, r->stream);
-    left -= now;
-  }
-  if (!rc) rc = (int) hipMemcpyAsync(mask.data(), d_mask, mask_bytes, hipMemcpyDeviceToHost, r->stream);
-  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
-  if (!rc) rc = cb_focus_cells(level, mask.data(), dilate, nullptr, &n_cells);
-  if (!rc && n_cells == 0) rc = CB_ERROR_FOCUS_EMPTY;
-  if (!rc) {
-    cells.resize(n_cells);
-    rc = cb_focus_cells(level, mask.data(), dilate, cells.data(), &n_cells);
-  }
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_cells), (size_t) n_cells * sizeof(uint32_t));
-  if (!rc) rc = (int) hipMemcpy(d_cells, cells.data(), (size_t) n_cells * sizeof(uint32_t), hipMemcpyHostToDevice);
-  (void) hipFree(d_states);
-  (void) hipFree(d_mask);
-  if (rc) {
-    (void) hipFree(d_cells);
-    return rc;
-  }
+  const auto probe = [=](void *d_states, uint32_t samples_per_thread, uint32_t *d_mask) {
+    return cb_focus_probe(&r->dims, &r->iterations, d_states, r->n_threads, samples_per_thread, level, d_mask, nullptr,
+                          kernel_variant, r->stream);
+  };
+  const int rc = probe_cells(r, level, probe_passes, dilate, probe, CB_ERROR_FOCUS_EMPTY);
+  if (rc) return rc;
   r->what.kind = kFocus;
-  r->focus_level = level;
-  r->d_focus_cells = d_cells;
-  r->focus_n_cells = n_cells;
-  r->focus_ship = (kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP) != 0;
+  r->what.cells.step_bits = kernel_variant & CB_KERNEL_FLAG_BURNING_SHIP;
   return 0;
 }
 
 int cb_renderer_focus_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total) {
   if (!r) return (int) hipErrorInvalidValue;
-  const uint32_t n = r->focus_level ? 4u << r->focus_level : 0u;
-  if (n_cells) *n_cells = r->focus_level ? r->focus_n_cells : 0u;
-  if (n_total) *n_total = n * n;
-  return 0;
+  return renderer_cells(r, r->what.kind == kFocus, n_cells, n_total);
 }
 
 // ---- the plotted renders (include/cudabrot_amd.h, "Projected render" .. "Phoenix render") ----------------------------
@@ -1489,8 +1497,7 @@ int cb_aim_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *
   const Launch l = {dims, nullptr, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
   Plotted p;
   if (!dims || !iterations || !d_states || !d_mask || dims->w <= 0 || dims->h <= 0 ||
-      !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c) || level < CB_FOCUS_MIN_LEVEL ||
-      level > CB_FOCUS_MAX_LEVEL) {
+      !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c) || !cell_level_ok(level)) {
     return (int) hipErrorInvalidValue;
   }
   cb::AimArgs aa;
@@ -1500,7 +1507,7 @@ int cb_aim_probe(const cb_fractal_dimensions *dims, const cb_iteration_control *
   if (rc) return rc;
   aa.bounded = bounded ? 1 : 0;
   aa.mask = d_mask;
-  aim_grid(aa, level);
+  cb::set_grid_level(aa, level);
   const hipError_t e = cb::launch_draw_aim(aa, lockstep, reinterpret_cast<hipStream_t>(stream));
   if (e == hipSuccess) g_last_draw_kernel.store(lockstep ? 31 : 30, std::memory_order_relaxed);  // a refusal names nothing
   return (int) e;
@@ -1512,77 +1519,37 @@ int cb_draw_buddhabrot_aimed(const cb_fractal_dimensions *dims, cb_pixel *d_hist
                              int level, const uint32_t *d_cells, uint32_t n_cells, void *stream) {
   const Launch l = {dims, d_hist, iterations, d_states, n_threads, samples_per_thread, d_counters, kernel_variant, stream};
   Plotted p;
-  if (!launch_ok(l) || !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c)) {
+  if (!launch_ok(l) || !plotted_source(&p, bounded ? kAimedBounded : kAimed, projection, julia_c) ||
+      !cell_list_ok(level, d_cells, n_cells)) {
     return (int) hipErrorInvalidValue;
   }
-  const bool uniform = d_cells == nullptr && n_cells == 0 && level == 0;  // the un-aimed render through this kernel
-  if (!uniform && (level < CB_FOCUS_MIN_LEVEL || level > CB_FOCUS_MAX_LEVEL || !d_cells || n_cells == 0)) {
-    return (int) hipErrorInvalidValue;
-  }
-  p.aim_level = level;
-  p.d_aim_cells = d_cells;
-  p.aim_n_cells = n_cells;
-  p.aim_step_bits = kernel_variant & kStepBits;
+  p.cells = {level, const_cast<uint32_t *>(d_cells), n_cells, kernel_variant & kStepBits};  // lent: a launch only reads it
   return draw_plotted(l, p, nullptr);
 }
 
 int cb_renderer_set_aim(cb_renderer *r, int level, uint32_t probe_passes, int dilate, int kernel_variant) {
   if (!r) return (int) hipErrorInvalidValue;
   const bool bounded = r->what.kind == kBounded;
-  if (!admits(r, bounded ? kAimedBounded : kAimed) || probe_passes == 0 || dilate < 0 || level < CB_FOCUS_MIN_LEVEL ||
-      level > CB_FOCUS_MAX_LEVEL) {
+  if (!admits(r, bounded ? kAimedBounded : kAimed) || probe_passes == 0 || dilate < 0 || !cell_level_ok(level)) {
     return (int) hipErrorInvalidValue;
   }
   const double *projection = r->what.kind == kNormal ? kIdentityProjection : r->what.projection;  // alone: the identity
   const double *julia_c = r->what.kind != kNormal && r->what.julia ? r->what.julia_c : nullptr;
-  CB_TRY(hipSetDevice(r->device));
-  const size_t mask_bytes = cb_focus_mask_bytes(level);
-  void *d_states = nullptr;
-  uint32_t *d_mask = nullptr, *d_cells = nullptr;
-  std::vector<uint32_t> mask(mask_bytes / sizeof(uint32_t)), cells;
-  uint32_t n_cells = 0;
-  int rc = (int) hipMalloc(&d_states, cb_rng_state_bytes(r->n_threads));
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_mask), mask_bytes);
-  if (!rc) rc = (int) hipMemsetAsync(d_mask, 0, mask_bytes, r->stream);
-  if (!rc) rc = cb_initialize_rng(r->seed, r->first_subsequence, r->n_threads, d_states, r->stream);
-  for (uint32_t left = probe_passes; !rc && left > 0;) {
-    const uint32_t now = left < kRendererPassesPerLaunch ? left : kRendererPassesPerLaunch;
-    rc = cb_aim_probe(&r->dims, &r->iterations, projection, julia_c, bounded ? 1 : 0, d_states, r->n_threads,
-                      now * CB_SAMPLES_PER_THREAD, level, d_mask, nullptr, kernel_variant, r->stream);
-    left -= now;
-  }
-  if (!rc) rc = (int) hipMemcpyAsync(mask.data(), d_mask, mask_bytes, hipMemcpyDeviceToHost, r->stream);
-  if (!rc) rc = (int) hipStreamSynchronize(r->stream);
-  if (!rc) rc = cb_focus_cells(level, mask.data(), dilate, nullptr, &n_cells);
-  if (!rc && n_cells == 0) rc = CB_ERROR_AIM_EMPTY;
-  if (!rc) {
-    cells.resize(n_cells);
-    rc = cb_focus_cells(level, mask.data(), dilate, cells.data(), &n_cells);
-  }
-  if (!rc) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_cells), (size_t) n_cells * sizeof(uint32_t));
-  if (!rc) rc = (int) hipMemcpy(d_cells, cells.data(), (size_t) n_cells * sizeof(uint32_t), hipMemcpyHostToDevice);
-  (void) hipFree(d_states);
-  (void) hipFree(d_mask);
-  if (rc) {
-    (void) hipFree(d_cells);
-    return rc;
-  }
+  const auto probe = [=](void *d_states, uint32_t samples_per_thread, uint32_t *d_mask) {
+    return cb_aim_probe(&r->dims, &r->iterations, projection, julia_c, bounded ? 1 : 0, d_states, r->n_threads,
+                        samples_per_thread, level, d_mask, nullptr, kernel_variant, r->stream);
+  };
+  const int rc = probe_cells(r, level, probe_passes, dilate, probe, CB_ERROR_AIM_EMPTY);
+  if (rc) return rc;
   if (r->what.kind == kNormal) memcpy(r->what.projection, kIdentityProjection, sizeof(r->what.projection));
   r->what.kind = bounded ? kAimedBounded : kAimed;
-  r->what.aim_level = level;
-  r->what.d_aim_cells = d_cells;
-  r->what.aim_n_cells = n_cells;
-  r->what.aim_step_bits = kernel_variant & kStepBits;
+  r->what.cells.step_bits = kernel_variant & kStepBits;
   return 0;
 }
 
 int cb_renderer_aim_cells(const cb_renderer *r, uint32_t *n_cells, uint32_t *n_total) {
   if (!r) return (int) hipErrorInvalidValue;
-  const bool aimed = r->what.kind == kAimed || r->what.kind == kAimedBounded;
-  const uint32_t n = aimed ? 4u << r->what.aim_level : 0u;
-  if (n_cells) *n_cells = aimed ? r->what.aim_n_cells : 0u;
-  if (n_total) *n_total = n * n;
-  return 0;
+  return renderer_cells(r, r->what.kind == kAimed || r->what.kind == kAimedBounded, n_cells, n_total);
 }
 
 int cb_draw_buddhabrot_periods(const cb_fractal_dimensions *dims, cb_pixel *d_hist, const cb_iteration_control *iterations,
@@ -1954,8 +1921,7 @@ void cb_renderer_destroy(cb_renderer *r) {
   (void) hipFree(r->d_states);
   (void) hipFree(r->d_counters);
   (void) hipFree(r->d_carry);
-  (void) hipFree(r->d_focus_cells);
-  (void) hipFree(const_cast<uint32_t *>(r->what.d_aim_cells));
+  (void) hipFree(r->what.cells.d_cells);
   (void) hipFree(const_cast<uint32_t *>(r->what.d_lut));
   (void) hipFree(const_cast<double *>(r->what.d_frames));
   delete r->frames;

@@ -224,6 +224,33 @@ const char *const kOk = nullptr;
 #define CB_TEXT_OF_(x) #x
 #define CB_TEXT_OF(x) CB_TEXT_OF_(x)  // a macro's value as text, for a message
 
+// The four rows of a cell-sourced render, --focus and --aim: FLAG, FLAG-level L, FLAG-probe PASSES, FLAG-dilate D into the
+// CellFlags `member` of Settings, `word` what the messages call it.  Each value flag turns the render on.
+#define CB_CELL_FLAGS(flag, word, member)                                                                     \
+  {flag, Value::kNone, nullptr, false,                                                                        \
+   [](Settings &s, long, double, const char *) { s.member.on = true; return kOk; }},                          \
+  {flag "-level", Value::kInt, nullptr, false,                                                                \
+   [](Settings &s, long i, double, const char *) {                                                            \
+     s.member.on = true;                                                                                      \
+     if (i < CB_FOCUS_MIN_LEVEL || i > CB_FOCUS_MAX_LEVEL) return "Invalid " word " level (want 4 to 10)";    \
+     s.member.level = (int) i;                                                                                \
+     return kOk;                                                                                              \
+   }},                                                                                                        \
+  {flag "-probe", Value::kInt, nullptr, false,                                                                \
+   [](Settings &s, long i, double, const char *) {                                                            \
+     s.member.on = true;                                                                                      \
+     if (i < 1) return "Invalid " word " probe (want at least 1 pass)";                                       \
+     s.member.probe = i;                                                                                      \
+     return kOk;                                                                                              \
+   }},                                                                                                        \
+  {flag "-dilate", Value::kInt, nullptr, false,                                                               \
+   [](Settings &s, long i, double, const char *) {                                                            \
+     s.member.on = true;                                                                                      \
+     if (i < 0) return "Invalid " word " dilation (want 0 or more cells)";                                    \
+     s.member.dilate = (int) i;                                                                               \
+     return kOk;                                                                                              \
+   }},
+
 const std::vector<Flag> &flag_table() {
   static const std::vector<Flag> table = {
       {"-d", Value::kInt, nullptr, false,
@@ -299,54 +326,10 @@ const std::vector<Flag> &flag_table() {
        [](Settings &s, long, double, const char *) { s.anti = true; return kOk; }},
       // --focus, --focus-level L, --focus-probe PASSES, --focus-dilate D: a cropped canvas sampled only from the cells of
       // the plane whose samples reach it (include/cudabrot_amd.h, "Focused render"); each value flag turns --focus on
-      {"--focus", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.focus = true; return kOk; }},
-      {"--focus-level", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i < CB_FOCUS_MIN_LEVEL || i > CB_FOCUS_MAX_LEVEL) return "Invalid focus level (want 4 to 10)";
-         s.focus_level = (int) i;
-         return kOk;
-       }},
-      {"--focus-probe", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i < 1) return "Invalid focus probe (want at least 1 pass)";
-         s.focus_probe = i;
-         return kOk;
-       }},
-      {"--focus-dilate", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.focus = true;
-         if (i < 0) return "Invalid focus dilation (want 0 or more cells)";
-         s.focus_dilate = (int) i;
-         return kOk;
-       }},
+      CB_CELL_FLAGS("--focus", "focus", focus)
       // --aim, --aim-level L, --aim-probe PASSES, --aim-dilate D: a cropped plotted render sampled only from the cells of its
       // sample plane whose samples reach the canvas (include/cudabrot_amd.h, "Aimed render"); each value flag turns --aim on
-      {"--aim", Value::kNone, nullptr, false,
-       [](Settings &s, long, double, const char *) { s.aim = true; return kOk; }},
-      {"--aim-level", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.aim = true;
-         if (i < CB_FOCUS_MIN_LEVEL || i > CB_FOCUS_MAX_LEVEL) return "Invalid aim level (want 4 to 10)";
-         s.aim_level = (int) i;
-         return kOk;
-       }},
-      {"--aim-probe", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.aim = true;
-         if (i < 1) return "Invalid aim probe (want at least 1 pass)";
-         s.aim_probe = i;
-         return kOk;
-       }},
-      {"--aim-dilate", Value::kInt, nullptr, false,
-       [](Settings &s, long i, double, const char *) {
-         s.aim = true;
-         if (i < 0) return "Invalid aim dilation (want 0 or more cells)";
-         s.aim_dilate = (int) i;
-         return kOk;
-       }},
+      CB_CELL_FLAGS("--aim", "aim", aim)
       // --project a,b,c,d:e,f,g,h, --plane X,Y, --rotate X,Y:DEG: the plane of the 4-D set (z_re, z_im, c_re, c_im) the
       // orbits are plotted on (include/cudabrot_amd.h, "Projected render")
       {"--project", Value::kText, nullptr, false,
@@ -553,7 +536,7 @@ struct Partner {
 const Partner kPower = {[](const Settings &s) { return s.power != 0; }, "--power"};
 const Partner kShip = {[](const Settings &s) { return s.burning_ship; }, "--burning-ship"};
 const Partner kAnti = {[](const Settings &s) { return s.anti; }, "--anti"};
-const Partner kFocus = {[](const Settings &s) { return s.focus; }, "--focus"};
+const Partner kFocus = {[](const Settings &s) { return s.focus.on; }, "--focus"};
 const Partner kChannel = {[](const Settings &s) { return s.n_channels > 0 || s.color_file; }, "--channel"};
 const Partner kGpus = {[](const Settings &s) { return s.gpus > 1; }, "--gpus above 1"};
 const Partner kRaw = {[](const Settings &s) { return s.raw_state; }, "--state-format raw"};
@@ -581,7 +564,7 @@ const std::vector<Refusal> &refusal_table() {
       // an aimed render is a projected, Julia or bounded render of one plane without a table, drawn from a cell list
       // (include/cudabrot_amd.h, "Aimed render").  The first row: it combines with --bounded, --formula, --power, --julia and
       // a projection, whose rows would otherwise say what it refuses in their own name -- and no line without --aim meets it
-      {[](const Settings &s) { return s.aim; }, "--aim",
+      {[](const Settings &s) { return s.aim.on; }, "--aim",
        {kFocus, kAnti, kPalette, kPeriodPalette, kDepth, kDepthPalette, kSweep, kPhoenix, kChannel, kGpus}, nullptr},
       // a period-palette render is a bounded render with a table (include/cudabrot_amd.h, "Period-palette render"): its
       // rows stand ahead of --bounded's, which refuses everything else in its own name -- and no line without the two flags
@@ -622,7 +605,7 @@ const std::vector<Refusal> &refusal_table() {
       {[](const Settings &s) { return s.projected(); }, "A projection", {kChannel, kAnti, kFocus, kGpus}, nullptr},
       // a focused render is one plane of escaping orbits on one device (include/cudabrot_amd.h, cb_renderer_set_focus);
       // with --gpus every rank would probe a mask of its own
-      {[](const Settings &s) { return s.focus; }, "--focus", {kChannel, kAnti, kGpus}, nullptr},
+      {[](const Settings &s) { return s.focus.on; }, "--focus", {kChannel, kAnti, kGpus}, nullptr},
       // no fused anti channels (include/cudabrot_amd.h)
       {[](const Settings &s) { return s.anti; }, "--anti", {kChannel}, nullptr},
       // after parsing: --color and the --channel flags come in any order

@@ -17,6 +17,14 @@ struct Sweep {
   int frames;
 };
 
+// --focus / --aim and their three value flags: whether samples come from a probed cell list, and how the list is made.
+struct CellFlags {
+  bool on = false;
+  int level = 8;     // --*-level: cells of side 2^-L
+  long probe = 64;   // --*-probe: reference passes of the probe
+  int dilate = 1;    // --*-dilate: cells the probe's mask is widened by
+};
+
 struct Settings {
   int device = 0;                                   // -d
   const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
@@ -45,10 +53,7 @@ struct Settings {
   const char *color_file = nullptr;
   cb_color_params color = {CB_COMPOSE_RGB, 2.0, 1.0, 0.0};
   // --focus (extension): samples drawn only from the cells a probe found to reach the canvas (cb_renderer_set_focus)
-  bool focus = false;
-  int focus_level = 8;                              // --focus-level: cells of side 2^-L
-  long focus_probe = 64;                            // --focus-probe: reference passes of the probe
-  int focus_dilate = 1;                             // --focus-dilate: cells the probe's mask is widened by
+  CellFlags focus;
   // --project / --plane / --rotate (extensions): the plotted plane, P[2][4] over (zr, zi, cr, ci) (cb_renderer_set_projection)
   bool project_given = false, plane_given = false, rotate_given = false;
   double projection[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
@@ -75,7 +80,7 @@ struct Settings {
   // projection's
   bool depth_given = false;
   cb_depth depth = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0, 0};
-  bool plotted() const { return projected() || depth_given || sweep_given || phoenix || bounded || aim; }
+  bool plotted() const { return projected() || depth_given || sweep_given || phoenix || bounded || aim.on; }
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
@@ -111,10 +116,7 @@ struct Settings {
   // --aim (extension): a plotted render -- projected or Julia, under any of their steps, or --bounded -- whose samples are
   // drawn only from the cells of the sample plane a probe found to reach the canvas (cb_renderer_set_aim); makes the run a
   // projected one as --depth does (alone: the identity), with a first refusal row of its own
-  bool aim = false;
-  int aim_level = 8;                                // --aim-level: cells of side 2^-L
-  long aim_probe = 64;                              // --aim-probe: reference passes of the probe
-  int aim_dilate = 1;                               // --aim-dilate: cells the probe's mask is widened by
+  CellFlags aim;
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

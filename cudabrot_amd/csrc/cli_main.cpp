@@ -84,9 +84,9 @@ class Run {
       if (cfg_.julia) fprintf(stderr, "{\"julia\": [\"%a\", \"%a\"]}\n", cfg_.julia_c[0], cfg_.julia_c[1]);  // and so does c
       if (cfg_.phoenix) fprintf(stderr, "{\"phoenix\": [\"%a\", \"%a\"]}\n", cfg_.phoenix_p[0], cfg_.phoenix_p[1]);  // and p
       if (cfg_.bounded) fprintf(stderr, "{\"bounded\": true}\n");  // and which orbits are plotted
-      if (cfg_.aim) {  // and where the samples come from: the list is a function of these and of the lines above
-        fprintf(stderr, "{\"aim\": {\"level\": %d, \"probe\": %ld, \"dilate\": %d}}\n", cfg_.aim_level, cfg_.aim_probe,
-                cfg_.aim_dilate);
+      if (cfg_.aim.on) {  // and where the samples come from: the list is a function of these and of the lines above
+        fprintf(stderr, "{\"aim\": {\"level\": %d, \"probe\": %ld, \"dilate\": %d}}\n", cfg_.aim.level, cfg_.aim.probe,
+                cfg_.aim.dilate);
       }
       if (cfg_.period_palette()) {  // and the colours of their periods, with the tolerance of the return test
         fprintf(stderr, "{\"period_palette\": [");
@@ -334,8 +334,8 @@ class Run {
     const int variant = cfg_.kernel_variant | (cfg_.burning_ship ? CB_KERNEL_FLAG_BURNING_SHIP : 0) |
                         (cfg_.anti ? CB_KERNEL_FLAG_ANTI : 0) | (cfg_.power ? CB_KERNEL_POWER(cfg_.power) : 0) |
                         (cfg_.formula ? CB_KERNEL_FORMULA(cfg_.formula) : 0);
-    if (cfg_.focus) set_focus(variant);
-    if (cfg_.aim) set_aim(variant);
+    if (cfg_.focus.on) set_focus(variant);
+    if (cfg_.aim.on) set_aim(variant);
     // what the reference allocates in SetupCUDA, before its clock starts (cudabrot.cu:153-189,476)
     CB_CHECK(cb_renderer_prepare(renderer_, variant));
     for (cb_renderer *p : peers_) CB_CHECK(cb_renderer_prepare(p, variant));
@@ -395,32 +395,28 @@ class Run {
   // --focus: the probe and the cell list, before the clock of the pass loop starts.  The probe runs on generators of its
   // own, so a run resumed with -s and --rng-state finds the list of the run it continues.
   void set_focus(int variant) {
-    const int rc = cb_renderer_set_focus(renderer_, cfg_.focus_level, (uint32_t) cfg_.focus_probe, cfg_.focus_dilate,
-                                         variant);
-    if (rc == CB_ERROR_FOCUS_EMPTY) {
-      printf("Focus: no sample of the %ld probe passes reaches the canvas; nothing to render.\n", cfg_.focus_probe);
-      die();
-    }
-    CB_CHECK(rc);
-    uint32_t n_cells = 0, n_total = 0;
-    CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
-    printf("Focus: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", n_cells, n_total,
-           cfg_.focus_level, cfg_.focus_probe, cfg_.focus_dilate);
-    fflush(stdout);
+    set_cells("Focus", cfg_.focus, cb_renderer_set_focus, CB_ERROR_FOCUS_EMPTY, cb_renderer_focus_cells, variant);
   }
 
   // --aim: likewise for a plotted render, after every setter that makes the renderer what it is.
   void set_aim(int variant) {
-    const int rc = cb_renderer_set_aim(renderer_, cfg_.aim_level, (uint32_t) cfg_.aim_probe, cfg_.aim_dilate, variant);
-    if (rc == CB_ERROR_AIM_EMPTY) {
-      printf("Aim: no sample of the %ld probe passes reaches the canvas; nothing to render.\n", cfg_.aim_probe);
+    set_cells("Aim", cfg_.aim, cb_renderer_set_aim, CB_ERROR_AIM_EMPTY, cb_renderer_aim_cells, variant);
+  }
+
+  // Set, report an empty list, print the sampling line: `set` and `cells` are the render's setter and its cell count,
+  // `empty` the setter's code for a probe that marked nothing, `name` what the lines call the render.
+  void set_cells(const char *name, const cb::CellFlags &f, int (*set)(cb_renderer *, int, uint32_t, int, int), int empty,
+                 int (*cells)(const cb_renderer *, uint32_t *, uint32_t *), int variant) {
+    const int rc = set(renderer_, f.level, (uint32_t) f.probe, f.dilate, variant);
+    if (rc == empty) {
+      printf("%s: no sample of the %ld probe passes reaches the canvas; nothing to render.\n", name, f.probe);
       die();
     }
     CB_CHECK(rc);
     uint32_t n_cells = 0, n_total = 0;
-    CB_CHECK(cb_renderer_aim_cells(renderer_, &n_cells, &n_total));
-    printf("Aim: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", n_cells, n_total,
-           cfg_.aim_level, cfg_.aim_probe, cfg_.aim_dilate);
+    CB_CHECK(cells(renderer_, &n_cells, &n_total));
+    printf("%s: sampling %u of %u cells of side 2^-%d (%ld probe passes, dilated by %d).\n", name, n_cells, n_total,
+           f.level, f.probe, f.dilate);
     fflush(stdout);
   }
 
@@ -650,6 +646,14 @@ class Run {
     printf("Done! Color image saved: %s\n", cfg_.color_file);
   }
 
+  // The cells / total / fraction piece of the stats line of a focused ("focus") or an aimed ("aim") run.
+  void print_cells(const char *key, int (*cells)(const cb_renderer *, uint32_t *, uint32_t *)) {
+    uint32_t n_cells = 0, n_total = 0;
+    CB_CHECK(cells(renderer_, &n_cells, &n_total));
+    fprintf(stderr, "\"%s_cells\": %u, \"%s_total\": %u, \"%s_fraction\": %.9g, ", key, n_cells, key, n_total, key,
+            n_total ? (double) n_cells / (double) n_total : 0.0);
+  }
+
   void print_stats() {
     cb_counters c;
     CB_CHECK(cb_renderer_read_counters(renderer_, &c));
@@ -671,18 +675,9 @@ class Run {
     std::string levels = std::to_string(cb_renderer_interior_map_level(renderer_));
     for (cb_renderer *p : peers_) levels += ", " + std::to_string(cb_renderer_interior_map_level(p));
     fprintf(stderr, "{\"interior_map_levels\": [%s], ", levels.c_str());
-    if (cfg_.focus) {  // the part of the plane the samples come from: the factor between focused and uniform sample counts
-      uint32_t n_cells = 0, n_total = 0;
-      CB_CHECK(cb_renderer_focus_cells(renderer_, &n_cells, &n_total));
-      fprintf(stderr, "\"focus_cells\": %u, \"focus_total\": %u, \"focus_fraction\": %.9g, ", n_cells, n_total,
-              n_total ? (double) n_cells / (double) n_total : 0.0);
-    }
-    if (cfg_.aim) {  // likewise for an aimed render
-      uint32_t n_cells = 0, n_total = 0;
-      CB_CHECK(cb_renderer_aim_cells(renderer_, &n_cells, &n_total));
-      fprintf(stderr, "\"aim_cells\": %u, \"aim_total\": %u, \"aim_fraction\": %.9g, ", n_cells, n_total,
-              n_total ? (double) n_cells / (double) n_total : 0.0);
-    }
+    // the part of the plane the samples come from: the factor between focused (aimed) and uniform sample counts
+    if (cfg_.focus.on) print_cells("focus", cb_renderer_focus_cells);
+    if (cfg_.aim.on) print_cells("aim", cb_renderer_aim_cells);
     fprintf(stderr,
             "\"samples\": %llu, \"rejected\": %llu, \"never_escaped\": %llu, \"too_fast\": %llu, "
             "\"recorded\": %llu, \"iterate_steps\": %llu, \"replay_steps\": %llu, "

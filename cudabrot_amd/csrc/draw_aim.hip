@@ -295,15 +295,10 @@ constexpr AimKernel kAimProbeKernels[2][2] = {{draw_aim_probe_kernel<false, fals
 }  // namespace
 
 hipError_t launch_draw_aim(const AimArgs &a, bool lockstep, hipStream_t stream) {
-  const bool from_cells = a.cells != nullptr, to_mask = a.mask != nullptr;
   if (!plot_launch_ok(a.p) || a.p.palette != 0 || a.p.lut != nullptr) return hipErrorInvalidValue;
-  if (from_cells && to_mask) return hipErrorInvalidValue;  // a probe of an aimed stream is not defined
-  if (from_cells && a.n_cells == 0) return hipErrorInvalidValue;
-  if ((from_cells || to_mask) && (a.level < CB_FOCUS_MIN_LEVEL || a.level > CB_FOCUS_MAX_LEVEL)) {
-    return hipErrorInvalidValue;
-  }
+  if (!grid_launch_ok(a)) return hipErrorInvalidValue;
   if (a.p.d.n_threads == 0 || a.p.d.samples_per_thread == 0) return hipSuccess;
-  const bool julia = a.p.julia != 0, bounded = a.bounded != 0;
+  const bool julia = a.p.julia != 0, bounded = a.bounded != 0, to_mask = a.mask != nullptr;
   const AimKernel kernel = lockstep  ? draw_aim_simple_kernel
                            : to_mask ? kAimProbeKernels[bounded][julia]
                                      : kAimKernels[plot_step_index(a.p)].by[bounded][julia];

@@ -30,17 +30,17 @@ __global__ void __launch_bounds__(256) draw_focus_simple_kernel(FocusArgs fa) {
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = tid < a.n_threads;
   const Canvas cv = make_canvas(a);
-  const bool from_cells = fa.cells != nullptr;
-  const bool to_mask = fa.mask != nullptr;
+  const bool from_cells = fa.g.cells != nullptr;
+  const bool to_mask = fa.g.mask != nullptr;
   LaneStats st;
   if (valid) {
     Xorwow rng = load_rng(a.states, a.n_threads, tid);
     for (uint32_t sample = 0; sample < a.samples_per_thread; ++sample) {
       double real, imag;
       if (from_cells) {
-        next_sample<true>(fa, rng, real, imag);
+        next_sample<true>(fa.g, rng, real, imag);
       } else {
-        next_sample<false>(fa, rng, real, imag);
+        next_sample<false>(fa.g, rng, real, imag);
       }
       st.samples++;
       if (!a.burning_ship && (in_main_cardioid(real, imag) || in_order2_bulb(real, imag))) {
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) draw_focus_simple_kernel(FocusArgs fa) {
         int row, col;
         if (pixel_of(r, i, cv, row, col)) {
           if (to_mask) {  // the first in-canvas point: the sample's cell reaches the canvas
-            mark_cell(fa, real, imag);
+            mark_cell(fa.g, real, imag);
             st.recorded++;
             break;
           }
@@ -100,7 +100,7 @@ struct FocusMode {
   const Canvas cv;
 
   __device__ __forceinline__ int next(Xorwow &rng, RoundLane &l) {
-    next_sample<kCells>(fa, rng, l.cr, l.ci);
+    next_sample<kCells>(fa.g, rng, l.cr, l.ci);
     if (!kShip && (in_main_cardioid(l.cr, l.ci) || in_order2_bulb(l.cr, l.ci))) return kSampleRejected;
     return kSampleIterate;
   }
@@ -115,7 +115,7 @@ struct FocusMode {
     int row, col;
     if (!pixel_of(l.r, l.i, cv, row, col)) return false;
     if (kMask) {  // the first in-canvas point ends the replay
-      mark_cell(fa, l.cr, l.ci);
+      mark_cell(fa.g, l.cr, l.ci);
       st.recorded++;
       st.replay_steps -= (unsigned long long) (l.end - l.k);
       return true;
@@ -148,19 +148,18 @@ void launch_product(const FocusArgs &a, uint32_t blocks, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream) {
+  if (!grid_launch_ok(a.g)) return hipErrorInvalidValue;
   if (a.d.n_threads == 0 || a.d.samples_per_thread == 0) return hipSuccess;
   const uint32_t blocks = (a.d.n_threads + 255u) / 256u;
-  const bool from_cells = a.cells != nullptr, to_mask = a.mask != nullptr;
+  const bool from_cells = a.g.cells != nullptr, to_mask = a.g.mask != nullptr;
   if (lockstep) {
     hipLaunchKernelGGL(draw_focus_simple_kernel, dim3(blocks), dim3(256), 0, stream, a);
   } else if (from_cells && !to_mask) {  // the focused draw
     launch_product<true, false>(a, blocks, stream);
   } else if (!from_cells && to_mask) {  // the probe
     launch_product<false, true>(a, blocks, stream);
-  } else if (!from_cells && !to_mask) {  // a normal render through this kernel (the tests' check against the oracle)
+  } else {  // a normal render through this kernel (the tests' check against the oracle)
     launch_product<false, false>(a, blocks, stream);
-  } else {
-    return hipErrorInvalidValue;  // (cells, mask): a probe of a focused stream is not defined
   }
   return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/cudabrot_amd.h"
@@ -222,15 +223,11 @@ hipError_t launch_draw_wide_ship(const DrawArgs &a, bool timed, hipStream_t stre
 // cycle-compressed draw_anti_kernel; a.burning_ship picks the step.  Direct atomics, no workspace, no carry.
 hipError_t launch_draw_anti(const DrawArgs &a, bool lockstep, hipStream_t stream);
 
-// draw_focus.hip: the focused render (include/cudabrot_amd.h, "Focused render").  A launch is a SOURCE of samples and a
-// SINK of accepted orbits:
-//   cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample);
-//   mask == null:  the histogram sink (d.hist, every in-canvas point); else the probe's mask (one bit per cell of the
-//                  c-plane, set by a sample whose accepted orbit has an in-canvas point; the replay stops there).
-// d carries the canvas, the iteration control, the generators, the counters and burning_ship; its workspace, carry and
-// interior-map fields are not read.
-struct FocusArgs {
-  DrawArgs d;
+// The cell grid of the sample plane (draw_cells.h), as the focused and the aimed launch carry it: the list a launch draws
+// its samples from, or the mask a probe marks.  All zero: neither, the uniform source and the histogram sink.  FocusArgs
+// holds one; AimArgs holds the same seven members itself (why: there).  What reads or fills a grid -- draw_cells.h and the
+// two helpers below -- is a template over the block that has the members, `Grid`.
+struct CellGrid {
   int level;              // cells of side 2^-level (cells or mask given)
   uint32_t n_cells;       // entries of `cells`
   const uint32_t *cells;  // ascending cell indices row * n + col, n = 4 << level
@@ -238,6 +235,38 @@ struct FocusArgs {
   double cell_side;       // 2^-level
   double cell_scale;      // 2^-(level + 2): (x + 2) * cell_scale lies in (0, 2^-level]
   double cells_per_unit;  // 2^level
+};
+// g.level and the three factors made from it (level 0: no grid, the factors stay as they are).
+template <class Grid>
+void set_grid_level(Grid &g, int level) {
+  g.level = level;
+  if (level) {
+    g.cell_side = ldexp(1.0, -level);
+    g.cell_scale = ldexp(1.0, -(level + 2));
+    g.cells_per_unit = ldexp(1.0, level);
+  }
+}
+// What no launch takes of a grid: cells and mask together (a probe of a listed stream is not defined), a list without
+// entries, a level outside CB_FOCUS_MIN_LEVEL .. CB_FOCUS_MAX_LEVEL when either is given.
+template <class Grid>
+bool grid_launch_ok(const Grid &g) {
+  const bool from_cells = g.cells != nullptr, to_mask = g.mask != nullptr;
+  if (from_cells && to_mask) return false;
+  if (from_cells && g.n_cells == 0) return false;
+  return !(from_cells || to_mask) || (g.level >= CB_FOCUS_MIN_LEVEL && g.level <= CB_FOCUS_MAX_LEVEL);
+}
+
+// draw_focus.hip: the focused render (include/cudabrot_amd.h, "Focused render").  A launch is a SOURCE of samples and a
+// SINK of accepted orbits:
+//   g.cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample);
+//   g.mask == null:  the histogram sink (d.hist, every in-canvas point); else the probe's mask (one bit per cell of the
+//                    c-plane, set by a sample whose accepted orbit has an in-canvas point; the replay stops there).
+// d carries the canvas, the iteration control, the generators, the counters and burning_ship; its workspace, carry and
+// interior-map fields are not read.
+// hipErrorInvalidValue, nothing launched: what grid_launch_ok refuses of g.
+struct FocusArgs {
+  DrawArgs d;
+  CellGrid g;
 };
 hipError_t launch_draw_focus(const FocusArgs &a, bool lockstep, hipStream_t stream);
 
@@ -359,24 +388,25 @@ hipError_t launch_draw_bounded(const PlotArgs &a, bool lockstep, hipStream_t str
 //            p.d.interior_map is read by the escaping kind with the Mandelbrot step on a sampled c only.
 //   bounded  0: the escaping orbits that pass the accept filter (launch_draw_plot); else the orbits that do not escape
 //            (launch_draw_bounded).
-//   cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample), the
-//            cells those of the SAMPLE plane: c when c is sampled, z_0 when c is fixed;
-//   mask == null:  the histogram sink (p.d.hist, what the un-aimed launch adds); else the probe's mask (one bit per cell, set
-//            by a sample whose plotted orbit has an in-canvas point; the replay stops there, p.d.hist is not read).
-//   The grid fields are FocusArgs', read when cells or mask is given.
-// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of p, a table, cells and mask together, cells
-// with n_cells == 0, a level outside CB_FOCUS_MIN_LEVEL .. CB_FOCUS_MAX_LEVEL when either is given.  lockstep: the
-// definition, one lane per reference thread, every point with weight 1.
+//   cells == null: the uniform source (4 draws per sample over [-2, 2)^2); else the cell list (6 draws per sample),
+//            the cells those of the SAMPLE plane: c when c is sampled, z_0 when c is fixed;
+//   mask == null:  the histogram sink (p.d.hist, what the un-aimed launch adds); else the probe's mask (one bit per
+//            cell, set by a sample whose plotted orbit has an in-canvas point; the replay stops there, p.d.hist is not
+//            read).
+//   The grid's members are CellGrid's, with its meanings, written out: behind the int `bounded` a nested CellGrid would
+//   start four bytes later than `level` does here, the compiler would fetch level, n_cells and cells with one scalar load
+//   where it now needs two, and the 53 kernels that read them would come out with other scalar registers and eight bytes
+//   shorter.  Measured, the Mandelbrot-step draw was 1.5 % slower that way, beyond the spread of its runs.
+// hipErrorInvalidValue, nothing launched: whatever launch_draw_plot refuses of p, a table, what grid_launch_ok refuses of
+// the grid.  lockstep: the definition, one lane per reference thread, every point with weight 1.
 struct AimArgs {
   PlotArgs p;
   int bounded;
-  int level;              // cells of side 2^-level (cells or mask given)
-  uint32_t n_cells;       // entries of `cells`
-  const uint32_t *cells;  // ascending cell indices row * n + col, n = 4 << level
-  uint32_t *mask;         // n * n bits
-  double cell_side;       // 2^-level
-  double cell_scale;      // 2^-(level + 2): (x + 2) * cell_scale lies in (0, 2^-level]
-  double cells_per_unit;  // 2^level
+  int level;
+  uint32_t n_cells;
+  const uint32_t *cells;
+  uint32_t *mask;
+  double cell_side, cell_scale, cells_per_unit;
 };
 hipError_t launch_draw_aim(const AimArgs &a, bool lockstep, hipStream_t stream);
 

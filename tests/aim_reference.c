@@ -1,7 +1,7 @@
 /* aim_reference.c -- CPU restatement of the aimed render (include/cudabrot_amd.h, "Aimed render"), for the tests only.
  * Plain C on the oracle's generator and shortcuts (oracle/liboracle.so), written from the definition, not from the kernels;
  * the steps, the projection and the binning are tests/plot_reference.c's and the save schedule tests/bounded_reference.c's,
- * included here.  Compiled by the tests with
+ * included here, and the grid's arithmetic tests/cells_reference.h's.  Compiled by the tests with
  *   gcc -O2 -shared -fPIC -ffp-contract=off -mfma [-fopenmp]
  *   aim_launch  one launch: a SOURCE (cells NULL: four draws per sample, uniform; else six, from the list, mapped as
  *               tests/focus_reference.c maps them), an un-aimed render (escaping or bounded orbits, a step, c sampled or
@@ -13,6 +13,7 @@
  *           weight 1, then ONE period with the exact integer weights.
  * It notes, per run, what a case must reach (aim_extra).  OpenMP variant: n_omp > 0 workers, atomic adds and bit sets. */
 #include "bounded_reference.c"
+#include "cells_reference.h"
 
 typedef struct {
   uint64_t samples, rejected, never_escaped, too_fast, recorded, iterate_steps, replay_steps, increments, skipped_steps;
@@ -26,34 +27,9 @@ typedef struct {
   uint64_t marking, plotted, cycles, no_cycle, both_weights, in_canvas, off_canvas;
 } aim_extra;
 
-/* The cell that holds the sample: (x + 2) * 2^L is exact; x = 2 is clamped into the last cell. */
-static uint32_t aim_cell_of(int level, double re, double im) {
-  const int n = 4 << level;
-  int col = (int) ((re + 2.0) * ldexp(1.0, level));
-  int row = (int) ((im + 2.0) * ldexp(1.0, level));
-  if (col > n - 1) col = n - 1;
-  if (row > n - 1) row = n - 1;
-  return (uint32_t) row * (uint32_t) n + (uint32_t) col;
-}
-
-/* A point of cell list entry j = high half of (a << 32 | b) * n_cells, from the two uniform coordinates x, y. */
-static void aim_point_of(int level, const uint32_t *cells, uint32_t n_cells, uint32_t a, uint32_t b, double x, double y,
-                         uint32_t *j_out, double *re, double *im) {
-  const unsigned __int128 product = (unsigned __int128) (((uint64_t) a << 32) | (uint64_t) b) * (unsigned __int128) n_cells;
-  const uint32_t j = (uint32_t) (uint64_t) (product >> 64);
-  const uint32_t cell = cells[j];
-  const uint32_t n = 4u << level;
-  *j_out = j;
-  *re = (-2.0 + (double) (cell % n) * ldexp(1.0, -level)) + (x + 2.0) * ldexp(1.0, -(level + 2));
-  *im = (-2.0 + (double) (cell / n) * ldexp(1.0, -level)) + (y + 2.0) * ldexp(1.0, -(level + 2));
-}
-
 void aim_map(int level, const uint32_t *cells, uint32_t n_cells, uint32_t a, uint32_t b, uint32_t x1, uint32_t x2,
              uint32_t y1, uint32_t y2, uint32_t *j_out, double *re, double *im) {
-  const double vx = (double) ((uint64_t) x1 | ((uint64_t) (x2 >> 11) << 32));
-  const double vy = (double) ((uint64_t) y1 | ((uint64_t) (y2 >> 11) << 32));
-  aim_point_of(level, cells, n_cells, a, b, (vx + 1.0) * 0x1p-53 * 4.0 - 2.0, (vy + 1.0) * 0x1p-53 * 4.0 - 2.0, j_out, re,
-               im);
+  cells_map(level, cells, n_cells, a, b, x1, x2, y1, y2, j_out, re, im);
 }
 
 /* One sample (sr, si): z_0, and c as well unless c is fixed.  hist != NULL: the draw; else the probe into mask. */
@@ -140,7 +116,7 @@ static void aim_sample(const orc_dims *d, const orc_iters *it, int bounded, int 
       continue;
     }
     if (!hist) { /* the probe: the first in-canvas point marks the SAMPLE's cell and ends the replay */
-      const uint32_t cell = aim_cell_of(level, sr, si);
+      const uint32_t cell = cells_cell_of(level, sr, si);
       if (atomic) {
         __atomic_fetch_or(mask + (cell >> 5), 1u << (cell & 31u), __ATOMIC_RELAXED);
       } else {
@@ -191,7 +167,7 @@ void aim_launch(const orc_dims *d, uint64_t *hist, uint32_t *mask, const orc_ite
           const double x = orc_uniform_double(&states[t]) * 4.0 - 2.0;
           const double y = orc_uniform_double(&states[t]) * 4.0 - 2.0;
           uint32_t j;
-          aim_point_of(level, cells, n_cells, a, b, x, y, &j, &sr, &si);
+          cells_point_of(level, cells, n_cells, a, b, x, y, &j, &sr, &si);
         } else {
           sr = orc_uniform_double(&states[t]) * 4.0 - 2.0;
           si = orc_uniform_double(&states[t]) * 4.0 - 2.0;

@@ -6,6 +6,7 @@
  *   focus_cells  the mask dilated by d cells (Chebyshev), as an ascending list
  *   focus_draw   the draw from a cell list (six draws per sample), or -- cells == NULL -- a normal render
  *   focus_map    the six-draw mapping alone, on given generator outputs
+ * The grid's arithmetic -- the cell that holds a point, the six-draw mapping -- is tests/cells_reference.h's.
  * Each launch has an OpenMP variant (n_omp > 0: that many workers, atomic increments and bit sets). */
 #include <math.h>
 #include <stdint.h>
@@ -13,6 +14,7 @@
 #include <string.h>
 
 #include "buddha_oracle.h"
+#include "cells_reference.h"
 
 typedef struct {
   uint64_t samples, rejected, never_escaped, too_fast, recorded, iterate_steps, replay_steps, increments;
@@ -38,33 +40,9 @@ static inline int pixel_of(const orc_dims *d, double re, double im, uint64_t *in
   return 1;
 }
 
-/* The cell that holds c: (c + 2) * 2^L is exact; c = 2 is clamped into the last cell. */
-static inline uint32_t cell_of(int level, double re, double im) {
-  const int n = 4 << level;
-  int col = (int) ((re + 2.0) * ldexp(1.0, level));
-  int row = (int) ((im + 2.0) * ldexp(1.0, level));
-  if (col > n - 1) col = n - 1;
-  if (row > n - 1) row = n - 1;
-  return (uint32_t) row * (uint32_t) n + (uint32_t) col;
-}
-
-/* The six-draw mapping on the outputs themselves: a, b pick the entry, (x1, x2) and (y1, y2) are the two draws of each
- * coordinate (v = x1 | (x2 >> 11) << 32, the coordinate (v + 1) * 2^-51 - 2). */
 void focus_map(int level, const uint32_t *cells, uint32_t n_cells, uint32_t a, uint32_t b, uint32_t x1, uint32_t x2,
                uint32_t y1, uint32_t y2, uint32_t *j_out, double *re, double *im) {
-  const unsigned __int128 product = (unsigned __int128) (((uint64_t) a << 32) | (uint64_t) b) * (unsigned __int128) n_cells;
-  const uint32_t j = (uint32_t) (uint64_t) (product >> 64);
-  const uint32_t cell = cells[j];
-  const uint32_t n = 4u << level;
-  const double lo_re = -2.0 + (double) (cell % n) * ldexp(1.0, -level);
-  const double lo_im = -2.0 + (double) (cell / n) * ldexp(1.0, -level);
-  const double vx = (double) ((uint64_t) x1 | ((uint64_t) (x2 >> 11) << 32));
-  const double vy = (double) ((uint64_t) y1 | ((uint64_t) (y2 >> 11) << 32));
-  const double x = (vx + 1.0) * 0x1p-53 * 4.0 - 2.0; /* rocrand_uniform_double * 4 - 2: every step exact */
-  const double y = (vy + 1.0) * 0x1p-53 * 4.0 - 2.0;
-  *j_out = j;
-  *re = lo_re + (x + 2.0) * ldexp(1.0, -(level + 2));
-  *im = lo_im + (y + 2.0) * ldexp(1.0, -(level + 2));
+  cells_map(level, cells, n_cells, a, b, x1, x2, y1, y2, j_out, re, im);
 }
 
 /* One sample c through the reference's path.  hist != NULL: the draw; else mask != NULL: the probe. */
@@ -103,7 +81,7 @@ static void one_sample(const orc_dims *d, const orc_iters *it, int ship, double 
     c->replay_steps++;
     if (pixel_of(d, r, i, &index)) {
       if (!hist) { /* the probe: the first in-canvas point marks the sample's cell and ends the replay */
-        const uint32_t cell = cell_of(level, cr, ci);
+        const uint32_t cell = cells_cell_of(level, cr, ci);
         if (atomic) {
           __atomic_fetch_or(mask + (cell >> 5), 1u << (cell & 31u), __ATOMIC_RELAXED);
         } else {
@@ -148,14 +126,10 @@ static void launch(const orc_dims *d, const orc_iters *it, int ship, orc_xorwow 
         if (cells) {
           const uint32_t a = orc_xorwow_next(&states[t]);
           const uint32_t b = orc_xorwow_next(&states[t]);
-          const unsigned __int128 product =
-              (unsigned __int128) (((uint64_t) a << 32) | (uint64_t) b) * (unsigned __int128) n_cells;
-          const uint32_t cell = cells[(uint64_t) (product >> 64)];
-          const uint32_t n = 4u << level;
           const double x = orc_uniform_double(&states[t]) * 4.0 - 2.0;
           const double y = orc_uniform_double(&states[t]) * 4.0 - 2.0;
-          re = (-2.0 + (double) (cell % n) * ldexp(1.0, -level)) + (x + 2.0) * ldexp(1.0, -(level + 2));
-          im = (-2.0 + (double) (cell / n) * ldexp(1.0, -level)) + (y + 2.0) * ldexp(1.0, -(level + 2));
+          uint32_t j;
+          cells_point_of(level, cells, n_cells, a, b, x, y, &j, &re, &im);
         } else {
           re = orc_uniform_double(&states[t]) * 4.0 - 2.0;
           im = orc_uniform_double(&states[t]) * 4.0 - 2.0;
