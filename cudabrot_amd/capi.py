@@ -352,6 +352,17 @@ def _load():
         "cb_renderer_set_frames": (i32, [vp, vp, i32]),
         "cb_renderer_frames": (i32, [vp, vp]),
         "cb_renderer_frames_image": (i32, [vp, C.c_double, i32, vp, C.POINTER(u64), C.POINTER(C.c_double)]),
+        "cb_white_clip_ok": (i32, [C.c_double]),
+        "cb_white_rank": (u64, [u64, C.c_double]),
+        "cb_white_count": (i32, [vp, u64, C.c_double, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "cb_set_grayscale_pixels_white": (i32, [vp, i32, i32, C.c_double, C.c_double, vp, C.POINTER(u64),
+                                                C.POINTER(C.c_double), C.POINTER(u64)]),
+        "cb_white_count_device": (i32, [vp, u64, C.c_double, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]),
+        "cb_tone_map_device_white": (i32, [vp, i32, i32, C.c_double, i32, C.c_double, vp, C.POINTER(u64),
+                                           C.POINTER(C.c_double), C.POINTER(u64), vp]),
+        "cb_renderer_set_white_clip": (i32, [vp, C.c_double]),
+        "cb_renderer_white_clip": (i32, [vp, C.POINTER(C.c_double)]),
+        "cb_renderer_last_white": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -384,7 +395,9 @@ EXPORTED_SYMBOLS = (
     "cb_draw_buddhabrot_periods cb_renderer_set_period_palette cb_renderer_period_palette "
     "cb_renderer_period_palette_image "
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
-    "cb_renderer_frames_image"
+    "cb_renderer_frames_image "
+    "cb_white_clip_ok cb_white_rank cb_white_count cb_set_grayscale_pixels_white cb_white_count_device "
+    "cb_tone_map_device_white cb_renderer_set_white_clip cb_renderer_white_clip cb_renderer_last_white"
 ).split()
 
 
@@ -946,6 +959,22 @@ class Renderer:
         )
         return gray, int(mx.value), float(scale.value)
 
+    def set_white_clip(self, percent):
+        """The white clip of every image call (cb_renderer_set_white_clip): a percentage of the lit counters, 0 = off."""
+        _check(lib.cb_renderer_set_white_clip(self._h, float(percent)), "cb_renderer_set_white_clip")
+
+    @property
+    def white_clip(self):
+        percent = C.c_double()
+        _check(lib.cb_renderer_white_clip(self._h, C.byref(percent)), "cb_renderer_white_clip")
+        return float(percent.value)
+
+    def last_white(self):
+        """(white, lit, clipped) of the last image call made with a clip set (cb_renderer_last_white)."""
+        white, lit, clipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib.cb_renderer_last_white(self._h, C.byref(white), C.byref(lit), C.byref(clipped)), "cb_renderer_last_white")
+        return int(white.value), int(lit.value), int(clipped.value)
+
     def color_image(self, planes=(0, 1, 2), gamma=1.0, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
         """Colour stage on the device (cb_renderer_color_image): planes[0..2] -> (big-endian u16 image [h,w,3] = the
         PPM body, levels [(black, white)] * 3)."""
@@ -1001,6 +1030,48 @@ def set_grayscale_pixels(hist, gamma):
     mx, scale = C.c_uint64(), C.c_double()
     lib.cb_set_grayscale_pixels(a.ctypes.data, w, h, float(gamma), gray.ctypes.data, C.byref(mx), C.byref(scale))
     return gray, int(mx.value), float(scale.value)
+
+
+def white_count(hist, clip):
+    """The white point of an array of counters ("White clip", cb_white_count) -> (white, lit, clipped)."""
+    a = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    white, lit, clipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(lib.cb_white_count(a.ctypes.data, a.size, float(clip), C.byref(white), C.byref(lit), C.byref(clipped)),
+           "cb_white_count")
+    return int(white.value), int(lit.value), int(clipped.value)
+
+
+def set_grayscale_pixels_white(hist, gamma, clip):
+    """cb_set_grayscale_pixels_white -> (u16 image [h,w] host-endian, max count, scale applied, white)."""
+    a = np.ascontiguousarray(hist, dtype=np.uint64)
+    h, w = a.shape
+    gray = np.empty((h, w), dtype=np.uint16)
+    mx, scale, white = C.c_uint64(), C.c_double(), C.c_uint64()
+    _check(
+        lib.cb_set_grayscale_pixels_white(a.ctypes.data, w, h, float(gamma), float(clip), gray.ctypes.data, C.byref(mx),
+                                          C.byref(scale), C.byref(white)),
+        "cb_set_grayscale_pixels_white",
+    )
+    return gray, int(mx.value), float(scale.value), int(white.value)
+
+
+def white_count_device(d_hist, n, clip, stream=0):
+    """cb_white_count_device on caller-owned device memory (an integer pointer to n u64) -> (white, lit, clipped)."""
+    white, lit, clipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(lib.cb_white_count_device(d_hist, int(n), float(clip), C.byref(white), C.byref(lit), C.byref(clipped), stream),
+           "cb_white_count_device")
+    return int(white.value), int(lit.value), int(clipped.value)
+
+
+def tone_map_device_white(d_hist, w, h, gamma, clip, d_gray_be, mode=0, stream=0):
+    """cb_tone_map_device_white on caller-owned device memory (integer pointers) -> (max count, scale applied, white)."""
+    mx, scale, white = C.c_uint64(), C.c_double(), C.c_uint64()
+    _check(
+        lib.cb_tone_map_device_white(d_hist, w, h, float(gamma), int(mode), float(clip), d_gray_be, C.byref(mx),
+                                     C.byref(scale), C.byref(white), stream),
+        "cb_tone_map_device_white",
+    )
+    return int(mx.value), float(scale.value), int(white.value)
 
 
 def draw_buddhabrot_channels(dims, d_hist, windows, d_states, n_threads, samples_per_thread, d_counters=0,

@@ -348,6 +348,10 @@ struct cb_renderer {
   // has kind_row(what).planes planes, or n_channels.
   Plotted what;
   std::vector<double> *frames;  // kFrames: what.d_frames on the host (cb_renderer_frames)
+  // The white clip ("White clip" of include/cudabrot_amd.h): an output setting the image calls read, 0 = off, and what
+  // the last image call made with it found (cb_renderer_last_white).  No launch, histogram or generator knows of it.
+  double white_clip;
+  cb::WhitePoint last_white;
 };
 
 namespace {
@@ -822,6 +826,23 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
   return 0;
 }
 
+// cb_tone_map_device over `rows` rows of w counters at `hist` -- or, on a renderer with a white clip, the clipped map over
+// the same array, whose white point the renderer keeps.  The one tone-map call of every image.
+int tone_map_rows(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
+                  uint64_t *max_out, double *scale_out) {
+  if (r->white_clip == 0.0) {
+    return cb_tone_map_device(hist, r->dims.w, rows, gamma, mode, d_gray_be, max_out, scale_out, r->stream);
+  }
+  cb::WhitePoint found = {0, 0, 0, 0};
+  const int rc = cb::tone_map_white(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma, mode,
+                                r->white_clip, d_gray_be, &found, r->stream);
+  if (rc) return rc;
+  r->last_white = found;
+  if (max_out) *max_out = found.max;  // the true maximum, and the scale applied
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.white);
+  return 0;
+}
+
 // `rows` rows of the histogram from `plane` on as one w x rows image, one maximum for all of it: finish, tone-map, copy
 // out.  What cb_renderer_grayscale_plane (one plane) and kind_image (all of them) do after their checks.
 int gray_image(cb_renderer *r, size_t plane, int rows, double gamma, int mode, uint16_t *host_gray_be, uint64_t *max_out,
@@ -834,8 +855,8 @@ int gray_image(cb_renderer *r, size_t plane, int rows, double gamma, int mode, u
   const size_t bytes = (size_t) rows * (size_t) r->dims.w * sizeof(uint16_t);
   uint16_t *d_gray = nullptr;
   CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
-  int rc = cb_tone_map_device(r->d_hist + plane * (size_t) r->dims.w * (size_t) r->dims.h, r->dims.w, rows, gamma, mode,
-                              d_gray, max_out, scale_out, r->stream);
+  int rc = tone_map_rows(r, r->d_hist + plane * (size_t) r->dims.w * (size_t) r->dims.h, rows, gamma, mode, d_gray, max_out,
+                         scale_out);
   if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
   if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
   (void) hipFree(d_gray);
@@ -1780,8 +1801,7 @@ int three_plane_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *hos
   int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_planes), 3 * n * sizeof(uint16_t));
   if (rc == 0) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_rgb), 3 * n * sizeof(uint16_t));
   // the three planes as one w x 3h image: one maximum for all of them
-  if (rc == 0) rc = cb_tone_map_device(r->d_hist, r->dims.w, 3 * r->dims.h, gamma, tone_mode, d_planes, max_out, scale_out,
-                                       r->stream);
+  if (rc == 0) rc = tone_map_rows(r, r->d_hist, 3 * r->dims.h, gamma, tone_mode, d_planes, max_out, scale_out);
   if (rc == 0) {
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(interleave_planes_kernel, dim3((uint32_t) (blocks < 4096 ? blocks : 4096)), dim3(256), 0, r->stream,
@@ -1840,6 +1860,7 @@ int cb_renderer_frames_image(cb_renderer *r, double gamma, int tone_mode, uint16
 int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, int tone_mode,
                             const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
+  if (r->white_clip != 0.0) return (int) hipErrorInvalidValue;  // the colour stage has a stretch of its own ("White clip")
   const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
   const cb_pixel *src[3];
   for (int j = 0; j < 3; ++j) {
@@ -1859,6 +1880,27 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
   if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
   (void) hipFree(d_rgb);
   return rc;
+}
+
+int cb_renderer_set_white_clip(cb_renderer *r, double percent) {
+  if (!r || !cb_white_clip_ok(percent)) return (int) hipErrorInvalidValue;
+  r->white_clip = percent;
+  r->last_white = {0, 0, 0, 0};
+  return 0;
+}
+
+int cb_renderer_white_clip(const cb_renderer *r, double *percent_out) {
+  if (!r || !percent_out) return (int) hipErrorInvalidValue;
+  *percent_out = r->white_clip;
+  return 0;
+}
+
+int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *lit_out, uint64_t *clipped_out) {
+  if (!r || !white_out || !lit_out || !clipped_out) return (int) hipErrorInvalidValue;
+  *white_out = r->last_white.white;
+  *lit_out = r->last_white.lit;
+  *clipped_out = r->last_white.clipped;
+  return 0;
 }
 
 int cb_renderer_write_histogram(cb_renderer *r, const cb_pixel *host_in) {

@@ -186,6 +186,10 @@ const char kUsageBody[] =
     "     If the program is loaded and the file exists, the buffer will be\n"
     "     filled with the contents of the file, but the dimensions must\n"
     "     match. Note that this file may be huge for high-resolution images.\n"
+    "  --white-clip <percent>: Scales the image against the count that this\n"
+    "     percentage of the nonzero pixels may exceed, rather than against\n"
+    "     the largest count; brighter pixels saturate. From 0 (the default,\n"
+    "     off) to below 100.\n"
     "\n"
     "The following settings control the location of the output image on the\n"
     "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
@@ -513,6 +517,18 @@ const std::vector<Flag> &flag_table() {
          s.color.white_percent = w;
          return kOk;
        }},
+      // --white-clip P: the white point of every image as a percentile of its lit counters (include/cudabrot_amd.h, "White
+      // clip"); text: a value that is no number gets the flag's own message (hexfloats accepted)
+      {"--white-clip", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         char *end = nullptr;
+         const double p = (t[0] == 0 || t[0] == ' ' || t[0] == '\t') ? NAN : strtod(t, &end);  // (strtod would skip blanks)
+         if (!end || end == t || *end != 0 || !cb_white_clip_ok(p)) {
+           return "Invalid white clip (want a percentage from 0 to below 100)";
+         }
+         s.white_clip = p;
+         return kOk;
+       }},
       // --tonemap lut|thresholds|host: the form of the device tone map, or the reference's host loop
       {"--tonemap", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
@@ -547,6 +563,7 @@ const Partner kFormula = {[](const Settings &s) { return s.formula != 0; }, "--f
 const Partner kSweep = {[](const Settings &s) { return s.sweep_given; }, "--sweep"};
 const Partner kPhoenix = {[](const Settings &s) { return s.phoenix; }, "--phoenix"};
 const Partner kPeriodPalette = {[](const Settings &s) { return s.period_palette(); }, "--period-palette"};
+const Partner kColor = {[](const Settings &s) { return s.color_file != nullptr; }, "--color"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -626,6 +643,9 @@ const std::vector<Refusal> &refusal_table() {
       // "Phoenix render"); the last row, likewise
       {[](const Settings &s) { return s.phoenix; }, "--phoenix",
        {kPower, kFormula, kShip, kPalette, kDepth, kDepthPalette, kSweep, kAnti, kFocus, kChannel, kGpus}, nullptr},
+      // a white clip exposes the planes' images; the colour stage stretches them itself (include/cudabrot_amd.h, "White
+      // clip").  The last row, likewise
+      {[](const Settings &s) { return s.white_clip > 0.0; }, "--white-clip", {kColor}, nullptr},
   };
   return table;
 }

@@ -117,6 +117,9 @@ struct Settings {
   // drawn only from the cells of the sample plane a probe found to reach the canvas (cb_renderer_set_aim); makes the run a
   // projected one as --depth does (alone: the identity), with a first refusal row of its own
   CellFlags aim;
+  // --white-clip P (extension): every image of the run exposed against a percentile of its counters instead of their
+  // maximum (include/cudabrot_amd.h, "White clip"; cb_renderer_set_white_clip); 0, the default, is off
+  double white_clip = 0.0;
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

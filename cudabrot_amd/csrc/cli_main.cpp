@@ -249,6 +249,7 @@ class Run {
     } else if (cfg_.bounded) {
       CB_CHECK(cb_renderer_set_bounded(renderer_));  // likewise
     }
+    if (cfg_.white_clip > 0.0) CB_CHECK(cb_renderer_set_white_clip(renderer_, cfg_.white_clip));  // an output setting
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -534,19 +535,45 @@ class Run {
   }
   static constexpr double launch_seconds_ = 0.2;
 
+  // The reference's host loop over `rows` rows of the counters at `hist` -- with --white-clip, the clipped one.
+  void host_tone_map(const cb_pixel *hist, int rows, uint16_t *gray, uint64_t *max, double *scale) {
+    if (cfg_.white_clip > 0.0) {
+      CB_CHECK(cb_set_grayscale_pixels_white(hist, cfg_.canvas.w, rows, cfg_.gamma_correction, cfg_.white_clip, gray, max,
+                                             scale, nullptr));
+    } else {
+      cb_set_grayscale_pixels(hist, cfg_.canvas.w, rows, cfg_.gamma_correction, gray, max, scale);
+    }
+  }
+
+  // The "Max value" line (cudabrot.cu:437) of an image over `rows` rows of the counters at `hist` (the host's mirror, read
+  // with --tonemap host only) -- and with --white-clip the line of what the clip found: by the host's definition or, on the
+  // device path, as the renderer's image call reported it.
+  void print_exposure(uint64_t max, double scale, const cb_pixel *hist, int rows) {
+    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);
+    if (!(cfg_.white_clip > 0.0)) return;
+    uint64_t white = 0, lit = 0, clipped = 0;
+    if (cfg_.host_tonemap) {
+      CB_CHECK(cb_white_count(hist, (uint64_t) cfg_.canvas.w * (uint64_t) rows, cfg_.white_clip, &white, &lit, &clipped));
+    } else {
+      CB_CHECK(cb_renderer_last_white(renderer_, &white, &lit, &clipped));
+    }
+    printf("White value: %lu (%g%% of %lu lit pixels may clip, %lu do)\n", (unsigned long) white, cfg_.white_clip,
+           (unsigned long) lit, (unsigned long) clipped);
+  }
+
   void tone_map(int plane) {
     uint64_t max = 0;
     double scale = 0.0;
+    const cb_pixel *hist = counts_ ? counts_ + (uint64_t) plane * pixel_count() : nullptr;
     if (cfg_.host_tonemap) {
-      cb_set_grayscale_pixels(counts_ + (uint64_t) plane * pixel_count(), cfg_.canvas.w, cfg_.canvas.h,
-                              cfg_.gamma_correction, gray_, &max, &scale);
+      host_tone_map(hist, cfg_.canvas.h, gray_, &max, &scale);
       gray_is_big_endian_ = false;
     } else {  // tone map on the device: only the 16-bit image crosses to the host
       CB_CHECK(cb_renderer_grayscale_plane(renderer_, plane, cfg_.gamma_correction, cfg_.tone_mode, gray_,
                                            &max, &scale));
       gray_is_big_endian_ = true;
     }
-    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+    print_exposure(max, scale, hist, cfg_.canvas.h);
   }
 
   // --palette, --depth-palette, --period-palette: the three planes tone-mapped against their common maximum, as one
@@ -558,7 +585,7 @@ class Run {
     palette_rgb_be_.resize(3 * pixel_count());
     if (cfg_.host_tonemap) {
       std::vector<uint16_t> planar(3 * pixel_count());
-      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, 3 * cfg_.canvas.h, cfg_.gamma_correction, planar.data(), &max, &scale);
+      host_tone_map(counts_, 3 * cfg_.canvas.h, planar.data(), &max, &scale);
       for (uint64_t i = 0; i < pixel_count(); ++i) {
         for (uint64_t j = 0; j < 3; ++j) {
           const uint16_t v = planar[j * pixel_count() + i];
@@ -571,7 +598,7 @@ class Run {
                                         : cb_renderer_palette_image)(
           renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max, &scale));
     }
-    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+    print_exposure(max, scale, counts_, 3 * cfg_.canvas.h);
   }
 
   // --depth, --sweep: the N planes tone-mapped against their common maximum, as one w x N*h image -- on the device, or
@@ -581,14 +608,13 @@ class Run {
     double scale = 0.0;
     planes_gray_be_.resize(planes() * pixel_count());
     if (cfg_.host_tonemap) {
-      cb_set_grayscale_pixels(counts_, cfg_.canvas.w, (int) planes() * cfg_.canvas.h, cfg_.gamma_correction,
-                              planes_gray_be_.data(), &max, &scale);
+      host_tone_map(counts_, (int) planes() * cfg_.canvas.h, planes_gray_be_.data(), &max, &scale);
       for (uint16_t &v : planes_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
     } else {
       CB_CHECK((cfg_.sweep_given ? cb_renderer_frames_image : cb_renderer_depth_image)(
           renderer_, cfg_.gamma_correction, cfg_.tone_mode, planes_gray_be_.data(), &max, &scale));
     }
-    printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);  // cudabrot.cu:437
+    print_exposure(max, scale, counts_, (int) planes() * cfg_.canvas.h);
   }
 
   // --depth, --sweep: N binary PGMs back to back in one file (Netpbm's format allows a sequence of images), each

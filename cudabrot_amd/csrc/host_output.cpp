@@ -5,6 +5,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <functional>
+#include <vector>
+
 #include "../../include/cudabrot_amd.h"
 
 namespace {
@@ -51,6 +55,53 @@ void cb_set_grayscale_pixels(const cb_pixel *hist, int w, int h, double gamma, u
   if (max_out) *max_out = max;
   if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);
   for (uint64_t i = 0; i < n; i++) gray_out[i] = cb_tone_value(hist[i], max, gamma);
+}
+
+int cb_white_clip_ok(double clip_percent) { return isfinite(clip_percent) && clip_percent >= 0.0 && clip_percent < 100.0; }
+
+uint64_t cb_white_rank(uint64_t lit, double clip_percent) {
+  if (lit == 0) return 0;
+  const uint64_t r = (uint64_t) ((double) lit * (clip_percent / 100.0));  // color_ranks' arithmetic (color_host.cpp)
+  return r < lit - 1 ? r : lit - 1;
+}
+
+// "White clip" of include/cudabrot_amd.h, the definition: the lit counters, partially ordered around rank r.
+int cb_white_count(const cb_pixel *hist, uint64_t n, double clip_percent, uint64_t *white_out, uint64_t *lit_out,
+                   uint64_t *clipped_out) {
+  if (!hist || !white_out || !lit_out || !clipped_out || !cb_white_clip_ok(clip_percent)) return 1;  // hipErrorInvalidValue
+  std::vector<uint64_t> lit;
+  for (uint64_t i = 0; i < n; i++) {
+    if (hist[i] > 0) lit.push_back(hist[i]);
+  }
+  uint64_t white = 0, clipped = 0;
+  if (!lit.empty()) {
+    const uint64_t r = cb_white_rank(lit.size(), clip_percent);
+    std::nth_element(lit.begin(), lit.begin() + (ptrdiff_t) r, lit.end(), std::greater<uint64_t>());
+    white = lit[(size_t) r];
+    for (uint64_t c : lit) clipped += c > white ? 1u : 0u;
+  }
+  *white_out = white;
+  *lit_out = lit.size();
+  *clipped_out = clipped;
+  return 0;
+}
+
+int cb_set_grayscale_pixels_white(const cb_pixel *hist, int w, int h, double gamma, double clip_percent, uint16_t *gray_out,
+                                  uint64_t *max_out, double *scale_out, uint64_t *white_out) {
+  if (!hist || !gray_out || w <= 0 || h <= 0 || !cb_white_clip_ok(clip_percent)) return 1;  // hipErrorInvalidValue
+  const uint64_t n = (uint64_t) w * (uint64_t) h;
+  uint64_t max = 0, white = 0, lit = 0, clipped = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (hist[i] > max) max = hist[i];
+  }
+  const int rc = cb_white_count(hist, n, clip_percent, &white, &lit, &clipped);
+  if (rc) return rc;
+  if (max_out) *max_out = max;
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) white);
+  if (white_out) *white_out = white;
+  // the clamp is on the count: gamma <= 0, the reference's unclamped branch, needs no case of its own
+  for (uint64_t i = 0; i < n; i++) gray_out[i] = cb_tone_value(hist[i] < white ? hist[i] : white, white, gamma);
+  return 0;
 }
 
 int cb_save_image(const char *path, uint16_t *gray, int w, int h) {

@@ -430,6 +430,22 @@ struct PeriodArgs {
 };
 hipError_t launch_draw_periods(const PeriodArgs &a, bool lockstep, hipStream_t stream);
 
+// tonemap.hip: the tone map of n device counters against `top` -- the table over [0, top] or the thresholds, as `mode`
+// (CB_TONE_*) and `top` choose -- into big-endian u16.  clamp: counts above `top` exist and take top's value (the white
+// clip); without it `top` is the largest counter.  Synchronises `stream`.
+int tone_map_against(const unsigned long long *hist, unsigned long long n, unsigned long long top, bool clamp, double gamma,
+                     int mode, uint16_t *d_gray_be, hipStream_t stream);
+// exposure.hip: cb_white_count_device, and the largest counter beside its three numbers (max_out may be null).
+int white_count_device(const unsigned long long *hist, unsigned long long n, double clip_percent, uint64_t *white_out,
+                       uint64_t *lit_out, uint64_t *clipped_out, uint64_t *max_out, hipStream_t stream);
+// exposure.hip: cb_tone_map_device_white with everything the select found: what a renderer keeps for
+// cb_renderer_last_white.
+struct WhitePoint {
+  uint64_t max, white, lit, clipped;
+};
+int tone_map_white(const unsigned long long *hist, int w, int h, double gamma, int mode, double clip_percent,
+                   uint16_t *d_gray_be, WhitePoint *found, hipStream_t stream);
+
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period
 // p is seen p / gcd(p, chunk) chunks after the save.  The periods that matter are mostly multiples of 3

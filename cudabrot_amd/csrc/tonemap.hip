@@ -57,16 +57,20 @@ __device__ __forceinline__ uint16_t big_endian(uint32_t v) {
   return (uint16_t) (((v & 0xffu) << 8) | ((v >> 8) & 0xffu));
 }
 
-// two pixels per thread: one 4-byte store
+// two pixels per thread: one 4-byte store.  kClamp (the white clip, exposure.hip): the table ends at `top` and every
+// larger count reads its last entry; without it `top` is not read and the kernel is the one it was.
+template <bool kClamp>
 __global__ void __launch_bounds__(kToneThreads) tone_lut_kernel(const unsigned long long *hist,
                                                                 unsigned long long n,
-                                                                const uint16_t *lut, uint16_t *out_be) {
+                                                                const uint16_t *lut, unsigned long long top,
+                                                                uint16_t *out_be) {
+  const auto at = [top](unsigned long long c) { return kClamp ? (c < top ? c : top) : c; };
   const unsigned long long stride = (unsigned long long) gridDim.x * kToneThreads * 2ull;
   for (unsigned long long i = ((unsigned long long) blockIdx.x * kToneThreads + threadIdx.x) * 2ull;
        i < n; i += stride) {
-    const uint32_t a = big_endian(lut[hist[i]]);
+    const uint32_t a = big_endian(lut[at(hist[i])]);
     if (i + 1 < n) {
-      const uint32_t b = big_endian(lut[hist[i + 1]]);
+      const uint32_t b = big_endian(lut[at(hist[i + 1])]);
       *reinterpret_cast<uint32_t *>(out_be + i) = a | (b << 16);  // n even or not: i is even
     } else {
       out_be[i] = (uint16_t) a;
@@ -154,6 +158,44 @@ std::vector<unsigned long long> build_thresholds(unsigned long long max, double 
 
 }  // namespace
 
+// The map against `top` on a device histogram of n counters: the table over [0, top] or the thresholds, as `mode` and
+// `top` choose.  clamp: counts above `top` exist (the white clip) and take top's value.
+int tone_map_against(const unsigned long long *hist, unsigned long long n, unsigned long long top, bool clamp, double gamma,
+                     int mode, uint16_t *d_gray_be, hipStream_t stream) {
+  DeviceBuffer d_table;
+  if (mode == CB_TONE_AUTO) mode = (top < kLutMaxEntries) ? CB_TONE_LUT : CB_TONE_THRESHOLDS;
+  if (mode == CB_TONE_LUT) {
+    if (top >= (1ull << 32)) return (int) hipErrorInvalidValue;  // not a sensible table
+    std::vector<uint16_t> lut((size_t) top + 1);
+    for (unsigned long long c = 0; c <= top; ++c) lut[(size_t) c] = cb_tone_value(c, top, gamma);
+    CB_TONE_TRY(hipMalloc(&d_table.p, lut.size() * sizeof(uint16_t)));
+    CB_TONE_TRY(hipMemcpyAsync(d_table.p, lut.data(), lut.size() * sizeof(uint16_t),
+                               hipMemcpyHostToDevice, stream));
+    if (clamp) {
+      hipLaunchKernelGGL(tone_lut_kernel<true>, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
+                         static_cast<const uint16_t *>(d_table.p), top, d_gray_be);
+    } else {
+      hipLaunchKernelGGL(tone_lut_kernel<false>, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
+                         static_cast<const uint16_t *>(d_table.p), top, d_gray_be);
+    }
+    CB_TONE_TRY(hipGetLastError());
+    CB_TONE_TRY(hipStreamSynchronize(stream));  // before the host table goes out of scope
+  } else {
+    // No clamp here, with a white clip or without: thr[k] is the smallest count in [0, top] whose value reaches k, the
+    // value of a count is the number of thresholds <= it, and every threshold is <= top -- so a count above top has
+    // top's value already.
+    const std::vector<unsigned long long> thr = build_thresholds(top, gamma);
+    CB_TONE_TRY(hipMalloc(&d_table.p, thr.size() * sizeof(unsigned long long)));
+    CB_TONE_TRY(hipMemcpyAsync(d_table.p, thr.data(), thr.size() * sizeof(unsigned long long),
+                               hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(tone_thresholds_kernel, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist,
+                       n, static_cast<const unsigned long long *>(d_table.p), d_gray_be);
+    CB_TONE_TRY(hipGetLastError());
+    CB_TONE_TRY(hipStreamSynchronize(stream));
+  }
+  return 0;
+}
+
 }  // namespace cb
 
 extern "C" int cb_tone_map_device(const cb_pixel *d_hist, int w, int h, double gamma, int mode,
@@ -167,7 +209,7 @@ extern "C" int cb_tone_map_device(const cb_pixel *d_hist, int w, int h, double g
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const unsigned long long n = (unsigned long long) w * (unsigned long long) h;
   const unsigned long long *hist = reinterpret_cast<const unsigned long long *>(d_hist);
-  DeviceBuffer d_max, d_table;
+  DeviceBuffer d_max;
   unsigned long long max = 0;
 
   // GetLinearColorScale, cudabrot.cu:425-439
@@ -180,28 +222,5 @@ extern "C" int cb_tone_map_device(const cb_pixel *d_hist, int w, int h, double g
   CB_TONE_TRY(hipStreamSynchronize(stream));
   if (max_out) *max_out = max;
   if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);
-
-  if (mode == CB_TONE_AUTO) mode = (max < kLutMaxEntries) ? CB_TONE_LUT : CB_TONE_THRESHOLDS;
-  if (mode == CB_TONE_LUT) {
-    if (max >= (1ull << 32)) return (int) hipErrorInvalidValue;  // not a sensible table
-    std::vector<uint16_t> lut((size_t) max + 1);
-    for (unsigned long long c = 0; c <= max; ++c) lut[(size_t) c] = cb_tone_value(c, max, gamma);
-    CB_TONE_TRY(hipMalloc(&d_table.p, lut.size() * sizeof(uint16_t)));
-    CB_TONE_TRY(hipMemcpyAsync(d_table.p, lut.data(), lut.size() * sizeof(uint16_t),
-                               hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(tone_lut_kernel, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
-                       static_cast<const uint16_t *>(d_table.p), d_gray_be);
-    CB_TONE_TRY(hipGetLastError());
-    CB_TONE_TRY(hipStreamSynchronize(stream));  // before the host table goes out of scope
-  } else {
-    const std::vector<unsigned long long> thr = build_thresholds(max, gamma);
-    CB_TONE_TRY(hipMalloc(&d_table.p, thr.size() * sizeof(unsigned long long)));
-    CB_TONE_TRY(hipMemcpyAsync(d_table.p, thr.data(), thr.size() * sizeof(unsigned long long),
-                               hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(tone_thresholds_kernel, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist,
-                       n, static_cast<const unsigned long long *>(d_table.p), d_gray_be);
-    CB_TONE_TRY(hipGetLastError());
-    CB_TONE_TRY(hipStreamSynchronize(stream));
-  }
-  return 0;
+  return tone_map_against(hist, n, max, false, gamma, mode, d_gray_be, stream);
 }

@@ -1209,6 +1209,64 @@ int cb_renderer_depth_palette_image(cb_renderer *r, double gamma, int tone_mode,
 int cb_renderer_period_palette_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *host_rgb_be, uint64_t *max_out,
                                      double *scale_out);
 
+/* ---- White clip: an image exposed against a percentile of its counters ------------- *
+ *
+ * Every image above is scaled against its LARGEST counter.  Where a few pixels hold counts thousands of times above the
+ * rest -- a bounded render onto an attracting cycle -- the rest lands in the lowest output levels.  The white clip picks
+ * the white point as an exact order statistic of the u64 counters instead, scales against it and saturates what lies
+ * above.  It is the project's own definition (the reference has none).  Normative; host, device and the tests' numpy
+ * restatement agree bit for bit:
+ *
+ *   input: the image's counters as ONE array of n values -- all planes of the image together, exactly the array whose
+ *   maximum the unclipped image takes -- and the clip percentage p, a finite double with 0 <= p < 100.
+ *     lit     = #{count > 0}.
+ *     r       = (uint64_t)((double) lit * (p / 100.0)), clamped to lit - 1 when lit > 0   (cb_white_rank).
+ *     white   = the (r + 1)-th largest counter: the largest c with #{count >= c} > r; 0 if lit == 0.
+ *     clipped = #{count > white}; by construction clipped <= r.
+ *     pixel   = cb_tone_value(min(count, white), white, gamma).  The clamp is on the count, so gamma <= 0, the
+ *               reference's unclamped branch, needs no case of its own.
+ *   The rank is taken over the lit counters only: a Buddhabrot canvas is mostly zeros, and a rank over all pixels would
+ *   make white 0 on any crop.
+ *   p = 0 gives white = the maximum and every byte, max and scale of the unclipped functions; p just under 100 gives the
+ *   smallest non-zero counter; an all-zero array gives white = 0, scale = inf and a zero image, as unclipped.
+ *   Planes that share a maximum unclipped share one white (the three planes of the palette renders, the N planes of a
+ *   depth or frames render: the ratios between planes carry the picture); each plane of a channel renderer has its own. */
+
+/* 1 for a valid clip percentage (finite, 0 <= p < 100), else 0. */
+int cb_white_clip_ok(double clip_percent);
+/* r of the definition for `lit` lit counters; 0 when lit == 0. */
+uint64_t cb_white_rank(uint64_t lit, double clip_percent);
+/* The definition on a host array of n counters: *white_out, *lit_out, *clipped_out.  0, or hipErrorInvalidValue for a
+ * NULL pointer or a bad percentage. */
+int cb_white_count(const cb_pixel *hist, uint64_t n, double clip_percent, uint64_t *white_out, uint64_t *lit_out,
+                   uint64_t *clipped_out);
+/* cb_set_grayscale_pixels with a white clip: gray_out receives w*h host-endian uint16; *max_out (may be NULL) is the true
+ * maximum, *scale_out (may be NULL) 65535 / white, the scale applied, *white_out (may be NULL) white.  0, or
+ * hipErrorInvalidValue for a NULL hist or gray_out, a canvas without pixels or a bad percentage. */
+int cb_set_grayscale_pixels_white(const cb_pixel *hist, int w, int h, double gamma, double clip_percent, uint16_t *gray_out,
+                                  uint64_t *max_out, double *scale_out, uint64_t *white_out);
+/* cb_white_count on a DEVICE array (8-byte aligned, 1 <= n <= 2^40): a radix select over the u64 counters, one sweep for
+ * the maximum and lit, then one 256-bin pass per significant byte of the maximum (none when r = 0); r is made on the
+ * host.  The three numbers equal cb_white_count's.  Synchronises `stream`. */
+int cb_white_count_device(const cb_pixel *d_hist, uint64_t n, double clip_percent, uint64_t *white_out, uint64_t *lit_out,
+                          uint64_t *clipped_out, void *stream);
+/* cb_tone_map_device with a white clip: the bytes of cb_set_grayscale_pixels_white + cb_save_image, and its three
+ * numbers.  CB_TONE_AUTO chooses by white, not by the maximum, and the table has white + 1 entries: a histogram whose hot
+ * pixels pass 2^32 still takes the table when white < 2^24.  At p = 0 the bytes are cb_tone_map_device's. */
+int cb_tone_map_device_white(const cb_pixel *d_hist, int w, int h, double gamma, int mode, double clip_percent,
+                             uint16_t *d_gray_be, uint64_t *max_out, double *scale_out, uint64_t *white_out, void *stream);
+/* A renderer's white clip: an output setting, 0 (the default) = off.  With one set, cb_renderer_grayscale_image and
+ * _plane, _palette_image, _depth_palette_image, _period_palette_image, _depth_image and _frames_image use the clipped map
+ * over the array they take the maximum of otherwise; *max_out stays the true maximum, *scale_out is 65535 / white.  It may
+ * be set and changed at any time: it touches no launch, no histogram and no generator state.  cb_renderer_color_image on
+ * a renderer with a clip returns hipErrorInvalidValue with nothing launched (the colour stage has a stretch of its own).
+ * hipErrorInvalidValue, the renderer left as it was: a bad percentage. */
+int cb_renderer_set_white_clip(cb_renderer *r, double percent);
+int cb_renderer_white_clip(const cb_renderer *r, double *percent_out);
+/* white, lit and clipped of the last image call made with a clip set; zeros before one, and after every
+ * cb_renderer_set_white_clip. */
+int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *lit_out, uint64_t *clipped_out);
+
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
  * The reference's colour recipe (generate_hires_color_image.sh) renders three windows, stretches each PGM with
