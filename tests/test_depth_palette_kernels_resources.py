@@ -11,7 +11,7 @@ import os
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, plot_instance_of
+from kernel_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, no_spill_no_scratch, plot_instance_of, row
 
 INSTANCES = [(s, j) for s in PLOT_STEPS for j in "01"]  # 13 steps x {sampled c, fixed c}: draw_depth.hip's instance set
 
@@ -22,17 +22,16 @@ def instance_of(name):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_depth_palette_kernels_fit_without_scratch(tmp_path):
-    kernels, assembly = compile_kernels(tmp_path, "draw_depth_palette")
+def test_depth_palette_kernels_fit_without_scratch():
+    kernels, assembly = compile_kernels("draw_depth_palette")
     product = [k for k in kernels if "draw_depth_palette_kernel" in k["name"]]
     lockstep = [k for k in kernels if "draw_depth_palette_simple_kernel" in k["name"]]
     # 26 product instances, the lock-step kernel, nothing else
     assert len(product) == 26 and len(lockstep) == 1 and len(kernels) == 27, [k["name"] for k in kernels]
     bar = at_most(128, 4)
     for k in kernels:
-        print(k["name"], "VGPRs", k["VGPRs"], "SGPRs", k["TotalSGPRs"], "waves/SIMD", k["Occupancy [waves/SIMD]"], "LDS",
-              k["LDS Size [bytes/block]"])
-        assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
+        print(row(k))
+        assert no_spill_no_scratch(k), k
         assert int(k["AGPRs"]) == 0, k
         assert bar(k), k
     for k in product:

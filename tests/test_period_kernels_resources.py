@@ -1,56 +1,34 @@
 """What the compiler makes of the period-palette render's kernels (draw_periods.hip: PeriodMode on draw_rounds.h's scheduler,
 one instance of draw_periods_kernel per step and per source of c, and the lock-step kernel), checked where it is built:
-hipcc cross-compiles for gfx950 without a GPU and reports every kernel's resources (the method of
-tests/test_round_kernels_resources.py).  The file is compiled once.  DESIGN.md 4.22 claims no spill, no scratch, no AGPRs
-and no LDS for all 27 -- the table is read from global memory, once per bounded orbit --, the plotted families' bar -- at
+hipcc cross-compiles for gfx950 without a GPU and reports every kernel's resources (tests/kernel_resources.py).
+The file is compiled once.  DESIGN.md 4.22 claims no spill, no scratch, no AGPRs and no LDS for all 27 -- the table is read from global memory, once per bounded orbit --, the plotted families' bar -- at
 most 128 VGPRs and at least 4 waves per SIMD --, and the figures of profiles/draw_periods_kernel_usage.txt.  Judged from
 the compiler's reported figures and the assembly's text only."""
 
 import os
-import re
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, PLOT_STEPS, ROOT, at_most, compile_kernels, plot_instance_of
+from kernel_resources import (HIPCC, PLOT_STEPS, at_most, compile_kernels, matches_record, no_spill_no_scratch,
+                              plot_instance_of, row)
 
-USAGE = os.path.join(ROOT, "profiles", "draw_periods_kernel_usage.txt")
 BAR = at_most(128, 4)
 
 
-def recorded_usage():
-    """{mangled name: (VGPRs, AGPRs, SGPRs, scratch, LDS, waves per SIMD)} of the committed record."""
-    rows = {}
-    with open(USAGE) as f:
-        for line in f:
-            if line.startswith("#") or not line.strip():
-                continue
-            m = re.match(r"(\S+)\s+VGPR\s+(\d+) AGPR\s+(\d+) SGPR\s+(\d+) spill s/v 0/0 scratch (\d+) LDS (\d+) occ (\d+)$",
-                         line.rstrip())
-            assert m, line
-            rows[m.group(1)] = tuple(int(v) for v in m.groups()[1:])
-    return rows
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_period_kernels_fit_without_scratch_and_match_the_record(tmp_path):
-    kernels, assembly = compile_kernels(tmp_path, "draw_periods")
+def test_period_kernels_fit_without_scratch_and_match_the_record():
+    kernels, assembly = compile_kernels("draw_periods")
     product = [k for k in kernels if "draw_periods_kernel" in k["name"]]
     lockstep = [k for k in kernels if "draw_periods_simple_kernel" in k["name"]]
     # 26 product instances, the lock-step kernel, nothing else
     assert len(product) == 26 and len(lockstep) == 1 and len(kernels) == 27, [k["name"] for k in kernels]
     for k in kernels:
-        print(k["name"], "VGPRs", k["VGPRs"], "SGPRs", k["TotalSGPRs"], "waves/SIMD", k["Occupancy [waves/SIMD]"])
-        assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
+        print(row(k))
+        assert no_spill_no_scratch(k), k
         assert int(k["AGPRs"]) == 0 and int(k["LDS Size [bytes/block]"]) == 0, k
         assert BAR(k), k
     # the exact instance set: every step of CB_PLOT_STEPS x {sampled c, fixed c}
     instances = sorted(plot_instance_of(k["name"], "draw_periods_kernel", 1, "10PeriodArgs") for k in product)
     assert instances == sorted((s, j) for s in PLOT_STEPS for j in "01")
     assert "scratch_" not in assembly
-    # the committed record says what the compiler says
-    record = recorded_usage()
-    assert sorted(record) == sorted(k["name"] for k in kernels)
-    for k in kernels:
-        now = (int(k["VGPRs"]), int(k["AGPRs"]), int(k["TotalSGPRs"]), int(k["ScratchSize [bytes/lane]"]),
-               int(k["LDS Size [bytes/block]"]), int(k["Occupancy [waves/SIMD]"]))
-        assert record[k["name"]] == now, (k["name"], record[k["name"]], now)
+    matches_record(kernels, "draw_periods")  # the committed record says what the compiler says

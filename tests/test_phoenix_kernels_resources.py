@@ -1,7 +1,7 @@
 """What the compiler makes of the Phoenix render's kernels (draw_phoenix.hip: PhoenixMode on draw_rounds.h's scheduler,
 one instance of draw_phoenix_kernel per source of c, and the lock-step kernel), checked where it is built: hipcc
-cross-compiles for gfx950 without a GPU and reports every kernel's resources (the method of
-tests/test_round_kernels_resources.py).  DESIGN.md section 4.19 claims the bar every plotted family has -- no spill, no
+cross-compiles for gfx950 without a GPU and reports every kernel's resources
+(tests/kernel_resources.py).  DESIGN.md section 4.19 claims the bar every plotted family has -- no spill, no
 scratch, no AGPRs, no LDS, at most 128 VGPRs and at least 4 waves per SIMD.  Judged from the compiler's reported figures
 and the assembly's text only."""
 
@@ -10,12 +10,12 @@ import re
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, at_most, compile_kernels
+from kernel_resources import HIPCC, at_most, compile_kernels, no_spill_no_scratch, row
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_phoenix_kernels_fit_without_scratch_or_lds(tmp_path):
-    kernels, assembly = compile_kernels(tmp_path, "draw_phoenix")
+def test_phoenix_kernels_fit_without_scratch_or_lds():
+    kernels, assembly = compile_kernels("draw_phoenix")
     product = [k for k in kernels if "draw_phoenix_kernel" in k["name"]]
     lockstep = [k for k in kernels if "draw_phoenix_simple_kernel" in k["name"]]
     # two product instances, the lock-step kernel, nothing else
@@ -25,9 +25,8 @@ def test_phoenix_kernels_fit_without_scratch_or_lds(tmp_path):
     assert flags == ["0", "1"]
     bar = at_most(128, 4)
     for k in kernels:
-        print(k["name"], "VGPRs", k["VGPRs"], "SGPRs", k["TotalSGPRs"], "waves/SIMD", k["Occupancy [waves/SIMD]"], "LDS",
-              k["LDS Size [bytes/block]"])
-        assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
+        print(row(k))
+        assert no_spill_no_scratch(k), k
         assert int(k["AGPRs"]) == 0 and int(k["LDS Size [bytes/block]"]) == 0, k
         assert bar(k), k
     assert "scratch_" not in assembly

@@ -1,16 +1,17 @@
 """What the compiler makes of the plotted renders' kernels (draw_plot.hip: the plot modes of draw_rounds.h's scheduler,
 one instance of draw_plot_kernel per step, per source of c and per sink, and the five lock-step kernels), checked where
-it is built: hipcc cross-compiles for gfx950 without a GPU and reports every kernel's resources (the method of
-tests/test_round_kernels_resources.py).  The file is compiled once.  DESIGN.md sections 4.11 to 4.15 claim, family by
+it is built: hipcc cross-compiles for gfx950 without a GPU and reports every kernel's resources
+(tests/kernel_resources.py).  The file is compiled once.  DESIGN.md sections 4.11 to 4.15 claim, family by
 family -- the projected render, the Multibrot step, the Julia render, the palette render, the formula step -- no spill,
 no scratch, no AGPRs and no LDS for every instance, at most 128 VGPRs and at least 4 waves per SIMD: each family's bar is
-stated on its own below.  Judged from the compiler's reported figures and the assembly's text only."""
+stated on its own below -- and the figures of profiles/draw_plot_kernel_usage.txt.  Judged from the compiler's reported figures and the assembly's text only."""
 
 import os
 
 import pytest
 
-from test_round_kernels_resources import HIPCC, PLOT_STEPS, at_most, compile_kernels, plot_instance_of
+from kernel_resources import (HIPCC, PLOT_STEPS, at_most, compile_kernels, matches_record, no_spill_no_scratch,
+                              plot_instance_of, row)
 
 LOCKSTEP = ["draw_project_simple_kernel", "draw_power_simple_kernel", "draw_julia_simple_kernel",
             "draw_palette_simple_kernel", "draw_formula_simple_kernel"]
@@ -42,8 +43,8 @@ def instance_of(name):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_plot_kernels_fit_without_scratch(tmp_path):
-    kernels, assembly = compile_kernels(tmp_path, "draw_plot")
+def test_plot_kernels_fit_without_scratch():
+    kernels, assembly = compile_kernels("draw_plot")
     product = [k for k in kernels if "draw_plot_kernel" in k["name"]]
     lockstep = [k for k in kernels if "_simple_kernel" in k["name"]]
     # 52 product instances, the five lock-step kernels, nothing else
@@ -51,8 +52,8 @@ def test_plot_kernels_fit_without_scratch(tmp_path):
     for name in LOCKSTEP:
         assert len([k for k in lockstep if name in k["name"]]) == 1, name
     for k in kernels:
-        print(k["name"], "VGPRs", k["VGPRs"], "SGPRs", k["TotalSGPRs"], "waves/SIMD", k["Occupancy [waves/SIMD]"])
-        assert int(k["VGPRs Spill"]) == 0 and int(k["SGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
+        print(row(k))
+        assert no_spill_no_scratch(k), k
         assert int(k["AGPRs"]) == 0 and int(k["LDS Size [bytes/block]"]) == 0, k
     by_instance = {instance_of(k["name"]): k for k in product}
     assert len(by_instance) == 52
@@ -68,3 +69,4 @@ def test_plot_kernels_fit_without_scratch(tmp_path):
                 assert bar(k), (family, k)
     assert sorted(seen) == sorted(by_instance)  # every instance belongs to exactly one family
     assert "scratch_" not in assembly
+    matches_record(kernels, "draw_plot")  # the committed record says what the compiler says
