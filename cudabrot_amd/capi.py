@@ -62,6 +62,7 @@ CB_STATUS_QUEUE_OVERFLOW, CB_STATUS_REPLAY_RUNAWAY, CB_STATUS_INTERIOR_MAP, CB_S
 CB_COMPOSE_RGB, CB_COMPOSE_HSL = 0, 1
 CB_PALETTE_MAX_ENTRIES, CB_PALETTE_MAX_STOPS = 1 << 24, 16  # palette render: the table's entries, the stops of one
 CB_DEPTH_MAX_SLICES = 256  # depth render: the planes of one
+CB_DENSITY_MAX_RADIUS = 8  # density filter: the widest kernel
 CB_PERIOD_MAX_ENTRIES = 1024  # period-palette render: the table's entries (periods 0 .. 1023)
 CB_FRAMES_MAX = 256  # frames render: the matrices (and planes) of one
 
@@ -363,6 +364,12 @@ def _load():
         "cb_renderer_set_white_clip": (i32, [vp, C.c_double]),
         "cb_renderer_white_clip": (i32, [vp, C.POINTER(C.c_double)]),
         "cb_renderer_last_white": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "cb_density_thresholds": (i32, [i32, C.c_double, u64, C.POINTER(u64)]),
+        "cb_density_arguments_ok": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(u64), vp]),
+        "cb_density_filter": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(u64), vp]),
+        "cb_density_filter_device": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(u64), vp, vp]),
+        "cb_renderer_set_density_filter": (i32, [vp, i32, C.c_double, u64]),
+        "cb_renderer_density_filter": (i32, [vp, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -397,7 +404,9 @@ EXPORTED_SYMBOLS = (
     "cb_rotate_projection cb_frames_from_sweep cb_draw_buddhabrot_frames cb_renderer_set_frames cb_renderer_frames "
     "cb_renderer_frames_image "
     "cb_white_clip_ok cb_white_rank cb_white_count cb_set_grayscale_pixels_white cb_white_count_device "
-    "cb_tone_map_device_white cb_renderer_set_white_clip cb_renderer_white_clip cb_renderer_last_white"
+    "cb_tone_map_device_white cb_renderer_set_white_clip cb_renderer_white_clip cb_renderer_last_white "
+    "cb_density_thresholds cb_density_arguments_ok cb_density_filter cb_density_filter_device "
+    "cb_renderer_set_density_filter cb_renderer_density_filter"
 ).split()
 
 
@@ -975,6 +984,19 @@ class Renderer:
         _check(lib.cb_renderer_last_white(self._h, C.byref(white), C.byref(lit), C.byref(clipped)), "cb_renderer_last_white")
         return int(white.value), int(lit.value), int(clipped.value)
 
+    def set_density_filter(self, radius, alpha=0.5, n0=1):
+        """The density filter of every image call (cb_renderer_set_density_filter): "Density filter"; radius 0 = off."""
+        _check(lib.cb_renderer_set_density_filter(self._h, int(radius), float(alpha), int(n0)),
+               "cb_renderer_set_density_filter")
+
+    @property
+    def density_filter(self):
+        """(radius, alpha, n0) as set; (0, 0.0, 0) without a filter."""
+        radius, alpha, n0 = C.c_int32(), C.c_double(), C.c_uint64()
+        _check(lib.cb_renderer_density_filter(self._h, C.byref(radius), C.byref(alpha), C.byref(n0)),
+               "cb_renderer_density_filter")
+        return int(radius.value), float(alpha.value), int(n0.value)
+
     def color_image(self, planes=(0, 1, 2), gamma=1.0, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
         """Colour stage on the device (cb_renderer_color_image): planes[0..2] -> (big-endian u16 image [h,w,3] = the
         PPM body, levels [(black, white)] * 3)."""
@@ -1053,6 +1075,35 @@ def set_grayscale_pixels_white(hist, gamma, clip):
         "cb_set_grayscale_pixels_white",
     )
     return gray, int(mx.value), float(scale.value), int(white.value)
+
+
+def density_thresholds(radius, alpha=0.5, n0=1):
+    """T[0 .. R] of the density filter ("Density filter", cb_density_thresholds) as a list of ints."""
+    radius = int(radius)
+    table = (C.c_uint64 * (max(radius, 0) + 1))()
+    _check(lib.cb_density_thresholds(radius, float(alpha), int(n0), table), "cb_density_thresholds")
+    return [int(t) for t in table]
+
+
+def _density_table(thresholds):
+    return (C.c_uint64 * len(thresholds))(*[int(t) for t in thresholds])
+
+
+def density_filter(hist, thresholds, group=1):
+    """cb_density_filter on a host array [h, w] or [planes, h, w] -> u64 array of the same shape, 8 fraction bits;
+    thresholds = T[0 .. R] (density_thresholds)."""
+    a = np.ascontiguousarray(hist, dtype=np.uint64)
+    planes, h, w = (1,) + a.shape if a.ndim == 2 else a.shape
+    out = np.zeros_like(a)
+    _check(lib.cb_density_filter(a.ctypes.data, w, h, planes, int(group), len(thresholds) - 1, _density_table(thresholds),
+                                 out.ctypes.data), "cb_density_filter")
+    return out
+
+
+def density_filter_device(d_hist, w, h, planes, group, thresholds, d_out, stream=0):
+    """cb_density_filter_device on caller-owned device memory (integer pointers to planes * h * w u64 each)."""
+    _check(lib.cb_density_filter_device(d_hist, int(w), int(h), int(planes), int(group), len(thresholds) - 1,
+                                        _density_table(thresholds), d_out, stream), "cb_density_filter_device")
 
 
 def white_count_device(d_hist, n, clip, stream=0):

@@ -352,6 +352,12 @@ struct cb_renderer {
   // the last image call made with it found (cb_renderer_last_white).  No launch, histogram or generator knows of it.
   double white_clip;
   cb::WhitePoint last_white;
+  // The density filter ("Density filter" of include/cudabrot_amd.h): an output setting too, radius 0 = off, with the
+  // table cb_density_thresholds made of it.
+  int density_radius;
+  double density_alpha;
+  uint64_t density_n0;
+  uint64_t density_thresholds[CB_DENSITY_MAX_RADIUS + 1];
 };
 
 namespace {
@@ -827,9 +833,9 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
 }
 
 // cb_tone_map_device over `rows` rows of w counters at `hist` -- or, on a renderer with a white clip, the clipped map over
-// the same array, whose white point the renderer keeps.  The one tone-map call of every image.
-int tone_map_rows(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
-                  uint64_t *max_out, double *scale_out) {
+// the same array, whose white point the renderer keeps.
+int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
+                      uint64_t *max_out, double *scale_out) {
   if (r->white_clip == 0.0) {
     return cb_tone_map_device(hist, r->dims.w, rows, gamma, mode, d_gray_be, max_out, scale_out, r->stream);
   }
@@ -841,6 +847,21 @@ int tone_map_rows(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, 
   if (max_out) *max_out = found.max;  // the true maximum, and the scale applied
   if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.white);
   return 0;
+}
+
+// The one tone-map call of every image: `rows` rows of w counters at `hist`, planes of `plane_h` rows each that are
+// smoothed in groups of `group` where the renderer has a density filter.  The filtered counters live for this call only.
+int tone_map_rows(cb_renderer *r, const cb_pixel *hist, int rows, int plane_h, int group, double gamma, int mode,
+                  uint16_t *d_gray_be, uint64_t *max_out, double *scale_out) {
+  if (r->density_radius == 0) return tone_map_counters(r, hist, rows, gamma, mode, d_gray_be, max_out, scale_out);
+  if (plane_h <= 0 || rows % plane_h != 0) return (int) hipErrorInvalidValue;
+  cb_pixel *d_filtered = nullptr;
+  CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_filtered), (size_t) rows * (size_t) r->dims.w * sizeof(cb_pixel)));
+  int rc = cb_density_filter_device(hist, r->dims.w, plane_h, rows / plane_h, group, r->density_radius,
+                                    r->density_thresholds, d_filtered, r->stream);
+  if (rc == 0) rc = tone_map_counters(r, d_filtered, rows, gamma, mode, d_gray_be, max_out, scale_out);  // synchronises
+  (void) hipFree(d_filtered);
+  return rc;
 }
 
 // `rows` rows of the histogram from `plane` on as one w x rows image, one maximum for all of it: finish, tone-map, copy
@@ -855,8 +876,8 @@ int gray_image(cb_renderer *r, size_t plane, int rows, double gamma, int mode, u
   const size_t bytes = (size_t) rows * (size_t) r->dims.w * sizeof(uint16_t);
   uint16_t *d_gray = nullptr;
   CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_gray), bytes));
-  int rc = tone_map_rows(r, r->d_hist + plane * (size_t) r->dims.w * (size_t) r->dims.h, rows, gamma, mode, d_gray, max_out,
-                         scale_out);
+  int rc = tone_map_rows(r, r->d_hist + plane * (size_t) r->dims.w * (size_t) r->dims.h, rows, r->dims.h, 1, gamma, mode,
+                         d_gray, max_out, scale_out);
   if (rc == 0) rc = (int) hipMemcpyAsync(host_gray_be, d_gray, bytes, hipMemcpyDeviceToHost, r->stream);
   if (rc == 0) rc = (int) hipStreamSynchronize(r->stream);
   (void) hipFree(d_gray);
@@ -1801,7 +1822,8 @@ int three_plane_image(cb_renderer *r, double gamma, int tone_mode, uint16_t *hos
   int rc = (int) hipMalloc(reinterpret_cast<void **>(&d_planes), 3 * n * sizeof(uint16_t));
   if (rc == 0) rc = (int) hipMalloc(reinterpret_cast<void **>(&d_rgb), 3 * n * sizeof(uint16_t));
   // the three planes as one w x 3h image: one maximum for all of them
-  if (rc == 0) rc = tone_map_rows(r, r->d_hist, 3 * r->dims.h, gamma, tone_mode, d_planes, max_out, scale_out);
+  // (and one group for the density filter: a colour pixel is smoothed as one thing)
+  if (rc == 0) rc = tone_map_rows(r, r->d_hist, 3 * r->dims.h, r->dims.h, 3, gamma, tone_mode, d_planes, max_out, scale_out);
   if (rc == 0) {
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(interleave_planes_kernel, dim3((uint32_t) (blocks < 4096 ? blocks : 4096)), dim3(256), 0, r->stream,
@@ -1861,6 +1883,7 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
                             const cb_color_params *p, uint16_t *host_rgb_be, uint16_t levels[6]) {
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
   if (r->white_clip != 0.0) return (int) hipErrorInvalidValue;  // the colour stage has a stretch of its own ("White clip")
+  if (r->density_radius != 0) return (int) hipErrorInvalidValue;  // and works on 16-bit planes ("Density filter")
   const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
   const cb_pixel *src[3];
   for (int j = 0; j < 3; ++j) {
@@ -1892,6 +1915,25 @@ int cb_renderer_set_white_clip(cb_renderer *r, double percent) {
 int cb_renderer_white_clip(const cb_renderer *r, double *percent_out) {
   if (!r || !percent_out) return (int) hipErrorInvalidValue;
   *percent_out = r->white_clip;
+  return 0;
+}
+
+int cb_renderer_set_density_filter(cb_renderer *r, int radius, double alpha, uint64_t n0) {
+  if (!r) return (int) hipErrorInvalidValue;
+  uint64_t table[CB_DENSITY_MAX_RADIUS + 1] = {};
+  if (radius != 0 && cb_density_thresholds(radius, alpha, n0, table) != 0) return (int) hipErrorInvalidValue;
+  r->density_radius = radius;
+  r->density_alpha = radius ? alpha : 0.0;
+  r->density_n0 = radius ? n0 : 0;
+  memcpy(r->density_thresholds, table, sizeof(table));
+  return 0;
+}
+
+int cb_renderer_density_filter(const cb_renderer *r, int *radius_out, double *alpha_out, uint64_t *n0_out) {
+  if (!r || !radius_out || !alpha_out || !n0_out) return (int) hipErrorInvalidValue;
+  *radius_out = r->density_radius;
+  *alpha_out = r->density_alpha;
+  *n0_out = r->density_n0;
   return 0;
 }
 

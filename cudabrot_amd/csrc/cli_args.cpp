@@ -160,6 +160,42 @@ bool parse_sweep(const char *text, Sweep *out) {
   return true;
 }
 
+// --density-filter R[:ALPHA[:N0]]: R and N0 decimal digits, ALPHA a number in strtod's syntax; the ranges are
+// cb_density_thresholds', which also refuses a table that starts at 2^22 or above.
+bool parse_density(const char *text, DensityFilter *out) {
+  const char *at = text;
+  DensityFilter d;
+  long r = 0;
+  if (*at < '0' || *at > '9') return false;
+  for (; *at >= '0' && *at <= '9'; ++at) {
+    r = r * 10 + (*at - '0');
+    if (r > CB_DENSITY_MAX_RADIUS) return false;
+  }
+  d.radius = (int) r;
+  if (*at == ':') {
+    ++at;
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    d.alpha = strtod(at, &end);
+    if (end == at || (*end != 0 && *end != ':')) return false;
+    at = end;
+    if (*at == ':') {
+      ++at;
+      unsigned long long n0 = 0;
+      if (*at < '0' || *at > '9') return false;
+      for (; *at >= '0' && *at <= '9'; ++at) {
+        n0 = n0 * 10 + (unsigned long long) (*at - '0');
+        if (n0 > (1ull << 20)) return false;
+      }
+      d.n0 = n0;
+    }
+  }
+  uint64_t table[CB_DENSITY_MAX_RADIUS + 1];
+  if (*at != 0 || d.radius < 1 || cb_density_thresholds(d.radius, d.alpha, d.n0, table) != 0) return false;
+  *out = d;
+  return true;
+}
+
 // The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
 const char kUsageBody[] =
     "Options may be one or more of the following:\n"
@@ -190,6 +226,10 @@ const char kUsageBody[] =
     "     percentage of the nonzero pixels may exceed, rather than against\n"
     "     the largest count; brighter pixels saturate. From 0 (the default,\n"
     "     off) to below 100.\n"
+    "  --density-filter <R[:ALPHA[:N0]]>: Smooths sparse counts before the\n"
+    "     image is made: a pixel's counts are spread over a radius that\n"
+    "     shrinks from R (1 to 8) as its count grows from N0 (default 1),\n"
+    "     as (R/r)^(1/ALPHA) (ALPHA from 1/16 to 4, default 0.5).\n"
     "\n"
     "The following settings control the location of the output image on the\n"
     "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
@@ -529,6 +569,13 @@ const std::vector<Flag> &flag_table() {
          s.white_clip = p;
          return kOk;
        }},
+      // --density-filter R[:ALPHA[:N0]]: every image made from counters smoothed with a radius that falls as the count
+      // rises (include/cudabrot_amd.h, "Density filter"); text, like the clip: R and N0 decimal digits, ALPHA in strtod's
+      // syntax (hexfloats accepted); what cb_density_thresholds refuses is refused here
+      {"--density-filter", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         return parse_density(t, &s.density) ? kOk : "Invalid density filter (want R[:ALPHA[:N0]], R from 1 to 8)";
+       }},
       // --tonemap lut|thresholds|host: the form of the device tone map, or the reference's host loop
       {"--tonemap", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
@@ -646,6 +693,9 @@ const std::vector<Refusal> &refusal_table() {
       // a white clip exposes the planes' images; the colour stage stretches them itself (include/cudabrot_amd.h, "White
       // clip").  The last row, likewise
       {[](const Settings &s) { return s.white_clip > 0.0; }, "--white-clip", {kColor}, nullptr},
+      // the density filter makes 64-bit counters; the colour stage works on the planes' 16-bit images
+      // (include/cudabrot_amd.h, "Density filter").  The last row, likewise
+      {[](const Settings &s) { return s.density.radius > 0; }, "--density-filter", {kColor}, nullptr},
   };
   return table;
 }

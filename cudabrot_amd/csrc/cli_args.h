@@ -25,6 +25,13 @@ struct CellFlags {
   int dilate = 1;    // --*-dilate: cells the probe's mask is widened by
 };
 
+// --density-filter R[:ALPHA[:N0]] as given, the defaults where a part is left out; radius 0: no flag.
+struct DensityFilter {
+  int radius = 0;
+  double alpha = 0.5;
+  uint64_t n0 = 1;
+};
+
 struct Settings {
   int device = 0;                                   // -d
   const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
@@ -120,6 +127,10 @@ struct Settings {
   // --white-clip P (extension): every image of the run exposed against a percentile of its counters instead of their
   // maximum (include/cudabrot_amd.h, "White clip"; cb_renderer_set_white_clip); 0, the default, is off
   double white_clip = 0.0;
+  // --density-filter R[:ALPHA[:N0]] (extension): every image of the run made from counters smoothed with a radius that
+  // falls as the count rises (include/cudabrot_amd.h, "Density filter"; cb_renderer_set_density_filter); radius 0, the
+  // default, is off
+  DensityFilter density;
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

@@ -127,6 +127,15 @@ class Run {
       }
       fflush(stderr);
     }
+    if (cfg_.density.radius > 0 && cfg_.print_stats) {  // on any run: the filter as given and the table made of it
+      uint64_t table[CB_DENSITY_MAX_RADIUS + 1];
+      if (cb_density_thresholds(cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0, table) != 0) return 1;  // (parsed)
+      fprintf(stderr, "{\"density_filter\": {\"radius\": %d, \"alpha\": \"%a\", \"n0\": %llu, \"thresholds\": [",
+              cfg_.density.radius, cfg_.density.alpha, (unsigned long long) cfg_.density.n0);
+      for (int r = 1; r <= cfg_.density.radius; ++r) fprintf(stderr, "%s%llu", r > 1 ? ", " : "", (unsigned long long) table[r]);
+      fprintf(stderr, "]}}\n");
+      fflush(stderr);
+    }
     setup();
     load_inprogress();
     load_rng_state();
@@ -163,6 +172,7 @@ class Run {
   uint16_t *gray_ = nullptr;
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
+  std::vector<cb_pixel> filtered_;  // --density-filter with --tonemap host: the counters the last image was mapped from
   std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette, --period-palette: the PPM body
   std::vector<uint16_t> planes_gray_be_;  // --depth, --sweep: the bodies of the N PGMs, slice or frame 0 first
   std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
@@ -250,6 +260,9 @@ class Run {
       CB_CHECK(cb_renderer_set_bounded(renderer_));  // likewise
     }
     if (cfg_.white_clip > 0.0) CB_CHECK(cb_renderer_set_white_clip(renderer_, cfg_.white_clip));  // an output setting
+    if (cfg_.density.radius > 0) {  // likewise
+      CB_CHECK(cb_renderer_set_density_filter(renderer_, cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0));
+    }
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
@@ -535,8 +548,17 @@ class Run {
   }
   static constexpr double launch_seconds_ = 0.2;
 
-  // The reference's host loop over `rows` rows of the counters at `hist` -- with --white-clip, the clipped one.
-  void host_tone_map(const cb_pixel *hist, int rows, uint16_t *gray, uint64_t *max, double *scale) {
+  // The reference's host loop over `rows` rows of the counters at `hist` -- with --white-clip, the clipped one; with
+  // --density-filter, over the filtered counters (filtered_): planes of the canvas's height, smoothed in groups of `group`.
+  void host_tone_map(const cb_pixel *hist, int rows, int group, uint16_t *gray, uint64_t *max, double *scale) {
+    if (cfg_.density.radius > 0) {
+      uint64_t table[CB_DENSITY_MAX_RADIUS + 1];
+      CB_CHECK(cb_density_thresholds(cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0, table));
+      filtered_.resize((size_t) rows * (size_t) cfg_.canvas.w);
+      CB_CHECK(cb_density_filter(hist, cfg_.canvas.w, cfg_.canvas.h, rows / cfg_.canvas.h, group, cfg_.density.radius,
+                                 table, filtered_.data()));
+      hist = filtered_.data();
+    }
     if (cfg_.white_clip > 0.0) {
       CB_CHECK(cb_set_grayscale_pixels_white(hist, cfg_.canvas.w, rows, cfg_.gamma_correction, cfg_.white_clip, gray, max,
                                              scale, nullptr));
@@ -547,9 +569,15 @@ class Run {
 
   // The "Max value" line (cudabrot.cu:437) of an image over `rows` rows of the counters at `hist` (the host's mirror, read
   // with --tonemap host only) -- and with --white-clip the line of what the clip found: by the host's definition or, on the
-  // device path, as the renderer's image call reported it.
+  // device path, as the renderer's image call reported it.  With --density-filter both lines speak of the filtered
+  // counters, and a line between them says so.
   void print_exposure(uint64_t max, double scale, const cb_pixel *hist, int rows) {
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);
+    if (cfg_.density.radius > 0) {
+      printf("Density filter: radius %d, alpha %g, n0 %lu (the values above carry 8 fraction bits)\n", cfg_.density.radius,
+             cfg_.density.alpha, (unsigned long) cfg_.density.n0);
+      if (cfg_.host_tonemap) hist = filtered_.data();  // what host_tone_map mapped
+    }
     if (!(cfg_.white_clip > 0.0)) return;
     uint64_t white = 0, lit = 0, clipped = 0;
     if (cfg_.host_tonemap) {
@@ -566,7 +594,7 @@ class Run {
     double scale = 0.0;
     const cb_pixel *hist = counts_ ? counts_ + (uint64_t) plane * pixel_count() : nullptr;
     if (cfg_.host_tonemap) {
-      host_tone_map(hist, cfg_.canvas.h, gray_, &max, &scale);
+      host_tone_map(hist, cfg_.canvas.h, 1, gray_, &max, &scale);
       gray_is_big_endian_ = false;
     } else {  // tone map on the device: only the 16-bit image crosses to the host
       CB_CHECK(cb_renderer_grayscale_plane(renderer_, plane, cfg_.gamma_correction, cfg_.tone_mode, gray_,
@@ -585,7 +613,7 @@ class Run {
     palette_rgb_be_.resize(3 * pixel_count());
     if (cfg_.host_tonemap) {
       std::vector<uint16_t> planar(3 * pixel_count());
-      host_tone_map(counts_, 3 * cfg_.canvas.h, planar.data(), &max, &scale);
+      host_tone_map(counts_, 3 * cfg_.canvas.h, 3, planar.data(), &max, &scale);
       for (uint64_t i = 0; i < pixel_count(); ++i) {
         for (uint64_t j = 0; j < 3; ++j) {
           const uint16_t v = planar[j * pixel_count() + i];
@@ -608,7 +636,7 @@ class Run {
     double scale = 0.0;
     planes_gray_be_.resize(planes() * pixel_count());
     if (cfg_.host_tonemap) {
-      host_tone_map(counts_, (int) planes() * cfg_.canvas.h, planes_gray_be_.data(), &max, &scale);
+      host_tone_map(counts_, (int) planes() * cfg_.canvas.h, 1, planes_gray_be_.data(), &max, &scale);
       for (uint16_t &v : planes_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
     } else {
       CB_CHECK((cfg_.sweep_given ? cb_renderer_frames_image : cb_renderer_depth_image)(

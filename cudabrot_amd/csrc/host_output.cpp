@@ -104,6 +104,90 @@ int cb_set_grayscale_pixels_white(const cb_pixel *hist, int w, int h, double gam
   return 0;
 }
 
+// "Density filter" of include/cudabrot_amd.h: the table of thresholds, the only floating point of the definition.
+int cb_density_thresholds(int radius, double alpha, uint64_t n0, uint64_t *thresholds_out) {
+  if (!thresholds_out || radius < 1 || radius > CB_DENSITY_MAX_RADIUS || !isfinite(alpha) || alpha < 1.0 / 16.0 ||
+      alpha > 4.0 || n0 < 1 || n0 > (1ull << 20)) {
+    return 1;  // hipErrorInvalidValue
+  }
+  double v[CB_DENSITY_MAX_RADIUS + 1];
+  for (int r = 1; r <= radius; ++r) v[r] = floor((double) n0 * pow((double) radius / (double) r, 1.0 / alpha));
+  if (!(v[1] < (double) CB_DENSITY_MAX_SMOOTHED)) return 1;  // (before any conversion: v[1] may pass 2^64)
+  thresholds_out[0] = ~0ull;
+  for (int r = 1; r <= radius; ++r) thresholds_out[r] = (uint64_t) v[r];
+  return 0;
+}
+
+namespace {
+
+// A table a filter accepts: T[0] = 2^64 - 1, T[1] < 2^22, non-increasing, T[R] >= 1.
+bool density_table_ok(int radius, const uint64_t *t) {
+  if (!t || radius < 1 || radius > CB_DENSITY_MAX_RADIUS || t[0] != ~0ull || t[1] >= CB_DENSITY_MAX_SMOOTHED) return false;
+  for (int r = 1; r <= radius; ++r) {
+    if (t[r] > t[r - 1] || t[r] < 1) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+int cb_density_arguments_ok(const void *hist, int w, int h, int planes, int group, int radius, const uint64_t *thresholds,
+                            const void *out) {
+  if (!hist || !out || w <= 0 || h <= 0 || planes <= 0 || (group != 1 && group != 3) || planes % group != 0) return 0;
+  if (!density_table_ok(radius, thresholds)) return 0;
+  const uint64_t bytes = (uint64_t) w * (uint64_t) h * (uint64_t) planes * sizeof(cb_pixel);
+  const uintptr_t a = (uintptr_t) hist, b = (uintptr_t) out;
+  return (a + bytes <= b || b + bytes <= a) ? 1 : 0;  // output and input may not alias
+}
+
+// The definition, plainly: every lit pixel spreads its counters over its neighbourhood.
+int cb_density_filter(const cb_pixel *hist, int w, int h, int planes, int group, int radius, const uint64_t *thresholds,
+                      uint64_t *out) {
+  if (!cb_density_arguments_ok(hist, w, h, planes, group, radius, thresholds, out)) return 1;  // hipErrorInvalidValue
+  const uint64_t n = (uint64_t) w * (uint64_t) h;
+  for (uint64_t i = 0; i < n * (uint64_t) planes; i++) {
+    if (hist[i] >= CB_DENSITY_MAX_COUNT) return 1;  // decided before anything is written
+  }
+  uint64_t binomial[CB_DENSITY_MAX_RADIUS + 1][2 * CB_DENSITY_MAX_RADIUS + 1] = {};  // [r][i + r] = C(2r, i + r)
+  binomial[0][0] = 1;
+  for (int r = 1; r <= radius; ++r) {
+    uint64_t row[2 * CB_DENSITY_MAX_RADIUS + 2] = {1};
+    for (int k = 1; k <= 2 * r; ++k) {
+      for (int i = k; i >= 1; --i) row[i] += row[i - 1];
+    }
+    for (int i = 0; i <= 2 * r; ++i) binomial[r][i] = row[i];
+  }
+  std::vector<uint64_t> acc((size_t) (n * (uint64_t) planes), 0);
+  for (int g = 0; g < planes / group; ++g) {
+    const cb_pixel *in = hist + (uint64_t) g * (uint64_t) group * n;
+    for (int y = 0; y < h; ++y) {
+      for (int x = 0; x < w; ++x) {
+        const uint64_t at = (uint64_t) y * (uint64_t) w + (uint64_t) x;
+        uint64_t key = 0;
+        for (int p = 0; p < group; ++p) key += in[(uint64_t) p * n + at];
+        int r = 0;
+        while (r < radius && key <= thresholds[r + 1]) ++r;  // the largest r with r = 0 or key <= T[r]
+        for (int p = 0; p < group; ++p) {
+          const uint64_t plane = ((uint64_t) g * (uint64_t) group + (uint64_t) p) * n;
+          const uint64_t count = in[(uint64_t) p * n + at];
+          out[plane + at] = (key != 0 && r == 0) ? count : 0;  // sharp
+          if (key == 0 || r == 0 || count == 0) continue;
+          for (int dy = -r; dy <= r; ++dy) {
+            if (y + dy < 0 || y + dy >= h) continue;
+            for (int dx = -r; dx <= r; ++dx) {
+              if (x + dx < 0 || x + dx >= w) continue;
+              acc[plane + (uint64_t) (y + dy) * (uint64_t) w + (uint64_t) (x + dx)] +=
+                  (count * binomial[r][dy + r] * binomial[r][dx + r]) << (32 - 4 * r);
+            }
+          }
+        }
+      }
+    }
+  }
+  for (uint64_t i = 0; i < n * (uint64_t) planes; i++) out[i] = (out[i] << 8) + (acc[i] >> 24);
+  return 0;
+}
+
 int cb_save_image(const char *path, uint16_t *gray, int w, int h) {
   const uint64_t pixel_count = (uint64_t) w * (uint64_t) h;
   // big-endian samples, cudabrot.cu:566-570

@@ -1267,6 +1267,69 @@ int cb_renderer_white_clip(const cb_renderer *r, double *percent_out);
  * cb_renderer_set_white_clip. */
 int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *lit_out, uint64_t *clipped_out);
 
+/* ---- Density filter: sparse counters smoothed with a kernel that shrinks as the count grows ---- *
+ *
+ * A histogram counter of n carries Poisson noise of relative size 1/sqrt(n): the faint regions of an image are salt and
+ * pepper.  The density filter (flame renderers' "density estimation") spreads each counter with a binomial kernel whose
+ * radius falls as the count rises: a pixel hit once becomes a soft blob, a pixel hit ten thousand times stays a pixel.
+ * It runs once per image, on the counters, before the tone map.  It is the project's own definition (the reference has
+ * none).  Normative; host, device and the tests' restatement in Python integers agree bit for bit.  All arithmetic on
+ * counters is unsigned 64-bit integer; the only floating point is the host's making of the threshold table.
+ *
+ *   parameters: R, an integer, 1 <= R <= CB_DENSITY_MAX_RADIUS; alpha, a finite double in [1/16, 4] (the CLI's default
+ *   0.5); n0, an integer, 1 <= n0 <= 2^20 (default 1).
+ *   thresholds (cb_density_thresholds, host only): T[0] = 2^64 - 1, and for r = 1 .. R
+ *     T[r] = (uint64_t) floor((double) n0 * pow((double) R / (double) r, 1.0 / alpha)),   in exactly this operation order.
+ *   T is non-increasing and T[R] = n0.  Parameters with T[1] >= 2^22 (CB_DENSITY_MAX_SMOOTHED) are refused.
+ *   (8, 0.5, 1) gives 64, 16, 7, 4, 2, 1, 1, 1; (4, 0.4, 16) gives 512, 90, 32, 16; (4, 0.5, 9) gives 144, 36, 16, 9.
+ *   planes and groups: the input is P planes of h rows of w counters, contiguous; `group` G, 1 or 3, divides P, and planes
+ *   jG .. jG + G - 1 are group j.  The KEY of a pixel is the sum of its counters over the G planes of its group (a colour
+ *   pixel is smoothed as one thing, so hue does not fringe).  The RADIUS of a pixel with key s >= 1 is the largest r in
+ *   0 .. R with r = 0 or s <= T[r]; a pixel with s = 0 adds nothing.
+ *   kernel: B_r[i] = C(2r, i + r) for i = -r .. r.  A counter n of a pixel with radius r >= 1 at (y, x) adds
+ *     n * B_r[dy] * B_r[dx] * 2^(32 - 4r)
+ *   to the accumulator acc of (y + dy, x + dx) of the SAME plane, for every |dy|, |dx| <= r that lies inside the plane;
+ *   taps outside the plane are dropped and no plane bleeds into the next.  The weights of one kernel sum to exactly 2^32.
+ *   A counter n of a pixel with radius 0 is kept apart: sharp = n at its own place (as if it added n * 2^32 there).
+ *   output: out = (sharp << 8) + (acc >> 24): a 64-bit fixed-point count with 8 fraction bits.
+ *   No overflow by construction: a smoothed counter is <= T[1] < 2^22, a tap weight <= 2^30, there are at most 289 taps,
+ *   so acc < 2^61; an input counter >= 2^55 (CB_DENSITY_MAX_COUNT) is refused with nothing written.  Output and input may
+ *   not alias.
+ * Consequences: a plane whose every lit key exceeds T[1] comes out as in << 8, bit for bit.  For an input whose lit
+ * pixels lie at least R from every border, 0 <= 256 * sum(in) - sum(out) < w * h * P: the unshifted accumulators conserve
+ * the mass exactly and only the final floor loses, less than one unit per pixel.  The result depends on no schedule. */
+#define CB_DENSITY_MAX_RADIUS 8
+#define CB_DENSITY_MAX_SMOOTHED (1ull << 22)
+#define CB_DENSITY_MAX_COUNT (1ull << 55)
+
+/* T[0 .. R] of the definition into thresholds_out (R + 1 values).  0, or hipErrorInvalidValue -- nothing written -- for a
+ * NULL pointer, an R, alpha or n0 outside its range, or parameters whose T[1] reaches 2^22. */
+int cb_density_thresholds(int radius, double alpha, uint64_t n0, uint64_t *thresholds_out);
+/* 1 when both filters below accept these arguments (the counters themselves apart): pointers not NULL, w, h, planes > 0,
+ * group 1 or 3 dividing planes, 1 <= radius <= 8, a table with T[0] = 2^64 - 1, T[1] < 2^22, non-increasing and
+ * T[radius] >= 1, and planes * h * w counters at `out` that do not overlap those at `hist`. */
+int cb_density_arguments_ok(const void *hist, int w, int h, int planes, int group, int radius, const uint64_t *thresholds,
+                            const void *out);
+/* The definition on host arrays, plainly (what --tonemap host calls).  0, or hipErrorInvalidValue with `out` untouched:
+ * arguments cb_density_arguments_ok refuses, or a counter >= 2^55. */
+int cb_density_filter(const cb_pixel *hist, int w, int h, int planes, int group, int radius, const uint64_t *thresholds,
+                      uint64_t *out);
+/* cb_density_filter on DEVICE arrays (8-byte aligned, at most 2^40 counters, h <= 16 * 65535, planes <= 65535: the
+ * grid's limits, hipErrorInvalidValue beyond them): a maximum pass decides the refusal, then one
+ * gather kernel, a workgroup per output tile with the tile and its halo staged in LDS (density.hip).  The values equal
+ * cb_density_filter's.  Synchronises `stream`. */
+int cb_density_filter_device(const cb_pixel *d_hist, int w, int h, int planes, int group, int radius,
+                             const uint64_t *thresholds, uint64_t *d_out, void *stream);
+/* A renderer's density filter: an output setting, radius 0 (the default) = off.  With one set, every image call of the
+ * white clip's list makes its image from the filtered counters: each plane of a grey, channel, depth or frames renderer
+ * on its own (group 1), the three planes of a palette, depth-palette or period-palette renderer as one group of 3.  The
+ * filtered array is made for the call and freed after it.  *max_out and *scale_out are those of the filtered array, whose
+ * values carry 8 fraction bits; a white clip takes its white point from the filtered values too.  No launch, histogram
+ * or generator state knows of it.  cb_renderer_color_image on a renderer with a filter returns hipErrorInvalidValue.
+ * hipErrorInvalidValue, the renderer left as it was: parameters cb_density_thresholds refuses (radius 0 apart). */
+int cb_renderer_set_density_filter(cb_renderer *r, int radius, double alpha, uint64_t n0);
+int cb_renderer_density_filter(const cb_renderer *r, int *radius_out, double *alpha_out, uint64_t *n0_out);
+
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
  * The reference's colour recipe (generate_hires_color_image.sh) renders three windows, stretches each PGM with
