@@ -1,0 +1,484 @@
+"""Planted samples: generator states whose FIRST sample is a point the test chose, to the bit, and the finders of the
+points worth choosing -- samples that sit on a decision edge of the draw kernels.  Plain Python and numpy on the oracle
+(oracle/liboracle.so); neither torch nor pytest.  tests/test_planted_samples_host.py shows on the reference alone that
+what this module finds is decisive; tests/test_gpu_planted_samples.py feeds it to the kernels.
+
+THE PLANTING RECIPE.  The generator state is caller-owned memory (six u32 planes x0 .. x4, d on the GPU, the records
+of oracle.binding.STATE_DTYPE in the oracle), and XORWOW can be run backwards.  With K = 362437, g(v) = v ^ (v << 4),
+f(x) = t ^ (t << 1) where t = x ^ (x >> 2), all mod 2^32:
+
+    output n (n = 1, 2, ...)   o_n  = d + n K + x4_n
+    the fifth word             x4_n = g(x4_{n-1}) ^ f(x_{n-1}),   x4_0 = x[4]
+
+and the x_{n-1} of the first four steps are the state's x[0] .. x[3] untouched.  f is a bijection of the 32-bit words
+(undo the left shift from bit 0 up, then the right shift from bit 31 down), so for ANY four wanted outputs o_1 .. o_4
+and any d and x[4]:
+
+    x4_n = o_n - d - n K,      x[n-1] = f^-1(x4_n ^ g(x4_{n-1}))      n = 1 .. 4.
+
+A coordinate is drawn from two outputs: v = o_a | ((o_b >> 11) << 32), c = (v + 1 - 2^52) * 2^-51 (uniform_double * 4 -
+2, every operation exact).  So every double on the 2^-51 grid in (-2, 2] can be planted, 0 and +2 included; -2 cannot (v
+would be -1).  The low 11 bits of o_b are free, and so are d and x[4] (plant_states varies them by subsequence, so that
+what FOLLOWS the planted sample differs from lane to lane).
+
+THE LIMIT: ONE PLANTED SAMPLE PER SUBSEQUENCE.  Four outputs make one sample (real, then imag), and the state has only
+those four free words: the fifth output already depends on x[4] and on what the first four fixed.  The second and later
+samples of a subsequence are the generator's own -- the oracle, given the same states, follows them too, so a launch of
+50 samples per subsequence is still compared bit for bit; only its first sample is chosen.
+
+The finders bisect the oracle's own predicates over steps of the 2^-51 grid, so what they return is decisive by the
+reference's arithmetic, not by a formula about it:
+
+    with_escape_count(N, ray)     a sample whose orc_iterate_mandelbrot count is exactly N
+    cardioid_pairs, bulb_pairs    grid neighbours that orc_in_main_cardioid / orc_in_order2_bulb tell apart
+    pixel_edge_canvases           canvases on which a given orbit has points where trunc(a / delta) and
+                                  trunc(a * RN(1 / delta)) differ (the replay burst's exact-division fallback decides
+                                  there), and canvases with an orbit point on, or one ulp off, a canvas edge
+    pixel_edge_samples            more samples, on the real axis, with such a point on a given canvas
+"""
+
+import ctypes as C
+import math
+import os
+import sys
+from fractions import Fraction
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from oracle import binding as oracle  # noqa: E402
+
+M32 = 0xFFFFFFFF
+K = 362437
+GRID = 2.0 ** -51
+GUARD = 0.5 - 2.0 ** -24          # the replay burst's test on the estimate's fraction (draw_wave.hip, CB_REPLAY_BIN_DIV)
+
+
+# ---- the generator, backwards ------------------------------------------------------------------------------------------
+
+
+def _g(v):
+    return (v ^ (v << 4)) & M32
+
+
+def _f(x):
+    t = x ^ (x >> 2)
+    return (t ^ (t << 1)) & M32
+
+
+def _f_inverse(y):
+    t = 0
+    for b in range(32):                       # y = t ^ (t << 1): bit b of t is bit b of y xor bit b - 1 of t
+        t |= (((y >> b) ^ ((t >> (b - 1)) if b else 0)) & 1) << b
+    x = 0
+    for b in range(31, -1, -1):               # t = x ^ (x >> 2): bit b of x is bit b of t xor bit b + 2 of x
+        x |= (((t >> b) ^ ((x >> (b + 2)) if b < 30 else 0)) & 1) << b
+    return x
+
+
+def grid_index(c):
+    """c as a count of 2^-51 steps; raises unless c is on the grid and in (-2, 2]."""
+    n = math.ldexp(float(c), 51)
+    if n != int(n) or not -(1 << 52) < n <= (1 << 52):
+        raise ValueError("%r is not on the 2^-51 grid in (-2, 2]" % (c,))
+    return int(n)
+
+
+def grid_point(n):
+    return math.ldexp(float(n), -51)
+
+
+def _outputs(c, low):
+    v = grid_index(c) + (1 << 52) - 1
+    return v & M32, (((v >> 32) << 11) | (low & 0x7FF)) & M32
+
+
+def first_sample(state):
+    """The first sample the oracle draws from a state (which is left as it was)."""
+    st = oracle.Xorwow(int(state["d"]), (C.c_uint32 * 5)(*[int(v) for v in state["x"]]))
+    re = oracle.lib.orc_uniform_double(C.byref(st)) * 4.0 - 2.0
+    im = oracle.lib.orc_uniform_double(C.byref(st)) * 4.0 - 2.0
+    return re, im
+
+
+def plant_state(re, im, d=6615241, x4=5783321, low=0):
+    """An oracle state (d, x[5]) whose first sample is exactly (re, im).  d, x4 and the 22 bits of `low` are free."""
+    o = _outputs(re, low) + _outputs(im, low >> 11)
+    x = [0, 0, 0, 0, x4 & M32]
+    before = x[4]
+    for n in range(1, 5):
+        now = (o[n - 1] - d - n * K) & M32
+        x[n - 1] = _f_inverse(now ^ _g(before))
+        before = now
+    state = np.zeros((), dtype=oracle.STATE_DTYPE)
+    state["d"] = d & M32
+    state["x"] = x
+    assert first_sample(state) == (float(re), float(im)), (re, im, first_sample(state))
+    return state
+
+
+def plant_states(points, salt=0):
+    """One state per point, subsequence by subsequence; d, x[4] and the free bits vary with the index (and salt)."""
+    out = np.zeros(len(points), dtype=oracle.STATE_DTYPE)
+    for k, (re, im) in enumerate(points):
+        mix = ((k + 1 + 7919 * salt) * 2654435761) & M32
+        out[k] = plant_state(re, im, d=mix ^ 0x2C7F967F, x4=((mix * 40503) ^ (mix >> 7)) & M32 | 1, low=mix >> 9)
+    return out
+
+
+# ---- the reference's step ----------------------------------------------------------------------------------------------
+
+
+def fma(a, b, c):
+    """One rounding: math.fma where Python has it, else the exact rational value rounded to nearest even (finite
+    operands).  A zero result takes the sign IEEE gives it."""
+    if hasattr(math, "fma"):
+        return math.fma(a, b, c)
+    exact = Fraction(a) * Fraction(b) + Fraction(c)
+    if exact == 0:
+        return a * b + c                       # exact product and sum of zeros: the signs as IEEE has them
+    return float(exact)
+
+
+def mandel_orbit(re, im, n, ship=False):
+    """The reference's step (oracle/buddha_oracle.c, mandel_step: one rounding per fma) from z = c, at most n times ->
+    (real parts, imag parts, count): the points z_1 .. as IterateAndRecord visits them, the escaping one included and
+    last, and IterateMandelbrot's count (the index of the first step with |z|^2 > 4, n if there is none)."""
+    r, i = float(re), float(im)
+    rs, is_ = [], []
+    for k in range(n):
+        ii = i * i
+        t = fma(r, r, -ii)
+        ni = fma(abs(r) + abs(r), abs(i), im) if ship else fma(r + r, i, im)
+        r, i = re + t, ni
+        rs.append(r)
+        is_.append(i)
+        if fma(i, i, r * r) > 4:
+            return np.array(rs), np.array(is_), k
+    return np.array(rs), np.array(is_), n
+
+
+def real_axis_orbits(c, n):
+    """z_1 .. z_n of the real samples c (an array; imag 0): there the step is r <- c + RN(r r) with i = 0, no fused
+    operation left, so numpy's doubles do it.  -> [n, len(c)]"""
+    c = np.asarray(c, dtype=np.float64)
+    r = c.copy()
+    out = np.empty((n,) + c.shape)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(n):
+            r = c + r * r
+            out[k] = r
+    return out
+
+
+def escape_count(re, im, cap):
+    return int(oracle.lib.orc_iterate_mandelbrot(float(re), float(im), int(cap)))
+
+
+def rejected(re, im):
+    """What DrawBuddhabrot's shortcut says (either shape)."""
+    return bool(oracle.lib.orc_in_main_cardioid(float(re), float(im)) or oracle.lib.orc_in_order2_bulb(float(re), float(im)))
+
+
+# ---- finders -----------------------------------------------------------------------------------------------------------
+
+
+def _last_true(pred, lo, hi):
+    """pred(lo) and not pred(hi) -> n in [lo, hi) with pred(n) and not pred(n + 1) (or the mirror image for hi < lo)."""
+    assert pred(lo) and not pred(hi), (lo, hi)
+    while abs(hi - lo) > 1:
+        mid = (lo + hi) // 2
+        if pred(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo, hi
+
+
+RAYS = {
+    "cusp": lambda e: (0.25 + e * GRID, 0.0),      # count ~ pi / sqrt(eps): the parabolic point of the cardioid
+    "neck": lambda e: (-0.75, e * GRID),           # count ~ pi / eps: between cardioid and bulb
+}
+RAY_ENDS = {"cusp": 7 << 49, "neck": 1 << 52}     # the last grid step of either ray: c = 2, and imag = 2 (count 0)
+
+
+def with_escape_count(n, ray="cusp"):
+    """A grid point on the ray whose IterateMandelbrot count is exactly n (n >= 1), outside both shapes of the shortcut.
+    The count falls along either ray in bands hundreds of grid steps wide even at 60 000; the bisection ends on the last
+    point of band n, next to band n - 1."""
+    point = RAYS[ray]
+    lo, hi = _last_true(lambda e: escape_count(*point(e), n + 1) >= n, 1, RAY_ENDS[ray])
+    c = point(lo)
+    assert escape_count(*c, n + 2) == n and escape_count(*point(hi), n + 2) == n - 1, (n, ray, lo)
+    assert not rejected(*c)
+    return c
+
+
+def _crossings(pred, rays):
+    """rays: (axis, fixed coordinate, inside, outside) -- along the real (0) or the imag (1) axis at the fixed other
+    coordinate, from a point where pred holds to one where it does not.  -> [((in), (out))] grid neighbours across the
+    edge whose outside point the shortcut does not reject for the other shape either."""
+    pairs = []
+    for axis, fixed, inside, outside in rays:
+        fixed = grid_point(round(math.ldexp(fixed, 51)))            # 0.3 and its like: the grid point next to it
+        at = (lambda n: (grid_point(n), fixed)) if axis == 0 else (lambda n: (fixed, grid_point(n)))
+        a, b = _last_true(lambda n: pred(*at(n)), grid_index(inside), grid_index(outside))
+        if rejected(*at(a)) and not rejected(*at(b)):
+            pairs.append((at(a), at(b)))
+    return pairs
+
+
+def cardioid_pairs(n=None):
+    """Pairs of grid neighbours (rejected, not rejected) across the edge of orc_in_main_cardioid: both signs of imag,
+    imag = 0, the cusp at 1/4 and its surroundings, and -3/4, where cardioid and bulb touch (the point itself is in
+    neither: both tests are strict)."""
+    tiny, near = 2.0 ** -30, 2.0 ** -12         # (at imag 2^-30 the rounded tests leave no gap between the shapes)
+    rays = [(0, 0.0, 0.0, 1.0), (0, tiny, 0.0, 1.0), (0, -tiny, 0.0, 1.0), (0, 2.0 ** -12, 0.0, 1.0),   # the cusp
+            (0, 0.0, -0.5, -0.75), (0, near, -0.5, -0.75), (0, -near, -0.5, -0.75)]                       # -3/4
+    for y in (0.3, 0.6, 0.125 * 5 + GRID * 12345):
+        for s in (1.0, -1.0):
+            rays += [(0, s * y, -0.125, 1.0), (0, s * y, -0.125, -0.75)]
+    for x in (-0.125, 0.2, -0.7, 0.25 - 2.0 ** -20):
+        rays += [(1, x, 0.0, 1.0), (1, x, 0.0, -1.0)]
+    pairs = _crossings(lambda re, im: bool(oracle.lib.orc_in_main_cardioid(re, im)), rays)
+    return pairs if n is None else pairs[:n]
+
+
+def bulb_pairs(n=None):
+    """The same across the edge of orc_in_order2_bulb (centre -1, radius 1/4)."""
+    near = 2.0 ** -12
+    rays = [(0, 0.0, -1.0, -1.5), (0, 0.0, -1.0, -0.75), (0, near, -1.0, -0.75), (0, -near, -1.0, -0.75)]
+    for y in (0.1, 0.2, 0.25 - 2.0 ** -18):
+        for s in (1.0, -1.0):
+            rays += [(0, s * y, -1.0, -1.5), (0, s * y, -1.0, -0.75)]
+    for x in (-1.0, -1.1, -0.9, -1.25 + 2.0 ** -22):
+        rays += [(1, x, 0.0, 1.0), (1, x, 0.0, -1.0)]
+    pairs = _crossings(lambda re, im: bool(oracle.lib.orc_in_order2_bulb(re, im)), rays)
+    return pairs if n is None else pairs[:n]
+
+
+# ---- pixel edges -------------------------------------------------------------------------------------------------------
+
+
+def deltas(box, w, h):
+    """The pixel sides as RecomputePixelDeltas makes them (the oracle's own)."""
+    d = oracle.make_dims(w, h, box[0], box[1], box[2], box[3])
+    return d.delta_real, d.delta_imag
+
+
+def _axis(z, lo, delta, n, estimate):
+    """One coordinate of IncrementPixelCounter: (pixel index, in range), with the quotient or with the estimate alone."""
+    z = np.asarray(z, dtype=np.float64)
+    a = z - lo
+    with np.errstate(over="ignore", invalid="ignore"):
+        q = a * (1.0 / np.float64(delta)) if estimate else a / np.float64(delta)
+    inside = (z >= lo) & (q < n)                  # for q >= 0, (int) q < n iff q < n
+    return np.where(inside, np.trunc(q), -1).astype(np.int64), inside
+
+
+def pixels(box, w, h, rs, is_, estimate=False):
+    """IncrementPixelCounter's pixel of every point -> (col, row, counted)."""
+    dr, di = deltas(box, w, h)
+    col, okx = _axis(rs, box[0], dr, w, estimate)
+    row, oky = _axis(is_, box[2], di, h, estimate)
+    return col, row, okx & oky
+
+
+def histogram(box, w, h, rs, is_, estimate=False):
+    col, row, ok = pixels(box, w, h, rs, is_, estimate)
+    hist = np.zeros((h, w), dtype=np.uint64)
+    np.add.at(hist, (row[ok], col[ok]), 1)
+    return hist
+
+
+def edge_disagreements(box, w, h, rs, is_):
+    """The indices of the points that the estimate alone would bin differently from the quotient (counted by at least one
+    of the two).  By tests/test_quotient_estimate.py each of them fails the guard, so the kernels' exact division decides
+    it -- asserted here as well."""
+    cq, rq, okq = pixels(box, w, h, rs, is_)
+    ce, re_, oke = pixels(box, w, h, rs, is_, estimate=True)
+    differ = (okq | oke) & ((okq != oke) | (cq != ce) | (rq != re_))
+    dr, di = deltas(box, w, h)
+    for z, lo, d, cols_differ in ((rs, box[0], dr, cq != ce), (is_, box[2], di, rq != re_)):
+        est = (np.asarray(z)[differ & cols_differ] - lo) * (1.0 / np.float64(d))
+        assert not np.any(np.abs((est - np.floor(est)) - 0.5) < GUARD)
+    return np.flatnonzero(differ)
+
+
+def _edge_hits(z, extent, n, ulps=3):
+    """For the coordinates z of an orbit: every lower bound `lo` near z_k - RN(j delta) (a few ulps either way, every
+    pixel edge j, every k) for which, on the axis [lo, lo + extent) of n pixels, the guard fails and the two truncations
+    differ at z_k.  -> (array of lo, array of k)"""
+    z = np.asarray(z, dtype=np.float64)[:, None, None]
+    j = np.arange(1, n, dtype=np.float64)[None, :, None]
+    lo = z - j * (extent / n)
+    lo = lo + np.arange(-ulps, ulps + 1)[None, None, :] * np.spacing(lo)
+    delta = ((lo + extent) - lo) / n
+    a = z - lo
+    q, est = a / delta, a * (1.0 / delta)
+    hit = (a >= 0) & (np.trunc(q) != np.trunc(est)) & ~(np.abs((est - np.floor(est)) - 0.5) < GUARD) & (q < n)
+    k = np.broadcast_to(np.arange(z.shape[0])[:, None, None], hit.shape)
+    return lo[hit], k[hit]
+
+
+def edge_rate(delta, n):
+    """For each pixel side of the array delta: the share of the points on a pixel edge (a = RN(j delta), j < n) or one ulp
+    below it whose two truncations differ.  It is a property of the side: of how far RN(1 / delta) is from 1 / delta."""
+    sides, back = np.unique(np.asarray(delta, dtype=np.float64), return_inverse=True)
+    sides = sides[:, None]
+    a = np.arange(1, n, dtype=np.float64)[None, :] * sides
+    a = np.concatenate([a, np.nextafter(a, 0.0)], axis=1)
+    return (np.trunc(a / sides) != np.trunc(a * (1.0 / sides))).mean(axis=1)[back]
+
+
+def fma_free_norm(rs, is_):
+    """|z|^2 to within an ulp (the choice of canvas edges needs no more)."""
+    return np.asarray(rs) ** 2 + np.asarray(is_) ** 2
+
+
+def pixel_edge_canvases(orbit, w, h, extents=None, limit=4):
+    """orbit = (real parts, imag parts) of a planted orbit's recorded points.  -> {kind: [boxes]} with boxes (min_real,
+    max_real, min_imag, max_imag) whose pixels are not dyadic:
+
+      "fallback"   some point z_k is binned differently by trunc(a / delta) and by trunc(a * RN(1 / delta)) in its
+                   column AND some point in its row, both counted on the canvas: min = z_k - RN(j delta) give or take a
+                   few ulps, searched over j, k and a few extents, verified with the oracle's deltas, the best kept;
+      "on_min"     an orbit point exactly on min_real, another exactly on min_imag (counted: pixel 0);
+      "below_min"  the same points one ulp below the bounds (not counted);
+      "on_max"     an orbit point exactly on max_real and one on max_imag: (max - min) / delta truncates to w or to
+                   w - 1 -- the oracle says which."""
+    rs, is_ = np.asarray(orbit[0], dtype=np.float64), np.asarray(orbit[1], dtype=np.float64)
+    if extents is None:
+        extents = [(2.6 + 0.0137 * t, 1.4 + 0.0071 * t) for t in range(12)]
+    xs, ys = [], []
+    for er, ei in extents:
+        x, _ = _edge_hits(rs, er, w)
+        y, _ = _edge_hits(is_, ei, h)
+        x = x[(x <= 0.25) & (x + er >= 1.0)]                    # room for pixel_edge_samples: the real axis right of the
+        y = y[(y <= -0.1) & (y + ei >= 0.1)]                    # cusp, imag = 0 well inside
+        xs += [(r, float(v), float(v + er)) for r, v in zip(edge_rate(((x + er) - x) / w, w), x)]
+        ys += [(r, float(v), float(v + ei)) for r, v in zip(edge_rate(((y + ei) - y) / h, h), y)]
+    xs.sort(reverse=True)                                       # the pixel sides that disagree most often first
+    ys.sort(reverse=True)
+    found = []
+    for (_, x0, x1), (_, y0, y1) in zip(xs, ys):
+        box = (x0, x1, y0, y1)
+        idx = edge_disagreements(box, w, h, rs, is_)
+        cq, rq, _ = pixels(box, w, h, rs, is_)
+        ce, re_, _ = pixels(box, w, h, rs, is_, estimate=True)
+        if np.any(cq[idx] != ce[idx]) and np.any(rq[idx] != re_[idx]):
+            found.append(box)
+        if len(found) == limit:
+            break
+    out = {"fallback": found}
+    er, ei = extents[0]
+    # among the points before the orbit's last sixteen, which take it away: the rest stays on the canvas with them
+    bounded = (np.arange(len(rs)) < max(len(rs) - 16, 1)) & (fma_free_norm(rs, is_) <= 4.0)
+    kx, ky = int(np.argmin(np.where(bounded, rs, np.inf))), int(np.argmin(np.where(bounded, is_, np.inf)))
+    x, y = float(rs[kx]), float(is_[ky])
+    out["on_min"] = [(x, x + er, y, y + ei)]
+    xb, yb = float(np.nextafter(x, np.inf)), float(np.nextafter(y, np.inf))
+    out["below_min"] = [(xb, xb + er, yb, yb + ei)]
+    kx, ky = int(np.argmax(np.where(bounded, rs, -np.inf))), int(np.argmax(np.where(bounded, is_, -np.inf)))
+    x, y = float(rs[kx]), float(is_[ky])
+    out["on_max"] = [(x - er, x, y - ei, y)]
+    return out
+
+
+def pixel_edge_samples(box, w, n, max_iter, min_iter, depth=40, spread=24):
+    """Up to n DISTINCT samples on the real axis, right of the cusp, each recorded under (max_iter, min_iter) and each with
+    an orbit point whose column the estimate alone would get wrong on this canvas.  For a pixel edge j and an orbit index
+    k the sample with z_k = min_real + RN(j delta) is bisected (z_k rises with c there) and its grid neighbours are kept
+    where they verify.  The row of these points is that of imag = 0, which must lie on the canvas."""
+    dr, _ = deltas(box, w, 1)
+    lo_c, hi_c = grid_index(with_escape_count(max_iter - 1, "cusp")[0]), grid_index(with_escape_count(min_iter, "cusp")[0])
+    ends = real_axis_orbits(np.array([grid_point(lo_c), grid_point(hi_c)]), depth)
+    samples = []
+    for k in range(depth - 1, 0, -1):
+        edges = box[0] + np.arange(1, w) * dr
+        edges = edges[(edges > ends[k, 0]) & (edges < ends[k, 1]) & (edges < 2.0)]
+        if not len(edges):
+            continue
+        a, b = np.full(len(edges), lo_c, dtype=np.int64), np.full(len(edges), hi_c, dtype=np.int64)
+        while np.any(b - a > 1):
+            mid = (a + b) // 2
+            below = real_axis_orbits(mid * GRID, k + 1)[k] < edges
+            a, b = np.where(below, mid, a), np.where(below, b, mid)
+        near = (a[:, None] + np.arange(-spread, spread + 1)[None, :]).reshape(-1)
+        near = np.unique(near[(near >= lo_c) & (near <= hi_c)])
+        z = real_axis_orbits(near * GRID, k + 1)[k]
+        cq, _ = _axis(z, box[0], dr, w, False)
+        ce, _ = _axis(z, box[0], dr, w, True)
+        for g in near[cq != ce]:
+            c = grid_point(int(g))
+            if c not in samples and min_iter <= escape_count(c, 0.0, max_iter) < max_iter and not rejected(c, 0.0):
+                samples.append(c)
+        if len(samples) >= n:
+            break
+    return [(c, 0.0) for c in samples[:n]]
+
+
+# ---- the cases both suites use -----------------------------------------------------------------------------------------
+
+CHUNK, HEAD_STEPS, MID_MIN = 60, 4, 12            # kernels.h kChunk; draw_wave.hip kHeadSteps, plan_stages' kMidMin
+
+WIDE_WINDOWS = [(1234, 20), (2000, 20), (20000, 20)]                                # draw_wide_kernel's usual split
+PROBE_WINDOWS = [(3000, 1000), (2999, 1007), (60000, 45000), (60007, 45011)]        # min_iter inside the LONG stage
+
+
+def stage_plan(max_iter, min_iter):
+    """plan_stages (draw_wave.hip) restated -> (long_start, tail_start): the first iteration of the LONG stage, and of an
+    orbit's last, shorter chunk.  For max_iter beyond the MID stage only (what the windows above are)."""
+    mid = 16 if min_iter <= HEAD_STEPS + MID_MIN else MID_MIN + (min_iter - HEAD_STEPS - MID_MIN) % CHUNK
+    long_start = HEAD_STEPS + mid
+    assert max_iter > long_start
+    return long_start, max_iter - (max_iter - long_start) % CHUNK
+
+
+def window_counts(max_iter, min_iter):
+    """The escape counts worth planting for a window: two either side of each decision -- min_iter (too fast / recorded),
+    max_iter (recorded / never escaped) --, the first LONG chunk's first and last steps and the next chunk's first two, and
+    the steps either side of the tail chunk's start."""
+    long_start, tail_start = stage_plan(max_iter, min_iter)
+    counts = {max_iter + k for k in (-2, -1, 0, 1)} | {min_iter + k for k in (-2, -1, 0, 1)}
+    counts |= {long_start + k for k in (0, 1, CHUNK - 1, CHUNK, CHUNK + 1)} | {tail_start + k for k in (-1, 0, 1)}
+    return sorted(n for n in counts if 1 <= n <= max_iter + 1)
+
+
+def window_samples(max_iter, min_iter):
+    """[(count, (re, im))]: every count of window_counts on both rays."""
+    return [(n, with_escape_count(n, ray)) for n in window_counts(max_iter, min_iter) for ray in ("cusp", "neck")]
+
+
+def expected_fate(count, max_iter, min_iter):
+    """The oracle counter that a sample of this escape count adds to (DrawBuddhabrot, cudabrot.cu:400-411)."""
+    return "never_escaped" if count >= max_iter else ("too_fast" if count < min_iter else "recorded")
+
+
+DULL = [(0.0, 0.0), (2.0, 2.0), (-1.0, 0.0), (1.5, -1.5)]     # in the cardioid, gone at once, in the bulb, gone at once
+
+
+def layout(deep, threads, shape):
+    """One planted first sample per subsequence: the deep samples `deep` cycled through "every" lane, or given to
+    subsequences 0 and 63 only ("ends": lanes 0 and 63 of the first wave), or to subsequence 64 + 5 only ("b_only": in
+    draw_wide_kernel generator B of lane 5 of the first wave, whose generator A is subsequence 5) -- the rest draw dull
+    samples that never reach the LONG stage."""
+    if shape == "every":
+        return [deep[k % len(deep)] for k in range(threads)]
+    points = [DULL[k % len(DULL)] for k in range(threads)]
+    for n, k in enumerate({"ends": (0, 63), "b_only": (64 + 5,)}[shape]):
+        points[k] = deep[n % len(deep)]
+    return points
+
+
+def pixel_edge_cases(w, h, count=1233, max_iter=1234, min_iter=20, samples=24):
+    """The pixel-edge inputs both suites use -> (base, {"fallback": [(box, [samples])], "on_min": [box], "below_min":
+    [box], "on_max": [box]}): the neck sample of the given escape count, pixel_edge_canvases for its orbit, and for each
+    fallback canvas the base sample followed by pixel_edge_samples' real ones."""
+    base = with_escape_count(count, "neck")
+    rs, is_, _ = mandel_orbit(*base, max_iter)
+    canvases = pixel_edge_canvases((rs, is_), w, h)
+    canvases["fallback"] = [(box, [base] + pixel_edge_samples(box, w, samples, max_iter, min_iter))
+                            for box in canvases["fallback"]]
+    return base, canvases
