@@ -439,8 +439,8 @@ const std::vector<Flag> &flag_table() {
       // tolerance of its return test (hexfloats accepted)
       {"--period-palette", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
-         s.n_period_stops = parse_palette(t, s.period_stops);
-         if (s.period_palette() && s.period_stops[s.n_period_stops - 1].k >= CB_PERIOD_MAX_ENTRIES) s.n_period_stops = 0;
+         s.period_stops.n = parse_palette(t, s.period_stops.at);
+         if (s.period_palette() && s.period_stops.at[s.period_stops.n - 1].k >= CB_PERIOD_MAX_ENTRIES) s.period_stops.n = 0;
          return s.period_palette() ? kOk
                                    : "Invalid period palette (want K:RRGGBB,... K ascending from 0 to 1023, at most 16 stops)";
        }},
@@ -456,7 +456,7 @@ const std::vector<Flag> &flag_table() {
       // --power, --julia or --burning-ship (include/cudabrot_amd.h, "Palette render")
       {"--palette", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
-         s.n_palette_stops = parse_palette(t, s.palette_stops);
+         s.palette_stops.n = parse_palette(t, s.palette_stops.at);
          return s.palette() ? kOk : "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops)";
        }},
       // --formula NAME: another step of the quadratic family, on the projected path with any plane, --julia or --palette
@@ -490,7 +490,7 @@ const std::vector<Flag> &flag_table() {
       // whatever N is, -o receives one 16-bit PPM (include/cudabrot_amd.h, "Depth-palette render")
       {"--depth-palette", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
-         s.n_depth_palette_stops = parse_palette(t, s.depth_palette_stops);
+         s.depth_palette_stops.n = parse_palette(t, s.depth_palette_stops.at);
          return s.depth_palette() ? kOk : "Invalid depth palette (want K:RRGGBB,... K ascending, at most 16 stops)";
        }},
       // --sweep X,Y:DEG0:DEG1:F: F frames of the plane as it stands after every --plane / --rotate / --project, rotated in

@@ -32,6 +32,25 @@ struct DensityFilter {
   uint64_t n0 = 1;
 };
 
+// A list of colour stops, K:RRGGBB[,K:RRGGBB...], as --palette, --depth-palette and --period-palette give one; none: no flag.
+struct Stops {
+  int n = 0;
+  cb_palette_stop at[CB_PALETTE_MAX_STOPS] = {};
+  bool given() const { return n > 0; }
+};
+
+// What a run renders into and writes, by the flag that decides it (Settings::output): the renderer's image of each is
+// cli_main.cpp's table.
+enum class Sink { kGray, kChannels, kDepth, kSweep, kPalette, kDepthPalette, kPeriodPalette };
+// The four shapes of the output: one gray plane, one PGM; --channel planes, one PGM each; N planes as N PGMs back to back
+// in one file; three planes as one PPM.
+enum class Shape { kGray, kChannels, kStack, kColor };
+struct Output {
+  Sink sink;
+  Shape shape;
+  int planes;  // of counters, each of the canvas's size
+};
+
 struct Settings {
   int device = 0;                                   // -d
   const char *output_image = "output.pgm";          // -o   (cudabrot.cu:26,764)
@@ -73,9 +92,8 @@ struct Settings {
   double julia_c[2] = {0.0, 0.0};
   // --palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a palette render (cb_palette_from_stops,
   // cb_renderer_set_palette); makes the run a projected one as --power does
-  int n_palette_stops = 0;
-  cb_palette_stop palette_stops[CB_PALETTE_MAX_STOPS] = {};
-  bool palette() const { return n_palette_stops > 0; }
+  Stops palette_stops;
+  bool palette() const { return palette_stops.given(); }
   // --formula NAME (extension): a formula step, CB_KERNEL_FORMULA(code); makes the run a projected one as --power does
   int formula = 0;
   const char *formula_name = nullptr;
@@ -91,9 +109,8 @@ struct Settings {
   // --depth-palette K:RRGGBB[,K:RRGGBB...] (extension): the colour stops of a depth-palette render, K a slice index
   // (cb_palette_from_stops with --depth's N entries, cb_renderer_set_depth_palette); needs --depth, whose N planes become
   // three
-  int n_depth_palette_stops = 0;
-  cb_palette_stop depth_palette_stops[CB_PALETTE_MAX_STOPS] = {};
-  bool depth_palette() const { return n_depth_palette_stops > 0; }
+  Stops depth_palette_stops;
+  bool depth_palette() const { return depth_palette_stops.given(); }
   // --sweep X,Y:DEG0:DEG1:F (extension): F frames of the plane rotated in (X, Y), one orbit pass (cb_frames_from_sweep,
   // cb_renderer_set_frames); makes the run a projected one as --depth does, with a last refusal row of its own.  The base
   // is `projection` as it stands when the flags have been read: the sweep is applied last, at most once.
@@ -111,11 +128,10 @@ struct Settings {
   // CB_PERIOD_MAX_ENTRIES - 1 (cb_palette_from_stops with the largest K + 1 entries, at least 2,
   // cb_renderer_set_period_palette); needs --bounded, whose one plane becomes three.  --period-eps X: the tolerance of the
   // return test, which needs --period-palette
-  int n_period_stops = 0;
-  cb_palette_stop period_stops[CB_PALETTE_MAX_STOPS] = {};
-  bool period_palette() const { return n_period_stops > 0; }
+  Stops period_stops;
+  bool period_palette() const { return period_stops.given(); }
   uint32_t period_entries() const {  // the largest K given + 1, and at least 2
-    const int last = n_period_stops > 0 ? period_stops[n_period_stops - 1].k : 0;
+    const int last = period_palette() ? period_stops.at[period_stops.n - 1].k : 0;
     return last < 1 ? 2u : (uint32_t) last + 1u;
   }
   bool period_eps_given = false;
@@ -131,6 +147,18 @@ struct Settings {
   // falls as the count rises (include/cudabrot_amd.h, "Density filter"; cb_renderer_set_density_filter); radius 0, the
   // default, is off
   DensityFilter density;
+  // The one place that says what the flags above make of the output: a palette of any kind turns its render's planes into
+  // three and the file into a PPM, so it goes before the render it colours; --depth and --sweep stack their planes;
+  // --channel has an image per plane.  The refusal table lets no two of the renders meet.
+  Output output() const {
+    if (depth_palette()) return {Sink::kDepthPalette, Shape::kColor, 3};
+    if (period_palette()) return {Sink::kPeriodPalette, Shape::kColor, 3};
+    if (palette()) return {Sink::kPalette, Shape::kColor, 3};
+    if (depth_given) return {Sink::kDepth, Shape::kStack, depth.slices};
+    if (sweep_given) return {Sink::kSweep, Shape::kStack, sweep.frames};
+    if (n_channels > 0) return {Sink::kChannels, Shape::kChannels, n_channels};
+    return {Sink::kGray, Shape::kGray, 1};
+  }
 };
 
 // argv -> Settings, with the reference's messages (cudabrot.cu:625-754).  A command line that is refused -- --help, an

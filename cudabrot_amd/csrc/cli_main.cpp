@@ -39,6 +39,29 @@ using cb::Settings;
 
 volatile sig_atomic_t g_quit_requested = 0;
 
+// The renderer's image of all the planes of a sink at once, by cb::Sink; none: plane by plane, cb_renderer_grayscale_plane.
+using ImageCall = int (*)(cb_renderer *, double, int, uint16_t *, uint64_t *, double *);
+constexpr ImageCall kImageOf[] = {
+    nullptr,                           // Sink::kGray
+    nullptr,                           // Sink::kChannels
+    cb_renderer_depth_image,           // Sink::kDepth
+    cb_renderer_frames_image,          // Sink::kSweep
+    cb_renderer_palette_image,         // Sink::kPalette
+    cb_renderer_depth_palette_image,   // Sink::kDepthPalette
+    cb_renderer_period_palette_image,  // Sink::kPeriodPalette
+};
+static_assert(sizeof(kImageOf) / sizeof(kImageOf[0]) == (size_t) cb::Sink::kPeriodPalette + 1, "one row per sink");
+
+// The opening of a --stats line that states a list of stops, {"KEY": [[k, "rrggbb"], ...] -- the caller closes the object.
+void print_stops(const char *key, const cb::Stops &stops) {
+  fprintf(stderr, "{\"%s\": [", key);
+  for (int j = 0; j < stops.n; ++j) {
+    const cb_palette_stop &stop = stops.at[j];
+    fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
+  }
+  fprintf(stderr, "]");
+}
+
 // ---- the run -------------------------------------------------------------------------------------
 
 double wall_seconds() {  // cudabrot.cu:122-129
@@ -52,7 +75,7 @@ double wall_seconds() {  // cudabrot.cu:122-129
 
 class Run {
  public:
-  explicit Run(const Settings &s) : cfg_(s) {}
+  explicit Run(const Settings &s) : cfg_(s), out_(s.output()) {}
   ~Run() { release(); }
 
   int execute() {
@@ -89,12 +112,8 @@ class Run {
                 cfg_.aim.dilate);
       }
       if (cfg_.period_palette()) {  // and the colours of their periods, with the tolerance of the return test
-        fprintf(stderr, "{\"period_palette\": [");
-        for (int j = 0; j < cfg_.n_period_stops; ++j) {
-          const cb_palette_stop &stop = cfg_.period_stops[j];
-          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
-        }
-        fprintf(stderr, "], \"period_eps\": \"%a\"}\n", cfg_.period_eps);
+        print_stops("period_palette", cfg_.period_stops);
+        fprintf(stderr, ", \"period_eps\": \"%a\"}\n", cfg_.period_eps);
       }
       if (cfg_.depth_given) {  // and the third row with its window
         const cb_depth &d = cfg_.depth;
@@ -110,20 +129,12 @@ class Run {
         fprintf(stderr, "]}}\n");
       }
       if (cfg_.depth_palette()) {  // and the colours of its slices
-        fprintf(stderr, "{\"depth_palette\": [");
-        for (int j = 0; j < cfg_.n_depth_palette_stops; ++j) {
-          const cb_palette_stop &stop = cfg_.depth_palette_stops[j];
-          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
-        }
-        fprintf(stderr, "]}\n");
+        print_stops("depth_palette", cfg_.depth_palette_stops);
+        fprintf(stderr, "}\n");
       }
       if (cfg_.palette()) {  // and the colours
-        fprintf(stderr, "{\"palette\": [");
-        for (int j = 0; j < cfg_.n_palette_stops; ++j) {
-          const cb_palette_stop &stop = cfg_.palette_stops[j];
-          fprintf(stderr, "%s[%d, \"%02x%02x%02x\"]", j ? ", " : "", stop.k, stop.r, stop.g, stop.b);
-        }
-        fprintf(stderr, "]}\n");
+        print_stops("palette", cfg_.palette_stops);
+        fprintf(stderr, "}\n");
       }
       fflush(stderr);
     }
@@ -142,17 +153,9 @@ class Run {
     render();
     save_inprogress();
     save_rng_state();
-    if (cfg_.n_channels > 0) {
+    if (out_.shape == cb::Shape::kChannels) {
       save_channels();
       if (cfg_.color_file) save_color();
-    } else if (cfg_.palette() || cfg_.depth_palette() || cfg_.period_palette()) {
-      printf("Saving image.\n");
-      report_save(cb_save_ppm_be(cfg_.output_image, palette_rgb_be_.data(), cfg_.canvas.w, cfg_.canvas.h));
-      printf("Done! Output image saved: %s\n", cfg_.output_image);
-    } else if (cfg_.depth_given || cfg_.sweep_given) {
-      printf("Saving image.\n");
-      report_save(save_plane_images(cfg_.output_image));
-      printf("Done! Output image saved: %s\n", cfg_.output_image);
     } else {
       printf("Saving image.\n");
       save_image(cfg_.output_image);
@@ -164,28 +167,24 @@ class Run {
 
  private:
   Settings cfg_;
+  cb::Output out_;  // what the flags make of the output: asked for the planes, the image and how it is saved
   cb_renderer *renderer_ = nullptr;      // rank 0: loads, receives the reduced histogram, tone-maps, saves
   // --gpus N: ranks 1..N-1, one per further device, subsequences [r T, (r+1) T) of the
   // same seed; their histograms are summed onto rank 0 once, after the pass loop (cb_renderers_reduce)
   std::vector<cb_renderer *> peers_;
   cb_pixel *counts_ = nullptr;   // host mirror of the histogram (only with -s or --tonemap host)
-  uint16_t *gray_ = nullptr;
+  uint16_t *gray_ = nullptr;  // the image: of one plane at a time (one gray plane, --channel), else of all the planes
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
   std::vector<cb_pixel> filtered_;  // --density-filter with --tonemap host: the counters the last image was mapped from
-  std::vector<uint16_t> palette_rgb_be_;  // --palette, --depth-palette, --period-palette: the PPM body
-  std::vector<uint16_t> planes_gray_be_;  // --depth, --sweep: the bodies of the N PGMs, slice or frame 0 first
   std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
 
   uint64_t pixel_count() const { return (uint64_t) cfg_.canvas.w * (uint64_t) cfg_.canvas.h; }
-  uint64_t planes() const {
-    if (cfg_.depth_palette() || cfg_.period_palette()) return 3u;
-    if (cfg_.depth_given) return (uint64_t) cfg_.depth.slices;
-    if (cfg_.sweep_given) return (uint64_t) cfg_.sweep.frames;
-    return cfg_.palette() ? 3u : (cfg_.n_channels > 0 ? (uint64_t) cfg_.n_channels : 1u);
-  }
+  uint64_t planes() const { return (uint64_t) out_.planes; }
+  // the planes of one image: --channel's and the one gray plane are mapped and saved one at a time
+  uint64_t image_planes() const { return kImageOf[(int) out_.sink] ? planes() : 1u; }
   uint64_t buffer_bytes() const { return planes() * pixel_count() * sizeof(cb_pixel); }
 
   void release() {  // cudabrot.cu:112-119
@@ -212,6 +211,13 @@ class Run {
     die();
   }
 #define CB_CHECK(call) check((call), #call, __LINE__)
+
+  // The device table of a list of stops: `entries` colours interpolated between them.
+  std::vector<uint32_t> table_of(const cb::Stops &stops, size_t entries) {
+    std::vector<uint32_t> lut(entries);
+    CB_CHECK(cb_palette_from_stops(stops.at, stops.n, lut.data(), (uint32_t) lut.size()));
+    return lut;
+  }
 
   void setup() {  // cudabrot.cu:153-189
     float gpu_mib = (float) (buffer_bytes() + cb_rng_state_bytes(CB_DEFAULT_THREADS));
@@ -244,8 +250,7 @@ class Run {
       CB_CHECK(cb_renderer_set_projection(renderer_, cfg_.projection));
     }
     if (cfg_.depth_palette()) {  // after the plane and c: the table of the stops, one entry per slice
-      std::vector<uint32_t> lut((size_t) cfg_.depth.slices);
-      CB_CHECK(cb_palette_from_stops(cfg_.depth_palette_stops, cfg_.n_depth_palette_stops, lut.data(), (uint32_t) lut.size()));
+      const std::vector<uint32_t> lut = table_of(cfg_.depth_palette_stops, (size_t) cfg_.depth.slices);
       CB_CHECK(cb_renderer_set_depth_palette(renderer_, &cfg_.depth, lut.data(), (uint32_t) lut.size()));
     } else if (cfg_.depth_given) {
       CB_CHECK(cb_renderer_set_depth(renderer_, &cfg_.depth));  // after the plane and c
@@ -253,8 +258,7 @@ class Run {
     if (cfg_.sweep_given) CB_CHECK(cb_renderer_set_frames(renderer_, frames_.data(), cfg_.sweep.frames));  // likewise
     if (cfg_.phoenix) CB_CHECK(cb_renderer_set_phoenix(renderer_, cfg_.phoenix_p));  // likewise
     if (cfg_.period_palette()) {  // likewise: the table of the stops, one entry per period up to the largest given
-      std::vector<uint32_t> lut((size_t) cfg_.period_entries());
-      CB_CHECK(cb_palette_from_stops(cfg_.period_stops, cfg_.n_period_stops, lut.data(), (uint32_t) lut.size()));
+      const std::vector<uint32_t> lut = table_of(cfg_.period_stops, (size_t) cfg_.period_entries());
       CB_CHECK(cb_renderer_set_period_palette(renderer_, lut.data(), (uint32_t) lut.size(), cfg_.period_eps));
     } else if (cfg_.bounded) {
       CB_CHECK(cb_renderer_set_bounded(renderer_));  // likewise
@@ -264,15 +268,14 @@ class Run {
       CB_CHECK(cb_renderer_set_density_filter(renderer_, cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0));
     }
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
-      std::vector<uint32_t> lut((size_t) cfg_.iterations.max_escape_iterations);
-      CB_CHECK(cb_palette_from_stops(cfg_.palette_stops, cfg_.n_palette_stops, lut.data(), (uint32_t) lut.size()));
+      const std::vector<uint32_t> lut = table_of(cfg_.palette_stops, (size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_renderer_set_palette(renderer_, lut.data(), (uint32_t) lut.size()));
     }
     if (need_host_counts()) {
       counts_ = (cb_pixel *) calloc(1, buffer_bytes());
       if (!counts_) die();
     }
-    gray_ = (uint16_t *) calloc(pixel_count(), sizeof(uint16_t));
+    gray_ = (uint16_t *) calloc(image_planes() * pixel_count(), sizeof(uint16_t));
     if (!gray_) {
       printf("Failed allocating grayscale image.\n");
       die();
@@ -361,27 +364,27 @@ class Run {
     if (cfg_.gpus > 1) {
       done = render_sharded(variant, by_clock, t0);
     } else {
-    while (!g_quit_requested) {
-      if (!by_clock) {
-        if (done >= cfg_.fixed_passes) break;
-        next = cfg_.fixed_passes - done;
-        if (next > 256) next = 256;
+      while (!g_quit_requested) {
+        if (!by_clock) {
+          if (done >= cfg_.fixed_passes) break;
+          next = cfg_.fixed_passes - done;
+          if (next > 256) next = 256;
+        }
+        CB_CHECK(cb_renderer_render_passes(renderer_, (uint32_t) next, variant));
+        done += next;
+        if (!by_clock) continue;
+        const double elapsed = wall_seconds() - t0;
+        if (cfg_.seconds_to_run >= 0 && elapsed > cfg_.seconds_to_run) break;
+        double budget = launch_seconds;
+        if (cfg_.seconds_to_run >= 0 && cfg_.seconds_to_run - elapsed < budget) {
+          budget = cfg_.seconds_to_run - elapsed;
+        }
+        const double per_pass = elapsed / (double) done;
+        next = per_pass > 0 ? (long) (budget / per_pass) : next * 2;
+        if (next < 1) next = 1;
+        if (next > 4096) next = 4096;
+        if (next > 128) next -= next % 128;  // whole launches of 128 passes (cb_renderer's): a short launch drains badly
       }
-      CB_CHECK(cb_renderer_render_passes(renderer_, (uint32_t) next, variant));
-      done += next;
-      if (!by_clock) continue;
-      const double elapsed = wall_seconds() - t0;
-      if (cfg_.seconds_to_run >= 0 && elapsed > cfg_.seconds_to_run) break;
-      double budget = launch_seconds;
-      if (cfg_.seconds_to_run >= 0 && cfg_.seconds_to_run - elapsed < budget) {
-        budget = cfg_.seconds_to_run - elapsed;
-      }
-      const double per_pass = elapsed / (double) done;
-      next = per_pass > 0 ? (long) (budget / per_pass) : next * 2;
-      if (next < 1) next = 1;
-      if (next > 4096) next = 4096;
-      if (next > 128) next -= next % 128;  // whole launches of 128 passes (cb_renderer's): a short launch drains badly
-    }
     }
     passes_this_run_ = (uint64_t) done;  // per rank: what the generators have consumed
     done *= cfg_.gpus;                   // reference-sized passes over all ranks
@@ -397,13 +400,7 @@ class Run {
     }
     printf("%ld Buddhabrot passes took %f seconds.\n", done, wall_seconds() - t0);
     if (cfg_.print_stats) print_stats();
-    if (cfg_.palette() || cfg_.depth_palette() || cfg_.period_palette()) {
-      palette_image();
-    } else if (cfg_.depth_given || cfg_.sweep_given) {
-      planes_image();
-    } else if (cfg_.n_channels == 0) {
-      tone_map(0);
-    }
+    if (out_.shape != cb::Shape::kChannels) make_image(0);  // (--channel: plane by plane, where each is saved)
   }
 
   // --focus: the probe and the cell list, before the clock of the pass loop starts.  The probe runs on generators of its
@@ -589,60 +586,37 @@ class Run {
            (unsigned long) lit, (unsigned long) clipped);
   }
 
-  void tone_map(int plane) {
+  // The image of the run into gray_: of `plane` alone where the sink has an image per plane, else of all its planes at once,
+  // as one w x N*h image against their common maximum -- on the device (only the 16-bit image crosses to the host), or with
+  // --tonemap host by the reference's host loop over the same rows; what is saved is the same bytes.  The loop's values are
+  // the host's: one plane keeps them for cb_save_image (and for --color's compose); the planes of a stack are swapped into
+  // the big-endian values the device hands over; the three planes of a colour image are interleaved into the PPM body first.
+  void make_image(int plane) {
     uint64_t max = 0;
     double scale = 0.0;
+    const ImageCall image = kImageOf[(int) out_.sink];
+    const bool color = out_.shape == cb::Shape::kColor;
+    const uint64_t values = image_planes() * pixel_count();
+    const int rows = (int) image_planes() * cfg_.canvas.h;
     const cb_pixel *hist = counts_ ? counts_ + (uint64_t) plane * pixel_count() : nullptr;
     if (cfg_.host_tonemap) {
-      host_tone_map(hist, cfg_.canvas.h, 1, gray_, &max, &scale);
-      gray_is_big_endian_ = false;
-    } else {  // tone map on the device: only the 16-bit image crosses to the host
-      CB_CHECK(cb_renderer_grayscale_plane(renderer_, plane, cfg_.gamma_correction, cfg_.tone_mode, gray_,
-                                           &max, &scale));
-      gray_is_big_endian_ = true;
-    }
-    print_exposure(max, scale, hist, cfg_.canvas.h);
-  }
-
-  // --palette, --depth-palette, --period-palette: the three planes tone-mapped against their common maximum, as one
-  // w x 3h image, and interleaved into the PPM body -- on the device, or with --tonemap host by the reference's host loop;
-  // the bytes are the same.
-  void palette_image() {
-    uint64_t max = 0;
-    double scale = 0.0;
-    palette_rgb_be_.resize(3 * pixel_count());
-    if (cfg_.host_tonemap) {
-      std::vector<uint16_t> planar(3 * pixel_count());
-      host_tone_map(counts_, 3 * cfg_.canvas.h, 3, planar.data(), &max, &scale);
-      for (uint64_t i = 0; i < pixel_count(); ++i) {
-        for (uint64_t j = 0; j < 3; ++j) {
-          const uint16_t v = planar[j * pixel_count() + i];
-          palette_rgb_be_[3 * i + j] = (uint16_t) ((v << 8) | (v >> 8));
+      host_tone_map(hist, rows, color ? 3 : 1, gray_, &max, &scale);
+      if (color) {
+        const std::vector<uint16_t> planar(gray_, gray_ + values);
+        for (uint64_t i = 0; i < pixel_count(); ++i) {
+          for (uint64_t j = 0; j < 3; ++j) gray_[3 * i + j] = planar[j * pixel_count() + i];
         }
       }
+      if (image) {  // all planes make one image: the device's byte order
+        for (uint64_t i = 0; i < values; ++i) gray_[i] = (uint16_t) ((gray_[i] << 8) | (gray_[i] >> 8));
+      }
+    } else if (image) {
+      CB_CHECK(image(renderer_, cfg_.gamma_correction, cfg_.tone_mode, gray_, &max, &scale));
     } else {
-      CB_CHECK((cfg_.depth_palette()    ? cb_renderer_depth_palette_image
-                : cfg_.period_palette() ? cb_renderer_period_palette_image
-                                        : cb_renderer_palette_image)(
-          renderer_, cfg_.gamma_correction, cfg_.tone_mode, palette_rgb_be_.data(), &max, &scale));
+      CB_CHECK(cb_renderer_grayscale_plane(renderer_, plane, cfg_.gamma_correction, cfg_.tone_mode, gray_, &max, &scale));
     }
-    print_exposure(max, scale, counts_, 3 * cfg_.canvas.h);
-  }
-
-  // --depth, --sweep: the N planes tone-mapped against their common maximum, as one w x N*h image -- on the device, or
-  // with --tonemap host by the reference's host loop; the bytes are the same.
-  void planes_image() {
-    uint64_t max = 0;
-    double scale = 0.0;
-    planes_gray_be_.resize(planes() * pixel_count());
-    if (cfg_.host_tonemap) {
-      host_tone_map(counts_, (int) planes() * cfg_.canvas.h, 1, planes_gray_be_.data(), &max, &scale);
-      for (uint16_t &v : planes_gray_be_) v = (uint16_t) ((v << 8) | (v >> 8));
-    } else {
-      CB_CHECK((cfg_.sweep_given ? cb_renderer_frames_image : cb_renderer_depth_image)(
-          renderer_, cfg_.gamma_correction, cfg_.tone_mode, planes_gray_be_.data(), &max, &scale));
-    }
-    print_exposure(max, scale, counts_, (int) planes() * cfg_.canvas.h);
+    gray_is_big_endian_ = image || !cfg_.host_tonemap;
+    print_exposure(max, scale, hist, rows);
   }
 
   // --depth, --sweep: N binary PGMs back to back in one file (Netpbm's format allows a sequence of images), each
@@ -654,7 +628,7 @@ class Run {
     for (uint64_t s = 0; s < planes() && rc == 0; ++s) {
       if (fprintf(f, "P5\n%d %d\n65535\n", cfg_.canvas.w, cfg_.canvas.h) <= 0) {
         rc = 2;
-      } else if (fwrite(planes_gray_be_.data() + s * pixel_count(), sizeof(uint16_t), pixel_count(), f) != pixel_count()) {
+      } else if (fwrite(gray_ + s * pixel_count(), sizeof(uint16_t), pixel_count(), f) != pixel_count()) {
         rc = 3;
       }
     }
@@ -667,7 +641,7 @@ class Run {
     for (int j = 0; j < cfg_.n_channels; ++j) {
       printf("Channel %d: %d max iterations, %d min iterations.\n", j,
              cfg_.channel_window[j].max_escape_iterations, cfg_.channel_window[j].min_escape_iterations);
-      tone_map(j);
+      make_image(j);
       if (cfg_.color_file && cfg_.host_tonemap) {  // before save_image swaps gray_ in place
         color_grays_.resize(3 * pixel_count());
         memcpy(color_grays_.data() + (uint64_t) j * pixel_count(), gray_, pixel_count() * sizeof(uint16_t));
@@ -750,9 +724,14 @@ class Run {
             (unsigned long long) c.rt_wave_life_sum);
   }
 
-  void save_image(const char *path) {  // cudabrot.cu:548-577: failures are reported and the run still ends with 0
-    report_save(gray_is_big_endian_ ? cb_save_image_be(path, gray_, cfg_.canvas.w, cfg_.canvas.h)
-                                    : cb_save_image(path, gray_, cfg_.canvas.w, cfg_.canvas.h));
+  // The image make_image left, as the file of its shape (cudabrot.cu:548-577: failures are reported and the run still ends
+  // with 0).
+  void save_image(const char *path) {
+    const int w = cfg_.canvas.w, h = cfg_.canvas.h;
+    report_save(out_.shape == cb::Shape::kColor   ? cb_save_ppm_be(path, gray_, w, h)
+                : out_.shape == cb::Shape::kStack ? save_plane_images(path)
+                : gray_is_big_endian_             ? cb_save_image_be(path, gray_, w, h)
+                                                  : cb_save_image(path, gray_, w, h));
   }
 
   static void report_save(int rc) {

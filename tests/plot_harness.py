@@ -8,15 +8,14 @@ imported as device_launches and shared with every other GPU suite and with tools
 picks the entry point and its arguments.  SAME, SQUARE, omp_threads, planar_states, run and gpu_run are re-exported from there for the plotted suites."""
 
 import collections
-import os
 
 import numpy as np
 import pytest
 
 import plot_reference as plot
+from cli_harness import exe  # noqa: F401 (the binary's fixture, re-exported for the GPU suites)
 from device_launches import SAME, SQUARE, Launches, gpu_run, omp_threads, planar_states, run  # noqa: F401 (re-exported)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 assert SAME == plot.COUNTER_NAMES
 INVALID = 1  # hipErrorInvalidValue
 NOT_INCREMENTS = [k for k in SAME if k != "increments"]
@@ -33,14 +32,6 @@ IRRATIONAL_ROW = plot.rotate(plot.rotate(plot.rotate(plot.IDENTITY, "zr", "zi", 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
     return plot.load(tmp_path_factory.mktemp("plot_ref"))
-
-
-@pytest.fixture(scope="module")
-def exe():
-    path = os.path.join(ROOT, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
 
 
 def variant_of(cb, base, degree=2, ship=False, formula=0):

@@ -2,15 +2,12 @@
 extension flags (tests/test_bounded_cli.py): message, usage, exit 0; nothing is rendered.  What the flags mean is read from
 the `"projection"`, `"julia"`, `"bounded"`, ... and `"aim"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 AIM = ["--aim"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 # the row's partners, in its order
 OTHERS = (
     (["--focus"], "--aim does not combine with --focus."),
@@ -43,7 +40,7 @@ OTHERS = (
     (["--burning-ship", "--depth", "cr:-2:0.5:4"], "--aim does not combine with --depth."),
 )
 FORMS = (AIM, ["--aim-level", "6"], ["--aim-probe", "8"], ["--aim-dilate", "0"])  # each value flag turns --aim on
-REFUSED = [(AIM + o, line) for o, line in OTHERS] + [(o + AIM, line) for o, line in OTHERS]
+REFUSED = both_orders(AIM, OTHERS)
 VALUE_FLAGS = [(form + o, line) for form in FORMS[1:] for o, line in OTHERS[:3]]
 # What the flag combines with keeps its own refusals, in both orders.
 OLDER_ROWS = (
@@ -53,20 +50,13 @@ OLDER_ROWS = (
     (["--project", "1,0,0,0:0,1,0,0", "--plane", "zr,cr"], "--project does not combine with --plane or --rotate."),
     (["--period-eps", "0"], "--period-eps needs --period-palette."),
 )
-BEHIND = [(AIM + o, line) for o, line in OLDER_ROWS] + [(o + AIM, line) for o, line in OLDER_ROWS]
+BEHIND = both_orders(AIM, OLDER_ROWS)
 WITH_STATS = [(AIM + ["--stats"] + o, line) for o, line in OTHERS]
 
 
 @pytest.mark.parametrize("args,first_line", REFUSED + VALUE_FLAGS + BEHIND + WITH_STATS)
 def test_aim_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 @pytest.mark.parametrize("args,first_line", [
@@ -93,29 +83,6 @@ def test_usage_does_not_list_the_flag(exe):
     assert "--aim" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
-
-
-IDENTITY = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-
-
 @pytest.mark.parametrize("form,aim", [
     (AIM, {"level": 8, "probe": 64, "dilate": 1}),
     (["--aim-level", "6"], {"level": 6, "probe": 64, "dilate": 1}),
@@ -128,10 +95,6 @@ def test_alone_it_is_the_identity_projected_render_aimed(exe, tmp_path, form, ai
     matrix, said = stated(exe, tmp_path, *form)
     assert matrix == IDENTITY
     assert said == {"aim": aim}
-
-
-RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s", "buffer.bin",
-             "--rng-state", "side.rng", "--state-format", "raw"]
 
 
 @pytest.mark.parametrize("first", ["aim", "others"])
@@ -152,11 +115,11 @@ RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tone
      [0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]),
 ])
 def test_it_combines_with_the_planes_the_steps_julia_bounded_and_the_run_flags(exe, tmp_path, others, keys, matrix, first):
-    args = (AIM + others if first == "aim" else others + AIM) + RUN_FLAGS
+    args = (AIM + others if first == "aim" else others + AIM) + RUN_FLAGS + ["--state-format", "raw"]
     got, said = stated(exe, tmp_path, *args)
     assert got == matrix and list(said) == keys and said["aim"] == {"level": 8, "probe": 64, "dilate": 1}
 
 
 def test_without_the_flag_no_aim_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--bounded", cwd=tmp_path)
+    r = run(exe, *SMALL, "--bounded", cwd=tmp_path)
     assert "aim" not in r.stderr and "projection" in r.stderr.split("\n")[0]

@@ -2,15 +2,12 @@
 other extension flags (tests/test_phoenix_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is read
 from the `"projection"`, `"julia"`, ... and `"bounded"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BOUNDED = ["--bounded"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 # the row's partners, in its order
 OTHERS = (
     (["--anti"], "--bounded does not combine with --anti."),
@@ -36,7 +33,7 @@ OTHERS = (
     (["--formula", "tricorn", "--gpus", "2"], "--bounded does not combine with --gpus above 1."),
     (["--burning-ship", "--palette", "0:ffffff"], "--bounded does not combine with --palette."),
 )
-REFUSED = [(BOUNDED + o, line) for o, line in OTHERS] + [(o + BOUNDED, line) for o, line in OTHERS]
+REFUSED = both_orders(BOUNDED, OTHERS)
 # What the flag combines with keeps its own refusals, in both orders.
 OLDER_ROWS = (
     (["--formula", "tricorn", "--power", "3"], "--formula does not combine with --power."),
@@ -44,20 +41,13 @@ OLDER_ROWS = (
     (["--power", "3", "--burning-ship"], "--power does not combine with --burning-ship."),
     (["--project", "1,0,0,0:0,1,0,0", "--plane", "zr,cr"], "--project does not combine with --plane or --rotate."),
 )
-BEHIND = [(BOUNDED + o, line) for o, line in OLDER_ROWS] + [(o + BOUNDED, line) for o, line in OLDER_ROWS]
+BEHIND = both_orders(BOUNDED, OLDER_ROWS)
 WITH_STATS = [(BOUNDED + ["--stats"] + o, line) for o, line in OTHERS]
 
 
 @pytest.mark.parametrize("args,first_line", REFUSED + BEHIND + WITH_STATS)
 def test_bounded_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_the_flag_takes_no_value(exe, tmp_path):
@@ -70,39 +60,15 @@ def test_usage_does_not_list_the_flag(exe):
     assert "--bounded" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
-
-
 def test_the_flag_alone_is_the_identity_plane_with_a_sampled_c(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, "--bounded")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    assert matrix == IDENTITY
     assert said == {"bounded": True}
 
 
 def test_the_stats_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--bounded", cwd=tmp_path)
+    r = run(exe, *SMALL, "--bounded", cwd=tmp_path)
     assert r.stderr.split("\n")[1] == '{"bounded": true}'
-
-
-RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s", "buffer.bin",
-             "--rng-state", "side.rng", "--state-format", "raw"]
 
 
 @pytest.mark.parametrize("first", ["bounded", "others"])
@@ -120,11 +86,11 @@ RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tone
     (["--burning-ship", "--julia", "-1,0"], ["julia", "bounded"], [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]),
 ])
 def test_it_combines_with_the_planes_the_steps_julia_and_the_run_flags(exe, tmp_path, others, keys, matrix, first):
-    args = (BOUNDED + others if first == "bounded" else others + BOUNDED) + RUN_FLAGS
+    args = (BOUNDED + others if first == "bounded" else others + BOUNDED) + RUN_FLAGS + ["--state-format", "raw"]
     got, said = stated(exe, tmp_path, *args)
     assert got == matrix and list(said) == keys and said["bounded"] is True
 
 
 def test_without_the_flag_no_bounded_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--julia", "0.3,0", cwd=tmp_path)
+    r = run(exe, *SMALL, "--julia", "0.3,0", cwd=tmp_path)
     assert "bounded" not in r.stderr and "projection" in r.stderr.split("\n")[0]

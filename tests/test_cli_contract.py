@@ -91,6 +91,26 @@ def test_banner_and_memory_line(exe):
     assert lines[2] == "Approximate memory needed: 134.000 MiB GPU, 160.000 MiB CPU"
 
 
+@pytest.mark.parametrize(
+    "flags,gpu_mib,cpu_mib",
+    [
+        ([], "14.000", "10.000"),                                                       # one gray plane
+        (["--bounded"], "14.000", "10.000"),
+        (["--palette", "0:ffffff"], "30.000", "26.000"),                                # three planes, one PPM
+        (["--depth", "cr:-2:0.5:4"], "38.000", "34.000"),                               # N planes, N PGMs in one file
+        (["--depth", "cr:-2:0.5:4", "--depth-palette", "0:ffffff"], "30.000", "26.000"),  # the N planes become three
+        (["--sweep", "zi,cr:0:90:5"], "46.000", "42.000"),
+        (["--bounded", "--period-palette", "0:ffffff"], "30.000", "26.000"),
+        (["--channel", "9:1:x", "--channel", "9:1:x", "--channel", "9:1:x"], "30.000", "26.000"),  # one image per plane
+    ],
+)
+def test_memory_line_counts_the_planes_of_every_output_shape(exe, flags, gpu_mib, cpu_mib, tmp_path):
+    """planes * w * h * 8 B of counters on both sides, + 262144 * 24 B of generator states on the GPU, + w * h * 2 B of image
+    on the host: at 1024 x 1024, 8 MiB a plane + 6 MiB and + 2 MiB.  Printed before any device is touched."""
+    r = run(exe, "-w", "1024", "-h", "1024", "--passes", "0", "-o", os.devnull, *flags, cwd=tmp_path)
+    assert r.stdout.split("\n")[2] == "Approximate memory needed: %s MiB GPU, %s MiB CPU" % (gpu_mib, cpu_mib)
+
+
 def test_without_a_gpu_the_device_error_line_goes_to_stdout_and_exit_is_one(exe):
     import torch
 

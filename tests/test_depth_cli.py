@@ -2,16 +2,13 @@
 other extension flags (tests/test_formula_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"projection"` and `"depth"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD = ("Invalid depth (want ROW:MIN:MAX[:N], ROW an axis zr, zi, cr, ci or four numbers, MIN < MAX, N from 1 to 256): ")
 DEPTH = ["--depth", "cr:-2:0.5:64"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 OTHERS = (
     (["--palette", "0:ffffff"], "--depth does not combine with --palette."),
     (["--anti"], "--depth does not combine with --anti."),
@@ -24,7 +21,7 @@ OTHERS = (
     (["--gpus", "2"], "--depth does not combine with --gpus above 1."),
     (["--state-format", "raw"], "--depth does not combine with --state-format raw."),
 )
-REFUSED = [(DEPTH + o, line) for o, line in OTHERS] + [(o + DEPTH, line) for o, line in OTHERS]
+REFUSED = both_orders(DEPTH, OTHERS)
 # The flag's row is the table's last: where another flag's row applies to the same command line, that row has spoken
 # already, with its own subject.  Recorded from the table, in both orders.
 EARLIER_ROWS = (
@@ -41,7 +38,7 @@ EARLIER_ROWS = (
     (["--anti", "--channel", "9:1:x"], "--anti does not combine with --channel."),
     (["--color", "c.ppm"], "--color needs exactly 3 --channel images, got 0."),
 )
-BEHIND = [(DEPTH + o, line) for o, line in EARLIER_ROWS] + [(o + DEPTH, line) for o, line in EARLIER_ROWS]
+BEHIND = both_orders(DEPTH, EARLIER_ROWS)
 WITH_STATS = [(DEPTH + ["--stats"] + o, line) for o, line in OTHERS]
 MALFORMED = ["", "cr", "cr:", "cr:-2", "cr:-2:", "cr:-2:0.5:", "cr:-2:0.5:0", "cr:-2:0.5:257", "cr:-2:0.5:-1", "cr:-2:0.5:+4",
              "cr:-2:0.5:4.0", "cr:-2:0.5:4:", "cr:-2:0.5:4:1", "cr:1:1", "cr:1:0", "cr:nan:1", "cr:0:inf", "cr:-inf:0",
@@ -61,39 +58,12 @@ MALFORMED = ["", "cr", "cr:", "cr:-2", "cr:-2:", "cr:-2:0.5:", "cr:-2:0.5:0", "c
     + WITH_STATS,
 )
 def test_depth_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     """The usage text is the reference's and lists no extension flag; README.md and DESIGN.md 4.16 describe this one."""
     assert "--depth" not in run(exe, "--help").stdout
-
-
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
 
 
 def depth_of(said):
@@ -105,7 +75,7 @@ def depth_of(said):
 @pytest.mark.parametrize("axis", ["zr", "zi", "cr", "ci"])
 def test_an_axis_alone_is_the_identity_plane_and_a_unit_row(exe, tmp_path, axis):
     matrix, said = stated(exe, tmp_path, "--depth", axis + ":-0.02:0.02")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    assert matrix == IDENTITY
     row = [1.0 if a == axis else 0.0 for a in ("zr", "zi", "cr", "ci")]
     assert list(said) == ["depth"] and depth_of(said) == (row, -0.02, 0.02, 1)  # N defaults to 1
 
@@ -135,10 +105,8 @@ def test_depth_takes_the_plane_that_is_given_and_rotate_does_not_turn_the_row(ex
 
 
 def test_depth_combines_with_the_steps_julia_and_the_run_flags(exe, tmp_path):
-    run_flags = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s",
-                 "buffer.bin", "--rng-state", "side.rng"]
-    matrix, said = stated(exe, tmp_path, "--depth", "ci:-1:1:8", "--julia", "-0.8,0.156", "--power", "3", *run_flags)
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    matrix, said = stated(exe, tmp_path, "--depth", "ci:-1:1:8", "--julia", "-0.8,0.156", "--power", "3", *RUN_FLAGS)
+    assert matrix == IDENTITY
     assert [float.fromhex(v) for v in said.pop("julia")] == [-0.8, 0.156] and said.pop("power") == 3
     assert depth_of(said) == ([0.0, 0.0, 0.0, 1.0], -1.0, 1.0, 8)
     _, said = stated(exe, tmp_path, "--formula", "buffalo", "--depth", "ci:-1:1:8", "--tonemap", "thresholds")
@@ -148,5 +116,5 @@ def test_depth_combines_with_the_steps_julia_and_the_run_flags(exe, tmp_path):
 
 
 def test_without_the_flag_no_depth_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--plane", "zr,cr", cwd=tmp_path)
+    r = run(exe, *SMALL, "--plane", "zr,cr", cwd=tmp_path)
     assert "depth" not in r.stderr and "projection" in r.stderr.split("\n")[0]

@@ -2,18 +2,15 @@
 the other extension flags (tests/test_depth_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"depth"` and `"depth_palette"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD = "Invalid depth palette (want K:RRGGBB,... K ascending, at most 16 stops): "
 NEEDS = "--depth-palette needs --depth."
 DEPTH = ["--depth", "cr:-2:0.5:64"]
 COLOURS = ["--depth-palette", "0:000030,32:ff8000,63:ffffff"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 # What the binary before this flag answered to DEPTH + these (recorded from it, in both orders of the two): the answer
 # with --depth-palette on the line as well is the same, because --depth's row of the refusal table, and every row before
 # it, speaks before the flag's own.
@@ -49,7 +46,7 @@ WITHOUT_DEPTH = (
     (["--focus", "--anti"], "--focus does not combine with --anti."),
     (["--color", "c.ppm"], "--color needs exactly 3 --channel images, got 0."),
 )
-ALONE = [(COLOURS + o, line) for o, line in WITHOUT_DEPTH] + [(o + COLOURS, line) for o, line in WITHOUT_DEPTH]
+ALONE = both_orders(COLOURS, WITHOUT_DEPTH)
 MALFORMED = ["", "0", "0:", "0:fff", "0:fffffff", "0:gggggg", "0:ffffff,", ",0:ffffff", "0:ffffff,0:000000", "5:ffffff,3:000000",
              "-1:ffffff", "+1:ffffff", "1.0:ffffff", " 0:ffffff", "0:ffffff ", "0: ffffff", "0;ffffff", "0:ffffff;1:000000",
              "0:#ffffff", "0:0xffff", "99999999999:ffffff", ",".join("%d:ffffff" % k for k in range(17))]
@@ -65,14 +62,7 @@ MALFORMED = ["", "0", "0:", "0:fff", "0:fffffff", "0:gggggg", "0:ffffff,", ",0:f
     + ALONE,
 )
 def test_depth_palette_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_is_unchanged_and_does_not_list_the_flag(exe):
@@ -82,53 +72,33 @@ def test_usage_is_unchanged_and_does_not_list_the_flag(exe):
     assert out.rstrip().split("\n")[-1] == "             include in the output image. Defaults to 2.0."
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats (tests/test_depth_cli.py, stated)."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = []
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.append(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
-
-
 def test_the_stops_are_stated_beside_the_depth(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, "--depth", "cr:-2:0.5:256", "--depth-palette", "0:000030,128:Ff8000,255:ffffff")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    assert [list(o) for o in said] == [["depth"], ["depth_palette"]]
-    assert said[0]["depth"]["slices"] == 256
-    assert said[1] == {"depth_palette": [[0, "000030"], [128, "ff8000"], [255, "ffffff"]]}
+    assert matrix == IDENTITY
+    assert list(said) == ["depth", "depth_palette"]
+    assert said["depth"]["slices"] == 256
+    assert said["depth_palette"] == [[0, "000030"], [128, "ff8000"], [255, "ffffff"]]
     # either order of the two flags, one stop, and stops at or above N are taken as --palette takes stops at or above -m
     _, said = stated(exe, tmp_path, "--depth-palette", "7:010203", "--depth", "zi:-1:1:4")
-    assert said[1] == {"depth_palette": [[7, "010203"]]} and said[0]["depth"]["slices"] == 4
+    assert said["depth_palette"] == [[7, "010203"]] and said["depth"]["slices"] == 4
     _, said = stated(exe, tmp_path, "--depth", "zi:-1:1", "--depth-palette", "0:000000,1000:ffffff")
-    assert said[1] == {"depth_palette": [[0, "000000"], [1000, "ffffff"]]} and said[0]["depth"]["slices"] == 1
+    assert said["depth_palette"] == [[0, "000000"], [1000, "ffffff"]] and said["depth"]["slices"] == 1
     # the last one counts
     _, said = stated(exe, tmp_path, *DEPTH, *COLOURS, "--depth-palette", "3:0a0b0c")
-    assert said[1] == {"depth_palette": [[3, "0a0b0c"]]}
+    assert said["depth_palette"] == [[3, "0a0b0c"]]
 
 
 def test_it_combines_with_the_steps_julia_the_plane_and_the_run_flags(exe, tmp_path):
-    run_flags = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s",
-                 "buffer.bin", "--rng-state", "side.rng"]
     matrix, said = stated(exe, tmp_path, *COLOURS, "--depth", "ci:-1:1:8", "--julia", "-0.8,0.156", "--power", "3",
-                          "--plane", "zr,cr", *run_flags)
+                          "--plane", "zr,cr", *RUN_FLAGS)
     assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
-    assert [list(o)[0] for o in said] == ["power", "julia", "depth", "depth_palette"]
+    assert list(said) == ["power", "julia", "depth", "depth_palette"]
     _, said = stated(exe, tmp_path, "--formula", "buffalo", *DEPTH, *COLOURS, "--tonemap", "thresholds")
-    assert [list(o)[0] for o in said] == ["formula", "depth", "depth_palette"]
+    assert list(said) == ["formula", "depth", "depth_palette"]
     _, said = stated(exe, tmp_path, "--burning-ship", *DEPTH, *COLOURS, "--state-format", "native")
-    assert [list(o)[0] for o in said] == ["depth", "depth_palette"]
+    assert list(said) == ["depth", "depth_palette"]
 
 
 def test_without_the_flag_no_depth_palette_line(exe, tmp_path):
     _, said = stated(exe, tmp_path, *DEPTH)
-    assert [list(o) for o in said] == [["depth"]]
+    assert list(said) == ["depth"]

@@ -1,22 +1,10 @@
 """The `cudabrot` binary's --focus flags without a GPU: messages, refusals and exit codes follow the conventions of the
 other extension flags (tests/test_cli_contract.py): message, usage, exit 0; nothing is rendered."""
 
-import os
-import subprocess
-
 import pytest
 
-
-@pytest.fixture(scope="module")
-def exe(repo_root):
-    path = os.path.join(repo_root, "cudabrot")
-    if not os.access(path, os.X_OK):
-        pytest.fail("./cudabrot is not built (run `make` or __graft_entry__.build())")
-    return path
-
-
-def run(exe, *args, **kw):
-    return subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, **kw)
+from cli_harness import refused, run
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 
 @pytest.mark.parametrize(
@@ -44,13 +32,7 @@ def run(exe, *args, **kw):
     ],
 )
 def test_focus_flags_print_message_then_usage_and_exit_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_extension_flags(exe):

@@ -2,12 +2,10 @@
 other extension flags (tests/test_power_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"projection"` and `"formula"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 NAMES = ["tricorn", "celtic", "buffalo", "perpendicular", "celtic-tricorn"]
 
@@ -26,7 +24,7 @@ OTHERS = (
     (["--color", "c.ppm"], "--formula does not combine with --channel."),
     (["--gpus", "2"], "--formula does not combine with --gpus above 1."),
 )
-REFUSED = [(FORMULA + o, line) for o, line in OTHERS] + [(o + FORMULA, line) for o, line in OTHERS]
+REFUSED = both_orders(FORMULA, OTHERS)
 # the flag's own refusal comes before those of --palette, --power, --julia and the projection, which the same command
 # line would trip as well
 PALETTE = ["--palette", "0:ffffff", "-m", "50"]
@@ -55,42 +53,17 @@ WITH_STATS = [(FORMULA + ["--stats"] + o, line) for o, line in OTHERS]
     + WITH_STATS,
 )
 def test_formula_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     assert "--formula" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
-
-
 @pytest.mark.parametrize("name", NAMES)
 def test_each_name_alone_is_the_identity_projection(exe, tmp_path, name):
     matrix, said = stated(exe, tmp_path, "--formula", name)
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    assert matrix == IDENTITY
     assert said == {"formula": name}
 
 
@@ -107,9 +80,8 @@ def test_formula_takes_the_plane_that_is_given(exe, tmp_path, order):
 
 def test_formula_combines_with_julia_palette_and_the_run_flags(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, "--formula", "perpendicular", "--julia", "-0.8,0.156", "--palette",
-                          "0:000030,49:ffffff", "-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap",
-                          "host", "-g", "2.2", "-s", "buffer.bin", "--rng-state", "side.rng")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+                          "0:000030,49:ffffff", *RUN_FLAGS)
+    assert matrix == IDENTITY
     assert [float.fromhex(v) for v in said.pop("julia")] == [-0.8, 0.156]
     assert said == {"formula": "perpendicular", "palette": [[0, "000030"], [49, "ffffff"]]}
 
@@ -119,5 +91,5 @@ def test_the_last_formula_counts(exe, tmp_path):
 
 
 def test_without_the_flag_no_formula_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--plane", "zr,cr", cwd=tmp_path)
+    r = run(exe, *SMALL, "--plane", "zr,cr", cwd=tmp_path)
     assert "formula" not in r.stderr and "projection" in r.stderr.split("\n")[0]

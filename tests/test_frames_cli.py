@@ -2,17 +2,13 @@
 other extension flags (tests/test_depth_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is read
 from the `"projection"` and `"sweep"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-import plot_reference as plot
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD = ("Invalid sweep (want X,Y:DEG0:DEG1:F, two different axes of zr, zi, cr, ci, two finite angles and 1 to 256 frames): ")
 SWEEP = ["--sweep", "zi,cr:0:90:64"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 OTHERS = (
     (["--palette", "0:ffffff"], "--sweep does not combine with --palette."),
     (["--depth", "cr:-2:0.5:4"], "--sweep does not combine with --depth."),
@@ -25,7 +21,7 @@ OTHERS = (
     (["--gpus", "2"], "--sweep does not combine with --gpus above 1."),
     (["--state-format", "raw"], "--sweep does not combine with --state-format raw."),
 )
-REFUSED = [(SWEEP + o, line) for o, line in OTHERS] + [(o + SWEEP, line) for o, line in OTHERS]
+REFUSED = both_orders(SWEEP, OTHERS)
 # The flag's row is the table's last: where an older row applies to the same command line, that row has spoken already,
 # with its own subject.  In both orders.
 EARLIER_ROWS = (
@@ -42,7 +38,7 @@ EARLIER_ROWS = (
     (["--depth", "cr:-2:0.5:4", "--anti"], "--depth does not combine with --anti."),
     (["--depth-palette", "0:ffffff"], "--depth-palette needs --depth."),
 )
-BEHIND = [(SWEEP + o, line) for o, line in EARLIER_ROWS] + [(o + SWEEP, line) for o, line in EARLIER_ROWS]
+BEHIND = both_orders(SWEEP, EARLIER_ROWS)
 WITH_STATS = [(SWEEP + ["--stats"] + o, line) for o, line in OTHERS]
 MALFORMED = ["", "zi", "zi,cr", "zi,cr:", "zi,cr:0", "zi,cr:0:", "zi,cr:0:90", "zi,cr:0:90:", "zi,cr:0:90:0", "zi,cr:0:90:257",
              "zi,cr:0:90:-1", "zi,cr:0:90:+4", "zi,cr:0:90:4.0", "zi,cr:0:90:4:", "zi,cr:0:90:4:1", "zi,zi:0:90:4",
@@ -62,39 +58,12 @@ MALFORMED = ["", "zi", "zi,cr", "zi,cr:", "zi,cr:0", "zi,cr:0:", "zi,cr:0:90", "
     + WITH_STATS,
 )
 def test_sweep_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     """The usage text is the reference's and lists no extension flag; README.md and DESIGN.md 4.18 describe this one."""
     assert "--sweep" not in run(exe, "--help").stdout
-
-
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
 
 
 def sweep_of(said):
@@ -105,7 +74,7 @@ def sweep_of(said):
 
 def test_the_flag_alone_sweeps_the_identity_plane(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, "--sweep", "zi,cr:0:90:4")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]  # the base: frame 0 of a sweep from 0
+    assert matrix == IDENTITY  # the base: frame 0 of a sweep from 0
     assert list(said) == ["sweep"] and sweep_of(said) == (["zi", "cr"], 0.0, 90.0, [0.0, 22.5, 45.0, 67.5])
 
 
@@ -130,10 +99,8 @@ def test_the_sweep_is_applied_last_wherever_it_stands(exe, tmp_path, order):
 
 
 def test_sweep_combines_with_the_steps_julia_and_the_run_flags(exe, tmp_path):
-    run_flags = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s",
-                 "buffer.bin", "--rng-state", "side.rng"]
-    matrix, said = stated(exe, tmp_path, "--sweep", "zi,cr:0:90:8", "--julia", "-0.8,0.156", "--power", "3", *run_flags)
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    matrix, said = stated(exe, tmp_path, "--sweep", "zi,cr:0:90:8", "--julia", "-0.8,0.156", "--power", "3", *RUN_FLAGS)
+    assert matrix == IDENTITY
     assert [float.fromhex(v) for v in said.pop("julia")] == [-0.8, 0.156] and said.pop("power") == 3
     assert len(sweep_of(said)[3]) == 8
     _, said = stated(exe, tmp_path, "--formula", "buffalo", "--sweep", "zi,cr:0:90:8", "--tonemap", "thresholds")
@@ -143,5 +110,5 @@ def test_sweep_combines_with_the_steps_julia_and_the_run_flags(exe, tmp_path):
 
 
 def test_without_the_flag_no_sweep_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--plane", "zr,cr", cwd=tmp_path)
+    r = run(exe, *SMALL, "--plane", "zr,cr", cwd=tmp_path)
     assert "sweep" not in r.stderr and "projection" in r.stderr.split("\n")[0]

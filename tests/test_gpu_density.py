@@ -291,3 +291,21 @@ def test_cli_palette_and_clip_on_filtered_counters(cb, exe, tmp_path):  # noqa: 
     assert bodies["device"] == bodies["host"] and bodies["device"].startswith(b"P6\n64 64\n65535\n")
     assert outs["device"] == outs["host"] and len(outs["device"]) == 3 and outs["device"][1] == LINE
     assert [line.split(":")[0] for line in outs["device"]] == ["Max value", "Density filter", "White value"]
+
+
+def test_cli_depth_planes_and_clip_on_filtered_counters(cb, exe, tmp_path):  # noqa: F811
+    """The stacked shape -- N planes as N PGMs in one file -- is where the host loop's rows, groups of one plane and the
+    byte swap meet: the same bytes and the same three lines from the device and from --tonemap host."""
+    common = ["-m", "300", "-w", "64", "-h", "64", "--passes", "2", "--depth", "cr:-2:0.5:4", "--density-filter", "4:0.5:2",
+              "--white-clip", "2"]
+    bodies, outs = {}, {}
+    for k, more in {"device": [], "host": ["--tonemap", "host"]}.items():
+        r = run(exe, *common, *more, "-o", str(tmp_path / (k + ".pgm")))
+        assert r.returncode == 0, r.stdout + r.stderr
+        bodies[k] = open(tmp_path / (k + ".pgm"), "rb").read()
+        outs[k] = [line for line in r.stdout.split("\n") if line.startswith(("Max value", "Density filter", "White value"))]
+    header, plane = b"P5\n64 64\n65535\n", len(b"P5\n64 64\n65535\n") + 64 * 64 * 2
+    assert bodies["device"] == bodies["host"] and len(bodies["device"]) == 4 * plane
+    assert all(bodies["device"][s * plane:].startswith(header) for s in range(4))
+    assert outs["device"] == outs["host"] and len(outs["device"]) == 3 and outs["device"][1] == LINE
+    assert [line.split(":")[0] for line in outs["device"]] == ["Max value", "Density filter", "White value"]

@@ -2,12 +2,10 @@
 other extension flags (tests/test_power_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"projection"`, `"power"` and `"julia"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import IDENTITY, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD_JULIA = "Invalid julia parameter (want RE,IM, two numbers from -2 to 2): "
 JULIA = ["--julia", "-0.8,0.156"]
@@ -21,7 +19,7 @@ OTHERS = (
     (["--color", "c.ppm"], "--julia does not combine with --channel."),
     (["--gpus", "2"], "--julia does not combine with --gpus above 1."),
 )
-REFUSED = [(JULIA + o, line) for o, line in OTHERS] + [(o + JULIA, line) for o, line in OTHERS]
+REFUSED = both_orders(JULIA, OTHERS)
 WITH_STATS = [(JULIA + ["--stats"] + o, line) for o, line in OTHERS] + [(o + ["--stats"] + JULIA, line) for o, line in OTHERS]
 # the flag's own refusal comes before the projection's, which the same command line would trip as well
 WITH_PLANE = [(["--plane", "zr,zi"] + JULIA + o, line) for o, line in OTHERS] + [
@@ -63,63 +61,46 @@ AFTER_POWER = [
     + AFTER_POWER,
 )
 def test_julia_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     assert "--julia" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on the first lines of stderr under --stats: the matrix, then
-    one JSON object per further line that defines the run.  The run itself goes on to the device (and ends there on a box
-    without one); its outcome is not looked at."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    lines = r.stderr.split("\n")
-    rest = {}
-    for line in lines[1:3]:
-        if line.startswith('{"power"') or line.startswith('{"julia"'):
-            rest.update(json.loads(line))
-    if "julia" in rest:  # "%a" texts -> the doubles
-        rest["julia"] = [float.fromhex(v) for v in rest["julia"]]
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], rest
+def with_c(said):
+    """What was stated, the "%a" texts of c as the doubles."""
+    return dict(said, julia=[float.fromhex(v) for v in said["julia"]])
 
 
 def test_julia_alone_is_the_identity_projection(exe, tmp_path):
-    matrix, rest = stated(exe, tmp_path, "--julia", "-0.8,0.156")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    assert rest == {"julia": [-0.8, 0.156]}
+    matrix, said = stated(exe, tmp_path, "--julia", "-0.8,0.156")
+    assert matrix == IDENTITY
+    assert with_c(said) == {"julia": [-0.8, 0.156]}
 
 
 @pytest.mark.parametrize("text,c", [("-2,2", (-2.0, 2.0)), ("0x1.8p-1,-0x1p-3", (0.75, -0.125)), ("0,-0", (0.0, -0.0)),
                                     ("1e-3,+2.0", (0.001, 2.0))])
 def test_julia_values_are_read_as_strtod_reads_them(exe, tmp_path, text, c):
-    _, rest = stated(exe, tmp_path, "--julia", text)
-    assert [v.hex() for v in rest["julia"]] == [c[0].hex(), c[1].hex()]  # (the sign of a zero included)
+    _, said = stated(exe, tmp_path, "--julia", text)
+    assert [v.hex() for v in with_c(said)["julia"]] == [c[0].hex(), c[1].hex()]  # (the sign of a zero included)
 
 
 @pytest.mark.parametrize("order", ["before", "after"])
 def test_julia_takes_the_plane_and_the_step_that_are_given(exe, tmp_path, order):
     plane = ["--plane", "zr,cr", "--rotate", "zr,cr:90", "--power", "5"]
     args = JULIA + plane if order == "before" else plane + JULIA
-    matrix, rest = stated(exe, tmp_path, *args)
+    matrix, said = stated(exe, tmp_path, *args)
     assert matrix == [0.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0, 0.0]
-    assert rest == {"power": 5, "julia": [-0.8, 0.156]}
-    matrix, rest = stated(exe, tmp_path, "--project", "0.5,0,0,1:0,2,0,0", "--burning-ship", *JULIA)
-    assert matrix == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0] and list(rest) == ["julia"]
+    assert with_c(said) == {"power": 5, "julia": [-0.8, 0.156]}
+    matrix, said = stated(exe, tmp_path, "--project", "0.5,0,0,1:0,2,0,0", "--burning-ship", *JULIA)
+    assert matrix == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0] and list(said) == ["julia"]
 
 
 def test_the_last_julia_counts(exe, tmp_path):
-    assert stated(exe, tmp_path, "--julia", "1,1", "--julia", "0.5,-0.25")[1] == {"julia": [0.5, -0.25]}
+    assert with_c(stated(exe, tmp_path, "--julia", "1,1", "--julia", "0.5,-0.25")[1]) == {"julia": [0.5, -0.25]}
 
 
 def test_without_the_flag_no_julia_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--power", "3", cwd=tmp_path)
+    r = run(exe, *SMALL, "--power", "3", cwd=tmp_path)
     assert "julia" not in r.stderr and "projection" in r.stderr.split("\n")[0]

@@ -2,12 +2,12 @@
 other extension flags (tests/test_julia_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"palette"` line that --stats prints, next to the `"projection"` line, before any device is touched."""
 
-import json
 import os
 
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import IDENTITY, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD = "Invalid palette (want K:RRGGBB,... K ascending, at most 16 stops): "
 PALETTE = ["--palette", "20:000030,60:ff8000"]
@@ -29,7 +29,7 @@ OTHERS = (
     (["-m", "0"], "--palette needs -m from 1 to 16777216."),
     (["-m", "-5"], "--palette needs -m from 1 to 16777216."),
 )
-REFUSED = [(PALETTE + o, line) for o, line in OTHERS] + [(o + PALETTE, line) for o, line in OTHERS]
+REFUSED = both_orders(PALETTE, OTHERS)
 WITH_STATS = [(PALETTE + ["--stats"] + o, line) for o, line in OTHERS] + [(o + ["--stats"] + PALETTE, line) for o, line in OTHERS]
 # the flag's own refusals come before those of the step, of c and of the projection, which the same command lines trip
 BEFORE_THE_OTHERS = []
@@ -56,14 +56,7 @@ OTHERS_RULES = [
     + OTHERS_RULES,
 )
 def test_palette_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 @pytest.mark.parametrize("order", ["before", "after"])
@@ -80,59 +73,42 @@ def test_usage_does_not_list_the_flag(exe):
     assert "--palette" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """The lines of stderr under --stats that define the run, as {key: value}: one JSON object per line, up to the first
-    line that is none.  The run itself goes on to the device (and ends there on a box without one); its outcome is not
-    looked at."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    out = {}
-    for line in r.stderr.split("\n"):
-        if not line.startswith('{"'):
-            break
-        one = json.loads(line)
-        if "samples" in one:  # the counters: not a definition
-            break
-        out.update(one)
-    return out
-
-
 def test_palette_alone_is_the_identity_projection_and_states_its_stops(exe, tmp_path):
-    out = stated(exe, tmp_path, "--palette", "20:000030,200:ff8000,2000:ffffff", "-m", "2000")
-    assert [float.fromhex(v) for v in out["projection"]] == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    assert out["palette"] == [[20, "000030"], [200, "ff8000"], [2000, "ffffff"]]
-    assert "power" not in out and "julia" not in out
+    matrix, said = stated(exe, tmp_path, "--palette", "20:000030,200:ff8000,2000:ffffff", "-m", "2000")
+    assert matrix == IDENTITY
+    assert said == {"palette": [[20, "000030"], [200, "ff8000"], [2000, "ffffff"]]}  # no "power", no "julia"
 
 
 def test_hex_digits_in_either_case_and_stops_beyond_m(exe, tmp_path):
-    out = stated(exe, tmp_path, "--palette", "0:AbCdEf,4294967:0000FF")
-    assert out["palette"] == [[0, "abcdef"], [4294967, "0000ff"]]
-    assert stated(exe, tmp_path, "--palette", ",".join("%d:0000%02x" % (k, k) for k in range(16)))["palette"][15] == [
+    _, said = stated(exe, tmp_path, "--palette", "0:AbCdEf,4294967:0000FF")
+    assert said["palette"] == [[0, "abcdef"], [4294967, "0000ff"]]
+    assert stated(exe, tmp_path, "--palette", ",".join("%d:0000%02x" % (k, k) for k in range(16)))[1]["palette"][15] == [
         15, "00000f"]
 
 
 @pytest.mark.parametrize("order", ["before", "after"])
 def test_palette_combines_with_plane_step_and_c(exe, tmp_path, order):
     rest = ["--plane", "zr,cr", "--rotate", "zr,cr:90", "--power", "5", "--julia", "-0.8,0.156"]
-    out = stated(exe, tmp_path, *(PALETTE + rest if order == "before" else rest + PALETTE))
-    assert [float.fromhex(v) for v in out["projection"]] == [0.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0, 0.0]
-    assert out["power"] == 5 and [float.fromhex(v) for v in out["julia"]] == [-0.8, 0.156]
-    assert out["palette"] == [[20, "000030"], [60, "ff8000"]]
-    out = stated(exe, tmp_path, "--burning-ship", "--project", "0.5,0,0,1:0,2,0,0", *PALETTE)
-    assert [float.fromhex(v) for v in out["projection"]] == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0]
-    assert out["palette"] == [[20, "000030"], [60, "ff8000"]]
+    matrix, said = stated(exe, tmp_path, *(PALETTE + rest if order == "before" else rest + PALETTE))
+    assert matrix == [0.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0, 0.0]
+    assert said["power"] == 5 and [float.fromhex(v) for v in said["julia"]] == [-0.8, 0.156]
+    assert said["palette"] == [[20, "000030"], [60, "ff8000"]]
+    matrix, said = stated(exe, tmp_path, "--burning-ship", "--project", "0.5,0,0,1:0,2,0,0", *PALETTE)
+    assert matrix == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0]
+    assert said["palette"] == [[20, "000030"], [60, "ff8000"]]
 
 
 def test_the_last_palette_counts(exe, tmp_path):
-    assert stated(exe, tmp_path, "--palette", "1:111111", "--palette", "2:222222,3:333333")["palette"] == [
+    assert stated(exe, tmp_path, "--palette", "1:111111", "--palette", "2:222222,3:333333")[1]["palette"] == [
         [2, "222222"], [3, "333333"]]
 
 
 def test_the_ends_of_the_range_of_m_are_taken(exe, tmp_path):
     for m in ("1", "16777216"):
-        r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "-m", m, *PALETTE, cwd=tmp_path)
+        r = run(exe, *SMALL, "-m", m, *PALETTE, cwd=tmp_path)
         assert "Creating 16x16 image, %s max iterations." % m in r.stdout.split("\n")[:2], r.stdout
 
 
 def test_without_the_flag_no_palette_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--julia", "0,0", cwd=tmp_path)
+    r = run(exe, *SMALL, "--julia", "0,0", cwd=tmp_path)
     assert "palette" not in r.stderr and "projection" in r.stderr.split("\n")[0]

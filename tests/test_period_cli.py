@@ -2,17 +2,14 @@
 the conventions of the other extension flags (tests/test_bounded_cli.py): message, usage, exit 0; nothing is rendered.  What
 the flags mean is read from the lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 PP = ["--period-palette", "1:ff0000,2:00ff00,3:0000ff"]
 BOUNDED = ["--bounded"]
 BOTH = BOUNDED + PP
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 # (the other flags of the line, its first line); every line is tried with the flags of this file first and last
 NEW_ROWS = (
     # the rows of this file, ahead of --bounded's
@@ -79,14 +76,7 @@ WITH_STATS = [(["--stats"] + a + b, line) for a, b, line in ROWS]
 
 @pytest.mark.parametrize("args,first_line", REFUSED + WITH_STATS)
 def test_the_flags_print_message_then_usage_and_exit_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 @pytest.mark.parametrize("flag", ["--period-palette", "--period-eps"])
@@ -101,32 +91,12 @@ def test_usage_does_not_list_the_flags(exe):
     assert "--period-palette" not in out and "--period-eps" not in out and "period" not in out
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = []
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or "samples" in obj:
-            break
-        said.append(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
-
-
 def test_the_stats_line_stands_beside_the_bounded_line(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, *BOTH)
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    assert said == [{"bounded": True},
-                    {"period_palette": [[1, "ff0000"], [2, "00ff00"], [3, "0000ff"]], "period_eps": "0x1p-66"}]
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *BOTH, cwd=tmp_path)
+    assert matrix == IDENTITY
+    assert said == {"bounded": True, "period_palette": [[1, "ff0000"], [2, "00ff00"], [3, "0000ff"]], "period_eps": "0x1p-66"}
+    assert list(said) == ["bounded", "period_palette", "period_eps"]
+    r = run(exe, *SMALL, *BOTH, cwd=tmp_path)
     assert r.stderr.split("\n")[1:3] == [
         '{"bounded": true}',
         '{"period_palette": [[1, "ff0000"], [2, "00ff00"], [3, "0000ff"]], "period_eps": "0x1p-66"}']
@@ -136,11 +106,7 @@ def test_the_stats_line_stands_beside_the_bounded_line(exe, tmp_path):
                                        ("0x1.8p-3", 0.1875), ("-0", 0.0)])
 def test_period_eps_takes_decimals_and_hexfloats(exe, tmp_path, text, want):
     _, said = stated(exe, tmp_path, *BOTH, "--period-eps", text)
-    assert float.fromhex(said[1]["period_eps"]) == want and list(said[1]) == ["period_palette", "period_eps"]
-
-
-RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s", "buffer.bin",
-             "--rng-state", "side.rng"]
+    assert float.fromhex(said["period_eps"]) == want and list(said) == ["bounded", "period_palette", "period_eps"]
 
 
 @pytest.mark.parametrize("first", ["period", "others"])
@@ -160,17 +126,17 @@ RUN_FLAGS = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tone
 def test_it_combines_with_the_planes_the_steps_julia_and_the_run_flags(exe, tmp_path, others, keys, matrix, first):
     args = (PP + BOUNDED + others if first == "period" else others + BOUNDED + PP) + RUN_FLAGS
     got, said = stated(exe, tmp_path, *args)
-    assert got == matrix and [list(o)[0] for o in said] == keys
-    assert said[-1]["period_palette"] == [[1, "ff0000"], [2, "00ff00"], [3, "0000ff"]]
+    assert got == matrix and list(said) == keys + ["period_eps"]  # (the last line's second key)
+    assert said["period_palette"] == [[1, "ff0000"], [2, "00ff00"], [3, "0000ff"]]
 
 
 def test_stops_at_the_ends_of_the_range_are_taken(exe, tmp_path):
     _, said = stated(exe, tmp_path, "--bounded", "--period-palette", "0:101010,1023:ABCDEF")
-    assert said[1]["period_palette"] == [[0, "101010"], [1023, "abcdef"]]
+    assert said["period_palette"] == [[0, "101010"], [1023, "abcdef"]]
     _, said = stated(exe, tmp_path, "--bounded", "--period-palette", "0:ffffff")  # one stop at 0: a table of two entries
-    assert said[1]["period_palette"] == [[0, "ffffff"]]
+    assert said["period_palette"] == [[0, "ffffff"]]
 
 
 def test_without_the_flags_no_period_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--bounded", cwd=tmp_path)
+    r = run(exe, *SMALL, "--bounded", cwd=tmp_path)
     assert "period" not in r.stderr and r.stderr.split("\n")[1] == '{"bounded": true}'

@@ -2,16 +2,13 @@
 other extension flags (tests/test_frames_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is read
 from the `"projection"`, `"julia"` and `"phoenix"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import CHANNELS, IDENTITY, RUN_FLAGS, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD = "Invalid phoenix parameter (want RE,IM, two numbers from -2 to 2): "
 PHOENIX = ["--phoenix", "-0.5,0"]
-CHANNELS = ["--channel", "9:1:a", "--channel", "9:2:b", "--channel", "9:3:c"]
 # the row's partners, in its order
 OTHERS = (
     (["--power", "3"], "--phoenix does not combine with --power."),
@@ -32,7 +29,7 @@ OTHERS = (
     (["--burning-ship", "--depth", "cr:-2:0.5:4"], "--phoenix does not combine with --burning-ship."),
     (["--julia", "0.3,0", "--sweep", "zi,cr:0:90:4"], "--phoenix does not combine with --sweep."),
 )
-REFUSED = [(PHOENIX + o, line) for o, line in OTHERS] + [(o + PHOENIX, line) for o, line in OTHERS]
+REFUSED = both_orders(PHOENIX, OTHERS)
 # The flag's row is the table's last: where an older row applies to the same command line, that row has spoken already,
 # with its own subject.  In both orders.
 EARLIER_ROWS = (
@@ -52,7 +49,7 @@ EARLIER_ROWS = (
     (["--sweep", "zi,cr:0:90:4", "--depth", "cr:-2:0.5:4"], "--sweep does not combine with --depth."),
     (["--palette", "0:ffffff", "--state-format", "raw"], "--palette does not combine with --state-format raw."),
 )
-BEHIND = [(PHOENIX + o, line) for o, line in EARLIER_ROWS] + [(o + PHOENIX, line) for o, line in EARLIER_ROWS]
+BEHIND = both_orders(PHOENIX, EARLIER_ROWS)
 WITH_STATS = [(PHOENIX + ["--stats"] + o, line) for o, line in OTHERS]
 MALFORMED = ["", "0", "0,", ",0", "0,0,", "0,0,0", "0 ,0", "0, 0", " 0,0", "0,0 ", "0;0", "a,b", "nan,0", "0,nan", "inf,0",
              "0,-inf", "2.0000001,0", "0,-2.0000001", "0x1.0000000000001p+1,0", "3,0", "0:0", "1e400,0"]
@@ -70,39 +67,12 @@ MALFORMED = ["", "0", "0,", ",0", "0,0,", "0,0,0", "0 ,0", "0, 0", " 0,0", "0,0 
     + WITH_STATS,
 )
 def test_phoenix_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     """The usage text is the reference's and lists no extension flag; README.md and DESIGN.md 4.19 describe this one."""
     assert "--phoenix" not in run(exe, "--help").stdout
-
-
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on stderr under --stats: the matrix, then one JSON object per
-    further line.  The run itself goes on to the device (and ends there on a box without one); its outcome is not looked
-    at, and what it prints after the lines that state the run is dropped."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    assert "Usage:" not in r.stdout  # accepted: on to the device
-    assert r.stdout.startswith("Creating 16x16 image")
-    lines = r.stderr.split("\n")
-    said = {}
-    for line in lines[1:]:
-        try:
-            obj = json.loads(line)
-        except ValueError:
-            break
-        if not isinstance(obj, dict) or len(obj) != 1:
-            break
-        said.update(obj)
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], said
 
 
 def p_of(said):
@@ -111,12 +81,12 @@ def p_of(said):
 
 def test_the_flag_alone_is_the_identity_plane_with_a_sampled_c(exe, tmp_path):
     matrix, said = stated(exe, tmp_path, "--phoenix", "-0.5,0")
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
+    assert matrix == IDENTITY
     assert list(said) == ["phoenix"] and p_of(said) == [-0.5, 0.0]
 
 
 def test_the_stats_line_is_two_hexfloats(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--phoenix", "0.3,-0.4", cwd=tmp_path)
+    r = run(exe, *SMALL, "--phoenix", "0.3,-0.4", cwd=tmp_path)
     assert r.stderr.split("\n")[1] == '{"phoenix": ["%s", "%s"]}' % ("0x1.3333333333333p-2", "-0x1.999999999999ap-2")
 
 
@@ -131,9 +101,7 @@ def test_accepted_forms(exe, tmp_path):
 @pytest.mark.parametrize("first", ["julia", "phoenix"])
 def test_it_combines_with_julia_a_plane_and_the_run_flags(exe, tmp_path, first):
     julia, flag = ["--julia", "0.56667,0"], ["--phoenix", "-0.5,0"]
-    run_flags = ["-m", "50", "-c", "5", "--seed", "7", "--kernel", "simple", "--tonemap", "host", "-g", "2.2", "-s",
-                 "buffer.bin", "--rng-state", "side.rng", "--state-format", "raw"]
-    args = (julia + flag if first == "julia" else flag + julia) + ["--plane", "zr,cr"] + run_flags
+    args = (julia + flag if first == "julia" else flag + julia) + ["--plane", "zr,cr"] + RUN_FLAGS + ["--state-format", "raw"]
     matrix, said = stated(exe, tmp_path, *args)
     assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
     assert list(said) == ["julia", "phoenix"]
@@ -145,5 +113,5 @@ def test_it_combines_with_julia_a_plane_and_the_run_flags(exe, tmp_path, first):
 
 
 def test_without_the_flag_no_phoenix_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--julia", "0.3,0", cwd=tmp_path)
+    r = run(exe, *SMALL, "--julia", "0.3,0", cwd=tmp_path)
     assert "phoenix" not in r.stderr and "projection" in r.stderr.split("\n")[0]

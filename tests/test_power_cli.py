@@ -2,12 +2,10 @@
 other extension flags (tests/test_project_cli.py): message, usage, exit 0; nothing is rendered.  What the flag means is
 read from the `"projection"` and `"power"` lines that --stats prints before any device is touched."""
 
-import json
-import os
-
 import pytest
 
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import IDENTITY, SMALL, both_orders, refused, run, stated
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD_POWER = "Invalid power (want an integer from 3 to 8): "
 POWER = ["--power", "3"]
@@ -22,7 +20,7 @@ OTHERS = (
     (["--color", "c.ppm"], "--power does not combine with --channel."),
     (["--gpus", "2"], "--power does not combine with --gpus above 1."),
 )
-REFUSED = [(POWER + o, line) for o, line in OTHERS] + [(o + POWER, line) for o, line in OTHERS]
+REFUSED = both_orders(POWER, OTHERS)
 # the flag's own refusal comes before the projection's, which the same command line would trip as well
 WITH_PLANE = [(["--plane", "zr,cr"] + POWER + o, line) for o, line in OTHERS[1:]]
 WITH_STATS = [(POWER + ["--stats"] + o, line) for o, line in OTHERS] + [(o + ["--stats"] + POWER, line) for o, line in OTHERS]
@@ -51,44 +49,29 @@ WITH_STATS = [(POWER + ["--stats"] + o, line) for o, line in OTHERS] + [(o + ["-
     + WITH_STATS,
 )
 def test_power_flag_prints_message_then_usage_and_exits_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before anything is printed under --stats and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_flag(exe):
     assert "--power" not in run(exe, "--help").stdout
 
 
-def stated(exe, tmp_path, *args):
-    """What a command line means, as the binary states it on the first two lines of stderr under --stats.  The run itself
-    goes on to the device (and ends there on a box without one); its outcome is not looked at."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    lines = r.stderr.split("\n")
-    return [float.fromhex(v) for v in json.loads(lines[0])["projection"]], json.loads(lines[1])
-
-
 @pytest.mark.parametrize("degree", range(3, 9))
 def test_power_alone_is_the_identity_projection(exe, tmp_path, degree):
-    matrix, second = stated(exe, tmp_path, "--power", str(degree))
-    assert matrix == [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    assert second == {"power": degree}
+    matrix, said = stated(exe, tmp_path, "--power", str(degree))
+    assert matrix == IDENTITY
+    assert said == {"power": degree}
 
 
 @pytest.mark.parametrize("order", ["before", "after"])
 def test_power_takes_the_plane_that_is_given(exe, tmp_path, order):
     plane = ["--plane", "zr,cr", "--rotate", "zr,cr:90"]
     args = ["--power", "5"] + plane if order == "before" else plane + ["--power", "5"]
-    matrix, second = stated(exe, tmp_path, *args)
+    matrix, said = stated(exe, tmp_path, *args)
     assert matrix == [0.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0, 0.0]
-    assert second == {"power": 5}
-    matrix, second = stated(exe, tmp_path, "--project", "0.5,0,0,1:0,2,0,0", "--power", "8")
-    assert matrix == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0] and second == {"power": 8}
+    assert said == {"power": 5}
+    matrix, said = stated(exe, tmp_path, "--project", "0.5,0,0,1:0,2,0,0", "--power", "8")
+    assert matrix == [0.5, 0.0, 0.0, 1.0, 0.0, 2.0, 0.0, 0.0] and said == {"power": 8}
 
 
 def test_the_last_power_counts(exe, tmp_path):
@@ -96,5 +79,5 @@ def test_the_last_power_counts(exe, tmp_path):
 
 
 def test_without_the_flag_no_power_line(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", "--plane", "zr,cr", cwd=tmp_path)
+    r = run(exe, *SMALL, "--plane", "zr,cr", cwd=tmp_path)
     assert "power" not in r.stderr and "projection" in r.stderr.split("\n")[0]

@@ -4,12 +4,12 @@ parsed matrix is read from the `"projection"` line that --stats prints before an
 
 import json
 import math
-import os
 
 import pytest
 
 import plot_reference as plot
-from plot_harness import exe, run  # noqa: F401
+from cli_harness import IDENTITY, SMALL, refused, run, stats_lines
+from cli_harness import exe  # noqa: F401 (a fixture)
 
 BAD_PROJECTION = "Invalid projection (want a,b,c,d:e,f,g,h, eight finite numbers): "
 BAD_PLANE = "Invalid plane (want X,Y, two different axes of zr, zi, cr, ci): "
@@ -70,14 +70,7 @@ REFUSED = [(p + o, line) for p in PROJECTIONS for o, line in OTHERS] + [(o + p, 
     + REFUSED,
 )
 def test_projection_flags_print_message_then_usage_and_exit_zero(exe, args, first_line, tmp_path):
-    r = run(exe, *args, cwd=tmp_path)
-    assert r.returncode == 0
-    lines = r.stdout.split("\n")
-    assert lines[0] == first_line
-    assert lines[1] == "Usage: %s [options]" % exe
-    assert r.stdout.rstrip().endswith("include in the output image. Defaults to 2.0.")  # the usage text is the reference's
-    assert r.stderr == ""  # decided before the matrix is printed and before any device is touched
-    assert os.listdir(tmp_path) == []
+    refused(exe, args, first_line, tmp_path)
 
 
 def test_usage_does_not_list_the_extension_flags(exe):
@@ -86,16 +79,10 @@ def test_usage_does_not_list_the_extension_flags(exe):
 
 
 def parsed_matrix(exe, tmp_path, *args):
-    """The matrix a command line means, as the binary states it: the first line of stderr under --stats, eight %a values.
-    The run itself goes on to the device (and ends there on a box without one); its outcome is not looked at."""
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", *args, cwd=tmp_path)
-    first = r.stderr.split("\n")[0]
-    values = json.loads(first)["projection"]
+    """The matrix a command line means, as the binary states it (cli_harness.stated), and its eight %a texts."""
+    values = json.loads(stats_lines(exe, tmp_path, *args)[0])["projection"]
     assert len(values) == 8
     return [float.fromhex(v) for v in values], values
-
-
-IDENTITY = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
 
 
 @pytest.mark.parametrize(
@@ -142,5 +129,5 @@ def test_a_general_rotation_uses_the_hosts_cos_and_sin(exe, tmp_path):
 
 
 def test_without_a_projection_nothing_is_printed_before_the_device(exe, tmp_path):
-    r = run(exe, "--stats", "--passes", "0", "-w", "16", "-h", "16", cwd=tmp_path)
+    r = run(exe, *SMALL, cwd=tmp_path)
     assert "projection" not in r.stderr
