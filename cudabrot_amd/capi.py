@@ -370,6 +370,17 @@ def _load():
         "cb_density_filter_device": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(u64), vp, vp]),
         "cb_renderer_set_density_filter": (i32, [vp, i32, C.c_double, u64]),
         "cb_renderer_density_filter": (i32, [vp, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(u64)]),
+        "cb_equalize_key": (u32, [u64]),
+        "cb_equalize_bins": (i32, [vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "cb_equalize_table": (i32, [vp, C.c_double, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "cb_set_grayscale_pixels_equalized": (i32, [vp, i32, i32, C.c_double, vp, C.POINTER(u64), C.POINTER(C.c_double),
+                                                    C.POINTER(u64)]),
+        "cb_equalize_bins_device": (i32, [vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]),
+        "cb_tone_map_device_equalized": (i32, [vp, i32, i32, C.c_double, vp, C.POINTER(u64), C.POINTER(C.c_double),
+                                               C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]),
+        "cb_renderer_set_equalize": (i32, [vp, i32]),
+        "cb_renderer_equalize": (i32, [vp]),
+        "cb_renderer_last_equalize": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -406,7 +417,9 @@ EXPORTED_SYMBOLS = (
     "cb_white_clip_ok cb_white_rank cb_white_count cb_set_grayscale_pixels_white cb_white_count_device "
     "cb_tone_map_device_white cb_renderer_set_white_clip cb_renderer_white_clip cb_renderer_last_white "
     "cb_density_thresholds cb_density_arguments_ok cb_density_filter cb_density_filter_device "
-    "cb_renderer_set_density_filter cb_renderer_density_filter"
+    "cb_renderer_set_density_filter cb_renderer_density_filter "
+    "cb_equalize_key cb_equalize_bins cb_equalize_table cb_set_grayscale_pixels_equalized cb_equalize_bins_device "
+    "cb_tone_map_device_equalized cb_renderer_set_equalize cb_renderer_equalize cb_renderer_last_equalize"
 ).split()
 
 
@@ -997,6 +1010,21 @@ class Renderer:
                "cb_renderer_density_filter")
         return int(radius.value), float(alpha.value), int(n0.value)
 
+    def set_equalize(self, on=True):
+        """Equalisation of every image call (cb_renderer_set_equalize): "Equalised image"; refused beside a white clip."""
+        _check(lib.cb_renderer_set_equalize(self._h, 1 if on else 0), "cb_renderer_set_equalize")
+
+    @property
+    def equalize(self):
+        return bool(lib.cb_renderer_equalize(self._h))
+
+    def last_equalize(self):
+        """(lit, keys, levels) of the last image call made equalised (cb_renderer_last_equalize)."""
+        lit, keys, levels = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib.cb_renderer_last_equalize(self._h, C.byref(lit), C.byref(keys), C.byref(levels)),
+               "cb_renderer_last_equalize")
+        return int(lit.value), int(keys.value), int(levels.value)
+
     def color_image(self, planes=(0, 1, 2), gamma=1.0, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
         """Colour stage on the device (cb_renderer_color_image): planes[0..2] -> (big-endian u16 image [h,w,3] = the
         PPM body, levels [(black, white)] * 3)."""
@@ -1075,6 +1103,68 @@ def set_grayscale_pixels_white(hist, gamma, clip):
         "cb_set_grayscale_pixels_white",
     )
     return gray, int(mx.value), float(scale.value), int(white.value)
+
+
+CB_EQUALIZE_KEYS = 56320  # equalised image: the number of keys
+
+
+def equalize_key(count):
+    """The key of a counter ("Equalised image", cb_equalize_key)."""
+    return int(lib.cb_equalize_key(int(count)))
+
+
+def equalize_bins(hist):
+    """cb_equalize_bins over every counter of `hist` as one array -> (u64 bins [CB_EQUALIZE_KEYS], lit, max)."""
+    a = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    bins = np.empty(CB_EQUALIZE_KEYS, dtype=np.uint64)
+    lit, mx = C.c_uint64(), C.c_uint64()
+    _check(lib.cb_equalize_bins(a.ctypes.data, a.size, bins.ctypes.data, C.byref(lit), C.byref(mx)), "cb_equalize_bins")
+    return bins, int(lit.value), int(mx.value)
+
+
+def equalize_table(bins, gamma):
+    """cb_equalize_table -> (u16 table [CB_EQUALIZE_KEYS], keys, levels)."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64)
+    assert b.shape == (CB_EQUALIZE_KEYS,)
+    table = np.empty(CB_EQUALIZE_KEYS, dtype=np.uint16)
+    keys, levels = C.c_uint64(), C.c_uint64()
+    _check(lib.cb_equalize_table(b.ctypes.data, float(gamma), table.ctypes.data, C.byref(keys), C.byref(levels)),
+           "cb_equalize_table")
+    return table, int(keys.value), int(levels.value)
+
+
+def set_grayscale_pixels_equalized(hist, gamma):
+    """cb_set_grayscale_pixels_equalized -> (u16 image [h,w] host-endian, max count, 65535 / max, lit)."""
+    a = np.ascontiguousarray(hist, dtype=np.uint64)
+    h, w = a.shape
+    gray = np.empty((h, w), dtype=np.uint16)
+    mx, scale, lit = C.c_uint64(), C.c_double(), C.c_uint64()
+    _check(
+        lib.cb_set_grayscale_pixels_equalized(a.ctypes.data, w, h, float(gamma), gray.ctypes.data, C.byref(mx),
+                                              C.byref(scale), C.byref(lit)),
+        "cb_set_grayscale_pixels_equalized",
+    )
+    return gray, int(mx.value), float(scale.value), int(lit.value)
+
+
+def equalize_bins_device(d_hist, n, stream=0):
+    """cb_equalize_bins_device on caller-owned device memory (an integer pointer to n u64) -> (bins, lit, max)."""
+    bins = np.empty(CB_EQUALIZE_KEYS, dtype=np.uint64)
+    lit, mx = C.c_uint64(), C.c_uint64()
+    _check(lib.cb_equalize_bins_device(d_hist, int(n), bins.ctypes.data, C.byref(lit), C.byref(mx), stream),
+           "cb_equalize_bins_device")
+    return bins, int(lit.value), int(mx.value)
+
+
+def tone_map_device_equalized(d_hist, w, h, gamma, d_gray_be, stream=0):
+    """cb_tone_map_device_equalized on caller-owned device memory (integer pointers) -> (max, scale, lit, keys, levels)."""
+    mx, scale, lit, keys, levels = C.c_uint64(), C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(
+        lib.cb_tone_map_device_equalized(d_hist, w, h, float(gamma), d_gray_be, C.byref(mx), C.byref(scale), C.byref(lit),
+                                         C.byref(keys), C.byref(levels), stream),
+        "cb_tone_map_device_equalized",
+    )
+    return int(mx.value), float(scale.value), int(lit.value), int(keys.value), int(levels.value)
 
 
 def density_thresholds(radius, alpha=0.5, n0=1):

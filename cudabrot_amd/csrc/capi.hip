@@ -358,6 +358,10 @@ struct cb_renderer {
   double density_alpha;
   uint64_t density_n0;
   uint64_t density_thresholds[CB_DENSITY_MAX_RADIUS + 1];
+  // Equalisation ("Equalised image" of include/cudabrot_amd.h): an output setting as well, never on beside a white clip,
+  // and what the last image call made with it found (cb_renderer_last_equalize).
+  bool equalize;
+  cb::Equalized last_equalize;
 };
 
 namespace {
@@ -833,9 +837,20 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
 }
 
 // cb_tone_map_device over `rows` rows of w counters at `hist` -- or, on a renderer with a white clip, the clipped map over
-// the same array, whose white point the renderer keeps.
+// the same array, whose white point the renderer keeps; or, on an equalised one, the equalised map, likewise.
 int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
                       uint64_t *max_out, double *scale_out) {
+  if (r->equalize) {
+    if (mode != CB_TONE_AUTO && mode != CB_TONE_LUT && mode != CB_TONE_THRESHOLDS) return (int) hipErrorInvalidValue;
+    cb::Equalized found = {0, 0, 0, 0};
+    const int rc = cb::tone_map_equalized(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma,
+                                          d_gray_be, &found, r->stream);
+    if (rc) return rc;
+    r->last_equalize = found;
+    if (max_out) *max_out = found.max;  // what the unflagged call reports
+    if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.max);
+    return 0;
+  }
   if (r->white_clip == 0.0) {
     return cb_tone_map_device(hist, r->dims.w, rows, gamma, mode, d_gray_be, max_out, scale_out, r->stream);
   }
@@ -1884,6 +1899,7 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
   if (!r || !planes || !host_rgb_be || !cb::color_params_ok(p)) return (int) hipErrorInvalidValue;
   if (r->white_clip != 0.0) return (int) hipErrorInvalidValue;  // the colour stage has a stretch of its own ("White clip")
   if (r->density_radius != 0) return (int) hipErrorInvalidValue;  // and works on 16-bit planes ("Density filter")
+  if (r->equalize) return (int) hipErrorInvalidValue;             // its stretch again ("Equalised image")
   const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
   const cb_pixel *src[3];
   for (int j = 0; j < 3; ++j) {
@@ -1907,6 +1923,7 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
 
 int cb_renderer_set_white_clip(cb_renderer *r, double percent) {
   if (!r || !cb_white_clip_ok(percent)) return (int) hipErrorInvalidValue;
+  if (percent != 0.0 && r->equalize) return (int) hipErrorInvalidValue;  // one exposure at a time ("Equalised image")
   r->white_clip = percent;
   r->last_white = {0, 0, 0, 0};
   return 0;
@@ -1942,6 +1959,23 @@ int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *
   *white_out = r->last_white.white;
   *lit_out = r->last_white.lit;
   *clipped_out = r->last_white.clipped;
+  return 0;
+}
+
+int cb_renderer_set_equalize(cb_renderer *r, int on) {
+  if (!r || (on != 0 && r->white_clip != 0.0)) return (int) hipErrorInvalidValue;
+  r->equalize = on != 0;
+  r->last_equalize = {0, 0, 0, 0};
+  return 0;
+}
+
+int cb_renderer_equalize(const cb_renderer *r) { return (r && r->equalize) ? 1 : 0; }
+
+int cb_renderer_last_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *keys_out, uint64_t *levels_out) {
+  if (!r || !lit_out || !keys_out || !levels_out) return (int) hipErrorInvalidValue;
+  *lit_out = r->last_equalize.lit;
+  *keys_out = r->last_equalize.keys;
+  *levels_out = r->last_equalize.levels;
   return 0;
 }
 

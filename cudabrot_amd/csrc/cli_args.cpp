@@ -230,6 +230,9 @@ const char kUsageBody[] =
     "     image is made: a pixel's counts are spread over a radius that\n"
     "     shrinks from R (1 to 8) as its count grows from N0 (default 1),\n"
     "     as (R/r)^(1/ALPHA) (ALPHA from 1/16 to 4, default 0.5).\n"
+    "  --equalize: Equalizes the image: a pixel's brightness is the share of\n"
+    "     the nonzero pixels that are no brighter than it, rather than its\n"
+    "     count over the largest count. -g applies to that share.\n"
     "\n"
     "The following settings control the location of the output image on the\n"
     "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
@@ -576,6 +579,9 @@ const std::vector<Flag> &flag_table() {
        [](Settings &s, long, double, const char *t) {
          return parse_density(t, &s.density) ? kOk : "Invalid density filter (want R[:ALPHA[:N0]], R from 1 to 8)";
        }},
+      // --equalize: every image exposed by the rank of its counters (include/cudabrot_amd.h, "Equalised image")
+      {"--equalize", Value::kNone, nullptr, false,
+       [](Settings &s, long, double, const char *) { s.equalize = true; return kOk; }},
       // --tonemap lut|thresholds|host: the form of the device tone map, or the reference's host loop
       {"--tonemap", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
@@ -611,6 +617,7 @@ const Partner kSweep = {[](const Settings &s) { return s.sweep_given; }, "--swee
 const Partner kPhoenix = {[](const Settings &s) { return s.phoenix; }, "--phoenix"};
 const Partner kPeriodPalette = {[](const Settings &s) { return s.period_palette(); }, "--period-palette"};
 const Partner kColor = {[](const Settings &s) { return s.color_file != nullptr; }, "--color"};
+const Partner kWhiteClip = {[](const Settings &s) { return s.white_clip > 0.0; }, "--white-clip"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -696,6 +703,9 @@ const std::vector<Refusal> &refusal_table() {
       // the density filter makes 64-bit counters; the colour stage works on the planes' 16-bit images
       // (include/cudabrot_amd.h, "Density filter").  The last row, likewise
       {[](const Settings &s) { return s.density.radius > 0; }, "--density-filter", {kColor}, nullptr},
+      // an equalised image has an exposure of its own: no white point to clip against, and the colour stage stretches its
+      // planes itself (include/cudabrot_amd.h, "Equalised image").  The last row, likewise
+      {[](const Settings &s) { return s.equalize; }, "--equalize", {kWhiteClip, kColor}, nullptr},
   };
   return table;
 }

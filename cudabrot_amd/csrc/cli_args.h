@@ -147,6 +147,9 @@ struct Settings {
   // falls as the count rises (include/cudabrot_amd.h, "Density filter"; cb_renderer_set_density_filter); radius 0, the
   // default, is off
   DensityFilter density;
+  // --equalize (extension): every image of the run exposed by the rank of its counters among the lit ones instead of by
+  // their size (include/cudabrot_amd.h, "Equalised image"; cb_renderer_set_equalize)
+  bool equalize = false;
   // The one place that says what the flags above make of the output: a palette of any kind turns its render's planes into
   // three and the file into a PPM, so it goes before the render it colours; --depth and --sweep stack their planes;
   // --channel has an image per plane.  The refusal table lets no two of the renders meet.

@@ -147,6 +147,10 @@ class Run {
       fprintf(stderr, "]}}\n");
       fflush(stderr);
     }
+    if (cfg_.equalize && cfg_.print_stats) {  // likewise
+      fprintf(stderr, "{\"equalize\": true}\n");
+      fflush(stderr);
+    }
     setup();
     load_inprogress();
     load_rng_state();
@@ -177,6 +181,7 @@ class Run {
   bool gray_is_big_endian_ = false;
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
   std::vector<cb_pixel> filtered_;  // --density-filter with --tonemap host: the counters the last image was mapped from
+  uint64_t host_equalized_[3] = {0, 0, 0};  // --equalize with --tonemap host: lit, keys, levels of the last image
   std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
@@ -267,6 +272,7 @@ class Run {
     if (cfg_.density.radius > 0) {  // likewise
       CB_CHECK(cb_renderer_set_density_filter(renderer_, cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0));
     }
+    if (cfg_.equalize) CB_CHECK(cb_renderer_set_equalize(renderer_, 1));  // likewise
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       const std::vector<uint32_t> lut = table_of(cfg_.palette_stops, (size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_renderer_set_palette(renderer_, lut.data(), (uint32_t) lut.size()));
@@ -546,7 +552,9 @@ class Run {
   static constexpr double launch_seconds_ = 0.2;
 
   // The reference's host loop over `rows` rows of the counters at `hist` -- with --white-clip, the clipped one; with
-  // --density-filter, over the filtered counters (filtered_): planes of the canvas's height, smoothed in groups of `group`.
+  // --equalize, the equalised one, whose bins and table are made once here and what they found kept (host_equalized_), as a
+  // renderer keeps it; with --density-filter, over the filtered counters (filtered_): planes of the canvas's height,
+  // smoothed in groups of `group`.
   void host_tone_map(const cb_pixel *hist, int rows, int group, uint16_t *gray, uint64_t *max, double *scale) {
     if (cfg_.density.radius > 0) {
       uint64_t table[CB_DENSITY_MAX_RADIUS + 1];
@@ -556,7 +564,15 @@ class Run {
                                  table, filtered_.data()));
       hist = filtered_.data();
     }
-    if (cfg_.white_clip > 0.0) {
+    if (cfg_.equalize) {  // cb_set_grayscale_pixels_equalized, its steps apart: it does not hand on the table's two numbers
+      const uint64_t n = (uint64_t) cfg_.canvas.w * (uint64_t) rows;
+      std::vector<uint64_t> bins(CB_EQUALIZE_KEYS);
+      std::vector<uint16_t> table(CB_EQUALIZE_KEYS);
+      CB_CHECK(cb_equalize_bins(hist, n, bins.data(), &host_equalized_[0], max));
+      CB_CHECK(cb_equalize_table(bins.data(), cfg_.gamma_correction, table.data(), &host_equalized_[1], &host_equalized_[2]));
+      *scale = ((double) 0xffff) / ((double) *max);
+      for (uint64_t i = 0; i < n; ++i) gray[i] = table[cb_equalize_key(hist[i])];
+    } else if (cfg_.white_clip > 0.0) {
       CB_CHECK(cb_set_grayscale_pixels_white(hist, cfg_.canvas.w, rows, cfg_.gamma_correction, cfg_.white_clip, gray, max,
                                              scale, nullptr));
     } else {
@@ -566,14 +582,20 @@ class Run {
 
   // The "Max value" line (cudabrot.cu:437) of an image over `rows` rows of the counters at `hist` (the host's mirror, read
   // with --tonemap host only) -- and with --white-clip the line of what the clip found: by the host's definition or, on the
-  // device path, as the renderer's image call reported it.  With --density-filter both lines speak of the filtered
-  // counters, and a line between them says so.
+  // device path, as the renderer's image call reported it; with --equalize, likewise, the line of what the equalisation
+  // found.  With --density-filter both lines speak of the filtered counters, and a line between them says so.
   void print_exposure(uint64_t max, double scale, const cb_pixel *hist, int rows) {
     printf("Max value: %lu, scale: %f\n", (unsigned long) max, scale);
     if (cfg_.density.radius > 0) {
       printf("Density filter: radius %d, alpha %g, n0 %lu (the values above carry 8 fraction bits)\n", cfg_.density.radius,
              cfg_.density.alpha, (unsigned long) cfg_.density.n0);
       if (cfg_.host_tonemap) hist = filtered_.data();  // what host_tone_map mapped
+    }
+    if (cfg_.equalize) {  // what the equalisation found, by the host's definition or as the renderer's image call reported it
+      uint64_t lit = host_equalized_[0], keys = host_equalized_[1], levels = host_equalized_[2];
+      if (!cfg_.host_tonemap) CB_CHECK(cb_renderer_last_equalize(renderer_, &lit, &keys, &levels));
+      printf("Equalized: %lu lit pixels in %lu keys, %lu output levels\n", (unsigned long) lit, (unsigned long) keys,
+             (unsigned long) levels);
     }
     if (!(cfg_.white_clip > 0.0)) return;
     uint64_t white = 0, lit = 0, clipped = 0;

@@ -62,6 +62,14 @@ CB_COLOR_FN void color_compose(int compose, double hue_shift, double s0, double 
 
 CB_COLOR_FN uint32_t color_swap16(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
 
+// The key of the equalised image (include/cudabrot_amd.h, "Equalised image"), ONE definition as well, for
+// cb_equalize_key (host_output.cpp) and the two kernels (equalize.hip): the 11 most significant bits of a counter and
+// where they stand.  A count-leading-zeros, a shift and an add; below 2048 the shift is 0 and the key is the count.
+CB_COLOR_FN uint32_t equalize_key(uint64_t c) {
+  const uint32_t s = c < 2048u ? 0u : 53u - (uint32_t) __builtin_clzll(c);  // floor(log2 c) - 10
+  return (s << 10) + (uint32_t) (c >> s);
+}
+
 // ---- host side of the levels (color_host.cpp) ----
 
 // 1 if p is a valid cb_color_params (compose, percentages, hue shift), else 0.

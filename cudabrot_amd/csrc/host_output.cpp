@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cudabrot_amd.h"
+#include "color_math.h"  // equalize_key
 
 namespace {
 
@@ -101,6 +102,64 @@ int cb_set_grayscale_pixels_white(const cb_pixel *hist, int w, int h, double gam
   if (white_out) *white_out = white;
   // the clamp is on the count: gamma <= 0, the reference's unclamped branch, needs no case of its own
   for (uint64_t i = 0; i < n; i++) gray_out[i] = cb_tone_value(hist[i] < white ? hist[i] : white, white, gamma);
+  return 0;
+}
+
+// "Equalised image" of include/cudabrot_amd.h, the definition: the key, the bins, the table, the image.
+uint32_t cb_equalize_key(uint64_t count) { return cb::equalize_key(count); }
+
+int cb_equalize_bins(const cb_pixel *hist, uint64_t n, uint64_t *bins_out, uint64_t *lit_out, uint64_t *max_out) {
+  if (!hist || n == 0 || !bins_out || !lit_out || !max_out) return 1;  // hipErrorInvalidValue
+  memset(bins_out, 0, CB_EQUALIZE_KEYS * sizeof(uint64_t));
+  uint64_t lit = 0, max = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (hist[i] == 0) continue;
+    bins_out[cb::equalize_key(hist[i])]++;
+    lit++;
+    if (hist[i] > max) max = hist[i];
+  }
+  *lit_out = lit;
+  *max_out = max;
+  return 0;
+}
+
+int cb_equalize_table(const uint64_t *bins, double gamma, uint16_t *table_out, uint64_t *keys_out, uint64_t *levels_out) {
+  if (!bins || !table_out || !keys_out || !levels_out) return 1;  // hipErrorInvalidValue
+  uint64_t lit = 0, le = 0, keys = 0, levels = 0;
+  for (uint32_t k = 0; k < CB_EQUALIZE_KEYS; k++) lit += bins[k];
+  table_out[0] = 0;
+  std::vector<bool> seen(65536, false);
+  // an empty bin has the rank, and so the value, of the key below it: cb_tone_value is called once per lit key
+  for (uint32_t k = 1; k < CB_EQUALIZE_KEYS; k++) {
+    table_out[k] = table_out[k - 1];
+    if (bins[k] == 0) continue;
+    le += bins[k];
+    // the full rank is full white: cb_tone_value(lit, lit, gamma) is 65535 in exact arithmetic, and 65534 in doubles for
+    // about one lit in seven (lit * (65535.0 / lit) rounds below 65535 and the conversion truncates)
+    table_out[k] = (le == lit && gamma > 0.0) ? (uint16_t) 0xffff : cb_tone_value(le, lit, gamma);
+    if (!seen[table_out[k]]) levels++;
+    seen[table_out[k]] = true;
+    keys++;
+  }
+  *keys_out = keys;
+  *levels_out = levels;
+  return 0;
+}
+
+int cb_set_grayscale_pixels_equalized(const cb_pixel *hist, int w, int h, double gamma, uint16_t *gray_out, uint64_t *max_out,
+                                      double *scale_out, uint64_t *lit_out) {
+  if (!hist || !gray_out || w <= 0 || h <= 0) return 1;  // hipErrorInvalidValue
+  const uint64_t n = (uint64_t) w * (uint64_t) h;
+  std::vector<uint64_t> bins(CB_EQUALIZE_KEYS);
+  std::vector<uint16_t> table(CB_EQUALIZE_KEYS);
+  uint64_t lit = 0, max = 0, keys = 0, levels = 0;
+  int rc = cb_equalize_bins(hist, n, bins.data(), &lit, &max);
+  if (rc == 0) rc = cb_equalize_table(bins.data(), gamma, table.data(), &keys, &levels);
+  if (rc) return rc;
+  if (max_out) *max_out = max;
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);  // what the unflagged call reports
+  if (lit_out) *lit_out = lit;
+  for (uint64_t i = 0; i < n; i++) gray_out[i] = table[cb::equalize_key(hist[i])];
   return 0;
 }
 

@@ -445,6 +445,15 @@ struct WhitePoint {
 };
 int tone_map_white(const unsigned long long *hist, int w, int h, double gamma, int mode, double clip_percent,
                    uint16_t *d_gray_be, WhitePoint *found, hipStream_t stream);
+// equalize.hip: cb_equalize_bins_device, and cb_tone_map_device_equalized with everything it found: what a renderer
+// keeps for cb_renderer_last_equalize.
+int equalize_bins_device(const unsigned long long *hist, unsigned long long n, uint64_t *bins_out_host, uint64_t *lit_out,
+                         uint64_t *max_out, hipStream_t stream);
+struct Equalized {
+  uint64_t max, lit, keys, levels;
+};
+int tone_map_equalized(const unsigned long long *hist, int w, int h, double gamma, uint16_t *d_gray_be, Equalized *found,
+                       hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

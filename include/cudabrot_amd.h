@@ -1330,6 +1330,72 @@ int cb_density_filter_device(const cb_pixel *d_hist, int w, int h, int planes, i
 int cb_renderer_set_density_filter(cb_renderer *r, int radius, double alpha, uint64_t n0);
 int cb_renderer_density_filter(const cb_renderer *r, int *radius_out, double *alpha_out, uint64_t *n0_out);
 
+/* ---- Equalised image: an image exposed by the rank of its counters ----------------- *
+ *
+ * Every image above is one linear-then-gamma curve of the count, and the counters span five to ten decades: no single
+ * curve shows the halo and the body at once.  Histogram equalisation maps a pixel to the fraction of the lit pixels that
+ * are no brighter, so every output level is used by about as many pixels.  It is the project's own definition (the
+ * reference has none).  Normative; host, device and the tests' restatement in Python integers agree bit for bit.  All
+ * arithmetic on counters is unsigned 64-bit integer; nothing but cb_tone_value touches floating point.
+ *
+ *   key: cb_equalize_key(c) keeps the 11 most significant bits of a counter.  For c < 2048, key = c; otherwise
+ *     s = floor(log2 c) - 10 and key = (s << 10) + (c >> s).
+ *   The key is non-decreasing in c and moves in steps of 0 or 1: key(2047) = 2047, key(2048) = key(2049) = 2048,
+ *   key(4095) = 3071, key(4096) = 3072, key(2^63 - 1) = 55295, key(2^64 - 1) = 56319; there are CB_EQUALIZE_KEYS = 56320.
+ *   Counts below 2048 are told apart exactly, larger ones to one part in 1024: counters that share a key differ by less
+ *   than a thousandth in brightness and get one rank, the ranks between keys stay exact -- and that is what lets ONE sweep
+ *   of the counters find the whole curve.
+ *   input: the image's counters as ONE array of n values -- all planes of the image together, exactly the array whose
+ *   maximum the unflagged image takes -- and gamma.
+ *     bins[k]  = #{count > 0 with key(count) = k}; zeros are not counted.
+ *     lit      = the sum of bins;  le[k] = the sum of bins[j] over j <= k.
+ *     table[0] = 0;  table[k] = cb_tone_value(le[k], lit, gamma) for k >= 1: the rank stands where the count stood and lit
+ *                where the maximum stood, so gamma works as before, the gamma <= 0 branch included.  One entry is pinned: for
+ *                gamma > 0 the brightest lit key, the one with le[k] = lit, gets 65535.  That is what cb_tone_value(lit, lit,
+ *                gamma) is in exact arithmetic; in doubles lit * (65535.0 / lit) rounds below 65535 for about one lit in
+ *                seven (162 is one) and the conversion would truncate to 65534.
+ *     pixel    = table[key(count)].  When lit = 0 the image is zero.
+ * Consequences: the map is monotone in the count; the brightest lit key gets 65535 for gamma > 0; lit counters that are
+ * distinct and below 2048 get cb_tone_value(r, lit, gamma), r the rank from 1 for the smallest (the largest, r = lit, by
+ * the pinned entry: the same value wherever the doubles give 65535, one level more where they do not); the image of hist << j is the image of hist for every
+ * j that overflows no counter (a shift keeps which counters share a key), so the density filter's 8 fraction bits change
+ * nothing by themselves.  Planes that share a maximum share one table, as they share one white. */
+#define CB_EQUALIZE_KEYS 56320
+
+uint32_t cb_equalize_key(uint64_t count);
+/* bins (CB_EQUALIZE_KEYS values), lit and the largest counter of a host array of n counters.  0, or hipErrorInvalidValue
+ * with nothing written: a NULL pointer or n = 0. */
+int cb_equalize_bins(const cb_pixel *hist, uint64_t n, uint64_t *bins_out, uint64_t *lit_out, uint64_t *max_out);
+/* table (CB_EQUALIZE_KEYS values) of the definition from bins and gamma; *keys_out is the number of non-empty bins,
+ * *levels_out the number of distinct table values over them.  0, or hipErrorInvalidValue with nothing written: a NULL
+ * pointer. */
+int cb_equalize_table(const uint64_t *bins, double gamma, uint16_t *table_out, uint64_t *keys_out, uint64_t *levels_out);
+/* cb_set_grayscale_pixels, equalised: gray_out receives w*h host-endian uint16; *max_out and *scale_out (may be NULL) are
+ * what cb_set_grayscale_pixels reports, the largest counter and 65535 / it; *lit_out (may be NULL) is lit.  0, or
+ * hipErrorInvalidValue with nothing written: a NULL hist or gray_out, or a canvas without pixels. */
+int cb_set_grayscale_pixels_equalized(const cb_pixel *hist, int w, int h, double gamma, uint16_t *gray_out, uint64_t *max_out,
+                                      double *scale_out, uint64_t *lit_out);
+/* cb_equalize_bins on a DEVICE array (8-byte aligned, 1 <= n <= 2^40): one streaming sweep (equalize.hip) into
+ * bins_out_host, CB_EQUALIZE_KEYS values on the HOST.  The numbers equal cb_equalize_bins'.  hipErrorInvalidValue with
+ * nothing written: a NULL pointer, an address that is not 8-byte aligned, n = 0 or n > 2^40.  Synchronises `stream`. */
+int cb_equalize_bins_device(const cb_pixel *d_hist, uint64_t n, uint64_t *bins_out_host, uint64_t *lit_out, uint64_t *max_out,
+                            void *stream);
+/* cb_tone_map_device, equalised: the bytes of cb_set_grayscale_pixels_equalized + cb_save_image into d_gray_be, and its
+ * numbers; *keys_out and *levels_out are cb_equalize_table's.  Every output number may be NULL.  The bins come from one
+ * sweep, the host makes the table and uploads it, a second kernel looks every pixel up.  Synchronises `stream`. */
+int cb_tone_map_device_equalized(const cb_pixel *d_hist, int w, int h, double gamma, uint16_t *d_gray_be, uint64_t *max_out,
+                                 double *scale_out, uint64_t *lit_out, uint64_t *keys_out, uint64_t *levels_out, void *stream);
+/* A renderer's equalisation: an output setting like the white clip, 0 (the default) = off.  With it on, every image call
+ * of the white clip's list makes the equalised image over the array it takes the maximum of otherwise -- the filtered one
+ * where a density filter is set; tone_mode is validated and otherwise not read (there is one form); *max_out and *scale_out
+ * stay what the unflagged call returns.  No launch, histogram or generator state knows of it.  cb_renderer_color_image on
+ * an equalised renderer returns hipErrorInvalidValue.  hipErrorInvalidValue, the renderer left as it was: equalisation
+ * turned on on a renderer with a white clip -- and cb_renderer_set_white_clip with a clip above 0 on an equalised one. */
+int cb_renderer_set_equalize(cb_renderer *r, int on);
+int cb_renderer_equalize(const cb_renderer *r);
+/* lit, keys and levels of the last image call made equalised; zeros before one, and after every cb_renderer_set_equalize. */
+int cb_renderer_last_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *keys_out, uint64_t *levels_out);
+
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
  * The reference's colour recipe (generate_hires_color_image.sh) renders three windows, stretches each PGM with
