@@ -8,7 +8,7 @@ import pytest
 
 import bounded_reference as bounded
 import plot_reference as plot
-from plot_harness import DEPTH_SHAPE, SAME, SQUARE, Launches, omp_threads, planar_states, variant_of
+from plot_harness import DEPTH_SHAPE, SAME, SQUARE, Launches, omp_threads, planar_states, variant_of, write_states
 
 PRODUCT, LOCKSTEP = 26, 27
 # 64 x 48, 1000 threads (a ragged last wave and workgroup), launches of 3, 50 and 1 samples on the same generators, -m 500
@@ -23,16 +23,21 @@ def bref(tmp_path_factory):
 
 
 def shape_of(kw):
+    """states: an oracle state array (tests/planted_samples.py plants its first samples) in the place of the fresh
+    generators; it is left as it was."""
     s = dict(w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN, threads=THREADS, launches=LAUNCHES, c=None,
-             projection=plot.IDENTITY, degree=2, ship=False, formula=0)
+             projection=plot.IDENTITY, degree=2, ship=False, formula=0, states=None)
     s.update(kw)
     return s
 
 
 def bounded_launches(cb, base, **kw):
-    """`launches` on fresh generators through cb_draw_buddhabrot_bounded -> (hist [h, w], counters, kernel, states)."""
+    """`launches` on fresh generators (or the given states) through cb_draw_buddhabrot_bounded -> (hist [h, w], counters,
+    kernel, states)."""
     s = shape_of(kw)
     bufs = Launches(cb, cb.FractalDimensions.make(s["w"], s["h"], *s["box"]), s["threads"])
+    if s["states"] is not None:
+        write_states(bufs, s["states"])
     variant = variant_of(cb, base, s["degree"], s["ship"], plot.code_of(s["formula"]))
     return bufs.launches(cb.draw_buddhabrot_bounded, s["launches"], variant,
                          iterations=cb.IterationControl(s["max_iter"], s["min_iter"]), projection=s["projection"],
@@ -42,7 +47,7 @@ def bounded_launches(cb, base, **kw):
 def restated(bref, oracle, mode=bounded.NAIVE, **kw):
     """The restatement of the same launches -> (hist, counters, extra, generator states after)."""
     s = shape_of(kw)
-    st = oracle.init_states(1337, 0, s["threads"])
+    st = oracle.init_states(1337, 0, s["threads"]) if s["states"] is None else s["states"].copy()
     extra = {}
     hist, cnt = bounded.draw(bref, s["w"], s["h"], s["max_iter"], s["threads"], list(s["launches"]),
                              projection=s["projection"], degree=s["degree"], ship=s["ship"], formula=s["formula"], c=s["c"],

@@ -35,6 +35,20 @@ reference's arithmetic, not by a formula about it:
                                   trunc(a * RN(1 / delta)) differ (the replay burst's exact-division fallback decides
                                   there), and canvases with an orbit point on, or one ulp off, a canvas edge
     pixel_edge_samples            more samples, on the real axis, with such a point on a given canvas
+
+The second half of the module does the same for the plotted renders (projected with its steps, Julia, palette, depth,
+depth palette, frames, bounded) on THEIR restatement's functions -- plot.step, plot.point, plot.depth_of, plot.slice_of of
+tests/plot_reference.py and .c:
+
+    with_end(lib, n, c, **step)   a sample (z_0 under a fixed c) whose orbit escapes at step n under any step of the table
+    slice_edges(lib, window)      grid neighbours in c_re that slice_of tells apart, one pair per boundary of the window
+    repeating(lib, step, c)       samples whose orbit repeats bit for bit, period 1 and 2, the two on |z|^2 == 4 among them
+    c_plane_edges, hologram_canvases   samples on pixel and canvas edges of a dyadic and of an irrational projection
+    FILLER                        the sample every family decides at its first step: the lanes not under test are idle
+    queue_fills                   the frames render's LDS queue, modelled from the planted lanes' ends
+
+tests/test_planted_plot_host.py shows these decisive on the restatement alone; tests/test_gpu_planted_plot.py and
+tests/test_gpu_planted_queue.py feed them to the kernels.
 """
 
 import ctypes as C
@@ -482,3 +496,281 @@ def pixel_edge_cases(w, h, count=1233, max_iter=1234, min_iter=20, samples=24):
     canvases["fallback"] = [(box, [base] + pixel_edge_samples(box, w, samples, max_iter, min_iter))
                             for box in canvases["fallback"]]
     return base, canvases
+
+
+# ---- the plotted renders: plants found on the restatement's own functions (tests/plot_reference.py, .c) ---------------------
+#
+# Everything below takes `lib`, plot_reference.load's library, and decides by plot.step, plot.point, plot.depth_of and
+# plot.slice_of alone.  A STEP is the keyword arguments of plot.step (degree, ship, formula); c None: the sample is c and
+# z_0, else c is fixed and the sample is z_0 (a Julia render).  An orbit's `end` is the step whose point escapes (the
+# scheduler's l.end; the reference's escape index k is end - 1).
+
+import plot_reference as plot  # noqa: E402
+
+ROUND, MANDELBROT = 12, {}                         # draw_rounds.h kRound; the reference's own step
+
+# The filler: a sample every family decides on the spot.  From z_0 = 2 + 2i the first step of every step there is, under any
+# c in [-2, 2]^2, lands at |z_1|^2 >= 36: `end` is 1, so it is too fast under any min_iter >= 1 and, in a bounded render,
+# an escaper.  (0, 0) is decided sooner still under the Mandelbrot step on a sampled c -- rejected --, but is an orbit that
+# never escapes under every other family.  plot_host checks both on the restatement.
+FILLER = (2.0, 2.0)
+
+
+def orbit_of(lib, sample, n, c=None, **step):
+    """z_1 .. of the sample under the restatement's step, at most n points, the escaping one included and last ->
+    (points [(r, i)], end or None where none of the n escapes)."""
+    cr, ci = sample if c is None else c
+    r, i = float(sample[0]), float(sample[1])
+    points = []
+    for k in range(1, n + 1):
+        r, i, m = plot.step(lib, cr, ci, r, i, **step)
+        points.append((r, i))
+        if m > 4.0:
+            return points, k
+    return points, None
+
+
+def end_of(lib, sample, cap, c=None, **step):
+    """The sample's `end` under the restatement's step, None if none of z_1 .. z_cap escapes."""
+    return orbit_of(lib, sample, cap, c, **step)[1]
+
+
+# rays from a point that never escapes to one that escapes at once; the count falls along them in wide bands near the start
+SAMPLED_RAYS = [
+    lambda e: (0.25 + e * GRID, 0.0),              # the cusp, where every step of the table is the reference's (z > 0 real)
+    lambda e: (0.25 + e * GRID, 2.0 ** -12),       # beside it: the imaginary part and the cross term take part
+    lambda e: (0.25 + 2.0 ** -3 + e * GRID, 0.0),  # degree 3 on the real axis: bounded up to 2 / sqrt(27) = 0.3849...
+]
+FIXED_C = (0.25, 0.0)                              # a Julia set with a parabolic point: z_0 = 1/2 stays, z_0 > 1/2 crawls away
+FIXED_RAYS = [lambda e: (0.5 + e * GRID, 0.0), lambda e: (0.5 + e * GRID, 2.0 ** -12)]
+RAY_LAST = 3 << 50                                 # every ray ends at or before real part 2 (e GRID = 1.5)
+
+
+def with_end(lib, end, c=None, ray=None, **step):
+    """A grid sample whose orbit escapes exactly at step `end` (>= 1) under the restatement's step: the last point of the
+    band `end` along a ray, next to the band end - 1; z_0 where c is fixed.  The rays are tried in turn (or the one given)
+    and what is returned is verified, not assumed."""
+    rays = (FIXED_RAYS if c is not None else SAMPLED_RAYS) if ray is None else [ray]
+    if ray is None and c is None and (step.get("ship") or step.get("formula")):
+        rays = [rays[1], rays[0], rays[2]]          # off the axis first: on it these steps are the reference's own
+    for point in rays:
+        def lasts(e):
+            got = end_of(lib, point(e), end, c, **step)
+            return got is None or got >= end
+        if end == 1:
+            lo = RAY_LAST
+        elif lasts(1) and not lasts(RAY_LAST):
+            lo, _ = _last_true(lasts, 1, RAY_LAST)
+        else:
+            continue
+        sample = point(lo)
+        grid_index(sample[0]), grid_index(sample[1])
+        if end_of(lib, sample, end + 2, c, **step) == end and (c is not None or step or not rejected(*sample)):
+            return sample
+    raise ValueError("no ray has a sample with end %d under %r, c %r" % (end, step, c))
+
+
+def slice_edges(lib, window, around=1 << 20):
+    """window = (min, max, N) of a depth along the row `cr`, where the depth of every point of an orbit is the sample's
+    c_re exactly.  -> {"pairs": [(j, below, above, slice below, slice above)], "disagree": [(c_re, slice, other)]}:
+    for every boundary j = 0 .. N whose two sides are both on the grid (min = -2 has nothing plantable below it) the grid
+    neighbours in c_re that plot.slice_of tells apart (None: outside the window), bisected over grid steps around min + j
+    delta; and, for a window whose delta is no power of two, the grid points within 64 steps of a boundary at which
+    trunc(fd / delta) -- plot.slice_of's, asserted -- and trunc(fd * RN(1 / delta)) differ, if the grid has any."""
+    lo, hi, n = window
+    delta = (hi - lo) / float(n)
+
+    def slice_at(g):
+        return plot.slice_of(lib, plot.depth_of(lib, "cr", 0.0, 0.0, grid_point(g), 0.0), lo, hi, n)
+
+    def rank(g):                                   # None (below), 0 .. N - 1, None (above) as -1 .. N
+        s = slice_at(g)
+        return s if s is not None else (-1 if grid_point(g) < lo + delta / 2 else n)
+
+    out = {"pairs": [], "disagree": []}
+    for j in range(n + 1):
+        centre = int(round(math.ldexp(lo + j * delta, 51)))
+        a, b = max(centre - around, 1 - (1 << 52)), min(centre + around, 1 << 52)
+        if not (rank(a) < j <= rank(b)):
+            continue                               # nothing plantable on one side
+        a, b = _last_true(lambda g: rank(g) < j, a, b)
+        out["pairs"].append((j, grid_point(a), grid_point(b), slice_at(a), slice_at(b)))
+        if math.frexp(delta)[0] != 0.5:
+            g = np.arange(max(a - 64, 1 - (1 << 52)), min(b + 64, 1 << 52) + 1, dtype=np.int64)
+            cre = g * GRID
+            fd = cre - lo
+            with np.errstate(invalid="ignore"):
+                exact, estimate = np.trunc(fd / np.float64(delta)), np.trunc(fd * (1.0 / np.float64(delta)))
+            for k in np.flatnonzero((exact != estimate) & (cre >= lo)):
+                s = slice_at(int(g[k]))
+                assert (s if s is not None else n) == min(int(exact[k]), n)
+                out["disagree"].append((float(cre[k]), s, int(estimate[k])))
+    return out
+
+
+REPEATING = [  # (step, fixed c or None, sample): candidates -- repeating() keeps what the restatement confirms
+    (dict(ship=True), None, (0.0, 0.0)), (dict(degree=3), None, (0.0, 0.0)), (dict(formula=1), None, (0.0, 0.0)),
+    (dict(ship=True), None, (-1.0, 0.0)),
+    (MANDELBROT, (-1.0, 0.0), (0.0, 0.0)),
+    (MANDELBROT, (-2.0, 0.0), (2.0, 0.0)), (MANDELBROT, (-2.0, 0.0), (0.0, 0.0)),
+]
+
+
+def repeating(lib, step, c=None, candidates=None):
+    """Samples whose orbit under (step, c) never escapes and repeats bit for bit -> [(sample, period, on_the_circle)]:
+    each candidate is stepped 121 times with the restatement; it is kept if z_120 is z_60 bit for bit (what the scheduler
+    sees at the first boundary where it can: it saves z_60 and compares at 120), and its period is the least p in (1, 2)
+    with z_{60+p} == z_60.  on_the_circle: some |z_k|^2 is 4.0 exactly (the strict test keeps it).  -2 itself cannot be
+    planted, so c = -2 occurs as a fixed c only."""
+    found = []
+    for st, cc, sample in (REPEATING if candidates is None else candidates):
+        if st != step or cc != c:
+            continue
+        cr, ci = sample if c is None else c
+        r, i = sample
+        zs, norms = [], []
+        for _ in range(121):
+            r, i, m = plot.step(lib, cr, ci, r, i, **step)
+            zs.append((r, i))
+            norms.append(m)
+        bits = [np.array(z).tobytes() for z in zs]                       # bits[k - 1] is z_k
+        if max(norms) > 4.0 or bits[119] != bits[59]:
+            continue
+        period = 1 if bits[60] == bits[59] else 2
+        assert bits[59 + period] == bits[59]
+        found.append((sample, period, 4.0 in norms))
+    return found
+
+
+def c_plane_edges(box, w, h):
+    """On a canvas with dyadic pixels under plot.C_PLANE, where (u, v) of every orbit point is the sample itself: for
+    each axis the coordinate on min, on an inner pixel edge and on max, each with the grid point one step below it ->
+    [(axis, name, on, below)]."""
+    out = []
+    for axis, (lo, hi, n) in enumerate(((box[0], box[1], w), (box[2], box[3], h))):
+        inner = lo + (n // 3) * ((hi - lo) / n)
+        for name, edge in (("min", lo), ("inner", inner), ("max", hi)):
+            out.append((axis, name, edge, grid_point(grid_index(edge) - 1)))
+    return out
+
+
+def projected_orbit(lib, projection, sample, n, c=None, **step):
+    """(u_k, v_k) of z_1 .. under plot.point, the escaping point included -> (u array, v array, end)."""
+    points, end = orbit_of(lib, sample, n, c, **step)
+    cr, ci = sample if c is None else c
+    uv = np.array([plot.point(lib, projection, r, i, cr, ci) for r, i in points])
+    return uv[:, 0], uv[:, 1], end
+
+
+def hologram_canvases(lib, w, h):
+    """pixel_edge_canvases on the plotted coordinates of one planted orbit (end 61) under plot.HOLOGRAM, an irrational
+    projection -> (sample, (u, v), {kind: [boxes]})."""
+    sample = with_end(lib, 61)
+    u, v, end = projected_orbit(lib, plot.HOLOGRAM, sample, 61)
+    assert end == 61
+    return sample, (u, v), pixel_edge_canvases((u, v), w, h, limit=2)
+
+
+# ---- the frames render's point queue, modelled (draw_frames.hip, FramesMode::converged and ::drain) -------------------------
+
+
+def queue_fills(ends, min_iter=1):
+    """The wave's LDS queue under one planted sample per lane: ends[lane] is the lane's `end`, None or an end below
+    min_iter + 1 for a lane that notes nothing (a filler, a sample that never escapes).  By the scheduler's round rule a lane
+    that escapes at step n iterates ceil(n / 12) rounds and replays from the next: in replay round j (0-based) it notes a
+    point at hook t (0 .. 11) iff 12 j + t < n.  At every hook count += lanes noting; a count >= 64 drains the newest 64.
+    -> (the count before each drain, the remainder drained at `last`)."""
+    fills, count, hook = [], 0, {}
+    for n in ends:
+        if n is None or n - 1 < min_iter:
+            continue
+        first = -(-n // ROUND)                      # rounds spent iterating
+        for p in range(n):
+            at = (first + p // ROUND) * ROUND + p % ROUND
+            hook[at] = hook.get(at, 0) + 1
+    for at in sorted(hook):
+        assert hook[at] <= 64
+        count += hook[at]
+        if count >= 64:
+            fills.append(count)
+            count -= 64
+    return fills, count
+
+
+# ---- the cases both plotted suites use (tests/test_planted_plot_host.py, tests/test_gpu_planted_plot*.py) -------------------
+
+ENDS = (1, 12, 13, 60, 61, 120, 121)               # a round's last step and the next round's first, likewise for a chunk and two
+SHAPES = ("lane0", "lane63", "all64")
+WIDE_BOX = (-4.0, 4.0, -3.0, 3.0)                  # 64 x 48 pixels of 1/8: z = 2 (c = -2, z_1 of c = 1) is on it
+
+
+def lanes(edge, threads=64, shape="lane0", filler=FILLER):
+    """One sample per subsequence: the edge sample alone in lane 0 or in lane 63 of the first wave, or in all its 64
+    lanes; fillers everywhere else."""
+    points = [filler] * threads
+    for k in {"lane0": (0,), "lane63": (63,), "all64": range(64)}[shape]:
+        points[k] = edge
+    return points
+
+
+def cycled(samples, threads):
+    return [samples[k % len(samples)] for k in range(threads)]
+
+
+def windows_of(end):
+    """(max_iter, min_iter) around an orbit's `end`, with what becomes of it: k = end - 1 is the last k accepted under
+    max_iter = end; at max_iter = end - 1 the orbit never escapes; min_iter = end - 1 accepts k and min_iter = end does not.
+    Wherever it can be min_iter is at least 1, so that the fillers are too fast."""
+    return [(end, min(1, end - 1), "recorded"), (end - 1, min(1, max(end - 2, 0)), "never_escaped"),
+            (end + 7, end - 1, "recorded"), (end + 7, end, "too_fast")]
+
+
+def model_counters(ends, max_iter, min_iter):
+    """The counters of one launch of one sample per subsequence from the samples' `end`s alone (None: never escapes
+    within any max_iter; "rejected": dropped unseen), by the definition: what planted counts must give exactly."""
+    c = dict.fromkeys(("samples", "rejected", "never_escaped", "too_fast", "recorded", "iterate_steps", "replay_steps"), 0)
+    for end in ends:
+        c["samples"] += 1
+        if end == "rejected":
+            c["rejected"] += 1
+        elif end is None or end > max_iter:
+            c["never_escaped"] += 1
+            c["iterate_steps"] += max(max_iter, 0)
+        else:
+            c["iterate_steps"] += end
+            if end - 1 < min_iter:
+                c["too_fast"] += 1
+            else:
+                c["recorded"] += 1
+                c["replay_steps"] += end
+    return c
+
+
+# The depth windows along `cr`.  The first two are tests/test_gpu_depth.py's (test_the_slice_arithmetic_is_the_row_arithmetic):
+# their deltas, 1/2 and 1/4, are both powers of two, so both take the reciprocal; the third (test_gpu_depth.py's
+# mandelbrot_cr_inner) has delta 0.18 and takes the division, and at c_re = -0.54 the two paths would differ.
+SLICE_WINDOWS = {"reciprocal_5": (-2.0, 0.5, 5), "reciprocal_8": (-1.0, 1.0, 8), "division_5": (-0.9, 0.0, 5),
+                 "one": (-1.0, 1.0, 1), "most": (-1.0, 1.0, 256)}
+C_BOX = (0.5, 0.75, 0.25, 0.4375)  # 64 x 48 pixels of 2^-8, right of the cardioid: every c on it escapes within a few steps
+
+
+def c_plane_sample(axis, coordinate):
+    """The sample of C_BOX with the given coordinate on one axis and an inner one, off every pixel edge, on the other."""
+    return (coordinate, 0.25 + 0.09375 + 5 * GRID) if axis == 0 else (0.5 + 0.109375 + 3 * GRID, coordinate)
+
+
+def consults_the_map(max_iter, min_iter):
+    """Whether the projected product kernel of the Mandelbrot step on a sampled c is given the interior map: where the
+    normal path has a LONG stage (capi.hip plot_args; draw_wave.hip plan_stages)."""
+    mid = 16 if min_iter <= HEAD_STEPS + MID_MIN else MID_MIN + (min_iter - HEAD_STEPS - MID_MIN) % CHUNK
+    return max_iter > HEAD_STEPS + mid
+
+
+def accepted_beside(lib, c_re, lo=2, hi=400):
+    """An imaginary part for the given real parts (a pair of grid neighbours) with which each is a sample the Mandelbrot
+    render accepts under min_iter = 1: not rejected, lo <= end <= hi -> (c_im, [ends])."""
+    for c_im in (1.125, 0.875, 0.75, 0.6875, 0.625, 0.5, 0.40625, 0.3125, 0.125, 0.0):
+        ends = [end_of(lib, (x, c_im), hi + 1) for x in c_re]
+        if all(e is not None and lo <= e <= hi for e in ends) and not any(rejected(x, c_im) for x in c_re):
+            return c_im, ends
+    raise ValueError("no accepted sample with real part %r" % (c_re,))

@@ -39,9 +39,17 @@ def variant_of(cb, base, degree=2, ship=False, formula=0):
             | (cb.CB_KERNEL_FORMULA(formula) if formula else 0))
 
 
+def write_states(run, states):
+    """An oracle state array (tests/planted_samples.py plants its first samples) written over the fresh generators of a
+    Launches, as the library's six planes."""
+    assert len(states) == run.threads
+    run.states.copy_(run.torch.from_numpy(planar_states(states).view(np.uint8)).to(run.dev))
+
+
 def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, c=None, lut=None, projection=plot.IDENTITY,
-                 depth=None, depth_lut=None):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) through the entry
+                 depth=None, depth_lut=None, states=None):
+    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)), or on the given
+    oracle `states` written over them (they are left as they were), through the entry
     point the arguments pick -- with depth = (row, min, max, slices) cb_draw_buddhabrot_depth_palette (depth_lut, a table
     of `slices` entries) or cb_draw_buddhabrot_depth; else cb_draw_buddhabrot_palette with a table, cb_draw_buddhabrot_julia
     with a c, else cb_draw_buddhabrot_projected, or, projection=None, the normal path: cb_draw_buddhabrot without workspace
@@ -53,6 +61,8 @@ def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, variant, 
     planes = 3 if lut is not None else None if depth is None else dd.slices
     run = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, planes=planes,
                    tables={} if lut is None else {"lut": lut})
+    if states is not None:
+        write_states(run, states)
     args = dict(iterations=cb.IterationControl(max_iter, min_iter), projection=projection)
     if lut is not None:
         args.update(d_lut=run.tables["lut"].data_ptr(), n_entries=run.tables["lut"].numel())
@@ -77,21 +87,25 @@ ThreeWays = collections.namedtuple("ThreeWays", "want wc product lockstep extra"
 
 
 def three_ways(cb, ref, oracle, kernels, map_level, w, h, box, max_iter, min_iter, threads, launches, *, degree=2,
-               ship=False, formula=0, c=None, lut=None, device_lut=None, projection=plot.IDENTITY, depth=None):
+               ship=False, formula=0, c=None, lut=None, device_lut=None, projection=plot.IDENTITY, depth=None, states=None):
     """Product == lock-step == restatement, bit for bit on histogram, generator states and the counters of SAME.
     kernels: the family's (product, lock-step) values of cb_debug_last_draw_kernel.  map_level: 0, or the least
     interior-map level the product kernel's launch must report (the lock-step kernel's reports 0 always); None is
     cb_draw_buddhabrot_projected's rule, 1 exactly under the Mandelbrot step on a sampled c.  device_lut: the table the
-    GPU is given where it is not `lut` itself.  depth: (row, min, max, slices); lut is then the table by slice."""
+    GPU is given where it is not `lut` itself.  depth: (row, min, max, slices); lut is then the table by slice.  states: an
+    oracle state array (planted first samples) in the place of the fresh generators, left as it was; the rule that only the
+    Mandelbrot step on a sampled c rejects then holds one way only (planted samples need not reach a shape)."""
     launches = list(launches)
-    st = oracle.init_states(1337, 0, threads)
+    before = states
+    st = oracle.init_states(1337, 0, threads) if before is None else before.copy()
     extra = {}
     kw = dict(projection=projection, degree=degree, ship=ship, formula=formula, c=c, box=box, omp_threads=omp_threads())
     want, wc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, lut=lut, depth=depth, states=st, extra=extra, **kw)
     assert wc["samples"] == threads * sum(launches) and int(want.sum()) == wc["increments"]
     assert want.shape == ((3, h, w) if lut is not None else (h, w) if depth is None else (depth[3], h, w))
     mandelbrot = c is None and not formula and degree == 2 and not ship
-    assert (wc["rejected"] > 0) == mandelbrot  # nothing is rejected but under the reference's own step on a sampled c
+    # nothing is rejected but under the reference's own step on a sampled c
+    assert (wc["rejected"] > 0) == mandelbrot or (before is not None and wc["rejected"] == 0)
     if map_level is None:
         map_level = 1 if mandelbrot else 0
     table = lut if device_lut is None else device_lut
@@ -100,7 +114,7 @@ def three_ways(cb, ref, oracle, kernels, map_level, w, h, box, max_iter, min_ite
         hist, cnt, launched, states = gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches,
                                                    variant_of(cb, base, degree, ship, formula), c,
                                                    table if depth is None else None, projection, depth,
-                                                   None if depth is None else table)
+                                                   None if depth is None else table, states=before)
         print(kernel, cnt)
         assert launched == kernel
         assert cnt["status"] == 0
@@ -122,9 +136,11 @@ def three_ways(cb, ref, oracle, kernels, map_level, w, h, box, max_iter, min_ite
         # restatement saw repeat a point at a chunk boundary offers it -- under a table too: nothing is skipped for a colour
         print("chunk_repeats", extra["chunk_repeats"], "product skipped_steps", product["skipped_steps"])
         assert extra["zero_entry_steps"] == 0
-        assert (product["skipped_steps"] > 0) == (mandelbrot or extra["chunk_repeats"] > 0)
+        if before is None:
+            assert (product["skipped_steps"] > 0) == (mandelbrot or extra["chunk_repeats"] > 0)
     if depth is not None and lut is not None:  # against the restatement of the depth alone
-        planes, vc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, depth=depth, **kw)
+        planes, vc = plot.draw(ref, w, h, max_iter, min_iter, threads, launches, depth=depth,
+                               states=None if before is None else before.copy(), **kw)
         assert np.array_equal(want, plot.combine(lut, planes))
         assert {k: vc[k] for k in NOT_INCREMENTS} == {k: wc[k] for k in NOT_INCREMENTS}
         extra["planes"] = planes

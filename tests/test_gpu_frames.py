@@ -39,10 +39,13 @@ def matrices(m):
 
 
 def frames_launches(cb, variant, mats, c=None, w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN, threads=THREADS,
-                    launches=LAUNCHES):
-    """`launches` on fresh generators through cb_draw_buddhabrot_frames -> (hist [F, h, w], counters, kernel, states)."""
+                    launches=LAUNCHES, states=None):
+    """`launches` on fresh generators, or on the given oracle `states` written over them, through
+    cb_draw_buddhabrot_frames -> (hist [F, h, w], counters, kernel, states)."""
     mats = matrices(mats)
     bufs = plot_harness.Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, planes=mats.shape[0])
+    if states is not None:
+        plot_harness.write_states(bufs, states)
     d_frames = bufs.on_device(mats.view(np.uint64), np.uint64)  # kept alive to the read
     out = bufs.launches(cb.draw_buddhabrot_frames, launches, variant, iterations=cb.IterationControl(max_iter, min_iter),
                         d_frames=d_frames.data_ptr(), n_frames=mats.shape[0], julia_c=c).read()
