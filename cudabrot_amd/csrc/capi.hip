@@ -348,20 +348,20 @@ struct cb_renderer {
   // has kind_row(what).planes planes, or n_channels.
   Plotted what;
   std::vector<double> *frames;  // kFrames: what.d_frames on the host (cb_renderer_frames)
-  // The white clip ("White clip" of include/cudabrot_amd.h): an output setting the image calls read, 0 = off, and what
-  // the last image call made with it found (cb_renderer_last_white).  No launch, histogram or generator knows of it.
+  // The white clip ("White clip" of include/cudabrot_amd.h): an output setting the image calls read, 0 = off.  No launch,
+  // histogram or generator knows of it.
   double white_clip;
-  cb::WhitePoint last_white;
   // The density filter ("Density filter" of include/cudabrot_amd.h): an output setting too, radius 0 = off, with the
   // table cb_density_thresholds made of it.
   int density_radius;
   double density_alpha;
   uint64_t density_n0;
   uint64_t density_thresholds[CB_DENSITY_MAX_RADIUS + 1];
-  // Equalisation ("Equalised image" of include/cudabrot_amd.h): an output setting as well, never on beside a white clip,
-  // and what the last image call made with it found (cb_renderer_last_equalize).
+  // Equalisation ("Equalised image" of include/cudabrot_amd.h): an output setting as well, never on beside a white clip.
   bool equalize;
-  cb::Equalized last_equalize;
+  // What the last image call found under the exposure set now (cb_renderer_last_white, cb_renderer_last_equalize): the
+  // two setters clear it.
+  cb::Exposed last_exposed;
 };
 
 namespace {
@@ -836,31 +836,19 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
   return 0;
 }
 
-// cb_tone_map_device over `rows` rows of w counters at `hist` -- or, on a renderer with a white clip, the clipped map over
-// the same array, whose white point the renderer keeps; or, on an equalised one, the equalised map, likewise.
+// The tone map of `rows` rows of w counters at `hist`, exposed as the renderer is set: plainly, against the white point of
+// its clip, or equalised.  The renderer keeps what the call found.
 int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
                       uint64_t *max_out, double *scale_out) {
-  if (r->equalize) {
-    if (mode != CB_TONE_AUTO && mode != CB_TONE_LUT && mode != CB_TONE_THRESHOLDS) return (int) hipErrorInvalidValue;
-    cb::Equalized found = {0, 0, 0, 0};
-    const int rc = cb::tone_map_equalized(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma,
-                                          d_gray_be, &found, r->stream);
-    if (rc) return rc;
-    r->last_equalize = found;
-    if (max_out) *max_out = found.max;  // what the unflagged call reports
-    if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.max);
-    return 0;
-  }
-  if (r->white_clip == 0.0) {
-    return cb_tone_map_device(hist, r->dims.w, rows, gamma, mode, d_gray_be, max_out, scale_out, r->stream);
-  }
-  cb::WhitePoint found = {0, 0, 0, 0};
-  const int rc = cb::tone_map_white(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma, mode,
-                                r->white_clip, d_gray_be, &found, r->stream);
+  const cb::Exposure how = {r->equalize ? cb::Exposure::kEqualized
+                                        : (r->white_clip != 0.0 ? cb::Exposure::kWhiteClip : cb::Exposure::kPlain),
+                            r->white_clip};
+  const int rc = cb::tone_map_exposed(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma, mode, how,
+                                      d_gray_be, &r->last_exposed, r->stream);
   if (rc) return rc;
-  r->last_white = found;
-  if (max_out) *max_out = found.max;  // the true maximum, and the scale applied
-  if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.white);
+  const cb::Exposed &e = r->last_exposed;
+  if (max_out) *max_out = e.max;  // the true maximum, and the scale applied
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) (how.kind == cb::Exposure::kWhiteClip ? e.white : e.max));
   return 0;
 }
 
@@ -1925,7 +1913,7 @@ int cb_renderer_set_white_clip(cb_renderer *r, double percent) {
   if (!r || !cb_white_clip_ok(percent)) return (int) hipErrorInvalidValue;
   if (percent != 0.0 && r->equalize) return (int) hipErrorInvalidValue;  // one exposure at a time ("Equalised image")
   r->white_clip = percent;
-  r->last_white = {0, 0, 0, 0};
+  if (!r->equalize) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (an equalised renderer keeps what it found: nothing changed)
   return 0;
 }
 
@@ -1956,16 +1944,16 @@ int cb_renderer_density_filter(const cb_renderer *r, int *radius_out, double *al
 
 int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *lit_out, uint64_t *clipped_out) {
   if (!r || !white_out || !lit_out || !clipped_out) return (int) hipErrorInvalidValue;
-  *white_out = r->last_white.white;
-  *lit_out = r->last_white.lit;
-  *clipped_out = r->last_white.clipped;
+  *white_out = r->last_exposed.white;
+  *lit_out = r->equalize ? 0 : r->last_exposed.lit;  // (an equalised image counts its lit pixels too)
+  *clipped_out = r->last_exposed.clipped;
   return 0;
 }
 
 int cb_renderer_set_equalize(cb_renderer *r, int on) {
   if (!r || (on != 0 && r->white_clip != 0.0)) return (int) hipErrorInvalidValue;
   r->equalize = on != 0;
-  r->last_equalize = {0, 0, 0, 0};
+  if (r->white_clip == 0.0) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (likewise a clipped one)
   return 0;
 }
 
@@ -1973,9 +1961,9 @@ int cb_renderer_equalize(const cb_renderer *r) { return (r && r->equalize) ? 1 :
 
 int cb_renderer_last_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *keys_out, uint64_t *levels_out) {
   if (!r || !lit_out || !keys_out || !levels_out) return (int) hipErrorInvalidValue;
-  *lit_out = r->last_equalize.lit;
-  *keys_out = r->last_equalize.keys;
-  *levels_out = r->last_equalize.levels;
+  *lit_out = r->equalize ? r->last_exposed.lit : 0;  // (so does a clipped one)
+  *keys_out = r->last_exposed.keys;
+  *levels_out = r->last_exposed.levels;
   return 0;
 }
 

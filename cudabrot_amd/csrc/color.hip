@@ -9,11 +9,10 @@
 //   3. one kernel stretches, composes and writes the PPM body, 6 bytes per pixel, 8 pixels per lane (three 16-byte
 //      stores).
 // Buddhabrot planes are mostly zeros, so one bin takes most of the increments: the histogram adds are aggregated per
-// wave first (the lanes that share the first active lane's bin add once, by popcount), the rest are LDS atomics.
+// wave first (counter_sweep.h's wave_count), the rest are LDS atomics.
 #include <stdlib.h>
 
-#include "color_math.h"
-#include "kernels.h"
+#include "counter_sweep.h"
 
 namespace cb {
 
@@ -22,21 +21,6 @@ namespace {
 constexpr uint32_t kColorThreads = 256;
 constexpr uint32_t kLevelBlocksPerPlane = 1024;
 constexpr uint32_t kComposeBlocks = 4096;
-
-// Lanes with `active` add 1 to lds[bin].  Every lane of the wave takes part (the callers keep it converged).
-__device__ __forceinline__ void wave_count(uint32_t *lds, uint32_t bin, bool active) {
-  const unsigned long long act = __ballot(active);
-  if (act == 0ull) return;
-  const int first = __ffsll((long long) act) - 1;
-  const uint32_t lead = (uint32_t) __builtin_amdgcn_readlane((int) bin, first);
-  const bool same = active && bin == lead;
-  const unsigned long long mate = __ballot(same);
-  if (same) {
-    if ((int) (threadIdx.x & 63u) == first) atomicAdd(&lds[lead], (uint32_t) __popcll(mate));
-  } else if (active) {
-    atomicAdd(&lds[bin], 1u);
-  }
-}
 
 __device__ __forceinline__ void flush_bins(const uint32_t *lds, unsigned long long *bins) {
   const uint32_t c = lds[threadIdx.x];
@@ -164,19 +148,6 @@ uint32_t blocks_for(unsigned long long groups, uint32_t cap) {
   return (uint32_t) (b == 0 ? 1 : (b > cap ? cap : b));
 }
 
-#define CB_COLOR_TRY(expr)                  \
-  do {                                      \
-    const hipError_t e_ = (expr);           \
-    if (e_ != hipSuccess) return (int) e_;  \
-  } while (0)
-
-struct DeviceBuffer {  // freed on every return path
-  void *p = nullptr;
-  ~DeviceBuffer() {
-    if (p) (void) hipFree(p);
-  }
-};
-
 }  // namespace
 
 }  // namespace cb
@@ -193,26 +164,27 @@ extern "C" int cb_compose_color_device(const cb_pixel *const d_hist[3], int w, i
   const unsigned long long stride = (n + 63ull) & ~63ull;  // whole 16-byte groups, aligned planes
   const unsigned long long groups = (n + 7ull) / 8ull;
   DeviceBuffer gray, bins;
-  CB_COLOR_TRY(hipMalloc(&gray.p, 3ull * stride * sizeof(uint16_t)));
+  CB_HIP_TRY(hipMalloc(&gray.p, 3ull * stride * sizeof(uint16_t)));
   uint16_t *d_gray = static_cast<uint16_t *>(gray.p);
   for (int j = 0; j < 3; ++j) {
-    const int rc = cb_tone_map_device(d_hist[j], w, h, gamma, tone_mode, d_gray + (unsigned long long) j * stride,
-                                      nullptr, nullptr, stream_v);
+    Exposed found;
+    const int rc = tone_map_exposed(reinterpret_cast<const unsigned long long *>(d_hist[j]), w, h, gamma, tone_mode,
+                                    {Exposure::kPlain, 0.0}, d_gray + (unsigned long long) j * stride, &found, stream);
     if (rc) return rc;
   }
 
   // levels: [3][256] high bytes, then [3][2][256] low bytes of the black and white buckets
   constexpr size_t kCoarse = 3 * 256, kFine = 3 * 2 * 256;
-  CB_COLOR_TRY(hipMalloc(&bins.p, (kCoarse + kFine) * sizeof(unsigned long long)));
+  CB_HIP_TRY(hipMalloc(&bins.p, (kCoarse + kFine) * sizeof(unsigned long long)));
   unsigned long long *d_coarse = static_cast<unsigned long long *>(bins.p);
   unsigned long long *d_fine = d_coarse + kCoarse;
-  CB_COLOR_TRY(hipMemsetAsync(bins.p, 0, (kCoarse + kFine) * sizeof(unsigned long long), stream));
+  CB_HIP_TRY(hipMemsetAsync(bins.p, 0, (kCoarse + kFine) * sizeof(unsigned long long), stream));
   const dim3 level_grid(blocks_for(groups, kLevelBlocksPerPlane), 3);
   hipLaunchKernelGGL(color_coarse_kernel, level_grid, dim3(kColorThreads), 0, stream, d_gray, stride, n, d_coarse);
-  CB_COLOR_TRY(hipGetLastError());
+  CB_HIP_TRY(hipGetLastError());
   uint64_t coarse[kCoarse], fine[kFine];
-  CB_COLOR_TRY(hipMemcpyAsync(coarse, d_coarse, sizeof(coarse), hipMemcpyDeviceToHost, stream));
-  CB_COLOR_TRY(hipStreamSynchronize(stream));
+  CB_HIP_TRY(hipMemcpyAsync(coarse, d_coarse, sizeof(coarse), hipMemcpyDeviceToHost, stream));
+  CB_HIP_TRY(hipStreamSynchronize(stream));
 
   uint64_t nb = 0, nw = 0;
   color_ranks(n, p, &nb, &nw);
@@ -226,9 +198,9 @@ extern "C" int cb_compose_color_device(const cb_pixel *const d_hist[3], int w, i
     white_rank[j] = nw - above;
   }
   hipLaunchKernelGGL(color_fine_kernel, level_grid, dim3(kColorThreads), 0, stream, d_gray, stride, n, buckets, d_fine);
-  CB_COLOR_TRY(hipGetLastError());
-  CB_COLOR_TRY(hipMemcpyAsync(fine, d_fine, sizeof(fine), hipMemcpyDeviceToHost, stream));
-  CB_COLOR_TRY(hipStreamSynchronize(stream));
+  CB_HIP_TRY(hipGetLastError());
+  CB_HIP_TRY(hipMemcpyAsync(fine, d_fine, sizeof(fine), hipMemcpyDeviceToHost, stream));
+  CB_HIP_TRY(hipStreamSynchronize(stream));
 
   ComposeArgs a;
   a.compose = p->compose;
@@ -245,7 +217,7 @@ extern "C" int cb_compose_color_device(const cb_pixel *const d_hist[3], int w, i
   }
   hipLaunchKernelGGL(color_compose_kernel, dim3(blocks_for(groups, kComposeBlocks)), dim3(kColorThreads), 0, stream,
                      d_gray, stride, n, a, d_rgb_be);
-  CB_COLOR_TRY(hipGetLastError());
-  CB_COLOR_TRY(hipStreamSynchronize(stream));  // before the padded planes are freed
+  CB_HIP_TRY(hipGetLastError());
+  CB_HIP_TRY(hipStreamSynchronize(stream));  // before the padded planes are freed
   return 0;
 }

@@ -16,7 +16,7 @@
 //
 // The refusal of a counter >= 2^55 is decided by a maximum pass in front (exposure.hip's sweep), before anything is written.
 
-#include "kernels.h"
+#include "counter_sweep.h"
 
 namespace cb {
 
@@ -151,7 +151,7 @@ extern "C" int cb_density_filter_device(const cb_pixel *d_hist, int w, int h, in
   if (((reinterpret_cast<uintptr_t>(d_hist) | reinterpret_cast<uintptr_t>(d_out)) & 7u) != 0u) return (int) hipErrorInvalidValue;
   const unsigned long long n = (unsigned long long) w * (unsigned long long) h * (unsigned long long) planes;
   const unsigned long long tiles_y = ((unsigned long long) h + cb::kTileH - 1) / cb::kTileH;
-  if (n > (1ull << 40) || tiles_y > 65535ull || planes > 65535) return (int) hipErrorInvalidValue;  // (the grid's limits)
+  if (n > cb::kMaxCounters || tiles_y > 65535ull || planes > 65535) return (int) hipErrorInvalidValue;  // (the grid's limits)
   // the largest counter, before anything is written
   uint64_t white = 0, lit = 0, clipped = 0, max = 0;
   const int rc = cb::white_count_device(reinterpret_cast<const unsigned long long *>(d_hist), n, 0.0, &white, &lit, &clipped,
@@ -168,7 +168,6 @@ extern "C" int cb_density_filter_device(const cb_pixel *d_hist, int w, int h, in
   for (int r = 1; r <= radius; ++r) a.thresholds[r] = (uint32_t) thresholds[r];
   const dim3 grid(((uint32_t) w + cb::kTileW - 1) / cb::kTileW, (uint32_t) tiles_y, (uint32_t) planes);
   hipLaunchKernelGGL(cb::density_filter_kernel, grid, dim3(cb::kDensityThreads), 0, stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int) e;
+  CB_HIP_TRY(hipGetLastError());
   return (int) hipStreamSynchronize(stream);
 }

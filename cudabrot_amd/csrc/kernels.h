@@ -430,30 +430,30 @@ struct PeriodArgs {
 };
 hipError_t launch_draw_periods(const PeriodArgs &a, bool lockstep, hipStream_t stream);
 
-// tonemap.hip: the tone map of n device counters against `top` -- the table over [0, top] or the thresholds, as `mode`
-// (CB_TONE_*) and `top` choose -- into big-endian u16.  clamp: counts above `top` exist and take top's value (the white
-// clip); without it `top` is the largest counter.  Synchronises `stream`.
-int tone_map_against(const unsigned long long *hist, unsigned long long n, unsigned long long top, bool clamp, double gamma,
-                     int mode, uint16_t *d_gray_be, hipStream_t stream);
+// How an image is exposed: against its largest counter, against the white point of a clip of `clip_percent` ("White
+// clip" of include/cudabrot_amd.h), or by the rank of its counters ("Equalised image").
+struct Exposure {
+  enum Kind { kPlain, kWhiteClip, kEqualized } kind;
+  double clip_percent;  // kWhiteClip's
+};
+// What exposing found: max always; white, lit and clipped under a white clip; lit, keys and levels equalised; 0 else.
+struct Exposed {
+  uint64_t max, white, lit, clipped, keys, levels;
+};
+// tonemap.hip: finds the top of w x h device counters as `how` says, maps them into big-endian u16 -- the table or the
+// thresholds, as `mode` (CB_TONE_*) and the top choose; an equalised image has one form -- and reports: what
+// cb_tone_map_device, cb_tone_map_device_white and cb_tone_map_device_equalized do, and what a renderer keeps for
+// cb_renderer_last_white and cb_renderer_last_equalize.  *found is written on success only.  Synchronises `stream`.
+int tone_map_exposed(const unsigned long long *hist, int w, int h, double gamma, int mode, const Exposure &how,
+                     uint16_t *d_gray_be, Exposed *found, hipStream_t stream);
 // exposure.hip: cb_white_count_device, and the largest counter beside its three numbers (max_out may be null).
 int white_count_device(const unsigned long long *hist, unsigned long long n, double clip_percent, uint64_t *white_out,
                        uint64_t *lit_out, uint64_t *clipped_out, uint64_t *max_out, hipStream_t stream);
-// exposure.hip: cb_tone_map_device_white with everything the select found: what a renderer keeps for
-// cb_renderer_last_white.
-struct WhitePoint {
-  uint64_t max, white, lit, clipped;
-};
-int tone_map_white(const unsigned long long *hist, int w, int h, double gamma, int mode, double clip_percent,
-                   uint16_t *d_gray_be, WhitePoint *found, hipStream_t stream);
-// equalize.hip: cb_equalize_bins_device, and cb_tone_map_device_equalized with everything it found: what a renderer
-// keeps for cb_renderer_last_equalize.
+// equalize.hip: cb_equalize_bins_device, and the lookup of n counters' keys in a host table of CB_EQUALIZE_KEYS values.
 int equalize_bins_device(const unsigned long long *hist, unsigned long long n, uint64_t *bins_out_host, uint64_t *lit_out,
                          uint64_t *max_out, hipStream_t stream);
-struct Equalized {
-  uint64_t max, lit, keys, levels;
-};
-int tone_map_equalized(const unsigned long long *hist, int w, int h, double gamma, uint16_t *d_gray_be, Equalized *found,
-                       hipStream_t stream);
+int equalize_map_device(const unsigned long long *hist, unsigned long long n, const uint16_t *table_host, uint16_t *d_gray_be,
+                        hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

@@ -22,7 +22,7 @@
 
 #include <vector>
 
-#include "kernels.h"
+#include "counter_sweep.h"
 
 extern "C" uint16_t cb_tone_value(uint64_t count, uint64_t max, double gamma);
 
@@ -30,15 +30,14 @@ namespace cb {
 
 namespace {
 
-constexpr uint32_t kToneThreads = 256;
 constexpr uint64_t kLutMaxEntries = 1ull << 24;
 
-__global__ void __launch_bounds__(kToneThreads) hist_max_kernel(const unsigned long long *hist,
-                                                                unsigned long long n,
-                                                                unsigned long long *out) {
+__global__ void __launch_bounds__(kSweepThreads) hist_max_kernel(const unsigned long long *hist,
+                                                                 unsigned long long n,
+                                                                 unsigned long long *out) {
   unsigned long long m = 0;
-  const unsigned long long stride = (unsigned long long) gridDim.x * kToneThreads;
-  for (unsigned long long i = (unsigned long long) blockIdx.x * kToneThreads + threadIdx.x; i < n;
+  const unsigned long long stride = (unsigned long long) gridDim.x * kSweepThreads;
+  for (unsigned long long i = (unsigned long long) blockIdx.x * kSweepThreads + threadIdx.x; i < n;
        i += stride) {
     const unsigned long long v = hist[i];
     m = v > m ? v : m;
@@ -53,29 +52,14 @@ __global__ void __launch_bounds__(kToneThreads) hist_max_kernel(const unsigned l
   }
 }
 
-__device__ __forceinline__ uint16_t big_endian(uint32_t v) {
-  return (uint16_t) (((v & 0xffu) << 8) | ((v >> 8) & 0xffu));
-}
-
-// two pixels per thread: one 4-byte store.  kClamp (the white clip, exposure.hip): the table ends at `top` and every
-// larger count reads its last entry; without it `top` is not read and the kernel is the one it was.
+// kClamp (the white clip, exposure.hip): the table ends at `top` and every larger count reads its last entry; without it
+// `top` is not read and the kernel is the one it was.
 template <bool kClamp>
-__global__ void __launch_bounds__(kToneThreads) tone_lut_kernel(const unsigned long long *hist,
-                                                                unsigned long long n,
-                                                                const uint16_t *lut, unsigned long long top,
-                                                                uint16_t *out_be) {
-  const auto at = [top](unsigned long long c) { return kClamp ? (c < top ? c : top) : c; };
-  const unsigned long long stride = (unsigned long long) gridDim.x * kToneThreads * 2ull;
-  for (unsigned long long i = ((unsigned long long) blockIdx.x * kToneThreads + threadIdx.x) * 2ull;
-       i < n; i += stride) {
-    const uint32_t a = big_endian(lut[at(hist[i])]);
-    if (i + 1 < n) {
-      const uint32_t b = big_endian(lut[at(hist[i + 1])]);
-      *reinterpret_cast<uint32_t *>(out_be + i) = a | (b << 16);  // n even or not: i is even
-    } else {
-      out_be[i] = (uint16_t) a;
-    }
-  }
+__global__ void __launch_bounds__(kSweepThreads) tone_lut_kernel(const unsigned long long *hist,
+                                                                 unsigned long long n,
+                                                                 const uint16_t *lut, unsigned long long top,
+                                                                 uint16_t *out_be) {
+  map_pairs(hist, n, out_be, [=](unsigned long long c) { return lut[kClamp ? (c < top ? c : top) : c]; });
 }
 
 // thr[k], k in [0, 65536): smallest count whose value is >= k (thr[0] = 0; ~0 if none).  The value
@@ -94,41 +78,12 @@ __device__ __forceinline__ uint32_t value_by_thresholds(unsigned long long c,
   return lo;
 }
 
-__global__ void __launch_bounds__(kToneThreads) tone_thresholds_kernel(const unsigned long long *hist,
-                                                                       unsigned long long n,
-                                                                       const unsigned long long *thr,
-                                                                       uint16_t *out_be) {
-  const unsigned long long stride = (unsigned long long) gridDim.x * kToneThreads * 2ull;
-  for (unsigned long long i = ((unsigned long long) blockIdx.x * kToneThreads + threadIdx.x) * 2ull;
-       i < n; i += stride) {
-    const uint32_t a = big_endian(value_by_thresholds(hist[i], thr));
-    if (i + 1 < n) {
-      const uint32_t b = big_endian(value_by_thresholds(hist[i + 1], thr));
-      *reinterpret_cast<uint32_t *>(out_be + i) = a | (b << 16);
-    } else {
-      out_be[i] = (uint16_t) a;
-    }
-  }
+__global__ void __launch_bounds__(kSweepThreads) tone_thresholds_kernel(const unsigned long long *hist,
+                                                                        unsigned long long n,
+                                                                        const unsigned long long *thr,
+                                                                        uint16_t *out_be) {
+  map_pairs(hist, n, out_be, [=](unsigned long long c) { return value_by_thresholds(c, thr); });
 }
-
-uint32_t tone_grid(unsigned long long n) {
-  unsigned long long blocks = (n / 2 + kToneThreads) / kToneThreads;
-  if (blocks > 256ull * 16ull) blocks = 256ull * 16ull;
-  return (uint32_t) (blocks ? blocks : 1);
-}
-
-#define CB_TONE_TRY(expr)                           \
-  do {                                              \
-    const hipError_t e_ = (expr);                   \
-    if (e_ != hipSuccess) return (int) e_;          \
-  } while (0)
-
-struct DeviceBuffer {  // freed on every return path
-  void *p = nullptr;
-  ~DeviceBuffer() {
-    if (p) (void) hipFree(p);
-  }
-};
 
 // thr[k] = smallest count in [0, max] whose value is >= k, by bisection over the host map
 std::vector<unsigned long long> build_thresholds(unsigned long long max, double gamma) {
@@ -156,71 +111,90 @@ std::vector<unsigned long long> build_thresholds(unsigned long long max, double 
   return thr;
 }
 
-}  // namespace
+// The largest of n device counters (GetLinearColorScale, cudabrot.cu:425-439).
+int hist_max_device(const unsigned long long *hist, unsigned long long n, uint64_t *max_out, hipStream_t stream) {
+  DeviceBuffer d_max;
+  CB_HIP_TRY(hipMalloc(&d_max.p, sizeof(unsigned long long)));
+  CB_HIP_TRY(hipMemsetAsync(d_max.p, 0, sizeof(unsigned long long), stream));
+  hipLaunchKernelGGL(hist_max_kernel, dim3(pairs_grid(n)), dim3(kSweepThreads), 0, stream, hist, n,
+                     static_cast<unsigned long long *>(d_max.p));
+  CB_HIP_TRY(hipGetLastError());
+  CB_HIP_TRY(hipMemcpyAsync(max_out, d_max.p, sizeof(*max_out), hipMemcpyDeviceToHost, stream));
+  CB_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
 
 // The map against `top` on a device histogram of n counters: the table over [0, top] or the thresholds, as `mode` and
 // `top` choose.  clamp: counts above `top` exist (the white clip) and take top's value.
 int tone_map_against(const unsigned long long *hist, unsigned long long n, unsigned long long top, bool clamp, double gamma,
                      int mode, uint16_t *d_gray_be, hipStream_t stream) {
   DeviceBuffer d_table;
+  const dim3 grid(pairs_grid(n)), block(kSweepThreads);
   if (mode == CB_TONE_AUTO) mode = (top < kLutMaxEntries) ? CB_TONE_LUT : CB_TONE_THRESHOLDS;
   if (mode == CB_TONE_LUT) {
     if (top >= (1ull << 32)) return (int) hipErrorInvalidValue;  // not a sensible table
     std::vector<uint16_t> lut((size_t) top + 1);
     for (unsigned long long c = 0; c <= top; ++c) lut[(size_t) c] = cb_tone_value(c, top, gamma);
-    CB_TONE_TRY(hipMalloc(&d_table.p, lut.size() * sizeof(uint16_t)));
-    CB_TONE_TRY(hipMemcpyAsync(d_table.p, lut.data(), lut.size() * sizeof(uint16_t),
-                               hipMemcpyHostToDevice, stream));
-    if (clamp) {
-      hipLaunchKernelGGL(tone_lut_kernel<true>, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
-                         static_cast<const uint16_t *>(d_table.p), top, d_gray_be);
-    } else {
-      hipLaunchKernelGGL(tone_lut_kernel<false>, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
-                         static_cast<const uint16_t *>(d_table.p), top, d_gray_be);
-    }
-    CB_TONE_TRY(hipGetLastError());
-    CB_TONE_TRY(hipStreamSynchronize(stream));  // before the host table goes out of scope
+    CB_HIP_TRY(hipMalloc(&d_table.p, lut.size() * sizeof(uint16_t)));
+    CB_HIP_TRY(hipMemcpyAsync(d_table.p, lut.data(), lut.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
+    const auto lut_kernel = clamp ? tone_lut_kernel<true> : tone_lut_kernel<false>;
+    hipLaunchKernelGGL(lut_kernel, grid, block, 0, stream, hist, n, static_cast<const uint16_t *>(d_table.p), top, d_gray_be);
+    CB_HIP_TRY(hipGetLastError());
+    CB_HIP_TRY(hipStreamSynchronize(stream));  // before the host table goes out of scope
   } else {
     // No clamp here, with a white clip or without: thr[k] is the smallest count in [0, top] whose value reaches k, the
     // value of a count is the number of thresholds <= it, and every threshold is <= top -- so a count above top has
     // top's value already.
     const std::vector<unsigned long long> thr = build_thresholds(top, gamma);
-    CB_TONE_TRY(hipMalloc(&d_table.p, thr.size() * sizeof(unsigned long long)));
-    CB_TONE_TRY(hipMemcpyAsync(d_table.p, thr.data(), thr.size() * sizeof(unsigned long long),
-                               hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(tone_thresholds_kernel, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist,
-                       n, static_cast<const unsigned long long *>(d_table.p), d_gray_be);
-    CB_TONE_TRY(hipGetLastError());
-    CB_TONE_TRY(hipStreamSynchronize(stream));
+    CB_HIP_TRY(hipMalloc(&d_table.p, thr.size() * sizeof(unsigned long long)));
+    CB_HIP_TRY(hipMemcpyAsync(d_table.p, thr.data(), thr.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(tone_thresholds_kernel, grid, block, 0, stream, hist, n,
+                       static_cast<const unsigned long long *>(d_table.p), d_gray_be);
+    CB_HIP_TRY(hipGetLastError());
+    CB_HIP_TRY(hipStreamSynchronize(stream));
   }
   return 0;
+}
+
+}  // namespace
+
+// Find, map, report.  The find step is the kind's own: hist_max_kernel; the radix select of exposure.hip; the bins of
+// equalize.hip and the host's table of them.  Under a white clip the table or the thresholds are chosen by white, not by
+// the maximum.
+int tone_map_exposed(const unsigned long long *hist, int w, int h, double gamma, int mode, const Exposure &how,
+                     uint16_t *d_gray_be, Exposed *found, hipStream_t stream) {
+  if (!hist || !d_gray_be || !found || w <= 0 || h <= 0 || !tone_mode_ok(mode)) return (int) hipErrorInvalidValue;
+  const unsigned long long n = (unsigned long long) w * (unsigned long long) h;
+  Exposed e = {0, 0, 0, 0, 0, 0};
+  int rc;
+  if (how.kind == Exposure::kEqualized) {
+    std::vector<uint64_t> bins(CB_EQUALIZE_KEYS);
+    std::vector<uint16_t> table(CB_EQUALIZE_KEYS);
+    rc = equalize_bins_device(hist, n, bins.data(), &e.lit, &e.max, stream);
+    if (rc == 0) rc = cb_equalize_table(bins.data(), gamma, table.data(), &e.keys, &e.levels);
+    if (rc == 0) rc = equalize_map_device(hist, n, table.data(), d_gray_be, stream);
+  } else if (how.kind == Exposure::kWhiteClip) {
+    rc = white_count_device(hist, n, how.clip_percent, &e.white, &e.lit, &e.clipped, &e.max, stream);
+    if (rc == 0) rc = tone_map_against(hist, n, e.white, e.max > e.white, gamma, mode, d_gray_be, stream);
+  } else {
+    rc = hist_max_device(hist, n, &e.max, stream);
+    if (rc == 0) rc = tone_map_against(hist, n, e.max, false, gamma, mode, d_gray_be, stream);
+  }
+  if (rc == 0) *found = e;
+  return rc;
 }
 
 }  // namespace cb
 
 extern "C" int cb_tone_map_device(const cb_pixel *d_hist, int w, int h, double gamma, int mode,
                                   uint16_t *d_gray_be, uint64_t *max_out, double *scale_out,
-                                  void *stream_v) {
-  using namespace cb;
-  if (!d_hist || !d_gray_be || w <= 0 || h <= 0) return (int) hipErrorInvalidValue;
-  if (mode != CB_TONE_AUTO && mode != CB_TONE_LUT && mode != CB_TONE_THRESHOLDS) {
-    return (int) hipErrorInvalidValue;
-  }
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const unsigned long long n = (unsigned long long) w * (unsigned long long) h;
-  const unsigned long long *hist = reinterpret_cast<const unsigned long long *>(d_hist);
-  DeviceBuffer d_max;
-  unsigned long long max = 0;
-
-  // GetLinearColorScale, cudabrot.cu:425-439
-  CB_TONE_TRY(hipMalloc(&d_max.p, sizeof(unsigned long long)));
-  CB_TONE_TRY(hipMemsetAsync(d_max.p, 0, sizeof(unsigned long long), stream));
-  hipLaunchKernelGGL(hist_max_kernel, dim3(tone_grid(n)), dim3(kToneThreads), 0, stream, hist, n,
-                     static_cast<unsigned long long *>(d_max.p));
-  CB_TONE_TRY(hipGetLastError());
-  CB_TONE_TRY(hipMemcpyAsync(&max, d_max.p, sizeof(max), hipMemcpyDeviceToHost, stream));
-  CB_TONE_TRY(hipStreamSynchronize(stream));
-  if (max_out) *max_out = max;
-  if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);
-  return tone_map_against(hist, n, max, false, gamma, mode, d_gray_be, stream);
+                                  void *stream) {
+  cb::Exposed found;
+  const int rc = cb::tone_map_exposed(reinterpret_cast<const unsigned long long *>(d_hist), w, h, gamma, mode,
+                                      {cb::Exposure::kPlain, 0.0}, d_gray_be, &found, static_cast<hipStream_t>(stream));
+  if (rc) return rc;
+  if (max_out) *max_out = found.max;
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) found.max);
+  return 0;
 }
+

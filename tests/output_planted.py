@@ -5,7 +5,14 @@ tests/test_output_planted_host.py shows on the host functions alone that every p
 (tests/test_gpu_tonemap_planted.py, tests/test_gpu_color_planted.py) then compare the device byte for byte.
 
 The tone builders take the host map as a function `value(counts) -> u16 values` (host_map below), so that this module
-needs neither the library nor a device."""
+needs neither the library nor a device.
+
+It also holds what the GPU suites of the whole output stage share (the two above and tests/test_gpu_exposure.py,
+test_gpu_equalize.py, test_gpu_density.py): arrays put on the device at an offset, guarded outputs, and the constants a
+source file names (the sweep's are counter_sweep.h's)."""
+
+import os
+import re
 
 import numpy as np
 
@@ -15,7 +22,7 @@ BEYOND_TOPS = ((1 << 24) + 12345, (1 << 37) + 12345, (1 << 53) + 1, (1 << 63) + 
 U64 = np.uint64
 
 # The launches the plants are sized by; each GPU suite checks its half against the source (the_grid_named_here_is_the_code_s).
-# tonemap.hip: kToneThreads lanes, two pixels per lane, the grid capped at 256 * 16 blocks.
+# tonemap.hip: kSweepThreads lanes, two pixels per lane, the grid capped at 256 * 16 blocks (counter_sweep.h).
 TONE_THREADS, TONE_BLOCK_CAP = 256, 256 * 16
 TONE_SWEEP = 2 * TONE_BLOCK_CAP * TONE_THREADS
 # color.hip: kColorThreads lanes, eight pixels per lane; kLevelBlocksPerPlane blocks per plane in the two level kernels,
@@ -26,6 +33,48 @@ LEVEL_SWEEP = LEVEL_BLOCKS * COLOR_THREADS * 8
 
 def u64(values):
     return np.array([int(v) for v in values], dtype=U64)
+
+
+def source(name):
+    """The text of cudabrot_amd/csrc/<name> and the uint32 constants it defines with a literal, {name: value}."""
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cudabrot_amd", "csrc", name)) as f:
+        text = f.read()
+    return text, {k: int(v) for k, v in re.findall(r"constexpr uint32_t (k\w+) = (\d+);", text)}
+
+
+# ---- what the GPU suites of the output stage put on the device, and how they look at what comes back ----
+
+GUARD, FILL = 8, 0x5a5a  # u16 on each side of an output
+
+
+def on_device(values, offset=0, fill=0, spare=0):
+    """A u64 array, flat, on cuda:0 `offset` elements into its allocation, `spare` elements behind it, `fill` around it
+    -> (tensor that owns it, view)."""
+    import torch
+
+    flat = np.array(values, dtype=np.uint64).reshape(-1)  # a copy: the plants are shared and read-only
+    base = torch.full((flat.size + offset + spare,), fill, dtype=torch.int64, device="cuda:0")
+    view = base[offset:offset + flat.size]
+    view.copy_(torch.from_numpy(flat.view(np.int64)))
+    torch.cuda.synchronize()
+    return base, view
+
+
+def guarded_output(samples, offset=0):
+    """`samples` u16 on cuda:0, GUARD + offset u16 into an allocation filled with FILL -> (the allocation, the output)."""
+    import torch
+
+    base = torch.full((GUARD + offset + samples + GUARD,), FILL, dtype=torch.int16, device="cuda:0")
+    return base, base[GUARD + offset:GUARD + offset + samples]
+
+
+def read_guarded(base, samples, offset=0):
+    """The output as big-endian samples, after the guards on both sides were seen untouched."""
+    host = base.cpu().numpy().view(np.uint16)
+    lo = GUARD + offset
+    assert np.all(host[:lo] == FILL), "a store in front of the image"
+    assert np.all(host[lo + samples:] == FILL), "a store behind the image"
+    return host[lo:lo + samples].view(">u2")
 
 
 # ---- tone map ----

@@ -5,40 +5,25 @@ own tone map at gamma 0, so the grey values are planted directly.  Byte for byte
 restatement, with guard words around every output.  tests/test_output_planted_host.py shows that the plants are decisive."""
 
 import functools
-import re
 
 import numpy as np
 import pytest
 
 import color_reference as ref
 import output_planted as op
+from output_planted import guarded_output, on_device, read_guarded
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("CB_TONE_LUT", "CB_TONE_THRESHOLDS")
-GUARD, FILL = 8, 0x5a5a  # u16 on each side of an output
 
 
-def test_the_grid_named_here_is_the_code_s(repo_root):
-    with open("%s/cudabrot_amd/csrc/color.hip" % repo_root) as f:
-        text = f.read()
-    said = {k: int(v) for k, v in re.findall(r"constexpr uint32_t (k\w+) = (\d+);", text)}
+def test_the_grid_named_here_is_the_code_s():
+    text, said = op.source("color.hip")
     assert said == {"kColorThreads": op.COLOR_THREADS, "kLevelBlocksPerPlane": op.LEVEL_BLOCKS, "kComposeBlocks": op.COMPOSE_BLOCKS}
     assert (op.COLOR_THREADS, op.LEVEL_BLOCKS, op.COMPOSE_BLOCKS) == (256, 1024, 4096)
     assert "plane + g * 8ull" in text                          # eight pixels per lane
     assert op.LEVEL_SWEEP == 1024 * 256 * 8
-
-
-def on_device(values, offset=0):
-    """A 1-D u64 array on cuda:0 `offset` elements into its allocation -> (tensor that owns it, view)."""
-    import torch
-
-    flat = np.array(values, dtype=np.uint64).reshape(-1)  # a copy: the plants are shared and read-only
-    base = torch.zeros(flat.size + offset, dtype=torch.int64, device="cuda:0")
-    view = base[offset:]
-    view.copy_(torch.from_numpy(flat.view(np.int64)))
-    torch.cuda.synchronize()
-    return base, view
 
 
 def device_compose(cb, case, mode, compose, hue, offset=0):
@@ -49,18 +34,13 @@ def device_compose(cb, case, mode, compose, hue, offset=0):
     h, w = case["planes"][0].shape
     samples = 3 * h * w
     held = [on_device(p) for p in case["planes"]]
-    base = torch.full((GUARD + offset + samples + GUARD,), FILL, dtype=torch.int16, device="cuda:0")
-    lo = GUARD + offset
-    d_rgb = base[lo:lo + samples]
+    base, d_rgb = guarded_output(samples, offset)
     assert d_rgb.data_ptr() % 16 == (2 * offset) % 16
     levels = cb.compose_color_device([view.data_ptr() for _, view in held], w, h, 0.0, d_rgb.data_ptr(), mode=mode,
                                      compose=compose, stretch=case["stretch"], hue_shift=hue,
                                      stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    host = base.cpu().numpy().view(np.uint16)
-    assert np.all(host[:lo] == FILL), "a store in front of the image"
-    assert np.all(host[lo + samples:] == FILL), "a store behind the image"
-    return host[lo:lo + samples].view(">u2").reshape(h, w, 3), levels
+    return read_guarded(base, samples, offset).reshape(h, w, 3), levels
 
 
 @functools.lru_cache(maxsize=None)

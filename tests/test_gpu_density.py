@@ -5,12 +5,12 @@ the definition says, and the binary writes one file whatever form of tone map it
 
 import ctypes as C
 import json
-import re
 
 import numpy as np
 import pytest
 
 import density_reference as dens
+import output_planted
 import plot_reference as plot
 from conftest import read_state_file
 from plot_harness import exe  # noqa: F401
@@ -24,23 +24,13 @@ MODES = ["CB_TONE_LUT", "CB_TONE_THRESHOLDS", "CB_TONE_AUTO"]
 INVALID = 1  # hipErrorInvalidValue
 
 
-def test_the_tile_named_here_is_the_code_s(repo_root):
-    with open("%s/cudabrot_amd/csrc/density.hip" % repo_root) as f:
-        text = f.read()
-    said = {k: int(v) for k, v in re.findall(r"constexpr uint32_t (kTileW|kTileH|kDensityThreads) = (\d+);", text)}
-    assert said == {"kTileW": TILE_W, "kTileH": TILE_H, "kDensityThreads": THREADS}
+def test_the_tile_named_here_is_the_code_s():
+    said = output_planted.source("density.hip")[1]
+    assert {k: said[k] for k in ("kTileW", "kTileH", "kDensityThreads")} == {"kTileW": TILE_W, "kTileH": TILE_H, "kDensityThreads": THREADS}
 
 
 def on_device(values, offset=0, fill=0):
-    """A u64 array on cuda:0 `offset` elements into its allocation -> (tensor that owns it, flat view)."""
-    import torch
-
-    flat = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
-    base = torch.full((flat.size + offset + 1,), fill, dtype=torch.int64, device="cuda:0")  # (one spare counter behind)
-    view = base[offset:offset + flat.size]
-    view.copy_(torch.from_numpy(flat.view(np.int64)))
-    torch.cuda.synchronize()
-    return base, view
+    return output_planted.on_device(values, offset, fill, spare=1)  # (one spare counter behind)
 
 
 def device_filter(cb, hist, table, group=1, offset=0):

@@ -4,7 +4,6 @@ only to break the kernel --, the mapped image equals the host function's bytes, 
 to the array whose maximum they take otherwise."""
 
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import equalize_reference as eq
 import plot_reference as plot
 from conftest import read_state_file
+from output_planted import on_device, source
 from plot_harness import DEPTH_SHAPE, exe  # noqa: F401
 from plot_harness import gpu_run as run
 
@@ -19,8 +19,9 @@ pytestmark = pytest.mark.gpu
 
 CASES = eq.cases()
 INVALID = 1  # hipErrorInvalidValue
-# equalize.hip's launch: kEqualizeBlocks blocks of kEqualizeThreads lanes, each lane kLoads loads of kVector counters per
-# turn -- one full sweep of the grid is their product; keys below kWindow are counted in LDS, the others in global memory
+# equalize.hip's launch (counter_sweep.h): kSweepBlocks blocks of kSweepThreads lanes, each lane kLoads loads of kVector
+# counters per turn -- one full sweep of the grid is their product; keys below equalize.hip's kWindow are counted in LDS,
+# the others in global memory
 BLOCKS, THREADS, LOADS, VECTOR, WINDOW = 1024, 256, 4, 2, 8192
 SWEEP = BLOCKS * THREADS * LOADS * VECTOR
 BLOCK_TURN = THREADS * LOADS * VECTOR
@@ -28,24 +29,9 @@ MODES = ["CB_TONE_LUT", "CB_TONE_THRESHOLDS", "CB_TONE_AUTO"]
 FILTER = (4, 0.5, 2)
 
 
-def test_the_grid_named_here_is_the_code_s(repo_root):
-    with open("%s/cudabrot_amd/csrc/equalize.hip" % repo_root) as f:
-        text = f.read()
-    said = {k: int(v) for k, v in re.findall(r"constexpr uint32_t (k\w+) = (\d+);", text)}
-    assert said == {"kEqualizeBlocks": BLOCKS, "kEqualizeThreads": THREADS, "kLoads": LOADS, "kVector": VECTOR,
-                    "kWindow": WINDOW}
-
-
-def on_device(values, offset=0):
-    """A 1-D u64 array on cuda:0 `offset` elements into its allocation -> (tensor that owns it, view)."""
-    import torch
-
-    flat = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
-    base = torch.zeros(flat.size + offset, dtype=torch.int64, device="cuda:0")
-    view = base[offset:]
-    view.copy_(torch.from_numpy(flat.view(np.int64)))
-    torch.cuda.synchronize()
-    return base, view
+def test_the_grid_named_here_is_the_code_s():
+    assert source("counter_sweep.h")[1] == {"kSweepBlocks": BLOCKS, "kSweepThreads": THREADS, "kLoads": LOADS, "kVector": VECTOR}
+    assert "for_each_counter(hist, n," in source("equalize.hip")[0] and source("equalize.hip")[1] == {"kWindow": WINDOW}
 
 
 def device_bins(cb, values, offset=0):

@@ -11,36 +11,23 @@ import pytest
 import exposure_reference as expo
 import plot_reference as plot
 from conftest import read_state_file
+from output_planted import on_device, source
 from plot_harness import DEPTH_SHAPE, exe  # noqa: F401
 from plot_harness import gpu_run as run
 
 pytestmark = pytest.mark.gpu
 
 CASES = expo.cases()
-# exposure.hip's launch: kExposureBlocks blocks of kExposureThreads lanes, each lane kLoads loads of kVector counters per
-# turn -- one full sweep of the grid is their product
+# exposure.hip's launch (counter_sweep.h): kSweepBlocks blocks of kSweepThreads lanes, each lane kLoads loads of kVector
+# counters per turn -- one full sweep of the grid is their product
 BLOCKS, THREADS, LOADS, VECTOR = 1024, 256, 4, 2
 SWEEP = BLOCKS * THREADS * LOADS * VECTOR
 MODES = ["CB_TONE_LUT", "CB_TONE_THRESHOLDS", "CB_TONE_AUTO"]
 
 
-def test_the_grid_named_here_is_the_code_s(repo_root):
-    with open("%s/cudabrot_amd/csrc/exposure.hip" % repo_root) as f:
-        text = f.read()
-    said = {k: int(v) for k, v in re.findall(r"constexpr uint32_t (kExposureBlocks|kExposureThreads|kLoads|kVector) = (\d+);", text)}
-    assert said == {"kExposureBlocks": BLOCKS, "kExposureThreads": THREADS, "kLoads": LOADS, "kVector": VECTOR}
-
-
-def on_device(values, offset=0):
-    """A 1-D u64 array on cuda:0 `offset` elements into its allocation -> (tensor that owns it, view)."""
-    import torch
-
-    flat = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
-    base = torch.zeros(flat.size + offset, dtype=torch.int64, device="cuda:0")
-    view = base[offset:]
-    view.copy_(torch.from_numpy(flat.view(np.int64)))
-    torch.cuda.synchronize()
-    return base, view
+def test_the_grid_named_here_is_the_code_s():
+    assert source("counter_sweep.h")[1] == {"kSweepBlocks": BLOCKS, "kSweepThreads": THREADS, "kLoads": LOADS, "kVector": VECTOR}
+    assert "for_each_counter(hist, n," in source("exposure.hip")[0] and source("exposure.hip")[1] == {}
 
 
 def device_white_count(cb, values, clip, offset=0):

@@ -10,50 +10,21 @@ import numpy as np
 import pytest
 
 import output_planted as op
+from output_planted import guarded_output, on_device, read_guarded
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("CB_TONE_LUT", "CB_TONE_THRESHOLDS", "CB_TONE_AUTO")
-GUARD, FILL = 8, 0x5a5a  # u16 on each side of an output
 
 
-def test_the_grid_named_here_is_the_code_s(repo_root):
-    with open("%s/cudabrot_amd/csrc/tonemap.hip" % repo_root) as f:
-        text = f.read()
-    assert re.findall(r"constexpr uint32_t kToneThreads = (\d+);", text) == [str(op.TONE_THREADS)]
+def test_the_grid_named_here_is_the_code_s():
+    text, said = op.source("counter_sweep.h")  # the lookup loop, its lanes and its grid are the header's
+    assert said["kSweepThreads"] == op.TONE_THREADS == 256
     caps = re.findall(r"if \(blocks > (\d+)ull \* (\d+)ull\) blocks = (\d+)ull \* (\d+)ull;", text)
     assert len(caps) == 1 and int(caps[0][0]) * int(caps[0][1]) == int(caps[0][2]) * int(caps[0][3]) == op.TONE_BLOCK_CAP
-    assert "* kToneThreads * 2ull" in text                     # two pixels per lane
+    assert text.count("* kSweepThreads * 2ull") == 1           # two pixels per lane, in the one loop: map_pairs
+    assert op.source("tonemap.hip")[0].count("map_pairs(hist, n, out_be,") == 2  # the table's and the thresholds' kernel
     assert op.TONE_SWEEP == 2 * 4096 * 256
-
-
-def on_device(values, offset=0):
-    """A 1-D u64 array on cuda:0 `offset` elements into its allocation -> (tensor that owns it, view)."""
-    import torch
-
-    flat = np.array(values, dtype=np.uint64).reshape(-1)  # a copy: the plants are shared and read-only
-    base = torch.zeros(flat.size + offset, dtype=torch.int64, device="cuda:0")
-    view = base[offset:]
-    view.copy_(torch.from_numpy(flat.view(np.int64)))
-    torch.cuda.synchronize()
-    return base, view
-
-
-def guarded_output(samples, offset=0):
-    """`samples` u16 on cuda:0, GUARD + offset u16 into an allocation filled with FILL -> (the allocation, the output)."""
-    import torch
-
-    base = torch.full((GUARD + offset + samples + GUARD,), FILL, dtype=torch.int16, device="cuda:0")
-    return base, base[GUARD + offset:GUARD + offset + samples]
-
-
-def read_guarded(base, samples, offset=0):
-    """The output as big-endian samples, after the guards on both sides were seen untouched."""
-    host = base.cpu().numpy().view(np.uint16)
-    lo = GUARD + offset
-    assert np.all(host[:lo] == FILL), "a store in front of the image"
-    assert np.all(host[lo + samples:] == FILL), "a store behind the image"
-    return host[lo:lo + samples].view(">u2")
 
 
 def device_tone(cb, hist, gamma, mode, clip=None):
