@@ -9,7 +9,7 @@ import pytest
 
 import aim_reference as aim
 import plot_reference as plot
-from plot_harness import SAME, Launches, omp_threads, planar_states, variant_of
+from plot_harness import SAME, Launches, omp_threads, planar_states, variant_of, write_states
 
 PRODUCT, LOCKSTEP = 30, 31
 BASES = ((0, PRODUCT), (1, LOCKSTEP))  # (lock-step?, cb_debug_last_draw_kernel)
@@ -30,25 +30,31 @@ def source_args(cb, s):
                 bounded=s["bounded"])
 
 
-def gpu_probe(cb, lockstep, **kw):
-    """shape_of(kw)["probe"] launches of cb_aim_probe on fresh generators, ORed into one mask -> (mask u32 words, counters,
-    kernel, states)."""
+def gpu_probe(cb, lockstep, states=None, guard=0, **kw):
+    """shape_of(kw)["probe"] launches of cb_aim_probe on fresh generators, or on the given oracle `states` written over them
+    (they are left as they were), ORed into one mask -> (mask u32 words, counters, kernel, states).  guard: that many
+    words allocated before and after the mask, and read back with it."""
     s = aim.shape_of(kw)
-    bufs = Launches(cb, cb.FractalDimensions.make(s["w"], s["h"], *s["box"]), s["threads"], words=aim.mask_words(s["level"]),
-                    seed=s.get("seed"))
+    bufs = Launches(cb, cb.FractalDimensions.make(s["w"], s["h"], *s["box"]), s["threads"],
+                    words=aim.mask_words(s["level"]) + 2 * guard, seed=s.get("seed"))
+    if states is not None:
+        write_states(bufs, states)
 
     def entry(d_hist, **args):  # the scaffolding's output buffer is the mask
-        cb.aim_probe(d_mask=d_hist, **args)
+        cb.aim_probe(d_mask=d_hist + 4 * guard, **args)
 
     return bufs.launches(entry, s["probe"], variant(cb, lockstep, s), level=s["level"], **source_args(cb, s)).read()
 
 
-def gpu_draw(cb, lockstep, cell_list, **kw):
-    """shape_of(kw)["draw"] launches of cb_draw_buddhabrot_aimed on fresh generators from `cell_list` (None: level 0, no
-    cells, the uniform source) -> (hist [h, w], counters, kernel, states)."""
+def gpu_draw(cb, lockstep, cell_list, states=None, **kw):
+    """shape_of(kw)["draw"] launches of cb_draw_buddhabrot_aimed on fresh generators, or on the given oracle `states` written
+    over them (they are left as they were), from `cell_list` (None: level 0, no cells, the uniform source) -> (hist [h, w],
+    counters, kernel, states)."""
     s = aim.shape_of(kw)
     tables = {} if cell_list is None else {"cells": cell_list}
     bufs = Launches(cb, cb.FractalDimensions.make(s["w"], s["h"], *s["box"]), s["threads"], tables=tables, seed=s.get("seed"))
+    if states is not None:
+        write_states(bufs, states)
     grid = dict(level=0) if cell_list is None else dict(level=s["level"], d_cells=bufs.tables["cells"].data_ptr(),
                                                         n_cells=len(cell_list))
     return bufs.launches(cb.draw_buddhabrot_aimed, s["draw"], variant(cb, lockstep, s), **grid, **source_args(cb, s)).read()

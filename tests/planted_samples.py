@@ -21,10 +21,15 @@ A coordinate is drawn from two outputs: v = o_a | ((o_b >> 11) << 32), c = (v + 
 would be -1).  The low 11 bits of o_b are free, and so are d and x[4] (plant_states varies them by subsequence, so that
 what FOLLOWS the planted sample differs from lane to lane).
 
-THE LIMIT: ONE PLANTED SAMPLE PER SUBSEQUENCE.  Four outputs make one sample (real, then imag), and the state has only
-those four free words: the fifth output already depends on x[4] and on what the first four fixed.  The second and later
-samples of a subsequence are the generator's own -- the oracle, given the same states, follows them too, so a launch of
-50 samples per subsequence is still compared bit for bit; only its first sample is chosen.
+THE LIMIT: ONE PLANTED SAMPLE PER SUBSEQUENCE, OF FOUR OUTPUTS OR OF SIX.  Four outputs make one sample of the normal
+stream (real, then imag), and four state words take any four outputs whatever d and x[4] are.  A sample of the cell-list
+source is six outputs (the entry draw a, b, then x1, x2, y1, y2), and six can be planted as well, by a search
+(plant_outputs): the fifth output fixes the last free word, x[4] = f^-1(x4_5 ^ g(x4_4)), the sixth is then a function of d
+alone, o_6 = d + 6 K + (g(x4_5) ^ f(x4_1)), and of it only the upper 21 bits matter (the offset draw drops the low 11 of its
+second output): one d in 2^21 fits, the search walks all 2^32 if it must and returns an exact state or raises, never a near
+one.  Nothing is left free after that, so the second and later samples of a subsequence are the generator's own -- the
+oracle, given the same states, follows them too, so a launch of 50 samples per subsequence is still compared bit for bit;
+only its first sample is chosen.
 
 The finders bisect the oracle's own predicates over steps of the 2^-51 grid, so what they return is decisive by the
 reference's arithmetic, not by a formula about it:
@@ -49,6 +54,20 @@ tests/plot_reference.py and .c:
 
 tests/test_planted_plot_host.py shows these decisive on the restatement alone; tests/test_gpu_planted_plot.py and
 tests/test_gpu_planted_queue.py feed them to the kernels.
+
+The third part is the cell grid of the focused and aimed renders (draw_cells.h; tests/cells_reference.h): six-draw samples
+of a cell list, with a reference of the mapping in integers and Fractions that shares no arithmetic with kernels or
+restatements, and four-draw samples on the edges of the probe's mask:
+
+    plant_outputs, plant_cell_states   states whose first SIX outputs are chosen
+    exact_entry, exact_point           the mapping by the definition: an integer product, a Fraction sum rounded once
+    entry_edges, spread_list           entry draws either side of a boundary of j, on lists whose neighbours are far apart
+    tie_draws                          offset draws whose exact corner + offset is a tie of the result's format
+    interior_edges, map_columns        samples one ulp below a marked cell of the interior map, whose c_re + 2 rounds onto it
+    shape_edges_off_the_grid           adjacent doubles across the cardioid's and the bulb's edge, off the 2^-51 grid
+    cell_edge_samples, mask_bit        samples on a cell's edge, by the word and the bit of the mask they set
+
+tests/test_planted_cells_host.py shows these decisive; tests/test_gpu_planted_cells.py feeds them to the kernels.
 """
 
 import ctypes as C
@@ -774,3 +793,469 @@ def accepted_beside(lib, c_re, lo=2, hi=400):
         if all(e is not None and lo <= e <= hi for e in ends) and not any(rejected(x, c_im) for x in c_re):
             return c_im, ends
     raise ValueError("no accepted sample with real part %r" % (c_re,))
+
+
+# ---- six planted outputs: a sample of the cell-list source (draw_cells.h, next_sample<true>; tests/cells_reference.h) ---------
+#
+# A cell-sourced sample is six outputs: a, b pick the entry j = high half of (a << 32 | b) * n_cells; (x1, x2) and (y1, y2)
+# are the offset draws v = o | (o' >> 11) << 32 of either axis, and the coordinate is ONE rounded addition of the cell's
+# corner -2 + col 2^-L and the offset (v + 1) 2^-(53 + L), both exact.  Everything here is integers and Fractions: it shares
+# no arithmetic with the kernels nor with tests/cells_reference.h.
+
+C_PLANE = plot.C_PLANE                             # --plane cr,ci: every plotted point of an orbit is its c
+V_MAX = (1 << 53) - 1                              # the largest offset draw: the next cell's corner, 2 in the last column
+SEARCH_BATCH = 1 << 20
+_SIX = {}                                          # planted six-output states, by (outputs, free bits, variant)
+
+
+def _f_np(x):
+    t = x ^ (x >> np.uint32(2))
+    return t ^ (t << np.uint32(1))
+
+
+def _g_np(v):
+    return v ^ (v << np.uint32(4))
+
+
+def six_outputs(state):
+    """The first six outputs of a state (which is left as it was)."""
+    st = oracle.Xorwow(int(state["d"]), (C.c_uint32 * 5)(*[int(v) for v in state["x"]]))
+    return [int(oracle.lib.orc_xorwow_next(C.byref(st))) for _ in range(6)]
+
+
+def plant_outputs(o, free_low_bits_of_o6=11, start=0):
+    """An oracle state whose first five outputs are o[0] .. o[4] and whose sixth agrees with o[5] in all but its low
+    `free_low_bits_of_o6` bits.  d is searched: from `start` on, batch by batch through all 2^32 values if need be, and the
+    first d found whose sixth output fits is taken -- exactly, never nearly; no d at all (chance e^-2048 at 11 free bits) raises."""
+    o = [int(v) & M32 for v in o]
+    free = int(free_low_bits_of_o6)
+    assert len(o) == 6 and 0 <= free < 32
+    o1, o5, want = np.uint32(o[0]), np.uint32(o[4]), np.uint32(o[5] >> free)
+    k1, k5, k6 = np.uint32(K), np.uint32(5 * K & M32), np.uint32(6 * K & M32)
+    step = np.arange(SEARCH_BATCH, dtype=np.uint64)
+    for batch in range((1 << 32) // SEARCH_BATCH):
+        # candidate number i is start + i * (an odd constant): every d once, and neighbours differ in their high bits (the
+        # sixth output's upper bits depend on d's upper bits alone, so consecutive d would repeat one miss 2^7 times)
+        i = step + np.uint64(batch * SEARCH_BATCH)
+        d = ((i * np.uint64(0x9E3779B1) + np.uint64(int(start) & M32)) & np.uint64(M32)).astype(np.uint32)
+        sixth = d + k6 + (_g_np(o5 - d - k5) ^ _f_np(o1 - d - k1))           # u32 arrays: every operation mod 2^32
+        hits = np.flatnonzero((sixth >> np.uint32(free)) == want)
+        if len(hits):
+            break
+    else:
+        raise ValueError("no generator state has the outputs %r" % (o,))
+    d = int(d[hits[0]])
+    v = [None] + [(o[n - 1] - d - n * K) & M32 for n in range(1, 6)]
+    x4 = _f_inverse(v[5] ^ _g(v[4]))
+    x = [_f_inverse(v[1] ^ _g(x4))] + [_f_inverse(v[n] ^ _g(v[n - 1])) for n in range(2, 5)] + [x4]
+    state = np.zeros((), dtype=oracle.STATE_DTYPE)
+    state["d"] = d
+    state["x"] = x
+    got = six_outputs(state)
+    assert got[:5] == o[:5] and got[5] >> free == o[5] >> free, (o, got)
+    return state
+
+
+def cell_outputs(ab, vx, vy, low=0):
+    """The six outputs of the entry draw ab (64 bits) and the offset draws vx, vy (53 bits each); the 11 low bits of the
+    fourth output are `low`, those of the sixth are left to plant_outputs."""
+    assert 0 <= ab < 1 << 64 and 0 <= vx <= V_MAX and 0 <= vy <= V_MAX
+    return (ab >> 32, ab & M32, vx & M32, ((vx >> 32) << 11) | (low & 0x7FF), vy & M32, (vy >> 32) << 11)
+
+
+def plant_cell_states(draws, variants=2):
+    """One state per (ab, vx, vy), subsequence by subsequence.  Subsequence k takes variant k % variants of its draws -- another
+    d, other free bits, so another continuation -- and every (draws, variant) is searched once per process."""
+    out = np.zeros(len(draws), dtype=oracle.STATE_DTYPE)
+    for k, (ab, vx, vy) in enumerate(draws):
+        key = (ab, vx, vy, k % variants)
+        if key not in _SIX:
+            mix = ((k % variants + 1) * 2654435761 + (ab ^ vx ^ vy) * 40503) & M32
+            _SIX[key] = plant_outputs(cell_outputs(ab, vx, vy, low=mix >> 7), start=mix)
+        out[k] = _SIX[key]
+    return out
+
+
+def exact_entry(ab, n_cells):
+    return (ab * n_cells) >> 64
+
+
+def cell_corner(level, cell):
+    """(re, im) of the cell's corner, exact."""
+    n = 4 << level
+    return Fraction(cell % n, 1 << level) - 2, Fraction(cell // n, 1 << level) - 2
+
+
+def cell_at(level, re, im):
+    """The cell that holds the point (2 is in the last one)."""
+    n = 4 << level
+    col, row = (min(int((Fraction(x) + 2) * (1 << level)), n - 1) for x in (re, im))
+    return row * n + col
+
+
+def exact_point(level, cell, vx, vy):
+    """The sample of the cell at the offset draws, by the definition: the exact corner plus the exact offset as Fractions,
+    rounded once by float()."""
+    return tuple(float(corner + Fraction(v + 1, 1 << (53 + level))) for corner, v in zip(cell_corner(level, cell), (vx, vy)))
+
+
+def two_roundings(level, cell, vx, vy):
+    """What -2 + (col side + offset) gives: the sum a kernel must NOT compute."""
+    n, side = 4 << level, 2.0 ** -level
+    return tuple(-2.0 + (float(k) * side + float(v + 1) * 2.0 ** -(53 + level)) for k, v in ((cell % n, vx), (cell // n, vy)))
+
+
+def exact_sample(level, cells, ab, vx, vy):
+    """(j, re, im) of six draws on a list, by exact_entry and exact_point."""
+    j = exact_entry(ab, len(cells))
+    return (j,) + exact_point(level, int(cells[j]), vx, vy)
+
+
+def draw_range(level, cell, x):
+    """The least and the largest offset draw v with which the coordinate is the double x exactly (corner + offset rounds to
+    x), or None if no draw gives x.  Per axis: `cell` is the column or row number."""
+    corner = Fraction(cell, 1 << level) - 2
+
+    def at(v):
+        return float(corner + Fraction(v + 1, 1 << (53 + level)))
+
+    def first(pred):                                  # the least v in [0, V_MAX + 1] with pred(at(v)); at is monotone
+        lo, hi = -1, V_MAX + 1
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (lo, mid) if pred(at(mid)) else (mid, hi)
+        return hi
+
+    least, above = first(lambda y: y >= x), first(lambda y: y > x)
+    return (least, above - 1) if above > least else None
+
+
+def draw_of(level, cell, x):
+    """The least draw of draw_range."""
+    found = draw_range(level, cell, x)
+    return None if found is None else found[0]
+
+
+def draws_for(level, cells, entry, re, im):
+    """(ab, vx, vy) that give exactly (re, im) from list entry `entry`: ab in the middle of the entry's range."""
+    n, cell = 4 << level, int(cells[entry])
+    vx, vy = draw_of(level, cell % n, re), draw_of(level, cell // n, im)
+    assert vx is not None and vy is not None, (level, cell, re, im)
+    ab = ((2 * entry + 1) << 64) // (2 * len(cells))
+    assert exact_sample(level, cells, ab, vx, vy) == (entry, re, im)
+    return ab, vx, vy
+
+
+def entry_edges(n_cells):
+    """The entry draws on the edges of j = high half of ab n_cells -> [(ab, j)]: 0 and 2^64 - 1, and for k = 1 and
+    n_cells - 1 the pair ceil(k 2^64 / n) - 1, ceil(k 2^64 / n)."""
+    out = [(0, 0), ((1 << 64) - 1, n_cells - 1)]
+    for k in sorted({1, n_cells - 1} - {0, n_cells}):
+        edge = -((-k << 64) // n_cells)
+        out += [(edge - 1, k - 1), (edge, k)]
+    assert all(exact_entry(ab, n_cells) == j for ab, j in out)
+    return out
+
+
+# four cells outside the set, far apart, whose samples escape after a step or more and whose z_1 is on WIDE_BOX
+BEACONS = [(-1.5, 0.5), (0.5, -1.0), (-0.5, 1.0), (1.0, 0.75)]
+LIST_SIZES = {"1": (4, 1), "2": (4, 2), "3": (4, 3), "7": (10, 7), "prime": (10, 999983), "grid": (10, 1 << 24)}
+
+
+def spread_list(level, n_cells):
+    """A list whose neighbouring entries are far-apart cells: entry j is cell j M + n^2 / 3 mod n^2 for an odd M near
+    n^2 / phi (neighbours lie 0.38 of the grid apart, rows and all), and entries 0, 1, n - 2 and n - 1, the ones the edges
+    of the entry draw select, are the BEACONS."""
+    total = (4 << level) ** 2
+    m = int(total * 0.6180339887) | 1
+    cells = ((np.arange(n_cells, dtype=np.uint64) * np.uint64(m) + np.uint64(total // 3)) % np.uint64(total)).astype(np.uint32)
+    for j, (re, im) in zip((0, 1, n_cells - 2, n_cells - 1), BEACONS):
+        if 0 <= j < n_cells:
+            cells[j] = cell_at(level, re, im)
+    return cells
+
+
+def filler_draws(n_cells):
+    """The six draws of FILLER from a list whose LAST entry is the grid's last cell: c = (2, 2) exactly."""
+    return ((1 << 64) - 1, V_MAX, V_MAX)
+
+
+def last_cell(level):
+    return (4 << level) ** 2 - 1
+
+
+def ulp_canvas(re, im, w=64, h=48):
+    """A canvas whose pixels are one ulp of re wide and one ulp of im high, with (re, im) in pixel (w / 2, h / 2): under
+    C_PLANE the histogram reads a sample to the bit.  Every operation of the binning is exact on it."""
+    ur, ui = math.ulp(re), math.ulp(im)
+    return (re - (w // 2) * ur, re + (w // 2) * ur, im - (h // 2) * ui, im + (h // 2) * ui)
+
+
+CORNER_CLASSES = {                                 # name -> the cell's column corner as a function of the level
+    "[-2,-1)": lambda level: Fraction(-3, 2),
+    "[-1,-1/2)": lambda level: Fraction(-3, 4),
+    "[1/2,1)": lambda level: Fraction(3, 4),
+    "-2^-L": lambda level: Fraction(-1, 1 << level),
+    "0": lambda level: Fraction(0),
+}
+
+
+def tie_draws(level, corner):
+    """Offset draws of the cell with the given corner coordinate whose exact sum corner + offset is a tie of the result's
+    format, and one unit of the offset either side: [(v, tie parity or None, what)] -- for the two corners near zero,
+    where every sum is exact, the same draws (no tie there: what = "exact")."""
+    unit = Fraction(1, 1 << (53 + level))
+    ulp = Fraction(math.ulp(float(corner + Fraction(1, 2 << level))))        # of the cell's middle: one binade per cell
+    r = int(ulp / unit)
+    if r < 2:                                                                 # beside zero: the sum is exact whatever the draw
+        r = 1 << level
+    else:
+        assert (corner / ulp).denominator == 1
+    out = []
+    for t in ((1 << 52) // r + 12345, (1 << 52) // r + 12346):               # both parities of the kept bit, mid-cell
+        m = t * r + r // 2
+        exact = corner + m * unit
+        tie = (exact / ulp - Fraction(1, 2)).denominator == 1
+        for dm, what in ((-1, "below"), (0, "tie" if tie else "exact"), (1, "above")):
+            out.append((m + dm - 1, t & 1 if tie else None, what))
+    return out
+
+
+def interior_edges(limit=3, level=10):
+    """From the shipped interior map: column edges E in (-1, 0) with an unmarked cell on the left and a marked one on the
+    right, in rows where neither (E - ulp, im) nor (E, im) is in the cardioid or the bulb -> [(E, im, map level)], im the
+    middle of the map's row."""
+    import gzip
+    import struct
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    raw = gzip.open(os.path.join(root, "cudabrot_amd", "interior_map.bin.gz"), "rb").read()
+    _, map_level, cols, rows = struct.unpack("<4I", raw[:16])
+    bits = np.unpackbits(np.frombuffer(raw, dtype=np.uint8, offset=16), bitorder="little")[:rows * cols].reshape(rows, cols)
+    side = 2.0 ** -map_level
+    out = []
+    for row in range(rows // 7, rows, rows // 5):                             # a few rows, apart
+        for col in np.flatnonzero(bits[row, 1:] & ~bits[row, :-1] & 1) + 1:
+            e, im = -2.0 + int(col) * side, (row + 0.5) * side
+            below = math.nextafter(e, -math.inf)
+            if -1.0 < e < 0.0 and not rejected(below, im) and not rejected(e, im):
+                out.append((e, im, map_level))
+                break
+        if len(out) == limit:
+            break
+    return out
+
+
+def map_columns(c_re, map_level):
+    """(the column of the cell that holds c_re, the column the rounded sum c_re + 2 gives)."""
+    return math.floor(Fraction(c_re) * (1 << map_level)) + (2 << map_level), int(math.ldexp(c_re + 2.0, map_level))
+
+
+def _adjacent(pred, inside, outside):
+    """Bisects the doubles between inside (pred holds) and outside (it does not) -> adjacent doubles (in, out)."""
+    assert pred(inside) and not pred(outside)
+    while math.nextafter(inside, outside) != outside:
+        mid = inside + (outside - inside) / 2
+        if mid in (inside, outside):
+            mid = math.nextafter(inside, outside)
+        if pred(mid):
+            inside = mid
+        else:
+            outside = mid
+    return inside, outside
+
+
+def shape_edges_off_the_grid():
+    """Pairs of ADJACENT doubles (rejected, not rejected) in c_re across the edge of the cardioid and of the bulb, at real
+    parts whose ulp is finer than the 2^-51 grid of the four-draw samples, both members off that grid: only a cell-sourced
+    sample can be there.  -> [(shape, (re in, im), (re out, im))]"""
+    rays = [("cardioid", 0.3, 0.0, 0.45), ("cardioid", -0.3, 0.0, 0.45), ("cardioid", 0.6, -0.3, -0.7),
+            ("cardioid", 0.0625 + 2.0 ** -30, 0.0, 0.45), ("bulb", 0.1, -0.9, -0.7), ("bulb", -0.2, -0.9, -0.7),
+            ("bulb", 0.2, -0.95, -0.7), ("bulb", 0.125 + 2.0 ** -33, -0.9, -0.7)]
+    out = []
+    for shape, im, inside, outside in rays:
+        pred = oracle.lib.orc_in_main_cardioid if shape == "cardioid" else oracle.lib.orc_in_order2_bulb
+        a, b = _adjacent(lambda x: bool(pred(x, im)), inside, outside)
+        off = [math.ldexp(x, 51) != int(math.ldexp(x, 51)) for x in (a, b)]
+        if all(off) and rejected(a, im) and not rejected(b, im):
+            out.append((shape, (a, im), (b, im)))
+    return out
+
+
+# ---- the mask sink: uniform-source samples on the edges of mark_cell (draw_cells.h) ------------------------------------------
+
+GUARD_WORDS = 64
+
+
+def mask_bit(level, re, im):
+    """(word, bit) of the mask that the sample's cell is."""
+    index = cell_at(level, re, im)
+    return index >> 5, index & 31
+
+
+def cell_edge_samples(level):
+    """Samples on a cell edge and their 2^-51 neighbours below it, chosen by the bit they mark: bit 0 and bit 31, the
+    first and the last word; and c = 2 on re, on im and on both -> [(name, (re, im))].  -2 cannot be planted: a sample of the
+    normal stream is never below -2 + 2^-51."""
+    n, s = 4 << level, 2.0 ** -level
+    half = s / 2
+    low, high = -2.0 + half, 2.0 - half              # the middles of the first and the last column (row)
+    edge = lambda k: -2.0 + k * s                    # noqa: E731
+    below = lambda x: grid_point(grid_index(x) - 1)  # noqa: E731
+    out = []
+    for name, re, im in (("row 0, column 32", edge(32), low), ("last row, column n - 32", edge(n - 32), high),
+                         ("last row, last column", edge(n - 1), high)):
+        out += [(name + ": on the edge", (re, im)), (name + ": below it", (below(re), im))]
+    for name, re, im in (("column 0, row 1", low, edge(1)), ("column 31, row 1", edge(31) + half, edge(1)),
+                         ("last column, last row", high, edge(n - 1))):
+        out += [(name + ": on the edge", (re, im)), (name + ": below it", (re, below(im)))]
+    out += [("re = 2", (2.0, 0.5)), ("im = 2", (0.5, 2.0)), ("both = 2", (2.0, 2.0)),
+            ("the first cell", (grid_point(1 - (1 << 52)), grid_point(1 - (1 << 52))))]
+    return out
+
+
+def box_around(point, half=0.25):
+    """A 64 x 48 canvas of dyadic extent with the point well inside."""
+    r, i = (math.floor(x * 8) / 8 for x in point)
+    return (r - half, r + half, i - half, i + half)
+
+
+def box_from(point, extent=0.5):
+    """A canvas whose LOWER edges are the point's coordinates exactly: the point is in pixel (0, 0), and whatever lies below
+    it on either axis is off the canvas."""
+    return (point[0], point[0] + extent, point[1] - extent / 2, point[1] + extent / 2)
+
+
+def filler_marks(box):
+    """Whether z_1 of FILLER, (2, 10), its only replayed point under min_iter 0, is on the canvas."""
+    return box[0] <= 2.0 < box[1] and box[2] <= 10.0 < box[3]
+
+
+NOWHERE = (10.0, 10.5, 10.0, 10.5)                 # |z| <= 2^2 + |c| < 7 for every plotted point: no orbit comes here
+
+
+# ---- the cases both cell suites use (tests/test_planted_cells_host.py, tests/test_gpu_planted_cells.py) -----------------------
+#
+# A cell case is (level, list, [(ab, vx, vy)] of the planted sample, the sample by exact_sample).  The lists of the cases that
+# idle their other lanes end with the grid's last cell, from which filler_draws gives FILLER itself.
+
+MID = (1 << 52) - 1                                # the offset draw of a cell's middle
+CELL_MAX_ITER = 121
+_LISTS = {}
+
+
+def sized_list(name):
+    if name not in _LISTS:
+        _LISTS[name] = spread_list(*LIST_SIZES[name])
+    return LIST_SIZES[name][0], _LISTS[name]
+
+
+def entry_plants(name):
+    """The entry draws of entry_edges on the list of that name, each with the cell's middle as its offset ->
+    (level, list, [((ab, vx, vy), j)])."""
+    level, cells = sized_list(name)
+    return level, cells, [((ab, MID, MID), j) for ab, j in entry_edges(len(cells))]
+
+
+def listed(level, *points):
+    """A list of the cells that hold the points, in their order, and then the grid's last cell."""
+    return np.array([cell_at(level, *p) for p in points] + [last_cell(level)], dtype=np.uint32)
+
+
+def offset_plants(level):
+    """Offset extremes -> [(name, list, draws, neighbour draws or None)]: v = 0 and v = 2^53 - 1 on either axis of an inner
+    cell whose corner on that axis is 0 (the cells of (0, 5/4) and of (1, 0), outside the set) -- beside zero every draw
+    gives another double, so the neighbour is v + 1 or v - 1 --, and v = 2^53 - 1 in the last column, the last row and the
+    last cell: c = 2 exactly, where the neighbour is the largest draw that still gives the double below 2."""
+    n, out = 4 << level, []
+    inner = listed(level, (0.0, 1.25), (1.0, 0.0))
+    first, second = 1 << 61, 1 << 63                                           # entry draws of the list's entries 0 and 1
+    for name, ab, vx, vy, wx, wy in (("re: v = 0", first, 0, MID, 1, MID), ("re: v = max", first, V_MAX, MID, V_MAX - 1, MID),
+                                     ("im: v = 0", second, MID, 0, MID, 1), ("im: v = max", second, MID, V_MAX, MID, V_MAX - 1)):
+        out.append(("inner, " + name, inner, (ab, vx, vy), (ab, wx, wy)))
+    under = draw_range(level, n - 1, math.nextafter(2.0, 0.0))[1]
+    assert draw_range(level, n - 1, 2.0) == (under + 1, V_MAX)                 # every draw above it gives 2
+    edge = listed(level, (2.0, 0.5), (0.5, 2.0))
+    third = (1 << 64) // 3
+    out.append(("last column: re = 2", edge, (third // 2, V_MAX, MID), (third // 2, under, MID)))
+    out.append(("last row: im = 2", edge, (third + third // 2, MID, V_MAX), (third + third // 2, MID, under)))
+    out.append(("last cell: both = 2", edge, filler_draws(3), None))
+    return out
+
+
+def tie_plants(level, axis):
+    """[(class, list, draws, tie parity, what)] of tie_draws on the given axis, in a cell outside the set: beside the row
+    of corner 5/4 (axis 0) or the column of corner 1 (axis 1)."""
+    out = []
+    for name, corner in CORNER_CLASSES.items():
+        x = float(corner(level))
+        cells = listed(level, (x, 1.25) if axis == 0 else (1.0, x))
+        for v, parity, what in tie_draws(level, corner(level)):
+            out.append((name, cells, (1 << 62, v, MID) if axis == 0 else (1 << 62, MID, v), parity, what))
+    return out
+
+
+def map_plants(level=10):
+    """[(E, im, list, draws below E, draws on E, map level)] of interior_edges."""
+    out = []
+    for e, im, map_level in interior_edges(level=level):
+        below = math.nextafter(e, -math.inf)
+        cells = listed(level, (below, im), (e, im))
+        out.append((e, im, cells, draws_for(level, cells, 0, below, im), draws_for(level, cells, 1, e, im), map_level))
+    return out
+
+
+def shape_plants(level=10):
+    """[(shape, list, draws inside, draws outside, (re, im) inside, (re, im) outside)] of shape_edges_off_the_grid."""
+    out = []
+    for shape, a, b in shape_edges_off_the_grid():
+        cells = listed(level, a, b)
+        out.append((shape, cells, draws_for(level, cells, 0, *a), draws_for(level, cells, 1, *b), a, b))
+    return out
+
+
+def cell_lanes(draws, threads=64, shape="lane0"):
+    return lanes(draws, threads, shape, filler=filler_draws(0))
+
+
+NECK = lambda e: (-0.75, e * GRID)                 # noqa: E731  a ray away from the cusp's cell: between cardioid and bulb
+
+
+def z_1(lib, sample, c=None, **step):
+    return orbit_of(lib, sample, 1, c, **step)[0][0]
+
+
+def replay_cases(lib):
+    """Where the probe's replay ends -> [(name, sample, end, box, t)]: a sample of the cusp's ray whose orbit escapes at
+    `end`, and a canvas whose lower edge is z_t itself, so that z_t is the orbit's first point on it (the ray's orbits climb
+    the real axis: every earlier point is below the edge, every later one on the canvas or beyond it); t None: a canvas no
+    orbit reaches.  t = 1, t = end (the escaping point), and on an orbit of 121 steps the round's and the chunk's edges."""
+    out = []
+    for end in ENDS:
+        sample = with_end(lib, end)
+        points, _ = orbit_of(lib, sample, end)
+        for t in sorted({1, end}):
+            out.append(("end %d: z_%d" % (end, t), sample, end, box_from(points[t - 1]), t))
+    for t in (12, 13, 60, 61, 120):
+        out.append(("end 121: z_%d" % t, sample, 121, box_from(points[t - 1]), t))
+    out.append(("end 121: no point", sample, 121, NOWHERE, None))
+    return out
+
+
+def unmarking_samples(lib):
+    """(window, marker, [samples that must not mark]): under max_iter 120, min_iter 13 a sample of the neck's ray that is
+    accepted (end 61), and from the cusp's cell and the shapes one that is too fast (end 13), one that never escapes (end
+    121) and two that are rejected -- every one with orbit points on WIDE_BOX."""
+    marker = with_end(lib, 61, ray=NECK)
+    return (120, 13), marker, [with_end(lib, 13), with_end(lib, 121), (-1.0, 0.0), (0.0, 0.0)]
+
+
+BOUNDED_MARKS = [  # (name, step, fixed c or None, sample, canvas, t: the first on-canvas point is z_t)
+    ("transient", MANDELBROT, (-2.0, 0.0), (0.0, 0.0), box_from((-2.0, 0.0)), 1),       # 0 -> -2 -> 2 -> 2 ...
+    ("period", MANDELBROT, (-2.0, 0.0), (0.0, 0.0), box_from((2.0, 0.0)), 2),
+    ("the saved point", MANDELBROT, (-2.0, 0.0), (2.0, 0.0), box_from((2.0, 0.0)), 1),  # 2 -> 2 ...: every point is z_60
+    ("period 2", MANDELBROT, (-1.0, 0.0), (0.0, 0.0), box_from((0.0, 0.0)), 2),         # 0 -> -1 -> 0 ...
+    ("sampled c", dict(ship=True), None, (-1.0, 0.0), box_from((-1.0, 0.0)), 2),        # -1 -> 0 -> -1 ...
+]                                                  # and each of them on NOWHERE: no point at all, the cycle found at 120
+BOUNDED_MAX_ITER = 180
+SQUARE_C = (-2.0, 2.0, -2.0, 2.0)                  # the whole sample plane as a canvas of --plane cr,ci: cells apart, pixels apart

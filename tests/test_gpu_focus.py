@@ -17,7 +17,7 @@ import pytest
 
 import focus_reference as focus
 from device_launches import SAME, SQUARE, Launches, assert_same, gpu_run as run, omp_threads, planar_states  # noqa: F401
-from plot_harness import exe  # noqa: F401 (a fixture)
+from plot_harness import exe, write_states  # noqa: F401 (exe: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,16 +31,25 @@ def ref(tmp_path_factory):
 
 
 def gpu_launches(cb, w, h, box, max_iter, min_iter, threads, launches, base, ship=False, level=0, cell_list=None,
-                 probe=False):
-    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)) -> (u64 hist [h, w]
-    or, probe=True, the mask's u32 words; counters dict; cb_debug_last_draw_kernel; generator states as u32 planes)."""
-    seq = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads, words=focus.mask_words(level) if probe else None,
+                 probe=False, states=None, guard=0):
+    """`launches` (samples per thread each) on fresh generators (seed 1337, subsequences [0, threads)), or on the given
+    oracle `states` written over them (they are left as they were) -> (u64 hist [h, w] or, probe=True, the mask's u32 words,
+    with `guard` words allocated before and after them and read back too; counters dict; cb_debug_last_draw_kernel;
+    generator states as u32 planes)."""
+    seq = Launches(cb, cb.FractalDimensions.make(w, h, *box), threads,
+                   words=focus.mask_words(level) + 2 * guard if probe else None,
                    tables={} if cell_list is None else {"cells": cell_list})
+    if states is not None:
+        write_states(seq, states)
     variant = base | (cb.CB_KERNEL_FLAG_BURNING_SHIP if ship else 0)
     args = dict(iterations=cb.IterationControl(max_iter, min_iter), level=level)
     if not probe and cell_list is not None:
         args.update(d_cells=seq.tables["cells"].data_ptr(), n_cells=seq.tables["cells"].numel())
-    return seq.launches(cb.focus_probe if probe else cb.draw_buddhabrot_focus, launches, variant, **args).read()
+
+    def probe_entry(d_hist, **a):  # the scaffolding's output buffer is the mask, between its guards
+        cb.focus_probe(d_mask=d_hist + 4 * guard, **a)
+
+    return seq.launches(probe_entry if probe else cb.draw_buddhabrot_focus, launches, variant, **args).read()
 
 
 # ---- 1. the uniform source: a normal render through the focus kernels -------------------------------------------------
