@@ -65,6 +65,8 @@ CB_DEPTH_MAX_SLICES = 256  # depth render: the planes of one
 CB_DENSITY_MAX_RADIUS = 8  # density filter: the widest kernel
 CB_PERIOD_MAX_ENTRIES = 1024  # period-palette render: the table's entries (periods 0 .. 1023)
 CB_FRAMES_MAX = 256  # frames render: the matrices (and planes) of one
+CB_LOCAL_EQUALIZE_MAX_TILES = 16  # locally equalised image: the tiles of one side
+LOCAL_EQUALIZE_CLIP_Q = 4 * 256  # ... and the clip the binary takes by default, in 1/256ths
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -381,6 +383,19 @@ def _load():
         "cb_renderer_set_equalize": (i32, [vp, i32]),
         "cb_renderer_equalize": (i32, [vp]),
         "cb_renderer_last_equalize": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "cb_local_equalize_ok": (i32, [i32, i32, i32, i32, i32, u32]),
+        "cb_local_equalize_bins": (i32, [vp, i32, i32, i32, i32, i32, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "cb_local_equalize_clip": (i32, [vp, u32, vp, C.POINTER(u64)]),
+        "cb_set_grayscale_pixels_local_equalized": (i32, [vp, i32, i32, i32, i32, i32, u32, C.c_double, vp, C.POINTER(u64),
+                                                          C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64),
+                                                          C.POINTER(u64)]),
+        "cb_local_equalize_bins_device": (i32, [vp, i32, i32, i32, i32, i32, vp, C.POINTER(u64), C.POINTER(u64), vp]),
+        "cb_tone_map_device_local_equalized": (i32, [vp, i32, i32, i32, i32, i32, u32, C.c_double, vp, C.POINTER(u64),
+                                                     C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64),
+                                                     vp]),
+        "cb_renderer_set_local_equalize": (i32, [vp, i32, i32, u32]),
+        "cb_renderer_local_equalize": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32)]),
+        "cb_renderer_last_local_equalize": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib_, name)  # AttributeError here = the library does not export the ABI
@@ -419,7 +434,10 @@ EXPORTED_SYMBOLS = (
     "cb_density_thresholds cb_density_arguments_ok cb_density_filter cb_density_filter_device "
     "cb_renderer_set_density_filter cb_renderer_density_filter "
     "cb_equalize_key cb_equalize_bins cb_equalize_table cb_set_grayscale_pixels_equalized cb_equalize_bins_device "
-    "cb_tone_map_device_equalized cb_renderer_set_equalize cb_renderer_equalize cb_renderer_last_equalize"
+    "cb_tone_map_device_equalized cb_renderer_set_equalize cb_renderer_equalize cb_renderer_last_equalize "
+    "cb_local_equalize_ok cb_local_equalize_bins cb_local_equalize_clip cb_set_grayscale_pixels_local_equalized "
+    "cb_local_equalize_bins_device cb_tone_map_device_local_equalized cb_renderer_set_local_equalize "
+    "cb_renderer_local_equalize cb_renderer_last_local_equalize"
 ).split()
 
 
@@ -1025,6 +1043,28 @@ class Renderer:
                "cb_renderer_last_equalize")
         return int(lit.value), int(keys.value), int(levels.value)
 
+    def set_local_equalize(self, tx, ty=None, clip_q=LOCAL_EQUALIZE_CLIP_Q):
+        """Local equalisation of every image call (cb_renderer_set_local_equalize): "Locally equalised image", a grid of
+        tx x ty tiles (ty = tx by default) and a clip in 1/256ths; tx = 0 turns it off.  Refused beside a white clip or
+        equalisation."""
+        tx = int(tx)
+        _check(lib.cb_renderer_set_local_equalize(self._h, tx, tx if ty is None else int(ty), int(clip_q)),
+               "cb_renderer_set_local_equalize")
+
+    @property
+    def local_equalize(self):
+        """(tx, ty, clip_q) as set; (0, 0, 0) without."""
+        tx, ty, clip_q = C.c_int32(), C.c_int32(), C.c_uint32()
+        _check(lib.cb_renderer_local_equalize(self._h, C.byref(tx), C.byref(ty), C.byref(clip_q)), "cb_renderer_local_equalize")
+        return int(tx.value), int(ty.value), int(clip_q.value)
+
+    def last_local_equalize(self):
+        """(lit, lit_tiles, moved) of the last image call made locally equalised (cb_renderer_last_local_equalize)."""
+        lit, lit_tiles, moved = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib.cb_renderer_last_local_equalize(self._h, C.byref(lit), C.byref(lit_tiles), C.byref(moved)),
+               "cb_renderer_last_local_equalize")
+        return int(lit.value), int(lit_tiles.value), int(moved.value)
+
     def color_image(self, planes=(0, 1, 2), gamma=1.0, mode=0, compose="rgb", stretch=(2.0, 1.0), hue_shift=0.0):
         """Colour stage on the device (cb_renderer_color_image): planes[0..2] -> (big-endian u16 image [h,w,3] = the
         PPM body, levels [(black, white)] * 3)."""
@@ -1165,6 +1205,72 @@ def tone_map_device_equalized(d_hist, w, h, gamma, d_gray_be, stream=0):
         "cb_tone_map_device_equalized",
     )
     return int(mx.value), float(scale.value), int(lit.value), int(keys.value), int(levels.value)
+
+
+def _planes_of(hist):
+    a = np.ascontiguousarray(hist, dtype=np.uint64)
+    return a.reshape((1,) + a.shape) if a.ndim == 2 else a
+
+
+def local_equalize_bins(hist, tx, ty):
+    """cb_local_equalize_bins over `hist` [h,w] or [planes,h,w] -> (u64 bins [ty*tx, CB_EQUALIZE_KEYS], lit, max)."""
+    a = _planes_of(hist)
+    planes, h, w = a.shape
+    bins = np.empty((max(int(tx) * int(ty), 1), CB_EQUALIZE_KEYS), dtype=np.uint64)
+    lit, mx = C.c_uint64(), C.c_uint64()
+    _check(lib.cb_local_equalize_bins(a.ctypes.data, w, h, planes, int(tx), int(ty), bins.ctypes.data, C.byref(lit), C.byref(mx)),
+           "cb_local_equalize_bins")
+    return bins, int(lit.value), int(mx.value)
+
+
+def local_equalize_clip(bins, clip_q):
+    """cb_local_equalize_clip of one tile's bins -> (u64 clipped [CB_EQUALIZE_KEYS], moved)."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64)
+    assert b.shape == (CB_EQUALIZE_KEYS,)
+    clipped = np.empty(CB_EQUALIZE_KEYS, dtype=np.uint64)
+    moved = C.c_uint64()
+    _check(lib.cb_local_equalize_clip(b.ctypes.data, int(clip_q), clipped.ctypes.data, C.byref(moved)), "cb_local_equalize_clip")
+    return clipped, int(moved.value)
+
+
+def set_grayscale_pixels_local_equalized(hist, tx, ty, clip_q, gamma):
+    """cb_set_grayscale_pixels_local_equalized over `hist` [h,w] or [planes,h,w] -> (u16 image in the shape of `hist`,
+    host-endian, max count, 65535 / max, lit, lit_tiles, moved)."""
+    a = _planes_of(hist)
+    planes, h, w = a.shape
+    gray = np.empty(np.shape(hist), dtype=np.uint16)
+    mx, scale, lit, lit_tiles, moved = C.c_uint64(), C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(
+        lib.cb_set_grayscale_pixels_local_equalized(a.ctypes.data, w, h, planes, int(tx), int(ty), int(clip_q), float(gamma),
+                                                    gray.ctypes.data, C.byref(mx), C.byref(scale), C.byref(lit),
+                                                    C.byref(lit_tiles), C.byref(moved)),
+        "cb_set_grayscale_pixels_local_equalized",
+    )
+    return gray, int(mx.value), float(scale.value), int(lit.value), int(lit_tiles.value), int(moved.value)
+
+
+def local_equalize_bins_device(d_hist, w, h, planes, tx, ty, stream=0):
+    """cb_local_equalize_bins_device on caller-owned device memory (an integer pointer to planes*h*w u64) -> (bins
+    [ty*tx, CB_EQUALIZE_KEYS], lit, max)."""
+    bins = np.empty((int(tx) * int(ty), CB_EQUALIZE_KEYS), dtype=np.uint64)
+    lit, mx = C.c_uint64(), C.c_uint64()
+    _check(lib.cb_local_equalize_bins_device(d_hist, w, h, planes, int(tx), int(ty), bins.ctypes.data, C.byref(lit),
+                                             C.byref(mx), stream),
+           "cb_local_equalize_bins_device")
+    return bins, int(lit.value), int(mx.value)
+
+
+def tone_map_device_local_equalized(d_hist, w, h, planes, tx, ty, clip_q, gamma, d_gray_be, stream=0):
+    """cb_tone_map_device_local_equalized on caller-owned device memory (integer pointers) -> (max, scale, lit, lit_tiles,
+    moved)."""
+    mx, scale, lit, lit_tiles, moved = C.c_uint64(), C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(
+        lib.cb_tone_map_device_local_equalized(d_hist, w, h, planes, int(tx), int(ty), int(clip_q), float(gamma), d_gray_be,
+                                               C.byref(mx), C.byref(scale), C.byref(lit), C.byref(lit_tiles),
+                                               C.byref(moved), stream),
+        "cb_tone_map_device_local_equalized",
+    )
+    return int(mx.value), float(scale.value), int(lit.value), int(lit_tiles.value), int(moved.value)
 
 
 def density_thresholds(radius, alpha=0.5, n0=1):

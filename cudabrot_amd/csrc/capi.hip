@@ -359,8 +359,12 @@ struct cb_renderer {
   uint64_t density_thresholds[CB_DENSITY_MAX_RADIUS + 1];
   // Equalisation ("Equalised image" of include/cudabrot_amd.h): an output setting as well, never on beside a white clip.
   bool equalize;
-  // What the last image call found under the exposure set now (cb_renderer_last_white, cb_renderer_last_equalize): the
-  // two setters clear it.
+  // Local equalisation ("Locally equalised image" of include/cudabrot_amd.h): an output setting too, tiles_x = 0 = off,
+  // never on beside a white clip or the equalisation above.
+  int local_tiles_x, local_tiles_y;
+  uint32_t local_clip_q;
+  // What the last image call found under the exposure set now (cb_renderer_last_white, cb_renderer_last_equalize,
+  // cb_renderer_last_local_equalize): the setters clear it.
   cb::Exposed last_exposed;
 };
 
@@ -837,12 +841,21 @@ int swap_in_planes(cb_renderer *r, size_t planes, const uint32_t *lut_host, uint
 }
 
 // The tone map of `rows` rows of w counters at `hist`, exposed as the renderer is set: plainly, against the white point of
-// its clip, or equalised.  The renderer keeps what the call found.
-int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, double gamma, int mode, uint16_t *d_gray_be,
-                      uint64_t *max_out, double *scale_out) {
-  const cb::Exposure how = {r->equalize ? cb::Exposure::kEqualized
-                                        : (r->white_clip != 0.0 ? cb::Exposure::kWhiteClip : cb::Exposure::kPlain),
-                            r->white_clip};
+// its clip, equalised, or locally equalised: the rows are then planes of `plane_h` rows that share the tiles' tables.  The
+// renderer keeps what the call found.
+int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, int plane_h, double gamma, int mode,
+                      uint16_t *d_gray_be, uint64_t *max_out, double *scale_out) {
+  cb::Exposure how = {r->equalize ? cb::Exposure::kEqualized
+                                  : (r->white_clip != 0.0 ? cb::Exposure::kWhiteClip : cb::Exposure::kPlain),
+                      r->white_clip};
+  if (r->local_tiles_x != 0) {
+    if (plane_h <= 0 || rows % plane_h != 0) return (int) hipErrorInvalidValue;
+    how.kind = cb::Exposure::kLocalEqualized;
+    how.planes = rows / plane_h;
+    how.tiles_x = r->local_tiles_x;
+    how.tiles_y = r->local_tiles_y;
+    how.clip_q = r->local_clip_q;
+  }
   const int rc = cb::tone_map_exposed(reinterpret_cast<const unsigned long long *>(hist), r->dims.w, rows, gamma, mode, how,
                                       d_gray_be, &r->last_exposed, r->stream);
   if (rc) return rc;
@@ -856,13 +869,13 @@ int tone_map_counters(cb_renderer *r, const cb_pixel *hist, int rows, double gam
 // smoothed in groups of `group` where the renderer has a density filter.  The filtered counters live for this call only.
 int tone_map_rows(cb_renderer *r, const cb_pixel *hist, int rows, int plane_h, int group, double gamma, int mode,
                   uint16_t *d_gray_be, uint64_t *max_out, double *scale_out) {
-  if (r->density_radius == 0) return tone_map_counters(r, hist, rows, gamma, mode, d_gray_be, max_out, scale_out);
+  if (r->density_radius == 0) return tone_map_counters(r, hist, rows, plane_h, gamma, mode, d_gray_be, max_out, scale_out);
   if (plane_h <= 0 || rows % plane_h != 0) return (int) hipErrorInvalidValue;
   cb_pixel *d_filtered = nullptr;
   CB_TRY(hipMalloc(reinterpret_cast<void **>(&d_filtered), (size_t) rows * (size_t) r->dims.w * sizeof(cb_pixel)));
   int rc = cb_density_filter_device(hist, r->dims.w, plane_h, rows / plane_h, group, r->density_radius,
                                     r->density_thresholds, d_filtered, r->stream);
-  if (rc == 0) rc = tone_map_counters(r, d_filtered, rows, gamma, mode, d_gray_be, max_out, scale_out);  // synchronises
+  if (rc == 0) rc = tone_map_counters(r, d_filtered, rows, plane_h, gamma, mode, d_gray_be, max_out, scale_out);  // synchronises
   (void) hipFree(d_filtered);
   return rc;
 }
@@ -1888,6 +1901,7 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
   if (r->white_clip != 0.0) return (int) hipErrorInvalidValue;  // the colour stage has a stretch of its own ("White clip")
   if (r->density_radius != 0) return (int) hipErrorInvalidValue;  // and works on 16-bit planes ("Density filter")
   if (r->equalize) return (int) hipErrorInvalidValue;             // its stretch again ("Equalised image")
+  if (r->local_tiles_x != 0) return (int) hipErrorInvalidValue;   // and again ("Locally equalised image")
   const size_t n = (size_t) r->dims.w * (size_t) r->dims.h;
   const cb_pixel *src[3];
   for (int j = 0; j < 3; ++j) {
@@ -1912,8 +1926,9 @@ int cb_renderer_color_image(cb_renderer *r, const int planes[3], double gamma, i
 int cb_renderer_set_white_clip(cb_renderer *r, double percent) {
   if (!r || !cb_white_clip_ok(percent)) return (int) hipErrorInvalidValue;
   if (percent != 0.0 && r->equalize) return (int) hipErrorInvalidValue;  // one exposure at a time ("Equalised image")
+  if (percent != 0.0 && r->local_tiles_x != 0) return (int) hipErrorInvalidValue;  // ("Locally equalised image")
   r->white_clip = percent;
-  if (!r->equalize) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (an equalised renderer keeps what it found: nothing changed)
+  if (!r->equalize && r->local_tiles_x == 0) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (an equalised renderer keeps what it found: nothing changed)
   return 0;
 }
 
@@ -1945,15 +1960,15 @@ int cb_renderer_density_filter(const cb_renderer *r, int *radius_out, double *al
 int cb_renderer_last_white(const cb_renderer *r, uint64_t *white_out, uint64_t *lit_out, uint64_t *clipped_out) {
   if (!r || !white_out || !lit_out || !clipped_out) return (int) hipErrorInvalidValue;
   *white_out = r->last_exposed.white;
-  *lit_out = r->equalize ? 0 : r->last_exposed.lit;  // (an equalised image counts its lit pixels too)
+  *lit_out = (r->equalize || r->local_tiles_x != 0) ? 0 : r->last_exposed.lit;  // (an equalised image counts its lit pixels too)
   *clipped_out = r->last_exposed.clipped;
   return 0;
 }
 
 int cb_renderer_set_equalize(cb_renderer *r, int on) {
-  if (!r || (on != 0 && r->white_clip != 0.0)) return (int) hipErrorInvalidValue;
+  if (!r || (on != 0 && (r->white_clip != 0.0 || r->local_tiles_x != 0))) return (int) hipErrorInvalidValue;
   r->equalize = on != 0;
-  if (r->white_clip == 0.0) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (likewise a clipped one)
+  if (r->white_clip == 0.0 && r->local_tiles_x == 0) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (likewise a clipped one)
   return 0;
 }
 
@@ -1964,6 +1979,36 @@ int cb_renderer_last_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t 
   *lit_out = r->equalize ? r->last_exposed.lit : 0;  // (so does a clipped one)
   *keys_out = r->last_exposed.keys;
   *levels_out = r->last_exposed.levels;
+  return 0;
+}
+
+int cb_renderer_set_local_equalize(cb_renderer *r, int tx, int ty, uint32_t clip_q) {
+  if (!r) return (int) hipErrorInvalidValue;
+  if (tx != 0) {  // one exposure at a time
+    if (r->white_clip != 0.0 || r->equalize || !cb_local_equalize_ok(r->dims.w, r->dims.h, 1, tx, ty, clip_q)) {
+      return (int) hipErrorInvalidValue;
+    }
+  }
+  r->local_tiles_x = tx;
+  r->local_tiles_y = tx ? ty : 0;
+  r->local_clip_q = tx ? clip_q : 0;
+  if (r->white_clip == 0.0 && !r->equalize) r->last_exposed = {0, 0, 0, 0, 0, 0};  // (those keep what they found)
+  return 0;
+}
+
+int cb_renderer_local_equalize(const cb_renderer *r, int *tx_out, int *ty_out, uint32_t *clip_q_out) {
+  if (!r || !tx_out || !ty_out || !clip_q_out) return (int) hipErrorInvalidValue;
+  *tx_out = r->local_tiles_x;
+  *ty_out = r->local_tiles_y;
+  *clip_q_out = r->local_clip_q;
+  return 0;
+}
+
+int cb_renderer_last_local_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out) {
+  if (!r || !lit_out || !lit_tiles_out || !moved_out) return (int) hipErrorInvalidValue;
+  *lit_out = r->local_tiles_x != 0 ? r->last_exposed.lit : 0;
+  *lit_tiles_out = r->last_exposed.lit_tiles;
+  *moved_out = r->last_exposed.moved;
   return 0;
 }
 

@@ -196,6 +196,40 @@ bool parse_density(const char *text, DensityFilter *out) {
   return true;
 }
 
+// --local-equalize TX[xTY][:CLIP]: TX and TY digits from 1 to 16, TY = TX where left out; CLIP 0 or from 1 to 256,
+// rounded to 1/256, 4 where left out.
+bool parse_local_equalize(const char *text, LocalEqualize *out) {
+  const char *at = text;
+  long side[2] = {0, 0};
+  for (int k = 0; k < 2; ++k) {
+    if (*at < '0' || *at > '9') return false;
+    for (; *at >= '0' && *at <= '9'; ++at) {
+      side[k] = side[k] * 10 + (*at - '0');
+      if (side[k] > CB_LOCAL_EQUALIZE_MAX_TILES) return false;
+    }
+    if (side[k] < 1) return false;
+    if (k == 0 && *at != 'x') {
+      side[1] = side[0];
+      break;
+    }
+    if (k == 0) ++at;
+  }
+  double clip = 4.0;
+  if (*at == ':') {
+    ++at;
+    if (*at == 0 || *at == ' ' || *at == '\t') return false;  // (strtod would skip blanks)
+    char *end = nullptr;
+    clip = strtod(at, &end);
+    if (end == at) return false;
+    at = end;
+  }
+  if (*at != 0 || !(clip == 0.0 || (clip >= 1.0 && clip <= 256.0))) return false;
+  out->tx = (int) side[0];
+  out->ty = (int) side[1];
+  out->clip_q = (uint32_t) floor(clip * 256.0 + 0.5);
+  return true;
+}
+
 // The usage text is the command's documented interface (cudabrot.cu:579-620) and is printed as is.
 const char kUsageBody[] =
     "Options may be one or more of the following:\n"
@@ -233,6 +267,12 @@ const char kUsageBody[] =
     "  --equalize: Equalizes the image: a pixel's brightness is the share of\n"
     "     the nonzero pixels that are no brighter than it, rather than its\n"
     "     count over the largest count. -g applies to that share.\n"
+    "  --local-equalize <TX[xTY][:CLIP]>: Equalizes the image tile by tile:\n"
+    "     the image is cut into TX by TY tiles (1 to 16 a side, TY = TX\n"
+    "     if left out), every tile gets the curve of --equalize over its\n"
+    "     own pixels, and a pixel the blend of the curves of the four tile\n"
+    "     centres around it. CLIP (0 = off, or 1 to 256; default 4) limits\n"
+    "     how far a tile may raise its contrast over an even spread.\n"
     "\n"
     "The following settings control the location of the output image on the\n"
     "complex plane, but samples are always drawn from the entire Mandelbrot-\n"
@@ -582,6 +622,15 @@ const std::vector<Flag> &flag_table() {
       // --equalize: every image exposed by the rank of its counters (include/cudabrot_amd.h, "Equalised image")
       {"--equalize", Value::kNone, nullptr, false,
        [](Settings &s, long, double, const char *) { s.equalize = true; return kOk; }},
+      // --local-equalize TX[xTY][:CLIP]: every image exposed by the rank of its counters within the tiles of a grid
+      // (include/cudabrot_amd.h, "Locally equalised image"); text: TX and TY decimal digits, CLIP in strtod's syntax
+      // (hexfloats accepted), rounded to 1/256
+      {"--local-equalize", Value::kText, nullptr, false,
+       [](Settings &s, long, double, const char *t) {
+         return parse_local_equalize(t, &s.local_equalize)
+                    ? kOk
+                    : "Invalid local equalisation (want TX[xTY][:CLIP], 1 to 16 tiles a side, CLIP 0 or from 1 to 256)";
+       }},
       // --tonemap lut|thresholds|host: the form of the device tone map, or the reference's host loop
       {"--tonemap", Value::kText, nullptr, false,
        [](Settings &s, long, double, const char *t) {
@@ -618,6 +667,7 @@ const Partner kPhoenix = {[](const Settings &s) { return s.phoenix; }, "--phoeni
 const Partner kPeriodPalette = {[](const Settings &s) { return s.period_palette(); }, "--period-palette"};
 const Partner kColor = {[](const Settings &s) { return s.color_file != nullptr; }, "--color"};
 const Partner kWhiteClip = {[](const Settings &s) { return s.white_clip > 0.0; }, "--white-clip"};
+const Partner kEqualize = {[](const Settings &s) { return s.equalize; }, "--equalize"};
 
 // The refusals behind the flag loop, in the order they are looked at: the first row that applies and has something to
 // say ends the process.  A row says "<subject> does not combine with <the first of its partners that is present>.", or,
@@ -706,6 +756,17 @@ const std::vector<Refusal> &refusal_table() {
       // an equalised image has an exposure of its own: no white point to clip against, and the colour stage stretches its
       // planes itself (include/cudabrot_amd.h, "Equalised image").  The last row, likewise
       {[](const Settings &s) { return s.equalize; }, "--equalize", {kWhiteClip, kColor}, nullptr},
+      // a locally equalised image is cut into tiles of at least a pixel (-w and -h may stand behind the flag), and is an
+      // exposure of its own as the equalised one is (include/cudabrot_amd.h, "Locally equalised image").  The last rows,
+      // likewise
+      {[](const Settings &s) {
+         return s.local_equalize.tx > 0 && (s.local_equalize.tx > s.canvas.w || s.local_equalize.ty > s.canvas.h);
+       },
+       nullptr, {}, [](const Settings &s) {
+         printf("--local-equalize needs a pixel per tile: %dx%d tiles on a %dx%d image.\n", s.local_equalize.tx,
+                s.local_equalize.ty, s.canvas.w, s.canvas.h);
+       }},
+      {[](const Settings &s) { return s.local_equalize.tx > 0; }, "--local-equalize", {kEqualize, kWhiteClip, kColor}, nullptr},
   };
   return table;
 }

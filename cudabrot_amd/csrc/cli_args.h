@@ -32,6 +32,12 @@ struct DensityFilter {
   uint64_t n0 = 1;
 };
 
+// --local-equalize TX[xTY][:CLIP] as given: TY = TX and CLIP = 4 where left out, the clip in 1/256ths; tx 0: no flag.
+struct LocalEqualize {
+  int tx = 0, ty = 0;
+  uint32_t clip_q = 0;
+};
+
 // A list of colour stops, K:RRGGBB[,K:RRGGBB...], as --palette, --depth-palette and --period-palette give one; none: no flag.
 struct Stops {
   int n = 0;
@@ -150,6 +156,10 @@ struct Settings {
   // --equalize (extension): every image of the run exposed by the rank of its counters among the lit ones instead of by
   // their size (include/cudabrot_amd.h, "Equalised image"; cb_renderer_set_equalize)
   bool equalize = false;
+  // --local-equalize TX[xTY][:CLIP] (extension): every image of the run exposed by the rank of its counters within the
+  // tiles of a grid, blended between the tile centres (include/cudabrot_amd.h, "Locally equalised image";
+  // cb_renderer_set_local_equalize); tx 0, the default, is off
+  LocalEqualize local_equalize;
   // The one place that says what the flags above make of the output: a palette of any kind turns its render's planes into
   // three and the file into a PPM, so it goes before the render it colours; --depth and --sweep stack their planes;
   // --channel has an image per plane.  The refusal table lets no two of the renders meet.

@@ -151,6 +151,11 @@ class Run {
       fprintf(stderr, "{\"equalize\": true}\n");
       fflush(stderr);
     }
+    if (cfg_.local_equalize.tx > 0 && cfg_.print_stats) {  // likewise: the grid and the clip in 1/256ths
+      fprintf(stderr, "{\"local_equalize\": {\"tiles\": [%d, %d], \"clip_q\": %u}}\n", cfg_.local_equalize.tx,
+              cfg_.local_equalize.ty, (unsigned) cfg_.local_equalize.clip_q);
+      fflush(stderr);
+    }
     setup();
     load_inprogress();
     load_rng_state();
@@ -182,6 +187,7 @@ class Run {
   std::vector<uint16_t> color_grays_;  // --color with --tonemap host: the three planes' values, kept for the compose
   std::vector<cb_pixel> filtered_;  // --density-filter with --tonemap host: the counters the last image was mapped from
   uint64_t host_equalized_[3] = {0, 0, 0};  // --equalize with --tonemap host: lit, keys, levels of the last image
+  uint64_t host_local_[3] = {0, 0, 0};  // --local-equalize with --tonemap host: lit, lit tiles, moved of the last image
   std::vector<double> frames_, sweep_angles_;  // --sweep: the F matrices and their angles (cb_frames_from_sweep)
 
   bool need_host_counts() const { return cfg_.inprogress_file != nullptr || cfg_.host_tonemap; }
@@ -273,6 +279,10 @@ class Run {
       CB_CHECK(cb_renderer_set_density_filter(renderer_, cfg_.density.radius, cfg_.density.alpha, cfg_.density.n0));
     }
     if (cfg_.equalize) CB_CHECK(cb_renderer_set_equalize(renderer_, 1));  // likewise
+    if (cfg_.local_equalize.tx > 0) {  // likewise
+      CB_CHECK(cb_renderer_set_local_equalize(renderer_, cfg_.local_equalize.tx, cfg_.local_equalize.ty,
+                                              cfg_.local_equalize.clip_q));
+    }
     if (cfg_.palette()) {  // after the plane and c: the table of the stops, one entry per escape index below -m
       const std::vector<uint32_t> lut = table_of(cfg_.palette_stops, (size_t) cfg_.iterations.max_escape_iterations);
       CB_CHECK(cb_renderer_set_palette(renderer_, lut.data(), (uint32_t) lut.size()));
@@ -553,8 +563,9 @@ class Run {
 
   // The reference's host loop over `rows` rows of the counters at `hist` -- with --white-clip, the clipped one; with
   // --equalize, the equalised one, whose bins and table are made once here and what they found kept (host_equalized_), as a
-  // renderer keeps it; with --density-filter, over the filtered counters (filtered_): planes of the canvas's height,
-  // smoothed in groups of `group`.
+  // renderer keeps it; with --local-equalize, the locally equalised one over the planes of the canvas's height, what it
+  // found kept likewise (host_local_); with --density-filter, over the filtered counters (filtered_): planes of the
+  // canvas's height, smoothed in groups of `group`.
   void host_tone_map(const cb_pixel *hist, int rows, int group, uint16_t *gray, uint64_t *max, double *scale) {
     if (cfg_.density.radius > 0) {
       uint64_t table[CB_DENSITY_MAX_RADIUS + 1];
@@ -572,6 +583,11 @@ class Run {
       CB_CHECK(cb_equalize_table(bins.data(), cfg_.gamma_correction, table.data(), &host_equalized_[1], &host_equalized_[2]));
       *scale = ((double) 0xffff) / ((double) *max);
       for (uint64_t i = 0; i < n; ++i) gray[i] = table[cb_equalize_key(hist[i])];
+    } else if (cfg_.local_equalize.tx > 0) {
+      CB_CHECK(cb_set_grayscale_pixels_local_equalized(hist, cfg_.canvas.w, cfg_.canvas.h, rows / cfg_.canvas.h,
+                                                       cfg_.local_equalize.tx, cfg_.local_equalize.ty,
+                                                       cfg_.local_equalize.clip_q, cfg_.gamma_correction, gray, max, scale,
+                                                       &host_local_[0], &host_local_[1], &host_local_[2]));
     } else if (cfg_.white_clip > 0.0) {
       CB_CHECK(cb_set_grayscale_pixels_white(hist, cfg_.canvas.w, rows, cfg_.gamma_correction, cfg_.white_clip, gray, max,
                                              scale, nullptr));
@@ -596,6 +612,13 @@ class Run {
       if (!cfg_.host_tonemap) CB_CHECK(cb_renderer_last_equalize(renderer_, &lit, &keys, &levels));
       printf("Equalized: %lu lit pixels in %lu keys, %lu output levels\n", (unsigned long) lit, (unsigned long) keys,
              (unsigned long) levels);
+    }
+    if (cfg_.local_equalize.tx > 0) {  // likewise
+      uint64_t lit = host_local_[0], lit_tiles = host_local_[1], moved = host_local_[2];
+      if (!cfg_.host_tonemap) CB_CHECK(cb_renderer_last_local_equalize(renderer_, &lit, &lit_tiles, &moved));
+      printf("Locally equalized: %dx%d tiles, clip %u/256, %lu lit pixels in %lu lit tiles, %lu counts moved\n",
+             cfg_.local_equalize.tx, cfg_.local_equalize.ty, (unsigned) cfg_.local_equalize.clip_q, (unsigned long) lit,
+             (unsigned long) lit_tiles, (unsigned long) moved);
     }
     if (!(cfg_.white_clip > 0.0)) return;
     uint64_t white = 0, lit = 0, clipped = 0;

@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "../../include/cudabrot_amd.h"
-#include "color_math.h"  // equalize_key
+#include "equalize_local.h"  // equalize_key (color_math.h) and the local grid
 
 namespace {
 
@@ -30,6 +30,123 @@ inline uint16_t to_u16(double v) {
 }
 
 }  // namespace
+
+namespace cb {
+
+void equalize_table_keys(const uint64_t *bins, uint32_t n_keys, double gamma, uint16_t *table_out, uint64_t *keys_out,
+                         uint64_t *levels_out) {
+  uint64_t lit = 0, le = 0, keys = 0, levels = 0;
+  for (uint32_t k = 0; k < n_keys; k++) lit += bins[k];
+  table_out[0] = 0;
+  std::vector<bool> seen(65536, false);
+  // an empty bin has the rank, and so the value, of the key below it: cb_tone_value is called once per lit key
+  for (uint32_t k = 1; k < n_keys; k++) {
+    table_out[k] = table_out[k - 1];
+    if (bins[k] == 0) continue;
+    le += bins[k];
+    // the full rank is full white: cb_tone_value(lit, lit, gamma) is 65535 in exact arithmetic, and 65534 in doubles for
+    // about one lit in seven (lit * (65535.0 / lit) rounds below 65535 and the conversion truncates)
+    table_out[k] = (le == lit && gamma > 0.0) ? (uint16_t) 0xffff : cb_tone_value(le, lit, gamma);
+    if (!seen[table_out[k]]) levels++;
+    seen[table_out[k]] = true;
+    keys++;
+  }
+  *keys_out = keys;
+  *levels_out = levels;
+}
+
+namespace {
+
+bool local_clip_ok(uint32_t clip_q) { return clip_q == 0 || (clip_q >= 256 && clip_q <= 65536); }
+
+// "Locally equalised image", clip: n_keys bins of one tile -> its clipped bins (which may be `bins` itself) and E.
+uint64_t local_clip(const uint64_t *bins, uint32_t n_keys, uint32_t clip_q, uint64_t *clipped) {
+  uint64_t lit = 0, keys = 0;
+  for (uint32_t k = 0; k < n_keys; k++) {
+    lit += bins[k];
+    keys += bins[k] != 0 ? 1u : 0u;
+  }
+  if (clip_q == 0 || keys == 0) {
+    if (clipped != bins) memcpy(clipped, bins, n_keys * sizeof(uint64_t));
+    return 0;
+  }
+  const uint64_t share = (uint64_t) clip_q * lit / (256 * keys), limit = share > 1 ? share : 1;
+  uint64_t excess = 0;
+  for (uint32_t k = 0; k < n_keys; k++) excess += bins[k] > limit ? bins[k] - limit : 0;
+  const uint64_t each = excess / keys, more = excess % keys;
+  uint64_t m = 0;  // the lit keys so far
+  for (uint32_t k = 0; k < n_keys; k++) {
+    const uint64_t b = bins[k];
+    clipped[k] = b == 0 ? 0 : (b < limit ? b : limit) + each + (m < more ? 1u : 0u);
+    m += b != 0 ? 1u : 0u;
+  }
+  return excess;
+}
+
+uint64_t largest(const cb_pixel *hist, uint64_t n) {
+  uint64_t max = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (hist[i] > max) max = hist[i];
+  }
+  return max;
+}
+
+// bins_t of the definition, n_keys entries a tile (every key of the array is below n_keys), and lit.
+void local_bins(const cb_pixel *hist, const LocalGrid &g, uint32_t n_keys, uint64_t *bins, uint64_t *lit_out) {
+  memset(bins, 0, (size_t) g.tx * g.ty * n_keys * sizeof(uint64_t));
+  uint64_t lit = 0;
+  for (uint32_t p = 0; p < g.planes; ++p) {
+    for (uint32_t j = 0; j < g.ty; ++j) {
+      for (uint32_t y = g.ey[j]; y < g.ey[j + 1]; ++y) {
+        const cb_pixel *row = hist + ((uint64_t) p * g.h + y) * g.w;
+        for (uint32_t i = 0; i < g.tx; ++i) {
+          uint64_t *mine = bins + (size_t) (j * g.tx + i) * n_keys;
+          for (uint32_t x = g.ex[i]; x < g.ex[i + 1]; ++x) {
+            if (row[x] == 0) continue;
+            mine[equalize_key(row[x])]++;
+            lit++;
+          }
+        }
+      }
+    }
+  }
+  *lit_out = lit;
+}
+
+}  // namespace
+
+void local_equalize_tables(const uint64_t *bins, uint32_t n_keys, uint32_t tiles, uint32_t clip_q, double gamma,
+                           uint16_t *tables_out, uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out) {
+  std::vector<uint64_t> all(n_keys, 0), clipped(n_keys);
+  std::vector<bool> empty(tiles, false);
+  uint64_t lit = 0, lit_tiles = 0, moved = 0, keys = 0, levels = 0;
+  for (uint32_t t = 0; t < tiles; ++t) {
+    const uint64_t *mine = bins + (size_t) t * n_keys;
+    uint64_t lit_t = 0;
+    for (uint32_t k = 0; k < n_keys; k++) {
+      all[k] += mine[k];
+      lit_t += mine[k];
+    }
+    empty[t] = lit_t == 0;
+    if (empty[t]) continue;
+    lit += lit_t;
+    lit_tiles++;
+    moved += local_clip(mine, n_keys, clip_q, clipped.data());
+    equalize_table_keys(clipped.data(), n_keys, gamma, tables_out + (size_t) t * n_keys, &keys, &levels);
+  }
+  if (lit_tiles < tiles) {  // the empty tiles take the global curve, unclipped
+    std::vector<uint16_t> global(n_keys);
+    equalize_table_keys(all.data(), n_keys, gamma, global.data(), &keys, &levels);
+    for (uint32_t t = 0; t < tiles; ++t) {
+      if (empty[t]) memcpy(tables_out + (size_t) t * n_keys, global.data(), n_keys * sizeof(uint16_t));
+    }
+  }
+  *lit_out = lit;
+  *lit_tiles_out = lit_tiles;
+  *moved_out = moved;
+}
+
+}  // namespace cb
 
 extern "C" {
 
@@ -125,24 +242,7 @@ int cb_equalize_bins(const cb_pixel *hist, uint64_t n, uint64_t *bins_out, uint6
 
 int cb_equalize_table(const uint64_t *bins, double gamma, uint16_t *table_out, uint64_t *keys_out, uint64_t *levels_out) {
   if (!bins || !table_out || !keys_out || !levels_out) return 1;  // hipErrorInvalidValue
-  uint64_t lit = 0, le = 0, keys = 0, levels = 0;
-  for (uint32_t k = 0; k < CB_EQUALIZE_KEYS; k++) lit += bins[k];
-  table_out[0] = 0;
-  std::vector<bool> seen(65536, false);
-  // an empty bin has the rank, and so the value, of the key below it: cb_tone_value is called once per lit key
-  for (uint32_t k = 1; k < CB_EQUALIZE_KEYS; k++) {
-    table_out[k] = table_out[k - 1];
-    if (bins[k] == 0) continue;
-    le += bins[k];
-    // the full rank is full white: cb_tone_value(lit, lit, gamma) is 65535 in exact arithmetic, and 65534 in doubles for
-    // about one lit in seven (lit * (65535.0 / lit) rounds below 65535 and the conversion truncates)
-    table_out[k] = (le == lit && gamma > 0.0) ? (uint16_t) 0xffff : cb_tone_value(le, lit, gamma);
-    if (!seen[table_out[k]]) levels++;
-    seen[table_out[k]] = true;
-    keys++;
-  }
-  *keys_out = keys;
-  *levels_out = levels;
+  cb::equalize_table_keys(bins, CB_EQUALIZE_KEYS, gamma, table_out, keys_out, levels_out);
   return 0;
 }
 
@@ -160,6 +260,63 @@ int cb_set_grayscale_pixels_equalized(const cb_pixel *hist, int w, int h, double
   if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);  // what the unflagged call reports
   if (lit_out) *lit_out = lit;
   for (uint64_t i = 0; i < n; i++) gray_out[i] = table[cb::equalize_key(hist[i])];
+  return 0;
+}
+
+// "Locally equalised image" of include/cudabrot_amd.h, the definition: the grid, the bins, the clip, the tables, the blend.
+int cb_local_equalize_ok(int w, int h, int planes, int tx, int ty, uint32_t clip_q) {
+  return (w > 0 && h > 0 && planes >= 1 && tx >= 1 && tx <= cb::kLocalMaxTiles && ty >= 1 && ty <= cb::kLocalMaxTiles &&
+          tx <= w && ty <= h && cb::local_clip_ok(clip_q))
+             ? 1
+             : 0;
+}
+
+int cb_local_equalize_bins(const cb_pixel *hist, int w, int h, int planes, int tx, int ty, uint64_t *bins_out,
+                           uint64_t *lit_out, uint64_t *max_out) {
+  if (!hist || !bins_out || !lit_out || !max_out || !cb_local_equalize_ok(w, h, planes, tx, ty, 0)) return 1;  // hipErrorInvalidValue
+  cb::local_bins(hist, cb::local_grid(w, h, planes, tx, ty), CB_EQUALIZE_KEYS, bins_out, lit_out);
+  *max_out = cb::largest(hist, (uint64_t) w * (uint64_t) h * (uint64_t) planes);
+  return 0;
+}
+
+int cb_local_equalize_clip(const uint64_t *bins, uint32_t clip_q, uint64_t *clipped_out, uint64_t *moved_out) {
+  if (!bins || !clipped_out || !moved_out || !cb::local_clip_ok(clip_q)) return 1;  // hipErrorInvalidValue
+  *moved_out = cb::local_clip(bins, CB_EQUALIZE_KEYS, clip_q, clipped_out);
+  return 0;
+}
+
+int cb_set_grayscale_pixels_local_equalized(const cb_pixel *hist, int w, int h, int planes, int tx, int ty, uint32_t clip_q,
+                                            double gamma, uint16_t *gray_out, uint64_t *max_out, double *scale_out,
+                                            uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out) {
+  if (!hist || !gray_out || !cb_local_equalize_ok(w, h, planes, tx, ty, clip_q)) return 1;  // hipErrorInvalidValue
+  const cb::LocalGrid g = cb::local_grid(w, h, planes, tx, ty);
+  const uint64_t n = (uint64_t) w * (uint64_t) h * (uint64_t) planes;
+  const uint64_t max = cb::largest(hist, n);
+  uint64_t lit = 0, lit_tiles = 0, moved = 0;
+  const uint32_t n_keys = cb::equalize_key(max) + 1, tiles = g.tx * g.ty;  // every key of the image is below n_keys
+  std::vector<uint64_t> bins((size_t) tiles * n_keys);
+  std::vector<uint16_t> tables((size_t) tiles * n_keys);
+  cb::local_bins(hist, g, n_keys, bins.data(), &lit);
+  cb::local_equalize_tables(bins.data(), n_keys, tiles, clip_q, gamma, tables.data(), &lit, &lit_tiles, &moved);
+  if (max_out) *max_out = max;
+  if (scale_out) *scale_out = ((double) 0xffff) / ((double) max);  // what the unflagged call reports
+  if (lit_out) *lit_out = lit;
+  if (lit_tiles_out) *lit_tiles_out = lit_tiles;
+  if (moved_out) *moved_out = moved;
+  std::vector<cb::LocalPlace> columns((size_t) w);
+  for (uint32_t x = 0; x < g.w; ++x) columns[x] = cb::local_place(g.cx, g.tx, 2 * x + 1);
+  for (uint32_t p = 0; p < g.planes; ++p) {
+    for (uint32_t y = 0; y < g.h; ++y) {
+      const cb::LocalPlace row = cb::local_place(g.cy, g.ty, 2 * y + 1);
+      const uint16_t *upper = tables.data() + (size_t) row.i0 * g.tx * n_keys, *lower = tables.data() + (size_t) row.i1 * g.tx * n_keys;
+      const uint64_t at = ((uint64_t) p * g.h + y) * g.w;
+      for (uint32_t x = 0; x < g.w; ++x) {
+        const cb::LocalPlace &col = columns[x];
+        const size_t k = cb::equalize_key(hist[at + x]), left = (size_t) col.i0 * n_keys + k, right = (size_t) col.i1 * n_keys + k;
+        gray_out[at + x] = (uint16_t) cb::local_blend(upper[left], upper[right], lower[left], lower[right], col, row);
+      }
+    }
+  }
   return 0;
 }
 

@@ -431,19 +431,24 @@ struct PeriodArgs {
 hipError_t launch_draw_periods(const PeriodArgs &a, bool lockstep, hipStream_t stream);
 
 // How an image is exposed: against its largest counter, against the white point of a clip of `clip_percent` ("White
-// clip" of include/cudabrot_amd.h), or by the rank of its counters ("Equalised image").
+// clip" of include/cudabrot_amd.h), by the rank of its counters ("Equalised image"), or by their rank in the tiles of a
+// grid ("Locally equalised image": the image is `planes` planes, one above the other, that share the tiles' tables).
 struct Exposure {
-  enum Kind { kPlain, kWhiteClip, kEqualized } kind;
+  enum Kind { kPlain, kWhiteClip, kEqualized, kLocalEqualized } kind;
   double clip_percent;  // kWhiteClip's
+  int planes = 1, tiles_x = 0, tiles_y = 0;  // kLocalEqualized's
+  uint32_t clip_q = 0;
 };
-// What exposing found: max always; white, lit and clipped under a white clip; lit, keys and levels equalised; 0 else.
+// What exposing found: max always; white, lit and clipped under a white clip; lit, keys and levels equalised; lit,
+// lit_tiles and moved locally equalised; 0 else.
 struct Exposed {
-  uint64_t max, white, lit, clipped, keys, levels;
+  uint64_t max, white, lit, clipped, keys, levels, lit_tiles = 0, moved = 0;
 };
 // tonemap.hip: finds the top of w x h device counters as `how` says, maps them into big-endian u16 -- the table or the
 // thresholds, as `mode` (CB_TONE_*) and the top choose; an equalised image has one form -- and reports: what
 // cb_tone_map_device, cb_tone_map_device_white and cb_tone_map_device_equalized do, and what a renderer keeps for
-// cb_renderer_last_white and cb_renderer_last_equalize.  *found is written on success only.  Synchronises `stream`.
+// cb_renderer_last_white, cb_renderer_last_equalize and cb_renderer_last_local_equalize.  *found is written on success
+// only.  Synchronises `stream`.
 int tone_map_exposed(const unsigned long long *hist, int w, int h, double gamma, int mode, const Exposure &how,
                      uint16_t *d_gray_be, Exposed *found, hipStream_t stream);
 // exposure.hip: cb_white_count_device, and the largest counter beside its three numbers (max_out may be null).
@@ -454,6 +459,12 @@ int equalize_bins_device(const unsigned long long *hist, unsigned long long n, u
                          uint64_t *max_out, hipStream_t stream);
 int equalize_map_device(const unsigned long long *hist, unsigned long long n, const uint16_t *table_host, uint16_t *d_gray_be,
                         hipStream_t stream);
+// tonemap.hip: the largest of n device counters.  Synchronises `stream`.
+int hist_max_device(const unsigned long long *hist, unsigned long long n, uint64_t *max_out, hipStream_t stream);
+// equalize_local.hip: what cb_local_equalize_bins_device (bins_out_host: tx * ty rows of CB_EQUALIZE_KEYS) and
+// cb_tone_map_device_local_equalized (d_gray_be) do; either output may be null.
+int local_equalize_device(const unsigned long long *hist, int w, int h, int planes, int tx, int ty, uint32_t clip_q,
+                          double gamma, uint64_t *bins_out_host, uint16_t *d_gray_be, Exposed *found, hipStream_t stream);
 
 // Steps per chunk of the LONG stage; the stage split is chosen so that no chunk straddles min_iter.
 // The exact-periodicity check compares z with a saved point at chunk boundaries only, so a cycle of period

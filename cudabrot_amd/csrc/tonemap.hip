@@ -111,6 +111,8 @@ std::vector<unsigned long long> build_thresholds(unsigned long long max, double 
   return thr;
 }
 
+}  // namespace
+
 // The largest of n device counters (GetLinearColorScale, cudabrot.cu:425-439).
 int hist_max_device(const unsigned long long *hist, unsigned long long n, uint64_t *max_out, hipStream_t stream) {
   DeviceBuffer d_max;
@@ -123,6 +125,8 @@ int hist_max_device(const unsigned long long *hist, unsigned long long n, uint64
   CB_HIP_TRY(hipStreamSynchronize(stream));
   return 0;
 }
+
+namespace {
 
 // The map against `top` on a device histogram of n counters: the table over [0, top] or the thresholds, as `mode` and
 // `top` choose.  clamp: counts above `top` exist (the white clip) and take top's value.
@@ -159,15 +163,19 @@ int tone_map_against(const unsigned long long *hist, unsigned long long n, unsig
 }  // namespace
 
 // Find, map, report.  The find step is the kind's own: hist_max_kernel; the radix select of exposure.hip; the bins of
-// equalize.hip and the host's table of them.  Under a white clip the table or the thresholds are chosen by white, not by
-// the maximum.
+// equalize.hip and the host's table of them; the bins of the tiles, equalize_local.hip's.  Under a white clip the table
+// or the thresholds are chosen by white, not by the maximum.
 int tone_map_exposed(const unsigned long long *hist, int w, int h, double gamma, int mode, const Exposure &how,
                      uint16_t *d_gray_be, Exposed *found, hipStream_t stream) {
   if (!hist || !d_gray_be || !found || w <= 0 || h <= 0 || !tone_mode_ok(mode)) return (int) hipErrorInvalidValue;
   const unsigned long long n = (unsigned long long) w * (unsigned long long) h;
   Exposed e = {0, 0, 0, 0, 0, 0};
   int rc;
-  if (how.kind == Exposure::kEqualized) {
+  if (how.kind == Exposure::kLocalEqualized) {  // h rows: `planes` planes of h / planes rows
+    if (how.planes < 1 || h % how.planes != 0) return (int) hipErrorInvalidValue;
+    rc = local_equalize_device(hist, w, h / how.planes, how.planes, how.tiles_x, how.tiles_y, how.clip_q, gamma, nullptr,
+                               d_gray_be, &e, stream);
+  } else if (how.kind == Exposure::kEqualized) {
     std::vector<uint64_t> bins(CB_EQUALIZE_KEYS);
     std::vector<uint16_t> table(CB_EQUALIZE_KEYS);
     rc = equalize_bins_device(hist, n, bins.data(), &e.lit, &e.max, stream);

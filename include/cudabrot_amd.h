@@ -1396,6 +1396,94 @@ int cb_renderer_equalize(const cb_renderer *r);
 /* lit, keys and levels of the last image call made equalised; zeros before one, and after every cb_renderer_set_equalize. */
 int cb_renderer_last_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *keys_out, uint64_t *levels_out);
 
+/* ---- Locally equalised image: one rank curve per tile of the canvas, blended between tile centres -- *
+ *
+ * The equalised image above is still ONE curve for the whole canvas, and a Buddhabrot is not one population: the filaments
+ * beside the body share the bottom few percent of the global ranks.  Contrast-limited adaptive equalisation gives every
+ * tile of the canvas a rank curve of its own, interpolates the curves between the tile centres and limits with a clip how
+ * far a tile may amplify its contrast.  The project's own definition (the reference has none).  Normative; host, device
+ * and the tests' restatement in Python integers agree bit for bit.  All arithmetic on counters, ranks and weights is
+ * unsigned 64-bit integer; cb_tone_value (inside cb_equalize_table) stays the only floating point.
+ *
+ *   input: the image's counters, `planes` planes of h rows of w counters -- the array whose maximum the unflagged image
+ *     takes, seen as planes --; a tile grid TX x TY with 1 <= TX, TY <= CB_LOCAL_EQUALIZE_MAX_TILES, TX <= w, TY <= h; a
+ *     clip clip_q in 1/256ths, 0 (off) or 256 .. 65536; gamma.
+ *   tiles: ex[i] = floor(i * w / TX) for i = 0 .. TX, ey[j] likewise from h and TY.  Tile (i, j), number t = j * TX + i, is
+ *     columns [ex[i], ex[i+1]) and rows [ey[j], ey[j+1]) of EVERY plane: planes that share a maximum share one table per
+ *     tile, as they share one table equalised -- which keeps the hue of the three palette renders and the ratio between
+ *     the slices of a depth or frames render.  A channel plane is an image of its own (planes = 1).
+ *   bins: bins_t[k] = the number of lit counters of tile t with cb_equalize_key(count) = k; lit_t their sum, keys_t the
+ *     number of non-empty bins; bins_all the sum over the tiles and lit its sum.
+ *   clip: with clip_q = 0, clipped_t = bins_t.  Else L_t = max(1, floor(clip_q * lit_t / (256 * keys_t))) (the product is
+ *     below 2^57), E_t = the sum over k of max(0, bins_t[k] - L_t), and for the m-th lit key k in ascending order (m from 0)
+ *       clipped_t[k] = min(bins_t[k], L_t) + floor(E_t / keys_t) + (m < E_t mod keys_t ? 1 : 0).
+ *     Empty bins stay empty, so the sum of clipped_t is lit_t, and every lit key keeps at least 1, so the table stays
+ *     strictly increasing in rank over the lit keys.  One redistribution pass, no iteration.  The excess goes to the tile's
+ *     LIT keys only -- the project's choice, not the textbook's: the 56 320 keys are almost all empty in any tile.
+ *   tables: table_t = cb_equalize_table(clipped_t, gamma).  A tile with lit_t = 0 takes cb_equalize_table(bins_all, gamma),
+ *     the global curve, unclipped: an empty tile beside a lit one then pulls its neighbours towards the global image and
+ *     not towards black (the corners of the default canvas lie outside radius 2).
+ *   pixel (x, y) of any plane, counter c, k = key(c).  Tile centres are kept doubled, so they are integers:
+ *     CX[i] = ex[i] + ex[i+1], px = 2x + 1; CY[j] and py likewise.  The columns: if TX = 1 or px <= CX[0],
+ *     (i0, i1, ax, dx) = (0, 0, 0, 1); if px >= CX[TX-1], (TX-1, TX-1, 0, 1); otherwise i0 is the largest i with
+ *     CX[i] <= px, i1 = i0 + 1, ax = px - CX[i0], dx = CX[i1] - CX[i0].  The rows likewise.  With v_ab = table_(ia, jb)[k]:
+ *       num   = (dy - ay) * ((dx - ax) * v00 + ax * v10) + ay * ((dx - ax) * v01 + ax * v11)
+ *       pixel = floor((num + floor(dx * dy / 2)) / (dx * dy))
+ *     dx * dy <= w * h <= 2^40, so everything stays below 2^57.  A counter of 0 gives 0: every table has table[0] = 0.
+ * Consequences: TX = TY = 1 with the clip off is cb_set_grayscale_pixels_equalized bit for bit; at a fixed position the
+ * value is monotone in the count; where all lit tiles have equal bins the image is each tile's own equalised image; a pixel
+ * with px = CX[i] and py = CY[j] takes table (i, j) alone; the image of hist << s is the image of hist for every s that
+ * overflows no counter, so the density filter's 8 fraction bits change nothing by themselves.
+ * Reported: lit; lit_tiles, the tiles with lit_t > 0; moved, the sum of E_t over the tiles. */
+#define CB_LOCAL_EQUALIZE_MAX_TILES 16
+
+/* 1 if the grid and the clip are ones the definition admits on a canvas of w x h with `planes` planes, else 0. */
+int cb_local_equalize_ok(int w, int h, int planes, int tx, int ty, uint32_t clip_q);
+/* bins_t of a host array: tx * ty rows of CB_EQUALIZE_KEYS values, tile t = j * tx + i at bins_out + t * CB_EQUALIZE_KEYS;
+ * *lit_out is lit, *max_out the largest counter.  0, or hipErrorInvalidValue with nothing written: a NULL pointer or
+ * what cb_local_equalize_ok refuses. */
+int cb_local_equalize_bins(const cb_pixel *hist, int w, int h, int planes, int tx, int ty, uint64_t *bins_out,
+                           uint64_t *lit_out, uint64_t *max_out);
+/* clipped_t (CB_EQUALIZE_KEYS values) and E_t of one tile's bins; clipped_out may be bins itself.  0, or
+ * hipErrorInvalidValue with nothing written: a NULL pointer, a clip_q that is neither 0 nor in 256 .. 65536. */
+int cb_local_equalize_clip(const uint64_t *bins, uint32_t clip_q, uint64_t *clipped_out, uint64_t *moved_out);
+/* cb_set_grayscale_pixels, locally equalised: gray_out receives planes*h*w host-endian uint16; *max_out and *scale_out
+ * (may be NULL) are what cb_set_grayscale_pixels reports over the whole array; *lit_out, *lit_tiles_out and *moved_out
+ * (may be NULL) are the three reported numbers.  0, or hipErrorInvalidValue with nothing written: a NULL hist or gray_out
+ * or what cb_local_equalize_ok refuses -- an empty canvas, planes < 1, a grid outside 1 .. 16 or larger than the canvas,
+ * a clip_q that is neither 0 nor in 256 .. 65536. */
+int cb_set_grayscale_pixels_local_equalized(const cb_pixel *hist, int w, int h, int planes, int tx, int ty, uint32_t clip_q,
+                                            double gamma, uint16_t *gray_out, uint64_t *max_out, double *scale_out,
+                                            uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out);
+/* cb_local_equalize_bins on a DEVICE array (8-byte aligned, planes*h*w <= 2^40): the largest counter first, then one sweep
+ * of the tiles (equalize_local.hip) into bins_out_host, tx * ty * CB_EQUALIZE_KEYS values on the HOST.  The numbers equal
+ * cb_local_equalize_bins'.  hipErrorInvalidValue with nothing written and nothing read: what the host function refuses, an
+ * address that is not 8-byte aligned, more than 2^40 counters, and a canvas whose widest tile row times `planes` is 2^32
+ * or more (a block's 32-bit bins could not hold the counters it reads).  Synchronises `stream`. */
+int cb_local_equalize_bins_device(const cb_pixel *d_hist, int w, int h, int planes, int tx, int ty, uint64_t *bins_out_host,
+                                  uint64_t *lit_out, uint64_t *max_out, void *stream);
+/* cb_tone_map_device, locally equalised: the bytes of cb_set_grayscale_pixels_local_equalized + cb_save_image into
+ * d_gray_be (planes*h*w big-endian u16), and its numbers; every output number may be NULL.  The bins come from one sweep
+ * sized by the largest counter's key, the host clips, makes the tables and uploads them, a second kernel blends four
+ * table values per pixel.  Refuses what cb_local_equalize_bins_device refuses and a d_gray_be that is not 4-byte aligned
+ * (two pixels are stored at once), with nothing written.  Synchronises `stream`. */
+int cb_tone_map_device_local_equalized(const cb_pixel *d_hist, int w, int h, int planes, int tx, int ty, uint32_t clip_q,
+                                       double gamma, uint16_t *d_gray_be, uint64_t *max_out, double *scale_out,
+                                       uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out, void *stream);
+/* A renderer's local equalisation: an output setting like cb_renderer_set_equalize, tx = 0 (the default) = off.  With it
+ * on, every image call of the white clip's list makes the locally equalised image over the array it takes the maximum of
+ * otherwise -- the filtered one where a density filter is set --, the planes of that image pooled; tone_mode is validated
+ * and otherwise not read; *max_out and *scale_out stay what the unflagged call returns.  No launch, histogram, state file
+ * or generator state knows of it.  cb_renderer_color_image on such a renderer returns hipErrorInvalidValue.
+ * hipErrorInvalidValue, the renderer left as it was: a grid or clip cb_local_equalize_ok refuses on the renderer's canvas
+ * (tx = 0 apart), a renderer that is equalised or has a white clip -- and cb_renderer_set_equalize(on) or a clip above 0
+ * on a locally equalised one. */
+int cb_renderer_set_local_equalize(cb_renderer *r, int tx, int ty, uint32_t clip_q);
+int cb_renderer_local_equalize(const cb_renderer *r, int *tx_out, int *ty_out, uint32_t *clip_q_out);
+/* lit, lit_tiles and moved of the last image call made locally equalised; zeros before one, and after every
+ * cb_renderer_set_local_equalize. */
+int cb_renderer_last_local_equalize(const cb_renderer *r, uint64_t *lit_out, uint64_t *lit_tiles_out, uint64_t *moved_out);
+
 /* ---- Colour image: three planes composed into one 16-bit RGB image ------------------------------- *
  *
  * The reference's colour recipe (generate_hires_color_image.sh) renders three windows, stretches each PGM with

@@ -5,6 +5,10 @@
 usage: output_rate.py run PARENT_PKGROOT OUT.txt WHERE [SIZE...]   the whole measurement: one child process per case
        output_rate.py child PKGROOT {current|parent} SIZE          one case, JSON lines on stdout
        output_rate.py --list [SIZE...]                             the rows and the children `run` would start
+       output_rate.py local PKGROOT OUT.txt WHERE SIZE...          --local-equalize against --equalize
+       output_rate.py local-child PKGROOT SIZE                     one size of it, JSON lines on stdout
+       output_rate.py local-trace TRACE.csv                        kernel medians of a local-child run under a kernel trace
+       output_rate.py local-clip PKGROOT                           what --local-equalize's clip does to one render
        output_rate.py picture PKGROOT [SECONDS [PASSES]]           what the density filter does to a short render
        output_rate.py readme PKGROOT                               README.md's two --bounded renders, clipped and not
 
@@ -21,6 +25,24 @@ host table, an upload and the lookup kernel: the lookup kernels alone are not se
 
 The record closes with one line per row and size: the branch's median over its six repetitions against the parent's
 largest repetition plus the parent's own spread (largest minus smallest) that day; a row within that is `unchanged`.
+
+local: the same render per SIZE, one child process per size under its own time limit, the first that fails ends the run.
+In ONE process the two global calls -- equalize_bins_device, tone_map_device_equalized -- and, for 1 x 1, 8 x 8 and 16 x 16
+tiles at the binary's default clip, local_equalize_bins_device and tone_map_device_local_equalized are each called once to
+warm them and then three times; the record (profiles/local_equalize_rate.txt) gives the median and the range of each, and
+closes with the local calls as ratios to the global ones.  The bins entry point expands every tile's bins to all 56 320
+keys on the host, which the image call does not; the kernels alone are not separated by a host clock.
+
+local-trace: TRACE.csv is the kernel trace a profiler wrote of one `local-child` run (rocprofv3 --kernel-trace
+--output-format csv -- python3 tools/output_rate.py local-child PKGROOT SIZE; profiles/local_equalize_SIZE_kernel_trace.csv
+are two).  Prints the median and the range, in microseconds, of every dispatch of the output stage's kernels, the two local
+kernels grid by grid: a child dispatches local_bins_kernel nine times and local_map_kernel five times per grid before the
+renderer's image calls, in LOCAL_GRIDS' order.
+
+local-clip: a 2048 x 2048 render (1000 / 20 iterations, 64 passes), its image unflagged, equalised and locally equalised in
+8 x 8 tiles at clips 2, 4, 8 and off (device bytes and numbers checked against the host function's): per tile with 1000 lit
+pixels or more, the span between the 5th and the 95th percentile of the lit pixels' output values and the number of
+distinct values (profiles/local_equalize_clip.txt).
 
 picture: a 4096 x 4096 default render (100 / 20 iterations) of SECONDS seconds (default 3), its image without and with
 --density-filter 4, 4:0.5:4 and 8, against a run of 64 times as many passes on other generators: the RMS difference of the
@@ -213,6 +235,148 @@ def run(parent_root, out_path, where, sizes, command=child_command, limit=LIMIT)
     return 0
 
 
+LOCAL_GRIDS, LOCAL_CLIP_Q = (1, 8, 16), 1024
+
+
+def local_child(pkgroot, size):
+    cb = load(pkgroot)
+    import torch
+
+    def row(what, t, **kw):
+        print(json.dumps(dict(kw, what=what, size=size, **t)), flush=True)
+
+    n = size * size
+    with rendered(cb, size) as r:
+        r.render_passes(passes(size))
+        r.finish()
+        ptr = r.device_histogram
+        gray = torch.zeros(n, dtype=torch.int16, device="cuda:0")
+        bins, lit, mx = cb.equalize_bins_device(ptr, n)
+        row("equalize_bins_device (one sweep)", timed(lambda: cb.equalize_bins_device(ptr, n)), lit=lit, max=mx,
+            keys=int((bins > 0).sum()), keys_per_tile_array=cb.equalize_key(mx) + 1)
+        row("tone_map_device_equalized (whole call)",
+            timed(lambda: cb.tone_map_device_equalized(ptr, size, size, GAMMA, gray.data_ptr())))
+        for tiles in LOCAL_GRIDS:
+            row("local_equalize_bins_device %dx%d (maximum, sweep, 56320 keys a tile to the caller)" % (tiles, tiles),
+                timed(lambda: cb.local_equalize_bins_device(ptr, size, size, 1, tiles, tiles)), tiles=tiles)
+            found = cb.tone_map_device_local_equalized(ptr, size, size, 1, tiles, tiles, LOCAL_CLIP_Q, GAMMA, gray.data_ptr())
+            row("tone_map_device_local_equalized %dx%d clip %d/256 (whole call)" % (tiles, tiles, LOCAL_CLIP_Q),
+                timed(lambda: cb.tone_map_device_local_equalized(ptr, size, size, 1, tiles, tiles, LOCAL_CLIP_Q, GAMMA,
+                                                                 gray.data_ptr())),
+                tiles=tiles, lit=found[2], lit_tiles=found[3], moved=found[4])
+        r.set_equalize()
+        row("grayscale_image equalised", timed(lambda: r.grayscale_image(GAMMA)))
+        r.set_equalize(False)
+        for tiles in LOCAL_GRIDS:
+            r.set_local_equalize(tiles)
+            row("grayscale_image locally equalised %dx%d" % (tiles, tiles), timed(lambda: r.grayscale_image(GAMMA)), tiles=tiles)
+        r.set_local_equalize(0)
+
+
+def local_ratios(lines):
+    """The local calls as ratios of medians to the global ones, one line per size and grid."""
+    by = {}
+    for line in lines:
+        rec = json.loads(line)
+        by[(rec["size"], rec["what"].split(" ")[0], rec.get("tiles", 0))] = rec
+    out = []
+    for (size, what, tiles), rec in by.items():
+        if what == "tone_map_device_local_equalized":
+            sweep, call = by[(size, "equalize_bins_device", 0)], by[(size, "tone_map_device_equalized", 0)]
+            out.append("# %5d  %2dx%-2d tiles: bins call %.6g s = %.2f of the global one; whole call %.6g s (%.6g .. %.6g) = %.2f of "
+                       "the global one\n"
+                       % (size, tiles, tiles, by[(size, "local_equalize_bins_device", tiles)]["median_s"],
+                          by[(size, "local_equalize_bins_device", tiles)]["median_s"] / sweep["median_s"], rec["median_s"],
+                          rec["min_s"], rec["max_s"], rec["median_s"] / call["median_s"]))
+    return out
+
+
+def local(pkgroot, out_path, where, sizes, limit=LIMIT):
+    lines = []
+    with open(out_path, "w") as out:
+        out.write("# tools/output_rate.py local on %s, sizes %s (DESIGN.md 4.28): the global and the tile-wise calls in one\n"
+                  "# process per size; three repetitions per figure after one call to warm it, seconds by the host clock around\n"
+                  "# calls that end in a device synchronise\n" % (where, " and ".join(str(s) for s in sizes)))
+        for size in sizes:
+            command = [sys.executable, os.path.abspath(__file__), "local-child", pkgroot, str(size)]
+            try:
+                done = subprocess.run(command, stdout=subprocess.PIPE, text=True, timeout=limit)
+                text, status = done.stdout, done.returncode
+            except subprocess.TimeoutExpired as e:
+                text, status = (e.stdout.decode() if isinstance(e.stdout, bytes) else e.stdout or ""), 124
+            out.write(text)
+            out.flush()
+            print(text, end="", flush=True)
+            if status != 0:  # nothing more is started on a device that a case has failed on
+                out.write("# size %d ended with status %d: stopped here\n" % (size, status))
+                return status if status > 0 else 128 - status
+            lines += text.splitlines()
+        out.write("# medians as ratios to the global calls of the same process\n")
+        out.writelines(local_ratios(lines))
+    return 0
+
+
+def local_trace(path):
+    import csv
+
+    names = ("local_bins_kernel", "local_map_kernel", "equalize_bins_kernel", "equalize_map_kernel", "hist_max_kernel")
+    took = {name: [] for name in names}
+    with open(path) as f:
+        for rec in csv.DictReader(f):
+            for name in names:
+                if name + "(" in rec["Kernel_Name"]:
+                    took[name].append((int(rec["End_Timestamp"]) - int(rec["Start_Timestamp"])) / 1e3)
+
+    def row(what, us):
+        print(json.dumps({"what": what, "dispatches": len(us), "median_us": statistics.median(us), "min_us": min(us),
+                          "max_us": max(us)}))
+
+    for name in names[2:]:
+        row(name, took[name])
+    for at, tiles in enumerate(LOCAL_GRIDS):  # the device calls come before the renderer's: 9 and 5 dispatches a grid
+        row("local_bins_kernel %dx%d" % (tiles, tiles), took["local_bins_kernel"][9 * at:9 * at + 9])
+        row("local_map_kernel %dx%d" % (tiles, tiles), took["local_map_kernel"][5 * at:5 * at + 5])
+
+
+def local_clip(pkgroot, size=2048, tiles=8):
+    cb = load(pkgroot)
+    import numpy as np
+
+    with rendered(cb, size) as r:
+        r.render_passes(64)
+        r.finish()
+        hist = r.read_histogram()
+        images, found = {"unflagged": r.grayscale_image(GAMMA)[0].astype(np.uint16)}, {}
+        r.set_equalize()
+        images["--equalize"] = r.grayscale_image(GAMMA)[0].astype(np.uint16)
+        r.set_equalize(False)
+        for clip in (2, 4, 8, 0):
+            name = "--local-equalize %d:%d" % (tiles, clip)
+            r.set_local_equalize(tiles, tiles, 256 * clip)
+            images[name] = r.grayscale_image(GAMMA)[0].astype(np.uint16)
+            found[name] = r.last_local_equalize()
+            host = cb.set_grayscale_pixels_local_equalized(hist, tiles, tiles, 256 * clip, GAMMA)
+            assert np.array_equal(host[0], images[name]) and tuple(host[3:]) == found[name]
+        r.set_local_equalize(0)
+    lit, step = hist > 0, size // tiles
+    print(json.dumps({"what": "local-clip: the render", "size": size, "tiles": [tiles, tiles], "gamma": GAMMA,
+                      "max": int(hist.max()), "lit": int(lit.sum())}))
+    for name, im in images.items():
+        levels, spans = [], []
+        for j in range(tiles):
+            for i in range(tiles):
+                where = (slice(j * step, (j + 1) * step), slice(i * step, (i + 1) * step))
+                if lit[where].sum() >= 1000:
+                    values = im[where][lit[where]]
+                    levels.append(int(np.unique(values).size))
+                    spans.append(float(np.subtract(*np.percentile(values, [95, 5]))))
+        numbers = found.get(name)
+        print(json.dumps({"what": "local-clip", "image": name, "tiles_counted": len(spans),
+                          "span_5_to_95_percent_median": float(np.median(spans)), "span_5_to_95_percent_min": min(spans),
+                          "distinct_values_median": float(np.median(levels)), "distinct_values_min": min(levels),
+                          "lit_tiles": numbers[1] if numbers else None, "moved": numbers[2] if numbers else None}), flush=True)
+
+
 def say(**kw):
     print(json.dumps(dict(kw, which="current")), flush=True)
 
@@ -307,6 +471,14 @@ def main(argv):
             print(json.dumps({"what": row}))
         for which, root, size in children("PARENT_PKGROOT", sizes):
             print(json.dumps({"child": which, "size": size, "passes": passes(size), "limit_s": LIMIT}))
+    elif what == "local" and len(rest) >= 4:
+        return local(os.path.abspath(rest[0]), rest[1], rest[2], [int(s) for s in rest[3:]])
+    elif what == "local-child" and len(rest) == 2:
+        local_child(os.path.abspath(rest[0]), int(rest[1]))
+    elif what == "local-trace" and len(rest) == 1:
+        local_trace(rest[0])
+    elif what == "local-clip" and len(rest) == 1:
+        local_clip(os.path.abspath(rest[0]))
     elif what == "picture" and 1 <= len(rest) <= 3:
         picture(os.path.abspath(rest[0]), float(rest[1]) if len(rest) > 1 else 3.0, int(rest[2]) if len(rest) > 2 else 0)
     elif what == "readme" and len(rest) == 1:
