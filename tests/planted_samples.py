@@ -55,6 +55,20 @@ tests/plot_reference.py and .c:
 tests/test_planted_plot_host.py shows these decisive on the restatement alone; tests/test_gpu_planted_plot.py and
 tests/test_gpu_planted_queue.py feed them to the kernels.
 
+The same finders take the Phoenix step, step = dict(phoenix=(p_re, p_im)), on the Phoenix render's restatement
+(tests/phoenix_reference.py and .c: `lib` is then phoenix_reference.load's library): orbit_of, end_of, with_end and
+projected_orbit iterate the pair (z, y) from y_0 = 0 with phoenix.step.  Beside them
+
+    ends_found(lib, c, **step)    the ends of ENDS that the rays have under a step, with their samples
+    phoenix_cycles(lib, p, c)     samples whose orbit returns to the saved z bit for bit at one chunk and to the saved state
+                                  (z, y) at a later one, or never: where the z-only rule and the state rule differ
+    PHOENIX_CIRCLE, PHOENIX_REPLAY, PHOENIX_ZEROS   hand-computed orbits: on |z|^2 == 4, for the replay's y_0, with negative zeros
+
+The candidates of PHOENIX_CYCLES beyond the first four are phoenix_cycle_search's: the real axis, where for a p that is a
+power of two every operation of the step is a plain rounded product or sum (numpy's doubles do it, 2^16 samples at a time);
+like every other plant they count only as far as the restatement's step confirms them.  tests/test_planted_phoenix_host.py shows
+these decisive; tests/test_gpu_planted_phoenix.py feeds them to kernels 24 and 25.
+
 The third part is the cell grid of the focused and aimed renders (draw_cells.h; tests/cells_reference.h): six-draw samples
 of a cell list, with a reference of the mapping in integers and Fractions that shares no arithmetic with kernels or
 restatements, and four-draw samples on the edges of the probe's mask:
@@ -524,9 +538,28 @@ def pixel_edge_cases(w, h, count=1233, max_iter=1234, min_iter=20, samples=24):
 # z_0, else c is fixed and the sample is z_0 (a Julia render).  An orbit's `end` is the step whose point escapes (the
 # scheduler's l.end; the reference's escape index k is end - 1).
 
+import phoenix_reference as phoenix  # noqa: E402
 import plot_reference as plot  # noqa: E402
 
 ROUND, MANDELBROT = 12, {}                         # draw_rounds.h kRound; the reference's own step
+
+
+def header_value(name):
+    """The integer include/cudabrot_amd.h defines under the name."""
+    import re
+
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cudabrot_amd.h")) as f:
+        m = re.search(r"^#define %s\s+(\S+)" % re.escape(name), f.read(), re.M)
+    assert m, name
+    return int(m.group(1), 0)
+
+
+# every formula code and every Multibrot degree the header defines, by the name of the command line or "power_D"
+FORMULA_CODES = range(header_value("CB_FORMULA_TRICORN"), header_value("CB_FORMULA_MAX") + 1)
+DEGREES = range(header_value("CB_POWER_MIN"), header_value("CB_POWER_MAX") + 1)
+assert sorted(plot.NAMES.values()) == list(FORMULA_CODES)
+FORMULA_STEPS = {name: dict(formula=code) for name, code in sorted(plot.NAMES.items(), key=lambda kv: kv[1])}
+POWER_STEPS = {"power_%d" % d: dict(degree=d) for d in DEGREES}
 
 # The filler: a sample every family decides on the spot.  From z_0 = 2 + 2i the first step of every step there is, under any
 # c in [-2, 2]^2, lands at |z_1|^2 >= 36: `end` is 1, so it is too fast under any min_iter >= 1 and, in a bounded render,
@@ -540,9 +573,13 @@ def orbit_of(lib, sample, n, c=None, **step):
     (points [(r, i)], end or None where none of the n escapes)."""
     cr, ci = sample if c is None else c
     r, i = float(sample[0]), float(sample[1])
+    p, yr, yi = step.get("phoenix"), 0.0, 0.0
     points = []
     for k in range(1, n + 1):
-        r, i, m = plot.step(lib, cr, ci, r, i, **step)
+        if p is None:
+            r, i, m = plot.step(lib, cr, ci, r, i, **step)
+        else:                                      # the state is the pair (z, y), y_0 = 0; y is never a point
+            r, i, yr, yi, m = phoenix.step(lib, cr, ci, p[0], p[1], r, i, yr, yi)
         points.append((r, i))
         if m > 4.0:
             return points, k
@@ -565,6 +602,54 @@ FIXED_RAYS = [lambda e: (0.5 + e * GRID, 0.0), lambda e: (0.5 + e * GRID, 2.0 **
 RAY_LAST = 3 << 50                                 # every ray ends at or before real part 2 (e GRID = 1.5)
 
 
+def ray_from(start, direction):
+    """The ray start + e GRID direction: a start on the grid and a direction of integers keep every point on it."""
+    return lambda e: (start[0] + e * GRID * direction[0], start[1] + e * GRID * direction[1])
+
+
+# The Phoenix step (step = dict(phoenix=(p_re, p_im)), on phoenix_reference.load's library).  A sampled c next to 0 is z_0
+# too and y_0 = 0, so the orbit stays next to 0 for any p with |sqrt(p)| < 1 and leaves it slowly for the others: rays from
+# c = 0 up the imaginary axis and along the real one have every band for p = (-1/2, 0) and (0.3, -0.4), and bands up to 61
+# at the bounds p = +-(2, 2).  PHOENIX_C is tests/test_gpu_phoenix.py's fixed c of p = (-1/2, 0); the rays of the Julia
+# renders start at z_0 = 1/2, which escapes within a few steps there, so these start at a z_0 inside that set (it does
+# not escape in 1000 steps).  They leave the sample plane before they end; what is returned is on the grid or refused.
+PHOENIX_SAMPLED_RAYS = [ray_from((0.0, 0.0), (0, 1)), ray_from((0.0, 0.0), (1, 0)), ray_from((0.0, 2.0 ** -12), (0, 1))]
+PHOENIX_C = (0.56667, 0.0)
+PHOENIX_FIXED_RAYS = [ray_from((-0.5625, 0.84375), (0, 1)), ray_from((-0.5625, 0.84375), (1, 0))]
+
+
+# The formula steps differ from the reference's step, and from one another, by signs and absolute values of z_re, z_im and
+# t = z_re^2 - z_im^2 (include/cudabrot_amd.h, "Formula step"): on the rays above, where all three stay positive, the five
+# are two maps.  These rays start left of the imaginary axis and cross |z_im| > |z_re|; with_end takes a formula's plant
+# from them and keeps it only where steps_told_apart says that the orbit up to `end` is another one under every other
+# step of EVERY_STEP.  One step cannot separate all seven: z_1 has one of two real parts (t or |t|) and one of two
+# imaginary parts (+-|2 z_re z_im| + c_im), so a plant of end 1 tells four classes apart, the most there are.
+# Another orbit under every other step still leaves an absolute value unproven where no other step differs by it alone:
+# buffalo's |z_im| matters only where z_im < 0, and from a c_im > 0 its z_im never is.  So a plant of end > 1 must also
+# have, among the points z_0 .. z_{end-1} that are stepped from, one with t < 0, one with z_re < 0 and one with z_im < 0 (the
+# other coordinate not 0): signs_seen.  The last two rays, just below the real axis and leftwards, are buffalo's.
+FORMULA_RAYS = [ray_from((-1.0, 2.0 ** -12), (0, 1)), ray_from((-1.0, 2.0 ** -12), (1, -1)),
+                ray_from((-1.0, -2.0 ** -12), (-1, 0)), ray_from((-1.0, -2.0 ** -20), (-1, 0))]
+EVERY_STEP = [MANDELBROT, dict(ship=True)] + list(FORMULA_STEPS.values())
+
+
+def steps_told_apart(lib, sample, n):
+    """How many different orbits z_1 .. z_n (each cut at its escape) the sampled c has under the steps of EVERY_STEP."""
+    return len({tuple(orbit_of(lib, sample, n, **st)[0]) for st in EVERY_STEP})
+
+
+def signs_seen(lib, sample, end, **step):
+    """(t < 0, z_re < 0, z_im < 0) each at some point of z_0 .. z_{end-1} under the step, the other coordinate not 0."""
+    points = [sample] + orbit_of(lib, sample, end, **step)[0][:-1]
+    return (any(r * r < i * i for r, i in points), any(r < 0 and i != 0 for r, i in points),
+            any(i < 0 and r != 0 for r, i in points))
+
+
+def told_apart_at(end):
+    """What steps_told_apart must give for a formula's plant: every step another orbit, or the four classes of one step."""
+    return 4 if end == 1 else len(EVERY_STEP)
+
+
 def with_end(lib, end, c=None, ray=None, **step):
     """A grid sample whose orbit escapes exactly at step `end` (>= 1) under the restatement's step: the last point of the
     band `end` along a ray, next to the band end - 1; z_0 where c is fixed.  The rays are tried in turn (or the one given)
@@ -572,6 +657,11 @@ def with_end(lib, end, c=None, ray=None, **step):
     rays = (FIXED_RAYS if c is not None else SAMPLED_RAYS) if ray is None else [ray]
     if ray is None and c is None and (step.get("ship") or step.get("formula")):
         rays = [rays[1], rays[0], rays[2]]          # off the axis first: on it these steps are the reference's own
+    if ray is None and step.get("phoenix") is not None:
+        rays = (PHOENIX_FIXED_RAYS if c is not None else PHOENIX_SAMPLED_RAYS) + rays
+    decisive = ray is None and c is None and bool(step.get("formula"))
+    if decisive:
+        rays = FORMULA_RAYS + rays
     for point in rays:
         def lasts(e):
             got = end_of(lib, point(e), end, c, **step)
@@ -583,10 +673,29 @@ def with_end(lib, end, c=None, ray=None, **step):
         else:
             continue
         sample = point(lo)
+        if c is not None and step.get("phoenix") is not None and max(abs(sample[0]), abs(sample[1])) > 2.0:
+            continue                                # a Phoenix ray's last point, for end 1, is beyond the sample plane
         grid_index(sample[0]), grid_index(sample[1])
+        if decisive and steps_told_apart(lib, sample, end) != told_apart_at(end):
+            continue
+        if decisive and end > 1 and not all(signs_seen(lib, sample, end, **step)):
+            continue
         if end_of(lib, sample, end + 2, c, **step) == end and (c is not None or step or not rejected(*sample)):
             return sample
     raise ValueError("no ray has a sample with end %d under %r, c %r" % (end, step, c))
+
+
+def ends_found(lib, c=None, ends=None, **step):
+    """[(end, sample)] of the ends of the list (ENDS) that with_end finds under the step: where the rays have no band for an
+    end -- at the bounds of the Phoenix parameter the orbits leave too fast for the long ones -- it is left out, and the
+    caller says which ends it needs."""
+    found = []
+    for end in (ENDS if ends is None else ends):
+        try:
+            found.append((end, with_end(lib, end, c, **step)))
+        except ValueError:
+            pass
+    return found
 
 
 def slice_edges(lib, window, around=1 << 20):
@@ -633,6 +742,8 @@ REPEATING = [  # (step, fixed c or None, sample): candidates -- repeating() keep
     (MANDELBROT, (-1.0, 0.0), (0.0, 0.0)),
     (MANDELBROT, (-2.0, 0.0), (2.0, 0.0)), (MANDELBROT, (-2.0, 0.0), (0.0, 0.0)),
 ]
+REPEATING += [(st, None, (0.0, 0.0)) for st in list(FORMULA_STEPS.values()) + list(POWER_STEPS.values())
+              if (st, None, (0.0, 0.0)) not in REPEATING]     # z = c = 0 stays 0 under every step of the table
 
 
 def repeating(lib, step, c=None, candidates=None):
@@ -661,6 +772,99 @@ def repeating(lib, step, c=None, candidates=None):
     return found
 
 
+def saves_after(chunks):
+    """The scheduler's save rule (draw_rounds.h brent_save; tests/phoenix_reference.c saves_after): the chunks done have no
+    set bit below their top two -- after 1, 2, 3, 4, 6, 8, 12 ... chunks."""
+    top = chunks.bit_length() - 1
+    return top < 1 or (chunks & ((1 << (top - 1)) - 1)) == 0
+
+
+PHOENIX_CYCLES = [  # (p, fixed c or None, sample): candidates -- phoenix_cycles() keeps what the restatement confirms
+    ((0.25, 0.0), None, (-0.8125, 0.0)), ((0.25, 0.0), None, (-0.853515625, 0.0)),
+    ((-0.5, 0.0), None, (-1.900390625, 0.0)),
+    ((-0.5, 0.0), None, (-1.80267333984375, 0.0)),           # z at 180, the state only at 360: across the saves after 3 and 4 chunks
+    ((-0.5, 0.0), None, (-1.4501953125, 0.0)),               # z at 180, the state never below 1000 steps
+    ((-0.5, 0.0), (-0.8, 0.156), (-1.470703125, 0.078125)),
+]
+
+
+def phoenix_cycles(lib, p, c=None, candidates=None, cap=1000):
+    """Samples whose Phoenix orbit under (p, c) never escapes and comes back to a saved z bit for bit -> [(sample, found_z,
+    found_state)]: each candidate is stepped at most `cap` times with the restatement's step and compared as
+    phoenix_reference.c's one_sample does it, at every k that is a multiple of CHUNK with the point saved last, which is
+    then replaced where saves_after(k / CHUNK).  found_z: the first such k at which z alone equals the saved z; found_state:
+    the first at which the whole state (z, y) equals the saved state, None if there is none up to cap.  Kept where z is
+    found at all and no point up to there (up to found_state, where there is one) escapes."""
+    found = []
+    for pp, cc, sample in (PHOENIX_CYCLES if candidates is None else candidates):
+        if tuple(pp) != tuple(p) or cc != c:
+            continue
+        cr, ci = sample if c is None else c
+        state, saved, found_z, found_state = (float(sample[0]), float(sample[1]), 0.0, 0.0), None, None, None
+        for k in range(1, cap + 1):
+            *state, m = phoenix.step(lib, cr, ci, p[0], p[1], *state)
+            if m > 4.0:
+                found_z = None
+                break
+            if k % CHUNK:
+                continue
+            bits = [np.float64(v).tobytes() for v in state]
+            if saved is not None and bits[:2] == saved[:2]:
+                found_z = k if found_z is None else found_z
+                if bits == saved:
+                    found_state = k
+                    break
+            if saves_after(k // CHUNK):
+                saved = bits
+        if found_z is not None:
+            found.append((sample, found_z, found_state))
+    return found
+
+
+_CYCLE_SEARCH = {}
+
+
+def phoenix_cycle_search(p_re, bits=14, cap=1000):
+    """Where the candidates of PHOENIX_CYCLES come from, and where a replacement is found should the restatement stop
+    confirming one: every real sampled c on the 2^-bits grid in (-2, 2], under a real p that is a power of two.  There z_im
+    = y_im = 0, p y is exact and the step is c + RN(z z), then + p y, each one rounding: numpy's doubles do it, all
+    samples at once (2^(bits + 2) orbits of `cap` steps: 65 536 of 1000 by default).  -> {(found_z, found_state or None):
+    [c_re]} of the samples that never escape and whose z is found before their state, by phoenix_cycles' rule; cached.
+    The signs of zeros are not followed here: a candidate counts once phoenix_cycles confirms it on the restatement."""
+    key = (float(p_re), bits, cap)
+    if key in _CYCLE_SEARCH:
+        return _CYCLE_SEARCH[key]
+    assert math.frexp(abs(p_re))[0] == 0.5, "p y must be exact"
+    c = np.arange(-(2 << bits) + 1, (2 << bits) + 1) / float(1 << bits)
+    z, y = c.copy(), np.zeros_like(c)
+    alive = np.ones(len(c), dtype=bool)
+    saved_z = saved_y = None
+    found_z, found_state = np.zeros(len(c), dtype=np.int64), np.zeros(len(c), dtype=np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(1, cap + 1):
+            z, y = (c + z * z) + p_re * y, z
+            alive &= ~(z * z > 4.0)
+            if k % CHUNK:
+                continue
+            if saved_z is not None:
+                same_z = z == saved_z
+                found_z = np.where((found_z == 0) & same_z, k, found_z)
+                found_state = np.where((found_state == 0) & same_z & (y == saved_y), k, found_state)
+            if saves_after(k // CHUNK):
+                saved_z, saved_y = z.copy(), y.copy()
+    out = {}
+    for j in np.flatnonzero(alive & (found_z > 0) & (found_z != found_state)):
+        out.setdefault((int(found_z[j]), int(found_state[j]) or None), []).append(float(c[j]))
+    _CYCLE_SEARCH[key] = out
+    return out
+
+
+def cycle_discount(found, max_iter):
+    """The steps the early-out saves on a sample found at `found` (None: never): max_iter - found where the comparison is
+    made at all, at found < max_iter."""
+    return max(max_iter - found, 0) if found is not None else 0
+
+
 def c_plane_edges(box, w, h):
     """On a canvas with dyadic pixels under plot.C_PLANE, where (u, v) of every orbit point is the sample itself: for
     each axis the coordinate on min, on an inner pixel edge and on max, each with the grid point one step below it ->
@@ -673,11 +877,12 @@ def c_plane_edges(box, w, h):
     return out
 
 
-def projected_orbit(lib, projection, sample, n, c=None, **step):
-    """(u_k, v_k) of z_1 .. under plot.point, the escaping point included -> (u array, v array, end)."""
+def projected_orbit(lib, projection, sample, n, c=None, plot_lib=None, **step):
+    """(u_k, v_k) of z_1 .. under plot.point, the escaping point included -> (u array, v array, end).  Under a Phoenix step
+    `lib` is phoenix_reference's library, and plot_lib is plot_reference's, whose plot.point the render shares."""
     points, end = orbit_of(lib, sample, n, c, **step)
     cr, ci = sample if c is None else c
-    uv = np.array([plot.point(lib, projection, r, i, cr, ci) for r, i in points])
+    uv = np.array([plot.point(plot_lib or lib, projection, r, i, cr, ci) for r, i in points])
     return uv[:, 0], uv[:, 1], end
 
 
@@ -793,6 +998,46 @@ def accepted_beside(lib, c_re, lo=2, hi=400):
         if all(e is not None and lo <= e <= hi for e in ends) and not any(rejected(x, c_im) for x in c_re):
             return c_im, ends
     raise ValueError("no accepted sample with real part %r" % (c_re,))
+
+
+# ---- the cases both Phoenix suites use (tests/test_planted_phoenix_host.py, tests/test_gpu_planted_phoenix.py) ----------------
+#
+# On phoenix_reference.load's library.  A setting is (p, fixed c or None).
+
+PHOENIX_SETTINGS = {"sampled": ((-0.5, 0.0), None), "fixed": ((-0.5, 0.0), PHOENIX_C), "sampled_complex": ((0.3, -0.4), None)}
+PHOENIX_BOUNDS = {"p_max": ((2.0, 2.0), None), "p_min": ((-2.0, -2.0), None)}   # the bounds the ABI accepts: fewer ends exist
+BOUND_ENDS = (1, 12, 13)                           # what the rays must have there at the least
+
+# On the escape circle, p = (-1/2, 0).  Sampled c = 1: z_1 = 1 + 1 = 2 and |z_1|^2 is 4.0 exactly, z_2 = 4 + 1 - 1/2 = 4.5:
+# `end` is 2, and a test with >= would make it 1.  Fixed c = -2 from z_0 = 2: z_1 = 2, z_2 = 4 - 2 - 1 = 1, z_3 = 1 - 2 - 1 =
+# -2: |z_1|^2 = |z_3|^2 = 4.0 exactly, and no later point escapes.  -> (p, c, sample, the steps on the circle, end)
+PHOENIX_CIRCLE = {"sampled": ((-0.5, 0.0), None, (1.0, 0.0), (1,), 2), "fixed": ((-0.5, 0.0), (-2.0, 0.0), (2.0, 0.0), (1, 3), None)}
+
+# The replay plant, by hand: p = (-1/2, 1/4), c = z_0 = (3/4, 1/4), every operation exact.
+#   z_1 = (9/16 - 1/16 + 3/4, 2 * 3/4 * 1/4 + 1/4) = (5/4, 5/8), |z_1|^2 = 125/64 < 4, and y_1 = z_0;
+#   z_2 = (25/16 - 25/64 + 3/4, 2 * 5/4 * 5/8 + 1/4) + p y_1 = (123/64, 29/16) + (-3/8 - 1/16, -1/8 + 3/16) = (95/64, 15/8),
+#   |z_2|^2 > 4: `end` is 2, and both points are on WIDE_BOX.  ITERATE ends with y = z_1; a REPLAY that began with it in the
+#   place of 0 would make z_1 = (5/4, 5/8) + p z_1 = (5/4 - 5/8 - 5/32, 5/8 - 5/16 + 5/16) = (15/32, 5/8): another pixel.
+PHOENIX_REPLAY = dict(p=(-0.5, 0.25), sample=(0.75, 0.25), end=2, points=[(1.25, 0.625), (1.484375, 1.875)],
+                      wrong_first=(0.46875, 0.625))
+
+# Negative zeros: a p and a fixed c whose zero parts carry the sign, from z_0 = 0.  Under p = (-0, -0) the orbit of c = (-1, -0)
+# is 0 -> -1 -> 0 ... in value, and the sign of its zero imaginary part has period 4; under p = (-1/2, -0) it passes a -0
+# once and settles.  -> (p, c, sample)
+PHOENIX_ZEROS = {"p_half": ((-0.5, -0.0), (-1.0, -0.0), (0.0, 0.0)), "p_zero": ((-0.0, -0.0), (-1.0, -0.0), (0.0, 0.0))}
+ZEROS_MAX_ITERS = (120, 121, 181, 300)
+
+
+def cycle_max_iters(found_z, found_state):
+    """The max_iter values at which a cycle plant is run: either side of the step at which z alone is found, either side
+    of the one at which the state is, and a chunk later (where the state is never found: a chunk later and 1000)."""
+    late = (found_state, found_state + 1, found_state + CHUNK) if found_state is not None else (found_z + CHUNK, 1000)
+    return (found_z, found_z + 1) + late
+
+
+def last_save_before(k):
+    """The step of the last save made before the comparison at step k (a multiple of CHUNK)."""
+    return max(n * CHUNK for n in range(1, k // CHUNK) if saves_after(n))
 
 
 # ---- six planted outputs: a sample of the cell-list source (draw_cells.h, next_sample<true>; tests/cells_reference.h) ---------

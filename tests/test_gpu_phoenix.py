@@ -23,6 +23,7 @@ import phoenix_reference as phoenix
 import plot_harness
 import plot_reference as plot
 from conftest import read_state_file
+from phoenix_harness import phoenix_launches, restated, shape_of, three_ways  # noqa: F401
 from plot_harness import DEPTH_SHAPE, INVALID, SAME, SQUARE, exe, omp_threads, planar_states, ref  # noqa: F401
 from plot_harness import gpu_run as run
 
@@ -41,56 +42,6 @@ CASES = {
 @pytest.fixture(scope="module")
 def pref(tmp_path_factory):
     return phoenix.load(tmp_path_factory.mktemp("phoenix_ref"))
-
-
-def shape_of(kw):
-    s = dict(w=W, h=H, box=SQUARE, max_iter=MAX, min_iter=MIN, threads=THREADS, launches=LAUNCHES, c=None,
-             projection=plot.IDENTITY)
-    s.update(kw)
-    return s
-
-
-def phoenix_launches(cb, variant, **kw):
-    """`launches` on fresh generators through cb_draw_buddhabrot_phoenix -> (hist [h, w], counters, kernel, states)."""
-    s = shape_of(kw)
-    bufs = plot_harness.Launches(cb, cb.FractalDimensions.make(s["w"], s["h"], *s["box"]), s["threads"])
-    return bufs.launches(cb.draw_buddhabrot_phoenix, s["launches"], variant,
-                         iterations=cb.IterationControl(s["max_iter"], s["min_iter"]), projection=s["projection"],
-                         julia_c=s["c"], phoenix_p=s["p"]).read()
-
-
-def restated(pref, oracle, **kw):
-    """The restatement of the same launches -> (hist, counters, discounts and cycles, generator states after)."""
-    s = shape_of(kw)
-    st = oracle.init_states(1337, 0, s["threads"])
-    extra = {}
-    hist, cnt = phoenix.draw(pref, s["w"], s["h"], s["max_iter"], s["min_iter"], s["threads"], list(s["launches"]),
-                             p=s["p"], projection=s["projection"], c=s["c"], box=s["box"], omp_threads=omp_threads(),
-                             states=st, extra=extra)
-    assert cnt["samples"] == s["threads"] * sum(s["launches"]) and int(hist.sum()) == cnt["increments"]
-    assert cnt["rejected"] == 0
-    return hist, cnt, extra, planar_states(st)
-
-
-def three_ways(cb, pref, oracle, **kw):
-    """Product == lock-step == restatement -> (restatement's hist, counters, extra, the product's counters)."""
-    want, wc, extra, states = restated(pref, oracle, **kw)
-    print("restatement", wc, extra)
-    got = {}
-    for base, kernel in ((cb.CB_KERNEL_DEFAULT, PRODUCT), (cb.CB_KERNEL_SIMPLE, LOCKSTEP)):
-        hist, cnt, launched, after = phoenix_launches(cb, base, **kw)
-        print(kernel, cnt)
-        assert launched == kernel
-        assert cnt["status"] == 0
-        assert {k: cnt[k] for k in SAME} == wc, (kernel, cnt, wc)
-        assert hist.shape == want.shape and np.array_equal(hist, want), kernel
-        assert np.array_equal(after, states), kernel
-        assert cb.lib.cb_debug_interior_map_level() == 0  # no map, whatever p is
-        got[kernel] = cnt
-    assert got[LOCKSTEP]["skipped_steps"] == 0
-    # no map and no table: the discount of the exact cycles found under the state rule is all skipped_steps contains
-    assert got[PRODUCT]["skipped_steps"] == extra["skipped_state"], (got[PRODUCT], extra)
-    return want, wc, extra, got[PRODUCT]
 
 
 # ---- 1 - 3. three ways, on inputs that reach the paths, with the whole state compared ----------------------------------

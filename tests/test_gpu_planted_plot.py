@@ -47,13 +47,17 @@ def three(cb, ref, oracle, kernels, points, max_iter, min_iter, launches=(1,), *
 # ---- the round scheduler ------------------------------------------------------------------------------------------------------
 
 
+MORE_STEPS = {**{name: (POWER, step, None) for name, step in P.POWER_STEPS.items()},   # degrees 3 .. 8: power_step_n<D>
+              **{name: (FORMULA, step, None) for name, step in P.FORMULA_STEPS.items()}}  # the five formula_step<F>
+
+
 @pytest.mark.parametrize("end", P.ENDS)
-@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("family", list(FAMILIES) + list(MORE_STEPS))
 def test_an_escape_at_a_round_or_chunk_edge_either_side_of_the_window(cb, ref, oracle, family, end):
     """`end` = 1, 12, 13, 60, 61, 120, 121 against kRound = 12 and kChunk = 60, with k = end - 1 the last k accepted
     (max_iter = end), never escaping (max_iter = end - 1), accepted (min_iter = end - 1) and too fast (min_iter = end): alone
     in lane 0, alone in lane 63, in all 64 lanes."""
-    kernels, step, c = FAMILIES[family]
+    kernels, step, c = {**FAMILIES, **MORE_STEPS}[family]
     sample = P.with_end(ref, end, c, **step)
     for max_iter, min_iter, fate in P.windows_of(end):
         for shape in P.SHAPES:
@@ -64,13 +68,10 @@ def test_an_escape_at_a_round_or_chunk_edge_either_side_of_the_window(cb, ref, o
             assert r.product["skipped_steps"] == 0
 
 
-MORE_STEPS = {"power_3": (POWER, dict(degree=3), None), "tricorn": (FORMULA, dict(formula=1), None)}
-
-
 @pytest.mark.parametrize("family", list(FAMILIES) + list(MORE_STEPS))
 def test_planted_ends_followed_by_the_generators_own_samples(cb, ref, oracle, family):
     """Every end of the list, cycled through 512 subsequences (two whole blocks), then 50 samples of the generators' own;
-    here also under a Multibrot step and a formula."""
+    under every Multibrot degree and every formula too."""
     kernels, step, c = {**FAMILIES, **MORE_STEPS}[family]
     points = P.cycled([P.with_end(ref, end, c, **step) for end in P.ENDS], 512)
     r = three(cb, ref, oracle, kernels, points, 121, 12, (1, 50), c=c, **step)

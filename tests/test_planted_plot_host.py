@@ -3,6 +3,7 @@ the restatement alone, no GPU: what tests/test_gpu_planted_plot.py and tests/tes
 does sit on the decision it is named after.
 
   1. a planted `end` gives exactly the counters of planted_samples.model_counters, either side of max_iter and min_iter;
+     a formula's planted orbit is another orbit under every other formula and under the two steps without one;
   2. the filler is decided at once under every step and source of c;
   3. the members of a slice pair put their increments into different planes, or in and out of the window;
   4. the members of a pixel pair put theirs into different pixels, or in and out of the canvas;
@@ -25,7 +26,7 @@ import planted_samples as P
 import plot_reference as plot
 
 W, H = 64, 48
-STEPS = {"mandelbrot": {}, "ship": dict(ship=True), "power_3": dict(degree=3), "tricorn": dict(formula=1)}
+STEPS = {"mandelbrot": {}, "ship": dict(ship=True), **P.POWER_STEPS, **P.FORMULA_STEPS}  # degrees 3 .. 8, the five formulas
 
 
 @pytest.fixture(scope="module")
@@ -62,6 +63,49 @@ def test_a_planted_end_is_that_end_and_gives_the_counters_of_the_model(ref, step
                 assert model[fate] >= n and (fate != "recorded" or model["replay_steps"] >= n * end)
                 if min_iter >= 1:  # the fillers are idle: nothing but the planted lanes is replayed
                     assert model["replay_steps"] == (n * end if fate == "recorded" else 0)
+
+
+def orbit_by_hand(ref, sample, n, **step):
+    """z_1 .. z_n under plot.step, cut at the first escape: this file's own loop."""
+    r, i = sample
+    out = []
+    for _ in range(n):
+        r, i, m = plot.step(ref, sample[0], sample[1], r, i, **step)
+        out.append(np.array([r, i]).tobytes())
+        if m > 4.0:
+            break
+    return tuple(out)
+
+
+@pytest.mark.parametrize("name", list(P.FORMULA_STEPS))
+def test_a_formulas_planted_orbit_is_another_orbit_under_every_other_step(ref, name):
+    """What makes a formula's plant decisive: up to its `end` the orbit of the planted sample differs bit for bit under every
+    other formula, under the reference's step and under the Burning Ship's -- a kernel that took another branch of
+    formula_step would visit other points.  One step has four classes only (P.FORMULA_RAYS): at end 1 the plant's z_1 is
+    in another class than the steps with the other real part or the other sign of the cross term."""
+    step = P.FORMULA_STEPS[name]
+    others = [st for st in P.EVERY_STEP if st != step]
+    assert len(others) == 6
+    planted = {}
+    for end in P.ENDS:
+        sample = P.with_end(ref, end, **step)
+        own = orbit_by_hand(ref, sample, end, **step)
+        assert len(own) == end
+        rest = [orbit_by_hand(ref, sample, end, **st) for st in others]
+        if end > 1:
+            assert own not in rest and len(set(rest)) == 6, (name, end)
+            # every absolute value of the table decides somewhere: t < 0, z_re < 0 and z_im < 0 at points stepped from
+            before = [sample] + [tuple(np.frombuffer(z)) for z in own[:-1]]
+            assert any(r * r < i * i for r, i in before) and any(r < 0 and i != 0 for r, i in before), (name, end)
+            assert any(i < 0 and r != 0 for r, i in before), (name, end)
+        else:
+            assert len({own, *rest}) == 4 == P.told_apart_at(1), (name, end)
+        planted[end] = own
+    # and the planted orbits themselves are not those of another formula's plants
+    for other, st in P.FORMULA_STEPS.items():
+        if other != name:
+            for end in P.ENDS[1:]:
+                assert orbit_by_hand(ref, P.with_end(ref, end, **st), end, **st) != planted[end]
 
 
 def test_the_filler_is_decided_at_the_first_step_everywhere(ref):
