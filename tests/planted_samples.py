@@ -41,6 +41,17 @@ reference's arithmetic, not by a formula about it:
                                   there), and canvases with an orbit point on, or one ulp off, a canvas edge
     pixel_edge_samples            more samples, on the real axis, with such a point on a given canvas
 
+For the fused multi-channel render the same counts are planted around the edges of several windows at once:
+
+    CHANNEL_SETS, hull            named window sets -- edges on, one past and at the end of a LONG chunk, nested, gapped,
+                                  empty, deepest first -- and the one window the fused launch iterates as
+    channel_counts, channel_layout   the counts either side of every edge, chunk end and stage start, and their lanes
+    fused_model                   per planted count its planes, whether the kernel may record it at once (direct) or
+                                  must measure it first, and the counters of the launch, restated from DESIGN.md 4.6
+
+tests/test_planted_channels_host.py shows them decisive on the oracle; tests/test_gpu_planted_channels.py feeds them to
+cb_draw_buddhabrot_channels.
+
 The second half of the module does the same for the plotted renders (projected with its steps, Julia, palette, depth,
 depth palette, frames, bounded) on THEIR restatement's functions -- plot.step, plot.point, plot.depth_of, plot.slice_of of
 tests/plot_reference.py and .c:
@@ -476,10 +487,12 @@ PROBE_WINDOWS = [(3000, 1000), (2999, 1007), (60000, 45000), (60007, 45011)]    
 
 def stage_plan(max_iter, min_iter):
     """plan_stages (draw_wave.hip) restated -> (long_start, tail_start): the first iteration of the LONG stage, and of an
-    orbit's last, shorter chunk.  For max_iter beyond the MID stage only (what the windows above are)."""
+    orbit's last, shorter chunk (max_iter where the LONG stage is whole chunks: no tail chunk).  (None, None): HEAD and
+    MID do all of it, there is no LONG stage -- max_iter lies inside them (a hull like (16, 0) of the channel sets)."""
     mid = 16 if min_iter <= HEAD_STEPS + MID_MIN else MID_MIN + (min_iter - HEAD_STEPS - MID_MIN) % CHUNK
     long_start = HEAD_STEPS + mid
-    assert max_iter > long_start
+    if max_iter <= long_start:
+        return None, None
     return long_start, max_iter - (max_iter - long_start) % CHUNK
 
 
@@ -529,6 +542,200 @@ def pixel_edge_cases(w, h, count=1233, max_iter=1234, min_iter=20, samples=24):
     canvases["fallback"] = [(box, [base] + pixel_edge_samples(box, w, samples, max_iter, min_iter))
                             for box in canvases["fallback"]]
     return base, canvases
+
+
+# ---- the cases both channel suites use ---------------------------------------------------------------------------------
+#
+# The fused multi-channel render (cb_draw_buddhabrot_channels): windows [(max_iter, min_iter)], plane j is
+# what a run of its own with window j adds.  tests/test_planted_channels_host.py shows on the oracle alone that the sets
+# and the planted counts below are decisive; tests/test_gpu_planted_channels.py feeds them to the kernel.  With kChunk = 60
+# and a hull min of 20 the LONG stage starts at 20 and its chunks at 20 + 60 i.
+
+CHANNEL_SETS = {
+    # every edge is a chunk's first index and there is no tail chunk: every accepted orbit is direct, none is measured
+    "edges_on_chunk_starts": [(140, 20), (620, 140), (2540, 620)],
+    # the chunk [140, 199] holds the edge 141; the tail chunk is one step long
+    "edges_one_past_a_start": [(141, 20), (621, 141), (2541, 621)],
+    # the edge is a chunk's last index, k_hi; the tail chunk is 59 steps long
+    "edges_on_a_chunk_s_last_index": [(199, 20), (679, 199), (2599, 679)],
+    "recipe_small": [(100, 20), (600, 100), (2500, 600)],                         # the colour recipe's shape at small depth
+    # an orbit is in 4, 2 or 1 planes; the first and the last window are identical, so a shallow orbit's passes go through
+    # every tag (with the outermost window twice, as first proposed, the counts would be 4, 3 and 2: never a single plane)
+    "nested_four": [(150, 20), (800, 20), (3000, 20), (150, 20)],
+    # the recipe's own order, deepest first, and two gaps: an orbit in a gap is measured and then counted too_fast
+    "recipe_deepest_first": [(60000, 45000), (8000, 1000), (500, 20)],
+    "gap_min_below_head": [(60, 5), (700, 300)],                                  # accepted in HEAD / MID: no chunk is known
+    "shallow": [(10, 0), (16, 5)],                                                # no LONG stage at all, min_iter 0
+    "empty_windows_among_others": [(500, 50), (100, 200), (300, 300)],            # planes 1 and 2 stay zero
+    # the probe path: long_start 40, the edge 1007 lies inside the chunk [1000, 1059], 2999 in the tail chunk
+    "hull_min_deep": [(3000, 1000), (2999, 1007)],
+}
+
+
+def hull(windows):
+    """(max_iter, min_iter) of the one run the fused launch iterates as (cb_draw_buddhabrot_channels): the largest max
+    and the smallest min of the windows, empty ones included."""
+    return max(m for m, _ in windows), min(c for _, c in windows)
+
+
+def chunk_of(k, long_start):
+    """(first, last) index of the 60-step LONG chunk that holds iteration k >= long_start."""
+    first = long_start + (k - long_start) // CHUNK * CHUNK
+    return first, first + CHUNK - 1
+
+
+def channel_counts(windows):
+    """The escape counts worth planting for a set of windows: two either side of every window's min and max; the first
+    and last index of the LONG chunk that holds each of these edges and of the chunks before and after it; the steps
+    either side of the LONG stage's start and of the tail chunk's; and of the hull's max.  From 1 (no grid point of the
+    rays has count 0) to the hull's max + 1."""
+    top, low = hull(windows)
+    long_start, tail_start = stage_plan(top, low)
+    counts = {top + k for k in (-1, 0, 1)}
+    for m, c in windows:
+        for edge in (m, c):
+            counts |= {edge + k for k in (-2, -1, 0, 1)}
+            if long_start is not None and edge >= long_start:
+                first, _ = chunk_of(edge, long_start)
+                for start in (first - CHUNK, first, first + CHUNK):
+                    if start >= long_start:
+                        counts |= {start, start + CHUNK - 1}
+    if long_start is not None:
+        counts |= {long_start + k for k in (-1, 0, 1)} | {tail_start + k for k in (-1, 0, 1)}
+    return sorted(n for n in counts if 1 <= n <= top + 1)
+
+
+_planted = {}
+
+
+def channel_samples(windows):
+    """[(count, (re, im))]: every count of channel_counts on both rays (found once per count and ray)."""
+    out = []
+    for n in channel_counts(windows):
+        for ray in ("cusp", "neck"):
+            if (n, ray) not in _planted:
+                _planted[n, ray] = with_escape_count(n, ray)
+            out.append((n, _planted[n, ray]))
+    return out
+
+
+def fused_model(windows, counts):
+    """What a fused launch does with samples of the given escape counts (None: a sample the shortcut rejects), by DESIGN.md
+    4.6 and the header's "Counters of a fused launch" -> {"samples": [(planes, how)], "planes": per plane the number of
+    orbits recorded into it, rejected, never_escaped, too_fast, recorded, replay_steps}.
+
+    planes: the tuple of the j with min_j <= k < max_j.  how: None for a sample the hull run does not accept (rejected,
+    k >= hull max: never escaped, k < hull min: too fast); else "direct" or "measured".  An accepted orbit is DIRECT when
+    the LONG stage knows the 60-step chunk it escaped in -- a full chunk [long_start + 60 i, + 60) that ends at or before
+    tail_start: not an escape in HEAD or MID, not one in the last, shorter chunk --, no window begins or ends inside that
+    chunk (an edge e, the min or max of any window, an empty one too, with first < e <= last: an edge ON the first index
+    leaves the whole chunk on one side), and it lands in at least one window.  Every other accepted orbit is MEASURED:
+    replayed once without recording, for its exact index.  recorded: accepted and in some window; too_fast: escaped and in
+    none; replay_steps: k + 1 steps per pass, one pass per plane and one more where measured."""
+    top, low = hull(windows)
+    long_start, tail_start = stage_plan(top, low)
+    edges = {e for w in windows for e in w}
+    out = {"samples": [], "planes": [0] * len(windows), "rejected": 0, "never_escaped": 0, "too_fast": 0, "recorded": 0,
+           "replay_steps": 0}
+    for k in counts:
+        if k is None:
+            out["rejected"] += 1
+            out["samples"].append(((), None))
+            continue
+        if k >= top:
+            out["never_escaped"] += 1
+            out["samples"].append(((), None))
+            continue
+        planes = tuple(j for j, (m, c) in enumerate(windows) if c <= k < m)
+        out["recorded" if planes else "too_fast"] += 1
+        if k < low:
+            assert not planes
+            out["samples"].append(((), None))
+            continue
+        measured = True
+        if long_start is not None and long_start <= k < tail_start:
+            first, last = chunk_of(k, long_start)
+            measured = any(first < e <= last for e in edges) or not planes
+        for j in planes:
+            out["planes"][j] += 1
+        out["replay_steps"] += (k + 1) * (len(planes) + (1 if measured else 0))
+        out["samples"].append((planes, "measured" if measured else "direct"))
+    return out
+
+
+def recorded_by_windows(windows, per_window, of_hull):
+    """The fused run's `recorded` from the oracle's separate runs: per_window[j] and of_hull are the `recorded` of window j
+    and of the hull window.  Windows that share no index (adjacent, gapped, empty): the sum; windows whose union is the
+    whole hull (nested in the outermost, or overlapping end to end): the hull's, which is the outermost window's where
+    there is one.  Where both hold they must agree; a set for which neither holds has no rule here."""
+    top, low = hull(windows)
+    spans = sorted((c, m) for m, c in windows if c < m)
+    disjoint = all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+    reach = low
+    for c, m in spans:
+        reach = max(reach, m) if c <= reach else reach
+    covers = bool(spans) and spans[0][0] == low and reach == top
+    assert disjoint or covers, windows
+    if disjoint and covers:
+        assert sum(per_window) == of_hull, (windows, per_window, of_hull)
+    return sum(per_window) if disjoint else of_hull
+
+
+_counts = {}
+
+
+def counts_of(points, cap, ship=False):
+    """The escape count of every point as fused_model takes it: None where the shortcut rejects the sample (never, under
+    the Burning Ship step, which has no shortcut), else the oracle's IterateMandelbrot count up to `cap` (of its
+    RENDER_BURNING_SHIP build where asked).  Once per point."""
+    out = []
+    oracle.lib.orc_set_burning_ship(1 if ship else 0)
+    try:
+        for p in points:
+            key = (p, cap, ship)
+            if key not in _counts:
+                _counts[key] = None if (not ship and rejected(*p)) else escape_count(p[0], p[1], cap)
+            out.append(_counts[key])
+    finally:
+        oracle.lib.orc_set_burning_ship(0)
+    return out
+
+
+def channel_layout(windows, threads):
+    """One planted first sample per subsequence, every sample of channel_samples among them and the three fates in
+    balance -> (samples, points).  Most planted counts are recorded ones, so every fourth lane cycles through the samples
+    that never escape (counts of the hull's max and beyond), the lane after it through those that escape in no window
+    (where the set has any), and the other two through all samples in turn."""
+    samples = channel_samples(windows)
+    top, _ = hull(windows)
+    model = fused_model(windows, [n for n, _ in samples])
+    never = [c for n, c in samples if n >= top]
+    nowhere = [c for (n, c), (planes, _) in zip(samples, model["samples"]) if n < top and not planes]
+    everyone = [c for _, c in samples]
+    points, turn = [], 0
+    for k in range(threads):
+        if k % 4 == 0:
+            points.append(never[(k // 4) % len(never)])
+        elif k % 4 == 1 and nowhere:
+            points.append(nowhere[(k // 4) % len(nowhere)])
+        else:
+            points.append(everyone[turn % len(everyone)])
+            turn += 1
+    assert set(everyone) <= set(points), "more planted samples than lanes for them"
+    return samples, points
+
+
+def occupancy_counts(windows):
+    """The planted counts of the occupancy layouts: for every kind of accepted orbit that channel_counts has -- its planes
+    and whether it is direct or measured -- the deepest count of that kind, and the hull's max (an orbit that never
+    escapes)."""
+    counts = channel_counts(windows)
+    model = fused_model(windows, counts)
+    deepest = {}
+    for n, (planes, how) in zip(counts, model["samples"]):
+        if how is not None:
+            deepest[planes, how] = n
+    return sorted(set(deepest.values()) | {hull(windows)[0]})
 
 
 # ---- the plotted renders: plants found on the restatement's own functions (tests/plot_reference.py, .c) ---------------------

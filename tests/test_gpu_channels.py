@@ -4,7 +4,8 @@ once per channel): plane j of one fused run must equal a separate run with windo
 import numpy as np
 import pytest
 
-from device_launches import SQUARE as BOX, Launches
+import planted_samples as P
+from device_launches import SQUARE as BOX, Launches, omp_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -17,6 +18,22 @@ def _fused(cb, w, h, windows, t, passes, mode, box=BOX, per_launch=1):
     seq.launches(cb.draw_buddhabrot_channels, [spt] * (passes // per_launch), drain="launch" if mode == "carry" else None,
                  windows=windows)
     return seq.read()[:2]
+
+
+def assert_fused_counters(cnt, windows, singles, of_hull):
+    """The counters of a fused run against the oracle's separate runs (singles: the counters of every window's run;
+    of_hull: those of a run of the hull window, largest max and smallest min): samples, rejected, never_escaped and
+    iterate_steps are the hull run's; every accepted orbit is recorded or too fast; recorded is the windows' sum where
+    they share no index and the outermost window's where they are nested (P.recorded_by_windows); replay_steps is at least
+    one pass per plane and at most a measuring pass more for every accepted orbit; increments counts all planes."""
+    assert cnt["status"] == 0
+    for k in ("samples", "rejected", "never_escaped", "iterate_steps"):
+        assert cnt[k] == of_hull[k], (k, cnt[k], of_hull[k])
+    assert cnt["recorded"] + cnt["too_fast"] == of_hull["samples"] - of_hull["rejected"] - of_hull["never_escaped"]
+    assert cnt["recorded"] == P.recorded_by_windows(windows, [c["recorded"] for c in singles], of_hull["recorded"])
+    low = sum(c["replay_steps"] for c in singles)
+    assert low <= cnt["replay_steps"] <= low + of_hull["replay_steps"], (low, cnt["replay_steps"], of_hull["replay_steps"])
+    assert cnt["increments"] == sum(c["increments"] for c in singles)
 
 
 WINDOWS = [
@@ -34,12 +51,15 @@ def test_each_plane_equals_a_separate_run(cb, oracle, windows, mode):
     planes, cnt = _fused(cb, w, h, windows, t, passes, mode, per_launch=2 if mode == "carry" else 1)
     assert cnt["status"] == 0
     assert cnt["samples"] == t * 50 * passes
-    total = 0
+    total, singles = 0, []
     for j, (m, c) in enumerate(windows):
         ref, rc = oracle.render(w, h, m, c, t, passes)
         assert np.array_equal(planes[j], ref), "channel %d (max %d, min %d)" % (j, m, c)
         total += rc["increments"]
+        singles.append(rc)
     assert int(planes.sum()) == total
+    _, of_hull = oracle.render(w, h, *P.hull(windows), t, passes, omp_threads=omp_threads())
+    assert_fused_counters(cnt, windows, singles, of_hull)
 
 
 @pytest.mark.parametrize("chunked", ["1", "0"])
@@ -86,10 +106,15 @@ def test_renderer_with_channels_pipelines_launches_and_tone_maps_each_plane(cb, 
         r.render_passes(passes)
         body, mx, _ = r.grayscale_image(2.2, plane=1)
         planes = r.read_histogram()
+        cnt = r.read_counters().as_dict()
     assert planes.shape == (2, h, w)
+    singles = []
     for j, (m, c) in enumerate(windows):
-        ref, _ = oracle.render(w, h, m, c, t, passes, omp_threads=0)
+        ref, rc = oracle.render(w, h, m, c, t, passes, omp_threads=0)
         assert np.array_equal(planes[j], ref)
+        singles.append(rc)
+    _, of_hull = oracle.render(w, h, *P.hull(windows), t, passes, omp_threads=0)
+    assert_fused_counters(cnt, windows, singles, of_hull)
     gray, mx_ref, _ = oracle.set_grayscale_pixels(planes[1], 2.2)
     assert mx == mx_ref and np.array_equal(body.astype(np.uint16), gray)
 

@@ -53,27 +53,30 @@ def reference(oracle, points, w, h, box, max_iter, min_iter, launches, ship=Fals
     return _references[key]
 
 
-def stream_capacity(cb, dims, nbytes):
-    layout = cb.debug_scatter_layout(dims, THREADS, 4096, nbytes)
+def stream_capacity(cb, dims, nbytes, n_channels=0):
+    layout = cb.debug_scatter_layout(dims, THREADS, 4096, nbytes, n_channels)
     return layout.cap * layout.n_waves if layout.enabled else 0
 
 
-def workspace_bytes(cb, dims, kind, increments):
+def workspace_bytes(cb, dims, kind, increments, n_channels=0):
     """"roomy": a stream that holds every increment of the run twice over; "small": the smallest the wide kernel still
-    takes (64 lanes x 32 steps per stream region), a fraction of the run's increments, so that the bursts add directly."""
+    takes (64 lanes x 32 steps per stream region), a fraction of the run's increments, so that the bursts add directly.
+    n_channels: of a fused launch (tests/test_gpu_planted_channels.py), whose stream words carry a plane's index."""
+    planes = max(n_channels, 1)
     if kind == "roomy":
         samples = 50
-        while stream_capacity(cb, dims, cb.scatter_workspace_bytes(dims, THREADS, samples)) < 2 * increments + 65536:
+        while stream_capacity(cb, dims, cb.scatter_workspace_bytes(dims, THREADS, samples, planes),
+                              n_channels) < 2 * increments + 65536:
             samples *= 2
-        return cb.scatter_workspace_bytes(dims, THREADS, samples)
-    nbytes = cb.scatter_workspace_bytes(dims, THREADS, 1)
+        return cb.scatter_workspace_bytes(dims, THREADS, samples, planes)
+    nbytes = cb.scatter_workspace_bytes(dims, THREADS, 1, planes)
     while True:
         less = nbytes - 8192
-        layout = cb.debug_scatter_layout(dims, THREADS, 4096, less) if less > 0 else None
+        layout = cb.debug_scatter_layout(dims, THREADS, 4096, less, n_channels) if less > 0 else None
         if layout is None or not layout.enabled or layout.cap < 64 * 32:
             break
         nbytes = less
-    assert 4 * stream_capacity(cb, dims, nbytes) < increments, "the small stream would hold the run"
+    assert 4 * stream_capacity(cb, dims, nbytes, n_channels) < increments, "the small stream would hold the run"
     return nbytes
 
 

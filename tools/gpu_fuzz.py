@@ -585,10 +585,15 @@ def main():
                 got, gc = render(t, cb.CB_KERNEL_DEFAULT, fused=True)
                 singles = [render(t, cb.CB_KERNEL_SIMPLE, window=w) for w in t["windows"]]
                 want = np.concatenate([h for h, _ in singles])
-                wc = dict(gc)                      # per-window counters do not add up to the fused run's ...
-                wc["samples"] = singles[0][1]["samples"]
-                wc["rejected"] = singles[0][1]["rejected"]
-                wc["increments"] = sum(c["increments"] for _, c in singles)   # ... except these
+                # per-window counters do not add up to the fused run's: what one run with the largest max and the smallest
+                # min counts is taken from a lock-step run of that window, the increments from the windows' runs, and
+                # too_fast, recorded and replay_steps stay the fused run's own
+                hull = (max(m for m, _ in t["windows"]), min(c for _, c in t["windows"]))
+                of_hull = render(t, cb.CB_KERNEL_SIMPLE, window=hull)[1]
+                wc = dict(gc)
+                for k in ("samples", "rejected", "never_escaped", "iterate_steps"):
+                    wc[k] = of_hull[k]
+                wc["increments"] = sum(c["increments"] for _, c in singles)
             else:
                 want, wc = render(t, cb.CB_KERNEL_SIMPLE)
                 got, gc = render(t, cb.CB_KERNEL_DEFAULT)
